@@ -2,9 +2,14 @@
 """
 bench.py -- decode attention hot path (Hydragen decomposed shared-prefix attention) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up (inputs, the placement of the unique K|V cache, 3 eager warm-up calls per suffix length), runs
+the W warm-up steps and the K timed steps, writes the last timed step's output with --dump-outputs, and prints the
+JSON line: the headline and what the timed region's own events give (per-kernel durations, rooflines).  --full runs
+the legs below as well; they take runs of their own.
 
 Workload (BASELINE.json configs[1], "C2"): bf16, batch 1024, one shared prefix of 2048 tokens, Llama-2-7B head
 config (32 q heads = 32 kv heads, head_dim 128), unique suffix anywhere in 1..128 tokens.
@@ -22,9 +27,10 @@ N > 1: tensor-parallel head sharding exactly as /root/reference/hydragen/tp.py:9
 Hkv/N kv heads per rank, batch replicated) with the per-layer all-reduce(sum) of the [B, 1, hidden] attention
 block output (tp.py:108-112) on RCCL, timed with its own events.  Total work is fixed -> "strong" scaling.
 
-Extra objects on the JSON line (rank 0):
+Extra objects on the JSON line (rank 0), all but `roofline` with --full only:
   roofline            the kernel that took most of the timed region (by its events): algorithmic bytes or flops /
                       mean launch duration against the gfx950 peak; the other kernel in `roofline_other`
+  trials              the K-step schedule repeated (--trials) without events, and once in the other step form
   reference_protocol  the reference's own timing protocol (hydragen/benchmark_utils.py:82-170,
                       scripts/microbenchmark.py:24-47): operator captured in a HIP graph, replays timed one by one
                       with a 512 MB cache flush in between, mean / std / rstd per sweep point s = 16..128
@@ -113,7 +119,26 @@ def parse():
     ap.add_argument("--no-xgmi", action="store_true", help="N > 1: skip the direct xGMI all-reduce (hyd_allreduce_sum) leg")
     ap.add_argument("--no-graph-collective", action="store_true",
                     help="N > 1: skip the HIP-graph capture of (attention + all-reduce), llama.py:849-854")
-    return apply_workload(ap.parse_args())
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: repeats (--trials) and the other step form, HBM bytes counted by rocprofv3 "
+                         "child passes, the reference protocol with the no-sharing baseline, accuracy, the paper sweep, the model decode leg, "
+                         "the CPU baseline, N > 1: the xGMI all-reduce and the in-graph collective (pre-flight stages and legs); the --no-* "
+                         "flags switch single legs off again.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (the attention output a caller receives) as "
+                         "DIR/attention_out.npy in float32 (N > 1: attention_out_rank<r>.npy per rank); above DUMP_BUDGET bytes a fixed, "
+                         "seeded sample of the batch rows")
+    return plain_or_full(apply_workload(ap.parse_args()))
+
+
+def plain_or_full(args):
+    """Without --full every leg outside the headline is off (the flags are the ones that switch a single leg off)."""
+    if not args.full:
+        args.trials = 0
+        for leg in ("no_cpu_baseline", "no_nosharing", "no_protocol", "no_model", "no_accuracy", "no_paper_sweep", "no_live_traffic",
+                    "no_xgmi", "no_graph_collective"):
+            setattr(args, leg, True)
+    return args
 
 
 def apply_workload(args):
@@ -137,6 +162,26 @@ def launch_schedule(steps: int, warmup: int, trials: int, smax: int) -> list[int
     steps, the timed steps, the repeats."""
     sched, warm = suffix_schedule(steps, smax), suffix_schedule(max(warmup, 1), smax)[:warmup]
     return [s for s in sorted(set(sched + suffix_schedule(max(warmup, 1), smax))) for _ in range(3)] + warm + sched * (1 + trials)
+
+
+DUMP_BUDGET = 48 << 20  # bytes that --dump-outputs writes at most, all ranks together
+
+
+def dump_outputs(out_dir: Path, out, rank: int, world: int) -> dict:
+    """--dump-outputs: what the last timed step computed, the [batch, 1, q heads, dim] attention output, as float32 in
+    out_dir/attention_out.npy (N > 1: attention_out_rank<r>.npy, this rank's heads).  An output larger than its share of
+    DUMP_BUDGET keeps the batch rows of a fixed sample (numpy default_rng(0), sorted): the same rows in every run."""
+    import numpy as np
+
+    B = out.shape[0]
+    keep = min(B, DUMP_BUDGET // world // (out[0].numel() * 4))
+    rows = np.arange(B) if keep == B else np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+    arr = out.float().cpu().numpy()[rows]
+    name = "attention_out" if world == 1 else f"attention_out_rank{rank}"
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / f"{name}.npy", arr)
+    return {"dir": str(out_dir), "files": {name: list(arr.shape)}, "dtype": "float32",
+            "batch_rows": "all" if keep == B else f"{keep} of {B}: numpy default_rng(0) sample, sorted"}
 
 
 def describe_schedule(sched: list[int]) -> str:
@@ -210,6 +255,10 @@ class Ops:
         self._call(s, self.PH[3], main.cuda_stream)
         main.wait_stream(self.side)
         self._call(s, self.PH[4], main.cuda_stream)
+
+    def warm(self, s):
+        """The eager calls of the one-call form that `graph(s)` makes before its capture, without the capture."""
+        _warm_up(lambda: self.fused(s, torch.cuda.current_stream().cuda_stream))
 
     def graph(self, s, two_stream=None):
         """The operator at suffix length s as a captured HIP graph (hydragen/benchmark_utils.py:140-170 captures the
@@ -286,8 +335,11 @@ def main():
     warm_sched = suffix_schedule(max(args.warmup, 1), S)
     sweep = [s for s in SWEEP + (160, 192, 224, 256) if s <= S]
     ops = Ops(q, k, v, sk, sv, sched + warm_sched + sweep, two_stream=args.two_stream)
-    for s_ in sorted(set(sched + warm_sched)):  # capture outside the timed region
-        ops.graph(s_)
+    for s_ in sorted(set(sched + warm_sched)):  # capture outside the timed region (eager steps of a plain run: its warm-up calls only)
+        if args.full or args.step_form == "graph" or args.two_stream:
+            ops.graph(s_)
+        else:
+            ops.warm(s_)
     # stand-in for the row-parallel o_proj partial output that tp.py:108-112 all-reduces
     ar_buf = torch.randn(B, 1, hidden, device=dev, dtype=dt) if world > 1 else None
     ar_host = ar_buf.float().cpu() if (world > 1 and backend != "nccl") else None
@@ -354,6 +406,7 @@ def main():
         t = torch.tensor([elapsed], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = dump_outputs(Path(args.dump_outputs), ops.out, rank, world) if args.dump_outputs else None
 
     # ---- spread: the same K-step schedule again, `--trials` times, without events (the headline stays trial 0 above) ----
     trial_us = []
@@ -478,14 +531,17 @@ def main():
                    "steps": ev_idx, "suffix_lens": sched_ev, "suffix_len_mean": sum(sched_ev) / n_ev,
                    "why": "a kernel's own duration needs the two kernels in order with an event between them; these steps run the "
                           "operator eagerly in that form, the per-kernel rooflines are theirs"},
-        "trials": {"headline": "trial 0 = the timed region above (HIP events on one step in five)", "trial0_us_per_step": elapsed / args.steps * 1e6,
-                   "repeat_us_per_step": trial_us, "repeat_note": "same schedule, every step in the headline's step form, no events, each bracketed like the headline",
-                   "other_form": other_form, "other_form_us_per_step": other_us,
-                   **({"repeat_mean_us": sum(trial_us) / len(trial_us), "repeat_min_us": min(trial_us), "repeat_max_us": max(trial_us)} if trial_us else {})},
         "suffix_frac_by_suffix_len": buckets,
         "roofline": suffix_roof if dominant_is_suffix else prefix_roof,
         "roofline_other": prefix_roof if dominant_is_suffix else suffix_roof,
     }
+    if args.full:
+        res["trials"] = {"headline": "trial 0 = the timed region above (HIP events on one step in five)", "trial0_us_per_step": elapsed / args.steps * 1e6,
+                         "repeat_us_per_step": trial_us, "repeat_note": "same schedule, every step in the headline's step form, no events, each bracketed like the headline",
+                         "other_form": other_form, "other_form_us_per_step": other_us,
+                         **({"repeat_mean_us": sum(trial_us) / len(trial_us), "repeat_min_us": min(trial_us), "repeat_max_us": max(trial_us)} if trial_us else {})}
+    if dumped is not None:
+        res["outputs"] = dumped
     if world > 1:
         res["preflight"] = pre
         ar_ms = [ev[2].elapsed_time(ev[3]) for ev in events]
@@ -530,7 +586,7 @@ def main():
         if args.detail_out:
             global DETAIL_FILE
             DETAIL_FILE = Path(args.detail_out).resolve()
-        print(json.dumps(compact_line(res)))
+        print(json.dumps(compact_line(res, write_detail=args.full or bool(args.detail_out))))
         sys.stdout.flush()
     if world > 1:
         dist.barrier()
@@ -580,19 +636,20 @@ def _round_floats(o):
     return _sig(o)
 
 
-def compact_line(res: dict) -> dict:
+def compact_line(res: dict, write_detail: bool = True) -> dict:
     """The ONE line the driver records must fit its 8 KB tail.  The full result (per-point std / rstd / n of the reference
     protocol, the paper sweep's rows as objects, the prose that says how each figure was taken) goes to
-    the detail file (DETAIL_FILE / --detail-out); the line keeps every figure's MEAN, five significant digits, and short notes."""
-    try:
-        DETAIL_FILE.parent.mkdir(parents=True, exist_ok=True)
-        DETAIL_FILE.write_text(json.dumps(res, indent=1))
-        detail = str(DETAIL_FILE.relative_to(REPO)) if DETAIL_FILE.is_relative_to(REPO) else str(DETAIL_FILE)
-    except OSError as ex:  # a read-only tree must not cost the line
-        detail = f"not written ({type(ex).__name__})"
+    the detail file (DETAIL_FILE / --detail-out; a plain run writes none unless --detail-out is given); the line keeps every
+    figure's MEAN, five significant digits, and short notes."""
     keep = ("value", "ms_per_step", "attn_us_per_step")  # the contract's own figures stay as measured
     line = {k: (v if k in keep else _round_floats(v)) for k, v in res.items()}
-    line["detail_file"] = detail
+    if write_detail:
+        try:
+            DETAIL_FILE.parent.mkdir(parents=True, exist_ok=True)
+            DETAIL_FILE.write_text(json.dumps(res, indent=1))
+            line["detail_file"] = str(DETAIL_FILE.relative_to(REPO)) if DETAIL_FILE.is_relative_to(REPO) else str(DETAIL_FILE)
+        except OSError as ex:  # a read-only tree must not cost the line
+            line["detail_file"] = f"not written ({type(ex).__name__})"
     rp = line.get("reference_protocol")
     if isinstance(rp, dict) and "by_suffix_len" in rp:
         cols = sorted({c for v in rp["by_suffix_len"].values() for c in v if isinstance(v[c], dict)})
@@ -899,8 +956,8 @@ def _guarded(fn, seconds, res, rank, key="graph_collective"):
         timer.cancel()
 
 
-def _capture(fn):
-    """HIP-graph capture after eager warm-ups on a side stream (hydragen/benchmark_utils.py:140-170)."""
+def _warm_up(fn):
+    """Three eager calls on a side stream (hydragen/benchmark_utils.py:140-170 warms up so before it captures)."""
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
@@ -908,6 +965,11 @@ def _capture(fn):
             fn()
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
+
+
+def _capture(fn):
+    """HIP-graph capture after eager warm-ups on a side stream (hydragen/benchmark_utils.py:140-170)."""
+    _warm_up(fn)
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
         fn()

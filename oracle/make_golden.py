@@ -42,7 +42,7 @@ sys.path.insert(0, str(REPO))
 sys.path.insert(0, str(REF))
 
 from oracle import hydragen_oracle as O  # noqa: E402
-from tests.cases import golden_case_list, make_case  # noqa: E402
+from tests.cases import golden_case_list, make_case, pack_combine_lse  # noqa: E402
 
 
 # --------------------------------------------------------------------------
@@ -212,7 +212,7 @@ def main():
     assert np.abs(r3 - O.combine_lse(list(o), list(l))).max() < 1e-5
     comb["n3_outs"], comb["n3_lses"], comb["n3_ref"] = o, l, r3
     comb["count"] = np.asarray(idx)
-    np.savez_compressed(outdir / "combine_lse.npz", **comb)
+    np.savez_compressed(outdir / "combine_lse.npz", **pack_combine_lse(comb))  # tests.cases.load_combine_lse unpacks it
 
     for r in report:
         print("%-28s %-40s max|ref-oracle|=%.2e mean rdiff=%.2e" % r)

@@ -11,7 +11,11 @@ outputs.
 
 from __future__ import annotations
 
+from pathlib import Path
+
 import numpy as np
+
+GOLDEN = Path(__file__).resolve().parent / "golden"
 
 # tests/test_attention.py:26-32
 REFERENCE_SIZE_SPECS = [
@@ -113,3 +117,33 @@ def golden_case_list():
     cases.append(("two_level_bf16", dict(sizes=[[48], [24] * 4, [7] * 8], qheads=8, kvheads=2, dim=128,
                                          dtype="bf16", seed=91, force_seq_lens=True)))
     return cases
+
+
+COMBINE_LSE_KINDS = ("o1", "o2", "l1", "l2", "ref")
+
+
+def pack_combine_lse(grid: dict) -> dict:
+    """The combine_lse grid fixture as a few flat arrays (one per kind + the [bs, seq, heads, dim] of every case) instead of
+    one array per case: the same values, without the per-entry overhead of a 540-entry archive."""
+    n = int(grid["count"])
+    packed = {k: np.concatenate([grid[f"{k}_{i}"].ravel() for i in range(n)]) for k in COMBINE_LSE_KINDS}
+    packed["shape"] = np.asarray([grid[f"o1_{i}"].shape for i in range(n)], dtype=np.int64)
+    for k in ("count", "n3_outs", "n3_lses", "n3_ref"):
+        packed[k] = grid[k]
+    return packed
+
+
+def load_combine_lse() -> dict:
+    """tests/golden/combine_lse.npz unpacked to {o1_i, o2_i, l1_i, l2_i, ref_i, n3_outs, n3_lses, n3_ref, count}."""
+    z = np.load(GOLDEN / "combine_lse.npz")
+    shapes = [tuple(int(x) for x in s) for s in z["shape"]]
+    grid = {k: z[k] for k in ("count", "n3_outs", "n3_lses", "n3_ref")}
+    for k in COMBINE_LSE_KINDS:
+        flat, at = z[k], 0
+        for i, s in enumerate(shapes):
+            s = s if k in ("o1", "o2", "ref") else s[:3]
+            n = int(np.prod(s))
+            grid[f"{k}_{i}"] = flat[at:at + n].reshape(s)
+            at += n
+        assert at == flat.size, k
+    return grid

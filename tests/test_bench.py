@@ -46,7 +46,7 @@ def _run_bench(args, extra_env=None, timeout=600):
 
 @pytest.mark.gpu
 def test_bench_two_ranks_without_a_launcher():
-    res = _run_bench(["--gpus", "2", "--steps", "8", "--warmup", "2", "--trials", "1", "--cpu-seconds", "2", "--no-xgmi"],
+    res = _run_bench(["--full", "--gpus", "2", "--steps", "8", "--warmup", "2", "--trials", "1", "--cpu-seconds", "2", "--no-xgmi"],
                      {"HYD_BENCH_BACKEND": "gloo", "HYD_BENCH_ONE_DEVICE": "1"})
     assert res["n_gpus"] == 2 and res["steps"] == 8 and res["scaling"] == "strong"
     for key in ("roofline", "roofline_other", "cpu_baseline", "allreduce_us", "rccl_ranks", "trials", "accuracy"):
@@ -64,7 +64,7 @@ def test_bench_preflight_runs_every_stage_on_two_ranks():
     env = dict(os.environ, HYD_BENCH_BACKEND="gloo", HYD_BENCH_ONE_DEVICE="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2", "--trials", "0",
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--full", "--gpus", "2", "--steps", "8", "--warmup", "2", "--trials", "0",
                         "--no-cpu-baseline", "--no-accuracy"], capture_output=True, text=True, timeout=600, env=env, cwd=str(REPO))
     assert r.returncode == 0, r.stderr[-3000:]
     stages = [json.loads(ln[len("[preflight] "):]) for ln in r.stdout.splitlines() if ln.startswith("[preflight] ")]
@@ -84,7 +84,7 @@ def test_bench_preflight_names_the_failing_stage(stage, rc):
     env = dict(os.environ, HYD_BENCH_BACKEND="gloo", HYD_BENCH_ONE_DEVICE="1", HYD_BENCH_FAIL_STAGE=stage)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2", "--trials", "0",
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--full", "--gpus", "2", "--steps", "8", "--warmup", "2", "--trials", "0",
                         "--no-cpu-baseline", "--no-accuracy"], capture_output=True, text=True, timeout=600, env=env, cwd=str(REPO))
     lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
     if rc == 3:
@@ -100,7 +100,7 @@ def test_bench_preflight_names_the_failing_stage(stage, rc):
 def test_bench_c5_workload_on_two_ranks():
     """BASELINE config 5 as north_star states it (batch 2048, prefix 4096, 64 q / 8 kv heads, suffix 1..256), sharded over
     heads on two ranks (32 q / 4 kv heads each, tp.py:90-124) with the 32 MiB [2048, 1, 8192] all-reduce per step."""
-    res = _run_bench(["--workload", "c5", "--gpus", "2", "--steps", "8", "--warmup", "2", "--trials", "1", "--cpu-seconds", "2",
+    res = _run_bench(["--full", "--workload", "c5", "--gpus", "2", "--steps", "8", "--warmup", "2", "--trials", "1", "--cpu-seconds", "2",
                       "--no-xgmi", "--no-accuracy"], {"HYD_BENCH_BACKEND": "gloo", "HYD_BENCH_ONE_DEVICE": "1"}, timeout=900)
     cfg = res["config"]
     assert res["n_gpus"] == 2 and res["rccl_ranks"] == 2 and res["value"] > 0
@@ -122,7 +122,7 @@ def test_bench_c5_workload_on_eight_ranks():
     env = dict(os.environ, HYD_BENCH_BACKEND="gloo", HYD_BENCH_ONE_DEVICE="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--workload", "c5", "--gpus", "8", "--batch", "256", "--steps", "8",
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--full", "--workload", "c5", "--gpus", "8", "--batch", "256", "--steps", "8",
                         "--warmup", "2", "--trials", "0", "--no-cpu-baseline", "--no-accuracy"],
                        capture_output=True, text=True, timeout=1200, env=env, cwd=str(REPO))
     assert r.returncode == 0, r.stderr[-3000:]
@@ -149,6 +149,63 @@ def test_workload_presets_and_overrides(monkeypatch):
     assert (a.batch, a.prefix, a.max_suffix, a.qheads, a.kvheads) == (512, 4096, 256, 64, 8)
 
 
+def test_plain_run_switches_every_other_leg_off(monkeypatch):
+    """Without --full a run only sets up, warms up, times the steps (and dumps the outputs when asked); --full brings back
+    every other leg with the defaults it had, and a --no-* flag still switches one of them off."""
+    import bench
+
+    legs = ("no_cpu_baseline", "no_nosharing", "no_protocol", "no_model", "no_accuracy", "no_paper_sweep", "no_live_traffic",
+            "no_xgmi", "no_graph_collective")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    a = bench.parse()
+    assert not a.full and a.trials == 0 and a.dump_outputs == "" and a.steps == 20 and a.warmup == 5
+    assert all(getattr(a, leg) for leg in legs)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-model"])
+    a = bench.parse()
+    assert a.full and a.trials == 3 and a.no_model and not any(getattr(a, leg) for leg in legs if leg != "no_model")
+
+
+def test_dump_outputs_writes_float32_and_samples_fixed_rows(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+
+    import bench
+
+    out = torch.randn(64, 1, 4, 8, generator=torch.Generator().manual_seed(0)).to(torch.bfloat16)
+    rec = bench.dump_outputs(tmp_path / "a", out, 0, 1)
+    got = np.load(tmp_path / "a" / "attention_out.npy")
+    assert rec["batch_rows"] == "all" and got.dtype == np.float32 and np.array_equal(got, out.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 10 * 4 * 8 * 4 * 2)  # room for 10 rows per rank at N = 2
+    rec = bench.dump_outputs(tmp_path / "b", out, 1, 2)
+    first = np.load(tmp_path / "b" / "attention_out_rank1.npy")
+    assert rec["files"] == {"attention_out_rank1": [10, 1, 4, 8]} and first.dtype == np.float32
+    bench.dump_outputs(tmp_path / "c", out, 1, 2)
+    again = np.load(tmp_path / "c" / "attention_out_rank1.npy")
+    rows = [i for i in range(64) if any(np.array_equal(r, out[i].float().numpy()) for r in first)]
+    assert np.array_equal(first, again) and len(rows) == 10 and np.array_equal(first, out[rows].float().numpy())
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_the_same_outputs_twice(tmp_path):
+    """The line of a plain run: the headline and what its own events give, nothing that takes runs of its own; --steps sets
+    the timed steps and ms_per_step is their time; --dump-outputs writes the last timed step's output, the same in two runs."""
+    shape = ["--batch", "128", "--prefix", "512", "--steps", "12", "--warmup", "3"]
+    res = [_run_bench(["--gpus", "1", *shape, "--dump-outputs", str(tmp_path / f"run{i}")]) for i in range(2)]
+    for r in res:
+        assert r["metric"] == "decode_attention_tokens_per_sec" and r["unit"] == "tokens/s" and r["higher_is_better"] is True
+        assert r["dtype"] == "bf16" and r["steps"] == 12 and r["warmup"] == 3 and r["value"] > 0
+        assert abs(r["value"] * r["ms_per_step"] * 1e-3 / 128 - 1) < 1e-9  # value = batch * steps / (steps * ms_per_step)
+        assert r["events"]["steps_with_events"] + r["step_forms"]["steps_in_that_form"] == 12
+        for key in ("trials", "reference_protocol", "accuracy", "paper_sweep", "model_decode", "cpu_baseline", "detail_file"):
+            assert key not in r, key
+        assert r["outputs"]["files"] == {"attention_out": [128, 1, 32, 128]} and r["outputs"]["batch_rows"] == "all"
+    import numpy as np
+
+    a, b = (np.load(tmp_path / f"run{i}" / "attention_out.npy") for i in range(2))
+    assert a.dtype == np.float32 and np.isfinite(a).all() and np.abs(a).max() > 0
+    assert np.array_equal(a, b)
+
+
 def test_region_watchdog_prints_an_error_line_and_exits():
     """A rank whose timed region never finishes (a peer that never arrives) leaves with an error line and a non-zero
     exit code instead of hanging the job."""
@@ -164,7 +221,7 @@ def test_region_watchdog_prints_an_error_line_and_exits():
 
 @pytest.mark.gpu
 def test_bench_single_gpu_line_is_complete():
-    res = _run_bench(["--gpus", "1", "--steps", "8", "--warmup", "2", "--trials", "2", "--cpu-seconds", "2", "--no-model",
+    res = _run_bench(["--full", "--gpus", "1", "--steps", "8", "--warmup", "2", "--trials", "2", "--cpu-seconds", "2", "--no-model",
                       "--no-protocol"])
     assert res["n_gpus"] == 1 and res["metric"] == "decode_attention_tokens_per_sec" and res["unit"] == "tokens/s"
     assert res["vs_baseline"] is None and res["dtype"] == "bf16" and res["data"] == "synthetic"

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from oracle import hydragen_oracle as O
-from tests.cases import golden_case_list, make_case
+from tests.cases import golden_case_list, load_combine_lse, make_case
 from tests.conftest import load_golden
 
 CASES = golden_case_list()
@@ -111,7 +111,7 @@ def test_c_oracle_decode_and_torch_port(name, kw, oracle_so):
 
 
 def test_combine_fixture_vs_oracle():
-    z = np.load("tests/golden/combine_lse.npz")
+    z = load_combine_lse()
     for i in range(int(z["count"])):
         r = O.combine_lse([z[f"o1_{i}"], z[f"o2_{i}"]], [z[f"l1_{i}"], z[f"l2_{i}"]])
         assert np.abs(r - z[f"ref_{i}"]).max() < 1e-6

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.cases import golden_case_list, make_case
+from tests.cases import golden_case_list, load_combine_lse, make_case
 from tests.conftest import load_golden
 from tests.gpu_util import assert_close, atol, case_to_device, dev
 
@@ -53,7 +53,7 @@ def test_combine_lse_vs_reference_grid():
     reference's combine_lse_torch outputs stored in the fixture."""
     from hydragen_amd.attention import combine_lse
 
-    z = np.load("tests/golden/combine_lse.npz")
+    z = load_combine_lse()
     for i in range(int(z["count"])):
         o1, o2, l1, l2 = (dev(z[f"{n}_{i}"]) for n in ("o1", "o2", "l1", "l2"))
         r = combine_lse([o1, o2], [l1, l2]).cpu().numpy()
