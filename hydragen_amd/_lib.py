@@ -13,6 +13,7 @@ from pathlib import Path
 
 HYD_MAX_LEVELS = 8
 HYD_F16, HYD_BF16, HYD_F32 = 0, 1, 2
+HYD_FP8_E4M3 = 3  # hyd_kv_quant.kv_dtype: e4m3fn unique caches
 HYD_LSE_BQH, HYD_LSE_BHQ = 0, 1
 HYD_PHASE_ALL, HYD_PHASE_SHARED, HYD_PHASE_UNIQUE, HYD_PHASE_UNIQUE_PARTIAL, HYD_PHASE_MERGE = 0, 1, 2, 3, 4
 
@@ -111,6 +112,10 @@ class SampleParams(C.Structure):
     ]
 
 
+class KvQuant(C.Structure):
+    _fields_ = [("kv_dtype", C.c_int32), ("reserved", C.c_int32), ("k_scale", C.c_void_p), ("v_scale", C.c_void_p)]
+
+
 class AllReduceParams(C.Structure):
     _fields_ = [
         ("blocks", C.POINTER(C.c_void_p)), ("in_", C.c_void_p), ("out", C.c_void_p), ("count", C.c_int64),
@@ -142,6 +147,10 @@ EXPORTS = {
     "hyd_allreduce_block_bytes": (C.c_size_t, [C.c_int32, C.c_size_t]),
     "hyd_allreduce_sum": (C.c_int, [C.POINTER(AllReduceParams), C.c_void_p]),
     "hyd_allreduce_status": (C.c_void_p, [C.c_void_p]),
+    "hyd_suffix_attn_fwd_kvq": (C.c_int, [C.POINTER(SuffixParams), C.POINTER(KvQuant), C.c_void_p]),
+    "hyd_decode_attn_fused_kvq": (C.c_int, [C.POINTER(DecodeParams), C.POINTER(KvQuant), C.c_void_p]),
+    "hyd_rope_append_decode_kvq": (C.c_int, [C.POINTER(RopeParams), C.POINTER(KvQuant), C.c_void_p]),
+    "hyd_kv_quant_supported": (C.c_int, [C.POINTER(SuffixParams), C.POINTER(KvQuant)]),
     "hyd_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }

@@ -94,10 +94,14 @@ def hydragen_attention(
     shared_max_seq_lens: list[int | None],
     use_varlens: list[bool],
     seq_lens: Tensor | None = None,
+    *,
+    k_scale: Tensor | None = None,
+    v_scale: Tensor | None = None,
 ):
     """
     Computes Hydragen attention (attention decomposition + inter-sequence batching); same
-    contract as attention.py:177-354.
+    contract as attention.py:177-354.  k / v (the unique caches, not the shared levels) may be
+    float8_e4m3fn with per-kv-head fp32 scales k_scale / v_scale ([Hkv], None = 1; kv_quant.py).
 
     Args:
         q: attention queries, shape [batch, qlen, qheads, head_dim]
@@ -124,6 +128,12 @@ def hydragen_attention(
     n_levels = len(shared_ks)
 
     b, nq, hq, d = q.shape
+    fp8 = _flash.check_kv_pair(k, v, k_scale, v_scale)
+    fused_ok = seq_lens is not None or nq == 1 or k.shape[1] == 0
+    if fp8 and not (fused_ok and n_levels <= HYD_MAX_LEVELS and _flash.fp8_native(q, k, v)):
+        # shapes the fp8 suffix kernel does not take: 16-bit temporaries and the existing path (functional, not fast)
+        return hydragen_attention(q, _flash.dequantize_kv(k, k_scale, q.dtype), _flash.dequantize_kv(v, v_scale, q.dtype),
+                                  shared_ks, shared_vs, shared_cu_seq_lens, shared_max_seq_lens, use_varlens, seq_lens)
     dp = _flash.padded_head_dim(d)
     if dp != d:  # zero-padded to the kernels' head dim, true scale (flash.py: "head dims other than ...")
         pad = lambda t: _flash.pad_head_dim(t, dp)
@@ -132,16 +142,18 @@ def hydragen_attention(
                                      shared_cu_seq_lens, shared_max_seq_lens, use_varlens, seq_lens)
         return out[..., :d].contiguous()
     q = _q_contig(q)
-    k, v = _lastdim_contig(k), _lastdim_contig(v)
+    if not fp8:  # (fp8 caches passed fp8_native as they are)
+        k, v = _lastdim_contig(k), _lastdim_contig(v)
     shared_ks = [_lastdim_contig(x) for x in shared_ks]
     shared_vs = [_lastdim_contig(x) for x in shared_vs]
+    if any(x.dtype == _flash.FP8_DTYPE for x in shared_ks + shared_vs):
+        raise NotImplementedError("shared-prefix caches stay 16-bit: only the unique (per-sequence) cache may be fp8")
 
     # seq_lens None means "causal over the unique part" in the reference (attention.py:343-345);
     # with a single query the bottom-right-aligned causal mask hides nothing, which is the decode case.
-    fused_ok = seq_lens is not None or nq == 1 or k.shape[1] == 0
     if fused_ok and n_levels <= HYD_MAX_LEVELS:
         return _decode_fused(q, k, v, shared_ks, shared_vs, shared_cu_seq_lens, shared_max_seq_lens,
-                             use_varlens, seq_lens)
+                             use_varlens, seq_lens, (k_scale, v_scale) if fp8 else None)
 
     # The general form, as the reference spells it for any number of levels (attention.py:250-352): one prefix pass per
     # level, one pass over the unique K/V, an N-way log-sum-exp merge.  Taken for the unique-suffix prefill (causal
@@ -293,12 +305,17 @@ def _want_two_stream(q, k, shared_ks, shared_max_seq_lens, use_varlens, capturin
     return 4.0 * b * nq * hq * d * keys >= 4.0e9  # prefix flops worth hiding (C2: 34e9, C1: 1e5)
 
 
-def _launch_decode(lib, p, two_stream: bool, stream: int):
-    """Issue the operator described by `p`: one call, or the three calls of the two-stream form."""
+def _launch_decode(lib, p, two_stream: bool, stream: int, kq=None):
+    """Issue the operator described by `p`: one call, or the three calls of the two-stream form.  kq: the hyd_kv_quant of fp8
+    unique caches, or None."""
+    if kq is None:
+        fused = lambda p_, s_: lib.hyd_decode_attn_fused(C.byref(p_), s_)  # noqa: E731
+    else:
+        fused = lambda p_, s_: lib.hyd_decode_attn_fused_kvq(C.byref(p_), C.byref(kq), s_)  # noqa: E731
     if not two_stream:
         p.phase, p.shared_max_workgroups = HYD_PHASE_ALL, 0
         p.single_launch_small = 1  # problems that are launch latency, not work, run as one kernel (hydragen_hip.h)
-        _lib.check(lib.hyd_decode_attn_fused(C.byref(p), stream))
+        _lib.check(fused(p, stream))
         return
     p.single_launch_small = 0
     main = torch.cuda.current_stream()
@@ -307,20 +324,21 @@ def _launch_decode(lib, p, two_stream: bool, stream: int):
     side.wait_stream(main)
     try:
         p.phase = HYD_PHASE_SHARED
-        _lib.check(lib.hyd_decode_attn_fused(C.byref(p), side.cuda_stream))
+        _lib.check(fused(p, side.cuda_stream))
         p.phase = HYD_PHASE_UNIQUE_PARTIAL
-        _lib.check(lib.hyd_decode_attn_fused(C.byref(p), stream))
+        _lib.check(fused(p, stream))
     finally:
         main.wait_stream(side)  # always join: a capture must not end with a dangling branch
     p.phase = HYD_PHASE_MERGE
-    _lib.check(lib.hyd_decode_attn_fused(C.byref(p), stream))
+    _lib.check(fused(p, stream))
 
 
 def _tensor_key(t):
     return None if t is None else (t.data_ptr(), tuple(t.shape), tuple(t.stride()), t.dtype)
 
 
-def _decode_fused(q, k, v, shared_ks, shared_vs, shared_cu_seq_lens, shared_max_seq_lens, use_varlens, seq_lens):
+def _decode_fused(q, k, v, shared_ks, shared_vs, shared_cu_seq_lens, shared_max_seq_lens, use_varlens, seq_lens, scales=None):
+    """scales: None for 16-bit unique caches, (k_scale, v_scale) for fp8 ones (either may be None = 1)."""
     lib = _lib.load()
     b, nq, hq, d = q.shape
     out = torch.empty_like(q)
@@ -334,15 +352,19 @@ def _decode_fused(q, k, v, shared_ks, shared_vs, shared_cu_seq_lens, shared_max_
     if not uncached:
         key = (_tensor_key(q), _tensor_key(k), _tensor_key(v), _tensor_key(seq_lens), _tensor_key(order), q.device.index, stream, threading.get_ident(), _f32_partials,
                tuple(_tensor_key(x) for x in shared_ks), tuple(_tensor_key(x) for x in shared_vs),
-               tuple(_tensor_key(x) for x in shared_cu_seq_lens), tuple(shared_max_seq_lens), tuple(use_varlens))
+               tuple(_tensor_key(x) for x in shared_cu_seq_lens), tuple(shared_max_seq_lens), tuple(use_varlens),
+               None if scales is None else tuple(_tensor_key(x) for x in scales))
         hit = _PARAM_CACHE.get(key)
         if hit is not None:
             p = hit[0]
             p.suffix.out = out.data_ptr()
-            _launch_decode(lib, p, two_stream, stream)
+            _launch_decode(lib, p, two_stream, stream, *hit[3:])
             return out
     p = DecodeParams()
+    kq = None if scales is None else _flash.kv_quant_params(*scales)
     keep = [fill_suffix_params(p.suffix, q, k, v, seq_lens, out), order]
+    if scales is not None:
+        keep.extend(scales)
     p.n_levels = len(shared_ks)
     p.f32_partials = 1 if _f32_partials else 0
     for i, (sk, sv, scu, smax, uv) in enumerate(
@@ -361,7 +383,8 @@ def _decode_fused(q, k, v, shared_ks, shared_vs, shared_cu_seq_lens, shared_max_
         p.workspace, p.workspace_bytes = ws.data_ptr(), ws_bytes
     if two_stream and not lib.hyd_decode_two_stream_ok(C.byref(p)):
         two_stream = False
-    _launch_decode(lib, p, two_stream, stream)
+    extra = () if kq is None else (kq,)  # (16-bit caches: the call keeps its four-argument form)
+    _launch_decode(lib, p, two_stream, stream, *extra)
     # cache only when every pointer in `p` refers to caller-owned memory or to tensors `keep` holds on to
     cacheable = key is not None and (seq_lens is None or seq_lens.dtype in (torch.int32, torch.int64)) and \
         all(x is None or x.is_contiguous() for x in shared_cu_seq_lens) and (seq_lens is None or seq_lens.is_contiguous())
@@ -369,7 +392,7 @@ def _decode_fused(q, k, v, shared_ks, shared_vs, shared_cu_seq_lens, shared_max_
         global _param_cache_bytes
         while _PARAM_CACHE and (len(_PARAM_CACHE) >= _PARAM_CACHE_MAX or _param_cache_bytes + ws_bytes > _PARAM_CACHE_MAX_BYTES):
             _param_cache_bytes -= _PARAM_CACHE.pop(next(iter(_PARAM_CACHE)))[2]
-        _PARAM_CACHE[key] = (p, keep, ws_bytes)
+        _PARAM_CACHE[key] = (p, keep, ws_bytes, *extra)
         _param_cache_bytes += ws_bytes
     return out
 
@@ -381,9 +404,13 @@ def hydragen_attention_nopad(
     shared_ks: List[Tensor],
     shared_vs: List[Tensor],
     seq_len: Optional[Tensor] = None,
+    *,
+    k_scale: Optional[Tensor] = None,
+    v_scale: Optional[Tensor] = None,
 ):
     """
-    Hydragen attention when no shared level needs padding (attention.py:357-392).
+    Hydragen attention when no shared level needs padding (attention.py:357-392); k / v may be fp8 caches
+    with k_scale / v_scale as in hydragen_attention.
 
     Args:
         q: [batch, qlen, qheads, head_dim]
@@ -396,5 +423,5 @@ def hydragen_attention_nopad(
         q, k, v,
         shared_ks=shared_ks, shared_vs=shared_vs,
         shared_cu_seq_lens=[None] * n, shared_max_seq_lens=[None] * n, use_varlens=[False] * n,
-        seq_lens=seq_len,
+        seq_lens=seq_len, k_scale=k_scale, v_scale=v_scale,
     )

@@ -320,7 +320,8 @@ void fill_suffix_args(const hyd_suffix_params* p, SuffixArgs* ap) {
     a.scale_log2e = scale_log2e_of(p->softmax_scale, p->D);
 }
 
-int run_suffix(const hyd_suffix_params* p, const hyd_partial* parts, int n_parts, hipStream_t s) {
+// kq: null, or fp8 unique caches (validated by check_kvq; K/V strides in bytes)
+int run_suffix(const hyd_suffix_params* p, const hyd_partial* parts, int n_parts, hipStream_t s, const hyd_kv_quant* kq = nullptr) {
     SuffixArgs a;
     fill_suffix_args(p, &a);
     const size_t rows = (size_t)p->B * p->nq * p->Hq;
@@ -343,11 +344,43 @@ int run_suffix(const hyd_suffix_params* p, const hyd_partial* parts, int n_parts
     a.n_partials = n;
     a.n_pre = 0;
     while (a.n_pre < 2 && a.n_pre < n && !a.partials[a.n_pre].is_f32) ++a.n_pre;
-    if ((int64_t)p->kv_len * p->k_tok_stride * 2 >= (1ll << 31) || (int64_t)p->kv_len * p->v_tok_stride * 2 >= (1ll << 31))
+    const int64_t esz = kq ? 1 : 2;
+    if ((int64_t)p->kv_len * p->k_tok_stride * esz >= (1ll << 31) || (int64_t)p->kv_len * p->v_tok_stride * esz >= (1ll << 31))
         return fail(HYD_ERR_UNSUPPORTED, "unique K/V of one sequence spans >= 2 GiB (32-bit in-sequence offsets)");
     if (p->Hkv > 4 * 65535 || a.rows > 8 * 65535) return fail(HYD_ERR_UNSUPPORTED, "too many kv heads / query rows for the suffix grid");
+    if (kq) {
+        if (!suffix_fp8_eligible(a, p->D))
+            return fail(HYD_ERR_UNSUPPORTED, "fp8 unique caches: shapes not native (nq == 1, Hq == Hkv, Hkv a multiple of %d at D = %d)",
+                        64 / (p->D / 8), p->D);
+        SuffixKvqArgs ka;
+        ka.k_scale = kq->k_scale;
+        ka.v_scale = kq->v_scale;
+        ka.a = a;
+        const int rc = launch_suffix_fp8(ka, p->dtype, p->D, s);
+        return rc ? fail(HYD_ERR_LAUNCH, "fp8 suffix kernel launch failed: hip error %d", rc) : HYD_OK;
+    }
     int rc = launch_suffix(a, p->dtype, p->D, s);
     return rc ? fail(HYD_ERR_LAUNCH, "suffix kernel launch failed: hip error %d", rc) : HYD_OK;
+}
+
+// hyd_kv_quant of a call whose q dtype is `dtype`: *fp8 = true for e4m3fn caches, false for "no quantization"
+int check_kvq(const hyd_kv_quant* kq, int dtype, bool* fp8) {
+    *fp8 = false;
+    if (!kq || kq->kv_dtype == dtype) return HYD_OK;
+    if (kq->kv_dtype != HYD_FP8_E4M3)
+        return fail(HYD_ERR_UNSUPPORTED, "kv_dtype %d: HYD_FP8_E4M3 (%d) or the q dtype (%d)", kq->kv_dtype, HYD_FP8_E4M3, dtype);
+    if ((kq->k_scale && (reinterpret_cast<uintptr_t>(kq->k_scale) & 3u)) || (kq->v_scale && (reinterpret_cast<uintptr_t>(kq->v_scale) & 3u)))
+        return fail(HYD_ERR_BAD_ARG, "k_scale / v_scale must be 4-byte aligned fp32 arrays");
+    *fp8 = true;
+    return HYD_OK;
+}
+
+// shapes-only: does the fp8 suffix kernel take these shapes (nothing is launched, no device memory read)
+bool kvq_native(const hyd_suffix_params* p) {
+    if (check_common(p->dtype, p->B, p->nq, p->Hq, p->Hkv, p->D)) return false;
+    SuffixArgs a;
+    fill_suffix_args(p, &a);
+    return suffix_fp8_eligible(a, p->D);
 }
 
 void level_to_prefix(const hyd_decode_params* p, int i, hyd_prefix_params* pp) {
@@ -479,6 +512,25 @@ int hyd_suffix_attn_fwd(const hyd_suffix_params* p, void* stream) {
     return run_suffix(p, p->partials, p->n_partials, static_cast<hipStream_t>(stream));
 }
 
+int hyd_suffix_attn_fwd_kvq(const hyd_suffix_params* p, const hyd_kv_quant* kq, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    int rc = check_suffix(p, true);
+    if (rc) return rc;
+    bool fp8;
+    if ((rc = check_kvq(kq, p->dtype, &fp8))) return rc;
+    if (!fp8) return hyd_suffix_attn_fwd(p, stream);
+    if (p->n_partials < 0 || p->n_partials > HYD_MAX_LEVELS) return fail(HYD_ERR_BAD_ARG, "n_partials %d", p->n_partials);
+    if (p->kv_len == 0 && p->n_partials == 0) return fail(HYD_ERR_BAD_ARG, "kv_len == 0 and no partials");
+    return run_suffix(p, p->partials, p->n_partials, static_cast<hipStream_t>(stream), kq);
+}
+
+int hyd_kv_quant_supported(const hyd_suffix_params* p, const hyd_kv_quant* kq) {
+    if (!p) return 0;
+    if (!kq || kq->kv_dtype == p->dtype) return 1;
+    if (kq->kv_dtype != HYD_FP8_E4M3) return 0;
+    return kvq_native(p) ? 1 : 0;
+}
+
 int hyd_combine_lse(const void* const* outs, const float* const* lses, int32_t n, int64_t rows, int32_t D,
                     int32_t dtype, void* out, float* out_lse, void* stream) {
     if (!outs || !lses || !out) return fail(HYD_ERR_BAD_ARG, "null pointer");
@@ -507,7 +559,20 @@ int hyd_combine_lse(const void* const* outs, const float* const* lses, int32_t n
     return rc ? fail(HYD_ERR_LAUNCH, "combine kernel launch failed: hip error %d", rc) : HYD_OK;
 }
 
-int hyd_rope_append_decode(const hyd_rope_params* p, void* stream) {
+static int rope_impl(const hyd_rope_params* p, const hyd_kv_quant* kq, void* stream);
+
+int hyd_rope_append_decode(const hyd_rope_params* p, void* stream) { return rope_impl(p, nullptr, stream); }
+
+int hyd_rope_append_decode_kvq(const hyd_rope_params* p, const hyd_kv_quant* kq, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    int rc = check_common(p->dtype, p->B, 1, p->Hq, p->Hkv, p->D);
+    if (rc) return rc;
+    bool fp8;
+    if ((rc = check_kvq(kq, p->dtype, &fp8))) return rc;
+    return rope_impl(p, fp8 ? kq : nullptr, stream);
+}
+
+static int rope_impl(const hyd_rope_params* p, const hyd_kv_quant* kq, void* stream) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
     int rc = check_common(p->dtype, p->B, 1, p->Hq, p->Hkv, p->D);
     if (rc) return rc;
@@ -535,6 +600,14 @@ int hyd_rope_append_decode(const hyd_rope_params* p, void* stream) {
     a.vc_bs = p->vc_batch_stride; a.vc_ts = p->vc_tok_stride; a.vc_hs = p->vc_head_stride;
     a.pos_stride = p->pos_stride; a.cs_stride = p->cs_stride;
     a.B = p->B; a.Hq = p->Hq; a.Hkv = p->Hkv; a.cache_len = p->cache_len; a.max_pos = p->max_pos;
+    if (kq) {
+        RopeKvqArgs ka;
+        ka.a = a;
+        ka.k_scale = kq->k_scale;
+        ka.v_scale = kq->v_scale;
+        rc = launch_rope_append_fp8(ka, p->dtype, p->D, static_cast<hipStream_t>(stream));
+        return rc ? fail(HYD_ERR_LAUNCH, "rope_append (fp8 caches) kernel launch failed: hip error %d", rc) : HYD_OK;
+    }
     rc = launch_rope_append(a, p->dtype, p->D, static_cast<hipStream_t>(stream));
     return rc ? fail(HYD_ERR_LAUNCH, "rope_append kernel launch failed: hip error %d", rc) : HYD_OK;
 }
@@ -730,7 +803,27 @@ size_t hyd_workspace_bytes(int32_t B, int32_t nq, int32_t Hq, int32_t Hkv, int32
     return hyd_decode_workspace_bytes(&p);
 }
 
-int hyd_decode_attn_fused(const hyd_decode_params* p, void* stream) {
+static int decode_impl(const hyd_decode_params* p, const hyd_kv_quant* kq, void* stream);
+
+int hyd_decode_attn_fused(const hyd_decode_params* p, void* stream) { return decode_impl(p, nullptr, stream); }
+
+int hyd_decode_attn_fused_kvq(const hyd_decode_params* p, const hyd_kv_quant* kq, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    int rc = check_suffix(&p->suffix, true);
+    if (rc) return rc;
+    bool fp8;
+    if ((rc = check_kvq(kq, p->suffix.dtype, &fp8))) return rc;
+    if (!fp8) return hyd_decode_attn_fused(p, stream);
+    // fp8 unique caches: validated up front (every phase, also those that do not read the unique cache) so that the phases of one
+    // call agree; kv_len == 0 reads no unique key and takes the existing path
+    if (p->suffix.kv_len > 0 && !kvq_native(&p->suffix))
+        return fail(HYD_ERR_UNSUPPORTED, "fp8 unique caches: shapes not native (nq == 1, Hq == Hkv, Hkv a multiple of %d at D = %d)",
+                    64 / (p->suffix.D / 8), p->suffix.D);
+    return decode_impl(p, p->suffix.kv_len > 0 ? kq : nullptr, stream);
+}
+
+// kq: null, or validated fp8 unique caches (then single_launch_small is ignored and the unique pass is the fp8 kernel)
+static int decode_impl(const hyd_decode_params* p, const hyd_kv_quant* kq, void* stream) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
     if (p->n_levels < 0 || p->n_levels > HYD_MAX_LEVELS) return fail(HYD_ERR_BAD_ARG, "n_levels %d", p->n_levels);
     if (p->phase < HYD_PHASE_ALL || p->phase > HYD_PHASE_MERGE) return fail(HYD_ERR_BAD_ARG, "phase %d", p->phase);
@@ -783,7 +876,7 @@ int hyd_decode_attn_fused(const hyd_decode_params* p, void* stream) {
         n_parts += (pls[i].nsplit == 1 || small[i]) ? 1 : pls[i].nsplit;
     }
     if (n_parts + (two_stream ? 1 : 0) > kMaxCombine) return fail(HYD_ERR_UNSUPPORTED, "%d partials (more than %d)", n_parts, kMaxCombine);
-    if (decode_runs_as_one_launch(p, pps, pls, small)) {
+    if (!kq && decode_runs_as_one_launch(p, pps, pls, small)) {
         // launch latency, not work: the grouped-query kernel walks the group's shared keys, then the sequence's own
         SuffixArgs a;
         fill_suffix_args(&sp, &a);
@@ -838,7 +931,7 @@ int hyd_decode_attn_fused(const hyd_decode_params* p, void* stream) {
             hyd_suffix_params su = sp;
             su.out = u_out;
             su.lse = u_lse;
-            return run_suffix(&su, nullptr, 0, s);
+            return run_suffix(&su, nullptr, 0, s, kq);
         }
         CombineArgs c;  // HYD_PHASE_MERGE: every level's partial(s) + the unique partial -> out
         memset(&c, 0, sizeof(c));
@@ -873,7 +966,7 @@ int hyd_decode_attn_fused(const hyd_decode_params* p, void* stream) {
         s0.seq_lens_i64 = nullptr;
         return run_suffix(&s0, parts, p->n_levels, s);
     }
-    return run_suffix(&sp, parts, p->n_levels, s);
+    return run_suffix(&sp, parts, p->n_levels, s, kq);
 }
 
 int hyd_decode_two_stream_ok(const hyd_decode_params* p) {

@@ -82,6 +82,14 @@ struct SuffixArgs {
     PartialDev partials[kMaxCombine];
 };
 
+// fp8 unique caches (hyd_kv_quant): the argument block of the existing kernel plus the per-kv-head scales ([Hkv] or null = 1).
+// The scales travel in front so that the fields the kernels read first stay within the first scalar-cache lines.
+struct SuffixKvqArgs {
+    const float* k_scale;
+    const float* v_scale;
+    SuffixArgs a;
+};
+
 struct CombineArgs {
     const void* outs[kMaxCombine];
     const float* lses[kMaxCombine];
@@ -111,6 +119,12 @@ struct RopeArgs {
     int64_t kc_bs, kc_ts, kc_hs, vc_bs, vc_ts, vc_hs;
     int64_t pos_stride, cs_stride;
     int32_t B, Hq, Hkv, cache_len, max_pos;
+};
+
+struct RopeKvqArgs {  // rope_append.hip, fp8 caches: k_cache / v_cache hold e4m3fn bytes (strides in bytes)
+    RopeArgs a;
+    const float* k_scale;  // [Hkv] or null = 1
+    const float* v_scale;
 };
 
 struct NormArgs {  // layer_ops.hip: h = residual + x; normed = RMSNorm(h) * weight
@@ -153,6 +167,9 @@ int launch_swiglu(const SwigluArgs& a, int dtype, hipStream_t s);
 int launch_sample(const SampleArgs& a, int dtype, hipStream_t s);
 int launch_suffix(const SuffixArgs& a, int dtype, int D, hipStream_t s);
 bool suffix_gqa_eligible(const SuffixArgs& a, int D, bool any_shape);
+bool suffix_fp8_eligible(const SuffixArgs& a, int D);                                 // suffix_attn_fp8.hip, shapes only
+int launch_suffix_fp8(const SuffixKvqArgs& a, int dtype, int D, hipStream_t s);       // q dtype; K/V e4m3fn
+int launch_rope_append_fp8(const RopeKvqArgs& a, int dtype, int D, hipStream_t s);
 int launch_suffix_gqa(const SuffixArgs& a, int dtype, int D, hipStream_t s);
 int launch_combine(const CombineArgs& a, hipStream_t s);
 size_t allreduce_block_bytes(int world, size_t max_bytes);

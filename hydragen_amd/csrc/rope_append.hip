@@ -78,6 +78,118 @@ __global__ __launch_bounds__(256) void rope_append_kernel(const RopeArgs a) {
     }
 }
 
+// fp8 caches (hyd_kv_quant): the same kernel, but the rotated k -- the 16-bit value the kernel above writes -- and v are stored as
+// quantize_kv(x, scale) (hydragen_amd/kv_quant.py): a correctly rounded x / scale[h], clamped to +-448 (NaN passes through the
+// comparisons), then v_cvt_pk_fp8_f32 (round-half-even; the clamp keeps it away from the overflow encoding), 8 bytes per store.
+__device__ __forceinline__ float fp8_prescale(float x, float s) {
+    const float y = x / s;
+    return y > 448.f ? 448.f : (y < -448.f ? -448.f : y);
+}
+__device__ __forceinline__ u32x2 quant_fp8x8(const float (&x)[8], float s) {
+    u32x2 r;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        int w = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_prescale(x[4 * i], s), fp8_prescale(x[4 * i + 1], s), 0, false);
+        w = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_prescale(x[4 * i + 2], s), fp8_prescale(x[4 * i + 3], s), w, true);
+        r[i] = (uint32_t)w;
+    }
+    return r;
+}
+template <typename T>
+__device__ __forceinline__ void widen8x(const u32x4& v, float (&f)[8]) {
+    using TR = Traits<T>;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        f[2 * i] = TR::lo(v[i]);
+        f[2 * i + 1] = TR::hi(v[i]);
+    }
+}
+
+template <typename T, int D>
+__global__ __launch_bounds__(256) void rope_append_fp8_kernel(const RopeKvqArgs ka) {
+    const RopeArgs& a = ka.a;
+    constexpr int TPR = D / 16;
+    const int rows_per_b = a.Hq + 2 * a.Hkv;
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t row = gid / TPR;
+    const int sub = (int)(gid % TPR);
+    if (row >= (int64_t)a.B * rows_per_b) return;
+    const int b = (int)(row / rows_per_b);
+    const int h = (int)(row % rows_per_b);
+    const int64_t pos_raw = a.pos[(int64_t)b * a.pos_stride];
+    const int64_t idx = pos_raw - (a.shared_len ? a.shared_len[b] : 0);
+    const int64_t pos = pos_raw < 0 ? 0 : (pos_raw >= a.max_pos ? (int64_t)a.max_pos - 1 : pos_raw);
+    if (h == 0 && sub == 0) a.seq_lens[b] = (int32_t)(idx + 1);
+    const int d0 = sub * 8;
+    u32x4 olo, ohi;
+    float s;
+    uint8_t* dst8;
+    if (h < a.Hq + a.Hkv) {
+        const bool isq = h < a.Hq;
+        const uint16_t* src = isq ? static_cast<const uint16_t*>(a.q) + (int64_t)b * a.q_bs + (int64_t)h * D
+                                  : static_cast<const uint16_t*>(a.k) + (int64_t)b * a.k_bs + (int64_t)(h - a.Hq) * D;
+        const u32x4 lo = *reinterpret_cast<const u32x4*>(src + d0);
+        const u32x4 hi = *reinterpret_cast<const u32x4*>(src + D / 2 + d0);
+        float c[8], sn[8];
+        const float* cr = a.cos + pos * a.cs_stride + d0;
+        const float* sr = a.sin + pos * a.cs_stride + d0;
+        const f32x4 c0 = *reinterpret_cast<const f32x4*>(cr), c1 = *reinterpret_cast<const f32x4*>(cr + 4);
+        const f32x4 s0 = *reinterpret_cast<const f32x4*>(sr), s1 = *reinterpret_cast<const f32x4*>(sr + 4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            c[i] = c0[i];
+            c[4 + i] = c1[i];
+            sn[i] = s0[i];
+            sn[4 + i] = s1[i];
+        }
+        rope8<T>(lo, hi, c, sn, olo, ohi);
+        if (isq) {
+            uint16_t* dst = static_cast<uint16_t*>(a.q_out) + ((int64_t)b * a.Hq + h) * D;
+            *reinterpret_cast<u32x4*>(dst + d0) = olo;
+            *reinterpret_cast<u32x4*>(dst + D / 2 + d0) = ohi;
+            return;
+        }
+        if (idx < 0 || idx >= a.cache_len) return;  // out of the allocated cache: never write out of bounds
+        const int hk = h - a.Hq;
+        s = ka.k_scale ? ka.k_scale[hk] : 1.0f;
+        dst8 = static_cast<uint8_t*>(a.k_cache) + (int64_t)b * a.kc_bs + idx * a.kc_ts + (int64_t)hk * a.kc_hs;
+    } else {
+        if (idx < 0 || idx >= a.cache_len) return;
+        const int hv = h - a.Hq - a.Hkv;
+        const uint16_t* src = static_cast<const uint16_t*>(a.v) + (int64_t)b * a.v_bs + (int64_t)hv * D;
+        olo = *reinterpret_cast<const u32x4*>(src + d0);
+        ohi = *reinterpret_cast<const u32x4*>(src + D / 2 + d0);
+        s = ka.v_scale ? ka.v_scale[hv] : 1.0f;
+        dst8 = static_cast<uint8_t*>(a.v_cache) + (int64_t)b * a.vc_bs + idx * a.vc_ts + (int64_t)hv * a.vc_hs;
+    }
+    float xl[8], xh[8];
+    widen8x<T>(olo, xl);
+    widen8x<T>(ohi, xh);
+    *reinterpret_cast<u32x2*>(dst8 + d0) = quant_fp8x8(xl, s);
+    *reinterpret_cast<u32x2*>(dst8 + D / 2 + d0) = quant_fp8x8(xh, s);
+}
+
+int launch_rope_append_fp8(const RopeKvqArgs& ka, int dtype, int D, hipStream_t s) {
+    const RopeArgs& a = ka.a;
+    const int64_t threads = (int64_t)a.B * (a.Hq + 2 * a.Hkv) * (D / 16);
+    const int grid = (int)((threads + 255) / 256);
+    if (grid == 0) return 0;
+#define HYD_ROPE(TT, DD) hipLaunchKernelGGL((rope_append_fp8_kernel<TT, DD>), dim3(grid), dim3(256), 0, s, ka)
+    if (dtype == HYD_F16) {
+        if (D == 128) HYD_ROPE(F16, 128);
+        else if (D == 64) HYD_ROPE(F16, 64);
+        else if (D == 256) HYD_ROPE(F16, 256);
+        else return (int)hipErrorInvalidValue;
+    } else {
+        if (D == 128) HYD_ROPE(BF16, 128);
+        else if (D == 64) HYD_ROPE(BF16, 64);
+        else if (D == 256) HYD_ROPE(BF16, 256);
+        else return (int)hipErrorInvalidValue;
+    }
+#undef HYD_ROPE
+    return (int)hipGetLastError();
+}
+
 int launch_rope_append(const RopeArgs& a, int dtype, int D, hipStream_t s) {
     const int64_t threads = (int64_t)a.B * (a.Hq + 2 * a.Hkv) * (D / 16);
     const int grid = (int)((threads + 255) / 256);

@@ -4,7 +4,8 @@ implemented by the hand-written gfx950 kernels behind the C ABI in include/hydra
 
     flash_attention          flash.py:284-306   -> hyd_prefix_attn_fwd (MFMA kernel)
     flash_attention_varlen   flash.py:309-351   -> hyd_prefix_attn_fwd (packed K/V + cu_seqlens)
-    flash_attention_seqlen   flash.py:163-281   -> hyd_suffix_attn_fwd (wavefront GEMV kernel)
+    flash_attention_seqlen   flash.py:163-281   -> hyd_suffix_attn_fwd (wavefront GEMV kernel); fp8 unique caches
+                                                   (kv_quant.py) -> hyd_suffix_attn_fwd_kvq
 
 PyTorch is used for device memory and the current stream only.
 """
@@ -13,12 +14,14 @@ from __future__ import annotations
 
 import contextvars
 import ctypes as C
+import functools
 
 import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import HYD_BF16, HYD_F16, HYD_LSE_BHQ, HYD_LSE_BQH, PrefixParams, SuffixParams
+from ._lib import HYD_BF16, HYD_F16, HYD_FP8_E4M3, HYD_LSE_BHQ, HYD_LSE_BQH, KvQuant, PrefixParams, SuffixParams
+from .kv_quant import FP8_DTYPE, dequantize_kv, quantize_kv  # noqa: F401  (quantize_kv: part of this module's face)
 
 
 def _dtype_code(t: Tensor) -> int:
@@ -283,7 +286,63 @@ def fill_suffix_params(p: SuffixParams, q: Tensor, k: Tensor, v: Tensor, seq_len
     return keep
 
 
-def flash_attention_seqlen(raw_q: Tensor, raw_k: Tensor, raw_v: Tensor, seq_len=None):
+# ---- fp8 unique caches (kv_quant.py) ------------------------------------------------------------------------------------
+# fp8 mode is told by k's dtype (v must match).  Shapes the fp8 suffix kernel takes natively (hyd_kv_quant_supported: nq == 1,
+# Hq == Hkv, D 64 / 128 / 256, Hkv a multiple of the heads of one wave instruction) go to the _kvq entry points; every other
+# shape -- grouped-query heads, several query rows, padded head dims, an odd number of heads -- is dequantized into a 16-bit
+# temporary and runs the existing path.  That fallback is functional, not fast (the cache is read, widened and written on
+# every call), in the spirit of pad_head_dim.
+def check_kv_pair(k: Tensor, v: Tensor, k_scale: Tensor | None, v_scale: Tensor | None) -> bool:
+    """True for fp8 caches (and validates their scales); scales given for 16-bit caches are an error."""
+    fp8 = k.dtype == FP8_DTYPE
+    if (v.dtype == FP8_DTYPE) != fp8:
+        raise TypeError(f"k and v caches must both be {FP8_DTYPE} or neither: got {k.dtype} / {v.dtype}")
+    if not fp8:
+        if k_scale is not None or v_scale is not None:
+            raise ValueError("k_scale / v_scale apply to float8_e4m3fn caches only")
+        return False
+    for name, sc in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if sc is not None:
+            if sc.dtype != torch.float32 or sc.ndim != 1 or sc.numel() != k.shape[-2] or not sc.is_contiguous():
+                raise ValueError(f"{name}: contiguous float32 [Hkv = {k.shape[-2]}] expected, got {sc.dtype} {tuple(sc.shape)}")
+            _require_gpu(sc)
+    return True
+
+
+def kv_quant_params(k_scale: Tensor | None, v_scale: Tensor | None) -> KvQuant:
+    kq = KvQuant()
+    kq.kv_dtype = HYD_FP8_E4M3
+    kq.k_scale = k_scale.data_ptr() if k_scale is not None else None
+    kq.v_scale = v_scale.data_ptr() if v_scale is not None else None
+    return kq
+
+
+def fp8_native(q: Tensor, k: Tensor, v: Tensor) -> bool:
+    """Shapes only: whether the fp8 suffix kernel takes (q, k, v) as they are (hyd_kv_quant_supported)."""
+    if k.numel() and (k.data_ptr() % 16 or v.data_ptr() % 16):
+        return False
+    return _fp8_native_shapes(tuple(q.shape), q.dtype, tuple(k.shape), k.stride(), v.stride())
+
+
+@functools.lru_cache(maxsize=256)
+def _fp8_native_shapes(qshape, qdtype, kshape, kstride, vstride) -> bool:
+    # (cached: a decode step asks once per layer with the same shapes, and the ctypes round trip costs ~10 us)
+    if qshape[-1] not in (64, 128, 256) or qdtype not in (torch.float16, torch.bfloat16):
+        return False
+    if kstride[-1] != 1 or vstride[-1] != 1 or any(st % 8 for st in kstride[:-1] + vstride[:-1]):
+        return False
+    p = SuffixParams()
+    b, nq, hq, d = qshape
+    p.k_batch_stride, p.k_tok_stride, p.k_head_stride = kstride[:3]
+    p.v_batch_stride, p.v_tok_stride, p.v_head_stride = vstride[:3]
+    p.dtype = HYD_F16 if qdtype == torch.float16 else HYD_BF16
+    p.B, p.nq, p.Hq, p.Hkv, p.D, p.kv_len = b, nq, hq, kshape[2], d, kshape[1]
+    kq = kv_quant_params(None, None)
+    return _lib.load().hyd_kv_quant_supported(C.byref(p), C.byref(kq)) == 1
+
+
+def flash_attention_seqlen(raw_q: Tensor, raw_k: Tensor, raw_v: Tensor, seq_len=None, *, k_scale: Tensor | None = None,
+                           v_scale: Tensor | None = None):
     """
     q shape: [batch, qseq_len, qheads, dim]
     k shape: [batch, kseq_len, kheads, dim]
@@ -292,6 +351,7 @@ def flash_attention_seqlen(raw_q: Tensor, raw_k: Tensor, raw_v: Tensor, seq_len=
     Non-causal attention of every query over the first seq_len[b] keys of sequence b
     (flash.py:163-281).  Returns (out [b, q, h, d], lse [b, q, h] fp32, natural log).
     seq_len may be int32 or int64 (no cast kernel, cf. flash.py:220); None = all keys.
+    k / v may be float8_e4m3fn caches (kv_quant.py) with per-kv-head fp32 scales k_scale / v_scale ([Hkv], None = 1).
     """
     _require_gpu(raw_q, raw_k, raw_v, seq_len)
     assert raw_q.ndim == 4 and raw_k.ndim == 4 and raw_v.ndim == 4
@@ -299,6 +359,22 @@ def flash_attention_seqlen(raw_q: Tensor, raw_k: Tensor, raw_v: Tensor, seq_len=
     assert raw_q.shape[-1] == raw_k.shape[-1], (
         f"Keys have head dim {raw_k.shape[-1]} but queries have head dim {raw_q.shape[-1]}"
     )
+    if check_kv_pair(raw_k, raw_v, k_scale, v_scale):
+        if not fp8_native(raw_q, raw_k, raw_v):  # functional fallback: 16-bit temporaries, the existing path
+            return flash_attention_seqlen(raw_q, dequantize_kv(raw_k, k_scale, raw_q.dtype),
+                                          dequantize_kv(raw_v, v_scale, raw_q.dtype), seq_len)
+        lib = _lib.load()
+        q = _q_contig(raw_q)
+        out = torch.empty_like(q)
+        lse = torch.empty(q.shape[:3], dtype=torch.float32, device=q.device)
+        p = SuffixParams()
+        keep = fill_suffix_params(p, q, raw_k, raw_v, seq_len, out)
+        p.lse = lse.data_ptr()
+        p.n_partials = 0
+        kq = kv_quant_params(k_scale, v_scale)
+        _lib.check(lib.hyd_suffix_attn_fwd_kvq(C.byref(p), C.byref(kq), _stream()))
+        del keep
+        return out, lse
     d = raw_q.shape[-1]
     dp = padded_head_dim(d)
     if dp != d:

@@ -10,16 +10,19 @@ from torch import Tensor
 
 from . import _lib
 from ._lib import RopeParams
-from .flash import _dtype_code, _require_gpu, _stream
+from .flash import _dtype_code, _require_gpu, _stream, check_kv_pair, kv_quant_params
 
 
 def rope_append_decode(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, position_ids: Tensor,
-                       shared_len: Tensor | None, k_cache: Tensor, v_cache: Tensor):
+                       shared_len: Tensor | None, k_cache: Tensor, v_cache: Tensor, *, k_scale: Tensor | None = None,
+                       v_scale: Tensor | None = None):
     """q [B,1,Hq,D], k/v [B,1,Hkv,D] (this step's projections), cos/sin fp32 [max_pos, D],
     position_ids int64 [B,1] absolute, shared_len int64 [B] or None, caches [maxB, maxS, Hkv, D].
     Returns (rotated q [B,1,Hq,D], seq_lens int32 [B]); k (rotated) and v are written into the caches
-    at index position - shared_len."""
+    at index position - shared_len.  float8_e4m3fn caches receive quantize_kv(k_rot, k_scale) and
+    quantize_kv(v, v_scale) (kv_quant.py), k_rot being the 16-bit rotated k a 16-bit cache would hold."""
     _require_gpu(q, k, v, cos, sin, position_ids, k_cache, v_cache)
+    fp8 = check_kv_pair(k_cache, v_cache, k_scale, v_scale)
     lib = _lib.load()
     B, one, Hq, D = q.shape
     assert one == 1 and k.shape[:2] == (B, 1) and v.shape == k.shape
@@ -46,5 +49,9 @@ def rope_append_decode(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor
     p.pos_stride, p.cs_stride = position_ids.stride(0), cos.stride(0)
     p.dtype, p.B, p.Hq, p.Hkv, p.D, p.cache_len = _dtype_code(q), B, Hq, Hkv, D, k_cache.shape[1]
     p.max_pos = cos.shape[0]
-    _lib.check(lib.hyd_rope_append_decode(C.byref(p), _stream()))
+    if fp8:
+        kq = kv_quant_params(k_scale, v_scale)
+        _lib.check(lib.hyd_rope_append_decode_kvq(C.byref(p), C.byref(kq), _stream()))
+    else:
+        _lib.check(lib.hyd_rope_append_decode(C.byref(p), _stream()))
     return q_out, seq_lens

@@ -27,6 +27,7 @@ from . import layer_ops, placement
 from .attention import hydragen_attention
 from . import flash as _flash
 from .flash import flash_attention, flash_attention_seqlen
+from .kv_quant import FP8_DTYPE, dequantize_kv, quantize_kv
 from .tp import all_reduce_sum, check_collectives
 
 
@@ -219,16 +220,29 @@ class PerLayerKVCache(nn.Module):
     """llama.py:173-346."""
 
     def __init__(self, max_unique_batch_size, max_unique_seq_length, max_shared_batch_sizes, max_shared_seq_lengths,
-                 n_kv_heads, head_dim, device, dtype, arena: Optional[Tensor] = None):
+                 n_kv_heads, head_dim, device, dtype, arena: Optional[Tensor] = None, kv_cache_dtype: Optional[torch.dtype] = None):
         super().__init__()
         shape = (max_unique_batch_size, max_unique_seq_length, n_kv_heads, head_dim)
+        # kv_cache_dtype = torch.float8_e4m3fn: the unique arena holds e4m3fn bytes (kv_quant.py) with one fp32 scale per kv head
+        # for K and for V (k_scale / v_scale, 1.0 until set in place: a captured graph keeps their pointers); the shared caches
+        # stay in `dtype`
+        udtype = dtype if kv_cache_dtype is None else kv_cache_dtype
+        if udtype not in (dtype, FP8_DTYPE):
+            raise NotImplementedError(f"unique KV cache dtype {udtype}: the model's {dtype} or {FP8_DTYPE}")
+        self.fp8 = udtype == FP8_DTYPE
+        if self.fp8:
+            self.register_buffer("k_scale", torch.ones((n_kv_heads,), dtype=torch.float32, device=device), persistent=False)
+            self.register_buffer("v_scale", torch.ones((n_kv_heads,), dtype=torch.float32, device=device), persistent=False)
+        else:
+            self.k_scale = self.v_scale = None
+        dtype_unique = udtype
         # One allocation per layer (the reference's two attribute names, llama.py:186-198, stay as views of it): a sequence's K rows,
         # then its V rows (placement.kv_arena: the suffix pass streams that 1.5-3 % faster than all K, then all V).  WHERE the arena
         # sits in HBM matters too (profiles/r05_gqa_placement.md): `setup_caches` hands in arenas chosen by hydragen_amd/placement.py;
         # without one, a plain allocation of the same layout.
         if arena is None:
-            arena = placement.kv_arena(shape, dtype, device, zero=True)
-        assert tuple(arena.shape) == (2,) + shape and arena.dtype == dtype, f"{tuple(arena.shape)} {arena.dtype}"
+            arena = placement.kv_arena(shape, dtype_unique, device, zero=True)
+        assert tuple(arena.shape) == (2,) + shape and arena.dtype == dtype_unique, f"{tuple(arena.shape)} {arena.dtype}"
         self.register_buffer("per_completion_k_cache", arena[0])
         self.register_buffer("per_completion_v_cache", arena[1])
         self.shared_caches = nn.ModuleList([
@@ -247,13 +261,25 @@ class PerLayerKVCache(nn.Module):
         assert n <= self.get_num_total_shared_caches(), f"{n} {self.get_num_total_shared_caches()}"
         self.num_used_shared_caches = n
 
+    def scales(self) -> dict:
+        """The k_scale / v_scale keywords of the attention operators (empty for 16-bit caches)."""
+        return dict(k_scale=self.k_scale, v_scale=self.v_scale) if self.fp8 else {}
+
+    def _store(self, cache: Tensor, x: Tensor, scale: Optional[Tensor]):
+        """(cache bytes, value bytes): fp8 caches receive quantize_kv(x, scale), moved as bytes."""
+        if not self.fp8:
+            return cache, x
+        return cache.view(torch.uint8), quantize_kv(x, scale).view(torch.uint8)
+
     def update_per_completion_kvs(self, input_pos: Tensor, k_val: Tensor, v_val: Tensor):
         """input_pos [bs, sl]; k_val/v_val [bs, sl, h, d] -> scatter into the caches (llama.py:236-262)."""
         assert input_pos.shape[1] == k_val.shape[1], f"{input_pos.shape} {k_val.shape}"
         bs, sl, h, d = k_val.shape
         idx = input_pos[:, :, None, None].expand(bs, -1, h, d).to(torch.int64)
-        self.per_completion_k_cache[:bs].scatter_(1, idx, k_val)
-        self.per_completion_v_cache[:bs].scatter_(1, idx, v_val)
+        kc, kv = self._store(self.per_completion_k_cache, k_val, self.k_scale)
+        vc, vv = self._store(self.per_completion_v_cache, v_val, self.v_scale)
+        kc[:bs].scatter_(1, idx, kv)
+        vc[:bs].scatter_(1, idx, vv)
         return self.per_completion_k_cache[:bs], self.per_completion_v_cache[:bs]
 
     @torch.no_grad()
@@ -265,17 +291,20 @@ class PerLayerKVCache(nn.Module):
         assert total_num_sequences % sb == 0
         rep = total_num_sequences // sb
         cu = sc.cumsum_lengths.tolist()
+        kc, kv = self._store(self.per_completion_k_cache, sc.k_cache, self.k_scale)
+        vc, vv = self._store(self.per_completion_v_cache, sc.v_cache, self.v_scale)
         for i in range(sb):
             n = cu[i + 1] - cu[i]
-            self.per_completion_k_cache[i * rep : (i + 1) * rep, :n] = sc.k_cache[cu[i] : cu[i + 1]].unsqueeze(0)
-            self.per_completion_v_cache[i * rep : (i + 1) * rep, :n] = sc.v_cache[cu[i] : cu[i + 1]].unsqueeze(0)
+            kc[i * rep : (i + 1) * rep, :n] = kv[cu[i] : cu[i + 1]].unsqueeze(0)
+            vc[i * rep : (i + 1) * rep, :n] = vv[cu[i] : cu[i + 1]].unsqueeze(0)
 
     @torch.no_grad()
     def repeat_per_completion_cache_for_num_samples(self, current_size: int, num_samples: int):
         if num_samples == 1:
             return
-        self.per_completion_k_cache[: current_size * num_samples] = self.per_completion_k_cache[:current_size].repeat_interleave(num_samples, 0)
-        self.per_completion_v_cache[: current_size * num_samples] = self.per_completion_v_cache[:current_size].repeat_interleave(num_samples, 0)
+        for c in (self.per_completion_k_cache, self.per_completion_v_cache):
+            c = c.view(torch.uint8) if self.fp8 else c  # a byte copy either way
+            c[: current_size * num_samples] = c[:current_size].repeat_interleave(num_samples, 0)
 
     def get_used_shared_caches(self) -> list[SharedCache]:
         return list(self.shared_caches)[: self.num_used_shared_caches]
@@ -303,8 +332,9 @@ class AttentionMode:
     DECODE = "decode"
 
 
-def hydragen_attention_on_caches(q, k, v, shared_caches: list[SharedCache], seq_len: Optional[Tensor] = None):
-    """llama.py:355-414: adapt the caches to the operator's arguments (views only, no copies)."""
+def hydragen_attention_on_caches(q, k, v, shared_caches: list[SharedCache], seq_len: Optional[Tensor] = None, **scales):
+    """llama.py:355-414: adapt the caches to the operator's arguments (views only, no copies).  scales: k_scale / v_scale of
+    fp8 unique caches."""
     keys, values, cu_seqlens, max_seqlens, use_varlens = [], [], [], [], []
     for sc in shared_caches:
         if sc.use_varlen:
@@ -320,7 +350,7 @@ def hydragen_attention_on_caches(q, k, v, shared_caches: list[SharedCache], seq_
             max_seqlens.append(None)
         use_varlens.append(sc.use_varlen)
     return hydragen_attention(q, k, v, shared_ks=keys, shared_vs=values, shared_cu_seq_lens=cu_seqlens,
-                              shared_max_seq_lens=max_seqlens, use_varlens=use_varlens, seq_lens=seq_len)
+                              shared_max_seq_lens=max_seqlens, use_varlens=use_varlens, seq_lens=seq_len, **scales)
 
 
 class HydragenLlamaAttention(nn.Module):
@@ -374,8 +404,9 @@ class HydragenLlamaAttention(nn.Module):
                 shared_len = None
             elif shared_len is None:
                 shared_len = self.kv_cache.get_shared_len(bsz)
+            sc = self.kv_cache.scales()
             q, seq_lens = rope_append_decode(q, k, v, cos, sin, position_ids, shared_len,
-                                             self.kv_cache.per_completion_k_cache, self.kv_cache.per_completion_v_cache)
+                                             self.kv_cache.per_completion_k_cache, self.kv_cache.per_completion_v_cache, **sc)
             key_states = self.kv_cache.per_completion_k_cache[:bsz]
             value_states = self.kv_cache.per_completion_v_cache[:bsz]
             if self.disable_attention:
@@ -383,10 +414,10 @@ class HydragenLlamaAttention(nn.Module):
                 # the other modes, so that this mode's step is the decode step minus exactly the attention kernels.
                 attn_output = q
             elif not self.kv_cache.has_shared() or self.disable_hydragen:
-                attn_output, _ = flash_attention_seqlen(q, key_states, value_states, seq_len=seq_lens)
+                attn_output, _ = flash_attention_seqlen(q, key_states, value_states, seq_len=seq_lens, **sc)
             else:
                 attn_output = hydragen_attention_on_caches(q, key_states, value_states,
-                                                           self.kv_cache.get_used_shared_caches(), seq_len=seq_lens)
+                                                           self.kv_cache.get_used_shared_caches(), seq_len=seq_lens, **sc)
             out = self.o_proj(attn_output.reshape(bsz, q_len, -1))
             return all_reduce_sum(out) if self.tp_reduce else out
 
@@ -408,7 +439,10 @@ class HydragenLlamaAttention(nn.Module):
             if self.disable_hydragen:
                 ks, vs = self.kv_cache.update_per_completion_kvs(unique_position_ids, k, v)
                 n = int(unique_position_ids.max().item()) + 1
-                attn_output, _ = flash_attention(q, ks[:, :n], vs[:, :n], causal=True)
+                ks, vs = ks[:, :n], vs[:, :n]
+                if self.kv_cache.fp8:  # the 16-bit prefix kernel reads the cache: dequantized rows
+                    ks, vs = dequantize_kv(ks, self.kv_cache.k_scale, q.dtype), dequantize_kv(vs, self.kv_cache.v_scale, q.dtype)
+                attn_output, _ = flash_attention(q, ks, vs, causal=True)
             else:
                 if not self.kv_cache.has_shared():
                     attn_output, _ = flash_attention(q, k, v, causal=True)
@@ -418,10 +452,12 @@ class HydragenLlamaAttention(nn.Module):
         elif self.mode == AttentionMode.DECODE:
             ks, vs = self.kv_cache.update_per_completion_kvs(unique_position_ids, k, v)
             seq_lens = unique_position_ids.squeeze(-1) + 1
+            sc = self.kv_cache.scales()
             if not self.kv_cache.has_shared() or self.disable_hydragen:
-                attn_output, _ = flash_attention_seqlen(q, ks, vs, seq_len=seq_lens)
+                attn_output, _ = flash_attention_seqlen(q, ks, vs, seq_len=seq_lens, **sc)
             else:
-                attn_output = hydragen_attention_on_caches(q, ks, vs, self.kv_cache.get_used_shared_caches(), seq_len=seq_lens)
+                attn_output = hydragen_attention_on_caches(q, ks, vs, self.kv_cache.get_used_shared_caches(), seq_len=seq_lens,
+                                                           **sc)
         else:
             raise ValueError(f"Unknown mode {self.mode}")
 
@@ -673,8 +709,10 @@ class HydragenLlamaForCausalLM(nn.Module):
         return self.config.num_attention_heads
 
     def setup_caches(self, max_unique_batch_size: int, max_unique_seq_length: int,
-                     max_shared_batch_sizes: list[int], max_shared_seq_lengths: list[int]):
-        """Allocate the unique KV cache and the shared cache levels at every layer (llama.py:921-955)."""
+                     max_shared_batch_sizes: list[int], max_shared_seq_lengths: list[int], kv_cache_dtype: Optional[torch.dtype] = None):
+        """Allocate the unique KV cache and the shared cache levels at every layer (llama.py:921-955).  kv_cache_dtype =
+        torch.float8_e4m3fn makes every layer's unique arena fp8 (half the bytes; per-kv-head k_scale / v_scale buffers on each
+        PerLayerKVCache, 1.0 until set in place); None = the model's dtype.  Shared caches stay in the model's dtype."""
         self.maybe_invalidate()
         max_unique_seq_length = (max_unique_seq_length + 15) // 16 * 16
         head_dim = self.config.hidden_size // self.get_num_heads()
@@ -684,14 +722,18 @@ class HydragenLlamaForCausalLM(nn.Module):
         self.kv_cache_allocated = False
         for layer in self.model.layers:
             layer.self_attn.kv_cache = None  # a second setup_caches: the old arenas are free before the candidates are made
+        udtype = dtype if kv_cache_dtype is None else kv_cache_dtype
+        if udtype not in (dtype, FP8_DTYPE):
+            raise NotImplementedError(f"kv_cache_dtype {kv_cache_dtype}: the model's {dtype} or {FP8_DTYPE}")
         arenas, self.kv_placement = placement.place_kv_arenas(
             len(self.model.layers), (max_unique_batch_size, max_unique_seq_length, self.config.num_key_value_heads, head_dim),
-            dtype, device, self.config.num_attention_heads)
+            udtype, device, self.config.num_attention_heads, q_dtype=dtype)
         for layer, arena in zip(self.model.layers, arenas):
             layer.self_attn.kv_cache = PerLayerKVCache(
                 max_unique_batch_size=max_unique_batch_size, max_unique_seq_length=max_unique_seq_length,
                 max_shared_batch_sizes=max_shared_batch_sizes, max_shared_seq_lengths=max_shared_seq_lengths,
-                n_kv_heads=self.config.num_key_value_heads, head_dim=head_dim, device=device, dtype=dtype, arena=arena)
+                n_kv_heads=self.config.num_key_value_heads, head_dim=head_dim, device=device, dtype=dtype, arena=arena,
+                kv_cache_dtype=udtype)
         # the decode loop's schedule hint (flash.seq_order): one buffer for the model's lifetime, so that a captured decode graph
         # keeps pointing at the current generation's order
         self.seq_order_buf = torch.arange(max_unique_batch_size, dtype=torch.int32, device=device)

@@ -42,7 +42,13 @@ def kv_arena(shape: Sequence[int], dtype: torch.dtype, device, zero: bool = True
     with the distance between sequences up to 512 rows, profiles/r06_suffix_rows_capacity.txt).  The operators take strided K / V."""
     b, rows, hkv, d = (int(x) for x in shape)
     make = torch.zeros if zero else torch.empty
+    if dtype == torch.float8_e4m3fn:  # fp8 unique caches (kv_quant.py): allocated and zeroed as bytes
+        return make((b, 2, rows, hkv, d), dtype=torch.uint8, device=device).view(dtype).permute(1, 0, 2, 3, 4)
     return make((b, 2, rows, hkv, d), dtype=dtype, device=device).permute(1, 0, 2, 3, 4)
+
+
+def _zero(a: Tensor) -> None:
+    (a.view(torch.uint8) if a.dtype == torch.float8_e4m3fn else a).zero_()
 
 
 def set_candidates(n: int) -> int:
@@ -56,18 +62,19 @@ def get_candidates() -> int:
     return _candidates
 
 
-def probe_suffix_pass_us(arena: Tensor, qheads: int, iters: int = 3) -> float:
+def probe_suffix_pass_us(arena: Tensor, qheads: int, iters: int = 3, q_dtype: torch.dtype | None = None) -> float:
     """Microseconds the suffix pass that will serve this cache takes on it: `flash_attention_seqlen` (= `hyd_suffix_attn_fwd`,
     the kernel the library picks for `qheads` query heads) over `arena` = [2 (K | V), batch, rows, kv heads, head dim], at
     HALF of the cache's rows per sequence and at all of them, min of `iters` launches each after a warm-up, summed (HIP
     events on the current stream).  The real kernel on the real strides, because the effect is one of placement x access
     pattern: a stand-in (the one-row decode kernel over a grouped-query cache) ranks the candidates differently
     (profiles/r05_kv_placement_probe.md).  Half length = the mean decode step of a generation that fills the cache.  The
-    arena's contents do not matter to the rate (measured: random, zeros, stale: +- 1 us of 170) and are not touched."""
+    arena's contents do not matter to the rate (measured: random, zeros, stale: +- 1 us of 170) and are not touched.  q_dtype:
+    the queries' dtype (None = the arena's); an fp8 arena is timed with the fp8 suffix kernel that will serve it."""
     from .flash import flash_attention_seqlen
 
     _, B, S, Hkv, D = arena.shape
-    q = torch.zeros((B, 1, qheads, D), dtype=arena.dtype, device=arena.device)
+    q = torch.zeros((B, 1, qheads, D), dtype=q_dtype or arena.dtype, device=arena.device)
     total = 0.0
     for rows in sorted({max(1, S // 2), S}):
         lens = torch.full((B,), rows, dtype=torch.int32, device=arena.device)
@@ -110,7 +117,7 @@ def plan(count: int, arena_bytes: int, free_bytes: int, candidates: int) -> tupl
 
 
 def place_kv_arenas(count: int, shape: Sequence[int], dtype: torch.dtype, device, qheads: int, *, zero: bool = True,
-                    probe: Callable[[Tensor], float] | None = None) -> tuple[list[Tensor], dict]:
+                    probe: Callable[[Tensor], float] | None = None, q_dtype: torch.dtype | None = None) -> tuple[list[Tensor], dict]:
     """`count` K|V arenas of logical shape [2, *shape] (shape = [batch, rows, kv heads, head dim]; memory layout: `kv_arena`) on
     `device`, each the unique cache of one layer, placed where the suffix pass streams fastest among the candidates tried.  Returns (arenas,
     report); report = {"candidates", "spacer_bytes", "probe_us", "kept"} -- or {"candidates": count, "probed": False, "why"}.
@@ -118,7 +125,8 @@ def place_kv_arenas(count: int, shape: Sequence[int], dtype: torch.dtype, device
     Side effects, once per call: up to MAX_FREE_FRACTION (half) of the device's FREE memory is allocated for a moment
     (candidates + spacers) and `torch.cuda.empty_cache()` runs before returning; ranks that share one device should place
     their caches one after the other (they would race on `mem_get_info`).  Only a shape the suffix pass refuses (ValueError /
-    NotImplementedError / AssertionError from the operator) falls back to plain allocation, with a warning; runtime faults propagate."""
+    NotImplementedError / AssertionError from the operator) falls back to plain allocation, with a warning; runtime faults propagate.
+    q_dtype: the queries' dtype when it differs from the arena's (fp8 unique caches)."""
     dev = torch.device(device)
     full = (2,) + tuple(int(x) for x in shape)
     arena_bytes = math.prod(full) * torch.empty((), dtype=dtype).element_size()
@@ -136,7 +144,7 @@ def place_kv_arenas(count: int, shape: Sequence[int], dtype: torch.dtype, device
         return plain("probing off" if _candidates <= 1 else
                      "arena below the memory-side cache's size" if arena_bytes < MIN_ARENA_BYTES else "not enough free memory for candidates")
     if probe is None:
-        probe = lambda a: probe_suffix_pass_us(a, qheads)  # noqa: E731
+        probe = lambda a: probe_suffix_pass_us(a, qheads, q_dtype=q_dtype)  # noqa: E731
     cands, spacers = [], []
     try:
         for i in range(n):
@@ -163,7 +171,7 @@ def place_kv_arenas(count: int, shape: Sequence[int], dtype: torch.dtype, device
             torch.cuda.empty_cache()
             if zero:
                 for a in out:
-                    a.zero_()
+                    _zero(a)
             return out, {"candidates": count, "probed": False, "why": f"probe refused the shape: {type(ex).__name__}: {str(ex)[:120]}"}
         kept = choose(times, count)
         out = [cands[i] for i in kept]
@@ -171,5 +179,5 @@ def place_kv_arenas(count: int, shape: Sequence[int], dtype: torch.dtype, device
         torch.cuda.empty_cache()  # candidates not kept and the spacers go back to the driver, not into torch's pool
         if zero:
             for a in out:
-                a.zero_()
+                _zero(a)
     return out, {"candidates": len(times), "probed": True, "spacer_bytes": spacer, "probe_us": [round(t, 1) for t in times], "kept": kept}

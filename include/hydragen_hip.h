@@ -44,6 +44,9 @@ extern "C" {
 /* the library is built with -fvisibility=hidden: these entry points are its whole dynamic symbol table */
 #define HYD_API __attribute__((visibility("default")))
 
+/* 0.5.0 also carries the fp8 unique-cache entry points (hyd_kv_quant, hyd_*_kvq, hyd_kv_quant_supported): they are new symbols
+ * and a new struct only -- no existing struct, entry point or result changed -- so a caller built against 0.5.0 without them is
+ * unaffected and the version stays 500. */
 #define HYD_VERSION 500 /* 0.5.0: hyd_suffix_params.seq_order (schedule hint for ragged lengths); 0.4.0: hyd_add_rmsnorm, hyd_swiglu, hyd_sample_tokens (model-shell glue); 0.3.0: two-stream phases + hyd_decode_params.shared_max_workgroups, hyd_decode_two_stream_ok; 0.2.2: hyd_allreduce_params.timeout_log2_polls; 0.2.1: softmax_scale; 0.2.0: hyd_decode_params.phase, hyd_rope_params.max_pos, hyd_allreduce_* */
 #define HYD_MAX_LEVELS 8
 
@@ -55,7 +58,7 @@ enum {
     HYD_ERR_LAUNCH = -4       /* hipLaunchKernel reported an error                            */
 };
 
-enum { HYD_F16 = 0, HYD_BF16 = 1, HYD_F32 = 2 /* hyd_combine_lse only */ };
+enum { HYD_F16 = 0, HYD_BF16 = 1, HYD_F32 = 2 /* hyd_combine_lse only */, HYD_FP8_E4M3 = 3 /* hyd_kv_quant.kv_dtype only */ };
 
 /* LSE layouts: BQH = [B, nq, Hq] (what attention.py:276-280 re-lays flash's output into),
  *              BHQ = [sb, Hq, (B/sb)*nq] (what flash-attn returns, flash.py:295-306). */
@@ -344,6 +347,38 @@ HYD_API size_t hyd_allreduce_block_bytes(int32_t world, size_t max_bytes);
 HYD_API int hyd_allreduce_sum(const hyd_allreduce_params* p, void* stream);
 /* Device pointer of the status word inside a block (uint32: 0 = ok, 1 / 2 = a peer timed out in shot 1 / 2). */
 HYD_API const uint32_t* hyd_allreduce_status(const void* own_block);
+
+/* ------------------------------------------------------------------------------------------
+ * fp8 unique (per-sequence) K/V caches.  The unique cache may hold OCP e4m3fn bytes (torch.float8_e4m3fn; NOT the fnuz
+ * format of gfx942) with one fp32 scale per kv head, separately for K and V: the stored value is
+ *     q8 = e4m3fn_rne(clamp(x / scale[h], -448, 448))        (correctly rounded division, round-half-even)
+ * (hydragen_amd/kv_quant.py quantize_kv is the definition every kernel matches).  q, out, partials and the shared-prefix
+ * caches stay 16-bit; only the unique cache is quantized.  Every e4m3fn value is exactly a bf16 and an f16 value, so the
+ * kernels widen without rounding and the quantization is the only new rounding of the operator.
+ *
+ * The _kvq entry points take the existing parameter struct unchanged plus a hyd_kv_quant:
+ *   - kq == NULL, or kq->kv_dtype == the q dtype: exactly the existing entry point;
+ *   - kq->kv_dtype == HYD_FP8_E4M3: the unique K/V (suffix / decode) or the caches (rope append) are fp8; their strides
+ *     are counted in 1-byte elements (still multiples of 8), and so is the "span < 2 GiB" check of a sequence's cache.
+ * hyd_decode_attn_fused_kvq takes every phase; with fp8 caches single_launch_small is ignored (the prefix + suffix pair
+ * runs).  The workspace query is unchanged: the unique partial of the two-stream form stays in q's dtype.
+ * Native fp8 shapes (hyd_kv_quant_supported): one query row (nq == 1), Hq == Hkv, D 64 / 128 / 256, and Hkv a multiple of
+ * the 64 / (D / 8) heads one wave instruction covers.  Other shapes return HYD_ERR_UNSUPPORTED; the Python operators then
+ * dequantize into a 16-bit temporary and call the existing path (functional, not fast).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct hyd_kv_quant {
+    int32_t kv_dtype;     /* HYD_FP8_E4M3, or the q dtype = no quantization                       */
+    int32_t reserved;
+    const float* k_scale; /* [Hkv] device, or NULL = 1                                           */
+    const float* v_scale; /* [Hkv] device, or NULL = 1                                           */
+} hyd_kv_quant;
+
+HYD_API int hyd_suffix_attn_fwd_kvq(const hyd_suffix_params* p, const hyd_kv_quant* kq, void* stream);
+HYD_API int hyd_decode_attn_fused_kvq(const hyd_decode_params* p, const hyd_kv_quant* kq, void* stream);
+HYD_API int hyd_rope_append_decode_kvq(const hyd_rope_params* p, const hyd_kv_quant* kq, void* stream);
+/* Shapes only (capture-safe, no device read): 1 when the suffix pass of these shapes runs natively with kq's cache dtype
+ * (always 1 for kq == NULL or kv_dtype == dtype), else 0. */
+HYD_API int hyd_kv_quant_supported(const hyd_suffix_params* p, const hyd_kv_quant* kq);
 
 HYD_API int hyd_version(void);
 HYD_API const char* hyd_last_error_string(void);

@@ -21,6 +21,8 @@ ap.add_argument("--modes", default="hydragen,noattention")
 ap.add_argument("--no-graph", action="store_true")
 ap.add_argument("--iters", type=int, default=2)
 ap.add_argument("--tunableop", default="", help="PyTorch TunableOp results file (tools/tune_gemms.py) to select the GEMM solutions from; tuning itself stays off")
+ap.add_argument("--kv-dtype", default="bf16", help="unique KV cache dtype: bf16 (the model's) or fp8 (e4m3fn, unit scales); "
+                "a comma list (bf16,fp8) measures each in the same process, alternating per mode")
 ap.add_argument("--tp-slice", type=int, default=1, help="build rank 0's shard of an N-way tensor-parallel model (no collectives: per-GPU compute only)")
 a = ap.parse_args()
 
@@ -40,22 +42,28 @@ model = HydragenLlamaForCausalLM.from_config(cfg, dtype=torch.bfloat16, device=d
 model.graph(not a.no_graph)
 prompt = torch.randint(1, cfg.vocab_size, (1, a.prefix), device=dev)
 
-def run(mode, new):
+KV_DTYPES = {"bf16": None, "fp8": torch.float8_e4m3fn}
+kv_dtypes = a.kv_dtype.split(",")
+assert all(k in KV_DTYPES for k in kv_dtypes), f"--kv-dtype {a.kv_dtype}: bf16, fp8"
+
+
+def run(mode, new, kv="bf16"):
     kw = dict(disable_hydragen=(mode == "hydragen_noshared"), disable_attention=(mode == "noattention"))
     uniq = a.new + (a.prefix if mode == "hydragen_noshared" else 0)   # synth.py:56-61
     model.setup_caches(max_unique_batch_size=a.batch, max_unique_seq_length=uniq + 16,
-                       max_shared_batch_sizes=[1], max_shared_seq_lengths=[a.prefix])
+                       max_shared_batch_sizes=[1], max_shared_seq_lengths=[a.prefix], kv_cache_dtype=KV_DTYPES[kv])
     torch.cuda.synchronize(); t0 = time.perf_counter()
     model.generate(input_ids=prompt, num_return_sequences=a.batch, max_new_tokens=new, temperature=100.0, **kw)
     torch.cuda.synchronize()
     return time.perf_counter() - t0
 
 for mode in a.modes.split(","):
-    run(mode, 4)  # warm-up incl. graph capture
-    full = min(run(mode, a.new) for _ in range(a.iters))
-    pre = min(run(mode, 1) for _ in range(a.iters))
-    dec = full - pre
-    print(json.dumps({"mode": mode, "model": a.model, "layers": cfg.num_hidden_layers, "batch": a.batch,
-                      "prefix": a.prefix, "new_tokens": a.new, "total_s": full, "prefill_s": pre,
-                      "decode_s": dec, "decode_tokens_per_s": a.batch * (a.new - 1) / dec,
-                      "ms_per_decode_step": dec / (a.new - 1) * 1e3, "graph": not a.no_graph}))
+    for kv in kv_dtypes:
+        run(mode, 4, kv)  # warm-up incl. graph capture
+        full = min(run(mode, a.new, kv) for _ in range(a.iters))
+        pre = min(run(mode, 1, kv) for _ in range(a.iters))
+        dec = full - pre
+        print(json.dumps({"mode": mode, "kv_dtype": kv, "model": a.model, "layers": cfg.num_hidden_layers, "batch": a.batch,
+                          "prefix": a.prefix, "new_tokens": a.new, "total_s": full, "prefill_s": pre,
+                          "decode_s": dec, "decode_tokens_per_s": a.batch * (a.new - 1) / dec,
+                          "ms_per_decode_step": dec / (a.new - 1) * 1e3, "graph": not a.no_graph}))
