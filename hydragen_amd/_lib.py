@@ -112,6 +112,18 @@ class SampleParams(C.Structure):
     ]
 
 
+class SampleFilterParams(C.Structure):
+    _fields_ = [
+        ("logits", C.c_void_p), ("out", C.c_void_p), ("logprobs", C.c_void_p), ("kept", C.c_void_p),
+        ("row_stride", C.c_int64), ("seed", C.c_uint64), ("offset", C.c_uint64),
+        ("rows", C.c_int32), ("n", C.c_int32), ("dtype", C.c_int32), ("temperature", C.c_float),
+        ("top_k", C.c_int32), ("top_p", C.c_float), ("min_p", C.c_float),
+    ]
+
+
+SAMPLE_FILTER_MAX_N = 1 << 22  # HYD_SAMPLE_FILTER_MAX_N
+
+
 class KvQuant(C.Structure):
     _fields_ = [("kv_dtype", C.c_int32), ("reserved", C.c_int32), ("k_scale", C.c_void_p), ("v_scale", C.c_void_p)]
 
@@ -151,6 +163,7 @@ EXPORTS = {
     "hyd_decode_attn_fused_kvq": (C.c_int, [C.POINTER(DecodeParams), C.POINTER(KvQuant), C.c_void_p]),
     "hyd_rope_append_decode_kvq": (C.c_int, [C.POINTER(RopeParams), C.POINTER(KvQuant), C.c_void_p]),
     "hyd_kv_quant_supported": (C.c_int, [C.POINTER(SuffixParams), C.POINTER(KvQuant)]),
+    "hyd_sample_tokens_filtered": (C.c_int, [C.POINTER(SampleFilterParams), C.c_void_p]),
     "hyd_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }

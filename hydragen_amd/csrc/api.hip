@@ -675,6 +675,35 @@ int hyd_sample_tokens(const hyd_sample_params* p, void* stream) {
     return rc ? fail(HYD_ERR_LAUNCH, "sample kernel launch failed: hip error %d", rc) : HYD_OK;
 }
 
+int hyd_sample_tokens_filtered(const hyd_sample_filter_params* p, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    if (p->dtype != HYD_F16 && p->dtype != HYD_BF16 && p->dtype != HYD_F32) return fail(HYD_ERR_UNSUPPORTED, "dtype %d", p->dtype);
+    if (p->rows < 0 || p->n <= 0) return fail(HYD_ERR_BAD_ARG, "rows %d, n %d", p->rows, p->n);
+    if (p->n > HYD_SAMPLE_FILTER_MAX_N) return fail(HYD_ERR_UNSUPPORTED, "n %d: rows of up to %d logits", p->n, HYD_SAMPLE_FILTER_MAX_N);
+    if (!p->logits || !p->out) return fail(HYD_ERR_BAD_ARG, "logits / out is null");
+    if (!(p->temperature >= 0.f)) return fail(HYD_ERR_BAD_ARG, "temperature %g must be >= 0", (double)p->temperature);
+    if (p->top_k < 0) return fail(HYD_ERR_BAD_ARG, "top_k %d must be >= 0 (0 = off)", p->top_k);
+    if (!(p->top_p > 0.f && p->top_p <= 1.f)) return fail(HYD_ERR_BAD_ARG, "top_p %g must be in (0, 1] (1 = off)", (double)p->top_p);
+    if (!(p->min_p >= 0.f && p->min_p <= 1.f)) return fail(HYD_ERR_BAD_ARG, "min_p %g must be in [0, 1] (0 = off)", (double)p->min_p);
+    if (p->row_stride < p->n) return fail(HYD_ERR_BAD_ARG, "row_stride %lld < n %d", (long long)p->row_stride, p->n);
+    const int esz = p->dtype == HYD_F32 ? 4 : 2;
+    if ((reinterpret_cast<uintptr_t>(p->logits) & (uintptr_t)(esz - 1)) != 0 || (reinterpret_cast<uintptr_t>(p->out) & 7u) != 0 ||
+        (reinterpret_cast<uintptr_t>(p->logprobs) & 3u) != 0 || (reinterpret_cast<uintptr_t>(p->kept) & 3u) != 0)
+        return fail(HYD_ERR_BAD_ARG, "logits / out / logprobs / kept is not aligned to its element size");
+    FilterArgs a;
+    memset(&a, 0, sizeof(a));
+    a.logits = p->logits; a.out = p->out; a.logprobs = p->logprobs; a.kept = p->kept;
+    a.row_stride = p->row_stride; a.seed = p->seed; a.offset = p->offset;
+    a.rows = p->rows; a.n = p->n;
+    a.inv_temperature = p->temperature > 0.f ? 1.0f / p->temperature : 0.f;  // (as hyd_sample_tokens: the same noise scale)
+    a.top_k = p->top_k < p->n ? p->top_k : 0;
+    a.top_p = p->top_p;
+    a.log_min_p = p->min_p > 0.f ? (float)log((double)p->min_p) : -INFINITY;
+    a.vec_ok = ((reinterpret_cast<uintptr_t>(p->logits) & 15u) == 0 && p->row_stride % (16 / esz) == 0) ? 1 : 0;
+    const int rc = launch_sample_filter(a, p->dtype, static_cast<hipStream_t>(stream));
+    return rc ? fail(HYD_ERR_LAUNCH, "sample_filter kernel launch failed: hip error %d", rc) : HYD_OK;
+}
+
 // hyd_decode_params.single_launch_small: one uniform shared level that already counts as small (few query rows per
 // (group, kv head), short prefix), unique keys present, the same token strides in the shared and the unique tensors, and
 // so few keys in all that the call is launch latency.  Measured per graph-replayed call (tests/probes/single_launch_probe.py,

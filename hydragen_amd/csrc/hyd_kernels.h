@@ -158,6 +158,21 @@ struct SampleArgs {  // layer_ops.hip: out[row] ~ softmax(logits[row] / T) (Gumb
     int32_t vec_ok;      // rows are 16-byte aligned
 };
 
+struct FilterArgs {  // sample_filter.hip: SampleArgs' draw over the tokens that survive top-k / top-p / min-p
+    const void* logits;
+    int64_t* out;
+    float* logprobs;     // may be null
+    int32_t* kept;       // may be null
+    int64_t row_stride;  // elements
+    uint64_t seed, offset;
+    int32_t rows, n;
+    float inv_temperature;
+    int32_t top_k;       // 0 = off
+    float top_p;         // >= 1 = off
+    float log_min_p;     // ln(min_p); -inf = off
+    int32_t vec_ok;      // rows are 16-byte aligned
+};
+
 // launchers (defined next to the kernels); return hipError_t as int
 int launch_prefix_w64(const PrefixArgs& a, int dtype, int D, bool causal, int grid, hipStream_t s);
 int launch_prefix_w64_f16(const PrefixArgs& a, int D, bool causal, int grid, hipStream_t s);  // prefix_attn_w64_f16.hip
@@ -165,6 +180,7 @@ int launch_rope_append(const RopeArgs& a, int dtype, int D, hipStream_t s);
 int launch_add_rmsnorm(const NormArgs& a, int dtype, hipStream_t s);
 int launch_swiglu(const SwigluArgs& a, int dtype, hipStream_t s);
 int launch_sample(const SampleArgs& a, int dtype, hipStream_t s);
+int launch_sample_filter(const FilterArgs& a, int dtype, hipStream_t s);  // sample_filter.hip
 int launch_suffix(const SuffixArgs& a, int dtype, int D, hipStream_t s);
 bool suffix_gqa_eligible(const SuffixArgs& a, int D, bool any_shape);
 bool suffix_fp8_eligible(const SuffixArgs& a, int D);                                 // suffix_attn_fp8.hip, shapes only

@@ -1,4 +1,4 @@
-"""Python face of `hyd_add_rmsnorm` / `hyd_swiglu` (include/hydragen_hip.h): the elementwise glue of the decoder layer
+"""Python face of `hyd_add_rmsnorm` / `hyd_swiglu` / `hyd_sample_tokens[_filtered]` (include/hydragen_hip.h): the elementwise glue of the decoder layer
 around the attention block -- residual add + RMSNorm (/root/reference/hydragen/llama.py:615-631 with transformers'
 LlamaRMSNorm, llama.py:605-608,656) and the SwiGLU gate (transformers' LlamaMLP, llama.py:2,604) -- each as one
 HIP kernel instead of two torch launches."""
@@ -14,6 +14,7 @@ from torch import Tensor
 from . import _lib
 from ._lib import AddRmsnormParams, SwigluParams
 from .flash import _dtype_code, _require_gpu, _stream
+from .sampling import check_filters, filters_active
 
 
 def supported(x: Tensor, n_max: int = 16384) -> bool:
@@ -87,20 +88,52 @@ def _next_sample_key(device: torch.device):
     return seed, offset
 
 
-def sample_tokens(logits: Tensor, temperature: float, key: Optional[tuple] = None) -> Tensor:
+def sample_tokens(logits: Tensor, temperature: float, key: Optional[tuple] = None, *, top_k: Optional[int] = None,
+                  top_p: Optional[float] = None, min_p: Optional[float] = None, return_logprobs: bool = False):
     """[B, V] logits (fp16 / bf16 / fp32, rows contiguous) -> [B, 1] int64 tokens drawn from softmax(logits / temperature)
-    (temperature 0: argmax) in one kernel."""
+    (temperature 0: argmax) in one kernel.  top_k / top_p / min_p cut the UNSCALED softmax(logits) first (hydragen_amd/
+    sampling.py states the rules); return_logprobs also returns the [B, 1] fp32 log softmax(logits) of each drawn token.
+    With no cut and no log-prob this is hyd_sample_tokens; otherwise hyd_sample_tokens_filtered, whose draw uses the same
+    noise (one key per call either way)."""
+    if not filters_active(top_k, top_p, min_p) and not return_logprobs:
+        _require_gpu(logits)
+        lib = _lib.load()
+        assert logits.ndim == 2 and logits.stride(1) == 1 and logits.shape[1] > 0
+        out = torch.empty((logits.shape[0], 1), dtype=torch.int64, device=logits.device)
+        if logits.shape[0] == 0:
+            return out
+        seed, offset = key if key is not None else _next_sample_key(logits.device)
+        p = _lib.SampleParams()
+        p.logits, p.out, p.row_stride = logits.data_ptr(), out.data_ptr(), logits.stride(0) if logits.shape[0] > 1 else logits.shape[1]
+        p.seed, p.offset, p.rows, p.n = seed, offset, logits.shape[0], logits.shape[1]
+        p.dtype = _HYD_F32 if logits.dtype == torch.float32 else _dtype_code(logits)
+        p.temperature = float(temperature)
+        _lib.check(lib.hyd_sample_tokens(C.byref(p), _stream()))
+        return out
+    tok, lp, _ = sample_tokens_filtered(logits, temperature, key, top_k=top_k, top_p=top_p, min_p=min_p)
+    return (tok, lp[:, None]) if return_logprobs else tok
+
+
+def sample_tokens_filtered(logits: Tensor, temperature: float, key: Optional[tuple] = None, *, top_k: Optional[int] = None,
+                           top_p: Optional[float] = None, min_p: Optional[float] = None):
+    """hyd_sample_tokens_filtered: ([B, 1] int64 tokens, [B] fp32 log-probs, [B] int32 number of kept tokens)."""
     _require_gpu(logits)
     lib = _lib.load()
     assert logits.ndim == 2 and logits.stride(1) == 1 and logits.shape[1] > 0
-    out = torch.empty((logits.shape[0], 1), dtype=torch.int64, device=logits.device)
-    if logits.shape[0] == 0:
-        return out
+    rows = logits.shape[0]
+    out = torch.empty((rows, 1), dtype=torch.int64, device=logits.device)
+    logprobs = torch.empty((rows,), dtype=torch.float32, device=logits.device)
+    kept = torch.empty((rows,), dtype=torch.int32, device=logits.device)
+    if rows == 0:
+        return out, logprobs, kept
+    check_filters(top_k, top_p, min_p)  # (before the key is taken: a rejected call leaves the generator as it was)
+    p = _lib.SampleFilterParams()
+    p.top_k, p.top_p, p.min_p = int(top_k or 0), 1.0 if top_p is None else float(top_p), float(min_p or 0.0)
     seed, offset = key if key is not None else _next_sample_key(logits.device)
-    p = _lib.SampleParams()
-    p.logits, p.out, p.row_stride = logits.data_ptr(), out.data_ptr(), logits.stride(0) if logits.shape[0] > 1 else logits.shape[1]
-    p.seed, p.offset, p.rows, p.n = seed, offset, logits.shape[0], logits.shape[1]
+    p.logits, p.out, p.logprobs, p.kept = logits.data_ptr(), out.data_ptr(), logprobs.data_ptr(), kept.data_ptr()
+    p.row_stride = logits.stride(0) if rows > 1 else logits.shape[1]
+    p.seed, p.offset, p.rows, p.n = seed, offset, rows, logits.shape[1]
     p.dtype = _HYD_F32 if logits.dtype == torch.float32 else _dtype_code(logits)
     p.temperature = float(temperature)
-    _lib.check(lib.hyd_sample_tokens(C.byref(p), _stream()))
-    return out
+    _lib.check(lib.hyd_sample_tokens_filtered(C.byref(p), _stream()))
+    return out, logprobs, kept

@@ -23,7 +23,7 @@ from typing import List, Optional, Union
 import torch
 from torch import Tensor, nn
 
-from . import layer_ops, placement
+from . import layer_ops, placement, sampling
 from .attention import hydragen_attention
 from . import flash as _flash
 from .flash import flash_attention, flash_attention_seqlen
@@ -780,18 +780,34 @@ class HydragenLlamaForCausalLM(nn.Module):
         remove[..., -min_tokens_to_keep:] = 0
         return logits.masked_fill(remove.scatter(1, sorted_indices, remove), filter_value)
 
-    def sample_from_logits(self, logits, temperature, num_samples=1, top_p=None):
-        if top_p is not None:
+    def sample_from_logits(self, logits, temperature, num_samples=1, top_p=None, top_k=None, min_p=None,
+                           return_logprobs=False):
+        """Tokens [B, num_samples] (and, with return_logprobs, their fp32 log softmax(logits) [B, num_samples]).  The cuts
+        act on the unscaled softmax(logits), before the temperature (hydragen_amd/sampling.py)."""
+        filtered = sampling.filters_active(top_k, top_p, min_p)
+        eligible = logits.is_cuda and logits.ndim == 2 and num_samples == 1 and logits.stride(-1) == 1 and temperature >= 0
+        if eligible and (return_logprobs or (filtered and self.fused_sampling_filters)):
+            # one HIP kernel: the cuts, the Gumbel-max draw over the kept tokens and the token's log-probability
+            return layer_ops.sample_tokens(logits, temperature, top_k=top_k, top_p=top_p, min_p=min_p,
+                                           return_logprobs=return_logprobs)
+        src = logits
+        if top_k or min_p:
+            logits = sampling.filter_logits(logits, top_k, top_p, min_p)
+        elif top_p is not None:
             logits = self.apply_top_p(logits, top_p)
-        if logits.is_cuda and logits.ndim == 2 and num_samples == 1 and logits.stride(-1) == 1 and temperature >= 0:
+        if eligible:
             # one HIP kernel: argmax(logits / T + Gumbel noise) draws exactly from softmax(logits / T) -- what the softmax +
             # torch.multinomial chain below draws, in one pass over the logits instead of ~12 launches over [B, vocab]
-            return layer_ops.sample_tokens(logits, temperature)
-        if temperature == 0:
+            tok = layer_ops.sample_tokens(logits, temperature)
+        elif temperature == 0:
             assert logits.ndim == 2
-            return logits.argmax(dim=-1, keepdim=True).repeat_interleave(num_samples, dim=-1)
-        probs = nn.functional.softmax(logits / temperature, dim=-1)
-        return torch.multinomial(probs, num_samples=num_samples, replacement=True)
+            tok = logits.argmax(dim=-1, keepdim=True).repeat_interleave(num_samples, dim=-1)
+        else:
+            probs = nn.functional.softmax(logits / temperature, dim=-1)
+            tok = torch.multinomial(probs, num_samples=num_samples, replacement=True)
+        if not return_logprobs:
+            return tok
+        return tok, torch.log_softmax(src.float(), dim=-1).gather(-1, tok)
 
     def _positions(self, input_ids):
         shared_lens = self.get_shared_cache_len(input_ids.shape[0])
@@ -859,13 +875,19 @@ class HydragenLlamaForCausalLM(nn.Module):
                  top_p: Optional[float] = None, eos_token_id: Optional[int] = None, return_logits: bool = False,
                  shared_cache_op: str = SharedCacheOp.PRESERVE, disable_hydragen: bool = False,
                  disable_attention: bool = False, disable_hierarchy: bool = False,
-                 token_overrides: Optional[Tensor] = None):
+                 token_overrides: Optional[Tensor] = None, top_k: Optional[int] = None, min_p: Optional[float] = None,
+                 return_logprobs: bool = False):
+        """Sampling: top_k / top_p / min_p cut the UNSCALED softmax(logits) (the reference's top-p order; HF applies the
+        temperature first), then a token is drawn from softmax(logits / temperature) over the kept tokens.  Returns the
+        tokens [B, generated]; return_logits adds the per-step fp32 logits, return_logprobs the fp32 [B, generated]
+        log softmax(logits) of every returned token (unscaled, unfiltered): (out, logits, logprobs) in that order."""
         if not self.kv_cache_allocated:
             raise RuntimeError("call setup_caches() before generate()")
         if (input_ids is None) == (starting_logits is None):
             raise ValueError("pass exactly one of input_ids and starting_logits")
         if temperature < 0:
             raise ValueError(f"temperature must be non-negative, {temperature} is invalid")
+        sampling.check_filters(top_k, top_p, min_p)
         fan_out = num_return_sequences > 1
         flatten = disable_hierarchy or disable_hydragen  # the baselines keep the last level per sequence
         if shared_cache_op == SharedCacheOp.WIPE:
@@ -894,17 +916,23 @@ class HydragenLlamaForCausalLM(nn.Module):
             self.repeat_per_completion_cache_for_num_samples(unique[0].shape[0], num_return_sequences)
 
         try:
-            return self._decode(logits[:, -1], unique, num_return_sequences, max_new_tokens, temperature, top_p,
-                                eos_token_id, return_logits, token_overrides)
+            return self._decode(logits[:, -1], unique, num_return_sequences, max_new_tokens,
+                                dict(temperature=temperature, top_p=top_p, top_k=top_k, min_p=min_p),
+                                eos_token_id, return_logits, token_overrides, return_logprobs)
         finally:
             if shared_cache_op == SharedCacheOp.PRESERVE:
                 self.truncate_shared_caches(levels_before)
             self.model.set_disable_hydragen(False)
             self.model.set_disable_attention(False)
 
-    def _decode(self, prefill_logits, unique, fan, max_new_tokens, temperature, top_p, eos_token_id, return_logits,
-                token_overrides):
-        first = self.sample_from_logits(prefill_logits, temperature=temperature, num_samples=fan, top_p=top_p).reshape(-1, 1)
+    def _decode(self, prefill_logits, unique, fan, max_new_tokens, samp, eos_token_id, return_logits, token_overrides,
+                return_logprobs=False):
+        first = self.sample_from_logits(prefill_logits, num_samples=fan, return_logprobs=return_logprobs, **samp)
+        kept_lp = None
+        if return_logprobs:
+            first, lp = first
+            kept_lp = [lp.reshape(-1, 1)]
+        first = first.reshape(-1, 1)
         kept_logits = [prefill_logits.repeat_interleave(fan, 0)] if return_logits else None
         start = self.get_shared_cache_len(first.shape[0])[:, None]
         if unique is not None:
@@ -924,26 +952,38 @@ class HydragenLlamaForCausalLM(nn.Module):
                 order = self.seq_order_buf[: lens0.numel()]
                 order.copy_(_flash.longest_first(lens0))
         with _flash.seq_order(order, check=False):
-            return self._decode_steps(feed, start, tokens, kept_logits, done, graphed, max_new_tokens, temperature, top_p,
-                                      eos_token_id, return_logits, token_overrides)
+            return self._decode_steps(feed, start, tokens, kept_logits, done, graphed, max_new_tokens, samp, eos_token_id,
+                                      return_logits, token_overrides, kept_lp)
 
     schedule_longest_first = True  # (tests switch it off to compare: only the schedule may depend on it, never a token)
+    # top-k / top-p / min-p in the sampling kernel (hyd_sample_tokens_filtered); False: torch cuts + hyd_sample_tokens, the
+    # path before the kernel existed (tests switch it off to compare)
+    fused_sampling_filters = True
 
-    def _decode_steps(self, feed, start, tokens, kept_logits, done, graphed, max_new_tokens, temperature, top_p, eos_token_id,
-                      return_logits, token_overrides):
+    def _decode_steps(self, feed, start, tokens, kept_logits, done, graphed, max_new_tokens, samp, eos_token_id,
+                      return_logits, token_overrides, kept_lp=None):
+        # 16-bit logits straight into the sampler unless the caller wants them (fp32, as the reference returns them) or
+        # the cuts run in torch
+        raw = not return_logits and (self.fused_sampling_filters or not sampling.filters_active(
+            samp["top_k"], samp["top_p"], samp["min_p"]))
         for step in range(max_new_tokens - 1):
-            # 16-bit logits straight into the sampler unless the caller wants them (fp32, as the reference returns them)
-            logits = self(input_ids=feed, position_ids=start + step, use_graph=graphed,
-                          raw_logits=not return_logits and top_p is None)[:, -1]
+            logits = self(input_ids=feed, position_ids=start + step, use_graph=graphed, raw_logits=raw)[:, -1]
             if return_logits:
                 kept_logits.append(logits)
-            nxt = self.sample_from_logits(logits, temperature=temperature, top_p=top_p)
+            nxt = self.sample_from_logits(logits, return_logprobs=kept_lp is not None, **samp)
+            if kept_lp is not None:
+                nxt, lp = nxt
             if done is not None:
                 done = done | (nxt == eos_token_id)
                 if bool(done.all()):
                     break
             tokens.append(nxt)
+            if kept_lp is not None:
+                kept_lp.append(lp)
             feed = nxt if token_overrides is None else token_overrides[:, step + 1 : step + 2]
         out = torch.cat(tokens, dim=-1)
         check_collectives()  # no-op without the direct xGMI all-reduce; raises if a rank ever gave up on a peer
-        return (out, kept_logits) if return_logits else out
+        ret = (out, kept_logits) if return_logits else (out,)
+        if kept_lp is not None:
+            ret = ret + (torch.cat(kept_lp, dim=-1),)
+        return ret if len(ret) > 1 else out

@@ -44,8 +44,8 @@ extern "C" {
 /* the library is built with -fvisibility=hidden: these entry points are its whole dynamic symbol table */
 #define HYD_API __attribute__((visibility("default")))
 
-/* 0.5.0 also carries the fp8 unique-cache entry points (hyd_kv_quant, hyd_*_kvq, hyd_kv_quant_supported): they are new symbols
- * and a new struct only -- no existing struct, entry point or result changed -- so a caller built against 0.5.0 without them is
+/* 0.5.0 also carries the fp8 unique-cache entry points (hyd_kv_quant, hyd_*_kvq, hyd_kv_quant_supported) and the filtered
+ * sampler (hyd_sample_filter_params, hyd_sample_tokens_filtered): they are new symbols and new structs only -- no existing struct, entry point or result changed -- so a caller built against 0.5.0 without them is
  * unaffected and the version stays 500. */
 #define HYD_VERSION 500 /* 0.5.0: hyd_suffix_params.seq_order (schedule hint for ragged lengths); 0.4.0: hyd_add_rmsnorm, hyd_swiglu, hyd_sample_tokens (model-shell glue); 0.3.0: two-stream phases + hyd_decode_params.shared_max_workgroups, hyd_decode_two_stream_ok; 0.2.2: hyd_allreduce_params.timeout_log2_polls; 0.2.1: softmax_scale; 0.2.0: hyd_decode_params.phase, hyd_rope_params.max_pos, hyd_allreduce_* */
 #define HYD_MAX_LEVELS 8
@@ -303,6 +303,40 @@ typedef struct hyd_sample_params {
 } hyd_sample_params;
 
 HYD_API int hyd_sample_tokens(const hyd_sample_params* p, void* stream);
+
+/* hyd_sample_tokens with the usual sampling cuts, and the sampled token's log-probability.  For one row l (length n), with
+ * m = max(l) and p = softmax(l):
+ *   - the cuts act on the UNSCALED distribution softmax(l), not on softmax(l / temperature) (the reference's apply_top_p;
+ *     HF applies the temperature first, so results differ from HF when temperature != 1);
+ *   - top_k > 0 keeps every token whose logit is >= the k-th largest logit (ties kept; k >= n: no cut);
+ *   - top_p < 1 then keeps, among the top-k survivors renormalised, the tokens with l >= t*, t* the largest logit value whose
+ *     top set {l >= t*} holds >= top_p of their mass: the token that crosses top_p and every token tied with it are kept;
+ *   - min_p > 0 keeps p_i >= min_p * p_max, i.e. l_i - m >= ln(min_p) (the max always survives);
+ *   - -inf and NaN logits are never kept; a row without a finite logit gives token 0, kept 0 and a NaN log-prob;
+ *   - the draw is argmax(l / temperature + g) over the kept tokens with hyd_sample_tokens' noise g for the same
+ *     (seed, offset, row, column), bit for bit: with no cut set the tokens are hyd_sample_tokens' tokens; temperature 0 is
+ *     the argmax (lowest index on ties);
+ *   - logprobs[row] = l_tok - m - ln sum_j exp(l_j - m) (fp32): the log-probability under the unscaled, unfiltered
+ *     distribution, independent of temperature and cuts;
+ *   - masses are summed as fixed-point integers: tokens, kept counts and log-probs do not depend on the run or the launch.
+ * Rows longer than HYD_SAMPLE_FILTER_MAX_N give HYD_ERR_UNSUPPORTED; top_k < 0, top_p outside (0, 1] and min_p outside
+ * [0, 1] (NaN included) give HYD_ERR_BAD_ARG. */
+#define HYD_SAMPLE_FILTER_MAX_N (1 << 22)
+typedef struct hyd_sample_filter_params {
+    const void* logits;    /* [rows, n] HYD_F16 | HYD_BF16 | HYD_F32, row stride in elements        */
+    int64_t* out;          /* [rows] sampled token                                                  */
+    float* logprobs;       /* [rows] or NULL: log softmax(logits)[out] (unscaled, unfiltered)       */
+    int32_t* kept;         /* [rows] or NULL: number of tokens that survived the filters            */
+    int64_t row_stride;
+    uint64_t seed, offset; /* as hyd_sample_params                                                  */
+    int32_t rows, n, dtype;
+    float temperature;     /* >= 0                                                                  */
+    int32_t top_k;         /* 0 = off                                                               */
+    float top_p;           /* (0, 1]; 1 = off                                                       */
+    float min_p;           /* [0, 1]; 0 = off                                                       */
+} hyd_sample_filter_params;
+
+HYD_API int hyd_sample_tokens_filtered(const hyd_sample_filter_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * All-reduce(sum) of the tensor-parallel block output (hydragen/tp.py:83-87 after down_proj, :108-112 after

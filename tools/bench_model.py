@@ -24,6 +24,11 @@ ap.add_argument("--tunableop", default="", help="PyTorch TunableOp results file 
 ap.add_argument("--kv-dtype", default="bf16", help="unique KV cache dtype: bf16 (the model's) or fp8 (e4m3fn, unit scales); "
                 "a comma list (bf16,fp8) measures each in the same process, alternating per mode")
 ap.add_argument("--tp-slice", type=int, default=1, help="build rank 0's shard of an N-way tensor-parallel model (no collectives: per-GPU compute only)")
+ap.add_argument("--top-p", type=float, default=None, help="generate(top_p=...)")
+ap.add_argument("--top-k", type=int, default=None, help="generate(top_k=...)")
+ap.add_argument("--min-p", type=float, default=None, help="generate(min_p=...)")
+ap.add_argument("--filters", default="fused", help="fused (the sampling kernel), torch (the torch cuts + plain sampler: the "
+                "path before the kernel), or fused,torch to measure both in the same process, alternating per mode")
 a = ap.parse_args()
 
 if a.tunableop:
@@ -47,8 +52,14 @@ kv_dtypes = a.kv_dtype.split(",")
 assert all(k in KV_DTYPES for k in kv_dtypes), f"--kv-dtype {a.kv_dtype}: bf16, fp8"
 
 
-def run(mode, new, kv="bf16"):
-    kw = dict(disable_hydragen=(mode == "hydragen_noshared"), disable_attention=(mode == "noattention"))
+SAMPLING = dict(top_p=a.top_p, top_k=a.top_k, min_p=a.min_p)
+filter_paths = a.filters.split(",")
+assert all(f in ("fused", "torch") for f in filter_paths), f"--filters {a.filters}: fused, torch"
+
+
+def run(mode, new, kv="bf16", filters="fused"):
+    model.fused_sampling_filters = filters == "fused"
+    kw = dict(disable_hydragen=(mode == "hydragen_noshared"), disable_attention=(mode == "noattention"), **SAMPLING)
     uniq = a.new + (a.prefix if mode == "hydragen_noshared" else 0)   # synth.py:56-61
     model.setup_caches(max_unique_batch_size=a.batch, max_unique_seq_length=uniq + 16,
                        max_shared_batch_sizes=[1], max_shared_seq_lengths=[a.prefix], kv_cache_dtype=KV_DTYPES[kv])
@@ -59,11 +70,12 @@ def run(mode, new, kv="bf16"):
 
 for mode in a.modes.split(","):
     for kv in kv_dtypes:
-        run(mode, 4, kv)  # warm-up incl. graph capture
-        full = min(run(mode, a.new, kv) for _ in range(a.iters))
-        pre = min(run(mode, 1, kv) for _ in range(a.iters))
-        dec = full - pre
-        print(json.dumps({"mode": mode, "kv_dtype": kv, "model": a.model, "layers": cfg.num_hidden_layers, "batch": a.batch,
-                          "prefix": a.prefix, "new_tokens": a.new, "total_s": full, "prefill_s": pre,
-                          "decode_s": dec, "decode_tokens_per_s": a.batch * (a.new - 1) / dec,
-                          "ms_per_decode_step": dec / (a.new - 1) * 1e3, "graph": not a.no_graph}))
+        for fp in filter_paths:
+            run(mode, 4, kv, fp)  # warm-up incl. graph capture
+            full = min(run(mode, a.new, kv, fp) for _ in range(a.iters))
+            pre = min(run(mode, 1, kv, fp) for _ in range(a.iters))
+            dec = full - pre
+            print(json.dumps({"mode": mode, "kv_dtype": kv, **SAMPLING, "filters": fp, "model": a.model, "layers": cfg.num_hidden_layers, "batch": a.batch,
+                              "prefix": a.prefix, "new_tokens": a.new, "total_s": full, "prefill_s": pre,
+                              "decode_s": dec, "decode_tokens_per_s": a.batch * (a.new - 1) / dec,
+                              "ms_per_decode_step": dec / (a.new - 1) * 1e3, "graph": not a.no_graph}))
