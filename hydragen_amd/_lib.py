@@ -124,6 +124,17 @@ class SampleFilterParams(C.Structure):
 SAMPLE_FILTER_MAX_N = 1 << 22  # HYD_SAMPLE_FILTER_MAX_N
 
 
+class TokenLogprobParams(C.Structure):
+    _fields_ = [
+        ("logits", C.c_void_p), ("dtype", C.c_int32), ("n", C.c_int32), ("rows", C.c_int64), ("row_stride", C.c_int64),
+        ("targets", C.c_void_p), ("logprobs", C.c_void_p), ("greedy", C.c_void_p), ("top_n", C.c_int32), ("reserved", C.c_int32),
+        ("top_ids", C.c_void_p), ("top_logprobs", C.c_void_p),
+    ]
+
+
+TOP_LOGPROBS_MAX = 20  # HYD_TOP_LOGPROBS_MAX
+
+
 class KvQuant(C.Structure):
     _fields_ = [("kv_dtype", C.c_int32), ("reserved", C.c_int32), ("k_scale", C.c_void_p), ("v_scale", C.c_void_p)]
 
@@ -164,6 +175,7 @@ EXPORTS = {
     "hyd_rope_append_decode_kvq": (C.c_int, [C.POINTER(RopeParams), C.POINTER(KvQuant), C.c_void_p]),
     "hyd_kv_quant_supported": (C.c_int, [C.POINTER(SuffixParams), C.POINTER(KvQuant)]),
     "hyd_sample_tokens_filtered": (C.c_int, [C.POINTER(SampleFilterParams), C.c_void_p]),
+    "hyd_token_logprobs": (C.c_int, [C.POINTER(TokenLogprobParams), C.c_void_p]),
     "hyd_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }

@@ -704,6 +704,30 @@ int hyd_sample_tokens_filtered(const hyd_sample_filter_params* p, void* stream) 
     return rc ? fail(HYD_ERR_LAUNCH, "sample_filter kernel launch failed: hip error %d", rc) : HYD_OK;
 }
 
+int hyd_token_logprobs(const hyd_token_logprob_params* p, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    if (p->dtype != HYD_F16 && p->dtype != HYD_BF16 && p->dtype != HYD_F32) return fail(HYD_ERR_UNSUPPORTED, "dtype %d", p->dtype);
+    if (p->rows < 0 || p->rows > (1LL << 31) || p->n <= 0) return fail(HYD_ERR_BAD_ARG, "rows %lld, n %d", (long long)p->rows, p->n);
+    if (p->n > HYD_SAMPLE_FILTER_MAX_N) return fail(HYD_ERR_UNSUPPORTED, "n %d: rows of up to %d logits", p->n, HYD_SAMPLE_FILTER_MAX_N);
+    if (!p->logits || !p->targets || !p->logprobs || !p->greedy) return fail(HYD_ERR_BAD_ARG, "logits / targets / logprobs / greedy is null");
+    if (p->top_n < 0 || p->top_n > HYD_TOP_LOGPROBS_MAX) return fail(HYD_ERR_BAD_ARG, "top_n %d must be in [0, %d]", p->top_n, HYD_TOP_LOGPROBS_MAX);
+    if (p->top_n > 0 && (!p->top_ids || !p->top_logprobs)) return fail(HYD_ERR_BAD_ARG, "top_n %d needs top_ids and top_logprobs (null)", p->top_n);
+    if (p->row_stride < p->n) return fail(HYD_ERR_BAD_ARG, "row_stride %lld < n %d", (long long)p->row_stride, p->n);
+    const int esz = p->dtype == HYD_F32 ? 4 : 2;
+    if ((reinterpret_cast<uintptr_t>(p->logits) & (uintptr_t)(esz - 1)) != 0 || (reinterpret_cast<uintptr_t>(p->targets) & 7u) != 0 ||
+        (reinterpret_cast<uintptr_t>(p->logprobs) & 3u) != 0 || (reinterpret_cast<uintptr_t>(p->top_ids) & 7u) != 0 ||
+        (reinterpret_cast<uintptr_t>(p->top_logprobs) & 3u) != 0)
+        return fail(HYD_ERR_BAD_ARG, "logits / targets / logprobs / top_ids / top_logprobs is not aligned to its element size");
+    TokenLogprobArgs a;
+    memset(&a, 0, sizeof(a));
+    a.logits = p->logits; a.targets = p->targets; a.logprobs = p->logprobs; a.greedy = p->greedy;
+    a.top_ids = p->top_ids; a.top_logprobs = p->top_logprobs;
+    a.row_stride = p->row_stride; a.rows = p->rows; a.n = p->n; a.top_n = p->top_n;
+    a.vec_ok = ((reinterpret_cast<uintptr_t>(p->logits) & 15u) == 0 && p->row_stride % (16 / esz) == 0) ? 1 : 0;
+    const int rc = launch_token_logprob(a, p->dtype, static_cast<hipStream_t>(stream));
+    return rc ? fail(HYD_ERR_LAUNCH, "token_logprob kernel launch failed: hip error %d", rc) : HYD_OK;
+}
+
 // hyd_decode_params.single_launch_small: one uniform shared level that already counts as small (few query rows per
 // (group, kv head), short prefix), unique keys present, the same token strides in the shared and the unique tensors, and
 // so few keys in all that the call is launch latency.  Measured per graph-replayed call (tests/probes/single_launch_probe.py,

@@ -173,6 +173,19 @@ struct FilterArgs {  // sample_filter.hip: SampleArgs' draw over the tokens that
     int32_t vec_ok;      // rows are 16-byte aligned
 };
 
+struct TokenLogprobArgs {  // token_logprob.hip: log-probs of given tokens, greedy flags, top-N alternatives
+    const void* logits;
+    const int64_t* targets;
+    float* logprobs;
+    uint8_t* greedy;
+    int64_t* top_ids;       // [rows, top_n]; unused when top_n == 0
+    float* top_logprobs;
+    int64_t row_stride;     // elements
+    int64_t rows, row0;     // row0: first row of this launch
+    int32_t n, top_n;
+    int32_t vec_ok;         // rows are 16-byte aligned
+};
+
 // launchers (defined next to the kernels); return hipError_t as int
 int launch_prefix_w64(const PrefixArgs& a, int dtype, int D, bool causal, int grid, hipStream_t s);
 int launch_prefix_w64_f16(const PrefixArgs& a, int D, bool causal, int grid, hipStream_t s);  // prefix_attn_w64_f16.hip
@@ -181,6 +194,7 @@ int launch_add_rmsnorm(const NormArgs& a, int dtype, hipStream_t s);
 int launch_swiglu(const SwigluArgs& a, int dtype, hipStream_t s);
 int launch_sample(const SampleArgs& a, int dtype, hipStream_t s);
 int launch_sample_filter(const FilterArgs& a, int dtype, hipStream_t s);  // sample_filter.hip
+int launch_token_logprob(const TokenLogprobArgs& a, int dtype, hipStream_t s);  // token_logprob.hip
 int launch_suffix(const SuffixArgs& a, int dtype, int D, hipStream_t s);
 bool suffix_gqa_eligible(const SuffixArgs& a, int D, bool any_shape);
 bool suffix_fp8_eligible(const SuffixArgs& a, int D);                                 // suffix_attn_fp8.hip, shapes only

@@ -1,4 +1,4 @@
-"""Python face of `hyd_add_rmsnorm` / `hyd_swiglu` / `hyd_sample_tokens[_filtered]` (include/hydragen_hip.h): the elementwise glue of the decoder layer
+"""Python face of `hyd_add_rmsnorm` / `hyd_swiglu` / `hyd_sample_tokens[_filtered]` / `hyd_token_logprobs` (include/hydragen_hip.h): the elementwise glue of the decoder layer
 around the attention block -- residual add + RMSNorm (/root/reference/hydragen/llama.py:615-631 with transformers'
 LlamaRMSNorm, llama.py:605-608,656) and the SwiGLU gate (transformers' LlamaMLP, llama.py:2,604) -- each as one
 HIP kernel instead of two torch launches."""
@@ -15,6 +15,7 @@ from . import _lib
 from ._lib import AddRmsnormParams, SwigluParams
 from .flash import _dtype_code, _require_gpu, _stream
 from .sampling import check_filters, filters_active
+from .scoring import check_top_n, token_logprobs_reference
 
 
 def supported(x: Tensor, n_max: int = 16384) -> bool:
@@ -137,3 +138,40 @@ def sample_tokens_filtered(logits: Tensor, temperature: float, key: Optional[tup
     p.temperature = float(temperature)
     _lib.check(lib.hyd_sample_tokens_filtered(C.byref(p), _stream()))
     return out, logprobs, kept
+
+
+def token_logprobs(logits: Tensor, targets: Tensor, top_n: int = 0):
+    """hyd_token_logprobs, one launch: [R, V] logits (fp16 / bf16 / fp32, unit last stride) and [R] int64 targets ->
+    (logprobs [R] f32, greedy [R] bool, top_ids [R, top_n] int64, top_logprobs [R, top_n] f32); hydragen_amd/scoring.py states
+    the definition.  Targets outside [0, V) mark padding rows (NaN, not greedy).  Shapes and dtypes are checked on the host;
+    nothing synchronises.  CPU tensors take scoring.token_logprobs_reference."""
+    top_n = check_top_n(top_n)
+    if logits.ndim != 2 or logits.shape[1] <= 0 or logits.stride(1) != 1:
+        raise ValueError(f"logits must be [R, V] with V > 0 and a unit last stride, got {tuple(logits.shape)} / {logits.stride()}")
+    if logits.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise ValueError(f"logits dtype {logits.dtype}: float16, bfloat16 or float32")
+    if targets.shape != (logits.shape[0],) or targets.dtype != torch.int64 or targets.device != logits.device:
+        raise ValueError(f"targets must be [{logits.shape[0]}] int64 on {logits.device}, got {tuple(targets.shape)} {targets.dtype} "
+                         f"on {targets.device}")
+    if logits.shape[1] > _lib.SAMPLE_FILTER_MAX_N:
+        raise ValueError(f"rows of {logits.shape[1]} logits: at most {_lib.SAMPLE_FILTER_MAX_N}")
+    if not logits.is_cuda:
+        return token_logprobs_reference(logits, targets, top_n)
+    _require_gpu(logits)
+    lib = _lib.load()
+    rows, n = logits.shape
+    dev = logits.device
+    lp = torch.empty((rows,), dtype=torch.float32, device=dev)
+    greedy = torch.empty((rows,), dtype=torch.uint8, device=dev)
+    top_ids = torch.empty((rows, top_n), dtype=torch.int64, device=dev)
+    top_lp = torch.empty((rows, top_n), dtype=torch.float32, device=dev)
+    if rows > 0:
+        t = targets.contiguous()
+        p = _lib.TokenLogprobParams()
+        p.logits, p.dtype, p.n, p.rows = logits.data_ptr(), _HYD_F32 if logits.dtype == torch.float32 else _dtype_code(logits), n, rows
+        p.row_stride = logits.stride(0) if rows > 1 else n
+        p.targets, p.logprobs, p.greedy, p.top_n = t.data_ptr(), lp.data_ptr(), greedy.data_ptr(), top_n
+        if top_n:
+            p.top_ids, p.top_logprobs = top_ids.data_ptr(), top_lp.data_ptr()
+        _lib.check(lib.hyd_token_logprobs(C.byref(p), _stream()))
+    return lp, greedy.view(torch.bool), top_ids, top_lp

@@ -23,7 +23,7 @@ from typing import List, Optional, Union
 import torch
 from torch import Tensor, nn
 
-from . import layer_ops, placement, sampling
+from . import layer_ops, placement, sampling, scoring
 from .attention import hydragen_attention
 from . import flash as _flash
 from .flash import flash_attention, flash_attention_seqlen
@@ -876,11 +876,14 @@ class HydragenLlamaForCausalLM(nn.Module):
                  shared_cache_op: str = SharedCacheOp.PRESERVE, disable_hydragen: bool = False,
                  disable_attention: bool = False, disable_hierarchy: bool = False,
                  token_overrides: Optional[Tensor] = None, top_k: Optional[int] = None, min_p: Optional[float] = None,
-                 return_logprobs: bool = False):
+                 return_logprobs: bool = False, top_logprobs: int = 0):
         """Sampling: top_k / top_p / min_p cut the UNSCALED softmax(logits) (the reference's top-p order; HF applies the
         temperature first), then a token is drawn from softmax(logits / temperature) over the kept tokens.  Returns the
         tokens [B, generated]; return_logits adds the per-step fp32 logits, return_logprobs the fp32 [B, generated]
-        log softmax(logits) of every returned token (unscaled, unfiltered): (out, logits, logprobs) in that order."""
+        log softmax(logits) of every returned token (unscaled, unfiltered): (out, logits, logprobs) in that order.
+        top_logprobs = N > 0 (needs return_logprobs) also returns, for every returned token, the N best alternatives of that
+        step's distribution (hyd_token_logprobs, hydragen_amd/scoring.py): (..., top_ids [B, generated, N] int64,
+        top_logprobs [B, generated, N] f32) after the other return values."""
         if not self.kv_cache_allocated:
             raise RuntimeError("call setup_caches() before generate()")
         if (input_ids is None) == (starting_logits is None):
@@ -888,6 +891,9 @@ class HydragenLlamaForCausalLM(nn.Module):
         if temperature < 0:
             raise ValueError(f"temperature must be non-negative, {temperature} is invalid")
         sampling.check_filters(top_k, top_p, min_p)
+        top_n = scoring.check_top_n(top_logprobs)
+        if top_n and not return_logprobs:
+            raise ValueError("top_logprobs needs return_logprobs=True")
         fan_out = num_return_sequences > 1
         flatten = disable_hierarchy or disable_hydragen  # the baselines keep the last level per sequence
         if shared_cache_op == SharedCacheOp.WIPE:
@@ -918,20 +924,161 @@ class HydragenLlamaForCausalLM(nn.Module):
         try:
             return self._decode(logits[:, -1], unique, num_return_sequences, max_new_tokens,
                                 dict(temperature=temperature, top_p=top_p, top_k=top_k, min_p=min_p),
-                                eos_token_id, return_logits, token_overrides, return_logprobs)
+                                eos_token_id, return_logits, token_overrides, return_logprobs, top_n)
         finally:
             if shared_cache_op == SharedCacheOp.PRESERVE:
                 self.truncate_shared_caches(levels_before)
             self.model.set_disable_hydragen(False)
             self.model.set_disable_attention(False)
 
+    # ---- scoring ----------------------------------------------------------------------------------------
+    score_chunk_bytes = 1 << 30  # lm_head output per chunk of score()'s scored rows (tests shrink it)
+    score_gemm_rows = 256        # rows per lm_head GEMM in score(): chunks are multiples of it
+
+    @torch.no_grad()
+    def score(self, input_ids: Union[Tensor, list[Tensor]], target_lens: Union[Tensor, list[int]],
+              seq_lens: Optional[Union[Tensor, list[Tensor]]] = None, top_logprobs: int = 0,
+              shared_cache_op: str = SharedCacheOp.PRESERVE, disable_hydragen: bool = False) -> scoring.ScoreResult:
+        """Log-likelihood of given continuations (lm-eval `loglikelihood`, multiple choice, reranking).  input_ids / seq_lens follow
+        generate()'s level contract with num_return_sequences == 1: every level but the last is shared (append_shared), the last
+        [B, Lu] (right-padded) is each sequence's own.  The last target_lens[b] real tokens of sequence b's own level are scored,
+        each under the distribution that precedes it; when target_lens[b] == its length, the first target's distribution is
+        the innermost shared level's last-position logits (shared row b // (B / sb)), so that level must be given in this call.
+        The decoder stack runs once over the unique level; lm_head and hyd_token_logprobs run on chunks of the scored rows
+        (score_chunk_bytes of logits each), never on [B, Lu, V].  shared_cache_op and disable_hydragen act as in generate().
+        The unique cache is overwritten; a captured decode graph is neither used nor invalidated.  Every argument and
+        capacity is checked on the host before the first launch."""
+        if not self.kv_cache_allocated:
+            raise RuntimeError("call setup_caches() before score()")
+        top_n = scoring.check_top_n(top_logprobs)
+        shared, unique = self._prompt_levels(input_ids, seq_lens, False, True)
+        if unique is None:
+            raise ValueError("score() needs at least one prompt level: the last one holds the scored tokens")
+        uids, ulens = unique
+        B, Lu = uids.shape
+        ul = [int(x) for x in ulens.reshape(-1).tolist()]
+        tl = [int(x) for x in torch.as_tensor(target_lens).reshape(-1).tolist()]
+        if len(tl) != B or len(ul) != B:
+            raise ValueError(f"target_lens has {len(tl)} entries and seq_lens {len(ul)} for a batch of {B}")
+        bad = [b for b in range(B) if not 1 <= tl[b] <= ul[b] or ul[b] > Lu]
+        if bad:
+            b = bad[0]
+            raise ValueError(f"sequence {b}: target_lens {tl[b]} must be in [1, {ul[b]}] (its unique length, <= {Lu})")
+        levels_before = 0 if shared_cache_op == SharedCacheOp.WIPE else self.get_num_used_shared_caches()
+        depth = levels_before + len(shared) + 1
+        if disable_hydragen and (depth != 2 or (shared and shared[0][0].shape[0] != 1)):
+            raise ValueError("disable_hydragen compares against ONE shared prompt: exactly two levels, the first of batch 1")
+        if any(t == u for t, u in zip(tl, ul)):
+            if depth == 1:
+                raise ValueError("target_lens == the unique length scores the first token with no context: give a shared level")
+            if not shared:
+                raise ValueError("target_lens == the unique length needs the innermost shared level's logits: pass that level in "
+                                 "this call")
+        kv = self.model.layers[0].self_attn.kv_cache
+        if levels_before + len(shared) > kv.get_num_total_shared_caches():
+            raise ValueError(f"{levels_before + len(shared)} shared levels, the caches hold {kv.get_num_total_shared_caches()}")
+        shared_len = torch.zeros(B, dtype=torch.long)
+        if levels_before:
+            shared_len += self.get_shared_cache_len(B).cpu()
+        for i, (ids, lens) in enumerate(shared):
+            sc = kv.shared_caches[levels_before + i]
+            if B % ids.shape[0] or ids.shape[0] > sc.max_batch_size or ids.shape[1] > sc.max_sequence_length:
+                raise ValueError(f"shared level {levels_before + i}: [{ids.shape[0]}, {ids.shape[1]}] against a batch of {B} and a "
+                                 f"cache of [{sc.max_batch_size}, {sc.max_sequence_length}]")
+            shared_len += lens.reshape(-1).cpu().long().repeat_interleave(B // ids.shape[0])
+        rows, room = kv.per_completion_k_cache.shape[:2]
+        if B > rows:
+            raise ValueError(f"batch {B} exceeds the unique cache's {rows} sequences")
+        need = Lu + (int(shared_len.max()) if disable_hydragen else 0)
+        if need > room:
+            raise ValueError(f"unique cache holds {room} tokens per sequence, scoring needs {need}")
+        last_pos = int((shared_len + Lu - 1).max())
+        if last_pos >= self.config.max_position_embeddings:
+            raise ValueError(f"position {last_pos} exceeds max_position_embeddings = {self.config.max_position_embeddings}")
+
+        if shared_cache_op == SharedCacheOp.WIPE:
+            self.empty_shared_cache()
+        levels_before = self.get_num_used_shared_caches()
+        self.model.set_disable_attention(False)
+        try:
+            shared_logits = None
+            for ids, lens in shared:
+                shared_logits = self.append_shared(ids, lens)
+            if disable_hydragen:
+                self.model.set_disable_hydragen(True)
+                if self.get_num_used_shared_caches() > 0:
+                    self.model.copy_shared_cache_to_unique(B)
+            self.set_mode(AttentionMode.UNIQUE_PREFILL)
+            hidden = self.model(input_ids=uids, position_ids=self._positions(uids))
+            return self._score_rows(hidden, shared_logits, uids, tl, ul, top_n)
+        finally:
+            if shared_cache_op == SharedCacheOp.PRESERVE:
+                self.truncate_shared_caches(levels_before)
+            self.model.set_disable_hydragen(False)
+
+    def _score_rows(self, hidden, shared_logits, uids, tl, ul, top_n):
+        """Log-probs of the targets from the unique level's hidden states [B, Lu, H] (target at unique position p >= 1: the
+        hidden state at p - 1) and the innermost shared level's last-position logits [sb, 1, V] (p == 0)."""
+        B, Lu = uids.shape
+        dev = uids.device
+        T = max(tl)
+        tl_t, ul_t = torch.tensor(tl, device=dev), torch.tensor(ul, device=dev)
+        j = torch.arange(T, device=dev)
+        pos = ul_t[:, None] - tl_t[:, None] + j[None, :]  # unique position of every target
+        live = j[None, :] < tl_t[:, None]
+        tgt = uids.long().gather(1, pos.clamp(0, Lu - 1))
+        lp = torch.full((B, T), float("nan"), dtype=torch.float32, device=dev)
+        greedy = torch.zeros((B, T), dtype=torch.bool, device=dev)
+        top_ids = torch.full((B, T, top_n), -1, dtype=torch.int64, device=dev)
+        top_lp = torch.full((B, T, top_n), float("-inf"), dtype=torch.float32, device=dev)
+        V = self.lm_head.weight.shape[0]
+
+        G = self.score_gemm_rows
+
+        def run(bi, ji, logits_of, esz):
+            per = max(G, self.score_chunk_bytes // (V * esz) // G * G)
+            for s in range(0, bi.numel(), per):
+                b, jj = bi[s : s + per], ji[s : s + per]
+                o = layer_ops.token_logprobs(logits_of(b, jj), tgt[b, jj], top_n)
+                lp[b, jj], greedy[b, jj] = o[0], o[1]
+                if top_n:
+                    top_ids[b, jj], top_lp[b, jj] = o[2], o[3]
+
+        hb, hj = (live & (pos >= 1)).nonzero(as_tuple=True)
+        def head(b, jj):
+            # the 16-bit lm_head output goes straight into the kernel.  The GEMM always sees blocks of G rows (the last one
+            # zero-padded): a row's logits come from the same GEMM shape whatever the chunk size and the batch
+            h = hidden[b, pos[b, jj] - 1]
+            r = h.shape[0]
+            h = torch.cat([h, h.new_zeros(((-r) % G, h.shape[1]))]) if r % G else h
+            out = h.new_empty((h.shape[0], V))
+            for k in range(0, h.shape[0], G):
+                torch.mm(h[k : k + G], self.lm_head.weight.t(), out=out[k : k + G])
+            return out[:r]
+
+        run(hb, hj, head, self.lm_head.weight.element_size())
+        sb_, sj = (live & (pos == 0)).nonzero(as_tuple=True)
+        if sb_.numel():
+            sh = shared_logits[:, -1]
+            rep = B // sh.shape[0]
+            run(sb_, sj, lambda b, jj: sh[b // rep], sh.element_size())
+        return scoring.ScoreResult(
+            logprobs=lp, token_greedy=greedy, sum=torch.where(live, lp.double(), torch.zeros_like(lp, dtype=torch.float64)).sum(1),
+            is_greedy=(greedy | ~live).all(1), top_ids=top_ids if top_n else None, top_logprobs=top_lp if top_n else None)
+
     def _decode(self, prefill_logits, unique, fan, max_new_tokens, samp, eos_token_id, return_logits, token_overrides,
-                return_logprobs=False):
+                return_logprobs=False, top_n=0):
         first = self.sample_from_logits(prefill_logits, num_samples=fan, return_logprobs=return_logprobs, **samp)
-        kept_lp = None
+        kept_lp = kept_top = None
         if return_logprobs:
             first, lp = first
             kept_lp = [lp.reshape(-1, 1)]
+        if top_n:
+            # the alternatives do not depend on the drawn token: once over the leaf_batch prefill rows, repeated per sample
+            rows = prefill_logits if prefill_logits.stride(-1) == 1 else prefill_logits.contiguous()
+            none = torch.full((rows.shape[0],), -1, dtype=torch.int64, device=rows.device)
+            _, _, ids, tlp = layer_ops.token_logprobs(rows, none, top_n)
+            kept_top = [(ids.repeat_interleave(fan, 0)[:, None], tlp.repeat_interleave(fan, 0)[:, None])]
         first = first.reshape(-1, 1)
         kept_logits = [prefill_logits.repeat_interleave(fan, 0)] if return_logits else None
         start = self.get_shared_cache_len(first.shape[0])[:, None]
@@ -953,7 +1100,7 @@ class HydragenLlamaForCausalLM(nn.Module):
                 order.copy_(_flash.longest_first(lens0))
         with _flash.seq_order(order, check=False):
             return self._decode_steps(feed, start, tokens, kept_logits, done, graphed, max_new_tokens, samp, eos_token_id,
-                                      return_logits, token_overrides, kept_lp)
+                                      return_logits, token_overrides, kept_lp, kept_top)
 
     schedule_longest_first = True  # (tests switch it off to compare: only the schedule may depend on it, never a token)
     # top-k / top-p / min-p in the sampling kernel (hyd_sample_tokens_filtered); False: torch cuts + hyd_sample_tokens, the
@@ -961,7 +1108,7 @@ class HydragenLlamaForCausalLM(nn.Module):
     fused_sampling_filters = True
 
     def _decode_steps(self, feed, start, tokens, kept_logits, done, graphed, max_new_tokens, samp, eos_token_id,
-                      return_logits, token_overrides, kept_lp=None):
+                      return_logits, token_overrides, kept_lp=None, kept_top=None):
         # 16-bit logits straight into the sampler unless the caller wants them (fp32, as the reference returns them) or
         # the cuts run in torch
         raw = not return_logits and (self.fused_sampling_filters or not sampling.filters_active(
@@ -980,10 +1127,15 @@ class HydragenLlamaForCausalLM(nn.Module):
             tokens.append(nxt)
             if kept_lp is not None:
                 kept_lp.append(lp)
+            if kept_top is not None:  # the same logits the sampler read; the sampled token's log-prob stays the sampler's
+                _, _, ids, tlp = layer_ops.token_logprobs(logits, nxt[:, 0], kept_top[0][0].shape[-1])
+                kept_top.append((ids[:, None], tlp[:, None]))
             feed = nxt if token_overrides is None else token_overrides[:, step + 1 : step + 2]
         out = torch.cat(tokens, dim=-1)
         check_collectives()  # no-op without the direct xGMI all-reduce; raises if a rank ever gave up on a peer
         ret = (out, kept_logits) if return_logits else (out,)
         if kept_lp is not None:
             ret = ret + (torch.cat(kept_lp, dim=-1),)
+        if kept_top is not None:
+            ret = ret + (torch.cat([i for i, _ in kept_top], dim=1), torch.cat([t for _, t in kept_top], dim=1))
         return ret if len(ret) > 1 else out

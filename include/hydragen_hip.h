@@ -45,7 +45,8 @@ extern "C" {
 #define HYD_API __attribute__((visibility("default")))
 
 /* 0.5.0 also carries the fp8 unique-cache entry points (hyd_kv_quant, hyd_*_kvq, hyd_kv_quant_supported) and the filtered
- * sampler (hyd_sample_filter_params, hyd_sample_tokens_filtered): they are new symbols and new structs only -- no existing struct, entry point or result changed -- so a caller built against 0.5.0 without them is
+ * sampler (hyd_sample_filter_params, hyd_sample_tokens_filtered) and the scoring entry point (hyd_token_logprob_params,
+ * hyd_token_logprobs): they are new symbols and new structs only -- no existing struct, entry point or result changed -- so a caller built against 0.5.0 without them is
  * unaffected and the version stays 500. */
 #define HYD_VERSION 500 /* 0.5.0: hyd_suffix_params.seq_order (schedule hint for ragged lengths); 0.4.0: hyd_add_rmsnorm, hyd_swiglu, hyd_sample_tokens (model-shell glue); 0.3.0: two-stream phases + hyd_decode_params.shared_max_workgroups, hyd_decode_two_stream_ok; 0.2.2: hyd_allreduce_params.timeout_log2_polls; 0.2.1: softmax_scale; 0.2.0: hyd_decode_params.phase, hyd_rope_params.max_pos, hyd_allreduce_* */
 #define HYD_MAX_LEVELS 8
@@ -337,6 +338,36 @@ typedef struct hyd_sample_filter_params {
 } hyd_sample_filter_params;
 
 HYD_API int hyd_sample_tokens_filtered(const hyd_sample_filter_params* p, void* stream);
+
+/* Log-probabilities of GIVEN tokens (scoring, teacher forcing) and the top-N alternatives of every row.  For one row l (length n)
+ * and its target token t, with the valid logits those that are neither NaN nor -inf and m = their max:
+ *   - logprobs[row] = l_t - m - ln sum_j exp(l_j - m) over the valid logits (fp32), with hyd_sample_tokens_filtered's fixed-point
+ *     masses and closing expression: for any row and token, the same bits as that entry point's log-prob of the token;
+ *   - greedy[row] = 1 iff t is the LOWEST-index maximum of the valid logits (torch.argmax's tie rule; what hyd_sample_tokens
+ *     picks at temperature 0), else 0;
+ *   - top_ids[row, :top_n] / top_logprobs[row, :top_n]: the top_n largest valid logits ordered by (value descending, index
+ *     ascending) and their log-probs (same expression); a row with fewer valid logits pads with id -1 and -inf;
+ *   - t < 0 or t >= n: logprob NaN, greedy 0, and no load at t (the caller marks padding this way); l_t NaN: NaN; l_t -inf:
+ *     -inf; a row without a valid logit: NaN, greedy 0, top-N all padding;
+ *   - masses are summed as fixed-point integers: a row's outputs do not depend on the run, the launch geometry or the other
+ *     rows of the launch.
+ * Null logits / targets / logprobs / greedy, rows outside [0, 2^31], n <= 0, row_stride < n, top_n outside
+ * [0, HYD_TOP_LOGPROBS_MAX], top_n > 0 without top_ids and top_logprobs, and misaligned pointers give HYD_ERR_BAD_ARG; a bad
+ * dtype and n > HYD_SAMPLE_FILTER_MAX_N give HYD_ERR_UNSUPPORTED. */
+#define HYD_TOP_LOGPROBS_MAX 20
+typedef struct hyd_token_logprob_params {
+    const void* logits;    /* [rows, n] HYD_F16 | HYD_BF16 | HYD_F32, row stride in elements           */
+    int32_t dtype, n;
+    int64_t rows, row_stride;
+    const int64_t* targets; /* [rows] token to score; outside [0, n): padding                          */
+    float* logprobs;       /* [rows]                                                                   */
+    uint8_t* greedy;       /* [rows] 0 / 1                                                             */
+    int32_t top_n, reserved;
+    int64_t* top_ids;      /* [rows, top_n] or NULL when top_n == 0                                    */
+    float* top_logprobs;   /* [rows, top_n] or NULL when top_n == 0                                    */
+} hyd_token_logprob_params;
+
+HYD_API int hyd_token_logprobs(const hyd_token_logprob_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * All-reduce(sum) of the tensor-parallel block output (hydragen/tp.py:83-87 after down_proj, :108-112 after
