@@ -1,4 +1,5 @@
-// Device-side pieces of the suffix-pass kernels (suffix_attn.hip): 16-bit widening, uniform pointers, online-softmax state merges, the output-row epilogue.
+// Device-side pieces of the suffix-pass kernels (suffix_attn.hip, suffix_attn_fp8.hip, suffix_rows.h): 16-bit widening, uniform pointers,
+// the chunk core (online-softmax step, P.V accumulate), online-softmax state merges, the output-row epilogue.
 #pragma once
 #include "hyd_kernels.h"
 
@@ -23,6 +24,44 @@ __device__ __forceinline__ gchar_p uniform_ptr(const char* p) {
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
     const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
     return (gchar_p)(((uint64_t)hi << 32) | lo);
+}
+
+// The chunk core every suffix kernel of suffix_attn.hip / suffix_attn_fp8.hip shares (base-2 domain).
+// softmax_step: one online-softmax update over the N scores of a key chunk -- s[] comes in as scores (-inf = masked key) and
+// leaves as probabilities relative to the new running maximum; (m, l, acc) are rescaled to it.  GUARD: the chunk may hold no
+// valid key at all while m is still -inf (the one-unit-per-wave kernel: a lane group's keys can all lie past the length);
+// the token-row and packed kernels only process chunks that start with a valid key and leave the test out.
+template <bool GUARD, int N>
+__device__ __forceinline__ void softmax_step(float (&s)[N], float& m, float& l, float (&acc)[8]) {
+    float cmax = s[0];
+#pragma unroll
+    for (int u = 1; u < N; ++u) cmax = fmaxf(cmax, s[u]);
+    const float mnew = fmaxf(m, cmax);
+    const float ms = (GUARD && mnew == -INFINITY) ? 0.f : mnew;
+    const float alpha = fast_exp2(m - ms);
+    float ps = 0.f;
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+        s[u] = fast_exp2(s[u] - ms);  // p
+        ps += s[u];
+    }
+    l = l * alpha + ps;
+    m = mnew;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] *= alpha;
+}
+// pv_accumulate: acc += p * (the 8 floats of V this lane holds for one key)
+__device__ __forceinline__ void pv_accumulate(float p, const float (&vf)[8], float (&acc)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = __builtin_fmaf(p, vf[j], acc[j]);
+}
+
+// shapes only: every byte offset a lane forms inside ONE sequence's cache (token row + head, the larger of K's and V's
+// strides) fits 32 bits -- the condition of the wave-uniform base + 32-bit lane offset addressing of the lane-group kernels
+inline bool cache_span_fits_32bit(const SuffixArgs& a, int elem_bytes) {
+    const int64_t span = (int64_t)a.kv_len * (a.k_ts > a.v_ts ? a.k_ts : a.v_ts) * elem_bytes +
+                         (int64_t)a.Hkv * (a.k_hs > a.v_hs ? a.k_hs : a.v_hs) * elem_bytes;
+    return span < ((int64_t)1 << 31);
 }
 
 // merge (m, l, acc) state pairs; all values in base-2 domain

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where the dominant kernel's time goes at C2 (development tool, GPU box):
 
-    python tools/suffix_gap.py [--iters 30] [--legs sweep,instep,occ]
+    python tools/suffix_gap.py [--iters 30] [--legs sweep,instep,rows,capacity,interleave,stride]
 
 `sweep`   suffix pass alone over S, with and without the fused merge epilogue (n_partials 1 / 0), on (i) a placed
           128-row K|V arena (the bench's: 1 MiB between sequences), (ii) the SAME sequences in a 2176-row arena
@@ -9,8 +9,9 @@
           from "merge epilogue".
 `instep`  HYD_PHASE_UNIQUE timed alone (back to back; one by one behind an idle gap) against the same launch behind
           HYD_PHASE_SHARED (events as bench.py places them) and behind an 8 MiB write burst alone.
-`occ`     occupancy A/B of the ablation library (HYDRAGEN_HIP_LIB=build_probe/libhydragen_abl.so): HYD_SUFFIX_OCC =
-          <key iterations in flight><waves per SIMD>.
+`rows`, `capacity`, `interleave`, `stride`
+          kernel A/B of the ablation library (HYDRAGEN_HIP_LIB=build_probe/libhydragen_abl.so) over the --rows variants:
+          token-row kernel on / off (HYD_SUFFIX_ROWS), optionally followed by `;NAME=value` development switches.
 All times are HIP events on the launch stream; every figure is min / median of `iters` launches."""
 import argparse
 import ctypes as C
@@ -70,9 +71,8 @@ def main():
     ap.add_argument("--shape", default="", help="B,Hq,Hkv instead of C2's 1024,32,32 (legs that take the suffix pass alone: interleave, capacity, stride)")
     ap.add_argument("--caps", default="128,144", help="interleave leg: cache rows")
     ap.add_argument("--layouts", default="2,B;B,2", help="interleave leg: K|V arena layouts, of 2,B  B,2  B,r,2  B,r,H,2 (semicolon-separated)")
-    ap.add_argument("--legs", default="sweep,instep,occ")
-    ap.add_argument("--occ", default="0,48,38,28,65,84")
-    ap.add_argument("--rows", default="0:8:1,1:8:1,1:8:0,1:4:1,1:4:0")
+    ap.add_argument("--legs", default="sweep,instep")
+    ap.add_argument("--rows", default="0,1", help="variants: HYD_SUFFIX_ROWS value[;NAME=value...], e.g. '0,1,1;HYD_ROWS_TS=1'")
     ap.add_argument("--S", default="16,32,64,128")
     a = ap.parse_args()
     global B, Hq, Hkv
@@ -86,7 +86,7 @@ def main():
     out = torch.empty_like(q)
     pout = torch.randn(B, 1, Hq, D, device=DEV, dtype=dt, generator=g)
     plse = torch.randn(B, 1, Hq, device=DEV, dtype=torch.float32, generator=g)
-    if set(legs) & {"sweep", "instep", "occ", "rows"}:
+    if set(legs) & {"sweep", "instep", "rows"}:
         arenas, rep = placement.place_kv_arenas(1, [B, 128, Hkv, D], dt, DEV, Hq, zero=False)
         a128 = arenas[0]
         a128.normal_()
@@ -166,28 +166,21 @@ def main():
     _extra_keys = set()
 
     def set_variant(v):
-        """occ leg: HYD_SUFFIX_OCC value; rows legs: 'ROWS:UT:ROT[:PIPE]' (token-row kernel on/off, tokens in flight, rotated start, pipelined form)."""
-        for k in ("HYD_SUFFIX_OCC", "HYD_SUFFIX_ROWS", "HYD_ROWS_UT", "HYD_ROWS_ROT", "HYD_ROWS_PIPE"):
-            os.environ.pop(k, None)
+        """'ROWS[;NAME=value;...]': token-row kernel on / off (HYD_SUFFIX_ROWS), then further development switches of the ablation library (e.g. HYD_ROWS_TS=1)."""
+        os.environ.pop("HYD_SUFFIX_ROWS", None)
         for k in [k for k in os.environ if k in _extra_keys]:
             os.environ.pop(k)
         if v is None:
             return
-        if ";" in v:  # 'ROWS:UT:ROT:PIPE;NAME=value;...': further development switches of the ablation library (e.g. HYD_ROWS_TS=1)
-            v, *extra = v.split(";")
-            for kv in extra:
-                k_, val = kv.split("=")
-                os.environ[k_] = val
-                _extra_keys.add(k_)
-        if ":" in v:
-            r_, u_, o_, *p_ = v.split(":")  # optional 4th field (HYD_ROWS_PIPE): 0 = the first form (loads, then arithmetic), 1 / 2 = blind K requests, 3 = the product form
-            os.environ.update(HYD_SUFFIX_ROWS=r_, HYD_ROWS_UT=u_, HYD_ROWS_ROT=o_, HYD_ROWS_PIPE=p_[0] if p_ else "0")
-        else:
-            os.environ.update(HYD_SUFFIX_ROWS="0", HYD_SUFFIX_OCC=v)
+        v, *extra = v.split(";")
+        for kv in extra:
+            k_, val = kv.split("=")
+            os.environ[k_] = val
+            _extra_keys.add(k_)
+        os.environ["HYD_SUFFIX_ROWS"] = v
 
-    for leg, default in (("occ", a.occ), ("rows", a.rows)):
-        if leg not in legs:
-            continue
+    if "rows" in legs:
+        leg, default = "rows", a.rows
         print(f"\n## {leg} A/B (ablation library only; first column = reference) -- unique phase b2b, us min / median; [max |diff| against the first column's output]")
         vals = default.split(",")
         print("| S | " + " | ".join(vals) + " |")
