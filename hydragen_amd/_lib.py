@@ -122,6 +122,33 @@ class SampleFilterParams(C.Structure):
 
 
 SAMPLE_FILTER_MAX_N = 1 << 22  # HYD_SAMPLE_FILTER_MAX_N
+SAMPLE_MAX_CONTEXT = HYD_MAX_LEVELS + 1  # HYD_SAMPLE_MAX_CONTEXT
+SAMPLE_BIAS_MAX = 1024  # HYD_SAMPLE_BIAS_MAX
+SAMPLE_GEN_MAX = 2048  # HYD_SAMPLE_GEN_MAX
+
+
+class TokenBitmap(C.Structure):
+    _fields_ = [("bits", C.c_void_p), ("rows_per_group", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SamplePenaltyParams(C.Structure):
+    _fields_ = [
+        ("logits", C.c_void_p), ("out", C.c_void_p), ("logprobs", C.c_void_p), ("kept", C.c_void_p),
+        ("row_stride", C.c_int64), ("seed", C.c_uint64), ("offset", C.c_uint64),
+        ("rows", C.c_int32), ("n", C.c_int32), ("dtype", C.c_int32), ("temperature", C.c_float),
+        ("top_k", C.c_int32), ("top_p", C.c_float), ("min_p", C.c_float), ("n_context", C.c_int32),
+        ("repetition_penalty", C.c_double), ("frequency_penalty", C.c_double), ("presence_penalty", C.c_double),
+        ("context", TokenBitmap * SAMPLE_MAX_CONTEXT),
+        ("gen", C.c_void_p), ("gen_len", C.c_void_p), ("gen_stride", C.c_int32), ("append_out", C.c_int32),
+        ("bias_ids", C.c_void_p), ("bias_values", C.c_void_p), ("n_bias", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class TokenBitmapParams(C.Structure):
+    _fields_ = [
+        ("ids", C.c_void_p), ("lens", C.c_void_p), ("bits", C.c_void_p), ("id_stride", C.c_int64),
+        ("groups", C.c_int32), ("L", C.c_int32), ("n", C.c_int32), ("reserved", C.c_int32),
+    ]
 
 
 class TokenLogprobParams(C.Structure):
@@ -175,6 +202,8 @@ EXPORTS = {
     "hyd_rope_append_decode_kvq": (C.c_int, [C.POINTER(RopeParams), C.POINTER(KvQuant), C.c_void_p]),
     "hyd_kv_quant_supported": (C.c_int, [C.POINTER(SuffixParams), C.POINTER(KvQuant)]),
     "hyd_sample_tokens_filtered": (C.c_int, [C.POINTER(SampleFilterParams), C.c_void_p]),
+    "hyd_sample_tokens_penalized": (C.c_int, [C.POINTER(SamplePenaltyParams), C.c_void_p]),
+    "hyd_token_bitmap_build": (C.c_int, [C.POINTER(TokenBitmapParams), C.c_void_p]),
     "hyd_token_logprobs": (C.c_int, [C.POINTER(TokenLogprobParams), C.c_void_p]),
     "hyd_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

@@ -704,6 +704,79 @@ int hyd_sample_tokens_filtered(const hyd_sample_filter_params* p, void* stream) 
     return rc ? fail(HYD_ERR_LAUNCH, "sample_filter kernel launch failed: hip error %d", rc) : HYD_OK;
 }
 
+int hyd_sample_tokens_penalized(const hyd_sample_penalty_params* p, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    if (p->dtype != HYD_F16 && p->dtype != HYD_BF16 && p->dtype != HYD_F32) return fail(HYD_ERR_UNSUPPORTED, "dtype %d", p->dtype);
+    if (p->rows < 0 || p->n <= 0) return fail(HYD_ERR_BAD_ARG, "rows %d, n %d", p->rows, p->n);
+    if (p->n > HYD_SAMPLE_FILTER_MAX_N) return fail(HYD_ERR_UNSUPPORTED, "n %d: rows of up to %d logits", p->n, HYD_SAMPLE_FILTER_MAX_N);
+    if (!p->logits || !p->out) return fail(HYD_ERR_BAD_ARG, "logits / out is null");
+    if (!(p->temperature >= 0.f)) return fail(HYD_ERR_BAD_ARG, "temperature %g must be >= 0", (double)p->temperature);
+    if (p->top_k < 0) return fail(HYD_ERR_BAD_ARG, "top_k %d must be >= 0 (0 = off)", p->top_k);
+    if (!(p->top_p > 0.f && p->top_p <= 1.f)) return fail(HYD_ERR_BAD_ARG, "top_p %g must be in (0, 1] (1 = off)", (double)p->top_p);
+    if (!(p->min_p >= 0.f && p->min_p <= 1.f)) return fail(HYD_ERR_BAD_ARG, "min_p %g must be in [0, 1] (0 = off)", (double)p->min_p);
+    if (p->row_stride < p->n) return fail(HYD_ERR_BAD_ARG, "row_stride %lld < n %d", (long long)p->row_stride, p->n);
+    if (!(p->repetition_penalty > 0.0) || std::isinf(p->repetition_penalty))
+        return fail(HYD_ERR_BAD_ARG, "repetition_penalty %g must be a finite number > 0 (1 = off)", p->repetition_penalty);
+    if (!std::isfinite(p->frequency_penalty) || !std::isfinite(p->presence_penalty))
+        return fail(HYD_ERR_BAD_ARG, "frequency_penalty %g / presence_penalty %g must be finite (0 = off)", p->frequency_penalty, p->presence_penalty);
+    if (p->n_context < 0 || p->n_context > HYD_SAMPLE_MAX_CONTEXT)
+        return fail(HYD_ERR_BAD_ARG, "n_context %d: 0 to %d context bitmaps", p->n_context, HYD_SAMPLE_MAX_CONTEXT);
+    for (int l = 0; l < p->n_context; ++l) {
+        if (!p->context[l].bits) return fail(HYD_ERR_BAD_ARG, "context[%d].bits is null", l);
+        if (p->context[l].rows_per_group <= 0) return fail(HYD_ERR_BAD_ARG, "context[%d].rows_per_group %d must be > 0", l, p->context[l].rows_per_group);
+        if ((reinterpret_cast<uintptr_t>(p->context[l].bits) & 3u) != 0) return fail(HYD_ERR_BAD_ARG, "context[%d].bits is not aligned to its element size", l);
+    }
+    if ((p->gen == nullptr) != (p->gen_len == nullptr)) return fail(HYD_ERR_BAD_ARG, "gen and gen_len go together (one of them is null)");
+    if (p->gen_stride < 0) return fail(HYD_ERR_BAD_ARG, "gen_stride %d must be >= 0", p->gen_stride);
+    if (p->gen_stride > HYD_SAMPLE_GEN_MAX) return fail(HYD_ERR_UNSUPPORTED, "gen_stride %d: up to %d generated tokens per row", p->gen_stride, HYD_SAMPLE_GEN_MAX);
+    if (p->append_out && !p->gen) return fail(HYD_ERR_BAD_ARG, "append_out needs gen and gen_len (null)");
+    if (p->n_bias < 0 || p->n_bias > HYD_SAMPLE_BIAS_MAX) return fail(HYD_ERR_BAD_ARG, "n_bias %d: 0 to %d logit-bias entries", p->n_bias, HYD_SAMPLE_BIAS_MAX);
+    if (p->n_bias > 0 && (!p->bias_ids || !p->bias_values)) return fail(HYD_ERR_BAD_ARG, "n_bias %d needs bias_ids and bias_values (null)", p->n_bias);
+    const int esz = p->dtype == HYD_F32 ? 4 : 2;
+    if ((reinterpret_cast<uintptr_t>(p->logits) & (uintptr_t)(esz - 1)) != 0 || (reinterpret_cast<uintptr_t>(p->out) & 7u) != 0 ||
+        (reinterpret_cast<uintptr_t>(p->logprobs) & 3u) != 0 || (reinterpret_cast<uintptr_t>(p->kept) & 3u) != 0)
+        return fail(HYD_ERR_BAD_ARG, "logits / out / logprobs / kept is not aligned to its element size");
+    if ((reinterpret_cast<uintptr_t>(p->gen) & 3u) != 0 || (reinterpret_cast<uintptr_t>(p->gen_len) & 3u) != 0 ||
+        (reinterpret_cast<uintptr_t>(p->bias_ids) & 7u) != 0 || (reinterpret_cast<uintptr_t>(p->bias_values) & 3u) != 0)
+        return fail(HYD_ERR_BAD_ARG, "gen / gen_len / bias_ids / bias_values is not aligned to its element size");
+    PenaltyArgs a;
+    memset(&a, 0, sizeof(a));
+    a.f.logits = p->logits; a.f.out = p->out; a.f.logprobs = p->logprobs; a.f.kept = p->kept;
+    a.f.row_stride = p->row_stride; a.f.seed = p->seed; a.f.offset = p->offset;
+    a.f.rows = p->rows; a.f.n = p->n;
+    a.f.inv_temperature = p->temperature > 0.f ? 1.0f / p->temperature : 0.f;  // (as hyd_sample_tokens_filtered, field by field)
+    a.f.top_k = p->top_k < p->n ? p->top_k : 0;
+    a.f.top_p = p->top_p;
+    a.f.log_min_p = p->min_p > 0.f ? (float)log((double)p->min_p) : -INFINITY;
+    a.f.vec_ok = ((reinterpret_cast<uintptr_t>(p->logits) & 15u) == 0 && p->row_stride % (16 / esz) == 0) ? 1 : 0;
+    a.rep = p->repetition_penalty; a.inv_rep = 1.0 / p->repetition_penalty; a.freq = p->frequency_penalty; a.pres = p->presence_penalty;
+    a.n_ctx = p->n_context; a.words = (p->n + 31) / 32;
+    for (int l = 0; l < p->n_context; ++l) {
+        a.ctx[l] = p->context[l].bits;
+        a.ctx_rpg[l] = p->context[l].rows_per_group;
+    }
+    a.gen = p->gen; a.gen_len = p->gen_len; a.gen_stride = p->gen_stride; a.append_out = p->append_out ? 1 : 0;
+    a.bias_ids = p->bias_ids; a.bias_values = p->bias_values; a.n_bias = p->n_bias;
+    const int rc = launch_sample_penalty(a, p->dtype, static_cast<hipStream_t>(stream));
+    return rc ? fail(HYD_ERR_LAUNCH, "sample_penalty kernel launch failed: hip error %d", rc) : HYD_OK;
+}
+
+int hyd_token_bitmap_build(const hyd_token_bitmap_params* p, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    if (p->groups < 0 || p->groups > 65535 || p->L < 0) return fail(HYD_ERR_BAD_ARG, "groups %d (0 to 65535), L %d", p->groups, p->L);
+    if (p->n <= 0 || p->n > HYD_SAMPLE_FILTER_MAX_N) return fail(HYD_ERR_BAD_ARG, "n %d: 1 to %d", p->n, HYD_SAMPLE_FILTER_MAX_N);
+    if (!p->ids || !p->bits) return fail(HYD_ERR_BAD_ARG, "ids / bits is null");
+    if (p->id_stride < p->L) return fail(HYD_ERR_BAD_ARG, "id_stride %lld < L %d", (long long)p->id_stride, p->L);
+    if ((reinterpret_cast<uintptr_t>(p->ids) & 7u) != 0 || (reinterpret_cast<uintptr_t>(p->lens) & 7u) != 0 || (reinterpret_cast<uintptr_t>(p->bits) & 3u) != 0)
+        return fail(HYD_ERR_BAD_ARG, "ids / lens / bits is not aligned to its element size");
+    BitmapArgs a;
+    memset(&a, 0, sizeof(a));
+    a.ids = p->ids; a.lens = p->lens; a.bits = p->bits; a.id_stride = p->id_stride;
+    a.groups = p->groups; a.L = p->L; a.n = p->n; a.words = (p->n + 31) / 32;
+    const int rc = launch_token_bitmap(a, static_cast<hipStream_t>(stream));
+    return rc ? fail(HYD_ERR_LAUNCH, "token_bitmap kernel launch failed: hip error %d", rc) : HYD_OK;
+}
+
 int hyd_token_logprobs(const hyd_token_logprob_params* p, void* stream) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
     if (p->dtype != HYD_F16 && p->dtype != HYD_BF16 && p->dtype != HYD_F32) return fail(HYD_ERR_UNSUPPORTED, "dtype %d", p->dtype);

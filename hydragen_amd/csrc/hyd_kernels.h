@@ -173,6 +173,29 @@ struct FilterArgs {  // sample_filter.hip: SampleArgs' draw over the tokens that
     int32_t vec_ok;      // rows are 16-byte aligned
 };
 
+constexpr int kMaxContext = HYD_MAX_LEVELS + 1;
+struct PenaltyArgs {  // sample_penalty.hip: FilterArgs' kernel over penalised logits (hyd_sample_tokens_penalized)
+    FilterArgs f;
+    double rep, inv_rep, freq, pres;  // 1, 1, 0, 0 = off; inv_rep = 1 / rep (no fp64 division in the kernel)
+    const uint32_t* ctx[kMaxContext];  // [groups, words] presence bitmaps
+    int32_t ctx_rpg[kMaxContext];    // rows per bitmap row
+    int32_t n_ctx, words;            // words = ceil(n / 32)
+    int32_t* gen;                    // [rows, gen_stride] or null
+    int32_t* gen_len;
+    int32_t gen_stride, append_out;
+    const int64_t* bias_ids;
+    const float* bias_values;
+    int32_t n_bias;
+};
+
+struct BitmapArgs {  // sample_penalty.hip: token ids -> presence bitmap (hyd_token_bitmap_build)
+    const int64_t* ids;
+    const int64_t* lens;  // may be null
+    uint32_t* bits;
+    int64_t id_stride;
+    int32_t groups, L, n, words;
+};
+
 struct TokenLogprobArgs {  // token_logprob.hip: log-probs of given tokens, greedy flags, top-N alternatives
     const void* logits;
     const int64_t* targets;
@@ -194,6 +217,8 @@ int launch_add_rmsnorm(const NormArgs& a, int dtype, hipStream_t s);
 int launch_swiglu(const SwigluArgs& a, int dtype, hipStream_t s);
 int launch_sample(const SampleArgs& a, int dtype, hipStream_t s);
 int launch_sample_filter(const FilterArgs& a, int dtype, hipStream_t s);  // sample_filter.hip
+int launch_sample_penalty(const PenaltyArgs& a, int dtype, hipStream_t s);     // sample_penalty.hip
+int launch_token_bitmap(const BitmapArgs& a, hipStream_t s);                     // sample_penalty.hip
 int launch_token_logprob(const TokenLogprobArgs& a, int dtype, hipStream_t s);  // token_logprob.hip
 int launch_suffix(const SuffixArgs& a, int dtype, int D, hipStream_t s);
 bool suffix_gqa_eligible(const SuffixArgs& a, int D, bool any_shape);

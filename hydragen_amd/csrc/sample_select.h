@@ -1,24 +1,9 @@
-// Token sampling with top-k / top-p / min-p cuts and the sampled token's log-probability, one workgroup per row
-// (hyd_sample_tokens_filtered, include/hydragen_hip.h).
-//
-//   * The cuts act on the UNSCALED distribution p = softmax(l) (the reference's apply_top_p, llama.py `apply_top_p`):
-//     top-k keeps l >= the k-th largest logit (ties kept), top-p then keeps the smallest top set of the top-k survivors whose
-//     renormalised mass reaches top_p (the crossing token and its ties kept), min-p keeps l - max >= ln(min_p).  Every cut
-//     keeps a top set of the row, so the kept set is "key >= one threshold" plus the min-p test.
-//   * The draw is argmax(l * (1/T) + g) over the kept tokens with the Gumbel noise g of sample_kernel (layer_ops.hip) bit for
-//     bit: Philox4x32-10 counter (2 (j / 8) + (j % 8) / 4, row, offset lo, offset hi), key seed, word j % 4.
-//   * Masses are fixed point, floor(exp(l - max) 2^40) in u64: integer sums do not depend on their order, so the kept set,
-//     the token and the log-prob are the same for every run (LDS integer atomics, no float atomics).  n <= 2^22 keeps every
-//     sum below 2^62.
-//   * Thresholds are found by a select over 256-bin LDS histograms: a first level bins the distance to the max in steps of
-//     1/8 (bin 255 = 31.875 and beyond, counted from the total instead of with atomics), then 8-bit radix levels over the
-//     order-preserving key of the logit's own bits (2 levels for 16-bit logits, 4 for fp32) resolve the bin to one value.
-// Mapping: 1024 threads; thread t owns the 8-element chunks t + 1024 j (16-byte loads when the row allows).  Every pass
-// re-reads the row: it is 64-512 KB, so the passes after the first hit L2 / MALL.  (Keeping 16-bit rows in VGPRs across
-// the passes -- up to 16 chunks per thread -- spilled to scratch at 4 and 8 chunks with this hipcc: DESIGN.md 4.11.)
-// NOTE: sample_select.h holds a COPY of everything below (helpers and kernel body, the body as a template over a logit map) for
-// sample_penalty.hip; this file's assembly is pinned by tests/test_scoring.py, so the text is not shared.  A change to the
-// sampling rules here must be made there too (tests/test_sampling_penalties_gpu.py compares the two bit for bit).
+// The vocabulary-row machinery of sample_penalty.hip: sample_filter.hip's helpers (Philox / Gumbel noise of sample_kernel,
+// order-preserving keys, 8-element chunk loads, block reductions, fixed-point masses, the 256-bin select) and its kernel body as
+// a function of a Map that rewrites every chunk before the select sees it (sample_row).  COPIED from sample_filter.hip, not
+// moved: that file's gfx950 assembly is pinned by tests/test_scoring.py, so it keeps its own text.  A change to the sampling
+// rules is made in both; tests/test_sampling_penalties_gpu.py holds them bit-equal on unpenalised rows.
+#pragma once
 #include "hyd_kernels.h"
 
 namespace hyd {
@@ -203,11 +188,24 @@ __device__ Pick pick_bin(const uint64_t* hist, uint64_t cum, uint64_t target, bo
     return p;
 }
 
-}  // namespace
+// What a sampling kernel does to a row before the select sees it.  chunk(c, f, key): rewrites the 8 logits of chunk c and
+// their keys (keys of KB bits); one(tok, l): the same map for a single token.  NoMap: the logits as they are.
+struct NoMap {
+    __device__ __forceinline__ void chunk(int, float (&)[8], uint32_t (&)[8]) const {}
+    __device__ __forceinline__ float one(int, float l) const { return l; }
+};
+template <int DT, typename Map, typename F>
+__device__ __forceinline__ void visit_mapped(const void* row, int n, int vec, const Map& map, F&& fn) {
+    visit<DT>(row, n, vec, [&](int c, float (&f)[8], uint32_t (&k)[8]) {
+        map.chunk(c, f, k);
+        fn(c, f, k);
+    });
+}
 
-template <int DT>
-__global__ __launch_bounds__(1024) void sample_filter_kernel(const FilterArgs a) {
-    constexpr int KB = DT == HYD_F32 ? 32 : 16;  // key bits
+// One row of hyd_sample_tokens_filtered (workgroup blockIdx.x, 1024 threads) over map(logits), keys of KB bits.  Returns the
+// token on thread 0 (every thread of a row without a valid logit: 0), -1 on the others.
+template <int DT, int KB, typename Map>
+__device__ __forceinline__ int sample_row(const FilterArgs& a, const Map& map) {
     __shared__ uint64_t hist[256];
     __shared__ float redf[kFW];
     __shared__ uint64_t redu[kFW];
@@ -222,7 +220,7 @@ __global__ __launch_bounds__(1024) void sample_filter_kernel(const FilterArgs a)
     // pass 1: max and the number of finite (or +inf) logits
     float m = -INFINITY;
     uint64_t nvalid = 0;
-    visit<DT>(rowp, n, a.vec_ok, [&](int, const float (&f)[8], const uint32_t (&)[8]) {
+    visit_mapped<DT>(rowp, n, a.vec_ok, map, [&](int, const float (&f)[8], const uint32_t (&)[8]) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             if (valid(f[i])) {
@@ -239,7 +237,7 @@ __global__ __launch_bounds__(1024) void sample_filter_kernel(const FilterArgs a)
             if (a.kept) a.kept[row] = 0;
             if (a.logprobs) a.logprobs[row] = __builtin_nanf("");
         }
-        return;
+        return 0;
     }
     const bool topk = a.top_k > 0 && (uint64_t)a.top_k < nvalid;
     const bool topp = a.top_p < 1.0f;
@@ -251,7 +249,7 @@ __global__ __launch_bounds__(1024) void sample_filter_kernel(const FilterArgs a)
         __syncthreads();
     }
     if (topk || a.logprobs) {
-        visit<DT>(rowp, n, a.vec_ok, [&](int, const float (&f)[8], const uint32_t (&)[8]) {
+        visit_mapped<DT>(rowp, n, a.vec_ok, map, [&](int, const float (&f)[8], const uint32_t (&)[8]) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 if (valid(f[i])) {
@@ -278,7 +276,7 @@ __global__ __launch_bounds__(1024) void sample_filter_kernel(const FilterArgs a)
             for (int i = threadIdx.x; i < 256; i += kFT) hist[i] = 0;
             __syncthreads();
             const int sh = KB - 8 * (lvl + 1);
-            visit<DT>(rowp, n, a.vec_ok, [&](int, const float (&f)[8], const uint32_t (&key)[8]) {
+            visit_mapped<DT>(rowp, n, a.vec_ok, map, [&](int, const float (&f)[8], const uint32_t (&key)[8]) {
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     if (valid(f[i]) && bin0(f[i], m) == b && (lvl == 0 || (key[i] >> (sh + 8)) == prefix))
@@ -298,7 +296,7 @@ __global__ __launch_bounds__(1024) void sample_filter_kernel(const FilterArgs a)
         __syncthreads();
         uint64_t tot1 = 0;
         const uint32_t kthr = thr;
-        visit<DT>(rowp, n, a.vec_ok, [&](int, const float (&f)[8], const uint32_t (&key)[8]) {
+        visit_mapped<DT>(rowp, n, a.vec_ok, map, [&](int, const float (&f)[8], const uint32_t (&key)[8]) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 if (valid(f[i]) && key[i] >= kthr) {
@@ -319,7 +317,7 @@ __global__ __launch_bounds__(1024) void sample_filter_kernel(const FilterArgs a)
             for (int i = threadIdx.x; i < 256; i += kFT) hist[i] = 0;
             __syncthreads();
             const int sh = KB - 8 * (lvl + 1);
-            visit<DT>(rowp, n, a.vec_ok, [&](int, const float (&f)[8], const uint32_t (&key)[8]) {
+            visit_mapped<DT>(rowp, n, a.vec_ok, map, [&](int, const float (&f)[8], const uint32_t (&key)[8]) {
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     if (valid(f[i]) && key[i] >= kthr && bin0(f[i], m) == b && (lvl == 0 || (key[i] >> (sh + 8)) == prefix)) {
@@ -340,7 +338,7 @@ __global__ __launch_bounds__(1024) void sample_filter_kernel(const FilterArgs a)
     float best = -INFINITY;
     int besti = 0x7fffffff;
     uint64_t kept = 0;
-    visit<DT>(rowp, n, a.vec_ok, [&](int c, const float (&f)[8], const uint32_t (&key)[8]) {
+    visit_mapped<DT>(rowp, n, a.vec_ok, map, [&](int c, const float (&f)[8], const uint32_t (&key)[8]) {
         bool keep[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -396,20 +394,15 @@ __global__ __launch_bounds__(1024) void sample_filter_kernel(const FilterArgs a)
         a.out[row] = tok;
         if (a.kept) a.kept[row] = (int32_t)kept;
         if (a.logprobs) {
-            const float lt = DT == HYD_F32 ? static_cast<const float*>(rowp)[tok] : h2f<DT>(static_cast<const uint16_t*>(rowp)[tok]);
+            const float lt = map.one(tok, DT == HYD_F32 ? static_cast<const float*>(rowp)[tok] : h2f<DT>(static_cast<const uint16_t*>(rowp)[tok]));
             const double d = lt == m ? 0.0 : (double)lt - (double)m;
             a.logprobs[row] = (float)(d - (log((double)total) - 40.0 * 0.6931471805599453));
         }
+        return tok;
     }
+    return -1;
 }
 
-int launch_sample_filter(const FilterArgs& a, int dtype, hipStream_t s) {
-    if (a.rows == 0) return 0;
-    const dim3 grid((unsigned)a.rows), block(kFT);
-    if (dtype == HYD_F16) hipLaunchKernelGGL((sample_filter_kernel<HYD_F16>), grid, block, 0, s, a);
-    else if (dtype == HYD_BF16) hipLaunchKernelGGL((sample_filter_kernel<HYD_BF16>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((sample_filter_kernel<HYD_F32>), grid, block, 0, s, a);
-    return (int)hipGetLastError();
-}
+}  // namespace
 
 }  // namespace hyd

@@ -6,6 +6,7 @@ HIP kernel instead of two torch launches."""
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass, field
 from typing import Optional
 
 import torch
@@ -14,6 +15,7 @@ from torch import Tensor
 from . import _lib
 from ._lib import AddRmsnormParams, SwigluParams
 from .flash import _dtype_code, _require_gpu, _stream
+from . import sampling
 from .sampling import check_filters, filters_active
 from .scoring import check_top_n, token_logprobs_reference
 
@@ -89,13 +91,160 @@ def _next_sample_key(device: torch.device):
     return seed, offset
 
 
+@dataclass
+class Penalties:
+    """What sampling.py's penalty definition needs for a batch of rows: the scalars, the bias list as (ids int64 [K], values fp32
+    [K]) tensors on the logits' device, the context bitmaps [(bits int32 [groups, ceil(V / 32)], rows_per_group)], and the rows'
+    generated tokens gen int32 [B, stride] with their device-side lengths gen_len int32 [B].  append: the kernel stores each
+    drawn token behind the row's list (hyd_sample_penalty_params.append_out); the torch route does the same with two small
+    launches, so either way the list follows the draws without a host sync."""
+    repetition_penalty: Optional[float] = None
+    presence_penalty: Optional[float] = None
+    frequency_penalty: Optional[float] = None
+    logit_bias: Optional[tuple] = None
+    context: list = field(default_factory=list)
+    gen: Optional[Tensor] = None
+    gen_len: Optional[Tensor] = None
+    append: bool = False
+
+    def active(self) -> bool:
+        return sampling.penalties_active(self.repetition_penalty, self.presence_penalty, self.frequency_penalty, self.logit_bias)
+
+    def apply(self, logits: Tensor, rows_per_sample: int = 1) -> Tensor:
+        """sampling.penalize_logits of these penalties (float64).  rows_per_sample = s > 1: `logits` holds one row for every s
+        consecutive rows of the batch (the fan-out first token: the samples of a leaf share its context and have generated
+        nothing yet)."""
+        ctx = self.context
+        gen, gen_len = self.gen, self.gen_len
+        if rows_per_sample > 1:
+            if any(k % rows_per_sample for _, k in ctx):
+                raise ValueError(f"context groups do not nest in {rows_per_sample} samples per row")
+            ctx = [(b, k // rows_per_sample) for b, k in ctx]
+            gen = gen_len = None
+        return sampling.penalize_logits(logits, self.repetition_penalty, self.presence_penalty, self.frequency_penalty,
+                                        self.logit_bias, ctx, gen, gen_len)
+
+    def push(self, tokens: Tensor) -> None:
+        """Append one token per row ([B, 1] or [B]) to gen / gen_len: two small launches, no sync."""
+        t = tokens.reshape(-1, 1).to(torch.int32)
+        pos = self.gen_len.long().clamp_(max=self.gen.shape[1] - 1)[:, None]
+        self.gen.scatter_(1, pos, torch.where(self.gen_len[:, None] < self.gen.shape[1], t, self.gen.gather(1, pos)))
+        self.gen_len += 1
+
+
+def token_bitmap(ids: Tensor, lens: Optional[Tensor], n: int, out: Optional[Tensor] = None) -> Tensor:
+    """hyd_token_bitmap_build: [groups, L] int64 token ids (+ [groups] lengths, None = all L) -> presence bitmap int32
+    [groups, ceil(n / 32)] (bit v % 32 of word v // 32 = token v occurs), one launch and no [groups, n] table.  out: OR into an
+    existing bitmap instead of a zeroed one.  CPU tensors take sampling.token_bitmap_reference."""
+    if ids.ndim != 2 or ids.dtype != torch.int64:
+        raise ValueError(f"ids must be [groups, L] int64, got {tuple(ids.shape)} {ids.dtype}")
+    groups, L = ids.shape
+    if lens is not None and (lens.numel() != groups or lens.device != ids.device):
+        raise ValueError(f"lens must hold {groups} lengths on {ids.device}")
+    words = (n + 31) // 32
+    if not ids.is_cuda:
+        ref = sampling.token_bitmap_reference(ids, lens, n)
+        return ref if out is None else out.bitwise_or_(ref)
+    _require_gpu(ids)
+    lib = _lib.load()
+    bits = torch.zeros((groups, words), dtype=torch.int32, device=ids.device) if out is None else out
+    assert bits.shape == (groups, words) and bits.dtype == torch.int32 and bits.is_contiguous()
+    if ids.stride(1) != 1:
+        ids = ids.contiguous()
+    p = _lib.TokenBitmapParams()
+    p.ids, p.bits, p.id_stride = ids.data_ptr(), bits.data_ptr(), ids.stride(0) if groups > 1 else L
+    if lens is not None:
+        lens = lens.reshape(-1).to(torch.int64).contiguous()
+        p.lens = lens.data_ptr()
+    p.groups, p.L, p.n = groups, L, n
+    _lib.check(lib.hyd_token_bitmap_build(C.byref(p), _stream()))
+    return bits
+
+
+def sample_tokens_penalized(logits: Tensor, temperature: float, key: Optional[tuple] = None, *, penalties: Penalties,
+                            top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None):
+    """hyd_sample_tokens_penalized, one launch whatever the penalties are (neutral ones included): ([B, 1] int64 tokens, [B] fp32
+    log-probs under softmax(penalised logits), [B] int32 number of kept tokens).  hydragen_amd/sampling.py states the
+    definition.  Nothing of size [B, V] is allocated and nothing synchronises; the bias list must already be checked
+    (sampling.check_penalties) and on the device."""
+    _require_gpu(logits)
+    lib = _lib.load()
+    assert logits.ndim == 2 and logits.stride(1) == 1 and logits.shape[1] > 0
+    rows, n = logits.shape
+    dev = logits.device
+    out = torch.empty((rows, 1), dtype=torch.int64, device=dev)
+    logprobs = torch.empty((rows,), dtype=torch.float32, device=dev)
+    kept = torch.empty((rows,), dtype=torch.int32, device=dev)
+    if rows == 0:
+        return out, logprobs, kept
+    check_filters(top_k, top_p, min_p)
+    pen = penalties
+    words = (n + 31) // 32
+    p = _lib.SamplePenaltyParams()
+    if len(pen.context) > _lib.SAMPLE_MAX_CONTEXT:
+        raise ValueError(f"{len(pen.context)} context bitmaps: at most {_lib.SAMPLE_MAX_CONTEXT}")
+    for i, (bits, rpg) in enumerate(pen.context):
+        if (bits.dtype != torch.int32 or bits.ndim != 2 or bits.shape[1] != words or not bits.is_contiguous() or bits.device != dev
+                or rpg <= 0 or bits.shape[0] * rpg < rows):
+            raise ValueError(f"context bitmap {i}: int32 [groups, {words}] on {dev} with groups * rows_per_group >= {rows}, got "
+                             f"{tuple(bits.shape)} {bits.dtype} x {rpg}")
+        p.context[i].bits, p.context[i].rows_per_group = bits.data_ptr(), int(rpg)
+    p.n_context = len(pen.context)
+    if pen.gen is not None:
+        g, gl = pen.gen, pen.gen_len
+        if (g.dtype != torch.int32 or g.ndim != 2 or g.shape[0] != rows or not g.is_contiguous() or g.device != dev
+                or gl is None or gl.dtype != torch.int32 or gl.shape != (rows,) or gl.device != dev or not gl.is_contiguous()):
+            raise ValueError(f"gen must be int32 [{rows}, stride] and gen_len int32 [{rows}], contiguous on {dev}")
+        if g.shape[1] > _lib.SAMPLE_GEN_MAX:
+            raise NotImplementedError(f"{g.shape[1]} generated tokens per row: the kernel counts up to {_lib.SAMPLE_GEN_MAX}")
+        p.gen, p.gen_len, p.gen_stride = g.data_ptr(), gl.data_ptr(), g.shape[1]
+        p.append_out = int(pen.append)
+    elif pen.append:
+        raise ValueError("append needs gen and gen_len")
+    if pen.logit_bias is not None:
+        ids, values = pen.logit_bias
+        if (ids.dtype != torch.int64 or values.dtype != torch.float32 or ids.shape != values.shape or ids.ndim != 1
+                or ids.device != dev or values.device != dev or not ids.is_contiguous() or not values.is_contiguous()):
+            raise ValueError(f"logit_bias must be (ids int64 [K], values fp32 [K]) on {dev}: sampling.normalize_logit_bias")
+        p.bias_ids, p.bias_values, p.n_bias = ids.data_ptr(), values.data_ptr(), ids.numel()
+    p.repetition_penalty = 1.0 if pen.repetition_penalty is None else float(pen.repetition_penalty)
+    p.frequency_penalty, p.presence_penalty = float(pen.frequency_penalty or 0.0), float(pen.presence_penalty or 0.0)
+    p.top_k, p.top_p, p.min_p = int(top_k or 0), 1.0 if top_p is None else float(top_p), float(min_p or 0.0)
+    seed, offset = key if key is not None else _next_sample_key(dev)
+    p.logits, p.out, p.logprobs, p.kept = logits.data_ptr(), out.data_ptr(), logprobs.data_ptr(), kept.data_ptr()
+    p.row_stride = logits.stride(0) if rows > 1 else n
+    p.seed, p.offset, p.rows, p.n = seed, offset, rows, n
+    p.dtype = _HYD_F32 if logits.dtype == torch.float32 else _dtype_code(logits)
+    p.temperature = float(temperature)
+    _lib.check(lib.hyd_sample_tokens_penalized(C.byref(p), _stream()))
+    return out, logprobs, kept
+
+
 def sample_tokens(logits: Tensor, temperature: float, key: Optional[tuple] = None, *, top_k: Optional[int] = None,
-                  top_p: Optional[float] = None, min_p: Optional[float] = None, return_logprobs: bool = False):
+                  top_p: Optional[float] = None, min_p: Optional[float] = None, return_logprobs: bool = False,
+                  penalties: Optional[Penalties] = None):
     """[B, V] logits (fp16 / bf16 / fp32, rows contiguous) -> [B, 1] int64 tokens drawn from softmax(logits / temperature)
     (temperature 0: argmax) in one kernel.  top_k / top_p / min_p cut the UNSCALED softmax(logits) first (hydragen_amd/
     sampling.py states the rules); return_logprobs also returns the [B, 1] fp32 log softmax(logits) of each drawn token.
     With no cut and no log-prob this is hyd_sample_tokens; otherwise hyd_sample_tokens_filtered, whose draw uses the same
-    noise (one key per call either way)."""
+    noise (one key per call either way).  penalties (a Penalties with something switched on): the cuts, the draw and the log-prob
+    act on the penalised logits (hydragen_amd/sampling.py), in one launch of hyd_sample_tokens_penalized; the log-prob is then
+    log softmax(penalised logits), the distribution the draw's policy is defined by.  CPU logits with penalties: the float64
+    definition and torch (no HIP kernel takes CPU tensors)."""
+    if penalties is not None and penalties.active():
+        if not logits.is_cuda:
+            xp = penalties.apply(logits)
+            x = xp.masked_fill(~sampling.kept_mask(xp, top_k, top_p, min_p), -float("inf"))
+            if temperature == 0:
+                tok = x.argmax(-1, keepdim=True)
+            else:
+                tok = torch.multinomial(torch.softmax(x / temperature, -1), 1)
+            lp = torch.log_softmax(xp, -1).gather(1, tok).float()
+            if penalties.append:
+                penalties.push(tok)
+            return (tok, lp) if return_logprobs else tok
+        tok, lp, _ = sample_tokens_penalized(logits, temperature, key, penalties=penalties, top_k=top_k, top_p=top_p, min_p=min_p)
+        return (tok, lp[:, None]) if return_logprobs else tok
     if not filters_active(top_k, top_p, min_p) and not return_logprobs:
         _require_gpu(logits)
         lib = _lib.load()

@@ -622,6 +622,8 @@ class HydragenLlamaForCausalLM(nn.Module):
         self.kv_cache_allocated = False
         self.graphed_model: Optional[GraphedHydragenLlamaModel] = None
         self.mode: Optional[str] = None
+        # one presence bitmap [sb, ceil(V / 32)] int32 per used shared level, recorded by append_shared (the penalties' context)
+        self.shared_bitmaps: list[Tensor] = []
 
     # ---- construction -----------------------------------------------------------------------------
     @classmethod
@@ -742,10 +744,12 @@ class HydragenLlamaForCausalLM(nn.Module):
     def empty_shared_cache(self):
         for layer in self.model.layers:
             layer.self_attn.kv_cache.empty_shared_cache()
+        self.shared_bitmaps.clear()
 
     def truncate_shared_caches(self, new_num_shared_caches: int):
         for layer in self.model.layers:
             layer.self_attn.kv_cache.truncate_shared_caches(new_num_shared_caches)
+        del self.shared_bitmaps[new_num_shared_caches:]
 
     def get_shared_cache_len(self, batch_size):
         return self.model.layers[0].self_attn.kv_cache.get_shared_len(batch_size)
@@ -781,11 +785,24 @@ class HydragenLlamaForCausalLM(nn.Module):
         return logits.masked_fill(remove.scatter(1, sorted_indices, remove), filter_value)
 
     def sample_from_logits(self, logits, temperature, num_samples=1, top_p=None, top_k=None, min_p=None,
-                           return_logprobs=False):
+                           return_logprobs=False, penalties=None):
         """Tokens [B, num_samples] (and, with return_logprobs, their fp32 log softmax(logits) [B, num_samples]).  The cuts
-        act on the unscaled softmax(logits), before the temperature (hydragen_amd/sampling.py)."""
+        act on the unscaled softmax(logits), before the temperature (hydragen_amd/sampling.py).  penalties (a
+        layer_ops.Penalties with something switched on): cuts, draw and log-prob act on the penalised logits instead; the
+        drawn tokens are appended to its list when it says so."""
         filtered = sampling.filters_active(top_k, top_p, min_p)
         eligible = logits.is_cuda and logits.ndim == 2 and num_samples == 1 and logits.stride(-1) == 1 and temperature >= 0
+        if penalties is not None and penalties.active():
+            if eligible and self.fused_sampling_penalties:
+                # one HIP kernel: penalties, cuts, draw, log-prob and the append to the rows' generated tokens
+                return layer_ops.sample_tokens(logits, temperature, top_k=top_k, top_p=top_p, min_p=min_p,
+                                               return_logprobs=return_logprobs, penalties=penalties)
+            # the definition in torch (float64, through [B, V] tables), then the paths below on the penalised logits
+            logits = penalties.apply(logits, num_samples).float()
+            out = self.sample_from_logits(logits, temperature, num_samples, top_p, top_k, min_p, return_logprobs)
+            if penalties.append and num_samples == 1:
+                penalties.push(out[0] if return_logprobs else out)
+            return out
         if eligible and (return_logprobs or (filtered and self.fused_sampling_filters)):
             # one HIP kernel: the cuts, the Gumbel-max draw over the kept tokens and the token's log-probability
             return layer_ops.sample_tokens(logits, temperature, top_k=top_k, top_p=top_p, min_p=min_p,
@@ -823,7 +840,15 @@ class HydragenLlamaForCausalLM(nn.Module):
             last = position_ids.gather(1, (seq_lens.long() - 1)[:, None])
             ar = torch.arange(input_ids.shape[1], device=input_ids.device)[None, :]
             position_ids = torch.where(ar >= seq_lens.long()[:, None], last, position_ids)
-        return self(input_ids=input_ids, position_ids=position_ids, seq_lens=seq_lens, full_logits=full_logits)
+        logits = self(input_ids=input_ids, position_ids=position_ids, seq_lens=seq_lens, full_logits=full_logits)
+        # the level's token set, for the sampling penalties (hydragen_amd/sampling.py): ALWAYS recorded, because a level
+        # outlives the call that appends it ("extend", starting_logits=) and a later call may ask for penalties; it is one
+        # memset and one launch next to a prefill forward, keeps no reference to the caller's tensor, and syncs nothing.
+        # After the forward: a refused level (no free shared cache) leaves the list as it was
+        del self.shared_bitmaps[self.get_num_used_shared_caches() - 1:]
+        lens = None if seq_lens is None else seq_lens.to(input_ids.device)
+        self.shared_bitmaps.append(layer_ops.token_bitmap(input_ids.long(), lens, self.vocab_size))
+        return logits
 
     @torch.no_grad()
     def process_unique(self, input_ids, seq_lens=None):
@@ -876,14 +901,23 @@ class HydragenLlamaForCausalLM(nn.Module):
                  shared_cache_op: str = SharedCacheOp.PRESERVE, disable_hydragen: bool = False,
                  disable_attention: bool = False, disable_hierarchy: bool = False,
                  token_overrides: Optional[Tensor] = None, top_k: Optional[int] = None, min_p: Optional[float] = None,
-                 return_logprobs: bool = False, top_logprobs: int = 0):
+                 return_logprobs: bool = False, top_logprobs: int = 0, repetition_penalty: Optional[float] = None,
+                 presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None, logit_bias=None):
         """Sampling: top_k / top_p / min_p cut the UNSCALED softmax(logits) (the reference's top-p order; HF applies the
         temperature first), then a token is drawn from softmax(logits / temperature) over the kept tokens.  Returns the
         tokens [B, generated]; return_logits adds the per-step fp32 logits, return_logprobs the fp32 [B, generated]
         log softmax(logits) of every returned token (unscaled, unfiltered): (out, logits, logprobs) in that order.
         top_logprobs = N > 0 (needs return_logprobs) also returns, for every returned token, the N best alternatives of that
         step's distribution (hyd_token_logprobs, hydragen_amd/scoring.py): (..., top_ids [B, generated, N] int64,
-        top_logprobs [B, generated, N] f32) after the other return values."""
+        top_logprobs [B, generated, N] f32) after the other return values.
+        Penalties (hydragen_amd/sampling.py states the rules; None = off): repetition_penalty r > 0 (HF / vLLM: l / r if l > 0
+        else l * r for every token of the row's context -- all shared levels on its path, levels kept by earlier calls included,
+        and its own prompt -- or of its generated tokens), frequency_penalty / presence_penalty (OpenAI / vLLM: generated
+        tokens only), logit_bias {token id: bias} or (ids, values), -inf bans a token.  "Generated" is what was fed back: the
+        sampled tokens, or token_overrides where given.  Cuts, draw and return_logprobs then act on the PENALISED logits
+        (log softmax of the penalised, unscaled, unfiltered logits: the distribution the draw's policy is defined by);
+        return_logits and top_logprobs keep reporting the model's raw distribution.  With every penalty off, generate()
+        runs exactly the launches it runs without these arguments."""
         if not self.kv_cache_allocated:
             raise RuntimeError("call setup_caches() before generate()")
         if (input_ids is None) == (starting_logits is None):
@@ -894,6 +928,13 @@ class HydragenLlamaForCausalLM(nn.Module):
         top_n = scoring.check_top_n(top_logprobs)
         if top_n and not return_logprobs:
             raise ValueError("top_logprobs needs return_logprobs=True")
+        sampling.check_penalties(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, self.vocab_size)
+        penalised = sampling.penalties_active(repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
+        # only the three penalties read the generated tokens; a bias / ban list alone needs no list and has no length limit
+        counted = sampling.penalties_active(repetition_penalty, presence_penalty, frequency_penalty)
+        if counted and max_new_tokens > sampling.GEN_MAX:
+            raise ValueError(f"repetition / presence / frequency penalties count up to {sampling.GEN_MAX} generated tokens per "
+                             f"sequence, max_new_tokens is {max_new_tokens}")
         fan_out = num_return_sequences > 1
         flatten = disable_hierarchy or disable_hydragen  # the baselines keep the last level per sequence
         if shared_cache_op == SharedCacheOp.WIPE:
@@ -922,14 +963,36 @@ class HydragenLlamaForCausalLM(nn.Module):
             self.repeat_per_completion_cache_for_num_samples(unique[0].shape[0], num_return_sequences)
 
         try:
-            return self._decode(logits[:, -1], unique, num_return_sequences, max_new_tokens,
-                                dict(temperature=temperature, top_p=top_p, top_k=top_k, min_p=min_p),
+            samp = dict(temperature=temperature, top_p=top_p, top_k=top_k, min_p=min_p)
+            if penalised:
+                samp["penalties"] = self._penalties(batch, unique, num_return_sequences, max_new_tokens, repetition_penalty,
+                                                    presence_penalty, frequency_penalty, logit_bias, counted)
+            return self._decode(logits[:, -1], unique, num_return_sequences, max_new_tokens, samp,
                                 eos_token_id, return_logits, token_overrides, return_logprobs, top_n)
         finally:
             if shared_cache_op == SharedCacheOp.PRESERVE:
                 self.truncate_shared_caches(levels_before)
             self.model.set_disable_hydragen(False)
             self.model.set_disable_attention(False)
+
+    def _penalties(self, batch, unique, fan, max_new_tokens, repetition_penalty, presence_penalty, frequency_penalty, logit_bias, counted):
+        """The call's layer_ops.Penalties: the used shared levels' bitmaps (one row per shared sequence, read by its
+        batch / sb rows: the same token set whether the keys sit in shared or -- disable_hydragen -- unique caches), the unique
+        prompts' bitmap shared by the samples of a leaf, and -- `counted`: a penalty that reads them is on -- an empty
+        [batch, max_new_tokens] list of generated tokens."""
+        if len(self.shared_bitmaps) != self.get_num_used_shared_caches():
+            raise RuntimeError(f"{self.get_num_used_shared_caches()} shared levels in use but {len(self.shared_bitmaps)} recorded token "
+                               "sets: a level was added or dropped behind append_shared / truncate_shared_caches")
+        context = [(bits, batch // bits.shape[0]) for bits in self.shared_bitmaps]
+        if unique is not None:
+            context.append((layer_ops.token_bitmap(unique[0].long(), unique[1].to(unique[0].device), self.vocab_size), fan))
+        if len(context) > sampling.MAX_CONTEXT:
+            raise ValueError(f"{len(context)} prompt levels: penalties take up to {sampling.MAX_CONTEXT}")
+        dev = self.lm_head.weight.device
+        return layer_ops.Penalties(
+            repetition_penalty, presence_penalty, frequency_penalty, sampling.normalize_logit_bias(logit_bias, dev), context,
+            gen=torch.zeros((batch, max_new_tokens), dtype=torch.int32, device=dev) if counted else None,
+            gen_len=torch.zeros((batch,), dtype=torch.int32, device=dev) if counted else None)
 
     # ---- scoring ----------------------------------------------------------------------------------------
     score_chunk_bytes = 1 << 30  # lm_head output per chunk of score()'s scored rows (tests shrink it)
@@ -1068,6 +1131,13 @@ class HydragenLlamaForCausalLM(nn.Module):
 
     def _decode(self, prefill_logits, unique, fan, max_new_tokens, samp, eos_token_id, return_logits, token_overrides,
                 return_logprobs=False, top_n=0):
+        pen = samp.get("penalties")
+        if pen is not None and pen.gen is None:
+            pen = None  # a bias alone: no list of generated tokens to keep
+        if pen is not None:
+            # the list of generated tokens follows what is FED: the sampler appends its own draws unless overrides replace them
+            # (or the first token fans out: one row of logits, `fan` rows of tokens)
+            pen.append = token_overrides is None and fan == 1
         first = self.sample_from_logits(prefill_logits, num_samples=fan, return_logprobs=return_logprobs, **samp)
         kept_lp = kept_top = None
         if return_logprobs:
@@ -1088,6 +1158,9 @@ class HydragenLlamaForCausalLM(nn.Module):
         done = (first == eos_token_id) if eos_token_id is not None else None
         tokens = [first]
         feed = first if token_overrides is None else token_overrides[:, 0:1]
+        if pen is not None and not pen.append:
+            pen.push(feed)
+            pen.append = token_overrides is None
         self.set_mode(AttentionMode.DECODE)
         graphed = self.graphed_model is not None
         # Ragged unique prompts: hand the longest sequences to the chip first.  Every length grows by one per step, so the order of
@@ -1106,6 +1179,9 @@ class HydragenLlamaForCausalLM(nn.Module):
     # top-k / top-p / min-p in the sampling kernel (hyd_sample_tokens_filtered); False: torch cuts + hyd_sample_tokens, the
     # path before the kernel existed (tests switch it off to compare)
     fused_sampling_filters = True
+    # penalties in the sampling kernel (hyd_sample_tokens_penalized); False: sampling.penalize_logits in torch, then the paths
+    # above (tests and tools/sampler_bench.py switch it off to compare)
+    fused_sampling_penalties = True
 
     def _decode_steps(self, feed, start, tokens, kept_logits, done, graphed, max_new_tokens, samp, eos_token_id,
                       return_logits, token_overrides, kept_lp=None, kept_top=None):
@@ -1113,6 +1189,9 @@ class HydragenLlamaForCausalLM(nn.Module):
         # the cuts run in torch
         raw = not return_logits and (self.fused_sampling_filters or not sampling.filters_active(
             samp["top_k"], samp["top_p"], samp["min_p"]))
+        pen = samp.get("penalties")
+        if pen is not None and pen.gen is None:
+            pen = None
         for step in range(max_new_tokens - 1):
             logits = self(input_ids=feed, position_ids=start + step, use_graph=graphed, raw_logits=raw)[:, -1]
             if return_logits:
@@ -1131,6 +1210,8 @@ class HydragenLlamaForCausalLM(nn.Module):
                 _, _, ids, tlp = layer_ops.token_logprobs(logits, nxt[:, 0], kept_top[0][0].shape[-1])
                 kept_top.append((ids[:, None], tlp[:, None]))
             feed = nxt if token_overrides is None else token_overrides[:, step + 1 : step + 2]
+            if pen is not None and not pen.append and feed.shape[1]:
+                pen.push(feed)
         out = torch.cat(tokens, dim=-1)
         check_collectives()  # no-op without the direct xGMI all-reduce; raises if a rank ever gave up on a peer
         ret = (out, kept_logits) if return_logits else (out,)

@@ -69,3 +69,142 @@ def filter_logits(logits: Tensor, top_k: Optional[int] = None, top_p: Optional[f
                   min_p: Optional[float] = None) -> Tensor:
     """`logits` with every token the cuts remove (and every NaN) set to -inf, in the input dtype."""
     return logits.masked_fill(~kept_mask(logits, top_k, top_p, min_p), -math.inf)
+
+
+# ---- penalties ------------------------------------------------------------------------------------------------------------
+# Repetition / presence / frequency penalties and a sparse logit bias: the definition `hyd_sample_tokens_penalized`
+# (csrc/sample_penalty.hip) implements, evaluated in float64.  For one row of logits l (length n), with
+#   ctx  = the token ids of the row's CONTEXT: every shared level on the row's path and the row's own prompt, given as
+#          presence bitmaps `(bits int32 [groups, ceil(n / 32)], rows_per_group)`; row b reads bitmap row b // rows_per_group,
+#          token v is bit v % 32 of word v // 32;
+#   c[v] = how often v occurs among the row's GENERATED tokens gen[b, :gen_len[b]] (entries outside [0, n) are ignored),
+# the penalised logits x are, in this order:
+#   1. repetition_penalty r > 0 (1 or None = off; the HF / vLLM rule, over prompt and output): for v in ctx or c[v] > 0,
+#      x = l / r if l > 0 else l * r; else x = l;
+#   2. frequency_penalty f, presence_penalty a (0 or None = off; any finite value; the OpenAI / vLLM rule, output only):
+#      x -= f * c[v] + a * (c[v] > 0);
+#   3. logit_bias (ids int64 [K], values fp32 [K]), ids distinct in [0, n), K <= BIAS_MAX, one list for all rows:
+#      x[ids] += values; -inf bans a token (the cuts' rule "-inf and NaN are never kept" then applies).
+# The cuts, the draw and the log-prob then act on x instead of l.
+BIAS_MAX = 1024  # HYD_SAMPLE_BIAS_MAX
+GEN_MAX = 2048   # HYD_SAMPLE_GEN_MAX: generated tokens per row the kernel counts
+MAX_CONTEXT = 9  # HYD_SAMPLE_MAX_CONTEXT
+
+
+def normalize_logit_bias(logit_bias, device=None):
+    """dict[int, float] or (ids, values) -> (ids int64 [K], values fp32 [K]) tensors, or None for an empty / absent bias."""
+    if logit_bias is None:
+        return None
+    if isinstance(logit_bias, dict):
+        ids = torch.tensor([int(k) for k in logit_bias.keys()], dtype=torch.int64)
+        values = torch.tensor([float(v) for v in logit_bias.values()], dtype=torch.float32)
+    else:
+        ids, values = logit_bias
+        ids = torch.as_tensor(ids).to(torch.int64).reshape(-1)
+        values = torch.as_tensor(values).to(torch.float32).reshape(-1)
+    if ids.numel() == 0 and values.numel() == 0:
+        return None
+    if device is not None:
+        ids, values = ids.to(device), values.to(device)
+    return ids.contiguous(), values.contiguous()
+
+
+def penalties_active(repetition_penalty: Optional[float] = None, presence_penalty: Optional[float] = None,
+                     frequency_penalty: Optional[float] = None, logit_bias=None) -> bool:
+    if isinstance(logit_bias, dict):
+        has_bias = len(logit_bias) > 0
+    else:
+        has_bias = logit_bias is not None and len(logit_bias[0]) > 0
+    return ((repetition_penalty is not None and repetition_penalty != 1.0) or bool(presence_penalty) or bool(frequency_penalty)
+            or has_bias)
+
+
+def check_penalties(repetition_penalty: Optional[float] = None, presence_penalty: Optional[float] = None,
+                    frequency_penalty: Optional[float] = None, logit_bias=None, n: Optional[int] = None) -> None:
+    """Host validation (reads the bias list: call it before the decode loop, not inside).  n: the vocabulary size, if known."""
+    r = repetition_penalty
+    if r is not None and not (r > 0 and math.isfinite(r)):
+        raise ValueError(f"repetition_penalty {r} must be a finite number > 0 (1 or None = off)")
+    for name, v in (("presence_penalty", presence_penalty), ("frequency_penalty", frequency_penalty)):
+        if v is not None and not math.isfinite(v):
+            raise ValueError(f"{name} {v} must be finite (0 or None = off)")
+    if logit_bias is None:
+        return
+    if not isinstance(logit_bias, dict) and not (isinstance(logit_bias, (tuple, list)) and len(logit_bias) == 2):
+        raise ValueError("logit_bias must be a dict {token id: bias} or an (ids, values) pair")
+    if not isinstance(logit_bias, dict) and len(logit_bias[0]) != len(logit_bias[1]):
+        raise ValueError(f"logit_bias has {len(logit_bias[0])} ids and {len(logit_bias[1])} values")
+    bias = normalize_logit_bias(logit_bias)
+    if bias is None:
+        return
+    ids, values = (t.cpu() for t in bias)
+    if ids.numel() > BIAS_MAX:
+        raise ValueError(f"logit_bias has {ids.numel()} entries: at most {BIAS_MAX}")
+    if ids.unique().numel() != ids.numel():
+        raise ValueError("logit_bias ids must be distinct")
+    if int(ids.min()) < 0 or (n is not None and int(ids.max()) >= n):
+        raise ValueError(f"logit_bias ids must be in [0, {n if n is not None else 'vocabulary size'})")
+    if bool((torch.isnan(values) | (values == math.inf)).any()):
+        raise ValueError("logit_bias values must be finite or -inf (-inf bans a token); +inf and NaN are refused")
+
+
+@torch.no_grad()
+def token_bitmap_reference(ids: Tensor, lens: Optional[Tensor], n: int) -> Tensor:
+    """[groups, L] token ids (+ [groups] lengths, None = all L) -> presence bitmap int32 [groups, ceil(n / 32)], in torch on any
+    device (the definition of hyd_token_bitmap_build; it goes through a [groups, n] table, which the kernel does not)."""
+    groups, L = ids.shape
+    words = (n + 31) // 32
+    ids = ids.long()
+    live = (ids >= 0) & (ids < n)
+    if lens is not None:
+        live &= torch.arange(L, device=ids.device)[None, :] < lens.to(ids.device).long().reshape(-1, 1)
+    present = torch.zeros((groups, words * 32 + 1), dtype=torch.int64, device=ids.device)
+    present.scatter_(1, torch.where(live, ids, torch.full_like(ids, words * 32)), 1)
+    weights = torch.ones(32, dtype=torch.int64, device=ids.device) << torch.arange(32, device=ids.device)
+    packed = (present[:, : words * 32].reshape(groups, words, 32) * weights).sum(-1)
+    return torch.where(packed >= 2 ** 31, packed - 2 ** 32, packed).to(torch.int32)
+
+
+@torch.no_grad()
+def context_mask(context, rows: int, n: int) -> Tensor:
+    """[rows, n] bool: the tokens of every row's context, from `context` = [(bits [groups, ceil(n / 32)], rows_per_group)]."""
+    mask = None
+    for bits, rpg in context:
+        shifts = torch.arange(32, device=bits.device, dtype=torch.int64)
+        unpacked = ((bits.long()[:, :, None] >> shifts) & 1).bool().reshape(bits.shape[0], -1)[:, :n]
+        m = unpacked.repeat_interleave(int(rpg), dim=0)[:rows]
+        if m.shape[0] != rows:
+            raise ValueError(f"a context bitmap of {bits.shape[0]} groups x {rpg} rows does not cover {rows} rows")
+        mask = m if mask is None else (mask | m)
+    return mask
+
+
+@torch.no_grad()
+def penalize_logits(logits: Tensor, repetition_penalty: Optional[float] = None, presence_penalty: Optional[float] = None,
+                    frequency_penalty: Optional[float] = None, logit_bias=None, context=(), gen: Optional[Tensor] = None,
+                    gen_len: Optional[Tensor] = None) -> Tensor:
+    """[rows, n] logits -> the penalised logits x in float64 (the comment block above), on the logits' device.  context:
+    [(bits, rows_per_group)]; gen [rows, stride] integer tokens with gen_len [rows] (None: no generated tokens)."""
+    check_penalties(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, logits.shape[-1])
+    rows, n = logits.shape
+    x = logits.double()
+    dev = x.device
+    counts = torch.zeros((rows, n + 1), dtype=torch.float64, device=dev)
+    if gen is not None and gen.shape[1] > 0:
+        g = gen.to(dev).long()
+        live = (g >= 0) & (g < n) & (torch.arange(g.shape[1], device=dev)[None, :] < gen_len.to(dev).long().reshape(-1, 1))
+        counts.scatter_add_(1, torch.where(live, g, torch.full_like(g, n)), torch.ones(g.shape, dtype=torch.float64, device=dev))
+    counts = counts[:, :n]
+    seen = counts > 0
+    r = 1.0 if repetition_penalty is None else float(repetition_penalty)
+    if r != 1.0:
+        ctx = context_mask([(b.to(dev), k) for b, k in context], rows, n) if len(context) else None
+        hit = seen if ctx is None else (seen | ctx)
+        x = torch.where(hit, torch.where(x > 0, x / r, x * r), x)
+    f, a = float(frequency_penalty or 0.0), float(presence_penalty or 0.0)
+    if f or a:
+        x = torch.where(seen, x - (f * counts + a * seen.double()), x)
+    bias = normalize_logit_bias(logit_bias, dev)
+    if bias is not None:
+        x[:, bias[0]] += bias[1].double()
+    return x

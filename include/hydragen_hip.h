@@ -45,8 +45,8 @@ extern "C" {
 #define HYD_API __attribute__((visibility("default")))
 
 /* 0.5.0 also carries the fp8 unique-cache entry points (hyd_kv_quant, hyd_*_kvq, hyd_kv_quant_supported) and the filtered
- * sampler (hyd_sample_filter_params, hyd_sample_tokens_filtered) and the scoring entry point (hyd_token_logprob_params,
- * hyd_token_logprobs): they are new symbols and new structs only -- no existing struct, entry point or result changed -- so a caller built against 0.5.0 without them is
+ * sampler (hyd_sample_filter_params, hyd_sample_tokens_filtered), the scoring entry point (hyd_token_logprob_params,
+ * hyd_token_logprobs) and the penalised sampler (hyd_sample_penalty_params, hyd_sample_tokens_penalized, hyd_token_bitmap_build): they are new symbols and new structs only -- no existing struct, entry point or result changed -- so a caller built against 0.5.0 without them is
  * unaffected and the version stays 500. */
 #define HYD_VERSION 500 /* 0.5.0: hyd_suffix_params.seq_order (schedule hint for ragged lengths); 0.4.0: hyd_add_rmsnorm, hyd_swiglu, hyd_sample_tokens (model-shell glue); 0.3.0: two-stream phases + hyd_decode_params.shared_max_workgroups, hyd_decode_two_stream_ok; 0.2.2: hyd_allreduce_params.timeout_log2_polls; 0.2.1: softmax_scale; 0.2.0: hyd_decode_params.phase, hyd_rope_params.max_pos, hyd_allreduce_* */
 #define HYD_MAX_LEVELS 8
@@ -338,6 +338,86 @@ typedef struct hyd_sample_filter_params {
 } hyd_sample_filter_params;
 
 HYD_API int hyd_sample_tokens_filtered(const hyd_sample_filter_params* p, void* stream);
+
+/* hyd_sample_tokens_filtered on PENALISED logits: repetition / presence / frequency penalties and a sparse logit bias, in the
+ * same single launch (one workgroup per row, no [rows, n] side tensor).  For one row l (length n), with
+ *   ctx  = the tokens of the row's context: the union of the row's bitmap rows, row b reading row b / rows_per_group of every
+ *          context bitmap (a prompt shared by a group of rows is one bitmap row of ceil(n / 32) words, bit v of the row = bit
+ *          v % 32 of word v / 32);
+ *   c[v] = how often v occurs among gen[row, 0 .. min(gen_len[row], gen_stride)) (entries outside [0, n) are ignored),
+ * the penalised logit x[v] is, in this order:
+ *   1. v in ctx or c[v] > 0:  x = l > 0 ? l / repetition_penalty : l * repetition_penalty (the HF / vLLM rule); else x = l;
+ *   2. x -= frequency_penalty * c[v] + presence_penalty * (c[v] > 0)   (the OpenAI / vLLM rule: generated tokens only);
+ *   3. v == bias_ids[k]:  x += bias_values[k]   (-inf bans the token; ids distinct, ids outside [0, n) are ignored).
+ *      The entry point cannot check that the ids are distinct: an id given twice gets the value at the bitwise OR of its
+ *      two (1-based) list positions if that is a position of the list, else no bias -- never a read outside the list.
+ * A token that no rule touches keeps its logit exactly; a touched one is evaluated in double from the fp32 / 16-bit logit
+ * and rounded ONCE to fp32.  Everything hyd_sample_tokens_filtered does then acts on x instead of l, unchanged: the cuts on
+ * the unscaled softmax(x), the draw argmax(x / temperature + g) with hyd_sample_tokens' noise for the same (seed, offset, row,
+ * column), temperature 0 = lowest-index argmax of x, -inf and NaN never kept (a row whose every x is one: token 0, kept 0,
+ * NaN log-prob), and logprobs[row] = log softmax(x)[token]: the PENALISED, unscaled, unfiltered distribution.  With every
+ * penalty neutral (1, 0, 0, no bitmap, no generated token, no bias) tokens, kept counts and log-probs are
+ * hyd_sample_tokens_filtered's bit for bit.  Fixed-point masses as there: a row's outputs do not depend on the run, the launch
+ * geometry or the other rows.  gen_len is read on the device at launch time.  append_out != 0: after the draw the kernel
+ * stores the token at gen[row, gen_len[row]] (if that is < gen_stride) and adds one to gen_len[row], so that a decode loop
+ * that feeds back what it samples needs no other launch to keep the list.
+ * Side memory is the bitmaps and gen; the kernel has no workspace.
+ * HYD_ERR_BAD_ARG: what hyd_sample_tokens_filtered refuses, repetition_penalty <= 0 or NaN or inf, a non-finite
+ * frequency_penalty / presence_penalty, n_context outside [0, HYD_SAMPLE_MAX_CONTEXT], a null context bitmap or rows_per_group
+ * <= 0, gen_len without gen (or gen without gen_len), gen_stride < 0, append_out without gen, n_bias outside
+ * [0, HYD_SAMPLE_BIAS_MAX] or n_bias > 0 without ids / values, misaligned pointers.  HYD_ERR_UNSUPPORTED: a bad dtype,
+ * n > HYD_SAMPLE_FILTER_MAX_N, gen_stride > HYD_SAMPLE_GEN_MAX. */
+#define HYD_SAMPLE_MAX_CONTEXT (HYD_MAX_LEVELS + 1) /* every shared level and the rows' own prompts */
+#define HYD_SAMPLE_BIAS_MAX 1024                    /* entries of the logit-bias list               */
+#define HYD_SAMPLE_GEN_MAX 2048                     /* generated tokens per row the kernel counts   */
+typedef struct hyd_token_bitmap {
+    const uint32_t* bits;   /* [groups, ceil(n / 32)]                                                */
+    int32_t rows_per_group; /* row b reads bitmap row b / rows_per_group                             */
+    int32_t reserved;
+} hyd_token_bitmap;
+
+typedef struct hyd_sample_penalty_params {
+    const void* logits;    /* [rows, n] HYD_F16 | HYD_BF16 | HYD_F32, row stride in elements        */
+    int64_t* out;          /* [rows] sampled token                                                  */
+    float* logprobs;       /* [rows] or NULL: log softmax(x)[out] (penalised, unscaled, unfiltered) */
+    int32_t* kept;         /* [rows] or NULL: number of tokens that survived the filters            */
+    int64_t row_stride;
+    uint64_t seed, offset; /* as hyd_sample_params                                                  */
+    int32_t rows, n, dtype;
+    float temperature;     /* >= 0                                                                  */
+    int32_t top_k;         /* 0 = off                                                               */
+    float top_p;           /* (0, 1]; 1 = off                                                       */
+    float min_p;           /* [0, 1]; 0 = off                                                       */
+    int32_t n_context;     /* context bitmaps in use                                                */
+    double repetition_penalty; /* > 0; 1 = off                                                      */
+    double frequency_penalty;  /* finite; 0 = off                                                   */
+    double presence_penalty;   /* finite; 0 = off                                                   */
+    hyd_token_bitmap context[HYD_MAX_LEVELS + 1];
+    int32_t* gen;          /* [rows, gen_stride] generated tokens, or NULL (written only by append_out) */
+    int32_t* gen_len;      /* [rows] device; NULL iff gen is NULL                                   */
+    int32_t gen_stride;    /* <= HYD_SAMPLE_GEN_MAX                                                 */
+    int32_t append_out;    /* != 0: append the drawn token to gen / gen_len                         */
+    const int64_t* bias_ids;  /* [n_bias] distinct                                                  */
+    const float* bias_values; /* [n_bias] finite or -inf                                            */
+    int32_t n_bias;        /* <= HYD_SAMPLE_BIAS_MAX                                                */
+    int32_t reserved;
+} hyd_sample_penalty_params;
+
+HYD_API int hyd_sample_tokens_penalized(const hyd_sample_penalty_params* p, void* stream);
+
+/* Presence bitmap of token ids: bits[g, v / 32] |= 1 << (v % 32) for every v = ids[g, j], j < lens[g] (lens NULL: j < L), 0 <= v
+ * < n.  The kernel ORs into `bits` (atomic OR): the caller zeroes it first, or accumulates several id tensors into one bitmap.
+ * One launch, nothing else is allocated.  Null ids / bits, groups < 0, L < 0, n <= 0 or n > HYD_SAMPLE_FILTER_MAX_N, id_stride
+ * < L and misaligned pointers give HYD_ERR_BAD_ARG. */
+typedef struct hyd_token_bitmap_params {
+    const int64_t* ids;    /* [groups, L], row stride id_stride (elements)                          */
+    const int64_t* lens;   /* [groups] or NULL                                                      */
+    uint32_t* bits;        /* [groups, ceil(n / 32)]                                                */
+    int64_t id_stride;
+    int32_t groups, L, n, reserved;
+} hyd_token_bitmap_params;
+
+HYD_API int hyd_token_bitmap_build(const hyd_token_bitmap_params* p, void* stream);
 
 /* Log-probabilities of GIVEN tokens (scoring, teacher forcing) and the top-N alternatives of every row.  For one row l (length n)
  * and its target token t, with the valid logits those that are neither NaN nor -inf and m = their max:
