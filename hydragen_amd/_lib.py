@@ -162,6 +162,20 @@ class TokenLogprobParams(C.Structure):
 TOP_LOGPROBS_MAX = 20  # HYD_TOP_LOGPROBS_MAX
 
 
+STOP_MAX_EOS, STOP_MAX_SEQS, STOP_MAX_LEN = 16, 32, 16  # HYD_STOP_MAX_EOS / _SEQS / _LEN
+
+
+class StopParams(C.Structure):
+    _fields_ = [
+        ("tok", C.c_void_p), ("out", C.c_void_p), ("length", C.c_void_p), ("reason", C.c_void_p), ("stop_index", C.c_void_p),
+        ("live", C.c_void_p), ("stop_tokens", C.c_void_p), ("start_pos", C.c_void_p), ("shared_len", C.c_void_p),
+        ("feed", C.c_void_p), ("next_pos", C.c_void_p), ("out_stride", C.c_int64), ("pad", C.c_int64),
+        ("eos", C.c_int64 * STOP_MAX_EOS), ("stop_lens", C.c_int32 * STOP_MAX_SEQS),
+        ("rows", C.c_int32), ("t", C.c_int32), ("n_eos", C.c_int32), ("n_stop", C.c_int32),
+        ("include_stop", C.c_int32), ("retire", C.c_int32),
+    ]
+
+
 class KvQuant(C.Structure):
     _fields_ = [("kv_dtype", C.c_int32), ("reserved", C.c_int32), ("k_scale", C.c_void_p), ("v_scale", C.c_void_p)]
 
@@ -205,6 +219,7 @@ EXPORTS = {
     "hyd_sample_tokens_penalized": (C.c_int, [C.POINTER(SamplePenaltyParams), C.c_void_p]),
     "hyd_token_bitmap_build": (C.c_int, [C.POINTER(TokenBitmapParams), C.c_void_p]),
     "hyd_token_logprobs": (C.c_int, [C.POINTER(TokenLogprobParams), C.c_void_p]),
+    "hyd_stop_update": (C.c_int, [C.POINTER(StopParams), C.c_void_p]),
     "hyd_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }

@@ -801,6 +801,41 @@ int hyd_token_logprobs(const hyd_token_logprob_params* p, void* stream) {
     return rc ? fail(HYD_ERR_LAUNCH, "token_logprob kernel launch failed: hip error %d", rc) : HYD_OK;
 }
 
+int hyd_stop_update(const hyd_stop_params* p, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    if (p->rows < 0) return fail(HYD_ERR_BAD_ARG, "rows %d", p->rows);
+    if (p->n_eos < 0 || p->n_eos > HYD_STOP_MAX_EOS) return fail(HYD_ERR_BAD_ARG, "n_eos %d: 0 to %d EOS ids", p->n_eos, HYD_STOP_MAX_EOS);
+    if (p->n_stop < 0 || p->n_stop > HYD_STOP_MAX_SEQS) return fail(HYD_ERR_BAD_ARG, "n_stop %d: 0 to %d stop sequences", p->n_stop, HYD_STOP_MAX_SEQS);
+    for (int k = 0; k < p->n_stop; ++k)
+        if (p->stop_lens[k] < 1 || p->stop_lens[k] > HYD_STOP_MAX_LEN)
+            return fail(HYD_ERR_BAD_ARG, "stop_lens[%d] = %d: a stop sequence holds 1 to %d tokens", k, p->stop_lens[k], HYD_STOP_MAX_LEN);
+    if (p->t < 0 || p->t >= p->out_stride) return fail(HYD_ERR_BAD_ARG, "t %d outside [0, out_stride = %lld)", p->t, (long long)p->out_stride);
+    if (!p->tok || !p->out || !p->length || !p->reason || !p->stop_index || !p->live)
+        return fail(HYD_ERR_BAD_ARG, "tok / out / length / reason / stop_index / live is null");
+    if (!p->start_pos || !p->feed || !p->next_pos) return fail(HYD_ERR_BAD_ARG, "start_pos / feed / next_pos is null");
+    if (p->n_stop > 0 && !p->stop_tokens) return fail(HYD_ERR_BAD_ARG, "n_stop %d needs stop_tokens (null)", p->n_stop);
+    if ((reinterpret_cast<uintptr_t>(p->tok) & 7u) != 0 || (reinterpret_cast<uintptr_t>(p->out) & 7u) != 0 ||
+        (reinterpret_cast<uintptr_t>(p->stop_tokens) & 7u) != 0 || (reinterpret_cast<uintptr_t>(p->start_pos) & 7u) != 0 ||
+        (reinterpret_cast<uintptr_t>(p->shared_len) & 7u) != 0 || (reinterpret_cast<uintptr_t>(p->feed) & 7u) != 0 ||
+        (reinterpret_cast<uintptr_t>(p->next_pos) & 7u) != 0)
+        return fail(HYD_ERR_BAD_ARG, "tok / out / stop_tokens / start_pos / shared_len / feed / next_pos is not aligned to its element size");
+    if ((reinterpret_cast<uintptr_t>(p->length) & 3u) != 0 || (reinterpret_cast<uintptr_t>(p->reason) & 3u) != 0 ||
+        (reinterpret_cast<uintptr_t>(p->stop_index) & 3u) != 0 || (reinterpret_cast<uintptr_t>(p->live) & 3u) != 0)
+        return fail(HYD_ERR_BAD_ARG, "length / reason / stop_index / live is not aligned to its element size");
+    if (p->rows == 0) return HYD_OK;
+    StopArgs a;
+    memset(&a, 0, sizeof(a));
+    a.tok = p->tok; a.out = p->out; a.length = p->length; a.reason = p->reason; a.stop_index = p->stop_index; a.live = p->live;
+    a.stop_tokens = p->stop_tokens; a.start_pos = p->start_pos; a.shared_len = p->shared_len; a.feed = p->feed; a.next_pos = p->next_pos;
+    a.out_stride = p->out_stride; a.pad = p->pad;
+    for (int i = 0; i < p->n_eos; ++i) a.eos[i] = p->eos[i];
+    for (int k = 0; k < p->n_stop; ++k) a.stop_lens[k] = p->stop_lens[k];
+    a.rows = p->rows; a.t = p->t; a.n_eos = p->n_eos; a.n_stop = p->n_stop;
+    a.include_stop = p->include_stop ? 1 : 0; a.retire = p->retire ? 1 : 0;
+    const int rc = launch_stop_update(a, static_cast<hipStream_t>(stream));
+    return rc ? fail(HYD_ERR_LAUNCH, "stop_update kernel launch failed: hip error %d", rc) : HYD_OK;
+}
+
 // hyd_decode_params.single_launch_small: one uniform shared level that already counts as small (few query rows per
 // (group, kv head), short prefix), unique keys present, the same token strides in the shared and the unique tensors, and
 // so few keys in all that the call is launch latency.  Measured per graph-replayed call (tests/probes/single_launch_probe.py,

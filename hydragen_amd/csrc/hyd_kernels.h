@@ -209,6 +209,24 @@ struct TokenLogprobArgs {  // token_logprob.hip: log-probs of given tokens, gree
     int32_t vec_ok;         // rows are 16-byte aligned
 };
 
+struct StopArgs {  // stop_update.hip: EOS ids / stop sequences judged per row, the next step's token and position (hyd_stop_update)
+    const int64_t* tok;
+    int64_t* out;
+    int32_t* length;
+    int32_t* reason;
+    int32_t* stop_index;
+    int32_t* live;
+    const int64_t* stop_tokens;  // [n_stop, HYD_STOP_MAX_LEN]
+    const int64_t* start_pos;
+    const int64_t* shared_len;   // may be null
+    int64_t* feed;
+    int64_t* next_pos;
+    int64_t out_stride, pad;
+    int64_t eos[HYD_STOP_MAX_EOS];
+    int32_t stop_lens[HYD_STOP_MAX_SEQS];
+    int32_t rows, t, n_eos, n_stop, include_stop, retire;
+};
+
 // launchers (defined next to the kernels); return hipError_t as int
 int launch_prefix_w64(const PrefixArgs& a, int dtype, int D, bool causal, int grid, hipStream_t s);
 int launch_prefix_w64_f16(const PrefixArgs& a, int D, bool causal, int grid, hipStream_t s);  // prefix_attn_w64_f16.hip
@@ -220,6 +238,7 @@ int launch_sample_filter(const FilterArgs& a, int dtype, hipStream_t s);  // sam
 int launch_sample_penalty(const PenaltyArgs& a, int dtype, hipStream_t s);     // sample_penalty.hip
 int launch_token_bitmap(const BitmapArgs& a, hipStream_t s);                     // sample_penalty.hip
 int launch_token_logprob(const TokenLogprobArgs& a, int dtype, hipStream_t s);  // token_logprob.hip
+int launch_stop_update(const StopArgs& a, hipStream_t s);                          // stop_update.hip
 int launch_suffix(const SuffixArgs& a, int dtype, int D, hipStream_t s);
 bool suffix_gqa_eligible(const SuffixArgs& a, int D, bool any_shape);
 bool suffix_fp8_eligible(const SuffixArgs& a, int D);                                 // suffix_attn_fp8.hip, shapes only

@@ -1,4 +1,4 @@
-"""Python face of `hyd_add_rmsnorm` / `hyd_swiglu` / `hyd_sample_tokens[_filtered]` / `hyd_token_logprobs` (include/hydragen_hip.h): the elementwise glue of the decoder layer
+"""Python face of `hyd_add_rmsnorm` / `hyd_swiglu` / `hyd_sample_tokens[_filtered]` / `hyd_token_logprobs` / `hyd_stop_update` (include/hydragen_hip.h): the elementwise glue of the decoder layer
 around the attention block -- residual add + RMSNorm (/root/reference/hydragen/llama.py:615-631 with transformers'
 LlamaRMSNorm, llama.py:605-608,656) and the SwiGLU gate (transformers' LlamaMLP, llama.py:2,604) -- each as one
 HIP kernel instead of two torch launches."""
@@ -15,7 +15,7 @@ from torch import Tensor
 from . import _lib
 from ._lib import AddRmsnormParams, SwigluParams
 from .flash import _dtype_code, _require_gpu, _stream
-from . import sampling
+from . import sampling, stopping
 from .sampling import check_filters, filters_active
 from .scoring import check_top_n, token_logprobs_reference
 
@@ -324,3 +324,62 @@ def token_logprobs(logits: Tensor, targets: Tensor, top_n: int = 0):
             p.top_ids, p.top_logprobs = top_ids.data_ptr(), top_lp.data_ptr()
         _lib.check(lib.hyd_token_logprobs(C.byref(p), _stream()))
     return lp, greedy.view(torch.bool), top_ids, top_lp
+
+
+def stop_update(tok: Tensor, t: int, spec: stopping.StopSpec, out: Tensor, length: Tensor, reason: Tensor, stop_index: Tensor,
+                live: Tensor, start_pos: Tensor, shared_len: Optional[Tensor] = None, retire: bool = True,
+                stop_tokens: Optional[Tensor] = None):
+    """hyd_stop_update, one launch: judge the tokens `tok` [rows] (or [rows, 1]) int64 just drawn as step t of a generation whose
+    state is (out int64 [rows, steps], length / reason / stop_index int32 [rows], live int32 [steps]; stopping.new_state), update
+    that state in place and return (feed, next_pos) int64 [rows] for the next decode step; hydragen_amd/stopping.py states the
+    rules.  start_pos int64 [rows]: the position step 0's token is fed at; shared_len int64 [rows] or None and retire: a finished
+    row's position becomes shared_len - 1, which retires it from the unique K/V stream.  stop_tokens: spec.stop_table(device)[0]
+    made once per generation (None: made here, one host-to-device copy).  Nothing synchronises.  CPU tensors take
+    stopping.stop_update_reference."""
+    tok = tok.reshape(-1)
+    rows = tok.shape[0]
+    if tok.dtype != torch.int64 or out.ndim != 2 or out.shape[0] != rows or out.dtype != torch.int64 or out.stride(1) != 1:
+        raise ValueError(f"tok must be int64 [rows] and out int64 [rows, steps] with a unit last stride, got {tuple(tok.shape)} {tok.dtype} "
+                         f"and {tuple(out.shape)} {out.dtype}")
+    steps = out.shape[1]
+    for name, x, n in (("length", length, rows), ("reason", reason, rows), ("stop_index", stop_index, rows), ("live", live, steps)):
+        if x.dtype != torch.int32 or x.shape != (n,) or not x.is_contiguous() or x.device != tok.device:
+            raise ValueError(f"{name} must be a contiguous int32 [{n}] on {tok.device}, got {tuple(x.shape)} {x.dtype} on {x.device}")
+    for name, x in (("start_pos", start_pos), ("shared_len", shared_len)):
+        if x is not None and (x.dtype != torch.int64 or x.shape != (rows,) or not x.is_contiguous() or x.device != tok.device):
+            raise ValueError(f"{name} must be a contiguous int64 [{rows}] on {tok.device}, got {tuple(x.shape)} {x.dtype} on {x.device}")
+    if out.device != tok.device:
+        raise ValueError(f"out is on {out.device}, tok on {tok.device}")
+    if not 0 <= t < steps:
+        raise ValueError(f"t {t} outside [0, {steps})")
+    if not tok.is_cuda:
+        return stopping.stop_update_reference(tok, t, spec, out, length, reason, stop_index, live, start_pos, shared_len, retire)
+    _require_gpu(tok)
+    lib = _lib.load()
+    tok = tok.contiguous()
+    feed = torch.empty((rows,), dtype=torch.int64, device=tok.device)
+    next_pos = torch.empty((rows,), dtype=torch.int64, device=tok.device)
+    p = _lib.StopParams()
+    if spec.stops:
+        if stop_tokens is None:
+            stop_tokens = spec.stop_table(tok.device)[0]
+        if (stop_tokens.shape != (len(spec.stops), _lib.STOP_MAX_LEN) or stop_tokens.dtype != torch.int64 or not stop_tokens.is_contiguous()
+                or stop_tokens.device != tok.device):
+            raise ValueError(f"stop_tokens must be a contiguous int64 [{len(spec.stops)}, {_lib.STOP_MAX_LEN}] on {tok.device}")
+        p.stop_tokens = stop_tokens.data_ptr()
+    if len(spec.eos) > _lib.STOP_MAX_EOS or len(spec.stops) > _lib.STOP_MAX_SEQS:
+        raise ValueError(f"{len(spec.eos)} EOS ids / {len(spec.stops)} stop sequences: at most {_lib.STOP_MAX_EOS} / {_lib.STOP_MAX_SEQS}")
+    for i, e in enumerate(spec.eos):
+        p.eos[i] = e
+    for k, s_ in enumerate(spec.stops):
+        p.stop_lens[k] = len(s_)
+    p.tok, p.out, p.length, p.reason = tok.data_ptr(), out.data_ptr(), length.data_ptr(), reason.data_ptr()
+    p.stop_index, p.live, p.start_pos = stop_index.data_ptr(), live.data_ptr(), start_pos.data_ptr()
+    if shared_len is not None:
+        p.shared_len = shared_len.data_ptr()
+    p.feed, p.next_pos = feed.data_ptr(), next_pos.data_ptr()
+    p.out_stride, p.pad = out.stride(0) if rows > 1 else steps, spec.pad
+    p.rows, p.t, p.n_eos, p.n_stop = rows, t, len(spec.eos), len(spec.stops)
+    p.include_stop, p.retire = int(spec.include_stop), int(bool(retire))
+    _lib.check(lib.hyd_stop_update(C.byref(p), _stream()))
+    return feed, next_pos

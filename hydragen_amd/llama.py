@@ -23,7 +23,7 @@ from typing import List, Optional, Union
 import torch
 from torch import Tensor, nn
 
-from . import layer_ops, placement, sampling, scoring
+from . import layer_ops, placement, sampling, scoring, stopping
 from .attention import hydragen_attention
 from . import flash as _flash
 from .flash import flash_attention, flash_attention_seqlen
@@ -897,12 +897,13 @@ class HydragenLlamaForCausalLM(nn.Module):
     def generate(self, input_ids: Optional[Union[Tensor, list[Tensor]]] = None,
                  seq_lens: Optional[Union[Tensor, list[Tensor]]] = None, starting_logits: Optional[Tensor] = None,
                  num_return_sequences: int = 1, max_new_tokens: int = 5, temperature: float = 1.0,
-                 top_p: Optional[float] = None, eos_token_id: Optional[int] = None, return_logits: bool = False,
+                 top_p: Optional[float] = None, eos_token_id: Optional[Union[int, list, tuple]] = None, return_logits: bool = False,
                  shared_cache_op: str = SharedCacheOp.PRESERVE, disable_hydragen: bool = False,
                  disable_attention: bool = False, disable_hierarchy: bool = False,
                  token_overrides: Optional[Tensor] = None, top_k: Optional[int] = None, min_p: Optional[float] = None,
                  return_logprobs: bool = False, top_logprobs: int = 0, repetition_penalty: Optional[float] = None,
-                 presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None, logit_bias=None):
+                 presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None, logit_bias=None,
+                 stop=None, pad_token_id: Optional[int] = None, include_stop: bool = False, return_finish: bool = False):
         """Sampling: top_k / top_p / min_p cut the UNSCALED softmax(logits) (the reference's top-p order; HF applies the
         temperature first), then a token is drawn from softmax(logits / temperature) over the kept tokens.  Returns the
         tokens [B, generated]; return_logits adds the per-step fp32 logits, return_logprobs the fp32 [B, generated]
@@ -917,9 +918,34 @@ class HydragenLlamaForCausalLM(nn.Module):
         sampled tokens, or token_overrides where given.  Cuts, draw and return_logprobs then act on the PENALISED logits
         (log softmax of the penalised, unscaled, unfiltered logits: the distribution the draw's policy is defined by);
         return_logits and top_logprobs keep reporting the model's raw distribution.  With every penalty off, generate()
-        runs exactly the launches it runs without these arguments."""
+        runs exactly the launches it runs without these arguments.
+        Stop conditions decided on the device (hyd_stop_update; hydragen_amd/stopping.py states the rules): eos_token_id given as a
+        LIST or tuple of ids (a list of one included), stop = a list of token-id sequences (lists, tuples or 1-d tensors, ragged; up
+        to 32 of 1..16 tokens), pad_token_id (default: the first EOS id if any, else 0) or return_finish select this path; an int
+        eos_token_id alone keeps the loop and the result it always had.  No tokenizer is involved: stop sequences match TOKEN ids,
+        which is not string matching across tokenisation boundaries (a stop string the tokenizer merges with its neighbours in
+        context is not found: pass every tokenisation that should stop).  A row finishes at its first EOS id (kept) or stop sequence
+        (cut unless include_stop); from then on its columns hold pad_token_id, it is fed pad, and -- with the fused decode preamble
+        -- it leaves the unique K/V stream: no K/V is appended for it and the suffix pass sees length 0 (what that gives back of
+        a step is measured in profiles/stopping.md).  The host does not look at a token per step:
+        it polls the count of running rows every stop_poll_steps steps and leaves the loop when that is 0.  The returned matrix is
+        [B, max(lengths)], whenever the exit was noticed.  return_finish appends a stopping.Finish(lengths, reasons, stop_index)
+        (int32 [B] each; reason 0 = ran to max_new_tokens, 1 = EOS, 2 = stop sequence) as the last return value.  With
+        return_logprobs, entries at or past a row's length are 0.0; with top_logprobs, id -1 / -inf; the return_logits rows of a
+        finished sequence past its length are unspecified.  Penalties keep working (what a finished row draws is ignored).
+        token_overrides cannot be combined with these arguments."""
         if not self.kv_cache_allocated:
             raise RuntimeError("call setup_caches() before generate()")
+        stop_spec = None
+        if isinstance(eos_token_id, (list, tuple)) or stop is not None or pad_token_id is not None or return_finish:
+            if token_overrides is not None:
+                raise ValueError("token_overrides (teacher forcing) has nothing to stop: it cannot be combined with a list of EOS ids, "
+                                 "stop, pad_token_id or return_finish")
+            stop_spec = stopping.check_stop(eos_token_id, stop, pad_token_id, include_stop, self.vocab_size)
+            if not self.lm_head.weight.is_cuda:
+                raise ValueError("stop conditions are decided by a HIP kernel (hyd_stop_update): the model must be on the GPU; "
+                                 "stopping.truncate_reference applies the same rules to CPU tokens")
+            eos_token_id = None
         if (input_ids is None) == (starting_logits is None):
             raise ValueError("pass exactly one of input_ids and starting_logits")
         if temperature < 0:
@@ -968,7 +994,7 @@ class HydragenLlamaForCausalLM(nn.Module):
                 samp["penalties"] = self._penalties(batch, unique, num_return_sequences, max_new_tokens, repetition_penalty,
                                                     presence_penalty, frequency_penalty, logit_bias, counted)
             return self._decode(logits[:, -1], unique, num_return_sequences, max_new_tokens, samp,
-                                eos_token_id, return_logits, token_overrides, return_logprobs, top_n)
+                                eos_token_id, return_logits, token_overrides, return_logprobs, top_n, stop_spec, return_finish)
         finally:
             if shared_cache_op == SharedCacheOp.PRESERVE:
                 self.truncate_shared_caches(levels_before)
@@ -1130,7 +1156,7 @@ class HydragenLlamaForCausalLM(nn.Module):
             is_greedy=(greedy | ~live).all(1), top_ids=top_ids if top_n else None, top_logprobs=top_lp if top_n else None)
 
     def _decode(self, prefill_logits, unique, fan, max_new_tokens, samp, eos_token_id, return_logits, token_overrides,
-                return_logprobs=False, top_n=0):
+                return_logprobs=False, top_n=0, stop_spec=None, return_finish=False):
         pen = samp.get("penalties")
         if pen is not None and pen.gen is None:
             pen = None  # a bias alone: no list of generated tokens to keep
@@ -1172,6 +1198,9 @@ class HydragenLlamaForCausalLM(nn.Module):
                 order = self.seq_order_buf[: lens0.numel()]
                 order.copy_(_flash.longest_first(lens0))
         with _flash.seq_order(order, check=False):
+            if stop_spec is not None:
+                return self._decode_steps_stop(first, start, kept_logits, graphed, max_new_tokens, samp, return_logits, kept_lp,
+                                               kept_top, stop_spec, return_finish)
             return self._decode_steps(feed, start, tokens, kept_logits, done, graphed, max_new_tokens, samp, eos_token_id,
                                       return_logits, token_overrides, kept_lp, kept_top)
 
@@ -1220,3 +1249,86 @@ class HydragenLlamaForCausalLM(nn.Module):
         if kept_top is not None:
             ret = ret + (torch.cat([i for i, _ in kept_top], dim=1), torch.cat([t for _, t in kept_top], dim=1))
         return ret if len(ret) > 1 else out
+
+    # hyd_stop_update path: every this many decode steps the host starts a non-blocking copy of the running-row count of the
+    # step just enqueued and looks at it one step later (tests shrink it)
+    stop_poll_steps = 8
+    # None: finished rows are retired from the unique K/V stream whenever the fused decode preamble is in use; False: never
+    # (tools/stop_bench.py and the tests compare the two: only the step time may depend on it, never a token)
+    stop_retire: Optional[bool] = None
+
+    def _decode_steps_stop(self, first, start, kept_logits, graphed, max_new_tokens, samp, return_logits, kept_lp, kept_top,
+                           spec, return_finish):
+        """_decode_steps with the stop conditions of `spec` decided by hyd_stop_update after every sampling launch: the kernel
+        writes the output matrix, keeps lengths and finish reasons, and hands back the token and the position to feed next."""
+        raw = not return_logits and (self.fused_sampling_filters or not sampling.filters_active(
+            samp["top_k"], samp["top_p"], samp["min_p"]))
+        # (penalties: _decode has switched the sampler's own append on -- nothing is overridden here -- so the list of generated
+        # tokens follows the draws; what a finished row draws goes nowhere else)
+        dev = first.device
+        B = first.shape[0]
+        attn = self.model.layers[0].self_attn
+        # a retired row is fed position shared_len - 1: cache index -1, which the fused preamble skips and the torch scatter of
+        # update_per_completion_kvs would not
+        retire = all(l.self_attn.use_fused_decode for l in self.model.layers) if self.stop_retire is None else bool(self.stop_retire)
+        if retire and not all(l.self_attn.use_fused_decode for l in self.model.layers):
+            raise ValueError("stop_retire needs the fused decode preamble (use_fused_decode) in every layer")
+        shared_len = None if attn.disable_hydragen else self.get_shared_cache_len(B).contiguous()
+        start_pos = start.reshape(-1).long().contiguous()
+        out, length, reason, stop_index, live = stopping.new_state(B, max_new_tokens, spec, dev)
+        stop_tokens = spec.stop_table(dev)[0] if spec.stops else None
+        poll = max(1, int(self.stop_poll_steps))
+        # (page-locked once per model, not once per call: every slot is written by its copy before it is read, and no copy
+        # is left in flight when a generation returns)
+        polled = getattr(self, "_stop_polled", None)
+        if polled is None or polled.numel() < max_new_tokens // poll + 1:
+            polled = self._stop_polled = torch.empty((max(max_new_tokens // poll + 1, 512),), dtype=torch.int32).pin_memory()
+        pending = None  # (slot, event) of the copy started at the previous step
+
+        def update(tok, t):
+            return layer_ops.stop_update(tok, t, spec, out, length, reason, stop_index, live, start_pos, shared_len, retire, stop_tokens)
+
+        feed, pos = update(first, 0)
+        steps = 1  # columns of `out` written
+        for step in range(max_new_tokens - 1):
+            logits = self(input_ids=feed[:, None], position_ids=pos[:, None], use_graph=graphed, raw_logits=raw)[:, -1]
+            if return_logits:
+                kept_logits.append(logits)
+            nxt = self.sample_from_logits(logits, return_logprobs=kept_lp is not None, **samp)
+            if kept_lp is not None:
+                nxt, lp = nxt
+                kept_lp.append(lp)
+            if kept_top is not None:
+                _, _, ids, tlp = layer_ops.token_logprobs(logits, nxt[:, 0], kept_top[0][0].shape[-1])
+                kept_top.append((ids[:, None], tlp[:, None]))
+            feed, pos = update(nxt, steps)
+            steps += 1
+            # The count of running rows, without draining the launch queue: the copy started after step c is waited for after step
+            # c + 1 has been enqueued, so the device always has a step of work queued behind what the host waits for, and an
+            # exit is noticed at most stop_poll_steps steps late.  (Only looking at events that happen to be complete would let
+            # the host run ahead by the whole launch queue before it notices anything.)
+            if pending is not None:
+                slot, ev = pending
+                ev.synchronize()
+                pending = None
+                if int(polled[slot]) == 0:
+                    break
+            if steps % poll == 0 and steps < max_new_tokens:
+                slot = steps // poll
+                polled[slot : slot + 1].copy_(live[steps - 1 : steps], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                pending = (slot, ev)
+        check_collectives()
+        width = int(length.max().item()) if B else 0  # (the one synchronisation of the generation)
+        tokens = out[:, :width]
+        past = torch.arange(width, device=dev)[None, :] >= length[:, None]
+        ret = (tokens, kept_logits[:width]) if return_logits else (tokens,)
+        if kept_lp is not None:
+            ret = ret + (torch.cat(kept_lp, dim=-1)[:, :width].masked_fill(past, 0.0),)
+        if kept_top is not None:
+            ret = ret + (torch.cat([i for i, _ in kept_top], dim=1)[:, :width].masked_fill(past[:, :, None], -1),
+                         torch.cat([t for _, t in kept_top], dim=1)[:, :width].masked_fill(past[:, :, None], float("-inf")))
+        if return_finish:
+            ret = ret + (stopping.Finish(length, reason, stop_index),)
+        return ret if len(ret) > 1 else tokens

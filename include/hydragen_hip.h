@@ -46,7 +46,7 @@ extern "C" {
 
 /* 0.5.0 also carries the fp8 unique-cache entry points (hyd_kv_quant, hyd_*_kvq, hyd_kv_quant_supported) and the filtered
  * sampler (hyd_sample_filter_params, hyd_sample_tokens_filtered), the scoring entry point (hyd_token_logprob_params,
- * hyd_token_logprobs) and the penalised sampler (hyd_sample_penalty_params, hyd_sample_tokens_penalized, hyd_token_bitmap_build): they are new symbols and new structs only -- no existing struct, entry point or result changed -- so a caller built against 0.5.0 without them is
+ * hyd_token_logprobs) and the penalised sampler (hyd_sample_penalty_params, hyd_sample_tokens_penalized, hyd_token_bitmap_build) and the stop-condition entry point (hyd_stop_params, hyd_stop_update): they are new symbols and new structs only -- no existing struct, entry point or result changed -- so a caller built against 0.5.0 without them is
  * unaffected and the version stays 500. */
 #define HYD_VERSION 500 /* 0.5.0: hyd_suffix_params.seq_order (schedule hint for ragged lengths); 0.4.0: hyd_add_rmsnorm, hyd_swiglu, hyd_sample_tokens (model-shell glue); 0.3.0: two-stream phases + hyd_decode_params.shared_max_workgroups, hyd_decode_two_stream_ok; 0.2.2: hyd_allreduce_params.timeout_log2_polls; 0.2.1: softmax_scale; 0.2.0: hyd_decode_params.phase, hyd_rope_params.max_pos, hyd_allreduce_* */
 #define HYD_MAX_LEVELS 8
@@ -223,6 +223,9 @@ HYD_API size_t hyd_workspace_bytes(int32_t B, int32_t nq, int32_t Hq, int32_t Hk
  * position - shared_len (llama.py:236-262, 487-492) and seq_lens = index + 1 (llama.py:569),
  * in one kernel.  q/k/v are [B, 1, H, D] with heads contiguous; cos/sin are fp32 [max_pos, D]
  * tables in the rotate-half convention (first D/2 columns are read).
+ * Contract: a position below the row's shared length (cache index < 0) writes no K/V for that row, and position
+ * shared_len - 1 (-1 without shared_len) reports seq_lens[b] = 0 -- the row takes no part in the suffix pass of the step;
+ * callers may rely on it (hyd_stop_update retires the finished rows of a generation this way).
  * ------------------------------------------------------------------------------------------ */
 typedef struct hyd_rope_params {
     const void* q;               /* [B, 1, Hq, D], batch stride q_batch_stride                   */
@@ -448,6 +451,53 @@ typedef struct hyd_token_logprob_params {
 } hyd_token_logprob_params;
 
 HYD_API int hyd_token_logprobs(const hyd_token_logprob_params* p, void* stream);
+
+/* Stop conditions of a generation, decided on the device: one launch per decode step, after the sampling launch.  Row b's token
+ * of step t (tok[b]; t = 0 is the token drawn from the prefill logits) is judged by these rules, in this order
+ * (hydragen_amd/stopping.py states the same definition in torch):
+ *   (a) reason[b] != 0 (the row finished at an earlier step): out[b, t] = pad, nothing else changes;
+ *   (b) otherwise out[b, t] = tok[b]; tok[b] == eos[i] for the lowest i < n_eos: reason 1, stop_index i, length t + 1 (the EOS
+ *       token is kept);
+ *   (c) otherwise the stop sequences in list order: sequence k (stop_lens[k] = len tokens, stop_tokens[k, 0 .. len)) matches
+ *       when t + 1 >= len and out[b, t + 1 - len .. t] equals it -- never reaching back in front of step 0, and never across
+ *       columns a finished row has padded, since only running rows are tested; the lowest matching k gives reason 2,
+ *       stop_index k; include_stop == 0: the len matched columns become pad and length = t + 1 - len, else they stay and
+ *       length = t + 1;
+ *   (d) otherwise the row keeps running: length = t + 1.
+ * Then, for the next step: feed[b] = tok[b] for a running row, pad for a finished one; next_pos[b] = start_pos[b] + t for a
+ * running row and shared_len[b] - 1 (-1 with shared_len NULL) for a finished one -- the position at which
+ * hyd_rope_append_decode writes no K/V and reports length 0, so that the row leaves the suffix pass; retire == 0: start_pos[b]
+ * + t for every row.  live[t] += the number of rows still running after the step (the caller zeroes live once per generation).
+ * A row's outputs depend on that row alone, not on the launch geometry.  t is a host value: the launch is not meant for a
+ * captured graph that is replayed with another t.
+ * HYD_ERR_BAD_ARG: a null tok / out / length / reason / stop_index / live / start_pos / feed / next_pos, rows < 0, n_eos outside
+ * [0, HYD_STOP_MAX_EOS], n_stop outside [0, HYD_STOP_MAX_SEQS], n_stop > 0 without stop_tokens, a stop length outside
+ * [1, HYD_STOP_MAX_LEN], t outside [0, out_stride), misaligned pointers.  rows == 0 succeeds without a launch. */
+#define HYD_STOP_MAX_EOS 16
+#define HYD_STOP_MAX_SEQS 32
+#define HYD_STOP_MAX_LEN 16
+typedef struct hyd_stop_params {
+    const int64_t* tok;         /* [rows] the tokens just drawn                                              */
+    int64_t* out;               /* [rows, out_stride] the generation's output matrix; column t is written     */
+    int32_t* length;            /* [rows] kept tokens                                                        */
+    int32_t* reason;            /* [rows] 0 = running, 1 = EOS, 2 = stop sequence                            */
+    int32_t* stop_index;        /* [rows] which EOS id / stop sequence matched; the caller starts it at -1   */
+    int32_t* live;              /* [out_stride] rows still running after each step; zeroed by the caller     */
+    const int64_t* stop_tokens; /* [n_stop, HYD_STOP_MAX_LEN] device, or NULL when n_stop == 0               */
+    const int64_t* start_pos;   /* [rows] absolute position at which a row's token of step 0 is fed          */
+    const int64_t* shared_len;  /* [rows] or NULL (= 0)                                                      */
+    int64_t* feed;              /* [rows] out: the token to feed next                                        */
+    int64_t* next_pos;          /* [rows] out: the position to feed it at                                    */
+    int64_t out_stride;         /* elements                                                                  */
+    int64_t pad;
+    int64_t eos[HYD_STOP_MAX_EOS];         /* HOST values                                                    */
+    int32_t stop_lens[HYD_STOP_MAX_SEQS];  /* HOST values, each in [1, HYD_STOP_MAX_LEN]                     */
+    int32_t rows, t, n_eos, n_stop;
+    int32_t include_stop;       /* != 0: a matched stop sequence stays in out and counts in length           */
+    int32_t retire;             /* != 0: finished rows get the position that retires them from the K/V stream */
+} hyd_stop_params;
+
+HYD_API int hyd_stop_update(const hyd_stop_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * All-reduce(sum) of the tensor-parallel block output (hydragen/tp.py:83-87 after down_proj, :108-112 after
