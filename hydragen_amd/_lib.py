@@ -14,6 +14,7 @@ from pathlib import Path
 HYD_MAX_LEVELS = 8
 HYD_F16, HYD_BF16, HYD_F32 = 0, 1, 2
 HYD_FP8_E4M3 = 3  # hyd_kv_quant.kv_dtype: e4m3fn unique caches
+HYD_KVQ_GQA = 1    # hyd_kv_quant.flags: grouped-query shapes run on the fp8 matrix-core kernel
 HYD_LSE_BQH, HYD_LSE_BHQ = 0, 1
 HYD_PHASE_ALL, HYD_PHASE_SHARED, HYD_PHASE_UNIQUE, HYD_PHASE_UNIQUE_PARTIAL, HYD_PHASE_MERGE = 0, 1, 2, 3, 4
 
@@ -177,7 +178,7 @@ class StopParams(C.Structure):
 
 
 class KvQuant(C.Structure):
-    _fields_ = [("kv_dtype", C.c_int32), ("reserved", C.c_int32), ("k_scale", C.c_void_p), ("v_scale", C.c_void_p)]
+    _fields_ = [("kv_dtype", C.c_int32), ("flags", C.c_int32), ("k_scale", C.c_void_p), ("v_scale", C.c_void_p)]
 
 
 class AllReduceParams(C.Structure):
@@ -215,6 +216,7 @@ EXPORTS = {
     "hyd_decode_attn_fused_kvq": (C.c_int, [C.POINTER(DecodeParams), C.POINTER(KvQuant), C.c_void_p]),
     "hyd_rope_append_decode_kvq": (C.c_int, [C.POINTER(RopeParams), C.POINTER(KvQuant), C.c_void_p]),
     "hyd_kv_quant_supported": (C.c_int, [C.POINTER(SuffixParams), C.POINTER(KvQuant)]),
+    "hyd_decode_kv_quant_supported": (C.c_int, [C.POINTER(DecodeParams), C.POINTER(KvQuant)]),
     "hyd_sample_tokens_filtered": (C.c_int, [C.POINTER(SampleFilterParams), C.c_void_p]),
     "hyd_sample_tokens_penalized": (C.c_int, [C.POINTER(SamplePenaltyParams), C.c_void_p]),
     "hyd_token_bitmap_build": (C.c_int, [C.POINTER(TokenBitmapParams), C.c_void_p]),

@@ -130,10 +130,12 @@ def hydragen_attention(
     b, nq, hq, d = q.shape
     fp8 = _flash.check_kv_pair(k, v, k_scale, v_scale)
     fused_ok = seq_lens is not None or nq == 1 or k.shape[1] == 0
-    if fp8 and not (fused_ok and n_levels <= HYD_MAX_LEVELS and _flash.fp8_native(q, k, v)):
-        # shapes the fp8 suffix kernel does not take: 16-bit temporaries and the existing path (functional, not fast)
+    def dequantized():  # 16-bit temporaries and the existing path (functional, not fast)
         return hydragen_attention(q, _flash.dequantize_kv(k, k_scale, q.dtype), _flash.dequantize_kv(v, v_scale, q.dtype),
                                   shared_ks, shared_vs, shared_cu_seq_lens, shared_max_seq_lens, use_varlens, seq_lens)
+
+    if fp8 and not (fused_ok and n_levels <= HYD_MAX_LEVELS and _flash.fp8_native(q, k, v)):
+        return dequantized()  # shapes no fp8 suffix kernel takes
     dp = _flash.padded_head_dim(d)
     if dp != d:  # zero-padded to the kernels' head dim, true scale (flash.py: "head dims other than ...")
         pad = lambda t: _flash.pad_head_dim(t, dp)
@@ -152,8 +154,11 @@ def hydragen_attention(
     # seq_lens None means "causal over the unique part" in the reference (attention.py:343-345);
     # with a single query the bottom-right-aligned causal mask hides nothing, which is the decode case.
     if fused_ok and n_levels <= HYD_MAX_LEVELS:
-        return _decode_fused(q, k, v, shared_ks, shared_vs, shared_cu_seq_lens, shared_max_seq_lens,
-                             use_varlens, seq_lens, (k_scale, v_scale) if fp8 else None)
+        out = _decode_fused(q, k, v, shared_ks, shared_vs, shared_cu_seq_lens, shared_max_seq_lens,
+                            use_varlens, seq_lens, (k_scale, v_scale) if fp8 else None)
+        if out is None:  # fp8 caches, and the call as it would be issued is refused (hyd_decode_kv_quant_supported)
+            return dequantized()
+        return out
 
     # The general form, as the reference spells it for any number of levels (attention.py:250-352): one prefix pass per
     # level, one pass over the unique K/V, an N-way log-sum-exp merge.  Taken for the unique-suffix prefill (causal
@@ -305,6 +310,11 @@ def _want_two_stream(q, k, shared_ks, shared_max_seq_lens, use_varlens, capturin
     return 4.0 * b * nq * hq * d * keys >= 4.0e9  # prefix flops worth hiding (C2: 34e9, C1: 1e5)
 
 
+def _param_cache_bytes_drop(n: int):
+    global _param_cache_bytes
+    _param_cache_bytes -= n
+
+
 def _launch_decode(lib, p, two_stream: bool, stream: int, kq=None):
     """Issue the operator described by `p`: one call, or the three calls of the two-stream form.  kq: the hyd_kv_quant of fp8
     unique caches, or None."""
@@ -356,6 +366,8 @@ def _decode_fused(q, k, v, shared_ks, shared_vs, shared_cu_seq_lens, shared_max_
                None if scales is None else tuple(_tensor_key(x) for x in scales))
         hit = _PARAM_CACHE.get(key)
         if hit is not None:
+            if hit[0] is None:  # fp8 caches: this call was refused when it was marshalled (below)
+                return None
             p = hit[0]
             p.suffix.out = out.data_ptr()
             _launch_decode(lib, p, two_stream, stream, *hit[3:])
@@ -384,6 +396,16 @@ def _decode_fused(q, k, v, shared_ks, shared_vs, shared_cu_seq_lens, shared_max_
     if two_stream and not lib.hyd_decode_two_stream_ok(C.byref(p)):
         two_stream = False
     extra = () if kq is None else (kq,)  # (16-bit caches: the call keeps its four-argument form)
+    if kq is not None:
+        # fp8 caches: does the library take the call natively, with the flags it will be issued with (_launch_decode)?  The unique
+        # phase of the two-stream form stands for its three calls; the answer is cached with the marshalled struct.
+        p.phase, p.single_launch_small = (HYD_PHASE_UNIQUE_PARTIAL, 0) if two_stream else (HYD_PHASE_ALL, 1)
+        if lib.hyd_decode_kv_quant_supported(C.byref(p), C.byref(kq)) != 1:
+            if key is not None:
+                while len(_PARAM_CACHE) >= _PARAM_CACHE_MAX:
+                    _param_cache_bytes_drop(_PARAM_CACHE.pop(next(iter(_PARAM_CACHE)))[2])
+                _PARAM_CACHE[key] = (None, None, 0)
+            return None
     _launch_decode(lib, p, two_stream, stream, *extra)
     # cache only when every pointer in `p` refers to caller-owned memory or to tensors `keep` holds on to
     cacheable = key is not None and (seq_lens is None or seq_lens.dtype in (torch.int32, torch.int64)) and \

@@ -320,6 +320,16 @@ void fill_suffix_args(const hyd_suffix_params* p, SuffixArgs* ap) {
     a.scale_log2e = scale_log2e_of(p->softmax_scale, p->D);
 }
 
+// HYD_KVQ_GQA: the caller takes the grouped-query fp8 kernel; without it the entry points keep the shapes of ABI 0.5.0 as first
+// released (callers of that time route refused shapes to a fallback of their own, and go on doing so)
+bool kvq_takes_gqa(const hyd_kv_quant* kq) { return kq && (kq->flags & HYD_KVQ_GQA) != 0; }
+
+int fail_kvq_shapes(int D) {
+    return fail(HYD_ERR_UNSUPPORTED,
+                "fp8 unique caches: shapes not native (grouped-query units of nq * Hq / Hkv >= 3 rows with hyd_kv_quant.flags & HYD_KVQ_GQA, or nq == 1, Hq == Hkv with Hkv a "
+                "multiple of %d at D = %d; D 64 / 128 / 256)", D >= 8 ? 64 / (D / 8) : 0, D);
+}
+
 // kq: null, or fp8 unique caches (validated by check_kvq; K/V strides in bytes)
 int run_suffix(const hyd_suffix_params* p, const hyd_partial* parts, int n_parts, hipStream_t s, const hyd_kv_quant* kq = nullptr) {
     SuffixArgs a;
@@ -349,14 +359,14 @@ int run_suffix(const hyd_suffix_params* p, const hyd_partial* parts, int n_parts
         return fail(HYD_ERR_UNSUPPORTED, "unique K/V of one sequence spans >= 2 GiB (32-bit in-sequence offsets)");
     if (p->Hkv > 4 * 65535 || a.rows > 8 * 65535) return fail(HYD_ERR_UNSUPPORTED, "too many kv heads / query rows for the suffix grid");
     if (kq) {
-        if (!suffix_fp8_eligible(a, p->D))
-            return fail(HYD_ERR_UNSUPPORTED, "fp8 unique caches: shapes not native (nq == 1, Hq == Hkv, Hkv a multiple of %d at D = %d)",
-                        64 / (p->D / 8), p->D);
+        // the 16-bit launcher's order: grouped-query shapes to the matrix-core kernel, one-row units to the token-row kernel
+        const bool gqa = kvq_takes_gqa(kq) && suffix_gqa_fp8_eligible(a, p->D);
+        if (!gqa && !suffix_fp8_eligible(a, p->D)) return fail_kvq_shapes(p->D);
         SuffixKvqArgs ka;
         ka.k_scale = kq->k_scale;
         ka.v_scale = kq->v_scale;
         ka.a = a;
-        const int rc = launch_suffix_fp8(ka, p->dtype, p->D, s);
+        const int rc = gqa ? launch_suffix_gqa_fp8(ka, p->dtype, p->D, s) : launch_suffix_fp8(ka, p->dtype, p->D, s);
         return rc ? fail(HYD_ERR_LAUNCH, "fp8 suffix kernel launch failed: hip error %d", rc) : HYD_OK;
     }
     int rc = launch_suffix(a, p->dtype, p->D, s);
@@ -375,12 +385,19 @@ int check_kvq(const hyd_kv_quant* kq, int dtype, bool* fp8) {
     return HYD_OK;
 }
 
-// shapes-only: does the fp8 suffix kernel take these shapes (nothing is launched, no device memory read)
-bool kvq_native(const hyd_suffix_params* p) {
+// shapes-only: does an fp8 suffix kernel take these shapes (nothing is launched, no device memory read)
+bool kvq_native(const hyd_suffix_params* p, const hyd_kv_quant* kq) {
     if (check_common(p->dtype, p->B, p->nq, p->Hq, p->Hkv, p->D)) return false;
     SuffixArgs a;
     fill_suffix_args(p, &a);
-    return suffix_fp8_eligible(a, p->D);
+    return (kvq_takes_gqa(kq) && suffix_gqa_fp8_eligible(a, p->D)) || suffix_fp8_eligible(a, p->D);
+}
+// ... and is it the grouped-query kernel that takes them (the one whose 16-bit twin tiny decode calls fold into one launch)
+bool kvq_native_gqa(const hyd_suffix_params* p, const hyd_kv_quant* kq) {
+    if (!kvq_takes_gqa(kq) || check_common(p->dtype, p->B, p->nq, p->Hq, p->Hkv, p->D)) return false;
+    SuffixArgs a;
+    fill_suffix_args(p, &a);
+    return suffix_gqa_fp8_eligible(a, p->D);
 }
 
 void level_to_prefix(const hyd_decode_params* p, int i, hyd_prefix_params* pp) {
@@ -528,7 +545,7 @@ int hyd_kv_quant_supported(const hyd_suffix_params* p, const hyd_kv_quant* kq) {
     if (!p) return 0;
     if (!kq || kq->kv_dtype == p->dtype) return 1;
     if (kq->kv_dtype != HYD_FP8_E4M3) return 0;
-    return kvq_native(p) ? 1 : 0;
+    return kvq_native(p, kq) ? 1 : 0;
 }
 
 int hyd_combine_lse(const void* const* outs, const float* const* lses, int32_t n, int64_t rows, int32_t D,
@@ -966,6 +983,19 @@ size_t hyd_workspace_bytes(int32_t B, int32_t nq, int32_t Hq, int32_t Hkv, int32
 
 static int decode_impl(const hyd_decode_params* p, const hyd_kv_quant* kq, void* stream);
 
+// Shapes only: a grouped-query fp8 call whose 16-bit twin would run as ONE launch (decode_runs_as_one_launch).  The one-launch walk
+// does not round a 16-bit prefix partial, the two-kernel pair does: the pair is not what the caller's 16-bit results are, so such a
+// call is refused instead of quietly run as the pair.  (Hq == Hkv shapes keep ignoring the flag, as they always have.)
+static bool decode_kvq_is_one_launch(const hyd_decode_params* p, const hyd_kv_quant* kq) {
+    if (p->n_levels != 1 || p->suffix.kv_len <= 0 || !kvq_native_gqa(&p->suffix, kq)) return false;
+    hyd_prefix_params pp;
+    level_to_prefix(p, 0, &pp);
+    PrefixPlan pl;
+    if (plan_prefix(&pp, &pl, level_split_cap(1))) return false;  // (decode_impl reports it)
+    const bool small = level_is_small(pp, pl);
+    return decode_runs_as_one_launch(p, &pp, &pl, &small);
+}
+
 int hyd_decode_attn_fused(const hyd_decode_params* p, void* stream) { return decode_impl(p, nullptr, stream); }
 
 int hyd_decode_attn_fused_kvq(const hyd_decode_params* p, const hyd_kv_quant* kq, void* stream) {
@@ -977,13 +1007,24 @@ int hyd_decode_attn_fused_kvq(const hyd_decode_params* p, const hyd_kv_quant* kq
     if (!fp8) return hyd_decode_attn_fused(p, stream);
     // fp8 unique caches: validated up front (every phase, also those that do not read the unique cache) so that the phases of one
     // call agree; kv_len == 0 reads no unique key and takes the existing path
-    if (p->suffix.kv_len > 0 && !kvq_native(&p->suffix))
-        return fail(HYD_ERR_UNSUPPORTED, "fp8 unique caches: shapes not native (nq == 1, Hq == Hkv, Hkv a multiple of %d at D = %d)",
-                    64 / (p->suffix.D / 8), p->suffix.D);
+    if (p->suffix.kv_len > 0 && !kvq_native(&p->suffix, kq)) return fail_kvq_shapes(p->suffix.D);
+    if (decode_kvq_is_one_launch(p, kq))
+        return fail(HYD_ERR_UNSUPPORTED, "fp8 unique caches: a grouped-query call this small runs as ONE launch with 16-bit caches "
+                                         "(single_launch_small), which has no fp8 form: clear the flag, or pass 16-bit caches");
     return decode_impl(p, p->suffix.kv_len > 0 ? kq : nullptr, stream);
 }
 
-// kq: null, or validated fp8 unique caches (then single_launch_small is ignored and the unique pass is the fp8 kernel)
+int hyd_decode_kv_quant_supported(const hyd_decode_params* p, const hyd_kv_quant* kq) {
+    if (!p) return 0;
+    if (!kq || kq->kv_dtype == p->suffix.dtype) return 1;
+    if (kq->kv_dtype != HYD_FP8_E4M3) return 0;
+    if (p->n_levels < 0 || p->n_levels > HYD_MAX_LEVELS) return 0;
+    if (p->suffix.kv_len <= 0) return p->suffix.kv_len == 0 ? 1 : 0;  // no unique key is read: the existing path
+    return kvq_native(&p->suffix, kq) && !decode_kvq_is_one_launch(p, kq) ? 1 : 0;
+}
+
+// kq: null, or validated fp8 unique caches (then the unique pass is an fp8 kernel and the call is never the one-launch form: Hq == Hkv
+// shapes ignore single_launch_small, grouped-query ones were refused by the caller where the flag would have applied)
 static int decode_impl(const hyd_decode_params* p, const hyd_kv_quant* kq, void* stream) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
     if (p->n_levels < 0 || p->n_levels > HYD_MAX_LEVELS) return fail(HYD_ERR_BAD_ARG, "n_levels %d", p->n_levels);

@@ -243,6 +243,8 @@ int launch_suffix(const SuffixArgs& a, int dtype, int D, hipStream_t s);
 bool suffix_gqa_eligible(const SuffixArgs& a, int D, bool any_shape);
 bool suffix_fp8_eligible(const SuffixArgs& a, int D);                                 // suffix_attn_fp8.hip, shapes only
 int launch_suffix_fp8(const SuffixKvqArgs& a, int dtype, int D, hipStream_t s);       // q dtype; K/V e4m3fn
+bool suffix_gqa_fp8_eligible(const SuffixArgs& a, int D);                             // suffix_attn_gqa_fp8.hip, shapes only
+int launch_suffix_gqa_fp8(const SuffixKvqArgs& a, int dtype, int D, hipStream_t s);   // q dtype; K/V e4m3fn, grouped-query shapes
 int launch_rope_append_fp8(const RopeKvqArgs& a, int dtype, int D, hipStream_t s);
 int launch_suffix_gqa(const SuffixArgs& a, int dtype, int D, hipStream_t s);
 int launch_combine(const CombineArgs& a, hipStream_t s);

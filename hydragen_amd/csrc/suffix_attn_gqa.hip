@@ -457,12 +457,6 @@ __global__ __launch_bounds__(64 * WPU * HPW) __attribute__((amdgpu_waves_per_eu(
     }
 }
 
-// shapes only: fewer than 4 one-wave units per CU (measured: B=32, 8/1 heads, 1152 keys 48 -> 31 us; at 1024 and
-// 2048 units -- C3, C5 -- one wave per unit is as fast or faster), and enough keys to deal out
-static bool gqa_few_units(const SuffixArgs& a, int chunks) {
-    return (int64_t)a.units * chunks < 256 * 4 && a.kv_len + (a.pk ? a.p_len : 0) >= 128;
-}
-
 // Shapes-only eligibility (capture-safe): enough query rows per unit for the matrix cores to pay, enough units to
 // fill the chip with one wave each, and byte offsets inside a unit's cache that fit the 32-bit buffer addressing.
 bool suffix_gqa_eligible(const SuffixArgs& a, int D, bool any_shape) {
@@ -507,22 +501,20 @@ template <typename T, int D>
 static int launch_gqa_t(const SuffixArgs& a_in, hipStream_t s) {
     SuffixArgs a = a_in;
     const int chunks = (a.rows + 15) / 16;
-    bool few_units = gqa_few_units(a, chunks);
+    // waves per unit and kv heads per workgroup, from shapes: gqa_launch_plan (suffix_gqa_common.h; the fp8 kernel takes the same)
+    const GqaLaunchPlan plan = gqa_launch_plan(a, D);
+    bool few_units = plan.few_units;
+    int hpw = plan.hpw;
 #ifdef HYD_ABLATION_BUILD
-    if (const char* e = getenv("HYD_GQA_WPU")) few_units = atoi(e) == 4;
     if (const char* e = getenv("HYD_GQA_BLIND")) a.dbg_blind = atoi(e);
-#endif
-    // kv heads of a sequence per workgroup (one-wave units of the unique phase).  Measured with this kernel (profiles/r05_gqa_hpw.txt,
-    // us at S = 32 / 128 / 256): 8 kv heads: 1 head per workgroup 61 / 197 / 364, 2: 60 / 185 / 355, 4: 64 / 184 / 352, 8: 71 / 187 / 341 -- a
-    // workgroup that fills the CU's LDS alone (8 x 16 KB) leaves it idle between workgroups, which short suffixes pay for; 16 kv heads:
-    // 1: 55 / 181 / 348, 4: 63 / 211 / 403, 8: 70 / 223 / 446 -- a part of a token's row per workgroup is worse than one head.  So: all
-    // heads of the token in one workgroup when there are at most 4 (<= 64 KB of tiles: two workgroups per CU), 4 of 8, else one.
-    int hpw = 1;
-    if (!few_units && !a.shared_kv && !a.pk && a.Hkv <= 8) {
-        hpw = a.Hkv % 4 == 0 ? 4 : a.Hkv % 2 == 0 ? 2 : 1;
-        if (D == 256 && hpw > 2) hpw = 2;  // 32 KB of tiles per wave
+    if (const char* e = getenv("HYD_GQA_WPU")) {  // (the heads per workgroup follow the forced choice, as they follow the measured one)
+        few_units = atoi(e) == 4;
+        hpw = 1;
+        if (!few_units && !a.shared_kv && !a.pk && a.Hkv <= 8) {
+            hpw = a.Hkv % 4 == 0 ? 4 : a.Hkv % 2 == 0 ? 2 : 1;
+            if (D == 256 && hpw > 2) hpw = 2;
+        }
     }
-#ifdef HYD_ABLATION_BUILD
     if (const char* e = getenv("HYD_GQA_HPW")) hpw = few_units ? 1 : atoi(e);
 #endif
     dim3 grid((unsigned)a.B * (unsigned)(a.Hkv / hpw), chunks, 1);

@@ -80,6 +80,33 @@ __device__ __forceinline__ float quad_sum(float x) {
     return __builtin_bit_cast(float, (int)q[0]) + __builtin_bit_cast(float, (int)q[1]);
 }
 
+// ---- host: the shapes-only launch choices both grouped-query kernels (16-bit, fp8) take ---------------------------------------
+// fewer than 4 one-wave units per CU (measured: B=32, 8/1 heads, 1152 keys 48 -> 31 us; at 1024 and
+// 2048 units -- C3, C5 -- one wave per unit is as fast or faster), and enough keys to deal out
+inline bool gqa_few_units(const SuffixArgs& a, int chunks) {
+    return (int64_t)a.units * chunks < 256 * 4 && a.kv_len + (a.pk ? a.p_len : 0) >= 128;
+}
+
+struct GqaLaunchPlan {
+    bool few_units;  // four waves per unit
+    int hpw;         // kv heads of a sequence per workgroup (one-wave units of the unique phase)
+};
+// kv heads per workgroup.  Measured with the 16-bit kernel (profiles/r05_gqa_hpw.txt,
+// us at S = 32 / 128 / 256): 8 kv heads: 1 head per workgroup 61 / 197 / 364, 2: 60 / 185 / 355, 4: 64 / 184 / 352, 8: 71 / 187 / 341 -- a
+// workgroup that fills the CU's LDS alone (8 x 16 KB) leaves it idle between workgroups, which short suffixes pay for; 16 kv heads:
+// 1: 55 / 181 / 348, 4: 63 / 211 / 403, 8: 70 / 223 / 446 -- a part of a token's row per workgroup is worse than one head.  So: all
+// heads of the token in one workgroup when there are at most 4 (<= 64 KB of tiles: two workgroups per CU), 4 of 8, else one.
+inline GqaLaunchPlan gqa_launch_plan(const SuffixArgs& a, int D) {
+    GqaLaunchPlan pl;
+    pl.few_units = gqa_few_units(a, (a.rows + 15) / 16);
+    pl.hpw = 1;
+    if (!pl.few_units && !a.shared_kv && !a.pk && a.Hkv <= 8) {
+        pl.hpw = a.Hkv % 4 == 0 ? 4 : a.Hkv % 2 == 0 ? 2 : 1;
+        if (D == 256 && pl.hpw > 2) pl.hpw = 2;  // 32 KB of tiles per wave
+    }
+    return pl;
+}
+
 }  // namespace
 
 }  // namespace hyd

@@ -20,7 +20,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import HYD_BF16, HYD_F16, HYD_FP8_E4M3, HYD_LSE_BHQ, HYD_LSE_BQH, KvQuant, PrefixParams, SuffixParams
+from ._lib import HYD_BF16, HYD_F16, HYD_FP8_E4M3, HYD_KVQ_GQA, HYD_LSE_BHQ, HYD_LSE_BQH, KvQuant, PrefixParams, SuffixParams
 from .kv_quant import FP8_DTYPE, dequantize_kv, quantize_kv  # noqa: F401  (quantize_kv: part of this module's face)
 
 
@@ -287,11 +287,14 @@ def fill_suffix_params(p: SuffixParams, q: Tensor, k: Tensor, v: Tensor, seq_len
 
 
 # ---- fp8 unique caches (kv_quant.py) ------------------------------------------------------------------------------------
-# fp8 mode is told by k's dtype (v must match).  Shapes the fp8 suffix kernel takes natively (hyd_kv_quant_supported: nq == 1,
-# Hq == Hkv, D 64 / 128 / 256, Hkv a multiple of the heads of one wave instruction) go to the _kvq entry points; every other
-# shape -- grouped-query heads, several query rows, padded head dims, an odd number of heads -- is dequantized into a 16-bit
-# temporary and runs the existing path.  That fallback is functional, not fast (the cache is read, widened and written on
-# every call), in the spirit of pad_head_dim.
+# fp8 mode is told by k's dtype (v must match).  Shapes an fp8 suffix kernel takes natively (hyd_kv_quant_supported, D 64 / 128 /
+# 256: grouped-query units of nq * Hq / Hkv >= 3 query rows -- the matrix-core kernel, bit-identical to the 16-bit one on the
+# dequantized caches --, and nq == 1, Hq == Hkv with Hkv a multiple of the heads of one wave instruction -- the token-row kernel)
+# go to the _kvq entry points (kv_quant_params sets HYD_KVQ_GQA, the opt-in of the grouped-query kernel); every other shape -- units of 2 rows, Hq == Hkv with two query rows, padded head dims, an odd
+# number of heads -- is dequantized into a 16-bit temporary and runs the existing path.  That fallback is functional, not fast
+# (the cache is read, widened and written on every call), in the spirit of pad_head_dim.  The whole operator
+# (attention.hydragen_attention) asks hyd_decode_kv_quant_supported as well: grouped-query calls so small that 16-bit caches
+# would run them as one launch stay on the fallback, whose results they keep.
 def check_kv_pair(k: Tensor, v: Tensor, k_scale: Tensor | None, v_scale: Tensor | None) -> bool:
     """True for fp8 caches (and validates their scales); scales given for 16-bit caches are an error."""
     fp8 = k.dtype == FP8_DTYPE
@@ -312,13 +315,14 @@ def check_kv_pair(k: Tensor, v: Tensor, k_scale: Tensor | None, v_scale: Tensor 
 def kv_quant_params(k_scale: Tensor | None, v_scale: Tensor | None) -> KvQuant:
     kq = KvQuant()
     kq.kv_dtype = HYD_FP8_E4M3
+    kq.flags = HYD_KVQ_GQA  # grouped-query shapes run on the fp8 matrix-core kernel (without the flag the library refuses them)
     kq.k_scale = k_scale.data_ptr() if k_scale is not None else None
     kq.v_scale = v_scale.data_ptr() if v_scale is not None else None
     return kq
 
 
 def fp8_native(q: Tensor, k: Tensor, v: Tensor) -> bool:
-    """Shapes only: whether the fp8 suffix kernel takes (q, k, v) as they are (hyd_kv_quant_supported)."""
+    """Shapes only: whether an fp8 suffix kernel takes (q, k, v) as they are (hyd_kv_quant_supported)."""
     if k.numel() and (k.data_ptr() % 16 or v.data_ptr() % 16):
         return False
     return _fp8_native_shapes(tuple(q.shape), q.dtype, tuple(k.shape), k.stride(), v.stride())

@@ -555,15 +555,26 @@ HYD_API const uint32_t* hyd_allreduce_status(const void* own_block);
  *   - kq == NULL, or kq->kv_dtype == the q dtype: exactly the existing entry point;
  *   - kq->kv_dtype == HYD_FP8_E4M3: the unique K/V (suffix / decode) or the caches (rope append) are fp8; their strides
  *     are counted in 1-byte elements (still multiples of 8), and so is the "span < 2 GiB" check of a sequence's cache.
- * hyd_decode_attn_fused_kvq takes every phase; with fp8 caches single_launch_small is ignored (the prefix + suffix pair
- * runs).  The workspace query is unchanged: the unique partial of the two-stream form stays in q's dtype.
- * Native fp8 shapes (hyd_kv_quant_supported): one query row (nq == 1), Hq == Hkv, D 64 / 128 / 256, and Hkv a multiple of
- * the 64 / (D / 8) heads one wave instruction covers.  Other shapes return HYD_ERR_UNSUPPORTED; the Python operators then
- * dequantize into a 16-bit temporary and call the existing path (functional, not fast).
+ * hyd_decode_attn_fused_kvq takes every phase.  The workspace query is unchanged: the unique partial of the two-stream form
+ * stays in q's dtype.
+ * Native fp8 shapes (hyd_kv_quant_supported), D 64 / 128 / 256:
+ *   - grouped-query units, for callers that set HYD_KVQ_GQA in hyd_kv_quant.flags (the field was `reserved`, 0, when 0.5.0 was
+ *     first released: callers of that time keep the shapes and refusals they were written against): every shape the suffix pass gives its matrix-core kernel with 16-bit caches -- nq * (Hq / Hkv) >= 3
+ *     query rows per (sequence, kv head); at D = 256 only with at least 1024 (sequence, kv head, 16-row chunk) units or
+ *     fewer than 128 keys.  `out` and `lse` are bit-identical to the 16-bit kernel run on the dequantized caches
+ *     (float(q8) * scale[h], rounded to fp32 and then to the q dtype, ties to even: hydragen_amd/kv_quant.py dequantize_kv);
+ *   - one query row (nq == 1), Hq == Hkv, and Hkv a multiple of the 64 / (D / 8) heads one wave instruction covers.
+ * Other shapes -- units of 2 rows, Hq == Hkv with nq == 2, 2 heads at D = 128, other head dims -- return HYD_ERR_UNSUPPORTED; the
+ * Python operators then dequantize into a 16-bit temporary and call the existing path (functional, not fast).
+ * single_launch_small with fp8 caches: where the same call with 16-bit caches would run as ONE launch, a grouped-query call
+ * returns HYD_ERR_UNSUPPORTED (that form has no fp8 kernel, and the prefix + suffix pair rounds a 16-bit prefix partial the
+ * one-launch walk does not: it is not run in its place); Hq == Hkv calls ignore the flag and run the pair, as before.
+ * hyd_decode_kv_quant_supported answers for a whole decode call, flags and phase included.
  * ------------------------------------------------------------------------------------------ */
+#define HYD_KVQ_GQA 1 /* hyd_kv_quant.flags: grouped-query shapes run on the fp8 matrix-core kernel instead of being refused */
 typedef struct hyd_kv_quant {
     int32_t kv_dtype;     /* HYD_FP8_E4M3, or the q dtype = no quantization                       */
-    int32_t reserved;
+    int32_t flags;        /* 0, or HYD_KVQ_GQA (formerly `reserved`)                             */
     const float* k_scale; /* [Hkv] device, or NULL = 1                                           */
     const float* v_scale; /* [Hkv] device, or NULL = 1                                           */
 } hyd_kv_quant;
@@ -574,6 +585,9 @@ HYD_API int hyd_rope_append_decode_kvq(const hyd_rope_params* p, const hyd_kv_qu
 /* Shapes only (capture-safe, no device read): 1 when the suffix pass of these shapes runs natively with kq's cache dtype
  * (always 1 for kq == NULL or kv_dtype == dtype), else 0. */
 HYD_API int hyd_kv_quant_supported(const hyd_suffix_params* p, const hyd_kv_quant* kq);
+/* Shapes only (capture-safe, no device read): 1 exactly when hyd_decode_attn_fused_kvq takes this call natively with kq's
+ * cache dtype -- phase, single_launch_small and the levels as given (always 1 for kq == NULL or kv_dtype == dtype) --, else 0. */
+HYD_API int hyd_decode_kv_quant_supported(const hyd_decode_params* p, const hyd_kv_quant* kq);
 
 HYD_API int hyd_version(void);
 HYD_API const char* hyd_last_error_string(void);
