@@ -21,10 +21,47 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
+// what a launcher returned -> HYD_OK, or HYD_ERR_LAUNCH with "<what> failed: hip error <rc>"
+int launched(int rc, const char* what) { return rc ? fail(HYD_ERR_LAUNCH, "%s failed: hip error %d", what, rc) : HYD_OK; }
+
 constexpr int kNumCU = 256;  // MI355X
 constexpr int kMaxSplits = 32;
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// Where the slices of one partial live: `count` output slices [rows, D] of esz-byte elements, then -- behind ALL of them --
+// `count` fp32 LSE slices [rows].  Every slice is padded to 256 bytes; the strides only matter when there are several
+// (slice j of a hyd_partial is at out + j * out_stride, lse + j * lse_stride), and a lone slice's LSE starts at lse_base
+// like any other.  The one statement of the rule: workspace sizes, carving and the expansion of stacked partials all ask here.
+struct SliceLayout {
+    size_t out_stride, lse_stride, lse_base, bytes;
+};
+SliceLayout slice_layout(size_t rows, int D, size_t esz, int count) {
+    SliceLayout l;
+    l.out_stride = align_up(rows * D * esz, 256);
+    l.lse_stride = align_up(rows * sizeof(float), 256);
+    l.lse_base = (size_t)count * l.out_stride;
+    l.bytes = (size_t)count * (l.out_stride + l.lse_stride);
+    return l;
+}
+
+// Every slice of stacked partials in order: f(n, out, lse, is_f32) for slice number n.  *n_slices = how many there were.
+template <typename F>
+int for_each_slice(const hyd_partial* parts, int n_parts, size_t rows, int D, int* n_slices, F&& f) {
+    int n = 0;
+    for (int i = 0; i < n_parts; ++i) {
+        if (!parts[i].out || !parts[i].lse || parts[i].count <= 0)
+            return fail(HYD_ERR_BAD_ARG, "partial %d: null pointer or non-positive count", i);
+        const SliceLayout l = slice_layout(rows, D, parts[i].is_f32 ? 4 : 2, parts[i].count);
+        for (int j = 0; j < parts[i].count; ++j, ++n) {
+            if (n >= kMaxCombine) return fail(HYD_ERR_UNSUPPORTED, "more than %d partials", kMaxCombine);
+            f(n, static_cast<const char*>(parts[i].out) + (size_t)j * l.out_stride,
+              reinterpret_cast<const float*>(reinterpret_cast<const char*>(parts[i].lse) + (size_t)j * l.lse_stride), parts[i].is_f32);
+        }
+    }
+    *n_slices = n;
+    return HYD_OK;
+}
 
 // Development switches exist only in HYD_ABLATION_BUILD libraries (A/B measurements on hardware); the product library
 // reads no environment variable and keeps no mutable state.
@@ -152,10 +189,9 @@ int plan_prefix(const hyd_prefix_params* p, PrefixPlan* pl, int max_splits = kMa
 // Split-KV slices are fp32 everywhere.  (16-bit slices on the fused decode path were measured: C3 80.5 -> 79.3 us,
 // C5 145.7 -> 140.9 us flushed, but every slice then carries its own rounding and the bf16 mean relative difference
 // of C3 / C5 / deep hierarchies rose from 0.8 % to 1.1-1.2 %, above the bound the parity tests state.)
-size_t prefix_ws_bytes(const hyd_prefix_params* p, const PrefixPlan& pl, size_t esz = sizeof(float)) {
+size_t prefix_ws_bytes(const hyd_prefix_params* p, const PrefixPlan& pl) {
     if (pl.nsplit <= 1) return 0;
-    const size_t rows = (size_t)p->B * p->nq * p->Hq;
-    return (size_t)pl.nsplit * (align_up(rows * p->D * esz, 256) + align_up(rows * sizeof(float), 256));
+    return slice_layout((size_t)p->B * p->nq * p->Hq, p->D, sizeof(float), pl.nsplit).bytes;
 }
 
 void fill_prefix_args(const hyd_prefix_params* p, const PrefixPlan& pl, PrefixArgs* a) {
@@ -222,34 +258,28 @@ int run_prefix(const hyd_prefix_params* p, const PrefixPlan& pl, bool merge, hip
         a.lse = p->lse;
         a.out_f32 = out_f32 ? 1 : 0;  // only the decode entry asks for an fp32 partial (hyd_decode_params.f32_partials)
         a.lse_layout = p->lse_layout;
-        int rc = launch_prefix_any(a, p->dtype, p->D, p->causal != 0, pl.grid, max_wgs, s);
-        return rc ? fail(HYD_ERR_LAUNCH, "prefix kernel launch failed: hip error %d", rc) : HYD_OK;
+        return launched(launch_prefix_any(a, p->dtype, p->D, p->causal != 0, pl.grid, max_wgs, s), "prefix kernel launch");
     }
-    const size_t esz = sizeof(float);
-    const size_t need = prefix_ws_bytes(p, pl, esz);
-    if (!p->workspace || p->workspace_bytes < need)
-        return fail(HYD_ERR_WORKSPACE, "prefix pass needs %zu workspace bytes, got %zu", need, p->workspace_bytes);
-    const size_t o_bytes = align_up(rows * p->D * esz, 256);
-    const size_t l_bytes = align_up(rows * sizeof(float), 256);
+    const SliceLayout l = slice_layout(rows, p->D, sizeof(float), pl.nsplit);
+    if (!p->workspace || p->workspace_bytes < l.bytes)
+        return fail(HYD_ERR_WORKSPACE, "prefix pass needs %zu workspace bytes, got %zu", l.bytes, p->workspace_bytes);
     char* ws = static_cast<char*>(p->workspace);
-    float* wo = reinterpret_cast<float*>(ws);
-    float* wl = reinterpret_cast<float*>(ws + (size_t)pl.nsplit * o_bytes);
-    a.out = wo;
-    a.lse = wl;
+    const hyd_partial slices = {ws, reinterpret_cast<float*>(ws + l.lse_base), pl.nsplit, /*is_f32=*/1};
+    a.out = ws;
+    a.lse = const_cast<float*>(slices.lse);
     a.out_f32 = 1;
     a.lse_layout = HYD_LSE_BQH;
-    a.out_split_stride = (int64_t)(o_bytes / esz);
-    a.lse_split_stride = (int64_t)(l_bytes / sizeof(float));
-    int rc = launch_prefix_any(a, p->dtype, p->D, p->causal != 0, pl.grid, max_wgs, s);
-    if (rc) return fail(HYD_ERR_LAUNCH, "prefix kernel launch failed: hip error %d", rc);
-    if (!merge) return HYD_OK;
+    a.out_split_stride = (int64_t)(l.out_stride / sizeof(float));
+    a.lse_split_stride = (int64_t)(l.lse_stride / sizeof(float));
+    int rc = launched(launch_prefix_any(a, p->dtype, p->D, p->causal != 0, pl.grid, max_wgs, s), "prefix kernel launch");
+    if (rc || !merge) return rc;
     CombineArgs c;
     memset(&c, 0, sizeof(c));
-    for (int i = 0; i < pl.nsplit; ++i) {
-        c.outs[i] = wo + (size_t)i * a.out_split_stride;
-        c.lses[i] = wl + (size_t)i * a.lse_split_stride;
-    }
-    c.n = pl.nsplit;
+    if ((rc = for_each_slice(&slices, 1, rows, p->D, &c.n, [&c](int n, const void* out, const float* lse, int) {
+            c.outs[n] = out;
+            c.lses[n] = lse;
+        })))
+        return rc;
     c.rows = (int64_t)rows;
     c.D = p->D;
     c.dtype_in = HYD_F32;
@@ -259,13 +289,14 @@ int run_prefix(const hyd_prefix_params* p, const PrefixPlan& pl, bool merge, hip
     c.lse_layout = p->lse_layout;
     c.Hq = p->Hq;
     c.qpg = pl.qpg;
-    rc = launch_combine(c, s);
-    return rc ? fail(HYD_ERR_LAUNCH, "combine kernel launch failed: hip error %d", rc) : HYD_OK;
+    return launched(launch_combine(c, s), "combine kernel launch");
 }
+
+bool misaligned(const void* p, size_t to) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(to - 1)) != 0; }  // (null is aligned)
 
 int check_ptr_align(const void* p, const char* name) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "%s is null", name);
-    if ((reinterpret_cast<uintptr_t>(p) & 15u) != 0) return fail(HYD_ERR_BAD_ARG, "%s must be 16-byte aligned", name);
+    if (misaligned(p, 16)) return fail(HYD_ERR_BAD_ARG, "%s must be 16-byte aligned", name);
     return HYD_OK;
 }
 int check_stride8(int64_t s, const char* name) {
@@ -334,26 +365,14 @@ int fail_kvq_shapes(int D) {
 int run_suffix(const hyd_suffix_params* p, const hyd_partial* parts, int n_parts, hipStream_t s, const hyd_kv_quant* kq = nullptr) {
     SuffixArgs a;
     fill_suffix_args(p, &a);
-    const size_t rows = (size_t)p->B * p->nq * p->Hq;
-    int n = 0;
-    for (int i = 0; i < n_parts; ++i) {
-        if (!parts[i].out || !parts[i].lse || parts[i].count <= 0)
-            return fail(HYD_ERR_BAD_ARG, "partial %d: null pointer or non-positive count", i);
-        for (int j = 0; j < parts[i].count; ++j) {
-            if (n >= kMaxCombine) return fail(HYD_ERR_UNSUPPORTED, "more than %d partials", kMaxCombine);
-            const size_t esz = parts[i].is_f32 ? 4 : 2;
-            // stacked slices are padded to 256 bytes exactly as hyd_prefix_attn_fwd lays them out
-            const size_t ostride = parts[i].count > 1 ? align_up(rows * p->D * esz, 256) : rows * p->D * esz;
-            const size_t lstride = parts[i].count > 1 ? align_up(rows * 4, 256) : rows * 4;
-            a.partials[n].out = static_cast<const char*>(parts[i].out) + (size_t)j * ostride;
-            a.partials[n].lse = reinterpret_cast<const float*>(reinterpret_cast<const char*>(parts[i].lse) + (size_t)j * lstride);
-            a.partials[n].is_f32 = parts[i].is_f32;
-            ++n;
-        }
-    }
-    a.n_partials = n;
+    int rc = for_each_slice(parts, n_parts, (size_t)p->B * p->nq * p->Hq, p->D, &a.n_partials, [&a](int n, const void* out, const float* lse, int is_f32) {
+        a.partials[n].out = out;
+        a.partials[n].lse = lse;
+        a.partials[n].is_f32 = is_f32;
+    });
+    if (rc) return rc;
     a.n_pre = 0;
-    while (a.n_pre < 2 && a.n_pre < n && !a.partials[a.n_pre].is_f32) ++a.n_pre;
+    while (a.n_pre < 2 && a.n_pre < a.n_partials && !a.partials[a.n_pre].is_f32) ++a.n_pre;
     const int64_t esz = kq ? 1 : 2;
     if ((int64_t)p->kv_len * p->k_tok_stride * esz >= (1ll << 31) || (int64_t)p->kv_len * p->v_tok_stride * esz >= (1ll << 31))
         return fail(HYD_ERR_UNSUPPORTED, "unique K/V of one sequence spans >= 2 GiB (32-bit in-sequence offsets)");
@@ -366,22 +385,29 @@ int run_suffix(const hyd_suffix_params* p, const hyd_partial* parts, int n_parts
         ka.k_scale = kq->k_scale;
         ka.v_scale = kq->v_scale;
         ka.a = a;
-        const int rc = gqa ? launch_suffix_gqa_fp8(ka, p->dtype, p->D, s) : launch_suffix_fp8(ka, p->dtype, p->D, s);
-        return rc ? fail(HYD_ERR_LAUNCH, "fp8 suffix kernel launch failed: hip error %d", rc) : HYD_OK;
+        return launched(gqa ? launch_suffix_gqa_fp8(ka, p->dtype, p->D, s) : launch_suffix_fp8(ka, p->dtype, p->D, s), "fp8 suffix kernel launch");
     }
-    int rc = launch_suffix(a, p->dtype, p->D, s);
-    return rc ? fail(HYD_ERR_LAUNCH, "suffix kernel launch failed: hip error %d", rc) : HYD_OK;
+    return launched(launch_suffix(a, p->dtype, p->D, s), "suffix kernel launch");
 }
 
-// hyd_kv_quant of a call whose q dtype is `dtype`: *fp8 = true for e4m3fn caches, false for "no quantization"
-int check_kvq(const hyd_kv_quant* kq, int dtype, bool* fp8) {
-    *fp8 = false;
-    if (!kq || kq->kv_dtype == dtype) return HYD_OK;
-    if (kq->kv_dtype != HYD_FP8_E4M3)
-        return fail(HYD_ERR_UNSUPPORTED, "kv_dtype %d: HYD_FP8_E4M3 (%d) or the q dtype (%d)", kq->kv_dtype, HYD_FP8_E4M3, dtype);
-    if ((kq->k_scale && (reinterpret_cast<uintptr_t>(kq->k_scale) & 3u)) || (kq->v_scale && (reinterpret_cast<uintptr_t>(kq->v_scale) & 3u)))
+// What a hyd_kv_quant asks of a call whose q dtype is `dtype`: nothing (absent, or the q dtype), e4m3fn caches, or a dtype nobody has.
+enum KvqKind { kKvqNone, kKvqFp8, kKvqUnsupported };
+KvqKind kvq_kind(const hyd_kv_quant* kq, int dtype) {
+    if (!kq || kq->kv_dtype == dtype) return kKvqNone;
+    return kq->kv_dtype == HYD_FP8_E4M3 ? kKvqFp8 : kKvqUnsupported;
+}
+
+// Validates *kq and narrows it to what the launch paths take: null, or fp8 unique caches.
+int check_kvq(const hyd_kv_quant** kq, int dtype) {
+    const KvqKind kind = kvq_kind(*kq, dtype);
+    if (kind == kKvqUnsupported)
+        return fail(HYD_ERR_UNSUPPORTED, "kv_dtype %d: HYD_FP8_E4M3 (%d) or the q dtype (%d)", (*kq)->kv_dtype, HYD_FP8_E4M3, dtype);
+    if (kind == kKvqNone) {
+        *kq = nullptr;
+        return HYD_OK;
+    }
+    if (misaligned((*kq)->k_scale, 4) || misaligned((*kq)->v_scale, 4))
         return fail(HYD_ERR_BAD_ARG, "k_scale / v_scale must be 4-byte aligned fp32 arrays");
-    *fp8 = true;
     return HYD_OK;
 }
 
@@ -453,26 +479,89 @@ int run_level_small(const hyd_prefix_params& pp, const PrefixPlan& pl, void* out
     a.units = pp.sb * pp.Hkv;
     a.scale_log2e = scale_log2e_of(pp.softmax_scale, pp.D);
     a.shared_kv = 1;
-    const int rc = launch_suffix_gqa(a, pp.dtype, pp.D, s);
-    return rc ? fail(HYD_ERR_LAUNCH, "small-level kernel launch failed: hip error %d", rc) : HYD_OK;
+    return launched(launch_suffix_gqa(a, pp.dtype, pp.D, s), "small-level kernel launch");
 }
 
 // The suffix epilogue merges at most kMaxCombine partials, so the levels of one decode call share that budget:
 // each level may cut its keys into at most kMaxCombine / n_levels slices (>= 8 with HYD_MAX_LEVELS = 8).
 int level_split_cap(int n_levels) { return n_levels > 0 ? kMaxCombine / n_levels : kMaxSplits; }
 
-// Scratch of the two-stream form: the unique pass's partial, a 16-bit [B, nq, Hq, D] + its fp32 LSE [B, nq, Hq].
-size_t unique_partial_bytes(const hyd_suffix_params& sp) {
-    const size_t rows = (size_t)sp.B * sp.nq * sp.Hq;
-    return align_up(rows * sp.D * 2, 256) + align_up(rows * 4, 256);
+// ---- one plan per decode call -----------------------------------------------------------------------------------------
+// Everything the shapes of a hyd_decode_params decide, derived in ONE place: the size queries, the support queries and the
+// launch all read a DecodePlan and plan nothing of their own, so they cannot disagree.
+enum DecodeForm {
+    kPrefixOnly,  // attention.py:273-274: a single shared level and no unique keys -> the prefix result IS the answer
+    kOneLaunch,   // single_launch_small applies (16-bit caches): one grouped-query kernel walks both segments
+    kInOrder,     // the level passes fill the workspace, the suffix pass merges them in its epilogue
+    kTwoStream,   // HYD_PHASE_UNIQUE_PARTIAL / HYD_PHASE_MERGE: the unique pass leaves a partial of its own, one combine merges all
+};
+struct LevelPlan {
+    hyd_prefix_params pp;  // the level as a prefix pass (out / lse / workspace are set when the workspace is carved)
+    PrefixPlan pl;
+    bool small;          // level_is_small: the grouped-query kernel runs it, unsplit, into a 16-bit partial
+    int count, is_f32;   // its partial: `count` slices (split-KV slices are fp32 everywhere) ...
+    SliceLayout layout;  // ... laid out like this in the level's layout.bytes of the workspace
+};
+struct DecodePlan {
+    DecodeForm form;
+    bool two_stream_ok;  // the shapes have both a shared and a unique part
+    int rc;              // HYD_OK, or what plan_prefix said of level `n_planned` (the message is in g_err)
+    int n_planned;       // levels planned: all of them when rc == HYD_OK
+    LevelPlan level[HYD_MAX_LEVELS];
+    int n_parts;          // slices of all levels' partials
+    size_t levels_bytes;  // the levels' regions (kPrefixOnly: the split-KV slices of the one pass, which writes straight to `out`)
+    SliceLayout unique;   // behind them, the unique pass's own 16-bit partial of the two-stream form; bytes = 0 without both parts
+};
+
+// hyd_decode_params.single_launch_small: one uniform shared level that already counts as small (few query rows per
+// (group, kv head), short prefix), unique keys present, the same token strides in the shared and the unique tensors, and
+// so few keys in all that the call is launch latency.  Measured per graph-replayed call (tests/probes/single_launch_probe.py,
+// units x keys = B * Hkv * (P + S)): 1152 keys (BASELINE config 1) 6.8 -> 4.1 us, 2176 keys 11.4 -> 8.1, 8072 keys (two
+// sequences on a 1000-key prefix) 19.5 -> 16.5, 8704 keys (32 sequences) 14.0 -> 14.1: even.  Shapes only: capture-safe.
+constexpr int64_t kSingleLaunchMaxKeys = 8192;
+bool decode_runs_as_one_launch(const hyd_decode_params* p, const LevelPlan& lv) {
+    const hyd_suffix_params& sp = p->suffix;
+    if (p->phase != HYD_PHASE_ALL || !p->single_launch_small || p->n_levels != 1 || !lv.small || sp.kv_len <= 0) return false;
+    if (sp.lse) return false;  // suffix.lse is the LSE of the unique keys alone in every form; one walk over both segments cannot give it
+    const hyd_prefix_params& pp = lv.pp;
+    if (pp.cu_seqlens_k || pp.sb <= 0 || sp.B % pp.sb != 0) return false;  // (a small level runs unsplit whatever the plan says)
+    if (pp.k_tok_stride != sp.k_tok_stride || pp.v_tok_stride != sp.v_tok_stride) return false;
+    if ((int64_t)sp.B * sp.Hkv * ((int64_t)pp.kv_len + sp.kv_len) > kSingleLaunchMaxKeys) return false;
+    SuffixArgs a;
+    fill_suffix_args(&sp, &a);
+    return suffix_gqa_eligible(a, sp.D, /*any_shape=*/true);
 }
 
-// per-level workspace: nsplit == 1 -> one dtype slice + lse; nsplit > 1 -> fp32 slices (prefix_ws_bytes)
-size_t level_ws_bytes(const hyd_prefix_params& pp, const PrefixPlan& pl, bool f32_partials) {
-    const size_t rows = (size_t)pp.B * pp.nq * pp.Hq;
-    const bool small = level_is_small(pp, pl);
-    if (pl.nsplit > 1 && !small) return prefix_ws_bytes(&pp, pl);
-    return align_up(rows * pp.D * ((f32_partials && !small) ? 4 : 2), 256) + align_up(rows * 4, 256);
+bool levels_in_range(const hyd_decode_params* p) { return p->n_levels >= 0 && p->n_levels <= HYD_MAX_LEVELS; }
+
+// Shapes only.  The caller has checked levels_in_range (each entry point has its own answer to that).  The prefix-only form
+// plans its one pass with the default split cap, every other form shares the merge budget among its levels.
+void plan_decode(const hyd_decode_params* p, DecodePlan* d) {
+    const hyd_suffix_params& sp = p->suffix;
+    memset(d, 0, sizeof(*d));
+    const bool prefix_only = p->n_levels == 1 && sp.kv_len == 0;
+    d->two_stream_ok = p->n_levels > 0 && sp.kv_len > 0;
+    // (a two-stream phase on prefix-only shapes is refused by the launch, and sized like the prefix-only form by the queries)
+    d->form = (p->phase == HYD_PHASE_UNIQUE_PARTIAL || p->phase == HYD_PHASE_MERGE) ? kTwoStream : prefix_only ? kPrefixOnly : kInOrder;
+    const int cap = prefix_only ? kMaxSplits : level_split_cap(p->n_levels);
+    const size_t rows = (size_t)sp.B * sp.nq * sp.Hq;
+    for (; d->n_planned < p->n_levels; ++d->n_planned) {
+        LevelPlan& lv = d->level[d->n_planned];
+        level_to_prefix(p, d->n_planned, &lv.pp);
+        if ((d->rc = plan_prefix(&lv.pp, &lv.pl, cap))) return;
+        if (prefix_only) {
+            d->levels_bytes = prefix_ws_bytes(&lv.pp, lv.pl);
+            continue;
+        }
+        lv.small = level_is_small(lv.pp, lv.pl);
+        lv.count = (lv.pl.nsplit == 1 || lv.small) ? 1 : lv.pl.nsplit;
+        lv.is_f32 = (lv.count > 1 || (p->f32_partials != 0 && !lv.small)) ? 1 : 0;
+        lv.layout = slice_layout(rows, sp.D, lv.is_f32 ? 4 : 2, lv.count);
+        d->levels_bytes += lv.layout.bytes;
+        d->n_parts += lv.count;
+    }
+    if (d->two_stream_ok) d->unique = slice_layout(rows, sp.D, 2, 1);
+    if (d->form == kInOrder && decode_runs_as_one_launch(p, d->level[0])) d->form = kOneLaunch;
 }
 
 int check_prefix_ptrs(const hyd_prefix_params* p) {
@@ -484,6 +573,53 @@ int check_prefix_ptrs(const hyd_prefix_params* p) {
         (rc = check_stride8(p->k_head_stride, "k_head_stride")) || (rc = check_stride8(p->v_group_stride, "v_group_stride")) ||
         (rc = check_stride8(p->v_tok_stride, "v_tok_stride")) || (rc = check_stride8(p->v_head_stride, "v_head_stride")))
         return rc;
+    return HYD_OK;
+}
+
+// ---- the logits entry points (hyd_sample_tokens, _filtered, _penalized, hyd_token_logprobs) ------------------------------------------
+int logits_esz(int dtype) { return dtype == HYD_F32 ? 4 : 2; }
+
+// The header of every [rows, n] logits call: dtype, row count, row length (max_n = 0: unbounded)
+int check_logits_rows(int dtype, int64_t rows, int n, int max_n) {
+    if (dtype != HYD_F16 && dtype != HYD_BF16 && dtype != HYD_F32) return fail(HYD_ERR_UNSUPPORTED, "dtype %d", dtype);
+    if (rows < 0 || rows > (1LL << 31) || n <= 0) return fail(HYD_ERR_BAD_ARG, "rows %lld, n %d", (long long)rows, n);
+    if (max_n && n > max_n) return fail(HYD_ERR_UNSUPPORTED, "n %d: rows of up to %d logits", n, max_n);
+    return HYD_OK;
+}
+int check_row_stride(int64_t row_stride, int n) {
+    return row_stride < n ? fail(HYD_ERR_BAD_ARG, "row_stride %lld < n %d", (long long)row_stride, n) : HYD_OK;
+}
+// 16-byte loads of a row: the base aligned and the row stride a multiple of `per16` elements
+int logits_vec_ok(const void* logits, int64_t row_stride, int per16) { return (!misaligned(logits, 16) && row_stride % per16 == 0) ? 1 : 0; }
+
+// What hyd_sample_tokens_filtered checks up to the row stride; the penalised sampler's parameters start with the same fields.
+template <typename P>
+int check_filter(const P* p) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    const int rc = check_logits_rows(p->dtype, p->rows, p->n, HYD_SAMPLE_FILTER_MAX_N);
+    if (rc) return rc;
+    if (!p->logits || !p->out) return fail(HYD_ERR_BAD_ARG, "logits / out is null");
+    if (!(p->temperature >= 0.f)) return fail(HYD_ERR_BAD_ARG, "temperature %g must be >= 0", (double)p->temperature);
+    if (p->top_k < 0) return fail(HYD_ERR_BAD_ARG, "top_k %d must be >= 0 (0 = off)", p->top_k);
+    if (!(p->top_p > 0.f && p->top_p <= 1.f)) return fail(HYD_ERR_BAD_ARG, "top_p %g must be in (0, 1] (1 = off)", (double)p->top_p);
+    if (!(p->min_p >= 0.f && p->min_p <= 1.f)) return fail(HYD_ERR_BAD_ARG, "min_p %g must be in [0, 1] (0 = off)", (double)p->min_p);
+    return check_row_stride(p->row_stride, p->n);
+}
+// ... and its last check, the alignment of the four row tensors, with the argument block of the filtered draw
+template <typename P>
+int fill_filter_args(const P* p, FilterArgs* a) {
+    const int esz = logits_esz(p->dtype);
+    if (misaligned(p->logits, esz) || misaligned(p->out, 8) || misaligned(p->logprobs, 4) || misaligned(p->kept, 4))
+        return fail(HYD_ERR_BAD_ARG, "logits / out / logprobs / kept is not aligned to its element size");
+    memset(a, 0, sizeof(*a));
+    a->logits = p->logits; a->out = p->out; a->logprobs = p->logprobs; a->kept = p->kept;
+    a->row_stride = p->row_stride; a->seed = p->seed; a->offset = p->offset;
+    a->rows = p->rows; a->n = p->n;
+    a->inv_temperature = p->temperature > 0.f ? 1.0f / p->temperature : 0.f;  // (as hyd_sample_tokens: the same noise scale)
+    a->top_k = p->top_k < p->n ? p->top_k : 0;
+    a->top_p = p->top_p;
+    a->log_min_p = p->min_p > 0.f ? (float)log((double)p->min_p) : -INFINITY;
+    a->vec_ok = logits_vec_ok(p->logits, p->row_stride, 16 / esz);
     return HYD_OK;
 }
 
@@ -521,31 +657,21 @@ int hyd_prefix_attn_fwd(const hyd_prefix_params* p, void* stream) {
     return run_prefix(p, pl, /*merge=*/true, static_cast<hipStream_t>(stream));
 }
 
-int hyd_suffix_attn_fwd(const hyd_suffix_params* p, void* stream) {
-    int rc = check_suffix(p, true);
-    if (rc) return rc;
-    if (p->n_partials < 0 || p->n_partials > HYD_MAX_LEVELS) return fail(HYD_ERR_BAD_ARG, "n_partials %d", p->n_partials);
-    if (p->kv_len == 0 && p->n_partials == 0) return fail(HYD_ERR_BAD_ARG, "kv_len == 0 and no partials");
-    return run_suffix(p, p->partials, p->n_partials, static_cast<hipStream_t>(stream));
-}
-
 int hyd_suffix_attn_fwd_kvq(const hyd_suffix_params* p, const hyd_kv_quant* kq, void* stream) {
-    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
     int rc = check_suffix(p, true);
     if (rc) return rc;
-    bool fp8;
-    if ((rc = check_kvq(kq, p->dtype, &fp8))) return rc;
-    if (!fp8) return hyd_suffix_attn_fwd(p, stream);
+    if ((rc = check_kvq(&kq, p->dtype))) return rc;
     if (p->n_partials < 0 || p->n_partials > HYD_MAX_LEVELS) return fail(HYD_ERR_BAD_ARG, "n_partials %d", p->n_partials);
     if (p->kv_len == 0 && p->n_partials == 0) return fail(HYD_ERR_BAD_ARG, "kv_len == 0 and no partials");
     return run_suffix(p, p->partials, p->n_partials, static_cast<hipStream_t>(stream), kq);
 }
 
+int hyd_suffix_attn_fwd(const hyd_suffix_params* p, void* stream) { return hyd_suffix_attn_fwd_kvq(p, nullptr, stream); }
+
 int hyd_kv_quant_supported(const hyd_suffix_params* p, const hyd_kv_quant* kq) {
     if (!p) return 0;
-    if (!kq || kq->kv_dtype == p->dtype) return 1;
-    if (kq->kv_dtype != HYD_FP8_E4M3) return 0;
-    return kvq_native(p, kq) ? 1 : 0;
+    const KvqKind kind = kvq_kind(kq, p->dtype);
+    return kind == kKvqNone || (kind == kKvqFp8 && kvq_native(p, kq)) ? 1 : 0;
 }
 
 int hyd_combine_lse(const void* const* outs, const float* const* lses, int32_t n, int64_t rows, int32_t D,
@@ -556,12 +682,12 @@ int hyd_combine_lse(const void* const* outs, const float* const* lses, int32_t n
     if (dtype != HYD_F16 && dtype != HYD_BF16 && dtype != HYD_F32) return fail(HYD_ERR_UNSUPPORTED, "dtype %d", dtype);
     CombineArgs c;
     memset(&c, 0, sizeof(c));
-    bool aligned = (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
+    bool aligned = !misaligned(out, 16);
     for (int i = 0; i < n; ++i) {
         if (!outs[i] || !lses[i]) return fail(HYD_ERR_BAD_ARG, "partial %d is null", i);
         c.outs[i] = outs[i];
         c.lses[i] = lses[i];
-        aligned = aligned && (reinterpret_cast<uintptr_t>(outs[i]) & 15u) == 0;
+        aligned = aligned && !misaligned(outs[i], 16);
     }
     c.n = n;
     c.rows = rows;
@@ -572,27 +698,14 @@ int hyd_combine_lse(const void* const* outs, const float* const* lses, int32_t n
     c.out_lse = out_lse;
     c.lse_layout = HYD_LSE_BQH;
     c.scalar_only = aligned ? 0 : 1;  // unaligned views take the element-wise kernel
-    int rc = launch_combine(c, static_cast<hipStream_t>(stream));
-    return rc ? fail(HYD_ERR_LAUNCH, "combine kernel launch failed: hip error %d", rc) : HYD_OK;
+    return launched(launch_combine(c, static_cast<hipStream_t>(stream)), "combine kernel launch");
 }
-
-static int rope_impl(const hyd_rope_params* p, const hyd_kv_quant* kq, void* stream);
-
-int hyd_rope_append_decode(const hyd_rope_params* p, void* stream) { return rope_impl(p, nullptr, stream); }
 
 int hyd_rope_append_decode_kvq(const hyd_rope_params* p, const hyd_kv_quant* kq, void* stream) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
     int rc = check_common(p->dtype, p->B, 1, p->Hq, p->Hkv, p->D);
     if (rc) return rc;
-    bool fp8;
-    if ((rc = check_kvq(kq, p->dtype, &fp8))) return rc;
-    return rope_impl(p, fp8 ? kq : nullptr, stream);
-}
-
-static int rope_impl(const hyd_rope_params* p, const hyd_kv_quant* kq, void* stream) {
-    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
-    int rc = check_common(p->dtype, p->B, 1, p->Hq, p->Hkv, p->D);
-    if (rc) return rc;
+    if ((rc = check_kvq(&kq, p->dtype))) return rc;
     if ((rc = check_ptr_align(p->q, "q")) || (rc = check_ptr_align(p->k, "k")) || (rc = check_ptr_align(p->v, "v")) ||
         (rc = check_ptr_align(p->q_out, "q_out")) || (rc = check_ptr_align(p->k_cache, "k_cache")) ||
         (rc = check_ptr_align(p->v_cache, "v_cache")) || (rc = check_ptr_align(p->cos, "cos")) ||
@@ -622,12 +735,12 @@ static int rope_impl(const hyd_rope_params* p, const hyd_kv_quant* kq, void* str
         ka.a = a;
         ka.k_scale = kq->k_scale;
         ka.v_scale = kq->v_scale;
-        rc = launch_rope_append_fp8(ka, p->dtype, p->D, static_cast<hipStream_t>(stream));
-        return rc ? fail(HYD_ERR_LAUNCH, "rope_append (fp8 caches) kernel launch failed: hip error %d", rc) : HYD_OK;
+        return launched(launch_rope_append_fp8(ka, p->dtype, p->D, static_cast<hipStream_t>(stream)), "rope_append (fp8 caches) kernel launch");
     }
-    rc = launch_rope_append(a, p->dtype, p->D, static_cast<hipStream_t>(stream));
-    return rc ? fail(HYD_ERR_LAUNCH, "rope_append kernel launch failed: hip error %d", rc) : HYD_OK;
+    return launched(launch_rope_append(a, p->dtype, p->D, static_cast<hipStream_t>(stream)), "rope_append kernel launch");
 }
+
+int hyd_rope_append_decode(const hyd_rope_params* p, void* stream) { return hyd_rope_append_decode_kvq(p, nullptr, stream); }
 
 int hyd_add_rmsnorm(const hyd_add_rmsnorm_params* p, void* stream) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
@@ -648,8 +761,7 @@ int hyd_add_rmsnorm(const hyd_add_rmsnorm_params* p, void* stream) {
     a.x = p->x; a.residual = p->residual; a.weight = p->weight; a.sum_out = p->residual ? p->sum_out : nullptr; a.norm_out = p->norm_out;
     a.x_rs = p->x_row_stride; a.r_rs = p->residual_row_stride; a.s_rs = p->sum_row_stride; a.o_rs = p->norm_row_stride;
     a.rows = p->rows; a.n = p->n; a.eps = p->eps;
-    rc = launch_add_rmsnorm(a, p->dtype, static_cast<hipStream_t>(stream));
-    return rc ? fail(HYD_ERR_LAUNCH, "add_rmsnorm kernel launch failed: hip error %d", rc) : HYD_OK;
+    return launched(launch_add_rmsnorm(a, p->dtype, static_cast<hipStream_t>(stream)), "add_rmsnorm kernel launch");
 }
 
 int hyd_swiglu(const hyd_swiglu_params* p, void* stream) {
@@ -668,70 +780,36 @@ int hyd_swiglu(const hyd_swiglu_params* p, void* stream) {
     a.gate = p->gate; a.up = p->up; a.out = p->out;
     a.g_rs = p->gate_row_stride; a.u_rs = p->up_row_stride; a.o_rs = p->out_row_stride;
     a.rows = p->rows; a.n = p->n;
-    rc = launch_swiglu(a, p->dtype, static_cast<hipStream_t>(stream));
-    return rc ? fail(HYD_ERR_LAUNCH, "swiglu kernel launch failed: hip error %d", rc) : HYD_OK;
+    return launched(launch_swiglu(a, p->dtype, static_cast<hipStream_t>(stream)), "swiglu kernel launch");
 }
 
 int hyd_sample_tokens(const hyd_sample_params* p, void* stream) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
-    if (p->dtype != HYD_F16 && p->dtype != HYD_BF16 && p->dtype != HYD_F32) return fail(HYD_ERR_UNSUPPORTED, "dtype %d", p->dtype);
-    if (p->rows < 0 || p->n <= 0) return fail(HYD_ERR_BAD_ARG, "rows %d, n %d", p->rows, p->n);
+    int rc = check_logits_rows(p->dtype, p->rows, p->n, /*max_n=*/0);  // (the plain sampler has no upper bound on n)
+    if (rc) return rc;
     if (!p->logits || !p->out) return fail(HYD_ERR_BAD_ARG, "logits / out is null");
     if (!(p->temperature >= 0.f)) return fail(HYD_ERR_BAD_ARG, "temperature %g must be >= 0", (double)p->temperature);
-    if (p->row_stride < p->n) return fail(HYD_ERR_BAD_ARG, "row_stride %lld < n %d", (long long)p->row_stride, p->n);
-    const int esz = p->dtype == HYD_F32 ? 4 : 2;
-    if ((reinterpret_cast<uintptr_t>(p->logits) & (uintptr_t)(esz - 1)) != 0 || (reinterpret_cast<uintptr_t>(p->out) & 7u) != 0)
-        return fail(HYD_ERR_BAD_ARG, "logits / out is not aligned to its element size");
+    if ((rc = check_row_stride(p->row_stride, p->n))) return rc;
+    if (misaligned(p->logits, logits_esz(p->dtype)) || misaligned(p->out, 8)) return fail(HYD_ERR_BAD_ARG, "logits / out is not aligned to its element size");
     SampleArgs a;
     memset(&a, 0, sizeof(a));
     a.logits = p->logits; a.out = p->out; a.row_stride = p->row_stride; a.seed = p->seed; a.offset = p->offset;
     a.rows = p->rows; a.n = p->n;
     a.inv_temperature = p->temperature > 0.f ? 1.0f / p->temperature : 0.f;
-    a.vec_ok = ((reinterpret_cast<uintptr_t>(p->logits) & 15u) == 0 && p->row_stride % 8 == 0) ? 1 : 0;
-    const int rc = launch_sample(a, p->dtype, static_cast<hipStream_t>(stream));
-    return rc ? fail(HYD_ERR_LAUNCH, "sample kernel launch failed: hip error %d", rc) : HYD_OK;
+    a.vec_ok = logits_vec_ok(p->logits, p->row_stride, 8);  // (8 elements for every dtype, fp32 included: as released)
+    return launched(launch_sample(a, p->dtype, static_cast<hipStream_t>(stream)), "sample kernel launch");
 }
 
 int hyd_sample_tokens_filtered(const hyd_sample_filter_params* p, void* stream) {
-    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
-    if (p->dtype != HYD_F16 && p->dtype != HYD_BF16 && p->dtype != HYD_F32) return fail(HYD_ERR_UNSUPPORTED, "dtype %d", p->dtype);
-    if (p->rows < 0 || p->n <= 0) return fail(HYD_ERR_BAD_ARG, "rows %d, n %d", p->rows, p->n);
-    if (p->n > HYD_SAMPLE_FILTER_MAX_N) return fail(HYD_ERR_UNSUPPORTED, "n %d: rows of up to %d logits", p->n, HYD_SAMPLE_FILTER_MAX_N);
-    if (!p->logits || !p->out) return fail(HYD_ERR_BAD_ARG, "logits / out is null");
-    if (!(p->temperature >= 0.f)) return fail(HYD_ERR_BAD_ARG, "temperature %g must be >= 0", (double)p->temperature);
-    if (p->top_k < 0) return fail(HYD_ERR_BAD_ARG, "top_k %d must be >= 0 (0 = off)", p->top_k);
-    if (!(p->top_p > 0.f && p->top_p <= 1.f)) return fail(HYD_ERR_BAD_ARG, "top_p %g must be in (0, 1] (1 = off)", (double)p->top_p);
-    if (!(p->min_p >= 0.f && p->min_p <= 1.f)) return fail(HYD_ERR_BAD_ARG, "min_p %g must be in [0, 1] (0 = off)", (double)p->min_p);
-    if (p->row_stride < p->n) return fail(HYD_ERR_BAD_ARG, "row_stride %lld < n %d", (long long)p->row_stride, p->n);
-    const int esz = p->dtype == HYD_F32 ? 4 : 2;
-    if ((reinterpret_cast<uintptr_t>(p->logits) & (uintptr_t)(esz - 1)) != 0 || (reinterpret_cast<uintptr_t>(p->out) & 7u) != 0 ||
-        (reinterpret_cast<uintptr_t>(p->logprobs) & 3u) != 0 || (reinterpret_cast<uintptr_t>(p->kept) & 3u) != 0)
-        return fail(HYD_ERR_BAD_ARG, "logits / out / logprobs / kept is not aligned to its element size");
     FilterArgs a;
-    memset(&a, 0, sizeof(a));
-    a.logits = p->logits; a.out = p->out; a.logprobs = p->logprobs; a.kept = p->kept;
-    a.row_stride = p->row_stride; a.seed = p->seed; a.offset = p->offset;
-    a.rows = p->rows; a.n = p->n;
-    a.inv_temperature = p->temperature > 0.f ? 1.0f / p->temperature : 0.f;  // (as hyd_sample_tokens: the same noise scale)
-    a.top_k = p->top_k < p->n ? p->top_k : 0;
-    a.top_p = p->top_p;
-    a.log_min_p = p->min_p > 0.f ? (float)log((double)p->min_p) : -INFINITY;
-    a.vec_ok = ((reinterpret_cast<uintptr_t>(p->logits) & 15u) == 0 && p->row_stride % (16 / esz) == 0) ? 1 : 0;
-    const int rc = launch_sample_filter(a, p->dtype, static_cast<hipStream_t>(stream));
-    return rc ? fail(HYD_ERR_LAUNCH, "sample_filter kernel launch failed: hip error %d", rc) : HYD_OK;
+    int rc = check_filter(p);
+    if (!rc) rc = fill_filter_args(p, &a);
+    return rc ? rc : launched(launch_sample_filter(a, p->dtype, static_cast<hipStream_t>(stream)), "sample_filter kernel launch");
 }
 
 int hyd_sample_tokens_penalized(const hyd_sample_penalty_params* p, void* stream) {
-    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
-    if (p->dtype != HYD_F16 && p->dtype != HYD_BF16 && p->dtype != HYD_F32) return fail(HYD_ERR_UNSUPPORTED, "dtype %d", p->dtype);
-    if (p->rows < 0 || p->n <= 0) return fail(HYD_ERR_BAD_ARG, "rows %d, n %d", p->rows, p->n);
-    if (p->n > HYD_SAMPLE_FILTER_MAX_N) return fail(HYD_ERR_UNSUPPORTED, "n %d: rows of up to %d logits", p->n, HYD_SAMPLE_FILTER_MAX_N);
-    if (!p->logits || !p->out) return fail(HYD_ERR_BAD_ARG, "logits / out is null");
-    if (!(p->temperature >= 0.f)) return fail(HYD_ERR_BAD_ARG, "temperature %g must be >= 0", (double)p->temperature);
-    if (p->top_k < 0) return fail(HYD_ERR_BAD_ARG, "top_k %d must be >= 0 (0 = off)", p->top_k);
-    if (!(p->top_p > 0.f && p->top_p <= 1.f)) return fail(HYD_ERR_BAD_ARG, "top_p %g must be in (0, 1] (1 = off)", (double)p->top_p);
-    if (!(p->min_p >= 0.f && p->min_p <= 1.f)) return fail(HYD_ERR_BAD_ARG, "min_p %g must be in [0, 1] (0 = off)", (double)p->min_p);
-    if (p->row_stride < p->n) return fail(HYD_ERR_BAD_ARG, "row_stride %lld < n %d", (long long)p->row_stride, p->n);
+    int rc = check_filter(p);
+    if (rc) return rc;
     if (!(p->repetition_penalty > 0.0) || std::isinf(p->repetition_penalty))
         return fail(HYD_ERR_BAD_ARG, "repetition_penalty %g must be a finite number > 0 (1 = off)", p->repetition_penalty);
     if (!std::isfinite(p->frequency_penalty) || !std::isfinite(p->presence_penalty))
@@ -741,7 +819,7 @@ int hyd_sample_tokens_penalized(const hyd_sample_penalty_params* p, void* stream
     for (int l = 0; l < p->n_context; ++l) {
         if (!p->context[l].bits) return fail(HYD_ERR_BAD_ARG, "context[%d].bits is null", l);
         if (p->context[l].rows_per_group <= 0) return fail(HYD_ERR_BAD_ARG, "context[%d].rows_per_group %d must be > 0", l, p->context[l].rows_per_group);
-        if ((reinterpret_cast<uintptr_t>(p->context[l].bits) & 3u) != 0) return fail(HYD_ERR_BAD_ARG, "context[%d].bits is not aligned to its element size", l);
+        if (misaligned(p->context[l].bits, 4)) return fail(HYD_ERR_BAD_ARG, "context[%d].bits is not aligned to its element size", l);
     }
     if ((p->gen == nullptr) != (p->gen_len == nullptr)) return fail(HYD_ERR_BAD_ARG, "gen and gen_len go together (one of them is null)");
     if (p->gen_stride < 0) return fail(HYD_ERR_BAD_ARG, "gen_stride %d must be >= 0", p->gen_stride);
@@ -749,23 +827,11 @@ int hyd_sample_tokens_penalized(const hyd_sample_penalty_params* p, void* stream
     if (p->append_out && !p->gen) return fail(HYD_ERR_BAD_ARG, "append_out needs gen and gen_len (null)");
     if (p->n_bias < 0 || p->n_bias > HYD_SAMPLE_BIAS_MAX) return fail(HYD_ERR_BAD_ARG, "n_bias %d: 0 to %d logit-bias entries", p->n_bias, HYD_SAMPLE_BIAS_MAX);
     if (p->n_bias > 0 && (!p->bias_ids || !p->bias_values)) return fail(HYD_ERR_BAD_ARG, "n_bias %d needs bias_ids and bias_values (null)", p->n_bias);
-    const int esz = p->dtype == HYD_F32 ? 4 : 2;
-    if ((reinterpret_cast<uintptr_t>(p->logits) & (uintptr_t)(esz - 1)) != 0 || (reinterpret_cast<uintptr_t>(p->out) & 7u) != 0 ||
-        (reinterpret_cast<uintptr_t>(p->logprobs) & 3u) != 0 || (reinterpret_cast<uintptr_t>(p->kept) & 3u) != 0)
-        return fail(HYD_ERR_BAD_ARG, "logits / out / logprobs / kept is not aligned to its element size");
-    if ((reinterpret_cast<uintptr_t>(p->gen) & 3u) != 0 || (reinterpret_cast<uintptr_t>(p->gen_len) & 3u) != 0 ||
-        (reinterpret_cast<uintptr_t>(p->bias_ids) & 7u) != 0 || (reinterpret_cast<uintptr_t>(p->bias_values) & 3u) != 0)
-        return fail(HYD_ERR_BAD_ARG, "gen / gen_len / bias_ids / bias_values is not aligned to its element size");
     PenaltyArgs a;
     memset(&a, 0, sizeof(a));
-    a.f.logits = p->logits; a.f.out = p->out; a.f.logprobs = p->logprobs; a.f.kept = p->kept;
-    a.f.row_stride = p->row_stride; a.f.seed = p->seed; a.f.offset = p->offset;
-    a.f.rows = p->rows; a.f.n = p->n;
-    a.f.inv_temperature = p->temperature > 0.f ? 1.0f / p->temperature : 0.f;  // (as hyd_sample_tokens_filtered, field by field)
-    a.f.top_k = p->top_k < p->n ? p->top_k : 0;
-    a.f.top_p = p->top_p;
-    a.f.log_min_p = p->min_p > 0.f ? (float)log((double)p->min_p) : -INFINITY;
-    a.f.vec_ok = ((reinterpret_cast<uintptr_t>(p->logits) & 15u) == 0 && p->row_stride % (16 / esz) == 0) ? 1 : 0;
+    if ((rc = fill_filter_args(p, &a.f))) return rc;
+    if (misaligned(p->gen, 4) || misaligned(p->gen_len, 4) || misaligned(p->bias_ids, 8) || misaligned(p->bias_values, 4))
+        return fail(HYD_ERR_BAD_ARG, "gen / gen_len / bias_ids / bias_values is not aligned to its element size");
     a.rep = p->repetition_penalty; a.inv_rep = 1.0 / p->repetition_penalty; a.freq = p->frequency_penalty; a.pres = p->presence_penalty;
     a.n_ctx = p->n_context; a.words = (p->n + 31) / 32;
     for (int l = 0; l < p->n_context; ++l) {
@@ -774,8 +840,7 @@ int hyd_sample_tokens_penalized(const hyd_sample_penalty_params* p, void* stream
     }
     a.gen = p->gen; a.gen_len = p->gen_len; a.gen_stride = p->gen_stride; a.append_out = p->append_out ? 1 : 0;
     a.bias_ids = p->bias_ids; a.bias_values = p->bias_values; a.n_bias = p->n_bias;
-    const int rc = launch_sample_penalty(a, p->dtype, static_cast<hipStream_t>(stream));
-    return rc ? fail(HYD_ERR_LAUNCH, "sample_penalty kernel launch failed: hip error %d", rc) : HYD_OK;
+    return launched(launch_sample_penalty(a, p->dtype, static_cast<hipStream_t>(stream)), "sample_penalty kernel launch");
 }
 
 int hyd_token_bitmap_build(const hyd_token_bitmap_params* p, void* stream) {
@@ -784,38 +849,33 @@ int hyd_token_bitmap_build(const hyd_token_bitmap_params* p, void* stream) {
     if (p->n <= 0 || p->n > HYD_SAMPLE_FILTER_MAX_N) return fail(HYD_ERR_BAD_ARG, "n %d: 1 to %d", p->n, HYD_SAMPLE_FILTER_MAX_N);
     if (!p->ids || !p->bits) return fail(HYD_ERR_BAD_ARG, "ids / bits is null");
     if (p->id_stride < p->L) return fail(HYD_ERR_BAD_ARG, "id_stride %lld < L %d", (long long)p->id_stride, p->L);
-    if ((reinterpret_cast<uintptr_t>(p->ids) & 7u) != 0 || (reinterpret_cast<uintptr_t>(p->lens) & 7u) != 0 || (reinterpret_cast<uintptr_t>(p->bits) & 3u) != 0)
+    if (misaligned(p->ids, 8) || misaligned(p->lens, 8) || misaligned(p->bits, 4))
         return fail(HYD_ERR_BAD_ARG, "ids / lens / bits is not aligned to its element size");
     BitmapArgs a;
     memset(&a, 0, sizeof(a));
     a.ids = p->ids; a.lens = p->lens; a.bits = p->bits; a.id_stride = p->id_stride;
     a.groups = p->groups; a.L = p->L; a.n = p->n; a.words = (p->n + 31) / 32;
-    const int rc = launch_token_bitmap(a, static_cast<hipStream_t>(stream));
-    return rc ? fail(HYD_ERR_LAUNCH, "token_bitmap kernel launch failed: hip error %d", rc) : HYD_OK;
+    return launched(launch_token_bitmap(a, static_cast<hipStream_t>(stream)), "token_bitmap kernel launch");
 }
 
 int hyd_token_logprobs(const hyd_token_logprob_params* p, void* stream) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
-    if (p->dtype != HYD_F16 && p->dtype != HYD_BF16 && p->dtype != HYD_F32) return fail(HYD_ERR_UNSUPPORTED, "dtype %d", p->dtype);
-    if (p->rows < 0 || p->rows > (1LL << 31) || p->n <= 0) return fail(HYD_ERR_BAD_ARG, "rows %lld, n %d", (long long)p->rows, p->n);
-    if (p->n > HYD_SAMPLE_FILTER_MAX_N) return fail(HYD_ERR_UNSUPPORTED, "n %d: rows of up to %d logits", p->n, HYD_SAMPLE_FILTER_MAX_N);
+    int rc = check_logits_rows(p->dtype, p->rows, p->n, HYD_SAMPLE_FILTER_MAX_N);
+    if (rc) return rc;
     if (!p->logits || !p->targets || !p->logprobs || !p->greedy) return fail(HYD_ERR_BAD_ARG, "logits / targets / logprobs / greedy is null");
     if (p->top_n < 0 || p->top_n > HYD_TOP_LOGPROBS_MAX) return fail(HYD_ERR_BAD_ARG, "top_n %d must be in [0, %d]", p->top_n, HYD_TOP_LOGPROBS_MAX);
     if (p->top_n > 0 && (!p->top_ids || !p->top_logprobs)) return fail(HYD_ERR_BAD_ARG, "top_n %d needs top_ids and top_logprobs (null)", p->top_n);
-    if (p->row_stride < p->n) return fail(HYD_ERR_BAD_ARG, "row_stride %lld < n %d", (long long)p->row_stride, p->n);
-    const int esz = p->dtype == HYD_F32 ? 4 : 2;
-    if ((reinterpret_cast<uintptr_t>(p->logits) & (uintptr_t)(esz - 1)) != 0 || (reinterpret_cast<uintptr_t>(p->targets) & 7u) != 0 ||
-        (reinterpret_cast<uintptr_t>(p->logprobs) & 3u) != 0 || (reinterpret_cast<uintptr_t>(p->top_ids) & 7u) != 0 ||
-        (reinterpret_cast<uintptr_t>(p->top_logprobs) & 3u) != 0)
+    if ((rc = check_row_stride(p->row_stride, p->n))) return rc;
+    const int esz = logits_esz(p->dtype);
+    if (misaligned(p->logits, esz) || misaligned(p->targets, 8) || misaligned(p->logprobs, 4) || misaligned(p->top_ids, 8) || misaligned(p->top_logprobs, 4))
         return fail(HYD_ERR_BAD_ARG, "logits / targets / logprobs / top_ids / top_logprobs is not aligned to its element size");
     TokenLogprobArgs a;
     memset(&a, 0, sizeof(a));
     a.logits = p->logits; a.targets = p->targets; a.logprobs = p->logprobs; a.greedy = p->greedy;
     a.top_ids = p->top_ids; a.top_logprobs = p->top_logprobs;
     a.row_stride = p->row_stride; a.rows = p->rows; a.n = p->n; a.top_n = p->top_n;
-    a.vec_ok = ((reinterpret_cast<uintptr_t>(p->logits) & 15u) == 0 && p->row_stride % (16 / esz) == 0) ? 1 : 0;
-    const int rc = launch_token_logprob(a, p->dtype, static_cast<hipStream_t>(stream));
-    return rc ? fail(HYD_ERR_LAUNCH, "token_logprob kernel launch failed: hip error %d", rc) : HYD_OK;
+    a.vec_ok = logits_vec_ok(p->logits, p->row_stride, 16 / esz);
+    return launched(launch_token_logprob(a, p->dtype, static_cast<hipStream_t>(stream)), "token_logprob kernel launch");
 }
 
 int hyd_stop_update(const hyd_stop_params* p, void* stream) {
@@ -831,13 +891,10 @@ int hyd_stop_update(const hyd_stop_params* p, void* stream) {
         return fail(HYD_ERR_BAD_ARG, "tok / out / length / reason / stop_index / live is null");
     if (!p->start_pos || !p->feed || !p->next_pos) return fail(HYD_ERR_BAD_ARG, "start_pos / feed / next_pos is null");
     if (p->n_stop > 0 && !p->stop_tokens) return fail(HYD_ERR_BAD_ARG, "n_stop %d needs stop_tokens (null)", p->n_stop);
-    if ((reinterpret_cast<uintptr_t>(p->tok) & 7u) != 0 || (reinterpret_cast<uintptr_t>(p->out) & 7u) != 0 ||
-        (reinterpret_cast<uintptr_t>(p->stop_tokens) & 7u) != 0 || (reinterpret_cast<uintptr_t>(p->start_pos) & 7u) != 0 ||
-        (reinterpret_cast<uintptr_t>(p->shared_len) & 7u) != 0 || (reinterpret_cast<uintptr_t>(p->feed) & 7u) != 0 ||
-        (reinterpret_cast<uintptr_t>(p->next_pos) & 7u) != 0)
+    if (misaligned(p->tok, 8) || misaligned(p->out, 8) || misaligned(p->stop_tokens, 8) || misaligned(p->start_pos, 8) ||
+        misaligned(p->shared_len, 8) || misaligned(p->feed, 8) || misaligned(p->next_pos, 8))
         return fail(HYD_ERR_BAD_ARG, "tok / out / stop_tokens / start_pos / shared_len / feed / next_pos is not aligned to its element size");
-    if ((reinterpret_cast<uintptr_t>(p->length) & 3u) != 0 || (reinterpret_cast<uintptr_t>(p->reason) & 3u) != 0 ||
-        (reinterpret_cast<uintptr_t>(p->stop_index) & 3u) != 0 || (reinterpret_cast<uintptr_t>(p->live) & 3u) != 0)
+    if (misaligned(p->length, 4) || misaligned(p->reason, 4) || misaligned(p->stop_index, 4) || misaligned(p->live, 4))
         return fail(HYD_ERR_BAD_ARG, "length / reason / stop_index / live is not aligned to its element size");
     if (p->rows == 0) return HYD_OK;
     StopArgs a;
@@ -849,31 +906,8 @@ int hyd_stop_update(const hyd_stop_params* p, void* stream) {
     for (int k = 0; k < p->n_stop; ++k) a.stop_lens[k] = p->stop_lens[k];
     a.rows = p->rows; a.t = p->t; a.n_eos = p->n_eos; a.n_stop = p->n_stop;
     a.include_stop = p->include_stop ? 1 : 0; a.retire = p->retire ? 1 : 0;
-    const int rc = launch_stop_update(a, static_cast<hipStream_t>(stream));
-    return rc ? fail(HYD_ERR_LAUNCH, "stop_update kernel launch failed: hip error %d", rc) : HYD_OK;
+    return launched(launch_stop_update(a, static_cast<hipStream_t>(stream)), "stop_update kernel launch");
 }
-
-// hyd_decode_params.single_launch_small: one uniform shared level that already counts as small (few query rows per
-// (group, kv head), short prefix), unique keys present, the same token strides in the shared and the unique tensors, and
-// so few keys in all that the call is launch latency.  Measured per graph-replayed call (tests/probes/single_launch_probe.py,
-// units x keys = B * Hkv * (P + S)): 1152 keys (BASELINE config 1) 6.8 -> 4.1 us, 2176 keys 11.4 -> 8.1, 8072 keys (two
-// sequences on a 1000-key prefix) 19.5 -> 16.5, 8704 keys (32 sequences) 14.0 -> 14.1: even.  Shapes only: capture-safe.
-constexpr int64_t kSingleLaunchMaxKeys = 8192;
-static bool decode_runs_as_one_launch(const hyd_decode_params* p, const hyd_prefix_params* pps, const PrefixPlan* pls, const bool* small) {
-    const hyd_suffix_params& sp = p->suffix;
-    if (p->phase != HYD_PHASE_ALL || !p->single_launch_small || p->n_levels != 1 || !small[0] || sp.kv_len <= 0) return false;
-    if (sp.lse) return false;  // suffix.lse is the LSE of the unique keys alone in every form; one walk over both segments cannot give it
-    const hyd_prefix_params& pp = pps[0];
-    if (pp.cu_seqlens_k || pp.sb <= 0 || sp.B % pp.sb != 0) return false;  // (a small level runs unsplit whatever the plan says)
-    if (pp.k_tok_stride != sp.k_tok_stride || pp.v_tok_stride != sp.v_tok_stride) return false;
-    if ((int64_t)sp.B * sp.Hkv * ((int64_t)pp.kv_len + sp.kv_len) > kSingleLaunchMaxKeys) return false;
-    SuffixArgs a;
-    fill_suffix_args(&sp, &a);
-    return suffix_gqa_eligible(a, sp.D, /*any_shape=*/true);
-}
-
-// attention.py:273-274: a single shared level and no unique keys -> the prefix result IS the answer
-static bool decode_is_prefix_only(const hyd_decode_params* p) { return p->n_levels == 1 && p->suffix.kv_len == 0; }
 
 int hyd_ipc_get_handle(const void* dev_ptr, void* handle_out) {
     static_assert(sizeof(hipIpcMemHandle_t) == HYD_IPC_HANDLE_BYTES, "IPC handle size");
@@ -932,32 +966,16 @@ int hyd_allreduce_sum(const hyd_allreduce_params* p, void* stream) {
         if (p->in != p->out) (void)hipMemcpyAsync(p->out, p->in, bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream));
         return HYD_OK;
     }
-    rc = launch_allreduce(blocks, allreduce_block_bytes(p->world, p->max_bytes), p->in, p->out, p->count, p->dtype, p->rank,
-                          p->world, p->max_bytes, p->timeout_log2_polls, static_cast<hipStream_t>(stream));
-    return rc ? fail(HYD_ERR_LAUNCH, "all-reduce kernel launch failed: hip error %d", rc) : HYD_OK;
+    return launched(launch_allreduce(blocks, allreduce_block_bytes(p->world, p->max_bytes), p->in, p->out, p->count, p->dtype, p->rank,
+                                     p->world, p->max_bytes, p->timeout_log2_polls, static_cast<hipStream_t>(stream)),
+                    "all-reduce kernel launch");
 }
 
 size_t hyd_decode_workspace_bytes(const hyd_decode_params* p) {
-    if (!p || p->n_levels < 0 || p->n_levels > HYD_MAX_LEVELS) return 0;
-    if (decode_is_prefix_only(p)) {
-        // written straight to `out` by the prefix pass; only its split-KV slices (if any) need scratch
-        hyd_prefix_params pp;
-        level_to_prefix(p, 0, &pp);
-        PrefixPlan pl;
-        if (plan_prefix(&pp, &pl)) return 0;
-        return prefix_ws_bytes(&pp, pl);
-    }
-    size_t total = 0;
-    for (int i = 0; i < p->n_levels; ++i) {
-        hyd_prefix_params pp;
-        level_to_prefix(p, i, &pp);
-        PrefixPlan pl;
-        if (plan_prefix(&pp, &pl, level_split_cap(p->n_levels))) return 0;
-        total += level_ws_bytes(pp, pl, p->f32_partials != 0);
-    }
-    // the unique pass's own partial (HYD_PHASE_UNIQUE_PARTIAL / HYD_PHASE_MERGE: the two-stream form)
-    if (p->n_levels > 0 && p->suffix.kv_len > 0) total += unique_partial_bytes(p->suffix);
-    return total;
+    if (!p || !levels_in_range(p)) return 0;
+    DecodePlan d;
+    plan_decode(p, &d);
+    return d.rc ? 0 : d.levels_bytes + d.unique.bytes;  // (the unique partial counts in every phase: one size for the whole call)
 }
 
 size_t hyd_workspace_bytes(int32_t B, int32_t nq, int32_t Hq, int32_t Hkv, int32_t D, int32_t n_levels,
@@ -987,13 +1005,10 @@ static int decode_impl(const hyd_decode_params* p, const hyd_kv_quant* kq, void*
 // does not round a 16-bit prefix partial, the two-kernel pair does: the pair is not what the caller's 16-bit results are, so such a
 // call is refused instead of quietly run as the pair.  (Hq == Hkv shapes keep ignoring the flag, as they always have.)
 static bool decode_kvq_is_one_launch(const hyd_decode_params* p, const hyd_kv_quant* kq) {
-    if (p->n_levels != 1 || p->suffix.kv_len <= 0 || !kvq_native_gqa(&p->suffix, kq)) return false;
-    hyd_prefix_params pp;
-    level_to_prefix(p, 0, &pp);
-    PrefixPlan pl;
-    if (plan_prefix(&pp, &pl, level_split_cap(1))) return false;  // (decode_impl reports it)
-    const bool small = level_is_small(pp, pl);
-    return decode_runs_as_one_launch(p, &pp, &pl, &small);
+    if (!levels_in_range(p) || !kvq_native_gqa(&p->suffix, kq)) return false;
+    DecodePlan d;
+    plan_decode(p, &d);
+    return !d.rc && d.form == kOneLaunch;  // (a level that does not plan: decode_impl reports it)
 }
 
 int hyd_decode_attn_fused(const hyd_decode_params* p, void* stream) { return decode_impl(p, nullptr, stream); }
@@ -1002,9 +1017,8 @@ int hyd_decode_attn_fused_kvq(const hyd_decode_params* p, const hyd_kv_quant* kq
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
     int rc = check_suffix(&p->suffix, true);
     if (rc) return rc;
-    bool fp8;
-    if ((rc = check_kvq(kq, p->suffix.dtype, &fp8))) return rc;
-    if (!fp8) return hyd_decode_attn_fused(p, stream);
+    if ((rc = check_kvq(&kq, p->suffix.dtype))) return rc;
+    if (!kq) return decode_impl(p, nullptr, stream);
     // fp8 unique caches: validated up front (every phase, also those that do not read the unique cache) so that the phases of one
     // call agree; kv_len == 0 reads no unique key and takes the existing path
     if (p->suffix.kv_len > 0 && !kvq_native(&p->suffix, kq)) return fail_kvq_shapes(p->suffix.D);
@@ -1016,9 +1030,9 @@ int hyd_decode_attn_fused_kvq(const hyd_decode_params* p, const hyd_kv_quant* kq
 
 int hyd_decode_kv_quant_supported(const hyd_decode_params* p, const hyd_kv_quant* kq) {
     if (!p) return 0;
-    if (!kq || kq->kv_dtype == p->suffix.dtype) return 1;
-    if (kq->kv_dtype != HYD_FP8_E4M3) return 0;
-    if (p->n_levels < 0 || p->n_levels > HYD_MAX_LEVELS) return 0;
+    const KvqKind kind = kvq_kind(kq, p->suffix.dtype);
+    if (kind != kKvqFp8) return kind == kKvqNone ? 1 : 0;
+    if (!levels_in_range(p)) return 0;
     if (p->suffix.kv_len <= 0) return p->suffix.kv_len == 0 ? 1 : 0;  // no unique key is read: the existing path
     return kvq_native(&p->suffix, kq) && !decode_kvq_is_one_launch(p, kq) ? 1 : 0;
 }
@@ -1027,7 +1041,7 @@ int hyd_decode_kv_quant_supported(const hyd_decode_params* p, const hyd_kv_quant
 // shapes ignore single_launch_small, grouped-query ones were refused by the caller where the flag would have applied)
 static int decode_impl(const hyd_decode_params* p, const hyd_kv_quant* kq, void* stream) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
-    if (p->n_levels < 0 || p->n_levels > HYD_MAX_LEVELS) return fail(HYD_ERR_BAD_ARG, "n_levels %d", p->n_levels);
+    if (!levels_in_range(p)) return fail(HYD_ERR_BAD_ARG, "n_levels %d", p->n_levels);
     if (p->phase < HYD_PHASE_ALL || p->phase > HYD_PHASE_MERGE) return fail(HYD_ERR_BAD_ARG, "phase %d", p->phase);
     if (p->shared_max_workgroups < 0) return fail(HYD_ERR_BAD_ARG, "shared_max_workgroups %d", p->shared_max_workgroups);
     if (p->f32_partials != 0 && p->f32_partials != 1) return fail(HYD_ERR_BAD_ARG, "f32_partials %d", p->f32_partials);
@@ -1039,96 +1053,72 @@ static int decode_impl(const hyd_decode_params* p, const hyd_kv_quant* kq, void*
     const size_t rows = (size_t)sp.B * sp.nq * sp.Hq;
     const bool do_shared = p->phase == HYD_PHASE_ALL || p->phase == HYD_PHASE_SHARED;
     const bool do_unique = p->phase == HYD_PHASE_ALL || p->phase == HYD_PHASE_UNIQUE;
-    const bool two_stream = p->phase == HYD_PHASE_UNIQUE_PARTIAL || p->phase == HYD_PHASE_MERGE;
+    DecodePlan d;
+    plan_decode(p, &d);
     // The two-stream form needs both a shared and a unique part; without one of them the in-order phases already are
     // the whole operator (the caller asks hyd_decode_two_stream_ok first).
-    if (two_stream && (p->n_levels == 0 || sp.kv_len == 0))
+    if (d.form == kTwoStream && !d.two_stream_ok)
         return fail(HYD_ERR_UNSUPPORTED, "two-stream phases need at least one shared level and unique keys");
+    if (d.form == kPrefixOnly && !do_shared) return HYD_OK;  // nothing left for the unique phase
 
-    if (decode_is_prefix_only(p)) {
-        if (!do_shared) return HYD_OK;  // nothing left for the unique phase
-        hyd_prefix_params pp;
-        level_to_prefix(p, 0, &pp);
-        PrefixPlan pl;
-        if ((rc = plan_prefix(&pp, &pl))) return rc;
-        if ((rc = check_prefix_ptrs(&pp))) return rc;
-        if (pp.kv_len == 0) return fail(HYD_ERR_BAD_ARG, "level 0 has kv_len == 0");
+    // ---- validate everything before the first launch: the levels in order, each one's plan before its pointers -----------
+    for (int i = 0; i < d.n_planned; ++i) {
+        if ((rc = check_prefix_ptrs(&d.level[i].pp))) return rc;
+        if (d.level[i].pp.kv_len == 0) return fail(HYD_ERR_BAD_ARG, "level %d has kv_len == 0", i);
+    }
+    if (d.rc) return d.rc;  // level n_planned did not plan: nothing above failed, so g_err still holds plan_prefix's message
+    if (d.form == kPrefixOnly) {
+        hyd_prefix_params pp = d.level[0].pp;
         pp.out = sp.out;
         pp.lse = nullptr;
         pp.workspace = p->workspace;
         pp.workspace_bytes = p->workspace_bytes;
-        return run_prefix(&pp, pl, true, s, p->shared_max_workgroups);
+        return run_prefix(&pp, d.level[0].pl, true, s, p->shared_max_workgroups);
     }
-
-    // ---- plan and validate everything before the first launch ----------------------------------------------
-    hyd_prefix_params pps[HYD_MAX_LEVELS];
-    PrefixPlan pls[HYD_MAX_LEVELS];
-    bool small[HYD_MAX_LEVELS];
-    size_t bytes[HYD_MAX_LEVELS];
-    size_t need = 0;
-    int n_parts = 0;
-    for (int i = 0; i < p->n_levels; ++i) {
-        level_to_prefix(p, i, &pps[i]);
-        if ((rc = plan_prefix(&pps[i], &pls[i], level_split_cap(p->n_levels)))) return rc;
-        if ((rc = check_prefix_ptrs(&pps[i]))) return rc;
-        if (pps[i].kv_len == 0) return fail(HYD_ERR_BAD_ARG, "level %d has kv_len == 0", i);
-        small[i] = level_is_small(pps[i], pls[i]);
-        bytes[i] = level_ws_bytes(pps[i], pls[i], p->f32_partials != 0);
-        need += bytes[i];
-        n_parts += (pls[i].nsplit == 1 || small[i]) ? 1 : pls[i].nsplit;
-    }
-    if (n_parts + (two_stream ? 1 : 0) > kMaxCombine) return fail(HYD_ERR_UNSUPPORTED, "%d partials (more than %d)", n_parts, kMaxCombine);
-    if (!kq && decode_runs_as_one_launch(p, pps, pls, small)) {
+    const bool two_stream = d.form == kTwoStream;
+    if (d.n_parts + (two_stream ? 1 : 0) > kMaxCombine) return fail(HYD_ERR_UNSUPPORTED, "%d partials (more than %d)", d.n_parts, kMaxCombine);
+    if (d.form == kOneLaunch && !kq) {
         // launch latency, not work: the grouped-query kernel walks the group's shared keys, then the sequence's own
+        const hyd_prefix_params& pp = d.level[0].pp;
         SuffixArgs a;
         fill_suffix_args(&sp, &a);
-        a.pk = pps[0].k; a.pv = pps[0].v;
-        a.pk_gs = pps[0].k_group_stride; a.pk_hs = pps[0].k_head_stride;
-        a.pv_gs = pps[0].v_group_stride; a.pv_hs = pps[0].v_head_stride;
-        a.p_len = pps[0].kv_len;
-        a.p_per = sp.B / pps[0].sb;
+        a.pk = pp.k; a.pv = pp.v;
+        a.pk_gs = pp.k_group_stride; a.pk_hs = pp.k_head_stride;
+        a.pv_gs = pp.v_group_stride; a.pv_hs = pp.v_head_stride;
+        a.p_len = pp.kv_len;
+        a.p_per = sp.B / pp.sb;
         a.shared_kv = 1;  // p_per sequences read the same prefix keys: default cache policy, not the read-once hint
-        rc = launch_suffix_gqa(a, sp.dtype, sp.D, s);
-        return rc ? fail(HYD_ERR_LAUNCH, "single-launch decode kernel failed: hip error %d", rc) : HYD_OK;
+        return launched(launch_suffix_gqa(a, sp.dtype, sp.D, s), "single-launch decode kernel");
     }
-    const size_t levels_bytes = need;
-    if (two_stream) need += unique_partial_bytes(sp);
+    const size_t need = d.levels_bytes + (two_stream ? d.unique.bytes : 0);
     if (need > 0 && (!p->workspace || p->workspace_bytes < need))
         return fail(HYD_ERR_WORKSPACE, "decode needs %zu workspace bytes, got %zu", need, p->workspace_bytes);
 
     hyd_partial parts[HYD_MAX_LEVELS];
     char* ws = static_cast<char*>(p->workspace);
     for (int i = 0; i < p->n_levels; ++i) {
-        hyd_prefix_params& pp = pps[i];
-        const PrefixPlan& pl = pls[i];
-        const bool part_f32 = p->f32_partials != 0 && !small[i];
-        if (pl.nsplit == 1 || small[i]) {
-            pp.out = ws;
-            pp.lse = reinterpret_cast<float*>(ws + align_up(rows * sp.D * (part_f32 ? 4 : 2), 256));
-            parts[i].out = pp.out;
-            parts[i].lse = pp.lse;
-            parts[i].count = 1;
-            parts[i].is_f32 = part_f32 ? 1 : 0;
-        } else {
-            pp.workspace = ws;
-            pp.workspace_bytes = bytes[i];
-            parts[i].out = ws;
-            parts[i].lse = reinterpret_cast<const float*>(ws + (size_t)pl.nsplit * align_up(rows * sp.D * 4, 256));
-            parts[i].count = pl.nsplit;
-            parts[i].is_f32 = 1;
-        }
+        const LevelPlan& lv = d.level[i];
+        float* lse = reinterpret_cast<float*>(ws + lv.layout.lse_base);
+        parts[i] = {ws, lse, lv.count, lv.is_f32};
         if (do_shared) {
-            if (small[i]) rc = run_level_small(pp, pl, const_cast<void*>(parts[i].out), const_cast<float*>(parts[i].lse), s);
-            else rc = run_prefix(&pp, pl, /*merge=*/false, s, p->shared_max_workgroups, part_f32);
+            hyd_prefix_params pp = lv.pp;
+            if (lv.count == 1) {
+                pp.out = ws;
+                pp.lse = lse;
+            } else {
+                pp.workspace = ws;
+                pp.workspace_bytes = lv.layout.bytes;
+            }
+            if (lv.small) rc = run_level_small(pp, lv.pl, ws, lse, s);
+            else rc = run_prefix(&pp, lv.pl, /*merge=*/false, s, p->shared_max_workgroups, lv.is_f32 != 0);
             if (rc) return rc;
         }
-        ws += bytes[i];
+        ws += lv.layout.bytes;
     }
     if (two_stream) {
         // the unique pass's partial lives behind the levels' regions
-        char* up = static_cast<char*>(p->workspace) + levels_bytes;
-        void* u_out = up;
-        float* u_lse = reinterpret_cast<float*>(up + align_up(rows * sp.D * 2, 256));
+        char* u_out = static_cast<char*>(p->workspace) + d.levels_bytes;
+        float* u_lse = reinterpret_cast<float*>(u_out + d.unique.lse_base);
         if (p->phase == HYD_PHASE_UNIQUE_PARTIAL) {
             hyd_suffix_params su = sp;
             su.out = u_out;
@@ -1138,16 +1128,12 @@ static int decode_impl(const hyd_decode_params* p, const hyd_kv_quant* kq, void*
         CombineArgs c;  // HYD_PHASE_MERGE: every level's partial(s) + the unique partial -> out
         memset(&c, 0, sizeof(c));
         int n = 0;
-        for (int i = 0; i < p->n_levels; ++i) {
-            const size_t esz = parts[i].is_f32 ? 4 : 2;
-            const size_t ostride = parts[i].count > 1 ? align_up(rows * sp.D * esz, 256) : rows * sp.D * esz;
-            const size_t lstride = parts[i].count > 1 ? align_up(rows * 4, 256) : rows * 4;
-            for (int j = 0; j < parts[i].count; ++j, ++n) {
-                c.outs[n] = static_cast<const char*>(parts[i].out) + (size_t)j * ostride;
-                c.lses[n] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(parts[i].lse) + (size_t)j * lstride);
-                if (parts[i].is_f32) c.f32_mask |= 1ull << n;
-            }
-        }
+        if ((rc = for_each_slice(parts, p->n_levels, rows, sp.D, &n, [&c](int i, const void* out, const float* lse, int is_f32) {
+                c.outs[i] = out;
+                c.lses[i] = lse;
+                if (is_f32) c.f32_mask |= 1ull << i;
+            })))
+            return rc;
         c.outs[n] = u_out;
         c.lses[n] = u_lse;
         c.n = n + 1;
@@ -1157,8 +1143,7 @@ static int decode_impl(const hyd_decode_params* p, const hyd_kv_quant* kq, void*
         c.dtype_out = sp.dtype;
         c.out = sp.out;
         c.lse_layout = HYD_LSE_BQH;
-        rc = launch_combine(c, s);
-        return rc ? fail(HYD_ERR_LAUNCH, "combine kernel launch failed: hip error %d", rc) : HYD_OK;
+        return launched(launch_combine(c, s), "combine kernel launch");
     }
     if (!do_unique) return HYD_OK;
     if (sp.kv_len == 0) {
@@ -1172,7 +1157,10 @@ static int decode_impl(const hyd_decode_params* p, const hyd_kv_quant* kq, void*
 }
 
 int hyd_decode_two_stream_ok(const hyd_decode_params* p) {
-    return p && p->n_levels > 0 && p->n_levels <= HYD_MAX_LEVELS && p->suffix.kv_len > 0 && !decode_is_prefix_only(p) ? 1 : 0;
+    if (!p || !levels_in_range(p)) return 0;
+    DecodePlan d;
+    plan_decode(p, &d);
+    return d.two_stream_ok ? 1 : 0;
 }
 
 }  // extern "C"

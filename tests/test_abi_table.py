@@ -1,0 +1,42 @@
+"""-m "not gpu": the host side of the C ABI answers exactly what tests/golden/abi_table.json recorded -- every plan, workspace size and
+support answer as the same integers, every refusal with the same return code and the same error string, character for character.
+The table was recorded (python tests/abi_table.py --write) from the library before csrc/api.hip was restructured; it is data, and
+is not regenerated from the code it checks."""
+import pytest
+
+from tests import abi_table
+
+
+@pytest.fixture(scope="module")
+def table():
+    return abi_table.load_fixture()
+
+
+def test_table_and_case_list_are_the_same_set(table):
+    ids = [c[0] for c in abi_table.QUERY_CASES + abi_table.REFUSAL_CASES]
+    assert sorted(ids) == sorted(table)
+    assert all(rec["rc"] not in (abi_table.HYD_OK, abi_table.HYD_ERR_LAUNCH) for cid, rec in table.items() if cid.startswith("refusal:"))
+
+
+def test_shapes_only_queries_match_the_record(table):
+    wrong = {}
+    for case in abi_table.QUERY_CASES:
+        got = abi_table.run_case(case)
+        if got != table[case[0]]:
+            wrong[case[0]] = (got, table[case[0]])
+    assert not wrong, f"{len(wrong)} of {len(abi_table.QUERY_CASES)} differ (got, recorded): {dict(list(wrong.items())[:5])}"
+
+
+def test_refusals_match_the_record(table):
+    """Runs only without a device: a refusal that a regression turns into an acceptance would launch a kernel on made-up addresses;
+    without a device the same regression comes back as HYD_ERR_LAUNCH instead of the recorded code."""
+    import torch
+
+    if torch.cuda.is_available():
+        pytest.skip("refusals are replayed on machines without a device only")
+    wrong = {}
+    for case in abi_table.REFUSAL_CASES:
+        got = abi_table.run_case(case)
+        if got != table[case[0]]:
+            wrong[case[0]] = (got, table[case[0]])
+    assert not wrong, f"{len(wrong)} of {len(abi_table.REFUSAL_CASES)} differ (got, recorded): {dict(list(wrong.items())[:5])}"
