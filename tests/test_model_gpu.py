@@ -15,11 +15,11 @@ def rdiff(a, b, eps=1e-8):
     return 2 * (a - b).abs() / (a.abs() + b.abs() + eps)
 
 
-def make_model(dtype, head_dim=64, kv_heads=2, layers=2, seed=0):
+def make_model(dtype, head_dim=64, kv_heads=2, layers=2, seed=0, heads=4):
     from hydragen_amd.llama import HydragenLlamaForCausalLM, LlamaConfig
 
-    cfg = LlamaConfig(hidden_size=4 * head_dim, intermediate_size=512, num_hidden_layers=layers,
-                      num_attention_heads=4, num_key_value_heads=kv_heads, vocab_size=512,
+    cfg = LlamaConfig(hidden_size=heads * head_dim, intermediate_size=512, num_hidden_layers=layers,
+                      num_attention_heads=heads, num_key_value_heads=kv_heads, vocab_size=512,
                       max_position_embeddings=1024, rms_norm_eps=1e-5)
     return HydragenLlamaForCausalLM.from_config(cfg, dtype=dtype, device=DEV, seed=seed, std=0.05)
 
@@ -118,6 +118,20 @@ def test_decode_graph_with_the_two_stream_form_in_every_layer(spec):
 @pytest.mark.parametrize("spec", ["prefix+completions", "three-level", "padded-shared", "prefix+suffix"])
 def test_decode_logits_vs_fp32_transformer(dtype, graph, spec, head_dim=None):
     model = make_model(dtype, head_dim=head_dim or (64 if dtype == torch.float16 else 128))
+    check_decode_logits(model, dtype, graph, spec)
+
+
+@pytest.mark.parametrize("heads,kv_heads", [(6, 2), (3, 3), (7, 1)])
+@pytest.mark.parametrize("graph", [False, True])
+@pytest.mark.parametrize("spec", ["prefix+completions", "three-level"])
+def test_decode_logits_odd_head_counts(heads, kv_heads, graph, spec):
+    """Head counts that are no power of two (tests/head_geometry_cases.py): 3 query heads per kv head, 3 MHA heads, 7 query heads
+    on one kv head; the same check as test_decode_logits_vs_fp32_transformer."""
+    model = make_model(torch.bfloat16, head_dim=128, kv_heads=kv_heads, heads=heads)
+    check_decode_logits(model, torch.bfloat16, graph, spec)
+
+
+def check_decode_logits(model, dtype, graph, spec):
     model.graph(graph)
     g = torch.Generator(device=DEV).manual_seed(3)
     rnd = lambda *s: torch.randint(1, 512, s, device=DEV, generator=g)
