@@ -51,7 +51,7 @@ class SuffixParams(C.Structure):
         ("v_batch_stride", C.c_int64), ("v_tok_stride", C.c_int64), ("v_head_stride", C.c_int64),
         ("dtype", C.c_int32), ("B", C.c_int32), ("nq", C.c_int32), ("Hq", C.c_int32), ("Hkv", C.c_int32),
         ("D", C.c_int32), ("kv_len", C.c_int32), ("n_partials", C.c_int32),
-        ("softmax_scale", C.c_float), ("reserved_", C.c_int32),
+        ("softmax_scale", C.c_float), ("kv_dim", C.c_int32),
         ("partials", Partial * HYD_MAX_LEVELS),
     ]
 
@@ -85,7 +85,7 @@ class RopeParams(C.Structure):
         ("vc_batch_stride", C.c_int64), ("vc_tok_stride", C.c_int64), ("vc_head_stride", C.c_int64),
         ("pos_stride", C.c_int64), ("cs_stride", C.c_int64),
         ("dtype", C.c_int32), ("B", C.c_int32), ("Hq", C.c_int32), ("Hkv", C.c_int32), ("D", C.c_int32),
-        ("cache_len", C.c_int32), ("max_pos", C.c_int32), ("reserved", C.c_int32),
+        ("cache_len", C.c_int32), ("max_pos", C.c_int32), ("head_dim", C.c_int32),
     ]
 
 
@@ -215,6 +215,7 @@ EXPORTS = {
     "hyd_suffix_attn_fwd_kvq": (C.c_int, [C.POINTER(SuffixParams), C.POINTER(KvQuant), C.c_void_p]),
     "hyd_decode_attn_fused_kvq": (C.c_int, [C.POINTER(DecodeParams), C.POINTER(KvQuant), C.c_void_p]),
     "hyd_rope_append_decode_kvq": (C.c_int, [C.POINTER(RopeParams), C.POINTER(KvQuant), C.c_void_p]),
+    "hyd_narrow_kv_supported": (C.c_int, [C.POINTER(SuffixParams)]),
     "hyd_kv_quant_supported": (C.c_int, [C.POINTER(SuffixParams), C.POINTER(KvQuant)]),
     "hyd_decode_kv_quant_supported": (C.c_int, [C.POINTER(DecodeParams), C.POINTER(KvQuant)]),
     "hyd_sample_tokens_filtered": (C.c_int, [C.POINTER(SampleFilterParams), C.c_void_p]),

@@ -134,6 +134,22 @@ def hydragen_attention(
         return hydragen_attention(q, _flash.dequantize_kv(k, k_scale, q.dtype), _flash.dequantize_kv(v, v_scale, q.dtype),
                                   shared_ks, shared_vs, shared_cu_seq_lens, shared_max_seq_lens, use_varlens, seq_lens)
 
+    # narrow unique caches (flash.py): k / v rows of a non-native head dim are read as they are; q and every shared level run at the
+    # kernels' head dim -- zero-padded here, or handed in that wide by a caller who vouches for zero pad columns (then nothing is
+    # copied and the output is that wide too)
+    dk = k.shape[-1]
+    narrow = (not fp8 and fused_ok and n_levels <= HYD_MAX_LEVELS and _flash.narrow_kv_native(q, k, v))
+    assert d == dk or narrow, f"Keys have head dim {dk} but queries have head dim {d}"
+    if narrow:
+        dp = _flash.padded_head_dim(dk)
+        for x in shared_ks:
+            assert x.shape[-1] in (dk, dp), f"shared level of head dim {x.shape[-1]}: {dk}, or {dp} with zero pad columns"
+        if d != dp or any(x.shape[-1] != dp for x in shared_ks + shared_vs):
+            widen = lambda t: t if t.shape[-1] == dp else _flash.pad_head_dim(t, dp)
+            out = hydragen_attention(widen(q), k, v, [widen(x) for x in shared_ks], [widen(x) for x in shared_vs],
+                                     shared_cu_seq_lens, shared_max_seq_lens, use_varlens, seq_lens)
+            return out if d == dp else out[..., :dk].contiguous()
+        d = dp
     if fp8 and not (fused_ok and n_levels <= HYD_MAX_LEVELS and _flash.fp8_native(q, k, v)):
         return dequantized()  # shapes no fp8 suffix kernel takes
     dp = _flash.padded_head_dim(d)

@@ -1,5 +1,6 @@
 // C ABI of libhydragen_hip.so (see include/hydragen_hip.h): argument validation, shapes-only launch
 // planning, workspace carving.  No allocation, no synchronisation, no device reads on the host.
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -304,10 +305,26 @@ int check_stride8(int64_t s, const char* name) {
     return HYD_OK;
 }
 
+// Narrow rows (hyd_suffix_params.kv_dim, hyd_rope_params.head_dim): 0 or D = rows of D elements; else 16 <= n < D, n % 16 == 0.
+int check_narrow_dim(int n, int D, const char* field) {
+    if (n == 0 || n == D) return HYD_OK;
+    if (n < 16 || n > D || n % 16 != 0)
+        return fail(HYD_ERR_BAD_ARG, "%s %d: 0 or %d (rows of D elements), or a multiple of 16 in [16, %d)", field, n, D, D);
+    return HYD_OK;
+}
+// the elements per head of the unique cache rows when they are narrower than D, else 0
+int narrow_kv_dim(const hyd_suffix_params* p) { return p->kv_dim != p->D ? p->kv_dim : 0; }
+// the softmax scale of a call: the caller's, else that of the TRUE head dim (kv_dim when the unique rows are narrow)
+float true_dim_scale(const hyd_suffix_params* p) {
+    if (p->softmax_scale > 0.f || !narrow_kv_dim(p)) return p->softmax_scale;
+    return (float)(1.0 / sqrt((double)p->kv_dim));
+}
+
 int check_suffix(const hyd_suffix_params* p, bool need_kv) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
     int rc = check_common(p->dtype, p->B, p->nq, p->Hq, p->Hkv, p->D);
     if (!rc) rc = check_scale(p->softmax_scale);
+    if (!rc) rc = check_narrow_dim(p->kv_dim, p->D, "kv_dim");
     if (rc) return rc;
     if (p->kv_len < 0) return fail(HYD_ERR_BAD_ARG, "kv_len %d", p->kv_len);
     if ((rc = check_ptr_align(p->q, "q"))) return rc;
@@ -348,7 +365,20 @@ void fill_suffix_args(const hyd_suffix_params* p, SuffixArgs* ap) {
     a.kv_len = p->kv_len;
     a.rows = p->nq * a.g;
     a.units = p->B * p->Hkv;
-    a.scale_log2e = scale_log2e_of(p->softmax_scale, p->D);
+    a.scale_log2e = scale_log2e_of(true_dim_scale(p), p->D);
+    a.kv_dim = p->kv_len > 0 ? narrow_kv_dim(p) : 0;  // (no unique key, nothing narrow to read: the merge-only call of the D-wide kernels)
+}
+
+int fail_narrow_fp8() { return fail(HYD_ERR_UNSUPPORTED, "kv_dim / head_dim with fp8 caches: narrow rows are implemented for 16-bit caches only"); }
+int fail_narrow_shapes(const hyd_suffix_params* p) {
+    return fail(HYD_ERR_UNSUPPORTED, "kv_dim %d: narrow unique caches run on the token-row kernel only (nq == 1, Hq == Hkv, Hkv a multiple of %d at D = %d, "
+                                     "a sequence's cache within 2 GiB)", p->kv_dim, 64 / (p->D / 8), p->D);
+}
+// shapes only: a narrow call (kv_dim set, unique keys present) the narrow token-row kernel takes
+bool narrow_native(const hyd_suffix_params* p) {
+    SuffixArgs a;
+    fill_suffix_args(p, &a);
+    return suffix_narrow_eligible(a, p->D);
 }
 
 // HYD_KVQ_GQA: the caller takes the grouped-query fp8 kernel; without it the entry points keep the shapes of ABI 0.5.0 as first
@@ -377,6 +407,10 @@ int run_suffix(const hyd_suffix_params* p, const hyd_partial* parts, int n_parts
     if ((int64_t)p->kv_len * p->k_tok_stride * esz >= (1ll << 31) || (int64_t)p->kv_len * p->v_tok_stride * esz >= (1ll << 31))
         return fail(HYD_ERR_UNSUPPORTED, "unique K/V of one sequence spans >= 2 GiB (32-bit in-sequence offsets)");
     if (p->Hkv > 4 * 65535 || a.rows > 8 * 65535) return fail(HYD_ERR_UNSUPPORTED, "too many kv heads / query rows for the suffix grid");
+    if (a.kv_dim) {
+        if (kq) return fail_narrow_fp8();
+        if (!suffix_narrow_eligible(a, p->D)) return fail_narrow_shapes(p);
+    }
     if (kq) {
         // the 16-bit launcher's order: grouped-query shapes to the matrix-core kernel, one-row units to the token-row kernel
         const bool gqa = kvq_takes_gqa(kq) && suffix_gqa_fp8_eligible(a, p->D);
@@ -413,7 +447,7 @@ int check_kvq(const hyd_kv_quant** kq, int dtype) {
 
 // shapes-only: does an fp8 suffix kernel take these shapes (nothing is launched, no device memory read)
 bool kvq_native(const hyd_suffix_params* p, const hyd_kv_quant* kq) {
-    if (check_common(p->dtype, p->B, p->nq, p->Hq, p->Hkv, p->D)) return false;
+    if (check_common(p->dtype, p->B, p->nq, p->Hq, p->Hkv, p->D) || narrow_kv_dim(p)) return false;
     SuffixArgs a;
     fill_suffix_args(p, &a);
     return (kvq_takes_gqa(kq) && suffix_gqa_fp8_eligible(a, p->D)) || suffix_fp8_eligible(a, p->D);
@@ -446,7 +480,7 @@ void level_to_prefix(const hyd_decode_params* p, int i, hyd_prefix_params* pp) {
     pp->Hq = s.Hq;
     pp->Hkv = s.Hkv;
     pp->D = s.D;
-    pp->softmax_scale = s.softmax_scale;
+    pp->softmax_scale = true_dim_scale(&s);
     pp->sb = lv.sb;
     pp->kv_len = lv.kv_len;
     pp->causal = 0;
@@ -522,6 +556,7 @@ constexpr int64_t kSingleLaunchMaxKeys = 8192;
 bool decode_runs_as_one_launch(const hyd_decode_params* p, const LevelPlan& lv) {
     const hyd_suffix_params& sp = p->suffix;
     if (p->phase != HYD_PHASE_ALL || !p->single_launch_small || p->n_levels != 1 || !lv.small || sp.kv_len <= 0) return false;
+    if (narrow_kv_dim(&sp)) return false;  // narrow unique caches: the pair of launches runs (the rule Hq == Hkv fp8 calls have)
     if (sp.lse) return false;  // suffix.lse is the LSE of the unique keys alone in every form; one walk over both segments cannot give it
     const hyd_prefix_params& pp = lv.pp;
     if (pp.cu_seqlens_k || pp.sb <= 0 || sp.B % pp.sb != 0) return false;  // (a small level runs unsplit whatever the plan says)
@@ -674,6 +709,12 @@ int hyd_kv_quant_supported(const hyd_suffix_params* p, const hyd_kv_quant* kq) {
     return kind == kKvqNone || (kind == kKvqFp8 && kvq_native(p, kq)) ? 1 : 0;
 }
 
+int hyd_narrow_kv_supported(const hyd_suffix_params* p) {
+    if (!p || check_common(p->dtype, p->B, p->nq, p->Hq, p->Hkv, p->D) || check_narrow_dim(p->kv_dim, p->D, "kv_dim")) return 0;
+    if (!narrow_kv_dim(p) || p->kv_len <= 0) return p->kv_len >= 0 ? 1 : 0;  // nothing narrow is read: the existing call
+    return narrow_native(p) ? 1 : 0;
+}
+
 int hyd_combine_lse(const void* const* outs, const float* const* lses, int32_t n, int64_t rows, int32_t D,
                     int32_t dtype, void* out, float* out_lse, void* stream) {
     if (!outs || !lses || !out) return fail(HYD_ERR_BAD_ARG, "null pointer");
@@ -705,7 +746,10 @@ int hyd_rope_append_decode_kvq(const hyd_rope_params* p, const hyd_kv_quant* kq,
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
     int rc = check_common(p->dtype, p->B, 1, p->Hq, p->Hkv, p->D);
     if (rc) return rc;
+    if ((rc = check_narrow_dim(p->head_dim, p->D, "head_dim"))) return rc;
     if ((rc = check_kvq(&kq, p->dtype))) return rc;
+    const int narrow = p->head_dim != p->D ? p->head_dim : 0;
+    if (narrow && kq) return fail_narrow_fp8();
     if ((rc = check_ptr_align(p->q, "q")) || (rc = check_ptr_align(p->k, "k")) || (rc = check_ptr_align(p->v, "v")) ||
         (rc = check_ptr_align(p->q_out, "q_out")) || (rc = check_ptr_align(p->k_cache, "k_cache")) ||
         (rc = check_ptr_align(p->v_cache, "v_cache")) || (rc = check_ptr_align(p->cos, "cos")) ||
@@ -730,6 +774,13 @@ int hyd_rope_append_decode_kvq(const hyd_rope_params* p, const hyd_kv_quant* kq,
     a.vc_bs = p->vc_batch_stride; a.vc_ts = p->vc_tok_stride; a.vc_hs = p->vc_head_stride;
     a.pos_stride = p->pos_stride; a.cs_stride = p->cs_stride;
     a.B = p->B; a.Hq = p->Hq; a.Hkv = p->Hkv; a.cache_len = p->cache_len; a.max_pos = p->max_pos;
+    if (narrow) {
+        RopeNarrowArgs na;
+        na.a = a;
+        na.D = p->D;
+        na.d = narrow;
+        return launched(launch_rope_append_narrow(na, p->dtype, static_cast<hipStream_t>(stream)), "rope_append (narrow head dim) kernel launch");
+    }
     if (kq) {
         RopeKvqArgs ka;
         ka.a = a;
@@ -1021,6 +1072,7 @@ int hyd_decode_attn_fused_kvq(const hyd_decode_params* p, const hyd_kv_quant* kq
     if (!kq) return decode_impl(p, nullptr, stream);
     // fp8 unique caches: validated up front (every phase, also those that do not read the unique cache) so that the phases of one
     // call agree; kv_len == 0 reads no unique key and takes the existing path
+    if (p->suffix.kv_len > 0 && narrow_kv_dim(&p->suffix)) return fail_narrow_fp8();
     if (p->suffix.kv_len > 0 && !kvq_native(&p->suffix, kq)) return fail_kvq_shapes(p->suffix.D);
     if (decode_kvq_is_one_launch(p, kq))
         return fail(HYD_ERR_UNSUPPORTED, "fp8 unique caches: a grouped-query call this small runs as ONE launch with 16-bit caches "
@@ -1049,6 +1101,10 @@ static int decode_impl(const hyd_decode_params* p, const hyd_kv_quant* kq, void*
     int rc = check_suffix(&sp, true);
     if (rc) return rc;
     if (p->n_levels == 0 && sp.kv_len == 0) return fail(HYD_ERR_BAD_ARG, "no shared levels and no unique keys");
+    if (narrow_kv_dim(&sp) && sp.kv_len > 0) {  // refused before the first launch, in every phase, so that the phases of one call agree
+        if (kq) return fail_narrow_fp8();
+        if (!narrow_native(&sp)) return fail_narrow_shapes(&sp);
+    }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t rows = (size_t)sp.B * sp.nq * sp.Hq;
     const bool do_shared = p->phase == HYD_PHASE_ALL || p->phase == HYD_PHASE_SHARED;

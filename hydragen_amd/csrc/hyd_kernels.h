@@ -73,6 +73,7 @@ struct SuffixArgs {
     int32_t rows_wps_log2;  // token-row kernel (suffix_attn.hip): log2 of the waves of a workgroup that share one sequence (set by its launcher)
     int32_t dbg_blind;  // 0 in product builds; HYD_ABLATION_BUILD: HYD_GQA_BLIND=1 restores the blind first key step of the grouped-query kernel (A/B)
     int32_t shared_kv;  // the keys are read by several workgroups (a small shared level on the grouped-query kernel): no non-temporal hint
+    int32_t kv_dim;     // 0, or the elements per head of NARROW unique cache rows (16 <= kv_dim < D, % 16 == 0; token-row kernel only); sits in what was padding
     // grouped-query kernel only: a shared-prefix segment walked before the unit's own keys (tiny problems: the whole
     // operator in one launch).  Sequence b reads rows [0, p_len) of group b / p_per; token strides equal k_ts / v_ts.
     const void* pk;
@@ -125,6 +126,11 @@ struct RopeKvqArgs {  // rope_append.hip, fp8 caches: k_cache / v_cache hold e4m
     RopeArgs a;
     const float* k_scale;  // [Hkv] or null = 1
     const float* v_scale;
+};
+
+struct RopeNarrowArgs {  // rope_append.hip, narrow head dims: q / k / v and the cache rows hold d elements per head, q_out D (zero pad columns)
+    RopeArgs a;
+    int32_t D, d;
 };
 
 struct NormArgs {  // layer_ops.hip: h = residual + x; normed = RMSNorm(h) * weight
@@ -240,12 +246,14 @@ int launch_token_bitmap(const BitmapArgs& a, hipStream_t s);                    
 int launch_token_logprob(const TokenLogprobArgs& a, int dtype, hipStream_t s);  // token_logprob.hip
 int launch_stop_update(const StopArgs& a, hipStream_t s);                          // stop_update.hip
 int launch_suffix(const SuffixArgs& a, int dtype, int D, hipStream_t s);
+bool suffix_narrow_eligible(const SuffixArgs& a, int D);                              // suffix_attn.hip, shapes only (a.kv_dim set)
 bool suffix_gqa_eligible(const SuffixArgs& a, int D, bool any_shape);
 bool suffix_fp8_eligible(const SuffixArgs& a, int D);                                 // suffix_attn_fp8.hip, shapes only
 int launch_suffix_fp8(const SuffixKvqArgs& a, int dtype, int D, hipStream_t s);       // q dtype; K/V e4m3fn
 bool suffix_gqa_fp8_eligible(const SuffixArgs& a, int D);                             // suffix_attn_gqa_fp8.hip, shapes only
 int launch_suffix_gqa_fp8(const SuffixKvqArgs& a, int dtype, int D, hipStream_t s);   // q dtype; K/V e4m3fn, grouped-query shapes
 int launch_rope_append_fp8(const RopeKvqArgs& a, int dtype, int D, hipStream_t s);
+int launch_rope_append_narrow(const RopeNarrowArgs& a, int dtype, hipStream_t s);      // 16-bit caches, head_dim d < D
 int launch_suffix_gqa(const SuffixArgs& a, int dtype, int D, hipStream_t s);
 int launch_combine(const CombineArgs& a, hipStream_t s);
 size_t allreduce_block_bytes(int world, size_t max_bytes);

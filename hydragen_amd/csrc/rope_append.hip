@@ -78,6 +78,87 @@ __global__ __launch_bounds__(256) void rope_append_kernel(const RopeArgs a) {
     }
 }
 
+// Narrow head dims (hyd_rope_params.head_dim = d < D, d % 16 == 0; 16-bit caches): q / k / v arrive from the GEMM as rows of d
+// elements with head stride d, the rotate-half pairs are (i, i + d / 2) -- 8-element vectors, hence d % 16 == 0 --, K (rotated)
+// and V go into the caches as rows of d elements at the caches' strides, and q_out keeps the attention kernels' pitch of D with
+// exact zeros in its pad columns.  D / 16 threads per row as in the kernel above: the first d / 16 do its work on the narrow
+// row, the others write the D - d pad columns of a q row (two vectors each) and have nothing to do for k / v.
+template <typename T>
+__global__ __launch_bounds__(256) void rope_append_narrow_kernel(const RopeNarrowArgs na) {
+    const RopeArgs& a = na.a;
+    const int D = na.D, d = na.d;
+    const int tpr = D / 16, act = d / 16;
+    const int rows_per_b = a.Hq + 2 * a.Hkv;
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t row = gid / tpr;
+    const int sub = (int)(gid % tpr);
+    if (row >= (int64_t)a.B * rows_per_b) return;
+    const int b = (int)(row / rows_per_b);
+    const int h = (int)(row % rows_per_b);
+    const int64_t pos_raw = a.pos[(int64_t)b * a.pos_stride];
+    const int64_t idx = pos_raw - (a.shared_len ? a.shared_len[b] : 0);
+    const int64_t pos = pos_raw < 0 ? 0 : (pos_raw >= a.max_pos ? (int64_t)a.max_pos - 1 : pos_raw);
+    if (h == 0 && sub == 0) a.seq_lens[b] = (int32_t)(idx + 1);
+    if (sub >= act) {
+        if (h < a.Hq) {  // q_out's pad columns: 16 of them per thread
+            uint16_t* dst = static_cast<uint16_t*>(a.q_out) + ((int64_t)b * a.Hq + h) * D + d + (sub - act) * 16;
+            const u32x4 z = {0u, 0u, 0u, 0u};
+            *reinterpret_cast<u32x4*>(dst) = z;
+            *reinterpret_cast<u32x4*>(dst + 8) = z;
+        }
+        return;
+    }
+    const int d0 = sub * 8, half = d / 2;
+    if (h < a.Hq + a.Hkv) {
+        const bool isq = h < a.Hq;
+        const uint16_t* src = isq ? static_cast<const uint16_t*>(a.q) + (int64_t)b * a.q_bs + (int64_t)h * d
+                                  : static_cast<const uint16_t*>(a.k) + (int64_t)b * a.k_bs + (int64_t)(h - a.Hq) * d;
+        const u32x4 lo = *reinterpret_cast<const u32x4*>(src + d0);
+        const u32x4 hi = *reinterpret_cast<const u32x4*>(src + half + d0);
+        float c[8], s[8];
+        const float* cr = a.cos + pos * a.cs_stride + d0;
+        const float* sr = a.sin + pos * a.cs_stride + d0;
+        const f32x4 c0 = *reinterpret_cast<const f32x4*>(cr), c1 = *reinterpret_cast<const f32x4*>(cr + 4);
+        const f32x4 s0 = *reinterpret_cast<const f32x4*>(sr), s1 = *reinterpret_cast<const f32x4*>(sr + 4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            c[i] = c0[i];
+            c[4 + i] = c1[i];
+            s[i] = s0[i];
+            s[4 + i] = s1[i];
+        }
+        u32x4 olo, ohi;
+        rope8<T>(lo, hi, c, s, olo, ohi);
+        uint16_t* dst;
+        if (isq) {
+            dst = static_cast<uint16_t*>(a.q_out) + ((int64_t)b * a.Hq + h) * D;
+        } else {
+            if (idx < 0 || idx >= a.cache_len) return;  // out of the allocated cache: never write out of bounds
+            dst = static_cast<uint16_t*>(a.k_cache) + (int64_t)b * a.kc_bs + idx * a.kc_ts + (int64_t)(h - a.Hq) * a.kc_hs;
+        }
+        *reinterpret_cast<u32x4*>(dst + d0) = olo;
+        *reinterpret_cast<u32x4*>(dst + half + d0) = ohi;
+    } else {
+        if (idx < 0 || idx >= a.cache_len) return;
+        const int hv = h - a.Hq - a.Hkv;
+        const uint16_t* src = static_cast<const uint16_t*>(a.v) + (int64_t)b * a.v_bs + (int64_t)hv * d;
+        uint16_t* dst = static_cast<uint16_t*>(a.v_cache) + (int64_t)b * a.vc_bs + idx * a.vc_ts + (int64_t)hv * a.vc_hs;
+        *reinterpret_cast<u32x4*>(dst + d0) = *reinterpret_cast<const u32x4*>(src + d0);
+        *reinterpret_cast<u32x4*>(dst + half + d0) = *reinterpret_cast<const u32x4*>(src + half + d0);
+    }
+}
+
+int launch_rope_append_narrow(const RopeNarrowArgs& na, int dtype, hipStream_t s) {
+    const RopeArgs& a = na.a;
+    if (na.D % 16 != 0 || na.d % 16 != 0 || na.d < 16 || na.d >= na.D) return (int)hipErrorInvalidValue;
+    const int64_t threads = (int64_t)a.B * (a.Hq + 2 * a.Hkv) * (na.D / 16);
+    const int grid = (int)((threads + 255) / 256);
+    if (grid == 0) return 0;
+    if (dtype == HYD_F16) hipLaunchKernelGGL((rope_append_narrow_kernel<F16>), dim3(grid), dim3(256), 0, s, na);
+    else hipLaunchKernelGGL((rope_append_narrow_kernel<BF16>), dim3(grid), dim3(256), 0, s, na);
+    return (int)hipGetLastError();
+}
+
 // fp8 caches (hyd_kv_quant): the same kernel, but the rotated k -- the 16-bit value the kernel above writes -- and v are stored as
 // quantize_kv(x, scale) (hydragen_amd/kv_quant.py): a correctly rounded x / scale[h], clamped to +-448 (NaN passes through the
 // comparisons), then v_cvt_pk_fp8_f32 (round-half-even; the clamp keeps it away from the overflow encoding), 8 bytes per store.

@@ -111,9 +111,10 @@ struct RowsCache16 {
     template <typename T>
     static __device__ __forceinline__ void v_f32(const u32x4& v, float (&f)[8]) { widen8<T>(v, f); }
 };
-template <typename T, int D, int UT, int NPRE, int TS = 1>
+// NARROW: cache rows of a.kv_dim < D elements per head (suffix_rows.h)
+template <typename T, int D, int UT, int NPRE, int TS = 1, bool NARROW = false>
 __global__ __launch_bounds__(256, 4) void suffix_attn_rows_kernel(const SuffixArgs a) {
-    suffix_rows_body<T, D, UT, NPRE, TS, RowsCache16>(a, nullptr, nullptr);
+    suffix_rows_body<T, D, UT, NPRE, TS, RowsCache16, NARROW>(a, nullptr, nullptr);
 }
 
 // NPRE: 16-bit partials fetched under the K/V stream (suffix_common.h); 2 is instantiated for the decode shape only
@@ -400,6 +401,14 @@ static bool suffix_packed_eligible(const SuffixArgs& a, int D) {
 template <typename T, int D>
 static int launch_suffix_t(const SuffixArgs& a0, hipStream_t s) {
     SuffixArgs a = a0;
+    if (a.kv_dim) {
+        // narrow unique caches (hyd_suffix_params.kv_dim): the token-row kernel whenever its shapes hold -- the D-wide rule's
+        // exceptions below hand work to the one-unit-per-wave kernel, which has no narrow form
+        if (!suffix_rows_shape_ok(a, D, 2)) return (int)hipErrorInvalidValue;  // (the entry points ask suffix_narrow_eligible first)
+        return launch_suffix_rows<D>(a, s, [](auto NPRE, auto TS) {
+            return &suffix_attn_rows_kernel<T, D, 8, decltype(NPRE)::value, decltype(TS)::value, true>;
+        });
+    }
     a.packed = suffix_packed_eligible(a, D) ? 1 : 0;
     {
         // token-row kernel (shapes only, capture-safe: suffix_rows_shape_ok): measured faster wherever the one-unit-per-wave kernel would run with one wave per unit
@@ -421,6 +430,11 @@ static int launch_suffix_t(const SuffixArgs& a0, hipStream_t s) {
     return launch_suffix_r<T, D, 8>(a, s);
 }
 
+// shapes only: a call with narrow unique caches (a.kv_dim set) that the narrow token-row kernel takes
+bool suffix_narrow_eligible(const SuffixArgs& a, int D) {
+    return a.kv_dim >= 16 && a.kv_dim < D && a.kv_dim % 16 == 0 && suffix_rows_shape_ok(a, D, 2);
+}
+
 int launch_suffix(const SuffixArgs& a, int dtype, int D, hipStream_t s) {
     // grouped-query shapes go to the matrix-core kernel (suffix_attn_gqa.hip).  Development builds only
     // (HYD_ABLATION_BUILD): HYD_SUFFIX_IMPL=valu keeps them here, =gqa sends every addressable shape there.
@@ -432,7 +446,7 @@ int launch_suffix(const SuffixArgs& a, int dtype, int D, hipStream_t s) {
 #else
     constexpr int force = 0;
 #endif
-    if (force != 1 && suffix_gqa_eligible(a, D, force == 2)) return launch_suffix_gqa(a, dtype, D, s);
+    if (!a.kv_dim && force != 1 && suffix_gqa_eligible(a, D, force == 2)) return launch_suffix_gqa(a, dtype, D, s);
     if (dtype == HYD_F16) {
         if (D == 128) return launch_suffix_t<F16, 128>(a, s);
         if (D == 64) return launch_suffix_t<F16, 64>(a, s);

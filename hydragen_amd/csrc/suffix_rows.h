@@ -48,7 +48,16 @@ namespace hyd {
 // fp8 caches: 8 BYTES per lane, token and tensor (one wave instruction covers 512 contiguous bytes at D = 128); UT = 8 tokens per
 // chunk is 4 KB of K + V in flight per wave, half the 16-bit kernel's bytes: UT = 16 would keep them, but hipcc then needs
 // 152-166 VGPRs (spills at 4 waves per SIMD, 3 waves per SIMD without).
-template <typename T, int D, int UT, int NPRE, int TS, typename FMT>
+//
+// NARROW (16-bit caches only): the cache rows hold a.kv_dim < D elements per head (a.kv_dim % 16 == 0; head dims 80 / 96 / 192
+// without a zero-padded copy of the cache) while q, the partials, `out` and the LSE keep their pitch of D with zero pad columns.
+// The lane geometry stays that of D.  A lane whose 8 columns start below kv_dim works as always; a PAD lane (sub * 8 >= kv_dim)
+// requests the first 16 bytes of its own head's row -- an address an active lane of the same instruction fetches anyway: no new
+// cache line, never a predicated load, never a byte past column kv_dim --, multiplies them by q registers that are zero (exactly
+// +0 into the v_dot2 chain, so the 16-lane group sum sees what it sees on a zero-padded cache) and drops what it accumulated
+// behind its last chunk: the merges and the epilogue then carry exact zeros into the pad columns of `out`.  Results are bit-identical to the D-wide form
+// on zero-padded tensors for finite caches.
+template <typename T, int D, int UT, int NPRE, int TS, typename FMT, bool NARROW = false>
 __device__ __forceinline__ void suffix_rows_body(const SuffixArgs& a, const float* k_scale, const float* v_scale) {
     using TR = Traits<T>;
     using elem = typename FMT::elem;
@@ -80,7 +89,12 @@ __device__ __forceinline__ void suffix_rows_body(const SuffixArgs& a, const floa
     else if (a.sl64) lenv = (int)a.sl64[b + zero];
 
     const int64_t ridx = (int64_t)b * a.Hq + h0 + hg;  // nq == 1, g == 1: [B, 1, Hq]
-    const u32x4 qp = *reinterpret_cast<const u32x4*>(static_cast<const uint16_t*>(a.q) + ridx * D + sub * 8);
+    u32x4 qp = *reinterpret_cast<const u32x4*>(static_cast<const uint16_t*>(a.q) + ridx * D + sub * 8);
+    bool pad_lane = false;
+    if constexpr (NARROW) {
+        pad_lane = sub * 8 >= a.kv_dim;
+        if (pad_lane) qp = u32x4{0u, 0u, 0u, 0u};
+    }
     float ks = 1.0f, vs = 1.0f;
     if constexpr (FMT::kScaled) {
         ks = k_scale ? k_scale[h0 + hg] : 1.0f;
@@ -97,7 +111,8 @@ __device__ __forceinline__ void suffix_rows_body(const SuffixArgs& a, const floa
     // partial's LSE is being loaded into, and the first K request waits for that load)
     unsigned khg = (unsigned)hg * (unsigned)(a.k_hs * EB), vhg = (unsigned)hg * (unsigned)(a.v_hs * EB);
     asm volatile("" : "+v"(khg), "+v"(vhg));
-    const unsigned klane = khg + sub * (8 * EB), vlane = vhg + sub * (8 * EB);
+    const int csub = NARROW && pad_lane ? 0 : sub;  // a pad lane asks for the head's first columns (see NARROW above)
+    const unsigned klane = khg + csub * (8 * EB), vlane = vhg + csub * (8 * EB);
     const unsigned krs = (unsigned)(a.k_ts * EB), vrs = (unsigned)(a.v_ts * EB);  // token stride in bytes
 
     vec kreg[UT], vreg[UT];
@@ -166,6 +181,15 @@ __device__ __forceinline__ void suffix_rows_body(const SuffixArgs& a, const floa
         int c = ts_id;
         for (; c + TS < nch; c += TS) chunk(c, std::integral_constant<bool, false>{});
         chunk(c, std::integral_constant<bool, true>{});  // this wave's last chunk: masked (it may be the sequence's last)
+    }
+    if constexpr (NARROW) {
+        // a pad lane drops what it accumulated.  HERE, in front of the token-split merge (0 * a1 + 0 * a2 stays 0), so that the merge
+        // and the epilogue are the D-wide kernel's code with nothing in between: hipcc then contracts them the same way (with the
+        // zeroing behind the merge it fused the merge of l in this instantiation alone, and the LSE differed in its last bit)
+        if (pad_lane) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+        }
     }
     if constexpr (TS > 1) {
         __shared__ float xch[4][10][64];  // [wave of the workgroup][m, l, acc[8]][lane]

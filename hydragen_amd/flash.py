@@ -74,8 +74,11 @@ def _q_contig(q: Tensor) -> Tensor:
 # flash-attn takes any head_dim that is a multiple of 8 up to 256 (flash.py:295-304 hands it whatever the model has).
 # The HIP kernels are instantiated for 64, 128 and 256; other multiples of 8 run zero-PADDED to the next of the three
 # with the TRUE head dim's softmax scale (hyd_*_params.softmax_scale): zero columns add nothing to q.k and produce zero
-# output columns, which are cut off again.  Functional, not fast: q, k and v are copied on every call -- a model with
-# such a head dim should keep its caches padded instead.
+# output columns, which are cut off again.  Functional, not fast: q, k and v are copied on every call.
+# The exception is the tensor whose width matters, the UNIQUE K/V cache of the decode shape: where the token-row suffix kernel
+# takes the call (narrow_kv_native: one query row, Hq == Hkv, whole lane groups, d % 16 == 0) k and v are passed as they are,
+# rows of d elements (hyd_suffix_params.kv_dim), and only q and the shared levels -- megabytes -- are padded; callers that keep
+# q and the levels D-wide with zero pad columns (hydragen_amd/llama.py) copy nothing at all and get D-wide output.
 # forwarded to the C ABI by the marshalling helpers below; 0 = head_dim ** -0.5.  A context variable: two threads (or
 # tasks) serving models with different head dims each see their own value.
 _scale_var: contextvars.ContextVar = contextvars.ContextVar("hydragen_amd_softmax_scale", default=0.0)
@@ -266,6 +269,7 @@ def fill_suffix_params(p: SuffixParams, q: Tensor, k: Tensor, v: Tensor, seq_len
     p.B, p.nq, p.Hq, p.Hkv, p.D = b, nq, hq, k.shape[2], d
     p.kv_len = k.shape[1]
     p.softmax_scale = _scale_var.get()
+    p.kv_dim = k.shape[3] if k.shape[3] != d else 0  # narrow unique rows (the caller asked narrow_kv_native); scale 0 is then kv_dim ** -0.5
     order = _order_var.get()
     if order is not None:
         if order.numel() != b or order.device != q.device:
@@ -345,6 +349,35 @@ def _fp8_native_shapes(qshape, qdtype, kshape, kstride, vstride) -> bool:
     return _lib.load().hyd_kv_quant_supported(C.byref(p), C.byref(kq)) == 1
 
 
+# ---- narrow unique caches (head dims 80 / 96 / 192 ...) -------------------------------------------------------------------
+def narrow_kv_native(q: Tensor, k: Tensor, v: Tensor) -> bool:
+    """Shapes only: whether the suffix pass reads 16-bit k / v of a non-native head dim d as they are (hyd_narrow_kv_supported);
+    q is d wide, or already padded_head_dim(d) wide with zero pad columns."""
+    d = k.shape[-1]
+    if d in (64, 128, 256) or d % 16 or not 16 <= d < 256 or k.dtype != q.dtype or k.shape[1] == 0:
+        return False
+    if q.shape[-1] not in (d, padded_head_dim(d)) or k.data_ptr() % 16 or v.data_ptr() % 16:
+        return False
+    return _narrow_kv_shapes(tuple(q.shape[:3]), q.dtype, tuple(k.shape), k.stride(), v.stride())
+
+
+@functools.lru_cache(maxsize=256)
+def _narrow_kv_shapes(qshape, qdtype, kshape, kstride, vstride) -> bool:
+    # (cached like _fp8_native_shapes: a decode step asks once per layer with the same shapes)
+    if qdtype not in (torch.float16, torch.bfloat16):
+        return False
+    if kstride[-1] != 1 or vstride[-1] != 1 or any(st % 8 for st in kstride[:-1] + vstride[:-1]):
+        return False
+    p = SuffixParams()
+    b, nq, hq = qshape
+    p.k_batch_stride, p.k_tok_stride, p.k_head_stride = kstride[:3]
+    p.v_batch_stride, p.v_tok_stride, p.v_head_stride = vstride[:3]
+    p.dtype = HYD_F16 if qdtype == torch.float16 else HYD_BF16
+    p.B, p.nq, p.Hq, p.Hkv, p.D, p.kv_len = b, nq, hq, kshape[2], padded_head_dim(kshape[3]), kshape[1]
+    p.kv_dim = kshape[3]
+    return _lib.load().hyd_narrow_kv_supported(C.byref(p)) == 1
+
+
 def flash_attention_seqlen(raw_q: Tensor, raw_k: Tensor, raw_v: Tensor, seq_len=None, *, k_scale: Tensor | None = None,
                            v_scale: Tensor | None = None):
     """
@@ -360,10 +393,26 @@ def flash_attention_seqlen(raw_q: Tensor, raw_k: Tensor, raw_v: Tensor, seq_len=
     _require_gpu(raw_q, raw_k, raw_v, seq_len)
     assert raw_q.ndim == 4 and raw_k.ndim == 4 and raw_v.ndim == 4
     assert raw_k.shape == raw_v.shape
-    assert raw_q.shape[-1] == raw_k.shape[-1], (
+    fp8 = check_kv_pair(raw_k, raw_v, k_scale, v_scale)
+    narrow = not fp8 and narrow_kv_native(raw_q, raw_k, raw_v)
+    # (narrow unique caches: q may arrive padded to the kernels' head dim already, with zero pad columns)
+    assert raw_q.shape[-1] == raw_k.shape[-1] or narrow, (
         f"Keys have head dim {raw_k.shape[-1]} but queries have head dim {raw_q.shape[-1]}"
     )
-    if check_kv_pair(raw_k, raw_v, k_scale, v_scale):
+    if narrow:
+        d, dq = raw_k.shape[-1], raw_q.shape[-1]
+        dp = padded_head_dim(d)
+        q = _q_contig(raw_q if dq == dp else pad_head_dim(raw_q, dp))
+        out = torch.empty_like(q)
+        lse = torch.empty(q.shape[:3], dtype=torch.float32, device=q.device)
+        p = SuffixParams()
+        keep = fill_suffix_params(p, q, _lastdim_contig(raw_k), _lastdim_contig(raw_v), seq_len, out)  # (views pass as they are)
+        p.lse = lse.data_ptr()
+        p.n_partials = 0
+        _lib.check(_lib.load().hyd_suffix_attn_fwd(C.byref(p), _stream()))
+        del keep
+        return (out if dq == dp else out[..., :d].contiguous()), lse
+    if fp8:
         if not fp8_native(raw_q, raw_k, raw_v):  # functional fallback: 16-bit temporaries, the existing path
             return flash_attention_seqlen(raw_q, dequantize_kv(raw_k, k_scale, raw_q.dtype),
                                           dequantize_kv(raw_v, v_scale, raw_q.dtype), seq_len)

@@ -10,7 +10,7 @@ from torch import Tensor
 
 from . import _lib
 from ._lib import RopeParams
-from .flash import _dtype_code, _require_gpu, _stream, check_kv_pair, kv_quant_params
+from .flash import _dtype_code, _require_gpu, _stream, check_kv_pair, kv_quant_params, padded_head_dim
 
 
 def rope_append_decode(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, position_ids: Tensor,
@@ -20,13 +20,23 @@ def rope_append_decode(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor
     position_ids int64 [B,1] absolute, shared_len int64 [B] or None, caches [maxB, maxS, Hkv, D].
     Returns (rotated q [B,1,Hq,D], seq_lens int32 [B]); k (rotated) and v are written into the caches
     at index position - shared_len.  float8_e4m3fn caches receive quantize_kv(k_rot, k_scale) and
-    quantize_kv(v, v_scale) (kv_quant.py), k_rot being the 16-bit rotated k a 16-bit cache would hold."""
+    quantize_kv(v, v_scale) (kv_quant.py), k_rot being the 16-bit rotated k a 16-bit cache would hold.
+    Narrow head dims (d % 16 == 0, not 64 / 128 / 256; 16-bit caches): q / k / v, the cos / sin tables and the caches are d wide,
+    the returned q is padded_head_dim(d) wide with zero pad columns -- what the attention operators take beside narrow unique
+    caches (hyd_rope_params.head_dim)."""
     _require_gpu(q, k, v, cos, sin, position_ids, k_cache, v_cache)
     fp8 = check_kv_pair(k_cache, v_cache, k_scale, v_scale)
     lib = _lib.load()
     B, one, Hq, D = q.shape
+    head_dim = 0
+    if D not in (64, 128, 256):  # narrow rows in, the kernels' head dim out
+        if fp8 or D % 16 or k_cache.shape[-1] != D or v_cache.shape[-1] != D:
+            raise NotImplementedError(f"head_dim {D}: the fused preamble takes 64 / 128 / 256, or a multiple of 16 below 256 with "
+                                      "16-bit caches of that width")
+        head_dim, D = D, padded_head_dim(D)
     assert one == 1 and k.shape[:2] == (B, 1) and v.shape == k.shape
-    assert q.stride(3) == 1 and q.stride(2) == D and k.stride(3) == 1 and k.stride(2) == D and v.stride(2) == D
+    dq = head_dim or D
+    assert q.stride(3) == 1 and q.stride(2) == dq and k.stride(3) == 1 and k.stride(2) == dq and v.stride(2) == dq
     assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.stride(1) == 1
     assert position_ids.dtype == torch.int64 and position_ids.shape[0] == B
     assert B <= k_cache.shape[0]
@@ -49,6 +59,7 @@ def rope_append_decode(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor
     p.pos_stride, p.cs_stride = position_ids.stride(0), cos.stride(0)
     p.dtype, p.B, p.Hq, p.Hkv, p.D, p.cache_len = _dtype_code(q), B, Hq, Hkv, D, k_cache.shape[1]
     p.max_pos = cos.shape[0]
+    p.head_dim = head_dim
     if fp8:
         kq = kv_quant_params(k_scale, v_scale)
         _lib.check(lib.hyd_rope_append_decode_kvq(C.byref(p), C.byref(kq), _stream()))

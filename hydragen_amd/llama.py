@@ -26,7 +26,7 @@ from torch import Tensor, nn
 from . import layer_ops, placement, sampling, scoring, stopping
 from .attention import hydragen_attention
 from . import flash as _flash
-from .flash import flash_attention, flash_attention_seqlen
+from .flash import flash_attention, flash_attention_seqlen, padded_head_dim
 from .kv_quant import FP8_DTYPE, dequantize_kv, quantize_kv
 from .tp import all_reduce_sum, check_collectives
 
@@ -176,8 +176,19 @@ def apply_rotary_pos_emb(q, k, cos, sin, position_ids):
     return (q * cos) + (rotate_half(q) * sin), (k * cos) + (rotate_half(k) * sin)
 
 
+def narrow_kv_head_dim(head_dim: int, n_kv_heads: int, n_q_heads: Optional[int] = None) -> int:
+    """The head dim the attention kernels run a model's q and shared caches at when its UNIQUE cache can keep rows of the true
+    width (narrow unique caches, flash.narrow_kv_native: head_dim % 16 == 0 and not 64 / 128 / 256, as many kv as query heads, whole
+    lane groups of the token-row suffix kernel), else 0: the model then keeps every tensor at head_dim, as always."""
+    if head_dim in (64, 128, 256) or head_dim % 16 or not 16 <= head_dim < 256 or n_q_heads not in (None, n_kv_heads):
+        return 0
+    D = padded_head_dim(head_dim)
+    return D if n_kv_heads % (64 // (D // 8)) == 0 else 0
+
+
 class SharedCache(nn.Module):
-    """llama.py:58-170: one shared level, sequences packed back to back in [maxB*maxP, Hkv, D]."""
+    """llama.py:58-170: one shared level, sequences packed back to back in [maxB*maxP, Hkv, D].  D may be wider than the model's
+    head dim (narrow_kv_head_dim): `fill` writes the leading columns, the others keep the zeros they were allocated with."""
 
     def __init__(self, max_batch_size, max_seq_length, num_heads, head_dim, dtype, device):
         super().__init__()
@@ -203,8 +214,8 @@ class SharedCache(nn.Module):
         lens = [int(x) for x in seq_lens.tolist()]  # host sync, as llama.py:159-167
         ks = torch.cat([key_states[i, : lens[i]] for i in range(bs)], dim=0)
         vs = torch.cat([value_states[i, : lens[i]] for i in range(bs)], dim=0)
-        self.k_cache[: ks.shape[0]] = ks
-        self.v_cache[: vs.shape[0]] = vs
+        self.k_cache[: ks.shape[0], :, : ks.shape[-1]] = ks
+        self.v_cache[: vs.shape[0], :, : vs.shape[-1]] = vs
         self.seq_lens[:bs] = seq_lens.to(torch.int32)
         self.cumsum_lengths[0] = 0
         self.cumsum_lengths[1 : bs + 1] = seq_lens.cumsum(0).to(torch.int32)
@@ -220,9 +231,11 @@ class PerLayerKVCache(nn.Module):
     """llama.py:173-346."""
 
     def __init__(self, max_unique_batch_size, max_unique_seq_length, max_shared_batch_sizes, max_shared_seq_lengths,
-                 n_kv_heads, head_dim, device, dtype, arena: Optional[Tensor] = None, kv_cache_dtype: Optional[torch.dtype] = None):
+                 n_kv_heads, head_dim, device, dtype, arena: Optional[Tensor] = None, kv_cache_dtype: Optional[torch.dtype] = None,
+                 n_q_heads: Optional[int] = None):
         super().__init__()
         shape = (max_unique_batch_size, max_unique_seq_length, n_kv_heads, head_dim)
+        self.head_dim = head_dim
         # kv_cache_dtype = torch.float8_e4m3fn: the unique arena holds e4m3fn bytes (kv_quant.py) with one fp32 scale per kv head
         # for K and for V (k_scale / v_scale, 1.0 until set in place: a captured graph keeps their pointers); the shared caches
         # stay in `dtype`
@@ -230,6 +243,10 @@ class PerLayerKVCache(nn.Module):
         if udtype not in (dtype, FP8_DTYPE):
             raise NotImplementedError(f"unique KV cache dtype {udtype}: the model's {dtype} or {FP8_DTYPE}")
         self.fp8 = udtype == FP8_DTYPE
+        # Narrow unique caches (head dims 80 / 96 / 192 ... on multi-head models): the unique arena keeps rows of head_dim elements --
+        # the suffix pass reads exactly those bytes --, the shared caches and q run at the kernels' head dim with zero pad columns
+        self.kernel_head_dim = (0 if self.fp8 else narrow_kv_head_dim(head_dim, n_kv_heads, n_q_heads)) or head_dim
+        self.narrow = self.kernel_head_dim != head_dim
         if self.fp8:
             self.register_buffer("k_scale", torch.ones((n_kv_heads,), dtype=torch.float32, device=device), persistent=False)
             self.register_buffer("v_scale", torch.ones((n_kv_heads,), dtype=torch.float32, device=device), persistent=False)
@@ -246,7 +263,7 @@ class PerLayerKVCache(nn.Module):
         self.register_buffer("per_completion_k_cache", arena[0])
         self.register_buffer("per_completion_v_cache", arena[1])
         self.shared_caches = nn.ModuleList([
-            SharedCache(b, s, n_kv_heads, head_dim, dtype, device)
+            SharedCache(b, s, n_kv_heads, self.kernel_head_dim, dtype, device)
             for b, s in zip(max_shared_batch_sizes, max_shared_seq_lengths)
         ])
         self.num_used_shared_caches = 0
@@ -291,8 +308,9 @@ class PerLayerKVCache(nn.Module):
         assert total_num_sequences % sb == 0
         rep = total_num_sequences // sb
         cu = sc.cumsum_lengths.tolist()
-        kc, kv = self._store(self.per_completion_k_cache, sc.k_cache, self.k_scale)
-        vc, vv = self._store(self.per_completion_v_cache, sc.v_cache, self.v_scale)
+        d = self.head_dim  # (the shared caches may be wider: zero pad columns)
+        kc, kv = self._store(self.per_completion_k_cache, sc.k_cache[..., :d], self.k_scale)
+        vc, vv = self._store(self.per_completion_v_cache, sc.v_cache[..., :d], self.v_scale)
         for i in range(sb):
             n = cu[i + 1] - cu[i]
             kc[i * rep : (i + 1) * rep, :n] = kv[cu[i] : cu[i + 1]].unsqueeze(0)
@@ -405,6 +423,11 @@ class HydragenLlamaAttention(nn.Module):
             elif shared_len is None:
                 shared_len = self.kv_cache.get_shared_len(bsz)
             sc = self.kv_cache.scales()
+            if self.head_dim not in (64, 128, 256) and not self.kv_cache.narrow:
+                raise NotImplementedError(f"head_dim {self.head_dim}: the fused decode preamble takes 64, 128 and 256, or narrow unique "
+                                          "caches (narrow_kv_head_dim); set use_fused_decode = False")
+            # narrow unique caches: the preamble takes head_dim-wide q / k / v and caches and returns q at the kernels' head dim with
+            # zero pad columns; the operators then copy nothing (shared caches that wide, the unique cache as it is) and so is their output
             q, seq_lens = rope_append_decode(q, k, v, cos, sin, position_ids, shared_len,
                                              self.kv_cache.per_completion_k_cache, self.kv_cache.per_completion_v_cache, **sc)
             key_states = self.kv_cache.per_completion_k_cache[:bsz]
@@ -418,6 +441,8 @@ class HydragenLlamaAttention(nn.Module):
             else:
                 attn_output = hydragen_attention_on_caches(q, key_states, value_states,
                                                            self.kv_cache.get_used_shared_caches(), seq_len=seq_lens, **sc)
+            if self.kv_cache.narrow:  # one copy of B x Hq x head_dim elements: o_proj reads the true columns
+                attn_output = attn_output[..., : self.head_dim]
             out = self.o_proj(attn_output.reshape(bsz, q_len, -1))
             return all_reduce_sum(out) if self.tp_reduce else out
 
@@ -735,7 +760,7 @@ class HydragenLlamaForCausalLM(nn.Module):
                 max_unique_batch_size=max_unique_batch_size, max_unique_seq_length=max_unique_seq_length,
                 max_shared_batch_sizes=max_shared_batch_sizes, max_shared_seq_lengths=max_shared_seq_lengths,
                 n_kv_heads=self.config.num_key_value_heads, head_dim=head_dim, device=device, dtype=dtype, arena=arena,
-                kv_cache_dtype=udtype)
+                kv_cache_dtype=udtype, n_q_heads=self.config.num_attention_heads)
         # the decode loop's schedule hint (flash.seq_order): one buffer for the model's lifetime, so that a captured decode graph
         # keeps pointing at the current generation's order
         self.seq_order_buf = torch.arange(max_unique_batch_size, dtype=torch.int32, device=device)

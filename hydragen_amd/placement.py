@@ -71,10 +71,16 @@ def probe_suffix_pass_us(arena: Tensor, qheads: int, iters: int = 3, q_dtype: to
     (profiles/r05_kv_placement_probe.md).  Half length = the mean decode step of a generation that fills the cache.  The
     arena's contents do not matter to the rate (measured: random, zeros, stale: +- 1 us of 170) and are not touched.  q_dtype:
     the queries' dtype (None = the arena's); an fp8 arena is timed with the fp8 suffix kernel that will serve it."""
-    from .flash import flash_attention_seqlen
+    from .flash import flash_attention_seqlen, narrow_kv_native, padded_head_dim
 
     _, B, S, Hkv, D = arena.shape
     q = torch.zeros((B, 1, qheads, D), dtype=q_dtype or arena.dtype, device=arena.device)
+    if D not in (64, 128, 256) and D % 8 == 0 and D <= 256:
+        # a narrow arena (rows of the model's true head dim) is timed with the narrow token-row kernel that will serve it, on
+        # queries at the kernels' head dim as the model hands them over: no pad copy inside the timed call
+        qw = torch.zeros((B, 1, qheads, padded_head_dim(D)), dtype=q.dtype, device=arena.device)
+        if narrow_kv_native(qw, arena[0], arena[1]):
+            q = qw
     total = 0.0
     for rows in sorted({max(1, S // 2), S}):
         lens = torch.full((B,), rows, dtype=torch.int32, device=arena.device)

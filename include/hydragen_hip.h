@@ -29,7 +29,9 @@
  *     message for the calling thread's last failure;
  *   - 16-bit dtypes: HYD_F16 (IEEE half) and HYD_BF16; accumulation, softmax and LSE are fp32.
  *   - q/out are [B, nq, Hq, D] contiguous; K/V tensors are token-major with explicit element
- *     strides and a contiguous head_dim; supported head_dim: 64, 128, 256.
+ *     strides and a contiguous head_dim; supported head_dim: 64, 128, 256.  Other head dims run zero-padded to the next of
+ *     the three with the true dim's softmax scale; the UNIQUE K/V cache alone may keep rows of the true width d (d % 16 == 0;
+ *     80 / 96 / 192 ...) without a padded copy: hyd_suffix_params.kv_dim, hyd_rope_params.head_dim.
  */
 #ifndef HYDRAGEN_HIP_H
 #define HYDRAGEN_HIP_H
@@ -136,12 +138,26 @@ typedef struct hyd_suffix_params {
     int32_t B, nq, Hq, Hkv, D;
     int32_t kv_len;             /* allocated keys per sequence (Mk); lengths are clamped to it */
     int32_t n_partials;         /* entries used in partials[]                                  */
-    float softmax_scale;        /* 0 = D^-0.5; > 0: that scale (hyd_decode_attn_fused applies it to    */
-    int32_t reserved_;          /*   every level as well)                                              */
+    float softmax_scale;        /* 0 = D^-0.5 (kv_dim^-0.5 with narrow rows); > 0: that scale           */
+                                /*   (hyd_decode_attn_fused applies either to every level as well)      */
+    int32_t kv_dim;             /* (was reserved_, 0) 0 or D: k / v rows hold D elements per head.      */
+                                /*   16 <= kv_dim < D, kv_dim % 16 == 0: NARROW unique caches -- rows   */
+                                /*   of kv_dim elements at the strides given, read as they are (no      */
+                                /*   padded copy); q, partials, levels, out and the workspace keep D,   */
+                                /*   with ZERO pad columns in q, the levels and the partials (the       */
+                                /*   caller vouches); out's pad columns are written as exact zeros.     */
+                                /*   16-bit caches and the shapes of hyd_narrow_kv_supported only.      */
     hyd_partial partials[HYD_MAX_LEVELS];
 } hyd_suffix_params;
 
 HYD_API int hyd_suffix_attn_fwd(const hyd_suffix_params* p, void* stream);
+/* Shapes only (capture-safe, no device read): 1 exactly when the suffix pass and the whole decode operator take the call with
+ * its kv_dim -- always for kv_dim 0 / D; for narrow rows: one query row (nq == 1), Hq == Hkv, Hkv a multiple of the 64 / (D / 8)
+ * heads one wave instruction covers, a sequence's cache within 2 GiB (the token-row kernel; the other suffix kernels have no
+ * narrow form) --, else 0: such calls return HYD_ERR_UNSUPPORTED, and so does kv_dim with fp8 caches (the _kvq entry points).
+ * For finite caches out and lse are bit-identical to the D-wide call on zero-padded k / v with the same softmax scale.  A call
+ * with narrow rows ignores single_launch_small: the prefix + suffix pair runs. */
+HYD_API int hyd_narrow_kv_supported(const hyd_suffix_params* p);
 
 /* ------------------------------------------------------------------------------------------
  * combine_lse for N partials (attention.py:21-43): out = sum_i out_i*exp(lse_i-m) / sum_i exp(lse_i-m).
@@ -245,7 +261,12 @@ typedef struct hyd_rope_params {
     int64_t pos_stride, cs_stride;
     int32_t dtype, B, Hq, Hkv, D, cache_len;
     int32_t max_pos;             /* rows of the cos/sin tables; positions are clamped to it (the  */
-    int32_t reserved;            /*   host checks the range before launching: a kernel cannot raise) */
+                                 /*   host checks the range before launching: a kernel cannot raise) */
+    int32_t head_dim;            /* (was reserved, 0) 0 or D: as above.  16 <= head_dim < D, % 16 == 0: q / k / v are rows of
+                                  * head_dim elements (head stride head_dim), cos / sin [max_pos, head_dim] (the first head_dim / 2
+                                  * columns are read, pairs (i, i + head_dim / 2)), K / V go into the caches as rows of head_dim
+                                  * elements at the cache strides, and q_out stays [B, 1, Hq, D] with exact zeros in its pad
+                                  * columns.  16-bit caches only. */
 } hyd_rope_params;
 
 HYD_API int hyd_rope_append_decode(const hyd_rope_params* p, void* stream);
