@@ -181,6 +181,17 @@ class KvQuant(C.Structure):
     _fields_ = [("kv_dtype", C.c_int32), ("flags", C.c_int32), ("k_scale", C.c_void_p), ("v_scale", C.c_void_p)]
 
 
+class KvPromoteParams(C.Structure):
+    _fields_ = [
+        ("k_src", C.c_void_p), ("v_src", C.c_void_p), ("k_dst", C.c_void_p), ("v_dst", C.c_void_p),
+        ("rows", C.c_void_p), ("lens", C.c_void_p), ("cu", C.c_void_p), ("k_scale", C.c_void_p), ("v_scale", C.c_void_p),
+        ("k_batch_stride", C.c_int64), ("k_tok_stride", C.c_int64), ("k_head_stride", C.c_int64),
+        ("v_batch_stride", C.c_int64), ("v_tok_stride", C.c_int64), ("v_head_stride", C.c_int64),
+        ("src_dtype", C.c_int32), ("dst_dtype", C.c_int32), ("n", C.c_int32), ("B", C.c_int32), ("src_rows", C.c_int32),
+        ("Hkv", C.c_int32), ("d_src", C.c_int32), ("d_dst", C.c_int32), ("capacity", C.c_int32), ("max_len", C.c_int32),
+    ]
+
+
 class AllReduceParams(C.Structure):
     _fields_ = [
         ("blocks", C.POINTER(C.c_void_p)), ("in_", C.c_void_p), ("out", C.c_void_p), ("count", C.c_int64),
@@ -223,6 +234,7 @@ EXPORTS = {
     "hyd_token_bitmap_build": (C.c_int, [C.POINTER(TokenBitmapParams), C.c_void_p]),
     "hyd_token_logprobs": (C.c_int, [C.POINTER(TokenLogprobParams), C.c_void_p]),
     "hyd_stop_update": (C.c_int, [C.POINTER(StopParams), C.c_void_p]),
+    "hyd_kv_promote": (C.c_int, [C.POINTER(KvPromoteParams), C.c_void_p]),
     "hyd_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }

@@ -233,7 +233,25 @@ struct StopArgs {  // stop_update.hip: EOS ids / stop sequences judged per row, 
     int32_t rows, t, n_eos, n_stop, include_stop, retire;
 };
 
+struct KvPromoteArgs {  // kv_promote.hip: chosen rows of the unique K/V caches -> a packed shared level (hyd_kv_promote)
+    const void* k_src;
+    const void* v_src;
+    void* k_dst;
+    void* v_dst;
+    const int32_t* rows;
+    const int32_t* lens;
+    const int32_t* cu;
+    const float* k_scale;  // fp8 sources: [Hkv] or null = 1
+    const float* v_scale;
+    int64_t k_bs, k_ts, k_hs, v_bs, v_ts, v_hs;  // source strides (elements)
+    int32_t n, B, max_len, capacity;
+    int32_t d_src;
+    int32_t vec_per_head, vec_per_tok;  // 16-byte vectors of a destination head row (d_dst / 8) and token row (Hkv * d_dst / 8)
+    FastDiv div_vec_per_head, div_vec_per_tok;
+};
+
 // launchers (defined next to the kernels); return hipError_t as int
+int launch_kv_promote(const KvPromoteArgs& a, int src_dtype, int dst_dtype, hipStream_t s);  // kv_promote.hip
 int launch_prefix_w64(const PrefixArgs& a, int dtype, int D, bool causal, int grid, hipStream_t s);
 int launch_prefix_w64_f16(const PrefixArgs& a, int D, bool causal, int grid, hipStream_t s);  // prefix_attn_w64_f16.hip
 int launch_rope_append(const RopeArgs& a, int dtype, int D, hipStream_t s);

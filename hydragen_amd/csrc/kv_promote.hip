@@ -1,0 +1,117 @@
+// Promote unique K/V rows to a packed shared level (hyd_kv_promote, include/hydragen_hip.h states the rules): the first lens[i]
+// tokens of unique sequence rows[i] become packed tokens [cu[i], cu[i] + lens[i]) of the destination, K and V in one launch.
+// A copy, HBM bound: every lane moves 16 destination bytes per step -- a 16-byte load and store for 16-bit sources (bytes as they
+// are, whatever they encode), an 8-byte load widened to eight 16-bit values for e4m3fn sources (kv_quant.dequantize_kv: float(q8)
+// * scale[h] as an fp32 product, rounded once to the destination dtype, ties to even) -- and the pad columns of a wider
+// destination row are stored as zeros.  Launch geometry comes from shapes and the host's length bound only; rows / lens / cu are
+// read on the device and checked there: a sequence whose entries would index outside the source or the destination is skipped
+// as a whole.  No LDS, no assembly, plain vector stores.
+#include "hyd_kernels.h"
+
+namespace hyd {
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kUnroll = 4;  // destination vectors per lane: 16 KiB written per workgroup
+
+enum { kCopy16 = 0, kFp8ToF16 = 1, kFp8ToBf16 = 2 };
+
+__device__ __forceinline__ unsigned fdiv(unsigned n, const FastDiv& f) {
+    const unsigned t = __umulhi(n, f.mul);
+    return (t + ((n - t) >> (f.sh & 0xffu))) >> (f.sh >> 8);
+}
+
+// One value of the destination dtype from the fp32 product x of e4m3fn code `byte`: round to nearest, ties to even -- bf16 by the
+// integer rule, f16 by the hardware conversion.  The NaN codes (0x7f, 0xff) get the encodings torch's casts give them, which
+// dequantize_kv is defined by: bf16 the one quiet NaN 0x7fc0; f16 the sign of the code and the payload its fp32 widening
+// (0x7ff00000) truncates to, 0x7f80 / 0xff80.
+template <int MODE>
+__device__ __forceinline__ uint32_t cvt1(float x, uint32_t byte) {
+    const bool nan_code = (byte & 0x7fu) == 0x7fu;
+    if (MODE == kFp8ToBf16) {
+        const uint32_t u = __builtin_bit_cast(uint32_t, x);
+        return (nan_code || x != x) ? 0x7fc0u : (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+    }
+    const uint32_t h = __builtin_bit_cast(uint16_t, (_Float16)x);
+    return nan_code ? (((byte & 0x80u) << 8) | 0x7f80u) : h;
+}
+
+// 8 e4m3fn bytes -> 8 values of the destination dtype (element j of the row in half j % 2 of dword j / 2)
+template <int MODE>
+__device__ __forceinline__ u32x4 widen8(const u32x2& v, float s) {
+    u32x4 r;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const uint32_t w = v[i];
+        const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+        const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+        r[2 * i] = cvt1<MODE>(lo[0] * s, w & 0xffu) | (cvt1<MODE>(lo[1] * s, (w >> 8) & 0xffu) << 16);
+        r[2 * i + 1] = cvt1<MODE>(hi[0] * s, (w >> 16) & 0xffu) | (cvt1<MODE>(hi[1] * s, w >> 24) << 16);
+    }
+    return r;
+}
+
+}  // namespace
+
+// grid (chunks of kThreads * kUnroll destination vectors, sequences, K | V)
+template <int MODE>
+__global__ __launch_bounds__(kThreads) void kv_promote_kernel(const KvPromoteArgs a) {
+    const int i = (int)blockIdx.y;
+    const int row = a.rows[i], len = a.lens[i], at = a.cu[i];
+    // bad device data: the sequence is skipped, nothing is indexed with it (uniform per workgroup)
+    if (row < 0 || row >= a.B || len <= 0 || len > a.max_len || at < 0 || (int64_t)at + len > (int64_t)a.capacity) return;
+    const unsigned total = (unsigned)len * (unsigned)a.vec_per_tok;  // (max_len * vec_per_tok < 2^31: the host checked)
+    const unsigned first = (unsigned)blockIdx.x * (kThreads * kUnroll) + threadIdx.x;
+    if ((unsigned)blockIdx.x * (kThreads * kUnroll) >= total) return;
+
+    const bool is_v = blockIdx.z != 0;
+    const char* src = static_cast<const char*>(is_v ? a.v_src : a.k_src);
+    char* dst = static_cast<char*>(is_v ? a.v_dst : a.k_dst);
+    const float* scale = is_v ? a.v_scale : a.k_scale;
+    const int64_t bs = is_v ? a.v_bs : a.k_bs, ts = is_v ? a.v_ts : a.k_ts, hs = is_v ? a.v_hs : a.k_hs;
+    constexpr int kSrcEsz = MODE == kCopy16 ? 2 : 1;
+    src += (int64_t)row * bs * kSrcEsz;
+    dst += (int64_t)at * a.vec_per_tok * 16;  // packed rows: a token is vec_per_tok 16-byte vectors
+    const unsigned src_vecs = (unsigned)a.d_src >> 3;
+
+    u32x4 val[kUnroll];
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+        const unsigned v = first + u * kThreads;
+        val[u] = u32x4{0u, 0u, 0u, 0u};
+        if (v < total) {
+            const unsigned t = fdiv(v, a.div_vec_per_tok), r = v - t * (unsigned)a.vec_per_tok;
+            const unsigned h = fdiv(r, a.div_vec_per_head), c = r - h * (unsigned)a.vec_per_head;
+            if (c < src_vecs) {  // else: a pad column of a wider destination row
+                const char* p = src + ((int64_t)t * ts + (int64_t)h * hs + c * 8) * kSrcEsz;
+                if (MODE == kCopy16) {
+                    val[u] = *reinterpret_cast<const u32x4*>(p);
+                } else {
+                    val[u] = widen8<MODE>(*reinterpret_cast<const u32x2*>(p), scale ? scale[h] : 1.f);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+        const unsigned v = first + u * kThreads;
+        if (v < total) *reinterpret_cast<u32x4*>(dst + (int64_t)v * 16) = val[u];
+    }
+}
+
+int launch_kv_promote(const KvPromoteArgs& a, int src_dtype, int dst_dtype, hipStream_t s) {
+    const int64_t vecs = (int64_t)a.max_len * a.vec_per_tok;
+    const int64_t chunks = (vecs + kThreads * kUnroll - 1) / (kThreads * kUnroll);
+    if (chunks <= 0 || chunks > 0x7fffffffLL || a.n <= 0 || a.n > 65535) return (int)hipErrorInvalidValue;
+    const dim3 grid((unsigned)chunks, (unsigned)a.n, 2), block(kThreads);
+    if (src_dtype != HYD_FP8_E4M3)
+        hipLaunchKernelGGL(kv_promote_kernel<kCopy16>, grid, block, 0, s, a);
+    else if (dst_dtype == HYD_F16)
+        hipLaunchKernelGGL(kv_promote_kernel<kFp8ToF16>, grid, block, 0, s, a);
+    else
+        hipLaunchKernelGGL(kv_promote_kernel<kFp8ToBf16>, grid, block, 0, s, a);
+    return (int)hipGetLastError();
+}
+
+}  // namespace hyd

@@ -343,6 +343,34 @@ class PerLayerKVCache(nn.Module):
         self.shared_caches[self.num_used_shared_caches].fill(key_states, value_states, seq_lens)
         self.num_used_shared_caches += 1
 
+    @torch.no_grad()
+    def promote_unique(self, rows: Tensor, lens: Tensor, host_lens, use_kernel: bool = True):
+        """Fork (hydragen_amd/fork.py): the first lens[i] cached tokens of unique sequence rows[i] become sequence i of the next
+        free shared level -- K and V gathered by one hyd_kv_promote launch (use_kernel=False: its torch definition), no forward
+        pass; fp8 unique caches are widened with this cache's scales.  rows / lens: [k] device vectors; host_lens: the same
+        lengths on the host (the caller has them: nothing is synchronised here).  The level is left exactly as SharedCache.fill
+        leaves it for the same data, and the same errors are raised: no free level, batch or length over the level's maximum."""
+        from .fork import promote_kv, promote_kv_reference
+
+        if self.num_used_shared_caches >= self.get_num_total_shared_caches():
+            raise ValueError(f"No more available shared caches: {self.num_used_shared_caches} {self.get_num_total_shared_caches()}")
+        sc: SharedCache = self.shared_caches[self.num_used_shared_caches]
+        host_lens = [int(x) for x in host_lens]
+        bs = len(host_lens)
+        if bs > sc.max_batch_size:
+            raise ValueError(f"Batch size {bs} exceeds max batch size {sc.max_batch_size}")
+        if max(host_lens) > sc.max_sequence_length:
+            raise ValueError(f"Sequence length {max(host_lens)} exceeds max sequence length {sc.max_sequence_length}")
+        cu = (promote_kv if use_kernel else promote_kv_reference)(
+            self.per_completion_k_cache, self.per_completion_v_cache, rows, lens, sc.k_cache, sc.v_cache,
+            max_len=max(host_lens), **self.scales())
+        sc.seq_lens[:bs] = lens.to(torch.int32)
+        sc.cumsum_lengths[: bs + 1] = cu
+        sc.use_varlen = max(host_lens) != min(host_lens)
+        sc.sliced_sequence_length = None if sc.use_varlen else host_lens[0]
+        sc.current_batch_size = bs
+        self.num_used_shared_caches += 1
+
 
 class AttentionMode:
     SHARED_PREFILL = "shared-prefill"
@@ -874,6 +902,68 @@ class HydragenLlamaForCausalLM(nn.Module):
         lens = None if seq_lens is None else seq_lens.to(input_ids.device)
         self.shared_bitmaps.append(layer_ops.token_bitmap(input_ids.long(), lens, self.vocab_size))
         return logits
+
+    @torch.no_grad()
+    def fork(self, rows, seq_lens, token_ids, old_batch: int, use_kernel: bool = True) -> int:
+        """Promote completions of the previous decode batch to a new shared level, without a forward pass: the first seq_lens[i]
+        cached tokens of unique sequence rows[i] become sequence i of the next free shared level at every layer (one
+        hyd_kv_promote launch per layer; use_kernel=False: the torch definition, hydragen_amd/fork.py).  The level comes directly
+        after the levels in use, so the rows' absolute RoPE positions stay valid.  Returns the number of levels in use.
+
+        rows [k]: batch indices of the previous decode batch of `old_batch` sequences (a list or a tensor); old_batch is passed
+        explicitly -- it cannot be told from the rows, and the rule below depends on it.  seq_lens [k]: cached tokens to promote, each
+        at least 1 and at most what is cached.  token_ids [k, max(seq_lens)] (right-padded): the tokens those K/V rows belong to --
+        their set is recorded next to the level for the sampling penalties, as append_shared does, because a later call may ask
+        for penalties.  check_fork_rows (fork.py) must hold for the levels in use: the same number of survivors under every shared
+        sequence of every level, listed in group order.  Every check runs on the host before the first launch; one host
+        synchronisation if rows / seq_lens are device tensors, none per layer.  A captured decode graph stays valid: its key holds
+        the levels' batch sizes, varlen flags and sliced lengths, and the level's buffers (K/V, lengths, offsets) are static.
+
+        What is cached: after a generate() that returned n tokens, row b holds unique_prompt_len + n - 1 tokens in the unique
+        cache -- its own prompt, then returned tokens 0 .. n - 2 (token_overrides where given): the last returned token was never
+        fed.  On the stop-condition path a row that finished with `length` kept tokens holds at least unique_prompt_len + length - 1
+        (a finished row is no longer fed; a stop sequence that was cut had its first tokens fed before it matched, they sit
+        behind those and need not be promoted).  To continue, pass each survivor's first uncached token as a one-token unique
+        prompt: generate(input_ids=last[rows].repeat_interleave(m, 0)[:, None], num_return_sequences=1, ...) samples every
+        survivor m times and uses one level per fork.  Tensor-parallel ranks call fork with the same arguments: the caches are
+        per-rank head shards, nothing else changes."""
+        from .fork import check_fork_rows
+
+        if not self.kv_cache_allocated:
+            raise RuntimeError("call setup_caches() before fork()")
+        rows_l = [int(x) for x in (rows.tolist() if isinstance(rows, Tensor) else rows)]
+        lens_l = [int(x) for x in (seq_lens.tolist() if isinstance(seq_lens, Tensor) else seq_lens)]
+        k = len(rows_l)
+        if k == 0 or len(lens_l) != k:
+            raise ValueError(f"fork of {k} rows with {len(lens_l)} lengths")
+        kv = self.model.layers[0].self_attn.kv_cache
+        max_batch, room = kv.per_completion_k_cache.shape[:2]
+        if not 1 <= int(old_batch) <= max_batch:
+            raise ValueError(f"old_batch {old_batch}: the unique cache holds {max_batch} sequences")
+        check_fork_rows(rows_l, old_batch, [c.current_batch_size for c in kv.get_used_shared_caches()])
+        if min(lens_l) < 1 or max(lens_l) > room:
+            raise ValueError(f"seq_lens {lens_l}: each at least 1 and at most the {room} tokens a unique sequence caches")
+        if not isinstance(token_ids, Tensor) or token_ids.ndim != 2 or token_ids.shape != (k, max(lens_l)):
+            raise ValueError(f"token_ids must be [{k}, {max(lens_l)}] (right-padded to the longest promoted length), got "
+                             f"{tuple(token_ids.shape) if isinstance(token_ids, Tensor) else type(token_ids)}")
+        used = kv.num_used_shared_caches
+        if used >= kv.get_num_total_shared_caches():
+            raise ValueError(f"No more available shared caches: {used} {kv.get_num_total_shared_caches()}")
+        sc = kv.shared_caches[used]
+        if k > sc.max_batch_size:
+            raise ValueError(f"Batch size {k} exceeds max batch size {sc.max_batch_size}")
+        if max(lens_l) > sc.max_sequence_length:
+            raise ValueError(f"Sequence length {max(lens_l)} exceeds max sequence length {sc.max_sequence_length}")
+        dev = kv.per_completion_k_cache.device
+        rows_t = torch.tensor(rows_l, dtype=torch.int32, device=dev)
+        lens_t = torch.tensor(lens_l, dtype=torch.int32, device=dev)
+        for layer in self.model.layers:
+            layer.self_attn.kv_cache.promote_unique(rows_t, lens_t, lens_l, use_kernel=use_kernel)
+        # the level's token set, with append_shared's discipline: after the level exists, whatever the list held beyond it dropped
+        del self.shared_bitmaps[used:]
+        ids = token_ids.to(dev).long()
+        self.shared_bitmaps.append(layer_ops.token_bitmap(ids, lens_t.to(device=ids.device, dtype=torch.int64), self.vocab_size))
+        return self.get_num_used_shared_caches()
 
     @torch.no_grad()
     def process_unique(self, input_ids, seq_lens=None):

@@ -48,7 +48,7 @@ extern "C" {
 
 /* 0.5.0 also carries the fp8 unique-cache entry points (hyd_kv_quant, hyd_*_kvq, hyd_kv_quant_supported) and the filtered
  * sampler (hyd_sample_filter_params, hyd_sample_tokens_filtered), the scoring entry point (hyd_token_logprob_params,
- * hyd_token_logprobs) and the penalised sampler (hyd_sample_penalty_params, hyd_sample_tokens_penalized, hyd_token_bitmap_build) and the stop-condition entry point (hyd_stop_params, hyd_stop_update): they are new symbols and new structs only -- no existing struct, entry point or result changed -- so a caller built against 0.5.0 without them is
+ * hyd_token_logprobs) and the penalised sampler (hyd_sample_penalty_params, hyd_sample_tokens_penalized, hyd_token_bitmap_build) and the stop-condition entry point (hyd_stop_params, hyd_stop_update) and the unique-to-shared K/V copy (hyd_kv_promote_params, hyd_kv_promote): they are new symbols and new structs only -- no existing struct, entry point or result changed -- so a caller built against 0.5.0 without them is
  * unaffected and the version stays 500. */
 #define HYD_VERSION 500 /* 0.5.0: hyd_suffix_params.seq_order (schedule hint for ragged lengths); 0.4.0: hyd_add_rmsnorm, hyd_swiglu, hyd_sample_tokens (model-shell glue); 0.3.0: two-stream phases + hyd_decode_params.shared_max_workgroups, hyd_decode_two_stream_ok; 0.2.2: hyd_allreduce_params.timeout_log2_polls; 0.2.1: softmax_scale; 0.2.0: hyd_decode_params.phase, hyd_rope_params.max_pos, hyd_allreduce_* */
 #define HYD_MAX_LEVELS 8
@@ -609,6 +609,53 @@ HYD_API int hyd_kv_quant_supported(const hyd_suffix_params* p, const hyd_kv_quan
 /* Shapes only (capture-safe, no device read): 1 exactly when hyd_decode_attn_fused_kvq takes this call natively with kq's
  * cache dtype -- phase, single_launch_small and the levels as given (always 1 for kq == NULL or kv_dtype == dtype) --, else 0. */
 HYD_API int hyd_decode_kv_quant_supported(const hyd_decode_params* p, const hyd_kv_quant* kq);
+
+/* ------------------------------------------------------------------------------------------
+ * Fork completions: promote rows of the UNIQUE K/V caches to a packed SHARED level, K and V in one launch (no forward pass: the
+ * rotated K/V of the chosen completions already sit in the unique caches, and a level that comes directly after the levels in
+ * use keeps their absolute RoPE positions valid).  For i < n, t < lens[i], every kv head h:
+ *     dst[cu[i] + t, h, c] = src[rows[i], t, h, c]   for c < d_src,      = 0   for d_src <= c < d_dst
+ * (the pad columns of a destination wider than the source rows are WRITTEN as zeros: the narrow-cache rule of the shared levels);
+ * destination tokens at or past cu[n] are not touched.
+ *   - source: the unique caches [B, src_rows, Hkv, d_src] by pointer and batch / token / head strides in elements (views of the
+ *     [batch, K | V, rows, heads, dim] arena: the batch stride is NOT src_rows * Hkv * d_src), d_src contiguous; HYD_F16, HYD_BF16,
+ *     or HYD_FP8_E4M3 (1-byte elements) with per-kv-head fp32 k_scale / v_scale (NULL = 1);
+ *   - destination: packed [capacity, Hkv, d_dst] contiguous, HYD_F16 | HYD_BF16; d_dst >= d_src, and 64 / 128 / 256 or == d_src;
+ *   - a 16-bit source is copied as BYTES (bit-exact, NaN payloads included; its dtype must be the destination's); an fp8 source
+ *     is widened by the rule of the fp8 unique caches above: float(q8) * scale[h] as an fp32 product, rounded once to dst_dtype,
+ *     ties to even (hydragen_amd/kv_quant.py dequantize_kv is the definition; bit-identical to it);
+ *   - rows / lens / cu are DEVICE arrays read at launch time (capture-safe; cu[i + 1] - cu[i] == lens[i] is the caller's to keep).
+ *     A sequence with rows[i] outside [0, B), lens[i] > max_len, cu[i] < 0 or cu[i] + lens[i] > capacity is skipped as a whole:
+ *     nothing is indexed with such a value; lens[i] <= 0 copies nothing;
+ *   - max_len is the HOST's bound on lens[] (0 = src_rows): the launch grid is sized by it and by n, never by device data.
+ * HYD_ERR_BAD_ARG: a null k_src / v_src / k_dst / v_dst / rows / lens / cu, n <= 0, Hkv <= 0, B <= 0, src_rows <= 0, capacity < 0,
+ * d_src <= 0 or d_src % 8 != 0, d_dst < d_src, max_len outside [0, src_rows], a 16-bit src_dtype that differs from dst_dtype,
+ * strides that are no multiple of 8 elements (or head stride < d_src), pointers that are not 16-byte (rows / lens / cu / scales:
+ * 4-byte) aligned.  HYD_ERR_UNSUPPORTED: dst_dtype other than HYD_F16 / HYD_BF16 (no fp8 or 32-bit shared levels), another
+ * src_dtype, d_dst that is neither 64 / 128 / 256 nor d_src, n > 65535, max_len * Hkv * d_dst / 8 >= 2^31.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct hyd_kv_promote_params {
+    const void* k_src;      /* sequence b, token t, head h at k_src + b*k_batch_stride + t*k_tok_stride + h*k_head_stride */
+    const void* v_src;
+    void* k_dst;            /* [capacity, Hkv, d_dst] contiguous, dst_dtype                                  */
+    void* v_dst;
+    const int32_t* rows;    /* [n] source batch index                                                        */
+    const int32_t* lens;    /* [n] tokens taken from the front of that row                                   */
+    const int32_t* cu;      /* [n + 1] destination token offsets                                             */
+    const float* k_scale;   /* [Hkv] or NULL = 1; fp8 sources only                                           */
+    const float* v_scale;
+    int64_t k_batch_stride, k_tok_stride, k_head_stride; /* elements of src_dtype                            */
+    int64_t v_batch_stride, v_tok_stride, v_head_stride;
+    int32_t src_dtype;      /* HYD_F16 | HYD_BF16 | HYD_FP8_E4M3                                             */
+    int32_t dst_dtype;      /* HYD_F16 | HYD_BF16                                                            */
+    int32_t n;              /* sequences to promote                                                          */
+    int32_t B, src_rows;    /* sequences and token rows of the source caches                                 */
+    int32_t Hkv, d_src, d_dst;
+    int32_t capacity;       /* token rows of the destination                                                 */
+    int32_t max_len;        /* host bound on lens[]; 0 = src_rows                                            */
+} hyd_kv_promote_params;
+
+HYD_API int hyd_kv_promote(const hyd_kv_promote_params* p, void* stream);
 
 HYD_API int hyd_version(void);
 HYD_API const char* hyd_last_error_string(void);
