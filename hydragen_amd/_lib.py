@@ -192,6 +192,26 @@ class KvPromoteParams(C.Structure):
     ]
 
 
+KV_ABSMAX_PASSES = 16  # HYD_KV_ABSMAX_PASSES
+
+
+class KvAbsmaxParams(C.Structure):
+    _fields_ = [
+        ("k", C.c_void_p), ("v", C.c_void_p), ("row_lens", C.c_void_p), ("amax", C.c_void_p),
+        ("k_outer_stride", C.c_int64), ("k_row_stride", C.c_int64), ("k_head_stride", C.c_int64),
+        ("v_outer_stride", C.c_int64), ("v_row_stride", C.c_int64), ("v_head_stride", C.c_int64),
+        ("dtype", C.c_int32), ("Hkv", C.c_int32), ("d", C.c_int32), ("n_outer", C.c_int32), ("n_rows", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class KvScalesParams(C.Structure):
+    _fields_ = [
+        ("amax", C.c_void_p), ("k_scale", C.c_void_p), ("v_scale", C.c_void_p),
+        ("Hkv", C.c_int32), ("c", C.c_float), ("pow2", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 class AllReduceParams(C.Structure):
     _fields_ = [
         ("blocks", C.POINTER(C.c_void_p)), ("in_", C.c_void_p), ("out", C.c_void_p), ("count", C.c_int64),
@@ -235,6 +255,8 @@ EXPORTS = {
     "hyd_token_logprobs": (C.c_int, [C.POINTER(TokenLogprobParams), C.c_void_p]),
     "hyd_stop_update": (C.c_int, [C.POINTER(StopParams), C.c_void_p]),
     "hyd_kv_promote": (C.c_int, [C.POINTER(KvPromoteParams), C.c_void_p]),
+    "hyd_kv_absmax": (C.c_int, [C.POINTER(KvAbsmaxParams), C.c_void_p]),
+    "hyd_kv_scales_from_absmax": (C.c_int, [C.POINTER(KvScalesParams), C.c_void_p]),
     "hyd_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }

@@ -1011,6 +1011,67 @@ int hyd_kv_promote(const hyd_kv_promote_params* p, void* stream) {
     return launched(launch_kv_promote(a, p->src_dtype, p->dst_dtype, static_cast<hipStream_t>(stream)), "kv_promote kernel launch");
 }
 
+int hyd_kv_absmax(const hyd_kv_absmax_params* p, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    if (p->dtype != HYD_F16 && p->dtype != HYD_BF16)
+        return fail(HYD_ERR_UNSUPPORTED, "dtype %d: the observed K / V are f16 / bf16 (no fp8 or 32-bit source)", p->dtype);
+    if (p->Hkv < 1) return fail(HYD_ERR_BAD_ARG, "Hkv %d must be >= 1", p->Hkv);
+    if (p->d < 8 || p->d > 256 || p->d % 8 != 0) return fail(HYD_ERR_BAD_ARG, "d %d must be a multiple of 8 in 8..256 (16-byte vectors)", p->d);
+    if (p->n_outer < 0 || p->n_rows < 0) return fail(HYD_ERR_BAD_ARG, "n_outer %d / n_rows %d must be >= 0", p->n_outer, p->n_rows);
+    if (!p->amax) return fail(HYD_ERR_BAD_ARG, "amax is null");
+    if (!p->k && !p->v) return fail(HYD_ERR_BAD_ARG, "k and v are both null");
+    if (misaligned(p->k, 16)) return fail(HYD_ERR_BAD_ARG, "k must be 16-byte aligned");
+    if (misaligned(p->v, 16)) return fail(HYD_ERR_BAD_ARG, "v must be 16-byte aligned");
+    if (misaligned(p->amax, 4) || misaligned(p->row_lens, 4)) return fail(HYD_ERR_BAD_ARG, "amax / row_lens is not aligned to its element size");
+    if (p->k) {
+        if (int rc = check_stride8(p->k_outer_stride, "k_outer_stride")) return rc;
+        if (int rc = check_stride8(p->k_row_stride, "k_row_stride")) return rc;
+        if (int rc = check_stride8(p->k_head_stride, "k_head_stride")) return rc;
+    }
+    if (p->v) {
+        if (int rc = check_stride8(p->v_outer_stride, "v_outer_stride")) return rc;
+        if (int rc = check_stride8(p->v_row_stride, "v_row_stride")) return rc;
+        if (int rc = check_stride8(p->v_head_stride, "v_head_stride")) return rc;
+    }
+    if (p->n_rows > (1 << 30)) return fail(HYD_ERR_UNSUPPORTED, "n_rows %d: up to 2^30 rows per outer index", p->n_rows);
+    const int64_t vpr = (int64_t)p->Hkv * (p->d / 8);
+    if (vpr > (1 << 24)) return fail(HYD_ERR_UNSUPPORTED, "Hkv %d x d %d: a token row of more than 2^24 16-byte vectors", p->Hkv, p->d);
+    if (p->n_outer == 0 || p->n_rows == 0) return HYD_OK;
+    KvAbsmaxArgs a;
+    memset(&a, 0, sizeof(a));
+    a.k = p->k; a.v = p->v; a.row_lens = p->row_lens; a.amax = reinterpret_cast<unsigned*>(p->amax);
+    a.k_os = p->k_outer_stride; a.k_rs = p->k_row_stride; a.k_hs = p->k_head_stride;
+    a.v_os = p->v_outer_stride; a.v_rs = p->v_row_stride; a.v_hs = p->v_head_stride;
+    a.Hkv = p->Hkv; a.n_outer = p->n_outer; a.n_rows = p->n_rows;
+    a.pph = p->d / 8; a.vpr = (int32_t)vpr;
+    a.cols = a.vpr < 256 ? a.vpr : 256;
+    a.rstep = 256 / a.cols;
+    a.group = a.pph & -a.pph;  // (pph <= 32)
+    const int rows_per_wg = HYD_KV_ABSMAX_PASSES * a.rstep;
+    a.chunks = (p->n_rows + rows_per_wg - 1) / rows_per_wg;
+    a.only = p->k && p->v ? 0 : (p->k ? 1 : 2);
+    a.div_pph = make_fastdiv((uint32_t)a.pph);
+    a.div_cols = make_fastdiv((uint32_t)a.cols);
+    a.div_chunks = make_fastdiv((uint32_t)a.chunks);
+    if ((int64_t)a.chunks * a.n_outer > 0x7fffffffLL || (a.vpr + a.cols - 1) / a.cols > 65535)
+        return fail(HYD_ERR_UNSUPPORTED, "n_outer %d x n_rows %d x Hkv %d: more workgroups than one launch takes", p->n_outer, p->n_rows, p->Hkv);
+    return launched(launch_kv_absmax(a, p->dtype, static_cast<hipStream_t>(stream)), "kv_absmax kernel launch");
+}
+
+int hyd_kv_scales_from_absmax(const hyd_kv_scales_params* p, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    if (!p->amax || !p->k_scale || !p->v_scale) return fail(HYD_ERR_BAD_ARG, "amax / k_scale / v_scale is null");
+    if (misaligned(p->amax, 4) || misaligned(p->k_scale, 4) || misaligned(p->v_scale, 4))
+        return fail(HYD_ERR_BAD_ARG, "amax / k_scale / v_scale is not aligned to its element size");
+    if (p->Hkv < 1) return fail(HYD_ERR_BAD_ARG, "Hkv %d must be >= 1", p->Hkv);
+    if (!(p->c > 0.f) || std::isinf(p->c)) return fail(HYD_ERR_BAD_ARG, "c %g must be finite and positive (margin / 448)", (double)p->c);
+    KvScalesArgs a;
+    memset(&a, 0, sizeof(a));
+    a.amax = p->amax; a.k_scale = p->k_scale; a.v_scale = p->v_scale;
+    a.Hkv = p->Hkv; a.pow2 = p->pow2 ? 1 : 0; a.c = p->c;
+    return launched(launch_kv_scales(a, static_cast<hipStream_t>(stream)), "kv_scales kernel launch");
+}
+
 int hyd_ipc_get_handle(const void* dev_ptr, void* handle_out) {
     static_assert(sizeof(hipIpcMemHandle_t) == HYD_IPC_HANDLE_BYTES, "IPC handle size");
     if (!dev_ptr || !handle_out) return fail(HYD_ERR_BAD_ARG, "null pointer");

@@ -250,7 +250,32 @@ struct KvPromoteArgs {  // kv_promote.hip: chosen rows of the unique K/V caches 
     FastDiv div_vec_per_head, div_vec_per_tok;
 };
 
+struct KvAbsmaxArgs {  // kv_scale.hip: per-kv-head max |x| of a strided 16-bit view [n_outer, n_rows, Hkv, d] (hyd_kv_absmax)
+    const void* k;
+    const void* v;
+    const int32_t* row_lens;  // [n_outer] or null = n_rows
+    unsigned* amax;           // f32 [2, Hkv] as bit patterns (non-negative floats order as their bits)
+    int64_t k_os, k_rs, k_hs, v_os, v_rs, v_hs;  // outer / row / head strides (elements)
+    int32_t Hkv, n_outer, n_rows;
+    int32_t pph, vpr;     // 16-byte pieces of a head row (d / 8) and of a token row (Hkv * d / 8)
+    int32_t cols, rstep;  // piece columns a workgroup covers (min(vpr, 256)) and the rows it takes side by side (256 / cols)
+    int32_t group;        // the largest power of two that divides pph: lanes that meet by shuffles
+    int32_t chunks;       // workgroups along the rows of one outer: ceil(n_rows / (HYD_KV_ABSMAX_PASSES * rstep))
+    int32_t only;         // 0: K and V; 1: K alone; 2: V alone
+    FastDiv div_pph, div_cols, div_chunks;
+};
+
+struct KvScalesArgs {  // kv_scale.hip: amax [2, Hkv] -> k_scale / v_scale [Hkv] (hyd_kv_scales_from_absmax)
+    const float* amax;
+    float* k_scale;
+    float* v_scale;
+    int32_t Hkv, pow2;
+    float c;
+};
+
 // launchers (defined next to the kernels); return hipError_t as int
+int launch_kv_absmax(const KvAbsmaxArgs& a, int dtype, hipStream_t s);  // kv_scale.hip
+int launch_kv_scales(const KvScalesArgs& a, hipStream_t s);             // kv_scale.hip
 int launch_kv_promote(const KvPromoteArgs& a, int src_dtype, int dst_dtype, hipStream_t s);  // kv_promote.hip
 int launch_prefix_w64(const PrefixArgs& a, int dtype, int D, bool causal, int grid, hipStream_t s);
 int launch_prefix_w64_f16(const PrefixArgs& a, int D, bool causal, int grid, hipStream_t s);  // prefix_attn_w64_f16.hip

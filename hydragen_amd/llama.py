@@ -27,7 +27,8 @@ from . import layer_ops, placement, sampling, scoring, stopping
 from .attention import hydragen_attention
 from . import flash as _flash
 from .flash import flash_attention, flash_attention_seqlen, padded_head_dim
-from .kv_quant import FP8_DTYPE, dequantize_kv, quantize_kv
+from . import kv_quant as _kv_quant
+from .kv_quant import FP8_DTYPE, dequantize_kv, quantize_kv, scale_constant
 from .tp import all_reduce_sum, check_collectives
 
 
@@ -232,13 +233,13 @@ class PerLayerKVCache(nn.Module):
 
     def __init__(self, max_unique_batch_size, max_unique_seq_length, max_shared_batch_sizes, max_shared_seq_lengths,
                  n_kv_heads, head_dim, device, dtype, arena: Optional[Tensor] = None, kv_cache_dtype: Optional[torch.dtype] = None,
-                 n_q_heads: Optional[int] = None):
+                 n_q_heads: Optional[int] = None, kv_scales: str = "unit", kv_scale_margin: float = 2.0):
         super().__init__()
         shape = (max_unique_batch_size, max_unique_seq_length, n_kv_heads, head_dim)
         self.head_dim = head_dim
         # kv_cache_dtype = torch.float8_e4m3fn: the unique arena holds e4m3fn bytes (kv_quant.py) with one fp32 scale per kv head
-        # for K and for V (k_scale / v_scale, 1.0 until set in place: a captured graph keeps their pointers); the shared caches
-        # stay in `dtype`
+        # for K and for V (k_scale / v_scale: 1.0 with kv_scales = "unit"; "calibrate" rewrites them in place from the prompts'
+        # K / V -- kv_amax, the freeze rule below -- so a captured graph keeps their pointers); the shared caches stay in `dtype`
         udtype = dtype if kv_cache_dtype is None else kv_cache_dtype
         if udtype not in (dtype, FP8_DTYPE):
             raise NotImplementedError(f"unique KV cache dtype {udtype}: the model's {dtype} or {FP8_DTYPE}")
@@ -252,6 +253,20 @@ class PerLayerKVCache(nn.Module):
             self.register_buffer("v_scale", torch.ones((n_kv_heads,), dtype=torch.float32, device=device), persistent=False)
         else:
             self.k_scale = self.v_scale = None
+        if kv_scales not in ("unit", "calibrate"):
+            raise ValueError(f'kv_scales {kv_scales!r}: "unit" or "calibrate"')
+        if kv_scales != "unit" and not self.fp8:
+            raise ValueError(f"kv_scales={kv_scales!r} belongs to fp8 unique caches, this cache is {udtype}")
+        # "calibrate": the running max |K|, max |V| per kv head of the prefills' 16-bit K / V (kv_quant.observe_absmax), allocated
+        # once; None with "unit": nothing is observed and nothing new is launched.  The scales are rewritten from it only inside a
+        # window that generate() / score() open and the first write to the unique cache closes: while no row of it is alive
+        self.kv_scale_margin = float(kv_scale_margin)
+        scale_constant(self.kv_scale_margin)  # (refuses a margin that is not finite and positive)
+        self._scale_window = False
+        if kv_scales == "calibrate":
+            self.register_buffer("kv_amax", torch.zeros((2, n_kv_heads), dtype=torch.float32, device=device), persistent=False)
+        else:
+            self.kv_amax = None
         dtype_unique = udtype
         # One allocation per layer (the reference's two attribute names, llama.py:186-198, stay as views of it): a sequence's K rows,
         # then its V rows (placement.kv_arena: the suffix pass streams that 1.5-3 % faster than all K, then all V).  WHERE the arena
@@ -277,6 +292,35 @@ class PerLayerKVCache(nn.Module):
     def truncate_shared_caches(self, n: int):
         assert n <= self.get_num_total_shared_caches(), f"{n} {self.get_num_total_shared_caches()}"
         self.num_used_shared_caches = n
+        if n == 0 and self.kv_amax is not None:
+            self.kv_amax.zero_()  # a fresh hierarchy is calibrated from its own prompts (kept levels keep the running maximum)
+
+    # ---- calibrated scales ("calibrate"): observe -> window -> freeze -----------------------------------------------------------
+    def observe_kv(self, k: Tensor, v: Tensor, row_lens: Optional[Tensor] = None):
+        """A prefill's 16-bit K (after RoPE) and V, as they come: one hyd_kv_absmax launch into kv_amax."""
+        if self.kv_amax is not None:
+            _kv_quant.observe_absmax(k, v, self.kv_amax, row_lens)
+
+    def open_scale_window(self):
+        """generate() / score() start: the unique cache holds no row that a later launch of the call reads, the scales may move."""
+        self._scale_window = self.kv_amax is not None
+
+    def close_scale_window(self, write: bool = True):
+        """The first write to the unique cache of a call (or the call's end, write=False): the scales are written once from
+        kv_amax and stay as they are until the next window -- every fp8 row is read with the scales it was written with."""
+        if self._scale_window:
+            self._scale_window = False
+            if write:
+                _kv_quant.scales_from_absmax(self.kv_amax, self.k_scale, self.v_scale, self.kv_scale_margin)
+
+    def reset_kv_scales(self):
+        """Forget the running maxima and set the scales back to 1.0 (in place: captured graphs keep the pointers)."""
+        self._scale_window = False
+        if self.kv_amax is not None:
+            self.kv_amax.zero_()
+        if self.fp8:
+            self.k_scale.fill_(1.0)
+            self.v_scale.fill_(1.0)
 
     def scales(self) -> dict:
         """The k_scale / v_scale keywords of the attention operators (empty for 16-bit caches)."""
@@ -291,6 +335,7 @@ class PerLayerKVCache(nn.Module):
     def update_per_completion_kvs(self, input_pos: Tensor, k_val: Tensor, v_val: Tensor):
         """input_pos [bs, sl]; k_val/v_val [bs, sl, h, d] -> scatter into the caches (llama.py:236-262)."""
         assert input_pos.shape[1] == k_val.shape[1], f"{input_pos.shape} {k_val.shape}"
+        self.close_scale_window()
         bs, sl, h, d = k_val.shape
         idx = input_pos[:, :, None, None].expand(bs, -1, h, d).to(torch.int64)
         kc, kv = self._store(self.per_completion_k_cache, k_val, self.k_scale)
@@ -303,6 +348,7 @@ class PerLayerKVCache(nn.Module):
     def copy_shared_to_unique(self, total_num_sequences: int):
         """llama.py:264-298 (the no-sharing baseline materialises the prefix per sequence)."""
         assert self.num_used_shared_caches == 1, "Cannot copy shared without exactly one active shared cache"
+        self.close_scale_window()
         sc: SharedCache = self.shared_caches[0]
         sb = sc.get_current_batch_size()
         assert total_num_sequences % sb == 0
@@ -479,6 +525,11 @@ class HydragenLlamaAttention(nn.Module):
         else:
             unique_position_ids = position_ids - self.kv_cache.get_shared_len(position_ids.shape[0]).unsqueeze(-1)
         q, k = apply_rotary_pos_emb(q, k, cos, sin, position_ids)
+        if self.kv_cache is not None and self.kv_cache.kv_amax is not None and self.mode in (AttentionMode.SHARED_PREFILL, AttentionMode.UNIQUE_PREFILL):
+            # calibrated fp8 scales: this prefill's K / V before any of it is stored.  A shared level stores the rows inside the
+            # lengths, a unique prefill every row it is given
+            lens = (unique_position_ids.max(1).values + 1).to(torch.int32) if self.mode == AttentionMode.SHARED_PREFILL else None
+            self.kv_cache.observe_kv(k, v, lens)
 
         if self.disable_attention:
             attn_output = q
@@ -764,10 +815,28 @@ class HydragenLlamaForCausalLM(nn.Module):
         return self.config.num_attention_heads
 
     def setup_caches(self, max_unique_batch_size: int, max_unique_seq_length: int,
-                     max_shared_batch_sizes: list[int], max_shared_seq_lengths: list[int], kv_cache_dtype: Optional[torch.dtype] = None):
+                     max_shared_batch_sizes: list[int], max_shared_seq_lengths: list[int], kv_cache_dtype: Optional[torch.dtype] = None,
+                     kv_scales: str = "unit", kv_scale_margin: float = 2.0):
         """Allocate the unique KV cache and the shared cache levels at every layer (llama.py:921-955).  kv_cache_dtype =
         torch.float8_e4m3fn makes every layer's unique arena fp8 (half the bytes; per-kv-head k_scale / v_scale buffers on each
-        PerLayerKVCache, 1.0 until set in place); None = the model's dtype.  Shared caches stay in the model's dtype."""
+        PerLayerKVCache); None = the model's dtype.  Shared caches stay in the model's dtype.
+
+        kv_scales (fp8 caches only; anything but "unit" on a 16-bit cache is a ValueError): "unit" keeps every scale at 1.0 and
+        launches nothing new.  "calibrate" sets them per layer and kv head from the prompts' K / V (kv_quant.py): every shared and
+        unique prefill folds max |K| (after RoPE) and max |V| of its 16-bit K / V into the layer's kv_amax [2, Hkv] (one
+        hyd_kv_absmax launch per layer and prefill; decode steps observe nothing), and scale = the smallest power of two >=
+        amax * kv_scale_margin / 448.  The scales are rewritten only while the layer's unique cache holds no live row: generate()
+        and score() open a window when they start, and the first write to the unique cache of that call closes it, writing the
+        scales once -- copy_shared_to_unique (no-sharing mode), the unique prefill's store after its own K / V were observed, or
+        else the call's first decode step.  Outside a window they never change: an append_shared() between a generate() and a
+        fork() observes but does not rescale, and fork() widens fp8 rows with the scales they were written with.  kv_amax is
+        zeroed whenever no shared level is left in use (empty_shared_cache, truncate_shared_caches(0), the "preserve" truncation of
+        a generate() that started from none, setup_caches): a fresh hierarchy is calibrated from its own prompts; kept levels
+        ("extend", fork flows) keep the running maximum, so a scale never shrinks under rows that are alive.  reset_kv_scales()
+        zeroes the maxima and sets the scales back to 1.0.  A tensor-parallel rank calibrates its own kv heads: no collective.
+        Limits: the K / V of generated tokens, and of unique prompts in the no-sharing mode (disable_hydragen: the copied prefix
+        closes the window first), are not observed before they are written -- kv_scale_margin is their headroom, beyond it the
+        quantizer's clamp at +-448 * scale applies, as with scale 1.  Calibration fixes range, not mantissa (kv_quant.py)."""
         self.maybe_invalidate()
         max_unique_seq_length = (max_unique_seq_length + 15) // 16 * 16
         head_dim = self.config.hidden_size // self.get_num_heads()
@@ -788,7 +857,8 @@ class HydragenLlamaForCausalLM(nn.Module):
                 max_unique_batch_size=max_unique_batch_size, max_unique_seq_length=max_unique_seq_length,
                 max_shared_batch_sizes=max_shared_batch_sizes, max_shared_seq_lengths=max_shared_seq_lengths,
                 n_kv_heads=self.config.num_key_value_heads, head_dim=head_dim, device=device, dtype=dtype, arena=arena,
-                kv_cache_dtype=udtype, n_q_heads=self.config.num_attention_heads)
+                kv_cache_dtype=udtype, n_q_heads=self.config.num_attention_heads, kv_scales=kv_scales,
+                kv_scale_margin=kv_scale_margin)
         # the decode loop's schedule hint (flash.seq_order): one buffer for the model's lifetime, so that a captured decode graph
         # keeps pointing at the current generation's order
         self.seq_order_buf = torch.arange(max_unique_batch_size, dtype=torch.int32, device=device)
@@ -798,6 +868,16 @@ class HydragenLlamaForCausalLM(nn.Module):
         for layer in self.model.layers:
             layer.self_attn.kv_cache.empty_shared_cache()
         self.shared_bitmaps.clear()
+
+    def reset_kv_scales(self):
+        """Calibrated fp8 scales (setup_caches kv_scales="calibrate"): zero every layer's running maxima and set the scales back
+        to 1.0, in place."""
+        for layer in self.model.layers:
+            layer.self_attn.kv_cache.reset_kv_scales()
+
+    def _scale_windows(self, op: str, **kw):
+        for layer in self.model.layers:
+            getattr(layer.self_attn.kv_cache, op)(**kw)
 
     def truncate_shared_caches(self, new_num_shared_caches: int):
         for layer in self.model.layers:
@@ -1090,6 +1170,7 @@ class HydragenLlamaForCausalLM(nn.Module):
             raise ValueError("disable_hierarchy flattens a three-level hierarchy with num_return_sequences > 1")
 
         self.model.set_disable_attention(bool(disable_attention))
+        self._scale_windows("open_scale_window")  # calibrated fp8 scales: they may move until this call first writes the unique cache
         logits = None if starting_logits is None else starting_logits.unsqueeze(1)
         for ids, lens in shared:
             logits = self.append_shared(ids, lens)
@@ -1111,6 +1192,7 @@ class HydragenLlamaForCausalLM(nn.Module):
             return self._decode(logits[:, -1], unique, num_return_sequences, max_new_tokens, samp,
                                 eos_token_id, return_logits, token_overrides, return_logprobs, top_n, stop_spec, return_finish)
         finally:
+            self._scale_windows("close_scale_window", write=False)  # (a call that raised before its first write)
             if shared_cache_op == SharedCacheOp.PRESERVE:
                 self.truncate_shared_caches(levels_before)
             self.model.set_disable_hydragen(False)
@@ -1204,6 +1286,7 @@ class HydragenLlamaForCausalLM(nn.Module):
             self.empty_shared_cache()
         levels_before = self.get_num_used_shared_caches()
         self.model.set_disable_attention(False)
+        self._scale_windows("open_scale_window")
         try:
             shared_logits = None
             for ids, lens in shared:
@@ -1216,6 +1299,7 @@ class HydragenLlamaForCausalLM(nn.Module):
             hidden = self.model(input_ids=uids, position_ids=self._positions(uids))
             return self._score_rows(hidden, shared_logits, uids, tl, ul, top_n)
         finally:
+            self._scale_windows("close_scale_window", write=False)
             if shared_cache_op == SharedCacheOp.PRESERVE:
                 self.truncate_shared_caches(levels_before)
             self.model.set_disable_hydragen(False)
@@ -1303,6 +1387,9 @@ class HydragenLlamaForCausalLM(nn.Module):
             pen.push(feed)
             pen.append = token_overrides is None
         self.set_mode(AttentionMode.DECODE)
+        # calibrated fp8 scales: a call without unique prompts first writes the unique cache in its first decode step (the fused
+        # preamble does not pass through update_per_completion_kvs): the scales are written here, once, outside any captured graph
+        self._scale_windows("close_scale_window")
         graphed = self.graphed_model is not None
         # Ragged unique prompts: hand the longest sequences to the chip first.  Every length grows by one per step, so the order of
         # this generation's first step is the order of all of them (C2 heads, lengths 1..128 at random: suffix pass 184 -> 169 us).

@@ -48,7 +48,7 @@ extern "C" {
 
 /* 0.5.0 also carries the fp8 unique-cache entry points (hyd_kv_quant, hyd_*_kvq, hyd_kv_quant_supported) and the filtered
  * sampler (hyd_sample_filter_params, hyd_sample_tokens_filtered), the scoring entry point (hyd_token_logprob_params,
- * hyd_token_logprobs) and the penalised sampler (hyd_sample_penalty_params, hyd_sample_tokens_penalized, hyd_token_bitmap_build) and the stop-condition entry point (hyd_stop_params, hyd_stop_update) and the unique-to-shared K/V copy (hyd_kv_promote_params, hyd_kv_promote): they are new symbols and new structs only -- no existing struct, entry point or result changed -- so a caller built against 0.5.0 without them is
+ * hyd_token_logprobs) and the penalised sampler (hyd_sample_penalty_params, hyd_sample_tokens_penalized, hyd_token_bitmap_build) and the stop-condition entry point (hyd_stop_params, hyd_stop_update) and the unique-to-shared K/V copy (hyd_kv_promote_params, hyd_kv_promote) and the fp8 scale calibration (hyd_kv_absmax_params, hyd_kv_absmax, hyd_kv_scales_params, hyd_kv_scales_from_absmax): they are new symbols and new structs only -- no existing struct, entry point or result changed -- so a caller built against 0.5.0 without them is
  * unaffected and the version stays 500. */
 #define HYD_VERSION 500 /* 0.5.0: hyd_suffix_params.seq_order (schedule hint for ragged lengths); 0.4.0: hyd_add_rmsnorm, hyd_swiglu, hyd_sample_tokens (model-shell glue); 0.3.0: two-stream phases + hyd_decode_params.shared_max_workgroups, hyd_decode_two_stream_ok; 0.2.2: hyd_allreduce_params.timeout_log2_polls; 0.2.1: softmax_scale; 0.2.0: hyd_decode_params.phase, hyd_rope_params.max_pos, hyd_allreduce_* */
 #define HYD_MAX_LEVELS 8
@@ -656,6 +656,59 @@ typedef struct hyd_kv_promote_params {
 } hyd_kv_promote_params;
 
 HYD_API int hyd_kv_promote(const hyd_kv_promote_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Calibrate the per-kv-head scales of the fp8 unique caches from 16-bit K / V (the prompt's, as the prefill computes them).
+ *
+ * hyd_kv_absmax: for every kv head h, the largest |x| over a strided view [n_outer, n_rows, Hkv, d] of K and of V, folded into
+ * the caller's running buffer amax f32 [2, Hkv] (row 0: K, row 1: V) by an integer atomic max on the bit pattern:
+ *     amax[t, h] = max(amax[t, h], max over o < n_outer, r < len(o), c < d of |x_t[o, r, h, c]|),  len(o) = row_lens ? row_lens[o] : n_rows
+ * (row_lens[o] is clamped to [0, n_rows]).  NaN and +-inf elements are ignored; -0 and subnormals count by magnitude.  The result
+ * is exact and does not depend on the order: hydragen_amd/kv_quant.py absmax_reference is the definition.  Rows at or past len(o)
+ * and columns at or past d are never read.  amax must hold non-negative finite floats (zero it once); k or v may be NULL: that
+ * tensor's row of amax is left as it is.  One launch: geometry from shapes only, no allocation, no synchronisation, no scratch;
+ * capture-safe.  A workgroup covers HYD_KV_ABSMAX_PASSES * max(1, 256 / (Hkv * d / 8)) consecutive rows of one outer index.
+ *   - element o, r, h, c of K at k + o*k_outer_stride + r*k_row_stride + h*k_head_stride + c (elements; d contiguous);
+ *   - dtype HYD_F16 | HYD_BF16 (fp8 sources are not taken); d % 8 == 0, 8 <= d <= 256; Hkv >= 1.
+ * HYD_ERR_BAD_ARG: null params or amax, k and v both null, d % 8 != 0 or outside 8..256, Hkv < 1, n_outer / n_rows < 0, k / v not
+ * 16-byte aligned, amax / row_lens not 4-byte aligned, a stride that is no multiple of 8 elements.  HYD_ERR_UNSUPPORTED: another
+ * dtype, n_rows > 2^30, Hkv * d / 8 > 2^24, more than 2^31 - 1 workgroups.  n_outer * n_rows == 0: HYD_OK, nothing launched.
+ *
+ * hyd_kv_scales_from_absmax: one small launch, amax [2, Hkv] -> k_scale [Hkv], v_scale [Hkv].  With t = amax * c as an fp32
+ * product (c = (float)(margin / 448.0): the host computes it):
+ *     scale = 1.0                                                       if amax == 0 (nothing observed, an all-zero head)
+ *           = the smallest power of two >= t, clamped to [2^-100, 2^100]   if pow2 (a t that is a power of two is kept)
+ *           = t clamped to [2^-100, 2^100]                              otherwise
+ * by exponent arithmetic on the bits of t: reproducible bit for bit on the host (kv_quant.py scales_from_absmax_reference).
+ * HYD_ERR_BAD_ARG: null params / amax / k_scale / v_scale, pointers not 4-byte aligned, Hkv < 1, c not finite and positive.
+ * ------------------------------------------------------------------------------------------ */
+#define HYD_KV_ABSMAX_PASSES 16
+
+typedef struct hyd_kv_absmax_params {
+    const void* k;           /* may be NULL (then v is not)                                                   */
+    const void* v;           /* may be NULL (then k is not)                                                   */
+    const int32_t* row_lens; /* [n_outer] or NULL = n_rows                                                    */
+    float* amax;             /* [2, Hkv] running maxima, K row then V row                                     */
+    int64_t k_outer_stride, k_row_stride, k_head_stride; /* elements                                          */
+    int64_t v_outer_stride, v_row_stride, v_head_stride;
+    int32_t dtype;           /* HYD_F16 | HYD_BF16                                                            */
+    int32_t Hkv, d;
+    int32_t n_outer, n_rows;
+    int32_t reserved;
+} hyd_kv_absmax_params;
+
+typedef struct hyd_kv_scales_params {
+    const float* amax;       /* [2, Hkv]                                                                      */
+    float* k_scale;          /* [Hkv]                                                                         */
+    float* v_scale;          /* [Hkv]                                                                         */
+    int32_t Hkv;
+    float c;                 /* (float)(margin / 448.0)                                                       */
+    int32_t pow2;            /* 1: power-of-two scales; 0: amax * c                                           */
+    int32_t reserved;
+} hyd_kv_scales_params;
+
+HYD_API int hyd_kv_absmax(const hyd_kv_absmax_params* p, void* stream);
+HYD_API int hyd_kv_scales_from_absmax(const hyd_kv_scales_params* p, void* stream);
 
 HYD_API int hyd_version(void);
 HYD_API const char* hyd_last_error_string(void);
