@@ -139,9 +139,11 @@ __global__ __launch_bounds__(64 * WPU * HPW) __attribute__((amdgpu_waves_per_eu(
     }
 
     // ---- K / V windows of this unit: rows [0, len) are in range, everything else reads as zero ------------------
-    // The windows span the cache's kv_len rows, NOT the sequence's length: the first step is requested before the length has
-    // arrived (below), so rows in [len, kv_len) may land in the tiles -- whatever they hold (the tests poison them with NaN): their
-    // scores are replaced by -inf (a select, not arithmetic) and their V rows are zeroed in registers (sanitize, masked steps only).
+    // The windows are BUILT over the cache's kv_len rows and cut to the sequence's length (learn_len, below) before the first step is
+    // requested: no row in [len, kv_len) is fetched, a step that reaches past the length is zero-filled by the address check.  What
+    // those rows hold -- NaN, or finite keys with enormous scores (tests/test_softmax_stress_gpu.py, spike_behind_length) -- cannot
+    // reach the maximum or the sums; the zero-filled tail of the last step still has its scores replaced by -inf (a select, not
+    // arithmetic) and its V rows zeroed in registers (sanitize, masked steps only).
     const unsigned k_ts2 = (unsigned)(a.k_ts * 2), v_ts2 = (unsigned)(a.v_ts * 2);
     const u32x4 krs = make_rsrc_g(static_cast<const uint16_t*>(a.k) + (int64_t)b * a.k_bs + (int64_t)hk * a.k_hs, (unsigned)a.kv_len * k_ts2);
     const u32x4 vrs = make_rsrc_g(static_cast<const uint16_t*>(a.v) + (int64_t)b * a.v_bs + (int64_t)hk * a.v_hs, (unsigned)a.kv_len * v_ts2);

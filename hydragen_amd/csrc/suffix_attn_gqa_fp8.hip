@@ -138,6 +138,8 @@ __global__ __launch_bounds__(64 * WPU * HPW) __attribute__((amdgpu_waves_per_eu(
     }
 
     // ---- K / V windows of this unit (strides count bytes): rows [0, len) are in range, everything else reads as zero bytes = +0 ----
+    // Built over the cache's kv_len rows here and cut to the sequence's length before the first step is requested (below): no row in
+    // [len, kv_len) is fetched, whatever it holds (tests/test_softmax_stress_gpu.py, spike_behind_length).
     const unsigned k_ts = (unsigned)a.k_ts, v_ts = (unsigned)a.v_ts;
     u32x4 krs = make_rsrc_g(static_cast<const uint8_t*>(a.k) + (int64_t)b * a.k_bs + (int64_t)hk * a.k_hs, (unsigned)a.kv_len * k_ts);
     u32x4 vrs = make_rsrc_g(static_cast<const uint8_t*>(a.v) + (int64_t)b * a.v_bs + (int64_t)hk * a.v_hs, (unsigned)a.kv_len * v_ts);

@@ -82,3 +82,43 @@ def assert_close_l2(got, want, dtype, what=""):
     bound = ATOL["f16"] * max(1.0, float(np.abs(want).max())) if dtype == "f16" else atol(dtype, want)
     assert err <= bound and l2 <= REL_L2[dtype], f"{what}: max abs {err:.3e} (bound {bound:.3e}) relative L2 {l2:.3e}"
     return err, l2
+
+
+def suffix_fwd_with_partials(tq, tk, tv, tsl, groups, dt, want_lse):
+    """hyd_suffix_attn_fwd with prefix partials handed in directly.  groups: [(is_f32, [(out [B, nq, Hq, D], lse [B, nq, Hq]), ...])],
+    float32 numpy; a group of several partials is marshalled as stacked slices (256-byte aligned strides, as a split prefix pass
+    leaves them), a group of one as a plain partial.  Returns (out, the suffix pass's own LSE or None)."""
+    import ctypes as C
+
+    from hydragen_amd import _lib
+    from hydragen_amd._lib import SuffixParams
+    from hydragen_amd.flash import fill_suffix_params
+
+    lib = _lib.load()
+    al = lambda x: (x + 255) // 256 * 256  # noqa: E731
+    B, _, Hq, D = tq.shape
+    out = torch.empty_like(tq)
+    lse = torch.empty(tuple(tq.shape[:3]), dtype=torch.float32, device=tq.device)
+    sp = SuffixParams()
+    keep = [fill_suffix_params(sp, tq, tk, tv, tsl, out)]
+    if want_lse:
+        sp.lse = lse.data_ptr()
+    rows = tq.shape[0] * tq.shape[1] * Hq
+    for n, (f32, members) in enumerate(groups):
+        cnt = len(members)
+        esz = 4 if f32 else 2
+        ostride = al(rows * D * esz) if cnt > 1 else rows * D * esz
+        lstride = al(rows * 4) if cnt > 1 else rows * 4
+        ob = torch.zeros(cnt * ostride, dtype=torch.uint8, device=tq.device)
+        lb = torch.zeros(cnt * lstride, dtype=torch.uint8, device=tq.device)
+        for j, (o, l) in enumerate(members):
+            t = torch.from_numpy(o).to(tq.device).to(torch.float32 if f32 else TORCH_DT[dt]).contiguous()
+            ob[j * ostride:j * ostride + rows * D * esz] = t.view(torch.uint8).flatten()
+            lb[j * lstride:j * lstride + rows * 4] = torch.from_numpy(l).to(tq.device).contiguous().view(torch.uint8).flatten()
+        sp.partials[n].out, sp.partials[n].lse, sp.partials[n].count, sp.partials[n].is_f32 = ob.data_ptr(), lb.data_ptr(), cnt, int(f32)
+        keep += [ob, lb]
+    sp.n_partials = len(groups)
+    _lib.check(lib.hyd_suffix_attn_fwd(C.byref(sp), torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    del keep
+    return out, (lse if want_lse else None)

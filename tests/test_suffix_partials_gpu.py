@@ -7,21 +7,14 @@ the number of 32-key steps a wave has, the waves per unit and whether the caller
 (then nothing may be folded before the keys end).  Every route against the float64 oracle: random normalised partials
 (16-bit, fp32, stacked fp32 slices as a split prefix pass leaves them) + the oracle's suffix attention, merged by the
 oracle's combine_lse."""
-import ctypes as C
-
 import numpy as np
 import pytest
-import torch
 
 from oracle import hydragen_oracle as O
 from tests.cases import _round
-from tests.gpu_util import TORCH_DT, assert_close_l2, dev
+from tests.gpu_util import assert_close_l2, dev, suffix_fwd_with_partials
 
 pytestmark = pytest.mark.gpu
-
-
-def _al(x):
-    return (x + 255) // 256 * 256
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
@@ -37,11 +30,6 @@ def _al(x):
     (200, 4, 4, 90, None, [("s", 3), ("h", 1)]),                             # one row per unit: the dot-product kernel
 ])
 def test_suffix_kernels_fold_partials_of_every_kind(dt, want_lse, B, Hq, Hkv, mk, lens, parts):
-    from hydragen_amd import _lib
-    from hydragen_amd._lib import SuffixParams
-    from hydragen_amd.flash import fill_suffix_params
-
-    lib = _lib.load()
     D = 128
     rng = np.random.default_rng(B * 131 + Hq + mk + len(parts))
     rnd = lambda *s: _round(rng.standard_normal(s, dtype=np.float32), dt)
@@ -49,40 +37,22 @@ def test_suffix_kernels_fold_partials_of_every_kind(dt, want_lse, B, Hq, Hkv, mk
     sl = np.asarray(lens, dtype=np.int32) if lens is not None else rng.integers(0, mk + 1, B).astype(np.int32)
     if lens is None:
         sl[0], sl[-1] = mk, 1
-    tq, tk, tv, tsl = dev(q, dt), dev(k, dt), dev(v, dt), dev(sl)
-    out = torch.empty_like(tq)
-    lse = torch.empty((B, 1, Hq), dtype=torch.float32, device=tq.device)
-    sp = SuffixParams()
-    keep = [fill_suffix_params(sp, tq, tk, tv, tsl, out)]
-    if want_lse:
-        sp.lse = lse.data_ptr()
-    rows = B * Hq
     outs, lses = [], []  # what the oracle merges
-    n = 0
+    groups = []          # what the library is handed: gpu_util.suffix_fwd_with_partials
     for kind, cnt in parts:
         f32 = kind in ("f", "s")
-        esz = 4 if f32 else 2
-        ostride = _al(rows * D * esz) if cnt > 1 else rows * D * esz
-        lstride = _al(rows * 4) if cnt > 1 else rows * 4
-        ob = torch.zeros(cnt * ostride, dtype=torch.uint8, device=tq.device)
-        lb = torch.zeros(cnt * lstride, dtype=torch.uint8, device=tq.device)
+        members = []
         for j in range(cnt):
             o = rng.standard_normal((B, 1, Hq, D), dtype=np.float32)
             o = o if f32 else _round(o, dt)
             l = (rng.standard_normal((B, 1, Hq)) * 2.0 + 3.0).astype(np.float32)
             l[rng.random((B, 1, Hq)) < 0.05] = -np.inf  # a partial over no keys (an empty ragged group): drops out exactly
             o[~np.isfinite(l)] = 0.0
-            t = torch.from_numpy(o).to(tq.device).to(torch.float32 if f32 else TORCH_DT[dt]).contiguous()
-            ob[j * ostride:j * ostride + rows * D * esz] = t.view(torch.uint8).flatten()
-            lb[j * lstride:j * lstride + rows * 4] = torch.from_numpy(l).to(tq.device).contiguous().view(torch.uint8).flatten()
+            members.append((o, l))
             outs.append(o)
             lses.append(l)
-        sp.partials[n].out, sp.partials[n].lse, sp.partials[n].count, sp.partials[n].is_f32 = ob.data_ptr(), lb.data_ptr(), cnt, int(f32)
-        keep += [ob, lb]
-        n += 1
-    sp.n_partials = n
-    _lib.check(lib.hyd_suffix_attn_fwd(C.byref(sp), torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
+        groups.append((f32, members))
+    out, lse = suffix_fwd_with_partials(dev(q, dt), dev(k, dt), dev(v, dt), dev(sl), groups, dt, want_lse)
     so, slse = O.flash_attention_seqlen(q, k, v, sl)
     so = np.where(np.isfinite(slse)[..., None], so, 0.0)
     want = O.combine_lse(outs + [so], lses + [slse])
