@@ -152,6 +152,16 @@ class TokenBitmapParams(C.Structure):
     ]
 
 
+HYD_DFA_REJECT, HYD_DFA_FREE = -1, -2
+
+
+class TokenDfa(C.Structure):
+    _fields_ = [
+        ("allowed", C.c_void_p), ("next", C.c_void_p), ("state", C.c_void_p), ("allowed_stride", C.c_int64),
+        ("next_stride", C.c_int64), ("n_states", C.c_int32), ("advance", C.c_int32),
+    ]
+
+
 class TokenLogprobParams(C.Structure):
     _fields_ = [
         ("logits", C.c_void_p), ("dtype", C.c_int32), ("n", C.c_int32), ("rows", C.c_int64), ("row_stride", C.c_int64),
@@ -252,6 +262,7 @@ EXPORTS = {
     "hyd_sample_tokens_filtered": (C.c_int, [C.POINTER(SampleFilterParams), C.c_void_p]),
     "hyd_sample_tokens_penalized": (C.c_int, [C.POINTER(SamplePenaltyParams), C.c_void_p]),
     "hyd_token_bitmap_build": (C.c_int, [C.POINTER(TokenBitmapParams), C.c_void_p]),
+    "hyd_sample_tokens_constrained": (C.c_int, [C.POINTER(SamplePenaltyParams), C.POINTER(TokenDfa), C.c_void_p]),
     "hyd_token_logprobs": (C.c_int, [C.POINTER(TokenLogprobParams), C.c_void_p]),
     "hyd_stop_update": (C.c_int, [C.POINTER(StopParams), C.c_void_p]),
     "hyd_kv_promote": (C.c_int, [C.POINTER(KvPromoteParams), C.c_void_p]),

@@ -658,6 +658,43 @@ int fill_filter_args(const P* p, FilterArgs* a) {
     return HYD_OK;
 }
 
+// Everything hyd_sample_tokens_penalized checks, and the argument block of its kernel (shared with hyd_sample_tokens_constrained)
+int fill_penalty_args(const hyd_sample_penalty_params* p, PenaltyArgs* ap) {
+    PenaltyArgs& a = *ap;
+    int rc = check_filter(p);
+    if (rc) return rc;
+    if (!(p->repetition_penalty > 0.0) || std::isinf(p->repetition_penalty))
+        return fail(HYD_ERR_BAD_ARG, "repetition_penalty %g must be a finite number > 0 (1 = off)", p->repetition_penalty);
+    if (!std::isfinite(p->frequency_penalty) || !std::isfinite(p->presence_penalty))
+        return fail(HYD_ERR_BAD_ARG, "frequency_penalty %g / presence_penalty %g must be finite (0 = off)", p->frequency_penalty, p->presence_penalty);
+    if (p->n_context < 0 || p->n_context > HYD_SAMPLE_MAX_CONTEXT)
+        return fail(HYD_ERR_BAD_ARG, "n_context %d: 0 to %d context bitmaps", p->n_context, HYD_SAMPLE_MAX_CONTEXT);
+    for (int l = 0; l < p->n_context; ++l) {
+        if (!p->context[l].bits) return fail(HYD_ERR_BAD_ARG, "context[%d].bits is null", l);
+        if (p->context[l].rows_per_group <= 0) return fail(HYD_ERR_BAD_ARG, "context[%d].rows_per_group %d must be > 0", l, p->context[l].rows_per_group);
+        if (misaligned(p->context[l].bits, 4)) return fail(HYD_ERR_BAD_ARG, "context[%d].bits is not aligned to its element size", l);
+    }
+    if ((p->gen == nullptr) != (p->gen_len == nullptr)) return fail(HYD_ERR_BAD_ARG, "gen and gen_len go together (one of them is null)");
+    if (p->gen_stride < 0) return fail(HYD_ERR_BAD_ARG, "gen_stride %d must be >= 0", p->gen_stride);
+    if (p->gen_stride > HYD_SAMPLE_GEN_MAX) return fail(HYD_ERR_UNSUPPORTED, "gen_stride %d: up to %d generated tokens per row", p->gen_stride, HYD_SAMPLE_GEN_MAX);
+    if (p->append_out && !p->gen) return fail(HYD_ERR_BAD_ARG, "append_out needs gen and gen_len (null)");
+    if (p->n_bias < 0 || p->n_bias > HYD_SAMPLE_BIAS_MAX) return fail(HYD_ERR_BAD_ARG, "n_bias %d: 0 to %d logit-bias entries", p->n_bias, HYD_SAMPLE_BIAS_MAX);
+    if (p->n_bias > 0 && (!p->bias_ids || !p->bias_values)) return fail(HYD_ERR_BAD_ARG, "n_bias %d needs bias_ids and bias_values (null)", p->n_bias);
+    memset(&a, 0, sizeof(a));
+    if ((rc = fill_filter_args(p, &a.f))) return rc;
+    if (misaligned(p->gen, 4) || misaligned(p->gen_len, 4) || misaligned(p->bias_ids, 8) || misaligned(p->bias_values, 4))
+        return fail(HYD_ERR_BAD_ARG, "gen / gen_len / bias_ids / bias_values is not aligned to its element size");
+    a.rep = p->repetition_penalty; a.inv_rep = 1.0 / p->repetition_penalty; a.freq = p->frequency_penalty; a.pres = p->presence_penalty;
+    a.n_ctx = p->n_context; a.words = (p->n + 31) / 32;
+    for (int l = 0; l < p->n_context; ++l) {
+        a.ctx[l] = p->context[l].bits;
+        a.ctx_rpg[l] = p->context[l].rows_per_group;
+    }
+    a.gen = p->gen; a.gen_len = p->gen_len; a.gen_stride = p->gen_stride; a.append_out = p->append_out ? 1 : 0;
+    a.bias_ids = p->bias_ids; a.bias_values = p->bias_values; a.n_bias = p->n_bias;
+    return HYD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -859,39 +896,31 @@ int hyd_sample_tokens_filtered(const hyd_sample_filter_params* p, void* stream) 
 }
 
 int hyd_sample_tokens_penalized(const hyd_sample_penalty_params* p, void* stream) {
-    int rc = check_filter(p);
-    if (rc) return rc;
-    if (!(p->repetition_penalty > 0.0) || std::isinf(p->repetition_penalty))
-        return fail(HYD_ERR_BAD_ARG, "repetition_penalty %g must be a finite number > 0 (1 = off)", p->repetition_penalty);
-    if (!std::isfinite(p->frequency_penalty) || !std::isfinite(p->presence_penalty))
-        return fail(HYD_ERR_BAD_ARG, "frequency_penalty %g / presence_penalty %g must be finite (0 = off)", p->frequency_penalty, p->presence_penalty);
-    if (p->n_context < 0 || p->n_context > HYD_SAMPLE_MAX_CONTEXT)
-        return fail(HYD_ERR_BAD_ARG, "n_context %d: 0 to %d context bitmaps", p->n_context, HYD_SAMPLE_MAX_CONTEXT);
-    for (int l = 0; l < p->n_context; ++l) {
-        if (!p->context[l].bits) return fail(HYD_ERR_BAD_ARG, "context[%d].bits is null", l);
-        if (p->context[l].rows_per_group <= 0) return fail(HYD_ERR_BAD_ARG, "context[%d].rows_per_group %d must be > 0", l, p->context[l].rows_per_group);
-        if (misaligned(p->context[l].bits, 4)) return fail(HYD_ERR_BAD_ARG, "context[%d].bits is not aligned to its element size", l);
-    }
-    if ((p->gen == nullptr) != (p->gen_len == nullptr)) return fail(HYD_ERR_BAD_ARG, "gen and gen_len go together (one of them is null)");
-    if (p->gen_stride < 0) return fail(HYD_ERR_BAD_ARG, "gen_stride %d must be >= 0", p->gen_stride);
-    if (p->gen_stride > HYD_SAMPLE_GEN_MAX) return fail(HYD_ERR_UNSUPPORTED, "gen_stride %d: up to %d generated tokens per row", p->gen_stride, HYD_SAMPLE_GEN_MAX);
-    if (p->append_out && !p->gen) return fail(HYD_ERR_BAD_ARG, "append_out needs gen and gen_len (null)");
-    if (p->n_bias < 0 || p->n_bias > HYD_SAMPLE_BIAS_MAX) return fail(HYD_ERR_BAD_ARG, "n_bias %d: 0 to %d logit-bias entries", p->n_bias, HYD_SAMPLE_BIAS_MAX);
-    if (p->n_bias > 0 && (!p->bias_ids || !p->bias_values)) return fail(HYD_ERR_BAD_ARG, "n_bias %d needs bias_ids and bias_values (null)", p->n_bias);
     PenaltyArgs a;
-    memset(&a, 0, sizeof(a));
-    if ((rc = fill_filter_args(p, &a.f))) return rc;
-    if (misaligned(p->gen, 4) || misaligned(p->gen_len, 4) || misaligned(p->bias_ids, 8) || misaligned(p->bias_values, 4))
-        return fail(HYD_ERR_BAD_ARG, "gen / gen_len / bias_ids / bias_values is not aligned to its element size");
-    a.rep = p->repetition_penalty; a.inv_rep = 1.0 / p->repetition_penalty; a.freq = p->frequency_penalty; a.pres = p->presence_penalty;
-    a.n_ctx = p->n_context; a.words = (p->n + 31) / 32;
-    for (int l = 0; l < p->n_context; ++l) {
-        a.ctx[l] = p->context[l].bits;
-        a.ctx_rpg[l] = p->context[l].rows_per_group;
-    }
-    a.gen = p->gen; a.gen_len = p->gen_len; a.gen_stride = p->gen_stride; a.append_out = p->append_out ? 1 : 0;
-    a.bias_ids = p->bias_ids; a.bias_values = p->bias_values; a.n_bias = p->n_bias;
-    return launched(launch_sample_penalty(a, p->dtype, static_cast<hipStream_t>(stream)), "sample_penalty kernel launch");
+    const int rc = fill_penalty_args(p, &a);
+    return rc ? rc : launched(launch_sample_penalty(a, p->dtype, static_cast<hipStream_t>(stream)), "sample_penalty kernel launch");
+}
+
+int hyd_sample_tokens_constrained(const hyd_sample_penalty_params* p, const hyd_token_dfa* c, void* stream) {
+    if (!c) return hyd_sample_tokens_penalized(p, stream);
+    PenaltyArgs a;
+    const int rc = fill_penalty_args(p, &a);
+    if (rc) return rc;
+    if (!c->allowed || !c->next || !c->state) return fail(HYD_ERR_BAD_ARG, "hyd_token_dfa: allowed / next / state is null");
+    if (c->n_states <= 0) return fail(HYD_ERR_BAD_ARG, "hyd_token_dfa: n_states %d must be > 0", c->n_states);
+    if (c->allowed_stride < (p->n + 31) / 32)
+        return fail(HYD_ERR_BAD_ARG, "hyd_token_dfa: allowed_stride %lld < ceil(n / 32) = %d words", (long long)c->allowed_stride, (p->n + 31) / 32);
+    if (c->next_stride < p->n) return fail(HYD_ERR_BAD_ARG, "hyd_token_dfa: next_stride %lld < n %d", (long long)c->next_stride, p->n);
+    if (misaligned(c->allowed, 4) || misaligned(c->next, 4) || misaligned(c->state, 4))
+        return fail(HYD_ERR_BAD_ARG, "hyd_token_dfa: allowed / next / state is not aligned to its element size");
+    ConstrainArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.allowed = c->allowed; ca.next = c->next; ca.state = c->state;
+    ca.allowed_stride = c->allowed_stride; ca.next_stride = c->next_stride;
+    ca.n_states = c->n_states; ca.advance = c->advance ? 1 : 0;
+    // every penalty neutral (and nothing to append): x = l, so the row keeps the keys of its own width (sample_filter.hip's cost)
+    const bool neutral = p->repetition_penalty == 1.0 && p->frequency_penalty == 0.0 && p->presence_penalty == 0.0 && p->n_bias == 0 && !p->append_out;
+    return launched(launch_sample_constrain(a, ca, neutral, p->dtype, static_cast<hipStream_t>(stream)), "sample_constrain kernel launch");
 }
 
 int hyd_token_bitmap_build(const hyd_token_bitmap_params* p, void* stream) {

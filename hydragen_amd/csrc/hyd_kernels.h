@@ -194,6 +194,14 @@ struct PenaltyArgs {  // sample_penalty.hip: FilterArgs' kernel over penalised l
     int32_t n_bias;
 };
 
+struct ConstrainArgs {  // sample_constrain.hip: the token automaton of hyd_sample_tokens_constrained (hyd_token_dfa)
+    const uint32_t* allowed;  // [n_states, allowed_stride] words
+    const int32_t* next;      // [n_states, next_stride]
+    int32_t* state;           // [rows]
+    int64_t allowed_stride, next_stride;
+    int32_t n_states, advance;
+};
+
 struct BitmapArgs {  // sample_penalty.hip: token ids -> presence bitmap (hyd_token_bitmap_build)
     const int64_t* ids;
     const int64_t* lens;  // may be null
@@ -285,6 +293,7 @@ int launch_swiglu(const SwigluArgs& a, int dtype, hipStream_t s);
 int launch_sample(const SampleArgs& a, int dtype, hipStream_t s);
 int launch_sample_filter(const FilterArgs& a, int dtype, hipStream_t s);  // sample_filter.hip
 int launch_sample_penalty(const PenaltyArgs& a, int dtype, hipStream_t s);     // sample_penalty.hip
+int launch_sample_constrain(const PenaltyArgs& a, const ConstrainArgs& c, bool neutral, int dtype, hipStream_t s);  // sample_constrain.hip
 int launch_token_bitmap(const BitmapArgs& a, hipStream_t s);                     // sample_penalty.hip
 int launch_token_logprob(const TokenLogprobArgs& a, int dtype, hipStream_t s);  // token_logprob.hip
 int launch_stop_update(const StopArgs& a, hipStream_t s);                          // stop_update.hip

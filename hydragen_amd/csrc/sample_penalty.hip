@@ -16,86 +16,9 @@
 //     double from its logit and rounded once to fp32.
 //   * x is an fp32 value even for 16-bit rows: the keys are the fp32 ones and the select runs 4 radix levels.
 // 1024 threads per row as sample_filter.hip; LDS 70.4 KB per workgroup: two rows per CU (160 KB).
-#include "sample_select.h"
+#include "sample_penalty_map.h"  // the map, its tables' prologue and the append: shared with sample_constrain.hip
 
 namespace hyd {
-
-namespace {
-
-constexpr int kCtxWords = 8192;   // context bitmap words kept in LDS: rows of up to 262144 tokens
-constexpr int kSlots = 4096;      // table slots (power of two)
-constexpr int kSlowBits = 32768;  // chunk bits: exact up to 262144 tokens, folded beyond
-constexpr int kEmpty = -1;
-static_assert(HYD_SAMPLE_GEN_MAX + HYD_SAMPLE_BIAS_MAX <= kSlots * 3 / 4, "table load");
-static_assert(HYD_SAMPLE_GEN_MAX < (1 << 16) && HYD_SAMPLE_BIAS_MAX < (1 << 15), "count | (bias position + 1) << 16");
-
-__device__ __forceinline__ uint32_t slot_of(int v) { return ((uint32_t)v * 0x9E3779B1u) >> 20; }  // top 12 bits
-
-struct PenaltyMap {
-    const PenaltyArgs& a;
-    const uint32_t* ctx;   // LDS, or null: read the levels in global memory
-    const uint32_t* slow;  // LDS
-    const int* keys;       // LDS
-    const uint32_t* vals;  // LDS: count | (bias position + 1) << 16
-    int row;
-
-    __device__ __forceinline__ uint32_t ctx_byte(int c) const {
-        if (ctx) return reinterpret_cast<const uint8_t*>(ctx)[c];
-        uint32_t b = 0;
-        for (int l = 0; l < a.n_ctx; ++l)
-            b |= reinterpret_cast<const uint8_t*>(a.ctx[l] + (int64_t)(row / a.ctx_rpg[l]) * a.words)[c];
-        return b;
-    }
-    __device__ __forceinline__ uint32_t find(int v) const {
-        for (uint32_t h = slot_of(v);; h = (h + 1) & (kSlots - 1)) {
-            const int k = keys[h];
-            if (k == v) return vals[h];
-            if (k == kEmpty) return 0;
-        }
-    }
-    // the definition's three steps, in double, one rounding
-    __device__ __forceinline__ float apply(float l, bool in_ctx, uint32_t val) const {
-        const uint32_t cnt = val & 0xffffu, bpos = val >> 16;
-        double x = (double)l;
-        if (in_ctx || cnt) x = x * (x > 0.0 ? a.inv_rep : a.rep);  // (1 / r in double: 2^-53 relative, far below the fp32 rounding)
-        if (cnt) x -= a.freq * (double)cnt + a.pres;
-        if (bpos && bpos <= (uint32_t)a.n_bias) x += (double)a.bias_values[bpos - 1];  // (repeated ids OR their positions)
-        return (float)x;
-    }
-    __device__ __forceinline__ float one(int tok, float l) const {
-        const int c = tok >> 3;
-        const bool in_ctx = (ctx_byte(c) >> (tok & 7)) & 1u;
-        const bool s = (slow[(c & (kSlowBits - 1)) >> 5] >> (c & 31)) & 1u;
-        const uint32_t val = s ? find(tok) : 0u;
-        return (in_ctx || val) ? apply(l, in_ctx, val) : l;
-    }
-};
-
-// 16-bit rows come with 16-bit keys: every key becomes the fp32 one.  fp32 rows: only the touched tokens' keys change.
-template <int DT>
-struct PenaltyMapT : PenaltyMap {
-    __device__ __forceinline__ void chunk(int c, float (&f)[8], uint32_t (&k)[8]) const {
-        const uint32_t cb = ctx_byte(c);
-        const bool s = (slow[(c & (kSlowBits - 1)) >> 5] >> (c & 31)) & 1u;
-        if (cb || s) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const bool in_ctx = (cb >> i) & 1u;
-                const uint32_t val = s ? find(8 * c + i) : 0u;
-                if (in_ctx || val) {
-                    f[i] = apply(f[i], in_ctx, val);
-                    if (DT == HYD_F32) k[i] = key32(__builtin_bit_cast(uint32_t, f[i]));
-                }
-            }
-        }
-        if (DT != HYD_F32) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) k[i] = key32(__builtin_bit_cast(uint32_t, f[i]));
-        }
-    }
-};
-
-}  // namespace
 
 template <int DT>
 __global__ __launch_bounds__(1024) void sample_penalty_kernel(const PenaltyArgs a) {
@@ -105,51 +28,11 @@ __global__ __launch_bounds__(1024) void sample_penalty_kernel(const PenaltyArgs 
     __shared__ uint32_t vals[kSlots];
     const int row = blockIdx.x, t = threadIdx.x;
     const bool ctx_lds = a.words <= kCtxWords;
-
-    // prologue: the row's context bitmap (plain stores: one thread per word), an empty table
-    if (ctx_lds) {
-        for (int w = t; w < a.words; w += kFT) {
-            uint32_t b = 0;
-            for (int l = 0; l < a.n_ctx; ++l) b |= a.ctx[l][(int64_t)(row / a.ctx_rpg[l]) * a.words + w];
-            ctx[w] = b;
-        }
-    }
-    for (int i = t; i < kSlowBits / 32; i += kFT) slow[i] = 0;
-    for (int i = t; i < kSlots; i += kFT) {
-        keys[i] = kEmpty;
-        vals[i] = 0;
-    }
-    __syncthreads();
-    int glen = 0;
-    if (a.gen) {
-        glen = a.gen_len[row];
-        glen = glen < 0 ? 0 : (glen > a.gen_stride ? a.gen_stride : glen);
-    }
-    // generated tokens (count + 1) and bias ids (position + 1 in the high half): ids outside [0, n) are ignored
-    for (int i = t; i < glen + a.n_bias; i += kFT) {
-        const bool is_gen = i < glen;
-        const int64_t v64 = is_gen ? (int64_t)a.gen[(int64_t)row * a.gen_stride + i] : a.bias_ids[i - glen];
-        if (v64 < 0 || v64 >= a.f.n) continue;
-        const int v = (int)v64;
-        uint32_t h = slot_of(v);
-        for (;; h = (h + 1) & (kSlots - 1)) {
-            const int old = atomicCAS(&keys[h], kEmpty, v);
-            if (old == kEmpty || old == v) break;
-        }
-        if (is_gen) atomicAdd(&vals[h], 1u);
-        else atomicOr(&vals[h], (uint32_t)(i - glen + 1) << 16);
-        const int c = v >> 3;
-        atomicOr(&slow[(c & (kSlowBits - 1)) >> 5], 1u << (c & 31));
-    }
-    __syncthreads();
+    penalty_tables(a, row, t, ctx_lds, ctx, slow, keys, vals);
 
     PenaltyMapT<DT> map{{a, ctx_lds ? ctx : nullptr, slow, keys, vals, row}};
     const int tok = sample_row<DT, 32>(a.f, map);
-    if (t == 0 && a.append_out) {  // (every read of gen / gen_len above is behind sample_row's barriers)
-        const int len = a.gen_len[row];
-        if (len >= 0 && len < a.gen_stride) a.gen[(int64_t)row * a.gen_stride + len] = tok;
-        a.gen_len[row] = len + 1;
-    }
+    if (t == 0 && a.append_out) penalty_append(a, row, tok);  // (every read of gen / gen_len above is behind sample_row's barriers)
 }
 
 int launch_sample_penalty(const PenaltyArgs& a, int dtype, hipStream_t s) {

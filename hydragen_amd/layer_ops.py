@@ -162,11 +162,13 @@ def token_bitmap(ids: Tensor, lens: Optional[Tensor], n: int, out: Optional[Tens
 
 
 def sample_tokens_penalized(logits: Tensor, temperature: float, key: Optional[tuple] = None, *, penalties: Penalties,
-                            top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None):
+                            top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None,
+                            constraint: Optional[tuple] = None):
     """hyd_sample_tokens_penalized, one launch whatever the penalties are (neutral ones included): ([B, 1] int64 tokens, [B] fp32
     log-probs under softmax(penalised logits), [B] int32 number of kept tokens).  hydragen_amd/sampling.py states the
     definition.  Nothing of size [B, V] is allocated and nothing synchronises; the bias list must already be checked
-    (sampling.check_penalties) and on the device."""
+    (sampling.check_penalties) and on the device.  constraint = (dfa, state int32 [B], advance): hyd_sample_tokens_constrained
+    instead -- the same launch behind the automaton's mask (sample_tokens_constrained)."""
     _require_gpu(logits)
     lib = _lib.load()
     assert logits.ndim == 2 and logits.stride(1) == 1 and logits.shape[1] > 0
@@ -216,13 +218,37 @@ def sample_tokens_penalized(logits: Tensor, temperature: float, key: Optional[tu
     p.seed, p.offset, p.rows, p.n = seed, offset, rows, n
     p.dtype = _HYD_F32 if logits.dtype == torch.float32 else _dtype_code(logits)
     p.temperature = float(temperature)
+    if constraint is not None:
+        dfa, state, advance = constraint
+        c = _lib.TokenDfa()
+        c.allowed, c.next, c.state = dfa.allowed.data_ptr(), dfa.next.data_ptr(), state.data_ptr()
+        c.allowed_stride, c.next_stride, c.n_states, c.advance = dfa.allowed.shape[1], n, dfa.next.shape[0], int(bool(advance))
+        _lib.check(lib.hyd_sample_tokens_constrained(C.byref(p), C.byref(c), _stream()))
+        return out, logprobs, kept
     _lib.check(lib.hyd_sample_tokens_penalized(C.byref(p), _stream()))
     return out, logprobs, kept
 
 
+def sample_tokens_constrained(logits: Tensor, temperature: float, key: Optional[tuple] = None, *, constraint: tuple,
+                              penalties: Optional[Penalties] = None, top_k: Optional[int] = None, top_p: Optional[float] = None,
+                              min_p: Optional[float] = None):
+    """hyd_sample_tokens_constrained, one launch: sample_tokens_penalized (penalties None: neutral ones, which is
+    sample_tokens_filtered) on the logits with the tokens that a row's automaton state does not allow at -inf -- bit for bit --
+    without a [B, V] mask.  constraint = (dfa, state, advance): dfa a constraint.TokenDFA on the logits' device, state int32 [B]
+    on the device (rows outside [0, S) are unconstrained); advance: state[row] = next[state[row], token] after the draw, in place.
+    hydragen_amd/sampling.py states the definition.  Returns ([B, 1] int64 tokens, [B] fp32 log-probs of the constrained
+    distribution, [B] int32 kept counts)."""
+    dfa, state, _ = constraint
+    sampling.check_constraint(dfa, logits.shape[-1], logits.shape[0], state)
+    if dfa.next.device != logits.device or state.device != logits.device:
+        raise ValueError(f"constraint: the automaton is on {dfa.next.device}, the state on {state.device}, the logits on {logits.device}")
+    return sample_tokens_penalized(logits, temperature, key, penalties=Penalties() if penalties is None else penalties, top_k=top_k,
+                                   top_p=top_p, min_p=min_p, constraint=constraint)
+
+
 def sample_tokens(logits: Tensor, temperature: float, key: Optional[tuple] = None, *, top_k: Optional[int] = None,
                   top_p: Optional[float] = None, min_p: Optional[float] = None, return_logprobs: bool = False,
-                  penalties: Optional[Penalties] = None):
+                  penalties: Optional[Penalties] = None, constraint: Optional[tuple] = None):
     """[B, V] logits (fp16 / bf16 / fp32, rows contiguous) -> [B, 1] int64 tokens drawn from softmax(logits / temperature)
     (temperature 0: argmax) in one kernel.  top_k / top_p / min_p cut the UNSCALED softmax(logits) first (hydragen_amd/
     sampling.py states the rules); return_logprobs also returns the [B, 1] fp32 log softmax(logits) of each drawn token.
@@ -230,7 +256,34 @@ def sample_tokens(logits: Tensor, temperature: float, key: Optional[tuple] = Non
     noise (one key per call either way).  penalties (a Penalties with something switched on): the cuts, the draw and the log-prob
     act on the penalised logits (hydragen_amd/sampling.py), in one launch of hyd_sample_tokens_penalized; the log-prob is then
     log softmax(penalised logits), the distribution the draw's policy is defined by.  CPU logits with penalties: the float64
-    definition and torch (no HIP kernel takes CPU tensors)."""
+    definition and torch (no HIP kernel takes CPU tensors).  constraint = (dfa, state, advance) (sample_tokens_constrained): every
+    rule above acts on the logits behind the automaton's mask, in one launch of hyd_sample_tokens_constrained, which also
+    advances `state` in place; CPU logits take the torch definition.  constraint None: exactly the calls made without it."""
+    if constraint is not None:
+        dfa, state, advance = constraint
+        pen = penalties if penalties is not None and penalties.active() else None
+        if not logits.is_cuda:
+            xp = logits if pen is None else pen.apply(logits)
+            xc = sampling.constrain_logits(xp, dfa, state)
+            keep = sampling.kept_mask(xc, top_k, top_p, min_p)
+            x = xc.masked_fill(~keep, -float("inf"))
+            drawn = keep.any(-1)
+            if temperature == 0:
+                tok = x.argmax(-1, keepdim=True)
+            else:
+                pr = torch.softmax(x.double() / temperature, -1)
+                tok = torch.multinomial(torch.where(drawn[:, None], pr, torch.ones_like(pr)), 1)
+            tok = torch.where(drawn[:, None], tok, torch.zeros_like(tok))
+            lp = torch.log_softmax(xc.double(), -1).gather(1, tok).float()
+            lp = torch.where(drawn[:, None], lp, torch.full_like(lp, float("nan")))
+            if advance:
+                state.copy_(sampling.advance_state(dfa, state, tok, drawn))
+            if pen is not None and pen.append:
+                pen.push(tok)
+            return (tok, lp) if return_logprobs else tok
+        tok, lp, _ = sample_tokens_constrained(logits, temperature, key, constraint=constraint, penalties=pen, top_k=top_k,
+                                               top_p=top_p, min_p=min_p)
+        return (tok, lp[:, None]) if return_logprobs else tok
     if penalties is not None and penalties.active():
         if not logits.is_cuda:
             xp = penalties.apply(logits)

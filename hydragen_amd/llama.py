@@ -918,13 +918,31 @@ class HydragenLlamaForCausalLM(nn.Module):
         return logits.masked_fill(remove.scatter(1, sorted_indices, remove), filter_value)
 
     def sample_from_logits(self, logits, temperature, num_samples=1, top_p=None, top_k=None, min_p=None,
-                           return_logprobs=False, penalties=None):
+                           return_logprobs=False, penalties=None, constraint=None):
         """Tokens [B, num_samples] (and, with return_logprobs, their fp32 log softmax(logits) [B, num_samples]).  The cuts
         act on the unscaled softmax(logits), before the temperature (hydragen_amd/sampling.py).  penalties (a
         layer_ops.Penalties with something switched on): cuts, draw and log-prob act on the penalised logits instead; the
-        drawn tokens are appended to its list when it says so."""
+        drawn tokens are appended to its list when it says so.  constraint = (dfa, state int32 [B * num_samples]): every rule
+        acts on the logits behind the automaton's mask and `state` advances in place (hyd_sample_tokens_constrained; the
+        torch definition for CPU logits and for num_samples > 1)."""
         filtered = sampling.filters_active(top_k, top_p, min_p)
         eligible = logits.is_cuda and logits.ndim == 2 and num_samples == 1 and logits.stride(-1) == 1 and temperature >= 0
+        if constraint is not None:
+            dfa, state = constraint
+            pen = penalties if penalties is not None and penalties.active() else None
+            if num_samples == 1 and (not logits.is_cuda or (eligible and (pen is None or self.fused_sampling_penalties))):
+                # one HIP kernel: mask, penalties, cuts, draw, log-prob, the append and the state update
+                return layer_ops.sample_tokens(logits, temperature, top_k=top_k, top_p=top_p, min_p=min_p,
+                                               return_logprobs=return_logprobs, penalties=pen, constraint=(dfa, state, True))
+            # the definition in torch ([B, V] tables), then the paths below on the masked logits, one sample per row
+            x = logits if pen is None else pen.apply(logits, num_samples).float()
+            x = sampling.constrain_logits(x.repeat_interleave(num_samples, 0), dfa, state)
+            tok, lp = self.sample_from_logits(x, temperature, 1, top_p, top_k, min_p, return_logprobs=True)
+            state.copy_(sampling.advance_state(dfa, state, tok, ~torch.isnan(lp.reshape(-1))))
+            if pen is not None and pen.append and num_samples == 1:
+                pen.push(tok)
+            tok, lp = tok.reshape(-1, num_samples), lp.reshape(-1, num_samples)
+            return (tok, lp) if return_logprobs else tok
         if penalties is not None and penalties.active():
             if eligible and self.fused_sampling_penalties:
                 # one HIP kernel: penalties, cuts, draw, log-prob and the append to the rows' generated tokens
@@ -1098,7 +1116,8 @@ class HydragenLlamaForCausalLM(nn.Module):
                  token_overrides: Optional[Tensor] = None, top_k: Optional[int] = None, min_p: Optional[float] = None,
                  return_logprobs: bool = False, top_logprobs: int = 0, repetition_penalty: Optional[float] = None,
                  presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None, logit_bias=None,
-                 stop=None, pad_token_id: Optional[int] = None, include_stop: bool = False, return_finish: bool = False):
+                 stop=None, pad_token_id: Optional[int] = None, include_stop: bool = False, return_finish: bool = False,
+                 constraint=None, constraint_state: Optional[Tensor] = None, return_constraint_state: bool = False):
         """Sampling: top_k / top_p / min_p cut the UNSCALED softmax(logits) (the reference's top-p order; HF applies the
         temperature first), then a token is drawn from softmax(logits / temperature) over the kept tokens.  Returns the
         tokens [B, generated]; return_logits adds the per-step fp32 logits, return_logprobs the fp32 [B, generated]
@@ -1128,9 +1147,27 @@ class HydragenLlamaForCausalLM(nn.Module):
         (int32 [B] each; reason 0 = ran to max_new_tokens, 1 = EOS, 2 = stop sequence) as the last return value.  With
         return_logprobs, entries at or past a row's length are 0.0; with top_logprobs, id -1 / -inf; the return_logits rows of a
         finished sequence past its length are unspecified.  Penalties keep working (what a finished row draws is ignored).
-        token_overrides cannot be combined with these arguments."""
+        token_overrides cannot be combined with these arguments.
+        Constrained decoding (hydragen_amd/sampling.py states the rules, hydragen_amd/constraint.py builds the automata):
+        constraint = a constraint.TokenDFA over the model's vocabulary restricts what every row may emit by what it has emitted so
+        far; constraint_state = the rows' start states, int [leaf batch] (repeated for num_return_sequences) or [batch], default 0;
+        a state outside the automaton leaves a row unconstrained.  The states live on the device for the whole call and advance
+        inside the sampling launch (hyd_sample_tokens_constrained; the token drawn from the prefill logits included), so there is
+        no [B, V] mask and no host synchronisation.  It composes with the cuts, the penalties and the stop conditions: with
+        TokenDFA.from_choices / from_regex(eos=ids) and eos_token_id=ids a row ends through the stop kernel once its output is
+        complete.  return_logprobs reports the CONSTRAINED distribution (the same rule as for penalties); return_logits and
+        top_logprobs stay raw.  return_constraint_state appends the final int32 [B] states as the last return value.  Not with
+        token_overrides.  With constraint=None, generate() runs exactly the launches it runs without these arguments."""
         if not self.kv_cache_allocated:
             raise RuntimeError("call setup_caches() before generate()")
+        if constraint is None and (constraint_state is not None or return_constraint_state):
+            raise ValueError("constraint_state / return_constraint_state need constraint=")
+        if constraint is not None:
+            if token_overrides is not None:
+                raise ValueError("constraint cannot be combined with token_overrides (teacher forcing draws nothing to constrain)")
+            sampling.check_constraint(constraint, self.vocab_size)
+            if constraint.next.device != self.lm_head.weight.device:
+                constraint = constraint.to(self.lm_head.weight.device)
         stop_spec = None
         if isinstance(eos_token_id, (list, tuple)) or stop is not None or pad_token_id is not None or return_finish:
             if token_overrides is not None:
@@ -1189,14 +1226,51 @@ class HydragenLlamaForCausalLM(nn.Module):
             if penalised:
                 samp["penalties"] = self._penalties(batch, unique, num_return_sequences, max_new_tokens, repetition_penalty,
                                                     presence_penalty, frequency_penalty, logit_bias, counted)
-            return self._decode(logits[:, -1], unique, num_return_sequences, max_new_tokens, samp,
-                                eos_token_id, return_logits, token_overrides, return_logprobs, top_n, stop_spec, return_finish)
+            if constraint is None:
+                return self._decode(logits[:, -1], unique, num_return_sequences, max_new_tokens, samp,
+                                    eos_token_id, return_logits, token_overrides, return_logprobs, top_n, stop_spec, return_finish)
+            state = self._constraint_state(constraint_state, leaf_batch, num_return_sequences)
+            samp["constraint"] = (constraint, state)
+            ret = self._decode(logits[:, -1], unique, num_return_sequences, max_new_tokens, samp,
+                               eos_token_id, return_logits, token_overrides, return_logprobs, top_n, stop_spec, return_finish)
+            if return_constraint_state:
+                ret = (ret if isinstance(ret, tuple) else (ret,)) + (state,)
+            return ret
         finally:
             self._scale_windows("close_scale_window", write=False)  # (a call that raised before its first write)
             if shared_cache_op == SharedCacheOp.PRESERVE:
                 self.truncate_shared_caches(levels_before)
             self.model.set_disable_hydragen(False)
             self.model.set_disable_attention(False)
+
+    def _constraint_state(self, constraint_state, leaf_batch, fan):
+        """The call's automaton states, int32 [batch] on the device: the given start states ([leaf batch], repeated per sample, or
+        [batch]), default 0."""
+        dev = self.lm_head.weight.device
+        batch = leaf_batch * fan
+        if constraint_state is None:
+            return torch.zeros((batch,), dtype=torch.int32, device=dev)
+        st = torch.as_tensor(constraint_state)
+        if st.ndim != 1 or st.dtype.is_floating_point or st.dtype == torch.bool or st.shape[0] not in (leaf_batch, batch):
+            raise ValueError(f"constraint_state must hold {leaf_batch} or {batch} integer states, got {tuple(st.shape)} {st.dtype}")
+        st = st.to(device=dev, dtype=torch.int32)
+        return (st.repeat_interleave(fan, 0) if st.shape[0] != batch else st.clone()).contiguous()
+
+    @torch.no_grad()
+    def choose(self, input_ids, choices, eos_token_id: int, seq_lens=None, temperature: float = 0.0, **kw):
+        """Multiple choice under shared prompts (the lm-eval-style call): every row answers with one of `choices` (token-id
+        sequences; a list of lists of them gives row b of the leaf batch its own set, choices[b]) followed by eos_token_id.
+        A thin wrapper over generate(constraint=TokenDFA.from_choices(...), eos_token_id=[eos_token_id]); kw goes to generate.
+        Returns (choice index int64 [B] -- within the row's set, -1: not finished --, tokens [B, generated])."""
+        from .constraint import TokenDFA
+
+        dfa = TokenDFA.from_choices(choices, self.vocab_size, eos=[int(eos_token_id)], on_accept="eos")
+        groups = dfa.meta["groups"]
+        start = torch.tensor(dfa.start_states, dtype=torch.int32) if len(groups) > 1 else None
+        longest = max(len(c) for g in groups for c in g) + 1
+        out = self.generate(input_ids, seq_lens=seq_lens, max_new_tokens=longest, temperature=temperature,
+                            eos_token_id=[int(eos_token_id)], constraint=dfa, constraint_state=start, return_constraint_state=True, **kw)
+        return dfa.choice_of(out[-1]), out[0]
 
     def _penalties(self, batch, unique, fan, max_new_tokens, repetition_penalty, presence_penalty, frequency_penalty, logit_bias, counted):
         """The call's layer_ops.Penalties: the used shared levels' bitmaps (one row per shared sequence, read by its

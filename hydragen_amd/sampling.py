@@ -208,3 +208,70 @@ def penalize_logits(logits: Tensor, repetition_penalty: Optional[float] = None, 
     if bias is not None:
         x[:, bias[0]] += bias[1].double()
     return x
+
+
+# ---- token automata ---------------------------------------------------------------------------------------------------------
+# Constrained decoding: the definition `hyd_sample_tokens_constrained` (csrc/sample_constrain.hip) implements.  A token
+# automaton over n tokens with S states is one table next int32 [S, n] (hydragen_amd/constraint.py builds them):
+#   next[s, v] >= 0           token v is allowed in state s and leads to that state (< S);
+#   next[s, v] == DFA_REJECT  v is not allowed in s;
+#   next[s, v] == DFA_FREE    v is allowed, and the row is unconstrained from then on;
+# and the bitmap allowed int32 [S, ceil(n / 32)] derived from it: bit v % 32 of word v // 32 is set iff next[s, v] != DFA_REJECT
+# (the bit layout of token_bitmap_reference).  A row whose state lies outside [0, S) is unconstrained: its logits are taken as
+# they are and its state does not change.  For a constrained row every sampling rule above (penalties, bias, cuts, draw,
+# log-prob, kept) acts on the row with the logits of the tokens that are not allowed replaced by -inf; bits at positions >= n
+# are ignored.  After the draw state[row] = next[state[row], token]; a row without any valid logit (token 0, kept 0, NaN
+# log-prob) keeps its state.  A `dfa` below is anything with .next, .allowed, .num_states and .vocab_size (constraint.TokenDFA).
+DFA_REJECT = -1  # HYD_DFA_REJECT
+DFA_FREE = -2    # HYD_DFA_FREE
+
+
+def check_constraint(dfa, vocab_size: int, batch: Optional[int] = None, state: Optional[Tensor] = None) -> None:
+    """Host validation of an automaton against the logits' width (shapes and dtypes only: nothing is read from the device)."""
+    nxt, allowed = dfa.next, dfa.allowed
+    if nxt.ndim != 2 or nxt.dtype != torch.int32 or nxt.shape[0] <= 0 or not nxt.is_contiguous():
+        raise ValueError(f"constraint: next must be a contiguous int32 [S, n] with S > 0, got {tuple(nxt.shape)} {nxt.dtype}")
+    if nxt.shape[1] != vocab_size:
+        raise ValueError(f"constraint: the automaton is over {nxt.shape[1]} tokens, the logits over {vocab_size}")
+    words = (vocab_size + 31) // 32
+    if allowed.shape != (nxt.shape[0], words) or allowed.dtype != torch.int32 or not allowed.is_contiguous() or allowed.device != nxt.device:
+        raise ValueError(f"constraint: allowed must be a contiguous int32 [{nxt.shape[0]}, {words}] on {nxt.device}, got "
+                         f"{tuple(allowed.shape)} {allowed.dtype} on {allowed.device}")
+    if state is not None:
+        if state.dtype != torch.int32 or state.ndim != 1 or not state.is_contiguous() or (batch is not None and state.shape[0] != batch):
+            raise ValueError(f"constraint: state must be a contiguous int32 [{'B' if batch is None else batch}], got "
+                             f"{tuple(state.shape)} {state.dtype}")
+
+
+@torch.no_grad()
+def allowed_mask(dfa, state: Tensor) -> Tensor:
+    """[B, n] bool: what each row may emit, read from the BITMAP (what the kernel reads); unconstrained rows: all True."""
+    S, n = dfa.next.shape
+    st = state.long().to(dfa.allowed.device)
+    on = (st >= 0) & (st < S)
+    words = dfa.allowed[torch.where(on, st, torch.zeros_like(st))].long()  # [B, words]
+    shifts = torch.arange(32, device=words.device, dtype=torch.int64)
+    bits = ((words[:, :, None] >> shifts) & 1).bool().reshape(words.shape[0], -1)[:, :n]
+    return bits | ~on[:, None]
+
+
+@torch.no_grad()
+def constrain_logits(logits: Tensor, dfa, state: Tensor) -> Tensor:
+    """`logits` [B, n] with the tokens a row's state does not allow set to -inf, in the input dtype, on the logits' device."""
+    check_constraint(dfa, logits.shape[-1], logits.shape[0])
+    return logits.masked_fill(~allowed_mask(dfa, state).to(logits.device), -math.inf)
+
+
+@torch.no_grad()
+def advance_state(dfa, state: Tensor, tokens: Tensor, drawn: Optional[Tensor] = None) -> Tensor:
+    """The states after `tokens` ([B] or [B, 1]): next[state, token] for constrained rows, the state itself for unconstrained
+    ones and for rows where nothing was drawn (drawn [B] bool, None = every row drew: a row without a valid logit reports
+    token 0 and keeps its state).  A REJECT or FREE entry leaves the row unconstrained.  Returns int32 [B] on the state's device."""
+    S = dfa.next.shape[0]
+    st = state.long()
+    tok = tokens.reshape(-1).long().to(st.device)
+    on = (st >= 0) & (st < S)
+    if drawn is not None:
+        on = on & drawn.reshape(-1).bool().to(st.device)
+    nxt = dfa.next.to(st.device)[torch.where(on, st, torch.zeros_like(st)), tok].long()
+    return torch.where(on, nxt, st).to(torch.int32)

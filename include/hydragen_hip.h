@@ -443,6 +443,42 @@ typedef struct hyd_token_bitmap_params {
 
 HYD_API int hyd_token_bitmap_build(const hyd_token_bitmap_params* p, void* stream);
 
+/* hyd_sample_tokens_penalized under a token automaton: what a row may emit depends on what it has emitted so far, decided inside
+ * the same single launch.  A token automaton over n tokens with n_states states is one table next [n_states, n] of int32:
+ *   next[s, v] >= 0               token v is allowed in state s and leads to that state (< n_states);
+ *   next[s, v] == HYD_DFA_REJECT  v is not allowed in s;
+ *   next[s, v] == HYD_DFA_FREE    v is allowed, and the row is unconstrained from then on;
+ * and the bitmap allowed [n_states, ceil(n / 32)] derived from it: bit v % 32 of word v / 32 of row s is set iff next[s, v] !=
+ * HYD_DFA_REJECT (hyd_token_bitmap's bit layout; one row per STATE, shared by every batch row in that state -- nothing of size
+ * [rows, n] exists).  state[row] is read on the device at launch time.  A row whose state lies outside [0, n_states) is
+ * unconstrained: its logits are taken as they are and its state does not change.  For a constrained row every rule of
+ * hyd_sample_tokens_penalized (penalties, bias, cuts, draw, log-prob, kept) acts on the row with the logits of the tokens whose
+ * bit is clear replaced by -inf; bits at positions >= n are ignored.  -inf is absorbing under every penalty rule and never kept,
+ * so tokens, kept counts and log-probs are, bit for bit, those of hyd_sample_tokens_penalized (with every penalty neutral: of
+ * hyd_sample_tokens_filtered) on logits filled with -inf at the tokens that are not allowed, for the same (seed, offset).
+ * advance != 0: after the draw state[row] = next[state[row], token].  A row without any valid logit gives token 0, kept 0 and a
+ * NaN log-prob, as there, and keeps its state.  The kernel reads `allowed` for the mask and `next` for the one entry of the
+ * drawn token: a pair that does not agree is the caller's responsibility -- a token drawn into a HYD_DFA_REJECT entry leaves
+ * the row unconstrained (state -1), like HYD_DFA_FREE, and so does any entry outside [0, n_states).  No indexing ever uses a
+ * state outside [0, n_states).
+ * c == NULL is exactly hyd_sample_tokens_penalized(p).  The call is capture-safe: no allocation, no synchronisation, no
+ * workspace, no environment variable; state is the only memory written besides what hyd_sample_tokens_penalized writes.
+ * HYD_ERR_BAD_ARG: everything hyd_sample_tokens_penalized refuses (HYD_ERR_UNSUPPORTED where it says so), a null allowed /
+ * next / state, n_states <= 0, allowed_stride < ceil(n / 32), next_stride < n, pointers not aligned to 4 bytes. */
+#define HYD_DFA_REJECT (-1)
+#define HYD_DFA_FREE (-2)
+typedef struct hyd_token_dfa {
+    const uint32_t* allowed;   /* [n_states, allowed_stride] words                                      */
+    const int32_t*  next;      /* [n_states, next_stride]                                               */
+    int32_t*        state;     /* [rows] device, read at launch time                                    */
+    int64_t allowed_stride;    /* words,    >= ceil(n / 32)                                             */
+    int64_t next_stride;       /* elements, >= n                                                        */
+    int32_t n_states;
+    int32_t advance;           /* != 0: state[row] = next[state[row], token] after the draw             */
+} hyd_token_dfa;
+
+HYD_API int hyd_sample_tokens_constrained(const hyd_sample_penalty_params* p, const hyd_token_dfa* c, void* stream);
+
 /* Log-probabilities of GIVEN tokens (scoring, teacher forcing) and the top-N alternatives of every row.  For one row l (length n)
  * and its target token t, with the valid logits those that are neither NaN nor -inf and m = their max:
  *   - logprobs[row] = l_t - m - ln sum_j exp(l_j - m) over the valid logits (fp32), with hyd_sample_tokens_filtered's fixed-point
