@@ -91,6 +91,32 @@ def _next_sample_key(device: torch.device):
     return seed, offset
 
 
+def _draw_outputs(logits: Tensor, stats: bool) -> tuple:
+    """What every sampling entry point starts with: the rows it takes, and its outputs -- ([B, 1] int64 tokens,) and, with
+    `stats`, ([B] fp32 log-probs, [B] int32 kept counts) behind them."""
+    _require_gpu(logits)
+    _lib.load()
+    assert logits.ndim == 2 and logits.stride(1) == 1 and logits.shape[1] > 0
+    rows, dev = logits.shape[0], logits.device
+    out = torch.empty((rows, 1), dtype=torch.int64, device=dev)
+    if not stats:
+        return (out,)
+    return out, torch.empty((rows,), dtype=torch.float32, device=dev), torch.empty((rows,), dtype=torch.int32, device=dev)
+
+
+def _fill_rows(p, logits: Tensor, outs: tuple, temperature: float, key: Optional[tuple], top_k=None, top_p=None, min_p=None):
+    """The logits-row header the three sampling structs share, and the cut fields of the two whose outputs have stats.  It takes
+    the call's key, so it comes after every check: a rejected call leaves the generator as it was."""
+    rows, n = logits.shape
+    p.logits, p.out, p.row_stride = logits.data_ptr(), outs[0].data_ptr(), logits.stride(0) if rows > 1 else n
+    p.seed, p.offset = key if key is not None else _next_sample_key(logits.device)
+    p.rows, p.n, p.temperature = rows, n, float(temperature)
+    p.dtype = _HYD_F32 if logits.dtype == torch.float32 else _dtype_code(logits)
+    if len(outs) > 1:
+        p.logprobs, p.kept = outs[1].data_ptr(), outs[2].data_ptr()
+        p.top_k, p.top_p, p.min_p = int(top_k or 0), 1.0 if top_p is None else float(top_p), float(min_p or 0.0)
+
+
 @dataclass
 class Penalties:
     """What sampling.py's penalty definition needs for a batch of rows: the scalars, the bias list as (ids int64 [K], values fp32
@@ -169,20 +195,14 @@ def sample_tokens_penalized(logits: Tensor, temperature: float, key: Optional[tu
     definition.  Nothing of size [B, V] is allocated and nothing synchronises; the bias list must already be checked
     (sampling.check_penalties) and on the device.  constraint = (dfa, state int32 [B], advance): hyd_sample_tokens_constrained
     instead -- the same launch behind the automaton's mask (sample_tokens_constrained)."""
-    _require_gpu(logits)
-    lib = _lib.load()
-    assert logits.ndim == 2 and logits.stride(1) == 1 and logits.shape[1] > 0
+    outs = _draw_outputs(logits, stats=True)
     rows, n = logits.shape
-    dev = logits.device
-    out = torch.empty((rows, 1), dtype=torch.int64, device=dev)
-    logprobs = torch.empty((rows,), dtype=torch.float32, device=dev)
-    kept = torch.empty((rows,), dtype=torch.int32, device=dev)
+    dev, pen = logits.device, penalties
     if rows == 0:
-        return out, logprobs, kept
+        return outs
     check_filters(top_k, top_p, min_p)
-    pen = penalties
-    words = (n + 31) // 32
     p = _lib.SamplePenaltyParams()
+    words = (n + 31) // 32
     if len(pen.context) > _lib.SAMPLE_MAX_CONTEXT:
         raise ValueError(f"{len(pen.context)} context bitmaps: at most {_lib.SAMPLE_MAX_CONTEXT}")
     for i, (bits, rpg) in enumerate(pen.context):
@@ -211,22 +231,16 @@ def sample_tokens_penalized(logits: Tensor, temperature: float, key: Optional[tu
         p.bias_ids, p.bias_values, p.n_bias = ids.data_ptr(), values.data_ptr(), ids.numel()
     p.repetition_penalty = 1.0 if pen.repetition_penalty is None else float(pen.repetition_penalty)
     p.frequency_penalty, p.presence_penalty = float(pen.frequency_penalty or 0.0), float(pen.presence_penalty or 0.0)
-    p.top_k, p.top_p, p.min_p = int(top_k or 0), 1.0 if top_p is None else float(top_p), float(min_p or 0.0)
-    seed, offset = key if key is not None else _next_sample_key(dev)
-    p.logits, p.out, p.logprobs, p.kept = logits.data_ptr(), out.data_ptr(), logprobs.data_ptr(), kept.data_ptr()
-    p.row_stride = logits.stride(0) if rows > 1 else n
-    p.seed, p.offset, p.rows, p.n = seed, offset, rows, n
-    p.dtype = _HYD_F32 if logits.dtype == torch.float32 else _dtype_code(logits)
-    p.temperature = float(temperature)
-    if constraint is not None:
-        dfa, state, advance = constraint
-        c = _lib.TokenDfa()
-        c.allowed, c.next, c.state = dfa.allowed.data_ptr(), dfa.next.data_ptr(), state.data_ptr()
-        c.allowed_stride, c.next_stride, c.n_states, c.advance = dfa.allowed.shape[1], n, dfa.next.shape[0], int(bool(advance))
-        _lib.check(lib.hyd_sample_tokens_constrained(C.byref(p), C.byref(c), _stream()))
-        return out, logprobs, kept
-    _lib.check(lib.hyd_sample_tokens_penalized(C.byref(p), _stream()))
-    return out, logprobs, kept
+    _fill_rows(p, logits, outs, temperature, key, top_k, top_p, min_p)
+    if constraint is None:
+        _lib.check(_lib.load().hyd_sample_tokens_penalized(C.byref(p), _stream()))
+        return outs
+    dfa, state, advance = constraint
+    c = _lib.TokenDfa()
+    c.allowed, c.next, c.state = dfa.allowed.data_ptr(), dfa.next.data_ptr(), state.data_ptr()
+    c.allowed_stride, c.next_stride, c.n_states, c.advance = dfa.allowed.shape[1], n, dfa.next.shape[0], int(bool(advance))
+    _lib.check(_lib.load().hyd_sample_tokens_constrained(C.byref(p), C.byref(c), _stream()))
+    return outs
 
 
 def sample_tokens_constrained(logits: Tensor, temperature: float, key: Optional[tuple] = None, *, constraint: tuple,
@@ -252,94 +266,52 @@ def sample_tokens(logits: Tensor, temperature: float, key: Optional[tuple] = Non
     """[B, V] logits (fp16 / bf16 / fp32, rows contiguous) -> [B, 1] int64 tokens drawn from softmax(logits / temperature)
     (temperature 0: argmax) in one kernel.  top_k / top_p / min_p cut the UNSCALED softmax(logits) first (hydragen_amd/
     sampling.py states the rules); return_logprobs also returns the [B, 1] fp32 log softmax(logits) of each drawn token.
-    With no cut and no log-prob this is hyd_sample_tokens; otherwise hyd_sample_tokens_filtered, whose draw uses the same
-    noise (one key per call either way).  penalties (a Penalties with something switched on): the cuts, the draw and the log-prob
-    act on the penalised logits (hydragen_amd/sampling.py), in one launch of hyd_sample_tokens_penalized; the log-prob is then
-    log softmax(penalised logits), the distribution the draw's policy is defined by.  CPU logits with penalties: the float64
-    definition and torch (no HIP kernel takes CPU tensors).  constraint = (dfa, state, advance) (sample_tokens_constrained): every
-    rule above acts on the logits behind the automaton's mask, in one launch of hyd_sample_tokens_constrained, which also
-    advances `state` in place; CPU logits take the torch definition.  constraint None: exactly the calls made without it."""
-    if constraint is not None:
-        dfa, state, advance = constraint
-        pen = penalties if penalties is not None and penalties.active() else None
-        if not logits.is_cuda:
-            xp = logits if pen is None else pen.apply(logits)
-            xc = sampling.constrain_logits(xp, dfa, state)
-            keep = sampling.kept_mask(xc, top_k, top_p, min_p)
-            x = xc.masked_fill(~keep, -float("inf"))
-            drawn = keep.any(-1)
-            if temperature == 0:
-                tok = x.argmax(-1, keepdim=True)
-            else:
-                pr = torch.softmax(x.double() / temperature, -1)
-                tok = torch.multinomial(torch.where(drawn[:, None], pr, torch.ones_like(pr)), 1)
-            tok = torch.where(drawn[:, None], tok, torch.zeros_like(tok))
-            lp = torch.log_softmax(xc.double(), -1).gather(1, tok).float()
-            lp = torch.where(drawn[:, None], lp, torch.full_like(lp, float("nan")))
-            if advance:
-                state.copy_(sampling.advance_state(dfa, state, tok, drawn))
-            if pen is not None and pen.append:
-                pen.push(tok)
-            return (tok, lp) if return_logprobs else tok
-        tok, lp, _ = sample_tokens_constrained(logits, temperature, key, constraint=constraint, penalties=pen, top_k=top_k,
-                                               top_p=top_p, min_p=min_p)
-        return (tok, lp[:, None]) if return_logprobs else tok
-    if penalties is not None and penalties.active():
-        if not logits.is_cuda:
-            xp = penalties.apply(logits)
-            x = xp.masked_fill(~sampling.kept_mask(xp, top_k, top_p, min_p), -float("inf"))
-            if temperature == 0:
-                tok = x.argmax(-1, keepdim=True)
-            else:
-                tok = torch.multinomial(torch.softmax(x / temperature, -1), 1)
-            lp = torch.log_softmax(xp, -1).gather(1, tok).float()
-            if penalties.append:
-                penalties.push(tok)
-            return (tok, lp) if return_logprobs else tok
-        tok, lp, _ = sample_tokens_penalized(logits, temperature, key, penalties=penalties, top_k=top_k, top_p=top_p, min_p=min_p)
-        return (tok, lp[:, None]) if return_logprobs else tok
-    if not filters_active(top_k, top_p, min_p) and not return_logprobs:
-        _require_gpu(logits)
-        lib = _lib.load()
-        assert logits.ndim == 2 and logits.stride(1) == 1 and logits.shape[1] > 0
-        out = torch.empty((logits.shape[0], 1), dtype=torch.int64, device=logits.device)
-        if logits.shape[0] == 0:
-            return out
-        seed, offset = key if key is not None else _next_sample_key(logits.device)
-        p = _lib.SampleParams()
-        p.logits, p.out, p.row_stride = logits.data_ptr(), out.data_ptr(), logits.stride(0) if logits.shape[0] > 1 else logits.shape[1]
-        p.seed, p.offset, p.rows, p.n = seed, offset, logits.shape[0], logits.shape[1]
-        p.dtype = _HYD_F32 if logits.dtype == torch.float32 else _dtype_code(logits)
-        p.temperature = float(temperature)
-        _lib.check(lib.hyd_sample_tokens(C.byref(p), _stream()))
-        return out
-    tok, lp, _ = sample_tokens_filtered(logits, temperature, key, top_k=top_k, top_p=top_p, min_p=min_p)
+    Which entry point that is, sampling.sample_route says (these rows count as eligible: the kernels check their layout):
+    hyd_sample_tokens with no cut and no log-prob; otherwise hyd_sample_tokens_filtered, whose draw uses the same noise (one
+    key per call either way).  penalties (a Penalties with something switched on): hyd_sample_tokens_penalized; the log-prob is
+    then log softmax(penalised logits), the distribution the draw's policy is defined by.  constraint = (dfa, state, advance)
+    (sample_tokens_constrained): hyd_sample_tokens_constrained, which also advances `state` in place.  CPU logits with
+    penalties or a constraint: their float64 definition in torch (no HIP kernel takes CPU tensors).  constraint None or
+    neutral penalties: exactly the calls made without them."""
+    pen = penalties if penalties is not None and penalties.active() else None
+    cuts = dict(top_k=top_k, top_p=top_p, min_p=min_p)
+    draw = sampling.sample_route(logits.is_cuda, True, True, 1, constraint is not None, pen is not None,
+                                 filters_active(top_k, top_p, min_p), return_logprobs).draw
+    if draw == sampling.PLAIN:
+        outs = _draw_outputs(logits, stats=False)
+        if logits.shape[0] > 0:
+            p = _lib.SampleParams()
+            _fill_rows(p, logits, outs, temperature, key)
+            _lib.check(_lib.load().hyd_sample_tokens(C.byref(p), _stream()))
+        return outs[0]
+    if draw == sampling.FILTERED:
+        tok, lp, _ = sample_tokens_filtered(logits, temperature, key, **cuts)
+    elif logits.is_cuda and draw == sampling.CONSTRAINED:
+        tok, lp, _ = sample_tokens_constrained(logits, temperature, key, constraint=constraint, penalties=pen, **cuts)
+    elif logits.is_cuda:
+        tok, lp, _ = sample_tokens_penalized(logits, temperature, key, penalties=pen, **cuts)
+    else:
+        dfa, state, advance = constraint if constraint is not None else (None, None, False)
+        x = logits if pen is None else pen.apply(logits)
+        tok, lp, drawn = sampling.reference_draw(x, temperature, dfa=dfa, state=state, **cuts)
+        if advance:
+            state.copy_(sampling.advance_state(dfa, state, tok, drawn))
+        if pen is not None and pen.append:
+            pen.push(tok)
     return (tok, lp[:, None]) if return_logprobs else tok
 
 
 def sample_tokens_filtered(logits: Tensor, temperature: float, key: Optional[tuple] = None, *, top_k: Optional[int] = None,
                            top_p: Optional[float] = None, min_p: Optional[float] = None):
     """hyd_sample_tokens_filtered: ([B, 1] int64 tokens, [B] fp32 log-probs, [B] int32 number of kept tokens)."""
-    _require_gpu(logits)
-    lib = _lib.load()
-    assert logits.ndim == 2 and logits.stride(1) == 1 and logits.shape[1] > 0
-    rows = logits.shape[0]
-    out = torch.empty((rows, 1), dtype=torch.int64, device=logits.device)
-    logprobs = torch.empty((rows,), dtype=torch.float32, device=logits.device)
-    kept = torch.empty((rows,), dtype=torch.int32, device=logits.device)
-    if rows == 0:
-        return out, logprobs, kept
-    check_filters(top_k, top_p, min_p)  # (before the key is taken: a rejected call leaves the generator as it was)
+    outs = _draw_outputs(logits, stats=True)
+    if logits.shape[0] == 0:
+        return outs
+    check_filters(top_k, top_p, min_p)
     p = _lib.SampleFilterParams()
-    p.top_k, p.top_p, p.min_p = int(top_k or 0), 1.0 if top_p is None else float(top_p), float(min_p or 0.0)
-    seed, offset = key if key is not None else _next_sample_key(logits.device)
-    p.logits, p.out, p.logprobs, p.kept = logits.data_ptr(), out.data_ptr(), logprobs.data_ptr(), kept.data_ptr()
-    p.row_stride = logits.stride(0) if rows > 1 else logits.shape[1]
-    p.seed, p.offset, p.rows, p.n = seed, offset, rows, logits.shape[1]
-    p.dtype = _HYD_F32 if logits.dtype == torch.float32 else _dtype_code(logits)
-    p.temperature = float(temperature)
-    _lib.check(lib.hyd_sample_tokens_filtered(C.byref(p), _stream()))
-    return out, logprobs, kept
+    _fill_rows(p, logits, outs, temperature, key, top_k, top_p, min_p)
+    _lib.check(_lib.load().hyd_sample_tokens_filtered(C.byref(p), _stream()))
+    return outs
 
 
 def token_logprobs(logits: Tensor, targets: Tensor, top_n: int = 0):

@@ -714,6 +714,84 @@ class SharedCacheOp:
     PRESERVE = "preserve"
 
 
+def draw_tokens(route: sampling.SampleRoute, logits, temperature, num_samples=1, top_p=None, top_k=None, min_p=None,
+                return_logprobs=False, penalties=None, constraint=None):
+    """Run one draw along `route` (sampling.sample_route's table): (tokens [B, num_samples], their fp32 log-probs
+    [B, num_samples] or, for a draw in torch that needs none, None).  The other arguments are sample_from_logits'."""
+    x, n = logits, num_samples
+    if route.torch_penalties:  # the definition, float64 through [B, V] tables
+        x = penalties.apply(x, n).float()
+    if route.torch_mask:
+        x, n = sampling.constrain_logits(x.repeat_interleave(n, 0), *constraint), 1
+    if route.draw in (sampling.PLAIN, sampling.TORCH):
+        src = x
+        # (a top_p of 1.0 is no cut to the kernels, but in torch it still passes through apply_top_p, as in the reference)
+        if route.torch_cuts or top_p is not None:
+            x = sampling.filter_logits(x, top_k, top_p, min_p) if top_k or min_p else sampling.apply_top_p(x, top_p)
+        if route.draw == sampling.PLAIN:
+            # argmax(logits / T + Gumbel noise) draws exactly from softmax(logits / T) -- what the softmax + torch.multinomial
+            # chain below draws, in one pass over the logits instead of ~12 launches over [B, vocab]
+            tok = layer_ops.sample_tokens(x, temperature)
+        elif temperature == 0:
+            assert x.ndim == 2
+            tok = x.argmax(dim=-1, keepdim=True).repeat_interleave(n, dim=-1)
+        else:
+            tok = torch.multinomial(nn.functional.softmax(x / temperature, dim=-1), num_samples=n, replacement=True)
+        lp = torch.log_softmax(src.float(), dim=-1).gather(-1, tok) if return_logprobs or route.torch_mask else None
+    else:
+        # one launch (CPU rows: its definition in torch): mask, penalties, cuts, draw, log-prob, the append and the state update
+        tok, lp = layer_ops.sample_tokens(
+            x, temperature, top_k=top_k, top_p=top_p, min_p=min_p, return_logprobs=True,
+            penalties=None if route.draw == sampling.FILTERED else penalties,
+            constraint=(*constraint, True) if route.draw == sampling.CONSTRAINED else None)
+    if route.torch_mask:  # a row drew something iff its log-prob is a number
+        dfa, state = constraint
+        state.copy_(sampling.advance_state(dfa, state, tok, ~torch.isnan(lp.reshape(-1))))
+    if route.torch_penalties and penalties.append and num_samples == 1:
+        penalties.push(tok)
+    return tok.reshape(-1, num_samples), None if lp is None else lp.reshape(-1, num_samples)
+
+
+@dataclass
+class _DecodeCall:
+    """What the decode half of one generate() call shares between _decode and its two step loops.  generate() sets the
+    fields down to `top`; _decode sets `route`, `pen`, `raw` and `graphed` before the steps; _decode, _step and keep() fill
+    the lists."""
+    sample: dict                               # sample_from_logits' arguments but the logits and num_samples
+    fan: int
+    max_new_tokens: int
+    top_n: int = 0
+    state: Optional[Tensor] = None             # the automaton states, if they are returned
+    logits: Optional[list] = None              # kept per step, if they are returned: [B, V] each
+    logprobs: Optional[list] = None            # [B, 1] each
+    top: Optional[tuple] = None                # (ids, log-probs) lists of [B, 1, top_n] each
+    route: Optional[sampling.SampleRoute] = None  # of the steps' draws (the first draw, which may fan out, has its own)
+    pen: Optional[layer_ops.Penalties] = None  # the penalties, if they keep a list of generated tokens (a bias alone does not)
+    raw: bool = False                          # the steps' logits stay in the lm_head's dtype
+    graphed: bool = False
+
+    def keep(self, logits, tok, lp):
+        """Record a step's returned log-probs and alternatives."""
+        if self.logprobs is not None:
+            self.logprobs.append(lp)
+        if self.top is not None:  # the same logits the sampler read; the sampled token's log-prob stays the sampler's
+            for kept, t in zip(self.top, layer_ops.token_logprobs(logits, tok[:, 0], self.top_n)[2:]):
+                kept.append(t[:, None])
+
+    def result(self, tokens, past=None, finish=None):
+        """generate()'s (tokens[, logits][, logprobs][, top_ids, top_logprobs][, finish][, state]), or the tokens alone.
+        past [B, width] bool (the stop path): what was kept is trimmed to the tokens' width and blanked at or past a row's
+        length."""
+        width = None if past is None else tokens.shape[1]
+        ret = (tokens,) if self.logits is None else (tokens, self.logits[:width])
+        for kept, blank in zip((self.logprobs,) + (self.top or ()), (0.0, -1, float("-inf"))):
+            if kept is not None:
+                t = torch.cat(kept, dim=1)
+                ret += (t if past is None else t[:, :width].masked_fill(past if t.ndim == 2 else past[:, :, None], blank),)
+        ret += tuple(x for x in (finish, self.state) if x is not None)
+        return ret if len(ret) > 1 else tokens
+
+
 class HydragenLlamaForCausalLM(nn.Module):
     """llama.py:875-1422."""
 
@@ -911,11 +989,16 @@ class HydragenLlamaForCausalLM(nn.Module):
         return logits if raw_logits else logits.float()
 
     def apply_top_p(self, logits, top_p, min_tokens_to_keep=1, filter_value=-float("Inf")):
-        sorted_logits, sorted_indices = torch.sort(logits, descending=False)
-        cumulative_probs = sorted_logits.softmax(dim=-1).cumsum(dim=-1)
-        remove = cumulative_probs <= (1 - top_p)
-        remove[..., -min_tokens_to_keep:] = 0
-        return logits.masked_fill(remove.scatter(1, sorted_indices, remove), filter_value)
+        return sampling.apply_top_p(logits, top_p, min_tokens_to_keep, filter_value)
+
+    def sample_route(self, cuda, unit_rows, temperature, num_samples=1, top_p=None, top_k=None, min_p=None, return_logprobs=False,
+                     penalties=None, constraint=None) -> sampling.SampleRoute:
+        """sampling.sample_route of a sample_from_logits call on logits that are on the GPU (cuda) and 2-D of unit last stride
+        (unit_rows), with the model's two switches as they are now."""
+        ok = cuda and temperature >= 0
+        return sampling.sample_route(cuda, ok and unit_rows, ok, num_samples, constraint is not None,
+                                     penalties is not None and penalties.active(), sampling.filters_active(top_k, top_p, min_p),
+                                     return_logprobs, self.fused_sampling_filters, self.fused_sampling_penalties)
 
     def sample_from_logits(self, logits, temperature, num_samples=1, top_p=None, top_k=None, min_p=None,
                            return_logprobs=False, penalties=None, constraint=None):
@@ -923,59 +1006,12 @@ class HydragenLlamaForCausalLM(nn.Module):
         act on the unscaled softmax(logits), before the temperature (hydragen_amd/sampling.py).  penalties (a
         layer_ops.Penalties with something switched on): cuts, draw and log-prob act on the penalised logits instead; the
         drawn tokens are appended to its list when it says so.  constraint = (dfa, state int32 [B * num_samples]): every rule
-        acts on the logits behind the automaton's mask and `state` advances in place (hyd_sample_tokens_constrained; the
-        torch definition for CPU logits and for num_samples > 1)."""
-        filtered = sampling.filters_active(top_k, top_p, min_p)
-        eligible = logits.is_cuda and logits.ndim == 2 and num_samples == 1 and logits.stride(-1) == 1 and temperature >= 0
-        if constraint is not None:
-            dfa, state = constraint
-            pen = penalties if penalties is not None and penalties.active() else None
-            if num_samples == 1 and (not logits.is_cuda or (eligible and (pen is None or self.fused_sampling_penalties))):
-                # one HIP kernel: mask, penalties, cuts, draw, log-prob, the append and the state update
-                return layer_ops.sample_tokens(logits, temperature, top_k=top_k, top_p=top_p, min_p=min_p,
-                                               return_logprobs=return_logprobs, penalties=pen, constraint=(dfa, state, True))
-            # the definition in torch ([B, V] tables), then the paths below on the masked logits, one sample per row
-            x = logits if pen is None else pen.apply(logits, num_samples).float()
-            x = sampling.constrain_logits(x.repeat_interleave(num_samples, 0), dfa, state)
-            tok, lp = self.sample_from_logits(x, temperature, 1, top_p, top_k, min_p, return_logprobs=True)
-            state.copy_(sampling.advance_state(dfa, state, tok, ~torch.isnan(lp.reshape(-1))))
-            if pen is not None and pen.append and num_samples == 1:
-                pen.push(tok)
-            tok, lp = tok.reshape(-1, num_samples), lp.reshape(-1, num_samples)
-            return (tok, lp) if return_logprobs else tok
-        if penalties is not None and penalties.active():
-            if eligible and self.fused_sampling_penalties:
-                # one HIP kernel: penalties, cuts, draw, log-prob and the append to the rows' generated tokens
-                return layer_ops.sample_tokens(logits, temperature, top_k=top_k, top_p=top_p, min_p=min_p,
-                                               return_logprobs=return_logprobs, penalties=penalties)
-            # the definition in torch (float64, through [B, V] tables), then the paths below on the penalised logits
-            logits = penalties.apply(logits, num_samples).float()
-            out = self.sample_from_logits(logits, temperature, num_samples, top_p, top_k, min_p, return_logprobs)
-            if penalties.append and num_samples == 1:
-                penalties.push(out[0] if return_logprobs else out)
-            return out
-        if eligible and (return_logprobs or (filtered and self.fused_sampling_filters)):
-            # one HIP kernel: the cuts, the Gumbel-max draw over the kept tokens and the token's log-probability
-            return layer_ops.sample_tokens(logits, temperature, top_k=top_k, top_p=top_p, min_p=min_p,
-                                           return_logprobs=return_logprobs)
-        src = logits
-        if top_k or min_p:
-            logits = sampling.filter_logits(logits, top_k, top_p, min_p)
-        elif top_p is not None:
-            logits = self.apply_top_p(logits, top_p)
-        if eligible:
-            # one HIP kernel: argmax(logits / T + Gumbel noise) draws exactly from softmax(logits / T) -- what the softmax +
-            # torch.multinomial chain below draws, in one pass over the logits instead of ~12 launches over [B, vocab]
-            tok = layer_ops.sample_tokens(logits, temperature)
-        elif temperature == 0:
-            assert logits.ndim == 2
-            tok = logits.argmax(dim=-1, keepdim=True).repeat_interleave(num_samples, dim=-1)
-        else:
-            probs = nn.functional.softmax(logits / temperature, dim=-1)
-            tok = torch.multinomial(probs, num_samples=num_samples, replacement=True)
-        if not return_logprobs:
-            return tok
-        return tok, torch.log_softmax(src.float(), dim=-1).gather(-1, tok)
+        acts on the logits behind the automaton's mask and `state` advances in place.  Which kernel or torch stage does what
+        is sampling.sample_route's table; generate() decides it once for its first draw and once for its steps."""
+        args = (temperature, num_samples, top_p, top_k, min_p, return_logprobs, penalties, constraint)
+        route = self.sample_route(logits.is_cuda, logits.ndim == 2 and logits.stride(-1) == 1, *args)
+        tok, lp = draw_tokens(route, logits, *args)
+        return (tok, lp) if return_logprobs else tok
 
     def _positions(self, input_ids):
         shared_lens = self.get_shared_cache_len(input_ids.shape[0])
@@ -1149,15 +1185,16 @@ class HydragenLlamaForCausalLM(nn.Module):
         finished sequence past its length are unspecified.  Penalties keep working (what a finished row draws is ignored).
         token_overrides cannot be combined with these arguments.
         Constrained decoding (hydragen_amd/sampling.py states the rules, hydragen_amd/constraint.py builds the automata):
-        constraint = a constraint.TokenDFA over the model's vocabulary restricts what every row may emit by what it has emitted so
-        far; constraint_state = the rows' start states, int [leaf batch] (repeated for num_return_sequences) or [batch], default 0;
-        a state outside the automaton leaves a row unconstrained.  The states live on the device for the whole call and advance
-        inside the sampling launch (hyd_sample_tokens_constrained; the token drawn from the prefill logits included), so there is
-        no [B, V] mask and no host synchronisation.  It composes with the cuts, the penalties and the stop conditions: with
-        TokenDFA.from_choices / from_regex(eos=ids) and eos_token_id=ids a row ends through the stop kernel once its output is
+        constraint = a constraint.TokenDFA over the model's vocabulary restricts what every row may emit by what it has emitted
+        so far; constraint_state = the rows' start states, int [leaf batch] (repeated for num_return_sequences) or [batch],
+        default 0; a state outside the automaton leaves a row unconstrained.  The states live on the device for the whole call
+        and advance with every draw, the one from the prefill logits included: no host synchronisation, and no [B, V] mask
+        wherever sampling.sample_route's table routes a draw to hyd_sample_tokens_constrained (every draw of one sample per
+        row).  It composes with the cuts, the penalties and the stop conditions: with TokenDFA.from_choices /
+        from_regex(eos=ids) and eos_token_id=ids a row ends through the stop kernel once its output is
         complete.  return_logprobs reports the CONSTRAINED distribution (the same rule as for penalties); return_logits and
-        top_logprobs stay raw.  return_constraint_state appends the final int32 [B] states as the last return value.  Not with
-        token_overrides.  With constraint=None, generate() runs exactly the launches it runs without these arguments."""
+        top_logprobs stay raw.  return_constraint_state appends the final int32 [B] states as the last return value.  Not
+        with token_overrides.  With constraint=None, generate() runs exactly the launches it runs without these arguments."""
         if not self.kv_cache_allocated:
             raise RuntimeError("call setup_caches() before generate()")
         if constraint is None and (constraint_state is not None or return_constraint_state):
@@ -1222,20 +1259,18 @@ class HydragenLlamaForCausalLM(nn.Module):
             self.repeat_per_completion_cache_for_num_samples(unique[0].shape[0], num_return_sequences)
 
         try:
-            samp = dict(temperature=temperature, top_p=top_p, top_k=top_k, min_p=min_p)
+            samp = dict(temperature=temperature, top_p=top_p, top_k=top_k, min_p=min_p, return_logprobs=return_logprobs)
             if penalised:
                 samp["penalties"] = self._penalties(batch, unique, num_return_sequences, max_new_tokens, repetition_penalty,
                                                     presence_penalty, frequency_penalty, logit_bias, counted)
-            if constraint is None:
-                return self._decode(logits[:, -1], unique, num_return_sequences, max_new_tokens, samp,
-                                    eos_token_id, return_logits, token_overrides, return_logprobs, top_n, stop_spec, return_finish)
-            state = self._constraint_state(constraint_state, leaf_batch, num_return_sequences)
-            samp["constraint"] = (constraint, state)
-            ret = self._decode(logits[:, -1], unique, num_return_sequences, max_new_tokens, samp,
-                               eos_token_id, return_logits, token_overrides, return_logprobs, top_n, stop_spec, return_finish)
-            if return_constraint_state:
-                ret = (ret if isinstance(ret, tuple) else (ret,)) + (state,)
-            return ret
+            state = None
+            if constraint is not None:
+                state = self._constraint_state(constraint_state, leaf_batch, num_return_sequences)
+                samp["constraint"] = (constraint, state)
+            call = _DecodeCall(sample=samp, fan=num_return_sequences, max_new_tokens=max_new_tokens, top_n=top_n,
+                               state=state if return_constraint_state else None, logits=[] if return_logits else None,
+                               logprobs=[] if return_logprobs else None, top=([], []) if top_n else None)
+            return self._decode(logits[:, -1], unique, call, eos_token_id, token_overrides, stop_spec, return_finish)
         finally:
             self._scale_windows("close_scale_window", write=False)  # (a call that raised before its first write)
             if shared_cache_op == SharedCacheOp.PRESERVE:
@@ -1428,43 +1463,45 @@ class HydragenLlamaForCausalLM(nn.Module):
             logprobs=lp, token_greedy=greedy, sum=torch.where(live, lp.double(), torch.zeros_like(lp, dtype=torch.float64)).sum(1),
             is_greedy=(greedy | ~live).all(1), top_ids=top_ids if top_n else None, top_logprobs=top_lp if top_n else None)
 
-    def _decode(self, prefill_logits, unique, fan, max_new_tokens, samp, eos_token_id, return_logits, token_overrides,
-                return_logprobs=False, top_n=0, stop_spec=None, return_finish=False):
+    def _decode(self, prefill_logits, unique, call: _DecodeCall, eos_token_id, token_overrides, stop_spec, return_finish):
+        samp, fan = call.sample, call.fan
         pen = samp.get("penalties")
-        if pen is not None and pen.gen is None:
-            pen = None  # a bias alone: no list of generated tokens to keep
-        if pen is not None:
+        if pen is not None and pen.gen is not None:  # (a bias alone keeps no list of generated tokens)
             # the list of generated tokens follows what is FED: the sampler appends its own draws unless overrides replace them
             # (or the first token fans out: one row of logits, `fan` rows of tokens)
+            call.pen = pen
             pen.append = token_overrides is None and fan == 1
-        first = self.sample_from_logits(prefill_logits, num_samples=fan, return_logprobs=return_logprobs, **samp)
-        kept_lp = kept_top = None
-        if return_logprobs:
+        first = self.sample_from_logits(prefill_logits, num_samples=fan, **samp)
+        if call.logprobs is not None:
             first, lp = first
-            kept_lp = [lp.reshape(-1, 1)]
-        if top_n:
+            call.logprobs.append(lp.reshape(-1, 1))
+        if call.top is not None:
             # the alternatives do not depend on the drawn token: once over the leaf_batch prefill rows, repeated per sample
             rows = prefill_logits if prefill_logits.stride(-1) == 1 else prefill_logits.contiguous()
             none = torch.full((rows.shape[0],), -1, dtype=torch.int64, device=rows.device)
-            _, _, ids, tlp = layer_ops.token_logprobs(rows, none, top_n)
-            kept_top = [(ids.repeat_interleave(fan, 0)[:, None], tlp.repeat_interleave(fan, 0)[:, None])]
+            for kept, t in zip(call.top, layer_ops.token_logprobs(rows, none, call.top_n)[2:]):
+                kept.append(t.repeat_interleave(fan, 0)[:, None])
         first = first.reshape(-1, 1)
-        kept_logits = [prefill_logits.repeat_interleave(fan, 0)] if return_logits else None
+        if call.logits is not None:
+            call.logits.append(prefill_logits.repeat_interleave(fan, 0))
         start = self.get_shared_cache_len(first.shape[0])[:, None]
         if unique is not None:
             start = start + unique[1].long().repeat_interleave(fan, 0)[:, None]
-        self._check_room(start, max_new_tokens)
-        done = (first == eos_token_id) if eos_token_id is not None else None
-        tokens = [first]
+        self._check_room(start, call.max_new_tokens)
         feed = first if token_overrides is None else token_overrides[:, 0:1]
-        if pen is not None and not pen.append:
+        if call.pen is not None and not pen.append:
             pen.push(feed)
             pen.append = token_overrides is None
         self.set_mode(AttentionMode.DECODE)
         # calibrated fp8 scales: a call without unique prompts first writes the unique cache in its first decode step (the fused
         # preamble does not pass through update_per_completion_kvs): the scales are written here, once, outside any captured graph
         self._scale_windows("close_scale_window")
-        graphed = self.graphed_model is not None
+        # 16-bit logits straight into the sampler unless the caller wants them (fp32, as the reference returns them) or
+        # the cuts run in torch
+        call.graphed = self.graphed_model is not None
+        call.route = self.sample_route(prefill_logits.is_cuda, True, **samp)  # (a step's logits are rows of the lm_head's output)
+        call.raw = call.logits is None and (self.fused_sampling_filters or not sampling.filters_active(
+            samp["top_k"], samp["top_p"], samp["min_p"]))
         # Ragged unique prompts: hand the longest sequences to the chip first.  Every length grows by one per step, so the order of
         # this generation's first step is the order of all of them (C2 heads, lengths 1..128 at random: suffix pass 184 -> 169 us).
         order = None
@@ -1475,10 +1512,8 @@ class HydragenLlamaForCausalLM(nn.Module):
                 order.copy_(_flash.longest_first(lens0))
         with _flash.seq_order(order, check=False):
             if stop_spec is not None:
-                return self._decode_steps_stop(first, start, kept_logits, graphed, max_new_tokens, samp, return_logits, kept_lp,
-                                               kept_top, stop_spec, return_finish)
-            return self._decode_steps(feed, start, tokens, kept_logits, done, graphed, max_new_tokens, samp, eos_token_id,
-                                      return_logits, token_overrides, kept_lp, kept_top)
+                return self._decode_steps_stop(call, first, start, stop_spec, return_finish)
+            return self._decode_steps(call, first, feed, start, eos_token_id, token_overrides)
 
     schedule_longest_first = True  # (tests switch it off to compare: only the schedule may depend on it, never a token)
     # top-k / top-p / min-p in the sampling kernel (hyd_sample_tokens_filtered); False: torch cuts + hyd_sample_tokens, the
@@ -1488,43 +1523,29 @@ class HydragenLlamaForCausalLM(nn.Module):
     # above (tests and tools/sampler_bench.py switch it off to compare)
     fused_sampling_penalties = True
 
-    def _decode_steps(self, feed, start, tokens, kept_logits, done, graphed, max_new_tokens, samp, eos_token_id,
-                      return_logits, token_overrides, kept_lp=None, kept_top=None):
-        # 16-bit logits straight into the sampler unless the caller wants them (fp32, as the reference returns them) or
-        # the cuts run in torch
-        raw = not return_logits and (self.fused_sampling_filters or not sampling.filters_active(
-            samp["top_k"], samp["top_p"], samp["min_p"]))
-        pen = samp.get("penalties")
-        if pen is not None and pen.gen is None:
-            pen = None
-        for step in range(max_new_tokens - 1):
-            logits = self(input_ids=feed, position_ids=start + step, use_graph=graphed, raw_logits=raw)[:, -1]
-            if return_logits:
-                kept_logits.append(logits)
-            nxt = self.sample_from_logits(logits, return_logprobs=kept_lp is not None, **samp)
-            if kept_lp is not None:
-                nxt, lp = nxt
+    def _step(self, call: _DecodeCall, input_ids, position_ids):
+        """One decode step along the call's route: (logits [B, V], tokens [B, 1], log-probs or None)."""
+        logits = self(input_ids=input_ids, position_ids=position_ids, use_graph=call.graphed, raw_logits=call.raw)[:, -1]
+        if call.logits is not None:
+            call.logits.append(logits)
+        return (logits,) + draw_tokens(call.route, logits, **call.sample)
+
+    def _decode_steps(self, call: _DecodeCall, first, feed, start, eos, overrides):
+        done = (first == eos) if eos is not None else None
+        tokens = [first]
+        for step in range(call.max_new_tokens - 1):
+            logits, nxt, lp = self._step(call, feed, start + step)
             if done is not None:
-                done = done | (nxt == eos_token_id)
+                done = done | (nxt == eos)
                 if bool(done.all()):
                     break
             tokens.append(nxt)
-            if kept_lp is not None:
-                kept_lp.append(lp)
-            if kept_top is not None:  # the same logits the sampler read; the sampled token's log-prob stays the sampler's
-                _, _, ids, tlp = layer_ops.token_logprobs(logits, nxt[:, 0], kept_top[0][0].shape[-1])
-                kept_top.append((ids[:, None], tlp[:, None]))
-            feed = nxt if token_overrides is None else token_overrides[:, step + 1 : step + 2]
-            if pen is not None and not pen.append and feed.shape[1]:
-                pen.push(feed)
-        out = torch.cat(tokens, dim=-1)
+            call.keep(logits, nxt, lp)
+            feed = nxt if overrides is None else overrides[:, step + 1 : step + 2]
+            if call.pen is not None and not call.pen.append and feed.shape[1]:
+                call.pen.push(feed)
         check_collectives()  # no-op without the direct xGMI all-reduce; raises if a rank ever gave up on a peer
-        ret = (out, kept_logits) if return_logits else (out,)
-        if kept_lp is not None:
-            ret = ret + (torch.cat(kept_lp, dim=-1),)
-        if kept_top is not None:
-            ret = ret + (torch.cat([i for i, _ in kept_top], dim=1), torch.cat([t for _, t in kept_top], dim=1))
-        return ret if len(ret) > 1 else out
+        return call.result(torch.cat(tokens, dim=-1))
 
     # hyd_stop_update path: every this many decode steps the host starts a non-blocking copy of the running-row count of the
     # step just enqueued and looks at it one step later (tests shrink it)
@@ -1533,12 +1554,9 @@ class HydragenLlamaForCausalLM(nn.Module):
     # (tools/stop_bench.py and the tests compare the two: only the step time may depend on it, never a token)
     stop_retire: Optional[bool] = None
 
-    def _decode_steps_stop(self, first, start, kept_logits, graphed, max_new_tokens, samp, return_logits, kept_lp, kept_top,
-                           spec, return_finish):
+    def _decode_steps_stop(self, call: _DecodeCall, first, start, spec, return_finish):
         """_decode_steps with the stop conditions of `spec` decided by hyd_stop_update after every sampling launch: the kernel
         writes the output matrix, keeps lengths and finish reasons, and hands back the token and the position to feed next."""
-        raw = not return_logits and (self.fused_sampling_filters or not sampling.filters_active(
-            samp["top_k"], samp["top_p"], samp["min_p"]))
         # (penalties: _decode has switched the sampler's own append on -- nothing is overridden here -- so the list of generated
         # tokens follows the draws; what a finished row draws goes nowhere else)
         dev = first.device
@@ -1551,14 +1569,14 @@ class HydragenLlamaForCausalLM(nn.Module):
             raise ValueError("stop_retire needs the fused decode preamble (use_fused_decode) in every layer")
         shared_len = None if attn.disable_hydragen else self.get_shared_cache_len(B).contiguous()
         start_pos = start.reshape(-1).long().contiguous()
-        out, length, reason, stop_index, live = stopping.new_state(B, max_new_tokens, spec, dev)
+        out, length, reason, stop_index, live = stopping.new_state(B, call.max_new_tokens, spec, dev)
         stop_tokens = spec.stop_table(dev)[0] if spec.stops else None
         poll = max(1, int(self.stop_poll_steps))
         # (page-locked once per model, not once per call: every slot is written by its copy before it is read, and no copy
         # is left in flight when a generation returns)
         polled = getattr(self, "_stop_polled", None)
-        if polled is None or polled.numel() < max_new_tokens // poll + 1:
-            polled = self._stop_polled = torch.empty((max(max_new_tokens // poll + 1, 512),), dtype=torch.int32).pin_memory()
+        if polled is None or polled.numel() < call.max_new_tokens // poll + 1:
+            polled = self._stop_polled = torch.empty((max(call.max_new_tokens // poll + 1, 512),), dtype=torch.int32).pin_memory()
         pending = None  # (slot, event) of the copy started at the previous step
 
         def update(tok, t):
@@ -1566,17 +1584,9 @@ class HydragenLlamaForCausalLM(nn.Module):
 
         feed, pos = update(first, 0)
         steps = 1  # columns of `out` written
-        for step in range(max_new_tokens - 1):
-            logits = self(input_ids=feed[:, None], position_ids=pos[:, None], use_graph=graphed, raw_logits=raw)[:, -1]
-            if return_logits:
-                kept_logits.append(logits)
-            nxt = self.sample_from_logits(logits, return_logprobs=kept_lp is not None, **samp)
-            if kept_lp is not None:
-                nxt, lp = nxt
-                kept_lp.append(lp)
-            if kept_top is not None:
-                _, _, ids, tlp = layer_ops.token_logprobs(logits, nxt[:, 0], kept_top[0][0].shape[-1])
-                kept_top.append((ids[:, None], tlp[:, None]))
+        for step in range(call.max_new_tokens - 1):
+            logits, nxt, lp = self._step(call, feed[:, None], pos[:, None])
+            call.keep(logits, nxt, lp)
             feed, pos = update(nxt, steps)
             steps += 1
             # The count of running rows, without draining the launch queue: the copy started after step c is waited for after step
@@ -1589,7 +1599,7 @@ class HydragenLlamaForCausalLM(nn.Module):
                 pending = None
                 if int(polled[slot]) == 0:
                     break
-            if steps % poll == 0 and steps < max_new_tokens:
+            if steps % poll == 0 and steps < call.max_new_tokens:
                 slot = steps // poll
                 polled[slot : slot + 1].copy_(live[steps - 1 : steps], non_blocking=True)
                 ev = torch.cuda.Event()
@@ -1597,14 +1607,5 @@ class HydragenLlamaForCausalLM(nn.Module):
                 pending = (slot, ev)
         check_collectives()
         width = int(length.max().item()) if B else 0  # (the one synchronisation of the generation)
-        tokens = out[:, :width]
         past = torch.arange(width, device=dev)[None, :] >= length[:, None]
-        ret = (tokens, kept_logits[:width]) if return_logits else (tokens,)
-        if kept_lp is not None:
-            ret = ret + (torch.cat(kept_lp, dim=-1)[:, :width].masked_fill(past, 0.0),)
-        if kept_top is not None:
-            ret = ret + (torch.cat([i for i, _ in kept_top], dim=1)[:, :width].masked_fill(past[:, :, None], -1),
-                         torch.cat([t for _, t in kept_top], dim=1)[:, :width].masked_fill(past[:, :, None], float("-inf")))
-        if return_finish:
-            ret = ret + (stopping.Finish(length, reason, stop_index),)
-        return ret if len(ret) > 1 else tokens
+        return call.result(out[:, :width], past, stopping.Finish(length, reason, stop_index) if return_finish else None)

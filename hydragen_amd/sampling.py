@@ -1,6 +1,6 @@
 """Sampling cuts in torch: the definition `hyd_sample_tokens_filtered` (csrc/sample_filter.hip) implements, evaluated in
-float64.  It is the fallback for tensors the kernel does not take (the fan-out first token with num_samples > 1, CPU
-tensors) and the reference of the tests.
+float64.  It runs where sample_route (below) routes a stage to torch (the fan-out first token with num_samples > 1, CPU
+tensors) and is the reference of the tests.
 
 For one row of logits l with m = max(l) and p = softmax(l):
   * the cuts act on the UNSCALED softmax(l), not on softmax(l / T) (the reference's `apply_top_p`; HF applies the
@@ -15,7 +15,7 @@ For one row of logits l with m = max(l) and p = softmax(l):
 from __future__ import annotations
 
 import math
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 from torch import Tensor
@@ -275,3 +275,69 @@ def advance_state(dfa, state: Tensor, tokens: Tensor, drawn: Optional[Tensor] = 
         on = on & drawn.reshape(-1).bool().to(st.device)
     nxt = dfa.next.to(st.device)[torch.where(on, st, torch.zeros_like(st)), tok].long()
     return torch.where(on, nxt, st).to(torch.int32)
+
+
+# ---- one draw, as a route ------------------------------------------------------------------------------------------------------
+# The draws: four entry points by their C names (CONSTRAINED and PENALIZED on CPU rows: their float64 definition,
+# reference_draw; the others take GPU rows only) and TORCH: argmax at temperature 0, else softmax + multinomial.
+CONSTRAINED, PENALIZED, FILTERED, PLAIN, TORCH = ("hyd_sample_tokens_constrained", "hyd_sample_tokens_penalized",
+                                                  "hyd_sample_tokens_filtered", "hyd_sample_tokens", "torch")
+
+
+class SampleRoute(NamedTuple):
+    draw: str                      # the entry point that draws (one key of the device's generator per call), or TORCH
+    torch_penalties: bool = False  # before the draw: Penalties.apply(rows, num_samples).float(); after it: Penalties.push
+    torch_mask: bool = False       # before the draw: repeat per sample + constrain_logits; after it: advance_state
+    torch_cuts: bool = False       # before the draw: filter_logits (top_p alone: the reference's apply_top_p)
+
+
+def sample_route(cuda: bool, eligible: bool, rewritten: bool, num_samples: int, constraint: bool, penalties: bool, filters: bool,
+                 logprobs: bool, fused_filters: bool = True, fused_penalties: bool = True) -> SampleRoute:
+    """THE table of the sampling routes: llama.draw_tokens runs a route, layer_ops.sample_tokens picks its entry point from one.
+    cuda: the rows are on the GPU; rewritten: and 2-D with temperature >= 0, what a kernel needs of rows a torch stage has
+    rewritten (contiguous); eligible: and of unit last stride as they are (a kernel takes them when num_samples == 1);
+    constraint / penalties / filters: given / active; logprobs: wanted; fused_*: the model's two switches.  The penalties in
+    torch hand on fp32 rows; mask and cuts keep the dtype: other rows reach the kernels in their own.  Penalties.push happens
+    only for one sample per row and a Penalties that appends."""
+    kernel = eligible and num_samples == 1
+    if constraint and num_samples == 1 and (not cuda or (kernel and (not penalties or fused_penalties))):
+        return SampleRoute(CONSTRAINED)  # one launch with everything in it
+    if penalties and not constraint and kernel and fused_penalties:
+        return SampleRoute(PENALIZED)
+    # otherwise penalties and mask run in torch, and what is left is a draw with neither, on the rows they have rewritten
+    if penalties:
+        kernel = rewritten and num_samples == 1
+    if constraint:
+        kernel, logprobs = rewritten, True  # one sample per masked row; whether a row drew a token is read off its log-prob
+    if kernel and (logprobs or (filters and fused_filters)):
+        return SampleRoute(FILTERED, penalties, constraint)
+    # cuts in torch; log-probs, if wanted (or forced on by the mask), are log softmax of the rows before the cuts
+    return SampleRoute(PLAIN if kernel else TORCH, penalties, constraint, filters)
+
+
+def apply_top_p(logits: Tensor, top_p: float, min_tokens_to_keep: int = 1, filter_value: float = -math.inf) -> Tensor:
+    """The reference's top-p cut (its llama.py, modified from HF's TopPLogitsWarper): what a top_p alone runs in torch."""
+    sorted_logits, sorted_indices = torch.sort(logits, descending=False)
+    cumulative_probs = sorted_logits.softmax(dim=-1).cumsum(dim=-1)
+    remove = cumulative_probs <= (1 - top_p)
+    remove[..., -min_tokens_to_keep:] = 0
+    return logits.masked_fill(remove.scatter(1, sorted_indices, remove), filter_value)
+
+
+@torch.no_grad()
+def reference_draw(x: Tensor, temperature: float, top_k: Optional[int] = None, top_p: Optional[float] = None,
+                   min_p: Optional[float] = None, dfa=None, state: Optional[Tensor] = None):
+    """PENALIZED / CONSTRAINED in torch, for CPU rows: x [B, n] the (penalised: float64) logits, masked here if an automaton is
+    given -> (tokens int64 [B, 1], fp32 log-probs [B], drawn bool [B]); a row without a valid logit: token 0, NaN, not drawn."""
+    xc = x if dfa is None else constrain_logits(x, dfa, state)
+    keep = kept_mask(xc, top_k, top_p, min_p)
+    drawn = keep.any(-1, keepdim=True)
+    xf = xc.masked_fill(~keep, -math.inf)
+    if temperature == 0:
+        tok = xf.argmax(-1, keepdim=True)
+    else:
+        pr = torch.softmax(xf.double() / temperature, -1)
+        tok = torch.multinomial(torch.where(drawn, pr, torch.ones_like(pr)), 1)
+    tok = torch.where(drawn, tok, torch.zeros_like(tok))
+    lp = torch.log_softmax(xc.double(), -1).gather(1, tok).float()
+    return tok, torch.where(drawn, lp, torch.full_like(lp, math.nan))[:, 0], drawn[:, 0]

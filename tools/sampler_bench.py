@@ -18,6 +18,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch
 
 from hydragen_amd import layer_ops
+from hydragen_amd.sampling import apply_top_p  # the path with fused_sampling_filters off
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--batches", default="1,128,1024")
@@ -30,13 +31,6 @@ ap.add_argument("--only", default="")
 a = ap.parse_args()
 DT = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
 dev = "cuda:0"
-
-
-def apply_top_p(logits, top_p):  # llama.py HydragenLlamaForCausalLM.apply_top_p, the path with fused_sampling_filters off
-    sorted_logits, sorted_indices = torch.sort(logits, descending=False)
-    remove = sorted_logits.softmax(dim=-1).cumsum(dim=-1) <= (1 - top_p)
-    remove[..., -1:] = 0
-    return logits.masked_fill(remove.scatter(1, sorted_indices, remove), -float("inf"))
 
 
 def timed(fn):
