@@ -202,6 +202,20 @@ class KvPromoteParams(C.Structure):
     ]
 
 
+class KvGatherParams(C.Structure):
+    _fields_ = [
+        ("level_k", C.c_void_p * HYD_MAX_LEVELS), ("level_v", C.c_void_p * HYD_MAX_LEVELS), ("level_cu", C.c_void_p * HYD_MAX_LEVELS),
+        ("level_s", C.c_int32 * HYD_MAX_LEVELS), ("level_cap", C.c_int32 * HYD_MAX_LEVELS), ("level_div", C.c_int32 * HYD_MAX_LEVELS),
+        ("k_src", C.c_void_p), ("v_src", C.c_void_p), ("k_dst", C.c_void_p), ("v_dst", C.c_void_p),
+        ("rows", C.c_void_p), ("lens", C.c_void_p), ("cu_dst", C.c_void_p), ("k_scale", C.c_void_p), ("v_scale", C.c_void_p),
+        ("k_batch_stride", C.c_int64), ("k_tok_stride", C.c_int64), ("k_head_stride", C.c_int64),
+        ("v_batch_stride", C.c_int64), ("v_tok_stride", C.c_int64), ("v_head_stride", C.c_int64),
+        ("src_dtype", C.c_int32), ("dst_dtype", C.c_int32), ("n", C.c_int32), ("n_levels", C.c_int32), ("B", C.c_int32),
+        ("src_rows", C.c_int32), ("Hkv", C.c_int32), ("d_src", C.c_int32), ("d_dst", C.c_int32), ("capacity", C.c_int32),
+        ("max_len", C.c_int32), ("max_path", C.c_int32),
+    ]
+
+
 KV_ABSMAX_PASSES = 16  # HYD_KV_ABSMAX_PASSES
 
 
@@ -266,6 +280,7 @@ EXPORTS = {
     "hyd_token_logprobs": (C.c_int, [C.POINTER(TokenLogprobParams), C.c_void_p]),
     "hyd_stop_update": (C.c_int, [C.POINTER(StopParams), C.c_void_p]),
     "hyd_kv_promote": (C.c_int, [C.POINTER(KvPromoteParams), C.c_void_p]),
+    "hyd_kv_gather_paths": (C.c_int, [C.POINTER(KvGatherParams), C.c_void_p]),
     "hyd_kv_absmax": (C.c_int, [C.POINTER(KvAbsmaxParams), C.c_void_p]),
     "hyd_kv_scales_from_absmax": (C.c_int, [C.POINTER(KvScalesParams), C.c_void_p]),
     "hyd_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

@@ -1040,6 +1040,81 @@ int hyd_kv_promote(const hyd_kv_promote_params* p, void* stream) {
     return launched(launch_kv_promote(a, p->src_dtype, p->dst_dtype, static_cast<hipStream_t>(stream)), "kv_promote kernel launch");
 }
 
+int hyd_kv_gather_paths(const hyd_kv_gather_params* p, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    if (p->dst_dtype != HYD_F16 && p->dst_dtype != HYD_BF16)
+        return fail(HYD_ERR_UNSUPPORTED, "dst_dtype %d: shared levels are f16 / bf16 (no fp8 or 32-bit destination)", p->dst_dtype);
+    if (p->src_dtype != HYD_F16 && p->src_dtype != HYD_BF16 && p->src_dtype != HYD_FP8_E4M3)
+        return fail(HYD_ERR_UNSUPPORTED, "src_dtype %d: f16, bf16 or HYD_FP8_E4M3 (%d)", p->src_dtype, HYD_FP8_E4M3);
+    if (p->src_dtype != HYD_FP8_E4M3 && p->src_dtype != p->dst_dtype)
+        return fail(HYD_ERR_BAD_ARG, "src_dtype %d differs from dst_dtype %d: a 16-bit source is copied as bytes", p->src_dtype, p->dst_dtype);
+    if (p->n <= 0) return fail(HYD_ERR_BAD_ARG, "n %d must be > 0", p->n);
+    if (p->n_levels < 0 || p->n_levels > HYD_MAX_LEVELS) return fail(HYD_ERR_BAD_ARG, "n_levels %d outside [0, %d]", p->n_levels, HYD_MAX_LEVELS);
+    if (p->Hkv <= 0) return fail(HYD_ERR_BAD_ARG, "Hkv %d must be > 0", p->Hkv);
+    if (p->B <= 0 || p->src_rows <= 0 || p->capacity < 0)
+        return fail(HYD_ERR_BAD_ARG, "B %d / src_rows %d must be > 0, capacity %d >= 0", p->B, p->src_rows, p->capacity);
+    if (p->d_src <= 0 || p->d_src % 8 != 0) return fail(HYD_ERR_BAD_ARG, "d_src %d must be a positive multiple of 8 (16-byte vectors)", p->d_src);
+    if (p->d_dst < p->d_src) return fail(HYD_ERR_BAD_ARG, "d_dst %d < d_src %d", p->d_dst, p->d_src);
+    if (p->d_dst != p->d_src && p->d_dst != 64 && p->d_dst != 128 && p->d_dst != 256)
+        return fail(HYD_ERR_UNSUPPORTED, "d_dst %d: 64, 128, 256 or d_src (%d)", p->d_dst, p->d_src);
+    if (p->max_len < 0 || p->max_len > p->src_rows) return fail(HYD_ERR_BAD_ARG, "max_len %d outside [0, src_rows = %d]", p->max_len, p->src_rows);
+    if (p->max_path < 0 || p->max_path > p->capacity) return fail(HYD_ERR_BAD_ARG, "max_path %d outside [0, capacity = %d]", p->max_path, p->capacity);
+    if (p->n > 65535) return fail(HYD_ERR_UNSUPPORTED, "n %d: up to 65535 sequences per launch", p->n);
+    if (int rc = check_ptr_align(p->k_src, "k_src")) return rc;
+    if (int rc = check_ptr_align(p->v_src, "v_src")) return rc;
+    if (int rc = check_ptr_align(p->k_dst, "k_dst")) return rc;
+    if (int rc = check_ptr_align(p->v_dst, "v_dst")) return rc;
+    if (!p->rows || !p->lens || !p->cu_dst) return fail(HYD_ERR_BAD_ARG, "rows / lens / cu_dst is null");
+    if (misaligned(p->rows, 4) || misaligned(p->lens, 4) || misaligned(p->cu_dst, 4) || misaligned(p->k_scale, 4) || misaligned(p->v_scale, 4))
+        return fail(HYD_ERR_BAD_ARG, "rows / lens / cu_dst / k_scale / v_scale is not aligned to its element size");
+    if (int rc = check_stride8(p->k_batch_stride, "k_batch_stride")) return rc;
+    if (int rc = check_stride8(p->k_tok_stride, "k_tok_stride")) return rc;
+    if (int rc = check_stride8(p->k_head_stride, "k_head_stride")) return rc;
+    if (int rc = check_stride8(p->v_batch_stride, "v_batch_stride")) return rc;
+    if (int rc = check_stride8(p->v_tok_stride, "v_tok_stride")) return rc;
+    if (int rc = check_stride8(p->v_head_stride, "v_head_stride")) return rc;
+    if (p->Hkv > 1 && (p->k_head_stride < p->d_src || p->v_head_stride < p->d_src))
+        return fail(HYD_ERR_BAD_ARG, "k_head_stride %lld / v_head_stride %lld < d_src %d", (long long)p->k_head_stride, (long long)p->v_head_stride, p->d_src);
+    for (int j = 0; j < p->n_levels; ++j) {
+        char name[32];
+        snprintf(name, sizeof(name), "level_k[%d]", j);
+        if (int rc = check_ptr_align(p->level_k[j], name)) return rc;
+        snprintf(name, sizeof(name), "level_v[%d]", j);
+        if (int rc = check_ptr_align(p->level_v[j], name)) return rc;
+        if (!p->level_cu[j] || misaligned(p->level_cu[j], 4)) return fail(HYD_ERR_BAD_ARG, "level_cu[%d] is null or not 4-byte aligned", j);
+        if (p->level_div[j] <= 0) return fail(HYD_ERR_BAD_ARG, "level_div[%d] = %d must be > 0 (old_batch / s_j)", j, p->level_div[j]);
+        if (p->level_s[j] <= 0 || p->level_cap[j] < 0)
+            return fail(HYD_ERR_BAD_ARG, "level_s[%d] = %d must be > 0, level_cap[%d] = %d >= 0", j, p->level_s[j], j, p->level_cap[j]);
+    }
+    const int max_len = p->max_len ? p->max_len : p->src_rows;
+    const int max_path = p->max_path ? p->max_path : p->capacity;
+    const int64_t vec_per_tok = (int64_t)p->Hkv * (p->d_dst / 8);
+    if (vec_per_tok * max_len >= (1LL << 31))
+        return fail(HYD_ERR_UNSUPPORTED, "max_len %d x Hkv %d x d_dst %d: a sequence of more than 2^31 16-byte vectors", max_len, p->Hkv, p->d_dst);
+    if (vec_per_tok * max_path >= (1LL << 31))
+        return fail(HYD_ERR_UNSUPPORTED, "max_path %d x Hkv %d x d_dst %d: a path of more than 2^31 16-byte vectors", max_path, p->Hkv, p->d_dst);
+    if (max_path == 0) return HYD_OK;  // (an empty destination: nothing can be written)
+    KvGatherArgs g;
+    memset(&g, 0, sizeof(g));
+    for (int j = 0; j < p->n_levels; ++j) {
+        g.lk[j] = p->level_k[j]; g.lv[j] = p->level_v[j]; g.lcu[j] = p->level_cu[j];
+        g.ls[j] = p->level_s[j]; g.lcap[j] = p->level_cap[j];
+        g.ldiv[j] = make_fastdiv((uint32_t)p->level_div[j]);
+    }
+    g.n_levels = p->n_levels; g.max_path = max_path;
+    KvPromoteArgs& a = g.u;
+    a.k_src = p->k_src; a.v_src = p->v_src; a.k_dst = p->k_dst; a.v_dst = p->v_dst;
+    a.rows = p->rows; a.lens = p->lens; a.cu = p->cu_dst;
+    if (p->src_dtype == HYD_FP8_E4M3) { a.k_scale = p->k_scale; a.v_scale = p->v_scale; }
+    a.k_bs = p->k_batch_stride; a.k_ts = p->k_tok_stride; a.k_hs = p->k_head_stride;
+    a.v_bs = p->v_batch_stride; a.v_ts = p->v_tok_stride; a.v_hs = p->v_head_stride;
+    a.n = p->n; a.B = p->B; a.max_len = max_len; a.capacity = p->capacity; a.d_src = p->d_src;
+    a.vec_per_head = p->d_dst / 8; a.vec_per_tok = (int32_t)vec_per_tok;
+    a.div_vec_per_head = make_fastdiv((uint32_t)a.vec_per_head);
+    a.div_vec_per_tok = make_fastdiv((uint32_t)a.vec_per_tok);
+    return launched(launch_kv_gather(g, p->src_dtype, p->dst_dtype, static_cast<hipStream_t>(stream)), "kv_gather kernel launch");
+}
+
 int hyd_kv_absmax(const hyd_kv_absmax_params* p, void* stream) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
     if (p->dtype != HYD_F16 && p->dtype != HYD_BF16)

@@ -258,6 +258,16 @@ struct KvPromoteArgs {  // kv_promote.hip: chosen rows of the unique K/V caches 
     FastDiv div_vec_per_head, div_vec_per_tok;
 };
 
+struct KvGatherArgs {  // kv_gather.hip: each survivor's path -- its parents' sequences in a chain of levels, then its unique rows -- into one packed level
+    const void* lk[HYD_MAX_LEVELS];       // chain level j: packed [cap_j, Hkv, d_dst] K / V of the destination dtype
+    const void* lv[HYD_MAX_LEVELS];
+    const int32_t* lcu[HYD_MAX_LEVELS];   // [s_j + 1] token offsets of its sequences
+    int32_t ls[HYD_MAX_LEVELS], lcap[HYD_MAX_LEVELS];
+    FastDiv ldiv[HYD_MAX_LEVELS];         // parent of unique row r in level j: r / div_j
+    KvPromoteArgs u;                      // the unique segment and the destination, as hyd_kv_promote has them (u.cu: cu_dst)
+    int32_t n_levels, max_path;
+};
+
 struct KvAbsmaxArgs {  // kv_scale.hip: per-kv-head max |x| of a strided 16-bit view [n_outer, n_rows, Hkv, d] (hyd_kv_absmax)
     const void* k;
     const void* v;
@@ -285,6 +295,7 @@ struct KvScalesArgs {  // kv_scale.hip: amax [2, Hkv] -> k_scale / v_scale [Hkv]
 int launch_kv_absmax(const KvAbsmaxArgs& a, int dtype, hipStream_t s);  // kv_scale.hip
 int launch_kv_scales(const KvScalesArgs& a, hipStream_t s);             // kv_scale.hip
 int launch_kv_promote(const KvPromoteArgs& a, int src_dtype, int dst_dtype, hipStream_t s);  // kv_promote.hip
+int launch_kv_gather(const KvGatherArgs& a, int src_dtype, int dst_dtype, hipStream_t s);    // kv_gather.hip
 int launch_prefix_w64(const PrefixArgs& a, int dtype, int D, bool causal, int grid, hipStream_t s);
 int launch_prefix_w64_f16(const PrefixArgs& a, int D, bool causal, int grid, hipStream_t s);  // prefix_attn_w64_f16.hip
 int launch_rope_append(const RopeArgs& a, int dtype, int D, hipStream_t s);

@@ -417,6 +417,55 @@ class PerLayerKVCache(nn.Module):
         sc.current_batch_size = bs
         self.num_used_shared_caches += 1
 
+    @torch.no_grad()
+    def promote_unique_merged(self, base: int, rows: Tensor, lens: Tensor, host_path_lens, *, old_batch: int, max_len: Optional[int] = None,
+                              staging: Optional[Tensor] = None, use_kernel: bool = True):
+        """Fork with merged levels (hydragen_amd/fork.py gather_paths): sequence i of level `base` becomes the whole path of
+        survivor rows[i] -- its parent's sequence in every level of [base, used), then the first lens[i] cached tokens of unique
+        sequence rows[i] -- and the levels behind `base` are dropped: num_used_shared_caches = base + 1.  One hyd_kv_gather_paths
+        launch (use_kernel=False: its torch definition) into `staging` ([2, >= sum(host_path_lens), Hkv, D] of the levels' dtype;
+        None: allocated here -- a caller with many layers passes one and reuses it), then ONE contiguous copy_ each of K and V
+        into slot `base`'s own buffers: the gather may not write what it reads (slot `base` is a chain level itself), and the
+        slot keeps its addresses, so a captured decode graph of the same key -- batch sizes, varlen flags, sliced lengths --
+        is replayed on it.  rows / lens: [k] device vectors; host_path_lens: the k path lengths in tokens on the host (the caller
+        computed them to check the room: nothing is synchronised here); old_batch: the batch rows index into.  The slot is left
+        exactly as SharedCache.fill leaves it for the concatenated paths, and fill's errors are raised before anything is written."""
+        from .fork import gather_paths, gather_paths_reference
+
+        base = int(base)
+        used = self.num_used_shared_caches
+        if not 0 <= base <= used:
+            raise ValueError(f"merge_from {base} outside [0, {used}] (the levels in use)")
+        if base >= self.get_num_total_shared_caches():
+            raise ValueError(f"No more available shared caches: {used} {self.get_num_total_shared_caches()}")
+        sc: SharedCache = self.shared_caches[base]
+        host_path_lens = [int(x) for x in host_path_lens]
+        bs, total = len(host_path_lens), sum(host_path_lens)
+        if bs > sc.max_batch_size:
+            raise ValueError(f"Batch size {bs} exceeds max batch size {sc.max_batch_size}")
+        if max(host_path_lens) > sc.max_sequence_length:
+            raise ValueError(f"Sequence length {max(host_path_lens)} exceeds max sequence length {sc.max_sequence_length}")
+        if total > sc.k_cache.shape[0]:
+            raise ValueError(f"{total} path tokens exceed the {sc.k_cache.shape[0]} tokens level {base} holds")
+        if staging is None:
+            staging = torch.empty((2, max(total, 1)) + tuple(sc.k_cache.shape[1:]), dtype=sc.k_cache.dtype, device=sc.k_cache.device)
+        if staging.ndim != 4 or staging.shape[0] != 2 or staging.shape[1] < total or staging.shape[2:] != sc.k_cache.shape[1:] \
+                or staging.dtype != sc.k_cache.dtype or not staging.is_contiguous():
+            raise ValueError(f"staging must be a contiguous [2, >= {total}, {sc.k_cache.shape[1]}, {sc.k_cache.shape[2]}] {sc.k_cache.dtype} "
+                             f"tensor, got {tuple(staging.shape)} {staging.dtype}")
+        chain = [(c.k_cache, c.v_cache, c.cumsum_lengths, c.current_batch_size) for c in list(self.shared_caches)[base:used]]
+        cu = (gather_paths if use_kernel else gather_paths_reference)(
+            chain, self.per_completion_k_cache, self.per_completion_v_cache, rows, lens, staging[0], staging[1], old_batch=old_batch,
+            max_len=max_len, max_path=max(host_path_lens), **self.scales())
+        sc.k_cache[:total].copy_(staging[0, :total])
+        sc.v_cache[:total].copy_(staging[1, :total])
+        sc.seq_lens[:bs] = cu[1:] - cu[:-1]
+        sc.cumsum_lengths[: bs + 1] = cu
+        sc.use_varlen = max(host_path_lens) != min(host_path_lens)
+        sc.sliced_sequence_length = None if sc.use_varlen else host_path_lens[0]
+        sc.current_batch_size = bs
+        self.num_used_shared_caches = base + 1
+
 
 class AttentionMode:
     SHARED_PREFILL = "shared-prefill"
@@ -1038,7 +1087,7 @@ class HydragenLlamaForCausalLM(nn.Module):
         return logits
 
     @torch.no_grad()
-    def fork(self, rows, seq_lens, token_ids, old_batch: int, use_kernel: bool = True) -> int:
+    def fork(self, rows, seq_lens, token_ids, old_batch: int, use_kernel: bool = True, merge_from: Optional[int] = None) -> int:
         """Promote completions of the previous decode batch to a new shared level, without a forward pass: the first seq_lens[i]
         cached tokens of unique sequence rows[i] become sequence i of the next free shared level at every layer (one
         hyd_kv_promote launch per layer; use_kernel=False: the torch definition, hydragen_amd/fork.py).  The level comes directly
@@ -1060,7 +1109,20 @@ class HydragenLlamaForCausalLM(nn.Module):
         behind those and need not be promoted).  To continue, pass each survivor's first uncached token as a one-token unique
         prompt: generate(input_ids=last[rows].repeat_interleave(m, 0)[:, None], num_return_sequences=1, ...) samples every
         survivor m times and uses one level per fork.  Tensor-parallel ranks call fork with the same arguments: the caches are
-        per-rank head shards, nothing else changes."""
+        per-rank head shards, nothing else changes.
+
+        merge_from=base (0 <= base <= levels in use; None: everything above, unchanged): fork with merged levels.  The levels
+        [base, used) -- the chain earlier forks left -- and the promoted rows are gathered into ONE level that replaces them
+        (PerLayerKVCache.promote_unique_merged: one hyd_kv_gather_paths launch and one copy per layer): sequence i of level
+        `base` becomes survivor i's whole path, its parent's sequence in every chain level and then its own seq_lens[i] tokens
+        (0 is allowed: the path alone), and base + 1 levels are in use afterwards, however many forks came before.  ANY distinct
+        rows may survive: check_fork_rows has to hold for the levels below `base` only (the prompt's), so two children of one
+        path and none of another is a valid selection -- what a global top-k needs.  Slot `base` must hold k sequences, each
+        path must fit its max_sequence_length and their total its capacity.  The chain levels' lengths are read from the device
+        once; every check runs on the host before the first launch, and a refused call leaves the levels, their count and the
+        bitmaps as they were.  shared_bitmaps[base] becomes, per survivor, the OR of its parents' bitmap rows in the chain
+        levels and token_bitmap(token_ids, seq_lens): the bitmap of the whole path's tokens.  merge_from == used is a chain of
+        no levels: the same level bytes and logits as the plain fork."""
         from .fork import check_fork_rows
 
         if not self.kv_cache_allocated:
@@ -1074,6 +1136,8 @@ class HydragenLlamaForCausalLM(nn.Module):
         max_batch, room = kv.per_completion_k_cache.shape[:2]
         if not 1 <= int(old_batch) <= max_batch:
             raise ValueError(f"old_batch {old_batch}: the unique cache holds {max_batch} sequences")
+        if merge_from is not None:
+            return self._fork_merged(rows_l, lens_l, token_ids, int(old_batch), use_kernel, merge_from)
         check_fork_rows(rows_l, old_batch, [c.current_batch_size for c in kv.get_used_shared_caches()])
         if min(lens_l) < 1 or max(lens_l) > room:
             raise ValueError(f"seq_lens {lens_l}: each at least 1 and at most the {room} tokens a unique sequence caches")
@@ -1097,6 +1161,66 @@ class HydragenLlamaForCausalLM(nn.Module):
         del self.shared_bitmaps[used:]
         ids = token_ids.to(dev).long()
         self.shared_bitmaps.append(layer_ops.token_bitmap(ids, lens_t.to(device=ids.device, dtype=torch.int64), self.vocab_size))
+        return self.get_num_used_shared_caches()
+
+    def _fork_merged(self, rows_l, lens_l, token_ids, old_batch: int, use_kernel: bool, base) -> int:
+        """fork(merge_from=base): the host checks, one staging allocation, one gather + copy per layer, the merged bitmap."""
+        from . import _lib
+        from .fork import check_fork_rows
+
+        kv = self.model.layers[0].self_attn.kv_cache
+        room = kv.per_completion_k_cache.shape[1]
+        used, k = kv.num_used_shared_caches, len(rows_l)
+        if isinstance(base, bool) or not isinstance(base, int) or not 0 <= base <= used:
+            raise ValueError(f"merge_from {base!r}: an index in [0, {used}] (the levels in use)")
+        levels = kv.get_used_shared_caches()
+        check_fork_rows(rows_l, old_batch, [c.current_batch_size for c in levels[:base]])
+        chain = levels[base:]
+        if len(chain) > _lib.HYD_MAX_LEVELS:
+            raise ValueError(f"{len(chain)} levels to merge: at most {_lib.HYD_MAX_LEVELS} in one fork")
+        for j, c in enumerate(chain):
+            if old_batch % c.current_batch_size:
+                raise ValueError(f"level {base + j}: {c.current_batch_size} shared sequences do not divide the previous batch of {old_batch}")
+        if min(lens_l) < 0 or max(lens_l) > room:
+            raise ValueError(f"seq_lens {lens_l}: each at least 0 and at most the {room} tokens a unique sequence caches")
+        width = max(max(lens_l), 1)
+        if not isinstance(token_ids, Tensor) or token_ids.ndim != 2 or token_ids.shape != (k, width):
+            raise ValueError(f"token_ids must be [{k}, {width}] (right-padded to the longest promoted length), got "
+                             f"{tuple(token_ids.shape) if isinstance(token_ids, Tensor) else type(token_ids)}")
+        if base >= kv.get_num_total_shared_caches():
+            raise ValueError(f"No more available shared caches: {used} {kv.get_num_total_shared_caches()}")
+        sc = kv.shared_caches[base]
+        if k > sc.max_batch_size:
+            raise ValueError(f"Batch size {k} exceeds max batch size {sc.max_batch_size}")
+        # the chain levels' lengths: one read of the device for all of them
+        path = list(lens_l)
+        parents = [[r // (old_batch // c.current_batch_size) for r in rows_l] for c in chain]
+        if chain:
+            host = torch.cat([c.seq_lens[: c.current_batch_size] for c in chain]).tolist()
+            at = 0
+            for c, par in zip(chain, parents):
+                for i, p in enumerate(par):
+                    path[i] += int(host[at + p])
+                at += c.current_batch_size
+        if max(path) > sc.max_sequence_length:
+            raise ValueError(f"Sequence length {max(path)} exceeds max sequence length {sc.max_sequence_length}")
+        if sum(path) > sc.k_cache.shape[0]:
+            raise ValueError(f"{sum(path)} path tokens exceed the {sc.k_cache.shape[0]} tokens level {base} holds")
+        dev = kv.per_completion_k_cache.device
+        rows_t = torch.tensor(rows_l, dtype=torch.int32, device=dev)
+        lens_t = torch.tensor(lens_l, dtype=torch.int32, device=dev)
+        # the path's token set first (it reads the chain levels' bitmaps, which the list is about to drop)
+        ids = token_ids.to(dev).long()
+        bits = torch.zeros((k, (self.vocab_size + 31) // 32), dtype=torch.int32, device=ids.device)
+        for j, par in enumerate(parents):
+            bits |= self.shared_bitmaps[base + j].to(ids.device)[torch.tensor(par, dtype=torch.int64, device=ids.device)]
+        bits = layer_ops.token_bitmap(ids, lens_t.to(device=ids.device, dtype=torch.int64), self.vocab_size, out=bits)
+        staging = torch.empty((2, max(sum(path), 1)) + tuple(sc.k_cache.shape[1:]), dtype=sc.k_cache.dtype, device=sc.k_cache.device)
+        for layer in self.model.layers:
+            layer.self_attn.kv_cache.promote_unique_merged(base, rows_t, lens_t, path, old_batch=old_batch, max_len=max(max(lens_l), 1),
+                                                           staging=staging, use_kernel=use_kernel)
+        del self.shared_bitmaps[base:]
+        self.shared_bitmaps.append(bits)
         return self.get_num_used_shared_caches()
 
     @torch.no_grad()

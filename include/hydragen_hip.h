@@ -48,7 +48,7 @@ extern "C" {
 
 /* 0.5.0 also carries the fp8 unique-cache entry points (hyd_kv_quant, hyd_*_kvq, hyd_kv_quant_supported) and the filtered
  * sampler (hyd_sample_filter_params, hyd_sample_tokens_filtered), the scoring entry point (hyd_token_logprob_params,
- * hyd_token_logprobs) and the penalised sampler (hyd_sample_penalty_params, hyd_sample_tokens_penalized, hyd_token_bitmap_build) and the stop-condition entry point (hyd_stop_params, hyd_stop_update) and the unique-to-shared K/V copy (hyd_kv_promote_params, hyd_kv_promote) and the fp8 scale calibration (hyd_kv_absmax_params, hyd_kv_absmax, hyd_kv_scales_params, hyd_kv_scales_from_absmax): they are new symbols and new structs only -- no existing struct, entry point or result changed -- so a caller built against 0.5.0 without them is
+ * hyd_token_logprobs) and the penalised sampler (hyd_sample_penalty_params, hyd_sample_tokens_penalized, hyd_token_bitmap_build) and the stop-condition entry point (hyd_stop_params, hyd_stop_update) and the unique-to-shared K/V copy (hyd_kv_promote_params, hyd_kv_promote) and the path gather of a fork with merged levels (hyd_kv_gather_params, hyd_kv_gather_paths) and the fp8 scale calibration (hyd_kv_absmax_params, hyd_kv_absmax, hyd_kv_scales_params, hyd_kv_scales_from_absmax): they are new symbols and new structs only -- no existing struct, entry point or result changed -- so a caller built against 0.5.0 without them is
  * unaffected and the version stays 500. */
 #define HYD_VERSION 500 /* 0.5.0: hyd_suffix_params.seq_order (schedule hint for ragged lengths); 0.4.0: hyd_add_rmsnorm, hyd_swiglu, hyd_sample_tokens (model-shell glue); 0.3.0: two-stream phases + hyd_decode_params.shared_max_workgroups, hyd_decode_two_stream_ok; 0.2.2: hyd_allreduce_params.timeout_log2_polls; 0.2.1: softmax_scale; 0.2.0: hyd_decode_params.phase, hyd_rope_params.max_pos, hyd_allreduce_* */
 #define HYD_MAX_LEVELS 8
@@ -692,6 +692,63 @@ typedef struct hyd_kv_promote_params {
 } hyd_kv_promote_params;
 
 HYD_API int hyd_kv_promote(const hyd_kv_promote_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Fork with merged levels: gather each survivor's whole PATH since the prompt into one packed SHARED level, K and V in one launch.
+ * The path of destination sequence i < n is, in order:
+ *   - chain segments: for every chain level j < n_levels (0 <= n_levels <= HYD_MAX_LEVELS) the tokens [cu_j[p], cu_j[p + 1]) of
+ *     that level, p = rows[i] / level_div[j] (the host passes level_div[j] = old_batch / level_s[j]: sequence r of the previous
+ *     batch read shared sequence r / (old_batch / s_j) of a level of s_j sequences).  A level is packed [level_cap[j], Hkv, d_dst]
+ *     contiguous K and V of dst_dtype with device offsets level_cu[j] [level_s[j] + 1]; its tokens are copied as BYTES;
+ *   - the unique segment: the first lens[i] tokens of unique sequence rows[i], written exactly as hyd_kv_promote writes them
+ *     (source layout, dtypes, scales, strides and d_src / d_dst as documented there: a 16-bit source is a byte copy, an e4m3fn
+ *     source is widened by the dequantize_kv rule with per-head scales, the pad columns of a wider destination row are zeros).
+ * It occupies packed tokens [cu_dst[i], cu_dst[i] + path_i) of k_dst / v_dst [capacity, Hkv, d_dst] contiguous; destination tokens
+ * at or past cu_dst[n] are not touched (cu_dst[i + 1] - cu_dst[i] == path_i is the caller's to keep).  THE DESTINATION MUST NOT
+ * OVERLAP ANY SOURCE (chain levels or unique caches): a workgroup reads while another writes, in no order.  To replace a chain
+ * level by the gathered one, gather into a staging buffer and copy.
+ *   - rows / lens / cu_dst and every level_cu[j] are DEVICE arrays read at launch time (capture-safe).  The kernel cannot raise:
+ *     a destination sequence is skipped AS A WHOLE, and nothing is indexed with the bad value, when rows[i] is outside [0, B), a
+ *     parent index rows[i] / level_div[j] is outside [0, level_s[j]), a segment is negative (cu_j[p] < 0 or cu_j[p + 1] < cu_j[p])
+ *     or runs past level_cap[j], lens[i] is outside [0, max_len], the path is longer than max_path, or cu_dst[i] < 0 or
+ *     cu_dst[i] + path_i > capacity;
+ *   - max_len is the HOST's bound on lens[] (0 = src_rows), max_path the host's bound on a path in tokens (0 = capacity): the
+ *     launch grid is sized by max_path, n and K | V, never by device data.  One launch, 16-byte loads and stores, no LDS, no
+ *     scratch, no allocation, no synchronisation.
+ * HYD_ERR_BAD_ARG: everything hyd_kv_promote refuses with it (cu_dst for cu), n_levels outside [0, HYD_MAX_LEVELS], a null or
+ * misaligned level_k[j] / level_v[j] (16 bytes) / level_cu[j] (4 bytes), level_div[j] <= 0, level_s[j] <= 0, level_cap[j] < 0,
+ * max_path outside [0, capacity].  HYD_ERR_UNSUPPORTED: what hyd_kv_promote refuses with it, and max_path * Hkv * d_dst / 8 >= 2^31.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct hyd_kv_gather_params {
+    const void* level_k[HYD_MAX_LEVELS];      /* chain level j: [level_cap[j], Hkv, d_dst] contiguous, dst_dtype         */
+    const void* level_v[HYD_MAX_LEVELS];
+    const int32_t* level_cu[HYD_MAX_LEVELS];  /* [level_s[j] + 1] token offsets (device)                                 */
+    int32_t level_s[HYD_MAX_LEVELS];          /* sequences of the level                                                  */
+    int32_t level_cap[HYD_MAX_LEVELS];        /* token rows of the level                                                 */
+    int32_t level_div[HYD_MAX_LEVELS];        /* old_batch / level_s[j]                                                  */
+    const void* k_src;      /* unique caches: as hyd_kv_promote_params                                       */
+    const void* v_src;
+    void* k_dst;            /* [capacity, Hkv, d_dst] contiguous, dst_dtype; overlaps no source              */
+    void* v_dst;
+    const int32_t* rows;    /* [n] batch index in the previous batch: the unique row, and the parents by it  */
+    const int32_t* lens;    /* [n] tokens taken from the front of that unique row (0 is allowed)             */
+    const int32_t* cu_dst;  /* [n + 1] destination token offsets                                             */
+    const float* k_scale;   /* [Hkv] or NULL = 1; fp8 sources only                                           */
+    const float* v_scale;
+    int64_t k_batch_stride, k_tok_stride, k_head_stride; /* elements of src_dtype                            */
+    int64_t v_batch_stride, v_tok_stride, v_head_stride;
+    int32_t src_dtype;      /* HYD_F16 | HYD_BF16 | HYD_FP8_E4M3                                             */
+    int32_t dst_dtype;      /* HYD_F16 | HYD_BF16                                                            */
+    int32_t n;              /* destination sequences                                                         */
+    int32_t n_levels;       /* chain levels, outermost first                                                 */
+    int32_t B, src_rows;    /* sequences and token rows of the unique caches                                 */
+    int32_t Hkv, d_src, d_dst;
+    int32_t capacity;       /* token rows of the destination                                                 */
+    int32_t max_len;        /* host bound on lens[]; 0 = src_rows                                            */
+    int32_t max_path;       /* host bound on a path in tokens; 0 = capacity                                  */
+} hyd_kv_gather_params;
+
+HYD_API int hyd_kv_gather_paths(const hyd_kv_gather_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Calibrate the per-kv-head scales of the fp8 unique caches from 16-bit K / V (the prompt's, as the prefill computes them).
