@@ -71,7 +71,7 @@ class DecodeParams(C.Structure):
         ("n_levels", C.c_int32), ("phase", C.c_int32),
         ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
         ("shared_max_workgroups", C.c_int32), ("f32_partials", C.c_int32),
-        ("single_launch_small", C.c_int32), ("reserved", C.c_int32),
+        ("single_launch_small", C.c_int32), ("causal_tail", C.c_int32),
     ]
 
 
@@ -86,6 +86,50 @@ class RopeParams(C.Structure):
         ("pos_stride", C.c_int64), ("cs_stride", C.c_int64),
         ("dtype", C.c_int32), ("B", C.c_int32), ("Hq", C.c_int32), ("Hkv", C.c_int32), ("D", C.c_int32),
         ("cache_len", C.c_int32), ("max_pos", C.c_int32), ("head_dim", C.c_int32),
+    ]
+
+
+class RopeMultiParams(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("q_out", C.c_void_p),
+        ("k_cache", C.c_void_p), ("v_cache", C.c_void_p), ("cos", C.c_void_p), ("sin", C.c_void_p),
+        ("position_ids", C.c_void_p), ("shared_len", C.c_void_p), ("seq_lens", C.c_void_p),
+        ("q_batch_stride", C.c_int64), ("k_batch_stride", C.c_int64), ("v_batch_stride", C.c_int64),
+        ("q_tok_stride", C.c_int64), ("k_tok_stride", C.c_int64), ("v_tok_stride", C.c_int64),
+        ("kc_batch_stride", C.c_int64), ("kc_tok_stride", C.c_int64), ("kc_head_stride", C.c_int64),
+        ("vc_batch_stride", C.c_int64), ("vc_tok_stride", C.c_int64), ("vc_head_stride", C.c_int64),
+        ("pos_stride", C.c_int64), ("cs_stride", C.c_int64),
+        ("dtype", C.c_int32), ("B", C.c_int32), ("T", C.c_int32), ("Hq", C.c_int32), ("Hkv", C.c_int32), ("D", C.c_int32),
+        ("cache_len", C.c_int32), ("max_pos", C.c_int32),
+    ]
+
+
+DRAFT_MAX_SEGMENTS, DRAFT_MAX_NGRAM = HYD_MAX_LEVELS + 2, 8  # HYD_DRAFT_MAX_SEGMENTS / _NGRAM
+
+
+class DraftSegment(C.Structure):
+    _fields_ = [
+        ("ids", C.c_void_p), ("lens_i64", C.c_void_p), ("lens_i32", C.c_void_p), ("row_stride", C.c_int64),
+        ("len", C.c_int32), ("div", C.c_int32),
+    ]
+
+
+class DraftLookupParams(C.Structure):
+    _fields_ = [
+        ("segments", DraftSegment * DRAFT_MAX_SEGMENTS), ("drafts", C.c_void_p), ("n_proposed", C.c_void_p),
+        ("drafts_stride", C.c_int64), ("n_segments", C.c_int32), ("B", C.c_int32), ("K", C.c_int32),
+        ("ngram_min", C.c_int32), ("ngram_max", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class DraftAcceptParams(C.Structure):
+    _fields_ = [
+        ("fed", C.c_void_p), ("sampled", C.c_void_p), ("logprobs", C.c_void_p), ("out", C.c_void_p), ("out_logprobs", C.c_void_p),
+        ("length", C.c_void_p), ("reason", C.c_void_p), ("stop_index", C.c_void_p), ("accepted", C.c_void_p), ("live", C.c_void_p),
+        ("start_pos", C.c_void_p), ("shared_len", C.c_void_p), ("feed", C.c_void_p), ("next_pos", C.c_void_p),
+        ("out_stride", C.c_int64), ("pad", C.c_int64), ("eos", C.c_int64 * 16),
+        ("rows", C.c_int32), ("T", C.c_int32), ("n_eos", C.c_int32), ("max_new_tokens", C.c_int32),
+        ("retire", C.c_int32), ("reserved", C.c_int32),
     ]
 
 
@@ -283,6 +327,10 @@ EXPORTS = {
     "hyd_kv_gather_paths": (C.c_int, [C.POINTER(KvGatherParams), C.c_void_p]),
     "hyd_kv_absmax": (C.c_int, [C.POINTER(KvAbsmaxParams), C.c_void_p]),
     "hyd_kv_scales_from_absmax": (C.c_int, [C.POINTER(KvScalesParams), C.c_void_p]),
+    "hyd_suffix_attn_causal_fwd": (C.c_int, [C.POINTER(SuffixParams), C.c_void_p]),
+    "hyd_rope_append_multi": (C.c_int, [C.POINTER(RopeMultiParams), C.c_void_p]),
+    "hyd_draft_lookup": (C.c_int, [C.POINTER(DraftLookupParams), C.c_void_p]),
+    "hyd_draft_accept": (C.c_int, [C.POINTER(DraftAcceptParams), C.c_void_p]),
     "hyd_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }

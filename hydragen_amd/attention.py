@@ -97,11 +97,15 @@ def hydragen_attention(
     *,
     k_scale: Tensor | None = None,
     v_scale: Tensor | None = None,
+    causal_tail: bool = False,
 ):
     """
     Computes Hydragen attention (attention decomposition + inter-sequence batching); same
     contract as attention.py:177-354.  k / v (the unique caches, not the shared levels) may be
     float8_e4m3fn with per-kv-head fp32 scales k_scale / v_scale ([Hkv], None = 1; kv_quant.py).
+    causal_tail=True (needs seq_lens): a multi-token decode step -- the qlen = T queries (2..8) are the last T tokens of their
+    sequences, their keys already in k / v, and query i sees the unique keys below seq_lens[b] - (T - 1 - i) and every shared
+    key (hyd_decode_params.causal_tail).  16-bit caches of head dim 64 / 128 / 256; anything else raises NotImplementedError.
 
     Args:
         q: attention queries, shape [batch, qlen, qheads, head_dim]
@@ -130,6 +134,14 @@ def hydragen_attention(
     b, nq, hq, d = q.shape
     fp8 = _flash.check_kv_pair(k, v, k_scale, v_scale)
     fused_ok = seq_lens is not None or nq == 1 or k.shape[1] == 0
+    if causal_tail:
+        if seq_lens is None or fp8 or d not in (64, 128, 256) or k.shape[-1] != d or n_levels > HYD_MAX_LEVELS or not 2 <= nq <= 8:
+            raise NotImplementedError("causal_tail: seq_lens, 2..8 queries per sequence, 16-bit unique caches of head dim 64 / 128 / 256 "
+                                      f"and at most {HYD_MAX_LEVELS} levels (got q {tuple(q.shape)}, k {tuple(k.shape)} {k.dtype})")
+        return _decode_fused(_q_contig(q), _lastdim_contig(k), _lastdim_contig(v), [_lastdim_contig(x) for x in shared_ks],
+                             [_lastdim_contig(x) for x in shared_vs], shared_cu_seq_lens, shared_max_seq_lens, use_varlens, seq_lens,
+                             causal_tail=True)
+
     def dequantized():  # 16-bit temporaries and the existing path (functional, not fast)
         return hydragen_attention(q, _flash.dequantize_kv(k, k_scale, q.dtype), _flash.dequantize_kv(v, v_scale, q.dtype),
                                   shared_ks, shared_vs, shared_cu_seq_lens, shared_max_seq_lens, use_varlens, seq_lens)
@@ -363,8 +375,10 @@ def _tensor_key(t):
     return None if t is None else (t.data_ptr(), tuple(t.shape), tuple(t.stride()), t.dtype)
 
 
-def _decode_fused(q, k, v, shared_ks, shared_vs, shared_cu_seq_lens, shared_max_seq_lens, use_varlens, seq_lens, scales=None):
-    """scales: None for 16-bit unique caches, (k_scale, v_scale) for fp8 ones (either may be None = 1)."""
+def _decode_fused(q, k, v, shared_ks, shared_vs, shared_cu_seq_lens, shared_max_seq_lens, use_varlens, seq_lens, scales=None,
+                  causal_tail=False):
+    """scales: None for 16-bit unique caches, (k_scale, v_scale) for fp8 ones (either may be None = 1).  causal_tail: the unique
+    part of a multi-token decode step (hyd_decode_params.causal_tail)."""
     lib = _lib.load()
     b, nq, hq, d = q.shape
     out = torch.empty_like(q)
@@ -379,7 +393,7 @@ def _decode_fused(q, k, v, shared_ks, shared_vs, shared_cu_seq_lens, shared_max_
         key = (_tensor_key(q), _tensor_key(k), _tensor_key(v), _tensor_key(seq_lens), _tensor_key(order), q.device.index, stream, threading.get_ident(), _f32_partials,
                tuple(_tensor_key(x) for x in shared_ks), tuple(_tensor_key(x) for x in shared_vs),
                tuple(_tensor_key(x) for x in shared_cu_seq_lens), tuple(shared_max_seq_lens), tuple(use_varlens),
-               None if scales is None else tuple(_tensor_key(x) for x in scales))
+               None if scales is None else tuple(_tensor_key(x) for x in scales), bool(causal_tail))
         hit = _PARAM_CACHE.get(key)
         if hit is not None:
             if hit[0] is None:  # fp8 caches: this call was refused when it was marshalled (below)
@@ -395,6 +409,7 @@ def _decode_fused(q, k, v, shared_ks, shared_vs, shared_cu_seq_lens, shared_max_
         keep.extend(scales)
     p.n_levels = len(shared_ks)
     p.f32_partials = 1 if _f32_partials else 0
+    p.causal_tail = 1 if causal_tail else 0
     for i, (sk, sv, scu, smax, uv) in enumerate(
         zip(shared_ks, shared_vs, shared_cu_seq_lens, shared_max_seq_lens, use_varlens)
     ):

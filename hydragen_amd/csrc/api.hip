@@ -391,8 +391,19 @@ int fail_kvq_shapes(int D) {
                 "multiple of %d at D = %d; D 64 / 128 / 256)", D >= 8 ? 64 / (D / 8) : 0, D);
 }
 
-// kq: null, or fp8 unique caches (validated by check_kvq; K/V strides in bytes)
-int run_suffix(const hyd_suffix_params* p, const hyd_partial* parts, int n_parts, hipStream_t s, const hyd_kv_quant* kq = nullptr) {
+// The causal tail (hyd_suffix_attn_causal_fwd, hyd_decode_params.causal_tail): 2..8 query tokens, 16-bit caches with rows of D elements.
+int check_causal_tail(const hyd_suffix_params* p, const hyd_kv_quant* kq) {
+    if (p->nq < 2 || p->nq > 8) return fail(HYD_ERR_BAD_ARG, "causal tail: nq = %d query tokens per sequence, 2 to 8 are taken", p->nq);
+    if (kq) return fail(HYD_ERR_UNSUPPORTED, "causal tail with fp8 unique caches: implemented for 16-bit caches only");
+    if (p->kv_len > 0 && narrow_kv_dim(p)) return fail(HYD_ERR_UNSUPPORTED, "causal tail with kv_dim %d: narrow unique rows run on the token-row kernel, which has no causal form", p->kv_dim);
+    return HYD_OK;
+}
+
+int fail_causal_shapes() { return fail(HYD_ERR_UNSUPPORTED, "causal tail: no kernel with the per-row key limit takes these shapes"); }
+
+// kq: null, or fp8 unique caches (validated by check_kvq; K/V strides in bytes).  causal: the causal tail (check_causal_tail passed) --
+// such a call goes to launch_suffix_causal or fails, never to a kernel without the per-row key limit.
+int run_suffix(const hyd_suffix_params* p, const hyd_partial* parts, int n_parts, hipStream_t s, const hyd_kv_quant* kq = nullptr, bool causal = false) {
     SuffixArgs a;
     fill_suffix_args(p, &a);
     int rc = for_each_slice(parts, n_parts, (size_t)p->B * p->nq * p->Hq, p->D, &a.n_partials, [&a](int n, const void* out, const float* lse, int is_f32) {
@@ -407,6 +418,10 @@ int run_suffix(const hyd_suffix_params* p, const hyd_partial* parts, int n_parts
     if ((int64_t)p->kv_len * p->k_tok_stride * esz >= (1ll << 31) || (int64_t)p->kv_len * p->v_tok_stride * esz >= (1ll << 31))
         return fail(HYD_ERR_UNSUPPORTED, "unique K/V of one sequence spans >= 2 GiB (32-bit in-sequence offsets)");
     if (p->Hkv > 4 * 65535 || a.rows > 8 * 65535) return fail(HYD_ERR_UNSUPPORTED, "too many kv heads / query rows for the suffix grid");
+    if (causal) {
+        if (kq || !suffix_causal_eligible(a, p->D)) return fail_causal_shapes();
+        return launched(launch_suffix_causal(a, p->dtype, p->D, s), "causal-tail suffix kernel launch");
+    }
     if (a.kv_dim) {
         if (kq) return fail_narrow_fp8();
         if (!suffix_narrow_eligible(a, p->D)) return fail_narrow_shapes(p);
@@ -556,6 +571,7 @@ constexpr int64_t kSingleLaunchMaxKeys = 8192;
 bool decode_runs_as_one_launch(const hyd_decode_params* p, const LevelPlan& lv) {
     const hyd_suffix_params& sp = p->suffix;
     if (p->phase != HYD_PHASE_ALL || !p->single_launch_small || p->n_levels != 1 || !lv.small || sp.kv_len <= 0) return false;
+    if (p->causal_tail) return false;  // the walk over both segments has no per-row key limit: the pair of launches runs
     if (narrow_kv_dim(&sp)) return false;  // narrow unique caches: the pair of launches runs (the rule Hq == Hkv fp8 calls have)
     if (sp.lse) return false;  // suffix.lse is the LSE of the unique keys alone in every form; one walk over both segments cannot give it
     const hyd_prefix_params& pp = lv.pp;
@@ -740,6 +756,15 @@ int hyd_suffix_attn_fwd_kvq(const hyd_suffix_params* p, const hyd_kv_quant* kq, 
 
 int hyd_suffix_attn_fwd(const hyd_suffix_params* p, void* stream) { return hyd_suffix_attn_fwd_kvq(p, nullptr, stream); }
 
+int hyd_suffix_attn_causal_fwd(const hyd_suffix_params* p, void* stream) {
+    int rc = check_suffix(p, true);
+    if (rc) return rc;
+    if ((rc = check_causal_tail(p, nullptr))) return rc;
+    if (p->n_partials < 0 || p->n_partials > HYD_MAX_LEVELS) return fail(HYD_ERR_BAD_ARG, "n_partials %d", p->n_partials);
+    if (p->kv_len == 0 && p->n_partials == 0) return fail(HYD_ERR_BAD_ARG, "kv_len == 0 and no partials");
+    return run_suffix(p, p->partials, p->n_partials, static_cast<hipStream_t>(stream), nullptr, /*causal=*/true);
+}
+
 int hyd_kv_quant_supported(const hyd_suffix_params* p, const hyd_kv_quant* kq) {
     if (!p) return 0;
     const KvqKind kind = kvq_kind(kq, p->dtype);
@@ -829,6 +854,32 @@ int hyd_rope_append_decode_kvq(const hyd_rope_params* p, const hyd_kv_quant* kq,
 }
 
 int hyd_rope_append_decode(const hyd_rope_params* p, void* stream) { return hyd_rope_append_decode_kvq(p, nullptr, stream); }
+
+int hyd_rope_append_multi(const hyd_rope_multi_params* p, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    if (p->T < 2 || p->T > 8) return fail(HYD_ERR_BAD_ARG, "T = %d tokens per row, 2 to 8 are taken (hyd_rope_append_decode takes one)", p->T);
+    int rc = check_common(p->dtype, p->B, p->T, p->Hq, p->Hkv, p->D);
+    if (rc) return rc;
+    if ((rc = check_ptr_align(p->q, "q")) || (rc = check_ptr_align(p->k, "k")) || (rc = check_ptr_align(p->v, "v")) ||
+        (rc = check_ptr_align(p->q_out, "q_out")) || (rc = check_ptr_align(p->k_cache, "k_cache")) ||
+        (rc = check_ptr_align(p->v_cache, "v_cache")) || (rc = check_ptr_align(p->cos, "cos")) ||
+        (rc = check_ptr_align(p->sin, "sin")))
+        return rc;
+    if (!p->position_ids || !p->seq_lens) return fail(HYD_ERR_BAD_ARG, "position_ids / seq_lens is null");
+    if (misaligned(p->position_ids, 8) || misaligned(p->shared_len, 8) || misaligned(p->seq_lens, 4))
+        return fail(HYD_ERR_BAD_ARG, "position_ids / shared_len / seq_lens is not aligned to its element size");
+    if ((rc = check_stride8(p->q_batch_stride, "q_batch_stride")) || (rc = check_stride8(p->k_batch_stride, "k_batch_stride")) ||
+        (rc = check_stride8(p->v_batch_stride, "v_batch_stride")) || (rc = check_stride8(p->q_tok_stride, "q_tok_stride")) ||
+        (rc = check_stride8(p->k_tok_stride, "k_tok_stride")) || (rc = check_stride8(p->v_tok_stride, "v_tok_stride")) ||
+        (rc = check_stride8(p->kc_batch_stride, "kc_batch_stride")) || (rc = check_stride8(p->kc_tok_stride, "kc_tok_stride")) ||
+        (rc = check_stride8(p->kc_head_stride, "kc_head_stride")) || (rc = check_stride8(p->vc_batch_stride, "vc_batch_stride")) ||
+        (rc = check_stride8(p->vc_tok_stride, "vc_tok_stride")) || (rc = check_stride8(p->vc_head_stride, "vc_head_stride")))
+        return rc;
+    if (p->cs_stride % 4 != 0) return fail(HYD_ERR_BAD_ARG, "cos/sin row stride must be a multiple of 4 floats");
+    if (p->cache_len <= 0) return fail(HYD_ERR_BAD_ARG, "cache_len %d", p->cache_len);
+    if (p->max_pos <= 0) return fail(HYD_ERR_BAD_ARG, "max_pos %d: the cos/sin tables need at least one row", p->max_pos);
+    return launched(launch_rope_append_multi(*p, static_cast<hipStream_t>(stream)), "rope_append (multi-token) kernel launch");
+}
 
 int hyd_add_rmsnorm(const hyd_add_rmsnorm_params* p, void* stream) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
@@ -987,6 +1038,47 @@ int hyd_stop_update(const hyd_stop_params* p, void* stream) {
     a.rows = p->rows; a.t = p->t; a.n_eos = p->n_eos; a.n_stop = p->n_stop;
     a.include_stop = p->include_stop ? 1 : 0; a.retire = p->retire ? 1 : 0;
     return launched(launch_stop_update(a, static_cast<hipStream_t>(stream)), "stop_update kernel launch");
+}
+
+int hyd_draft_lookup(const hyd_draft_lookup_params* p, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    if (p->B < 0) return fail(HYD_ERR_BAD_ARG, "B %d", p->B);
+    if (p->K < 1 || p->K > 7) return fail(HYD_ERR_BAD_ARG, "K = %d drafts per row, 1 to 7 are taken", p->K);
+    if (p->ngram_min < 1 || p->ngram_max < p->ngram_min || p->ngram_max > HYD_DRAFT_MAX_NGRAM)
+        return fail(HYD_ERR_BAD_ARG, "ngram (%d, %d): 1 <= min <= max <= %d", p->ngram_min, p->ngram_max, HYD_DRAFT_MAX_NGRAM);
+    if (p->n_segments < 1 || p->n_segments > HYD_DRAFT_MAX_SEGMENTS)
+        return fail(HYD_ERR_BAD_ARG, "n_segments %d: 1 to %d segments", p->n_segments, HYD_DRAFT_MAX_SEGMENTS);
+    if (!p->drafts || !p->n_proposed) return fail(HYD_ERR_BAD_ARG, "drafts / n_proposed is null");
+    if (misaligned(p->drafts, 8) || misaligned(p->n_proposed, 4)) return fail(HYD_ERR_BAD_ARG, "drafts / n_proposed is not aligned to its element size");
+    if (p->drafts_stride < p->K) return fail(HYD_ERR_BAD_ARG, "drafts_stride %lld < K = %d", (long long)p->drafts_stride, p->K);
+    for (int i = 0; i < p->n_segments; ++i) {
+        const hyd_draft_segment& g = p->segments[i];
+        if (g.div < 1) return fail(HYD_ERR_BAD_ARG, "segment %d: div %d (rows of the batch per row of the segment) must be positive", i, g.div);
+        if (g.len < 0) return fail(HYD_ERR_BAD_ARG, "segment %d: len %d", i, g.len);
+        if (!g.ids && g.len != 0) return fail(HYD_ERR_BAD_ARG, "segment %d: ids is null", i);
+        if (misaligned(g.ids, 8) || misaligned(g.lens_i64, 8) || misaligned(g.lens_i32, 4))
+            return fail(HYD_ERR_BAD_ARG, "segment %d: ids / lens is not aligned to its element size", i);
+    }
+    return launched(launch_draft_lookup(*p, static_cast<hipStream_t>(stream)), "draft_lookup kernel launch");
+}
+
+int hyd_draft_accept(const hyd_draft_accept_params* p, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    if (p->rows < 0) return fail(HYD_ERR_BAD_ARG, "rows %d", p->rows);
+    if (p->T < 1 || p->T > 8) return fail(HYD_ERR_BAD_ARG, "T = %d tokens per row (K = %d drafts): 1 to 8 tokens are taken", p->T, p->T - 1);
+    if (p->n_eos < 0 || p->n_eos > HYD_STOP_MAX_EOS) return fail(HYD_ERR_BAD_ARG, "n_eos %d: 0 to %d EOS ids", p->n_eos, HYD_STOP_MAX_EOS);
+    if (p->max_new_tokens < 1 || p->max_new_tokens > p->out_stride)
+        return fail(HYD_ERR_BAD_ARG, "max_new_tokens %d outside [1, out_stride = %lld]", p->max_new_tokens, (long long)p->out_stride);
+    if (!p->fed || !p->sampled || !p->out || !p->length || !p->reason || !p->stop_index || !p->accepted || !p->live)
+        return fail(HYD_ERR_BAD_ARG, "fed / sampled / out / length / reason / stop_index / accepted / live is null");
+    if (!p->start_pos || !p->feed || !p->next_pos) return fail(HYD_ERR_BAD_ARG, "start_pos / feed / next_pos is null");
+    if (misaligned(p->fed, 8) || misaligned(p->sampled, 8) || misaligned(p->out, 8) || misaligned(p->start_pos, 8) ||
+        misaligned(p->shared_len, 8) || misaligned(p->feed, 8) || misaligned(p->next_pos, 8))
+        return fail(HYD_ERR_BAD_ARG, "fed / sampled / out / start_pos / shared_len / feed / next_pos is not aligned to its element size");
+    if (misaligned(p->length, 4) || misaligned(p->reason, 4) || misaligned(p->stop_index, 4) || misaligned(p->accepted, 4) ||
+        misaligned(p->live, 4) || misaligned(p->logprobs, 4) || misaligned(p->out_logprobs, 4))
+        return fail(HYD_ERR_BAD_ARG, "length / reason / stop_index / accepted / live / logprobs / out_logprobs is not aligned to its element size");
+    return launched(launch_draft_accept(*p, static_cast<hipStream_t>(stream)), "draft_accept kernel launch");
 }
 
 int hyd_kv_promote(const hyd_kv_promote_params* p, void* stream) {
@@ -1321,6 +1413,14 @@ static int decode_impl(const hyd_decode_params* p, const hyd_kv_quant* kq, void*
         if (kq) return fail_narrow_fp8();
         if (!narrow_native(&sp)) return fail_narrow_shapes(&sp);
     }
+    if (p->causal_tail != 0 && p->causal_tail != 1) return fail(HYD_ERR_BAD_ARG, "causal_tail %d", p->causal_tail);
+    const bool causal = p->causal_tail != 0;
+    if (causal && (rc = check_causal_tail(&sp, kq))) return rc;  // in every phase, so that the phases of one call agree
+    if (causal && sp.kv_len > 0) {  // ... and so is a shape no kernel with the per-row key limit takes: before the level passes go out
+        SuffixArgs ca;
+        fill_suffix_args(&sp, &ca);
+        if (!suffix_causal_eligible(ca, sp.D)) return fail_causal_shapes();
+    }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t rows = (size_t)sp.B * sp.nq * sp.Hq;
     const bool do_shared = p->phase == HYD_PHASE_ALL || p->phase == HYD_PHASE_SHARED;
@@ -1395,7 +1495,7 @@ static int decode_impl(const hyd_decode_params* p, const hyd_kv_quant* kq, void*
             hyd_suffix_params su = sp;
             su.out = u_out;
             su.lse = u_lse;
-            return run_suffix(&su, nullptr, 0, s, kq);
+            return run_suffix(&su, nullptr, 0, s, kq, causal);
         }
         CombineArgs c;  // HYD_PHASE_MERGE: every level's partial(s) + the unique partial -> out
         memset(&c, 0, sizeof(c));
@@ -1425,7 +1525,7 @@ static int decode_impl(const hyd_decode_params* p, const hyd_kv_quant* kq, void*
         s0.seq_lens_i64 = nullptr;
         return run_suffix(&s0, parts, p->n_levels, s);
     }
-    return run_suffix(&sp, parts, p->n_levels, s, kq);
+    return run_suffix(&sp, parts, p->n_levels, s, kq, causal);
 }
 
 int hyd_decode_two_stream_ok(const hyd_decode_params* p) {

@@ -318,6 +318,12 @@ int launch_suffix_gqa_fp8(const SuffixKvqArgs& a, int dtype, int D, hipStream_t 
 int launch_rope_append_fp8(const RopeKvqArgs& a, int dtype, int D, hipStream_t s);
 int launch_rope_append_narrow(const RopeNarrowArgs& a, int dtype, hipStream_t s);      // 16-bit caches, head_dim d < D
 int launch_suffix_gqa(const SuffixArgs& a, int dtype, int D, hipStream_t s);
+bool suffix_causal_eligible(const SuffixArgs& a, int D);                              // suffix_attn_causal.hip, shapes only
+int launch_suffix_causal(const SuffixArgs& a, int dtype, int D, hipStream_t s);       // the causal-tail suffix pass (nq = 2..8)
+// speculative decoding: these kernels take the validated public parameter blocks as they are
+int launch_rope_append_multi(const hyd_rope_multi_params& p, hipStream_t s);          // rope_append.hip
+int launch_draft_lookup(const hyd_draft_lookup_params& p, hipStream_t s);             // draft_lookup.hip
+int launch_draft_accept(const hyd_draft_accept_params& p, hipStream_t s);             // draft_accept.hip
 int launch_combine(const CombineArgs& a, hipStream_t s);
 size_t allreduce_block_bytes(int world, size_t max_bytes);
 int launch_allreduce(char* const* blocks, size_t block_bytes, const void* in, void* out, int64_t count, int dtype,

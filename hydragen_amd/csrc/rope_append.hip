@@ -271,6 +271,86 @@ int launch_rope_append_fp8(const RopeKvqArgs& ka, int dtype, int D, hipStream_t 
     return (int)hipGetLastError();
 }
 
+// Multi-token decode step (hyd_rope_append_multi): q / k / v are [B, T, H, D], the row's position is that of its FIRST token and
+// token i is rotated at position + i and appended at cache index idx + i, idx = position - shared length; seq_lens[b] = idx + T.
+// The thread layout of rope_append_kernel with the token as one more row index.  A row with idx < 0 (position shared_len - 1: a
+// retired row) takes no part at all -- idx + i >= 0 for its later tokens must not write --, so the guard is on idx, then on the
+// token's own index against cache_len.  K/V rows of drafts that the step rejects stay in the cache behind the row's next length:
+// nothing reads them (every kernel stops at seq_len), and the next step, which starts behind the last accepted token and writes T
+// rows again, overwrites them.
+template <typename T, int D>
+__global__ __launch_bounds__(256) void rope_append_multi_kernel(const hyd_rope_multi_params a) {
+    constexpr int TPR = D / 16;
+    const int rows_per_t = a.Hq + 2 * a.Hkv;
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t row = gid / TPR;
+    const int sub = (int)(gid % TPR);
+    if (row >= (int64_t)a.B * a.T * rows_per_t) return;
+    const int h = (int)(row % rows_per_t);
+    const int64_t bt = row / rows_per_t;
+    const int b = (int)(bt / a.T), i = (int)(bt % a.T);
+    const int64_t pos0 = a.position_ids[(int64_t)b * a.pos_stride];
+    const int64_t idx0 = pos0 - (a.shared_len ? a.shared_len[b] : 0);
+    const int64_t idx = idx0 + i, pos_raw = pos0 + i;
+    const int64_t pos = pos_raw < 0 ? 0 : (pos_raw >= a.max_pos ? (int64_t)a.max_pos - 1 : pos_raw);
+    if (h == 0 && sub == 0 && i == 0) a.seq_lens[b] = idx0 >= 0 ? (int32_t)(idx0 + a.T) : 0;
+    const bool store_kv = idx0 >= 0 && idx < a.cache_len;  // never write out of bounds, never for a retired row
+    const int d0 = sub * 8;
+    if (h < a.Hq + a.Hkv) {
+        const bool isq = h < a.Hq;
+        if (!isq && !store_kv) return;
+        const uint16_t* src = isq ? static_cast<const uint16_t*>(a.q) + (int64_t)b * a.q_batch_stride + (int64_t)i * a.q_tok_stride + (int64_t)h * D
+                                  : static_cast<const uint16_t*>(a.k) + (int64_t)b * a.k_batch_stride + (int64_t)i * a.k_tok_stride + (int64_t)(h - a.Hq) * D;
+        const u32x4 lo = *reinterpret_cast<const u32x4*>(src + d0);
+        const u32x4 hi = *reinterpret_cast<const u32x4*>(src + D / 2 + d0);
+        float c[8], s[8];
+        const float* cr = a.cos + pos * a.cs_stride + d0;
+        const float* sr = a.sin + pos * a.cs_stride + d0;
+        const f32x4 c0 = *reinterpret_cast<const f32x4*>(cr), c1 = *reinterpret_cast<const f32x4*>(cr + 4);
+        const f32x4 s0 = *reinterpret_cast<const f32x4*>(sr), s1 = *reinterpret_cast<const f32x4*>(sr + 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            c[j] = c0[j];
+            c[4 + j] = c1[j];
+            s[j] = s0[j];
+            s[4 + j] = s1[j];
+        }
+        u32x4 olo, ohi;
+        rope8<T>(lo, hi, c, s, olo, ohi);
+        uint16_t* dst = isq ? static_cast<uint16_t*>(a.q_out) + (bt * a.Hq + h) * D
+                            : static_cast<uint16_t*>(a.k_cache) + (int64_t)b * a.kc_batch_stride + idx * a.kc_tok_stride + (int64_t)(h - a.Hq) * a.kc_head_stride;
+        *reinterpret_cast<u32x4*>(dst + d0) = olo;
+        *reinterpret_cast<u32x4*>(dst + D / 2 + d0) = ohi;
+    } else {
+        if (!store_kv) return;
+        const int hv = h - a.Hq - a.Hkv;
+        const uint16_t* src = static_cast<const uint16_t*>(a.v) + (int64_t)b * a.v_batch_stride + (int64_t)i * a.v_tok_stride + (int64_t)hv * D;
+        uint16_t* dst = static_cast<uint16_t*>(a.v_cache) + (int64_t)b * a.vc_batch_stride + idx * a.vc_tok_stride + (int64_t)hv * a.vc_head_stride;
+        *reinterpret_cast<u32x4*>(dst + d0) = *reinterpret_cast<const u32x4*>(src + d0);
+        *reinterpret_cast<u32x4*>(dst + D / 2 + d0) = *reinterpret_cast<const u32x4*>(src + D / 2 + d0);
+    }
+}
+
+int launch_rope_append_multi(const hyd_rope_multi_params& p, hipStream_t s) {
+    const int64_t threads = (int64_t)p.B * p.T * (p.Hq + 2 * p.Hkv) * (p.D / 16);
+    const int grid = (int)((threads + 255) / 256);
+    if (grid == 0) return 0;
+#define HYD_ROPE(TT, DD) hipLaunchKernelGGL((rope_append_multi_kernel<TT, DD>), dim3(grid), dim3(256), 0, s, p)
+    if (p.dtype == HYD_F16) {
+        if (p.D == 128) HYD_ROPE(F16, 128);
+        else if (p.D == 64) HYD_ROPE(F16, 64);
+        else if (p.D == 256) HYD_ROPE(F16, 256);
+        else return (int)hipErrorInvalidValue;
+    } else {
+        if (p.D == 128) HYD_ROPE(BF16, 128);
+        else if (p.D == 64) HYD_ROPE(BF16, 64);
+        else if (p.D == 256) HYD_ROPE(BF16, 256);
+        else return (int)hipErrorInvalidValue;
+    }
+#undef HYD_ROPE
+    return (int)hipGetLastError();
+}
+
 int launch_rope_append(const RopeArgs& a, int dtype, int D, hipStream_t s) {
     const int64_t threads = (int64_t)a.B * (a.Hq + 2 * a.Hkv) * (D / 16);
     const int grid = (int)((threads + 255) / 256);

@@ -379,7 +379,7 @@ def _narrow_kv_shapes(qshape, qdtype, kshape, kstride, vstride) -> bool:
 
 
 def flash_attention_seqlen(raw_q: Tensor, raw_k: Tensor, raw_v: Tensor, seq_len=None, *, k_scale: Tensor | None = None,
-                           v_scale: Tensor | None = None):
+                           v_scale: Tensor | None = None, causal_tail: bool = False):
     """
     q shape: [batch, qseq_len, qheads, dim]
     k shape: [batch, kseq_len, kheads, dim]
@@ -389,11 +389,17 @@ def flash_attention_seqlen(raw_q: Tensor, raw_k: Tensor, raw_v: Tensor, seq_len=
     (flash.py:163-281).  Returns (out [b, q, h, d], lse [b, q, h] fp32, natural log).
     seq_len may be int32 or int64 (no cast kernel, cf. flash.py:220); None = all keys.
     k / v may be float8_e4m3fn caches (kv_quant.py) with per-kv-head fp32 scales k_scale / v_scale ([Hkv], None = 1).
+    causal_tail=True (a multi-token decode step, hyd_suffix_attn_causal_fwd): the T = qseq_len queries (2..8) are the LAST T
+    tokens of their sequences and their keys are in k / v already, so query i sees the keys below seq_len[b] - (T - 1 - i).
+    16-bit caches of head dim 64 / 128 / 256 only; everything else raises NotImplementedError (never a non-causal result).
     """
     _require_gpu(raw_q, raw_k, raw_v, seq_len)
     assert raw_q.ndim == 4 and raw_k.ndim == 4 and raw_v.ndim == 4
     assert raw_k.shape == raw_v.shape
     fp8 = check_kv_pair(raw_k, raw_v, k_scale, v_scale)
+    if causal_tail and (fp8 or raw_k.shape[-1] not in (64, 128, 256) or raw_q.shape[-1] != raw_k.shape[-1]):
+        raise NotImplementedError(f"causal_tail: 16-bit caches of head dim 64 / 128 / 256 only (got {raw_k.dtype}, head dims "
+                                  f"{raw_q.shape[-1]} / {raw_k.shape[-1]})")
     narrow = not fp8 and narrow_kv_native(raw_q, raw_k, raw_v)
     # (narrow unique caches: q may arrive padded to the kernels' head dim already, with zero pad columns)
     assert raw_q.shape[-1] == raw_k.shape[-1] or narrow, (
@@ -443,6 +449,6 @@ def flash_attention_seqlen(raw_q: Tensor, raw_k: Tensor, raw_v: Tensor, seq_len=
     keep = fill_suffix_params(p, q, k, v, seq_len, out)
     p.lse = lse.data_ptr()
     p.n_partials = 0
-    _lib.check(lib.hyd_suffix_attn_fwd(C.byref(p), _stream()))
+    _lib.check((lib.hyd_suffix_attn_causal_fwd if causal_tail else lib.hyd_suffix_attn_fwd)(C.byref(p), _stream()))
     del keep
     return out, lse

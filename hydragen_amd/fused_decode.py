@@ -13,6 +13,48 @@ from ._lib import RopeParams
 from .flash import _dtype_code, _require_gpu, _stream, check_kv_pair, kv_quant_params, padded_head_dim
 
 
+def rope_append_multi(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, position_ids: Tensor,
+                      shared_len: Tensor | None, k_cache: Tensor, v_cache: Tensor):
+    """hyd_rope_append_multi: the preamble of a MULTI-TOKEN decode step (speculative.py).  q [B,T,Hq,D], k/v [B,T,Hkv,D] with
+    2 <= T <= 8, position_ids int64 [B] or [B, T] (column 0 is read: the first token's absolute position, token i uses + i),
+    shared_len int64 [B] or None, 16-bit caches [maxB, maxS, Hkv, D] with D 64 / 128 / 256.  Returns (rotated q [B,T,Hq,D],
+    seq_lens int32 [B] = cache index of the first token + T); K (rotated) and V of token i are written at that index + i.  A
+    row at position shared_len - 1 writes nothing and reports length 0."""
+    _require_gpu(q, k, v, cos, sin, position_ids, k_cache, v_cache)
+    if check_kv_pair(k_cache, v_cache, None, None):
+        raise NotImplementedError("multi-token decode steps with fp8 unique caches: 16-bit caches only")
+    B, T, Hq, D = q.shape
+    if D not in (64, 128, 256) or k_cache.shape[-1] != D:
+        raise NotImplementedError(f"head_dim {D} (caches {k_cache.shape[-1]}): the multi-token preamble takes 64 / 128 / 256")
+    Hkv = k.shape[2]
+    assert k.shape == (B, T, Hkv, D) and v.shape == k.shape and B <= k_cache.shape[0]
+    for x in (q, k, v):
+        assert x.stride(3) == 1 and x.stride(2) == D, "heads contiguous"
+    assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.stride(1) == 1
+    assert position_ids.dtype == torch.int64 and position_ids.shape[0] == B
+    q_out = torch.empty((B, T, Hq, D), dtype=q.dtype, device=q.device)
+    seq_lens = torch.empty((B,), dtype=torch.int32, device=q.device)
+    p = _lib.RopeMultiParams()
+    p.q, p.k, p.v, p.q_out = q.data_ptr(), k.data_ptr(), v.data_ptr(), q_out.data_ptr()
+    p.k_cache, p.v_cache = k_cache.data_ptr(), v_cache.data_ptr()
+    p.cos, p.sin = cos.data_ptr(), sin.data_ptr()
+    p.position_ids = position_ids.data_ptr()
+    if shared_len is not None:
+        assert shared_len.dtype == torch.int64 and shared_len.shape == (B,)
+        shared_len = shared_len.contiguous()
+        p.shared_len = shared_len.data_ptr()
+    p.seq_lens = seq_lens.data_ptr()
+    p.q_batch_stride, p.k_batch_stride, p.v_batch_stride = q.stride(0), k.stride(0), v.stride(0)
+    p.q_tok_stride, p.k_tok_stride, p.v_tok_stride = q.stride(1), k.stride(1), v.stride(1)
+    p.kc_batch_stride, p.kc_tok_stride, p.kc_head_stride = k_cache.stride(0), k_cache.stride(1), k_cache.stride(2)
+    p.vc_batch_stride, p.vc_tok_stride, p.vc_head_stride = v_cache.stride(0), v_cache.stride(1), v_cache.stride(2)
+    p.pos_stride, p.cs_stride = position_ids.stride(0), cos.stride(0)
+    p.dtype, p.B, p.T, p.Hq, p.Hkv, p.D, p.cache_len = _dtype_code(q), B, T, Hq, Hkv, D, k_cache.shape[1]
+    p.max_pos = cos.shape[0]
+    _lib.check(_lib.load().hyd_rope_append_multi(C.byref(p), _stream()))
+    return q_out, seq_lens
+
+
 def rope_append_decode(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, position_ids: Tensor,
                        shared_len: Tensor | None, k_cache: Tensor, v_cache: Tensor, *, k_scale: Tensor | None = None,
                        v_scale: Tensor | None = None):

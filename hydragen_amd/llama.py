@@ -23,7 +23,7 @@ from typing import List, Optional, Union
 import torch
 from torch import Tensor, nn
 
-from . import layer_ops, placement, sampling, scoring, stopping
+from . import layer_ops, placement, sampling, scoring, speculative, stopping
 from .attention import hydragen_attention
 from . import flash as _flash
 from .flash import flash_attention, flash_attention_seqlen, padded_head_dim
@@ -473,9 +473,8 @@ class AttentionMode:
     DECODE = "decode"
 
 
-def hydragen_attention_on_caches(q, k, v, shared_caches: list[SharedCache], seq_len: Optional[Tensor] = None, **scales):
-    """llama.py:355-414: adapt the caches to the operator's arguments (views only, no copies).  scales: k_scale / v_scale of
-    fp8 unique caches."""
+def shared_level_args(shared_caches: list[SharedCache]) -> dict:
+    """The shared caches as the attention operators' level arguments (views only, no copies)."""
     keys, values, cu_seqlens, max_seqlens, use_varlens = [], [], [], [], []
     for sc in shared_caches:
         if sc.use_varlen:
@@ -490,8 +489,13 @@ def hydragen_attention_on_caches(q, k, v, shared_caches: list[SharedCache], seq_
             cu_seqlens.append(None)
             max_seqlens.append(None)
         use_varlens.append(sc.use_varlen)
-    return hydragen_attention(q, k, v, shared_ks=keys, shared_vs=values, shared_cu_seq_lens=cu_seqlens,
-                              shared_max_seq_lens=max_seqlens, use_varlens=use_varlens, seq_lens=seq_len, **scales)
+    return dict(shared_ks=keys, shared_vs=values, shared_cu_seq_lens=cu_seqlens, shared_max_seq_lens=max_seqlens, use_varlens=use_varlens)
+
+
+def hydragen_attention_on_caches(q, k, v, shared_caches: list[SharedCache], seq_len: Optional[Tensor] = None, **scales):
+    """llama.py:355-414: adapt the caches to the operator's arguments.  scales: k_scale / v_scale of fp8 unique caches (and
+    causal_tail of a multi-token decode step)."""
+    return hydragen_attention(q, k, v, **shared_level_args(shared_caches), seq_lens=seq_len, **scales)
 
 
 class HydragenLlamaAttention(nn.Module):
@@ -520,6 +524,41 @@ class HydragenLlamaAttention(nn.Module):
         self.use_fused_decode = True
         self._qkv: Optional[Tensor] = None
 
+    def _decode_multi(self, q, k, v, cos, sin, position_ids, shared_len):
+        """Attention of a MULTI-TOKEN decode step (speculative.py): q / k / v [B, T, H, D] are T consecutive tokens per row,
+        position_ids [B, T] their absolute positions (column 0 + i).  With the fused preamble: hyd_rope_append_multi, then the
+        causal-tail operator; otherwise, and for a call the library refuses, the definition assembled from existing operators
+        (speculative.assembled_causal_tail_attention).  Every token sees all shared keys and the unique keys up to itself."""
+        bsz, q_len = q.shape[:2]
+        kvc = self.kv_cache
+        if not 2 <= q_len <= speculative.MAX_DRAFTS + 1:
+            raise NotImplementedError(f"a decode step feeds 1 to {speculative.MAX_DRAFTS + 1} tokens per row, got {q_len}")
+        if kvc.fp8 or kvc.narrow or self.head_dim not in (64, 128, 256) or self.disable_attention:
+            raise NotImplementedError("multi-token decode steps take 16-bit unique caches of head dim 64 / 128 / 256 (no fp8 caches, no "
+                                      "narrow head dims, no disable_attention)")
+        if self.disable_hydragen:
+            shared_len = None
+        elif shared_len is None:
+            shared_len = kvc.get_shared_len(bsz)
+        shared = [] if self.disable_hydragen else kvc.get_used_shared_caches()
+        if self.use_fused_decode:
+            from .fused_decode import rope_append_multi
+
+            q, seq_lens = rope_append_multi(q, k, v, cos, sin, position_ids, shared_len, kvc.per_completion_k_cache, kvc.per_completion_v_cache)
+            ks, vs = kvc.per_completion_k_cache[:bsz], kvc.per_completion_v_cache[:bsz]
+            try:
+                if not shared:
+                    return flash_attention_seqlen(q, ks, vs, seq_len=seq_lens, causal_tail=True)[0]
+                return hydragen_attention_on_caches(q, ks, vs, shared, seq_len=seq_lens, causal_tail=True)
+            except NotImplementedError:  # a shape the library refuses: the same attention from the existing launches
+                pass
+        else:
+            unique_position_ids = position_ids if shared_len is None else position_ids - shared_len.unsqueeze(-1)
+            q, k = apply_rotary_pos_emb(q, k, cos, sin, position_ids)
+            ks, vs = kvc.update_per_completion_kvs(unique_position_ids, k, v)
+            seq_lens = unique_position_ids[:, -1] + 1
+        return speculative.assembled_causal_tail_attention(q, ks, vs, seq_lens, **shared_level_args(shared))
+
     def forward(self, hidden_states: Tensor, position_ids: Tensor, shared_len: Optional[Tensor] = None):
         """shared_len: the per-sequence total shared length [B] (get_shared_len) when the caller already has it -- it is
         the same for every layer of a forward pass, and computing it is three small launches (~17 us) per layer."""
@@ -535,6 +574,9 @@ class HydragenLlamaAttention(nn.Module):
         v = v.view(bsz, q_len, self.num_key_value_heads, self.head_dim)
         cos, sin = self.rotary_emb.cos_cached, self.rotary_emb.sin_cached
 
+        if self.mode == AttentionMode.DECODE and q_len > 1:
+            out = self.o_proj(self._decode_multi(q, k, v, cos, sin, position_ids, shared_len).reshape(bsz, q_len, -1))
+            return all_reduce_sum(out) if self.tp_reduce else out
         fused = self.mode == AttentionMode.DECODE and self.use_fused_decode and q_len == 1
         if fused:
             # one HIP kernel: RoPE(q, k) at absolute positions, append k/v at (position - shared length),
@@ -692,7 +734,7 @@ class HydragenLlamaModel(nn.Module):
         # filled in lockstep, so every layer would compute the same [B] tensor with three small launches
         a0 = layers[0].self_attn
         shared_len = None
-        if a0.mode == AttentionMode.DECODE and a0.kv_cache is not None and not a0.disable_hydragen and h.shape[1] == 1:
+        if a0.mode == AttentionMode.DECODE and a0.kv_cache is not None and not a0.disable_hydragen and h.shape[1] <= 8:
             shared_len = a0.kv_cache.get_shared_len(h.shape[0])
         for i, layer in enumerate(layers):
             post = layer.post_attention_layernorm
@@ -818,6 +860,7 @@ class _DecodeCall:
     pen: Optional[layer_ops.Penalties] = None  # the penalties, if they keep a list of generated tokens (a bias alone does not)
     raw: bool = False                          # the steps' logits stay in the lm_head's dtype
     graphed: bool = False
+    draft: Optional[dict] = None               # speculative decoding: k, given drafts or None, ngram, the call's segments, stats
 
     def keep(self, logits, tok, lp):
         """Record a step's returned log-probs and alternatives."""
@@ -1246,11 +1289,13 @@ class HydragenLlamaForCausalLM(nn.Module):
             return pairs, None
         return pairs[:-1], pairs[-1]
 
-    def _check_room(self, start_positions, new_tokens):
+    def _check_room(self, start_positions, new_tokens, extra=0):
         """The fused decode preamble cannot raise from the device: refuse on the host anything that would index past
-        the unique cache or the rotary tables (the reference's scatter_/index ops device-assert)."""
+        the unique cache or the rotary tables (the reference's scatter_/index ops device-assert).  extra: the K
+        draft tokens a speculative step feeds behind a row's last token -- K more cache rows and positions."""
         if new_tokens < 2:
             return  # the first token comes from the prefill logits: no decode step runs
+        new_tokens += extra
         room = self.model.layers[0].self_attn.kv_cache.per_completion_k_cache.shape[1]
         last_pos = int(start_positions.max().item()) + new_tokens - 2
         # cache index = position - shared length, PER SEQUENCE (llama.py:487-492 of the reference): with ragged shared
@@ -1277,8 +1322,23 @@ class HydragenLlamaForCausalLM(nn.Module):
                  return_logprobs: bool = False, top_logprobs: int = 0, repetition_penalty: Optional[float] = None,
                  presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None, logit_bias=None,
                  stop=None, pad_token_id: Optional[int] = None, include_stop: bool = False, return_finish: bool = False,
-                 constraint=None, constraint_state: Optional[Tensor] = None, return_constraint_state: bool = False):
-        """Sampling: top_k / top_p / min_p cut the UNSCALED softmax(logits) (the reference's top-p order; HF applies the
+                 constraint=None, constraint_state: Optional[Tensor] = None, return_constraint_state: bool = False,
+                 draft_tokens: Optional[int] = None, draft="prompt_lookup", ngram=(1, 3), return_draft_stats: bool = False):
+        """Speculative decoding (hydragen_amd/speculative.py states the scheme and why it is lossless): draft_tokens = K in 1..7
+        makes every decode step feed each row its last token and K drafts, verify them in ONE forward pass over [B, K + 1] (the
+        multi-token RoPE + append, the causal-tail attention) and keep the draws up to the first wrong draft; None or 0 runs
+        exactly the launches generate() runs without it.  draft = "prompt_lookup": drafts are the tokens that followed the latest
+        earlier occurrence of the row's last n-gram (ngram = (min, max) lengths, longest first) in the prompt levels GIVEN TO THIS
+        CALL on the row's path, its own prompt and its generated tokens (hyd_draft_lookup; levels kept by earlier calls with
+        shared_cache_op="extend" are not searched -- their ids are not given to this call); or an int tensor [B, max_new_tokens]
+        whose column p is the draft for output position p (tests, benchmarks; no lookup launch).  Rows advance by different
+        amounts; EOS ids and max_new_tokens are applied on the device (hyd_draft_accept) and the result is [B, max(lengths)] padded
+        with pad_token_id, as on the stop path (an int eos_token_id is treated as a list of one).  return_draft_stats appends a
+        speculative.DraftStats(steps, proposed, accepted) as the last return value.  Works with temperature, top_k / top_p /
+        min_p, return_logprobs, eos_token_id, pad_token_id, return_finish, num_return_sequences, seq_lens and shared_cache_op;
+        refused (before any launch): penalties and logit_bias, constraint, stop, token_overrides, top_logprobs, return_logits,
+        disable_hydragen / disable_attention / disable_hierarchy, fp8 or narrow unique caches, a model on the CPU.
+        Sampling: top_k / top_p / min_p cut the UNSCALED softmax(logits) (the reference's top-p order; HF applies the
         temperature first), then a token is drawn from softmax(logits / temperature) over the kept tokens.  Returns the
         tokens [B, generated]; return_logits adds the per-step fp32 logits, return_logprobs the fp32 [B, generated]
         log softmax(logits) of every returned token (unscaled, unfiltered): (out, logits, logprobs) in that order.
@@ -1329,8 +1389,22 @@ class HydragenLlamaForCausalLM(nn.Module):
             sampling.check_constraint(constraint, self.vocab_size)
             if constraint.next.device != self.lm_head.weight.device:
                 constraint = constraint.to(self.lm_head.weight.device)
+        spec_draft = None
+        if draft_tokens:
+            spec_draft = self._check_draft(
+                draft_tokens, draft, ngram, max_new_tokens,
+                {"repetition / presence / frequency penalties or logit_bias": sampling.penalties_active(
+                    repetition_penalty, presence_penalty, frequency_penalty, logit_bias),
+                 "constraint": constraint is not None, "stop": stop is not None, "token_overrides": token_overrides is not None,
+                 "top_logprobs": bool(top_logprobs), "return_logits": return_logits, "disable_hydragen": disable_hydragen,
+                 "disable_attention": disable_attention, "disable_hierarchy": disable_hierarchy},
+                n_given=0 if input_ids is None else 1 if isinstance(input_ids, Tensor) else len(input_ids))
+            if eos_token_id is not None and not isinstance(eos_token_id, (list, tuple, Tensor)):
+                eos_token_id = [eos_token_id]
+        elif return_draft_stats:
+            raise ValueError("return_draft_stats needs draft_tokens")
         stop_spec = None
-        if isinstance(eos_token_id, (list, tuple)) or stop is not None or pad_token_id is not None or return_finish:
+        if isinstance(eos_token_id, (list, tuple)) or stop is not None or pad_token_id is not None or return_finish or spec_draft:
             if token_overrides is not None:
                 raise ValueError("token_overrides (teacher forcing) has nothing to stop: it cannot be combined with a list of EOS ids, "
                                  "stop, pad_token_id or return_finish")
@@ -1394,6 +1468,13 @@ class HydragenLlamaForCausalLM(nn.Module):
             call = _DecodeCall(sample=samp, fan=num_return_sequences, max_new_tokens=max_new_tokens, top_n=top_n,
                                state=state if return_constraint_state else None, logits=[] if return_logits else None,
                                logprobs=[] if return_logprobs else None, top=([], []) if top_n else None)
+            if spec_draft is not None:
+                # the logical context of the lookup: the levels given to THIS call, outermost first, then the rows' own prompts
+                # (moved to the model's device: hyd_draft_lookup reads them there every step, whatever device the caller's ids are on)
+                dev = self.lm_head.weight.device
+                given = [speculative.Segment(ids.to(dev).long(), None if lens is None else lens.to(dev).long())
+                         for ids, lens in shared + ([unique] if unique is not None else [])]
+                call.draft = dict(spec_draft, segments=given, stats=return_draft_stats)
             return self._decode(logits[:, -1], unique, call, eos_token_id, token_overrides, stop_spec, return_finish)
         finally:
             self._scale_windows("close_scale_window", write=False)  # (a call that raised before its first write)
@@ -1611,7 +1692,7 @@ class HydragenLlamaForCausalLM(nn.Module):
         start = self.get_shared_cache_len(first.shape[0])[:, None]
         if unique is not None:
             start = start + unique[1].long().repeat_interleave(fan, 0)[:, None]
-        self._check_room(start, call.max_new_tokens)
+        self._check_room(start, call.max_new_tokens, extra=call.draft["k"] if call.draft else 0)
         feed = first if token_overrides is None else token_overrides[:, 0:1]
         if call.pen is not None and not pen.append:
             pen.push(feed)
@@ -1635,6 +1716,8 @@ class HydragenLlamaForCausalLM(nn.Module):
                 order = self.seq_order_buf[: lens0.numel()]
                 order.copy_(_flash.longest_first(lens0))
         with _flash.seq_order(order, check=False):
+            if call.draft is not None:
+                return self._decode_steps_draft(call, first, start, stop_spec, return_finish)
             if stop_spec is not None:
                 return self._decode_steps_stop(call, first, start, stop_spec, return_finish)
             return self._decode_steps(call, first, feed, start, eos_token_id, token_overrides)
@@ -1733,3 +1816,114 @@ class HydragenLlamaForCausalLM(nn.Module):
         width = int(length.max().item()) if B else 0  # (the one synchronisation of the generation)
         past = torch.arange(width, device=dev)[None, :] >= length[:, None]
         return call.result(out[:, :width], past, stopping.Finish(length, reason, stop_index) if return_finish else None)
+
+    # ---- speculative decoding (hydragen_amd/speculative.py) -----------------------------------------------------------------
+    def _check_draft(self, draft_tokens, draft, ngram, max_new_tokens, refused: dict, n_given: int = 0) -> dict:
+        """generate()'s draft arguments, checked before any launch -> dict(k, given, ngram).  n_given: the prompt levels given to
+        the call (each is a segment of the lookup's table, beside the generated tokens)."""
+        k = speculative.check_draft_tokens(draft_tokens)
+        for what, on in refused.items():
+            if on:
+                raise NotImplementedError(f"draft_tokens cannot be combined with {what}: a speculative step draws and accepts "
+                                          "several tokens per row in launches that do not carry it")
+        given = None
+        if isinstance(draft, Tensor):
+            if draft.ndim != 2 or draft.shape[1] != max_new_tokens or draft.is_floating_point() or draft.dtype == torch.bool:
+                raise ValueError(f"draft: an int tensor [batch, max_new_tokens = {max_new_tokens}], got {tuple(draft.shape)} {draft.dtype}")
+            given = draft
+        elif not isinstance(draft, str) or draft != "prompt_lookup":
+            raise ValueError(f"draft = {draft!r}: 'prompt_lookup' or an int tensor [batch, max_new_tokens]")
+        elif n_given + 1 > speculative.MAX_SEGMENTS:
+            raise ValueError(f"draft='prompt_lookup' searches {n_given} given levels and the generated tokens: at most "
+                             f"{speculative.MAX_SEGMENTS} segments (hyd_draft_lookup)")
+        ngram = speculative.check_ngram(ngram)
+        attn = self.model.layers[0].self_attn
+        if attn.kv_cache.fp8 or attn.kv_cache.narrow or attn.head_dim not in (64, 128, 256):
+            raise NotImplementedError("draft_tokens with fp8 unique caches or a head dim other than 64 / 128 / 256: the multi-token "
+                                      "preamble and the causal-tail suffix pass take 16-bit caches of those head dims only")
+        if not self.lm_head.weight.is_cuda:
+            raise ValueError("draft_tokens: drafts are proposed, verified and accepted by HIP kernels, the model must be on the GPU "
+                             "(speculative.prompt_lookup_reference / accept_reference state the rules in torch)")
+        return dict(k=k, given=given, ngram=ngram)
+
+    def _decode_steps_draft(self, call: _DecodeCall, first, start, spec, return_finish):
+        """The decode loop with draft_tokens = K: per step the drafts (hyd_draft_lookup, or a gather from the given ones), ONE
+        forward over [B, K + 1] with all its logits, one draw per logits row along the call's route, then hyd_draft_accept, which
+        keeps the output matrix, the lengths and the finish reasons and hands back each row's next token and position.  The host
+        polls the running-row count every stop_poll_steps steps, exactly like _decode_steps_stop."""
+        dev, B = first.device, first.shape[0]
+        d = call.draft
+        K, mx = d["k"], call.max_new_tokens
+        T = K + 1
+        fused = all(l.self_attn.use_fused_decode for l in self.model.layers)
+        retire = fused if self.stop_retire is None else bool(self.stop_retire)
+        if retire and not fused:
+            raise ValueError("stop_retire needs the fused decode preamble (use_fused_decode) in every layer")
+        shared_len = self.get_shared_cache_len(B).contiguous()
+        start_pos = start.reshape(-1).long().contiguous()
+        want_lp = call.logprobs is not None
+        out, length, reason, stop_index, out_lp = speculative.new_state(B, mx, spec.pad, dev, want_lp)
+        live = torch.zeros((mx,), dtype=torch.int32, device=dev)
+        eos = spec.eos
+
+        def accept(fed, sampled, lp, slot):
+            return speculative.draft_accept(fed, sampled, out, length, reason, stop_index, live[slot : slot + 1], start_pos, shared_len,
+                                            eos, spec.pad, mx, retire, lp, out_lp if lp is not None else None)
+
+        # the first token, drawn from the prefill logits, enters like a step of one token
+        first = first.reshape(B, 1).long()
+        feed, pos, _ = accept(first, first, call.logprobs[0].reshape(B, 1).float() if want_lp else None, 0)
+        given = d["given"]
+        if given is not None:
+            if given.shape[0] != B:
+                raise ValueError(f"draft holds {given.shape[0]} rows for a batch of {B}")
+            given = given.to(dev).long()
+        segments = d["segments"] + [speculative.Segment(out, length)]
+        cols = torch.arange(K, device=dev)[None, :]
+        offs = torch.arange(T, device=dev)[None, :]
+        fed = torch.full((B, T), spec.pad, dtype=torch.int64, device=dev)
+        proposed = torch.zeros((B,), dtype=torch.int64, device=dev)
+        accepted = torch.zeros((B,), dtype=torch.int64, device=dev)
+        poll = max(1, int(self.stop_poll_steps))
+        polled = getattr(self, "_stop_polled", None)
+        if polled is None or polled.numel() < mx // poll + 1:
+            polled = self._stop_polled = torch.empty((max(mx // poll + 1, 512),), dtype=torch.int32).pin_memory()
+        pending = None
+        steps = 0
+        for step in range(1, mx):
+            fed[:, 0] = feed
+            # a draft counts as proposed when accepting it can add a token: the one for output position p lets the draw for p + 1
+            # out, so a row with `length` tokens has room for max_new_tokens - 1 - length of them (0 for a finished row)
+            room = (mx - 1 - length).clamp_(min=0) * (reason == 0)
+            if given is not None:
+                fed[:, 1:] = given.gather(1, (length.long()[:, None] + cols).clamp_(max=mx - 1))
+                proposed += room.clamp(max=K)
+            else:
+                _, n_prop = speculative.draft_lookup(segments, B, K, d["ngram"], out=fed[:, 1:])
+                proposed += torch.minimum(n_prop, room)
+            logits = self(input_ids=fed, position_ids=pos[:, None] + offs, use_graph=call.graphed, full_logits=True, raw_logits=call.raw)
+            tok, lp = draw_tokens(call.route, logits.reshape(B * T, -1), **call.sample)
+            feed, pos, acc = accept(fed, tok.reshape(B, T), lp.reshape(B, T).float() if want_lp else None, step)
+            accepted += acc
+            steps += 1
+            if pending is not None:
+                slot, ev = pending
+                ev.synchronize()
+                pending = None
+                if int(polled[slot]) == 0:
+                    break
+            if steps % poll == 0 and step + 1 < mx:
+                slot = steps // poll
+                polled[slot : slot + 1].copy_(live[step : step + 1], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                pending = (slot, ev)
+        check_collectives()
+        width = int(length.max().item()) if B else 0  # (the one synchronisation of the generation)
+        past = torch.arange(width, device=dev)[None, :] >= length[:, None]
+        if want_lp:
+            call.logprobs = [out_lp]
+        ret = call.result(out[:, :width], past, stopping.Finish(length, reason, stop_index) if return_finish else None)
+        if d["stats"]:
+            ret = (ret if isinstance(ret, tuple) else (ret,)) + (speculative.DraftStats(steps, proposed, accepted),)
+        return ret

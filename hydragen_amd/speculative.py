@@ -1,0 +1,320 @@
+"""Speculative decoding: several tokens per forward pass, verified in ONE multi-token decode step.
+
+Each step feeds every row T = K + 1 tokens -- its last emitted token and K drafts -- and one forward pass over [B, T] gives T rows of
+logits per row.  The sampler draws one token t_i from each of them with the call's temperature and cuts, and the row keeps
+t_0 .. t_n, n = the number of leading drafts with draft_{i+1} == t_i.
+
+Why this is lossless, for greedy AND sampled decoding: the logits behind fed token i are the model's distribution of the next token
+given the context and fed tokens 0 .. i.  t_0 is therefore always a draw from the target distribution -- it is what a one-token step
+would have drawn.  t_1 is a draw from the target distribution GIVEN that the token after the context is draft_1; it is kept only when
+t_0 == draft_1, i.e. when the token actually emitted in front of it is the one it was conditioned on -- and so on down the row.
+Every emitted token is thus a draw from the target distribution given a correct prefix; a draw behind a wrong draft was conditioned
+on a token that was never emitted and is thrown away, which costs nothing but its slot.  No acceptance probability, no
+resampling: the drafts are not sampled from a proposal distribution whose mass would have to be corrected for, they are only
+compared with what the target drew.  (With temperature 0 the tokens are exactly those of one-token decoding up to the numerics
+of the T-token kernels.)
+
+The drafts come from the prompt (`draft="prompt_lookup"`): the completions of long-document QA, few-shot prompts and many samples of
+one prompt copy from their shared prompt, so the tokens that followed the latest earlier occurrence of the row's last n-gram are
+proposed -- no draft model.  Levels kept from EARLIER generate() calls (shared_cache_op="extend") are not searched: their token
+ids are not given to the call that decodes.
+
+This module holds the definitions in torch (`prompt_lookup_reference`, `accept_reference`,
+`assembled_causal_tail_attention`) and the Python faces of the kernels (`draft_lookup`, `draft_accept`; the multi-token RoPE +
+append is fused_decode.rope_append_multi, the causal-tail attention flash.flash_attention_seqlen / attention.hydragen_attention
+with causal_tail=True)."""
+
+from __future__ import annotations
+
+import ctypes as C
+from typing import NamedTuple, Optional, Sequence
+
+import torch
+from torch import Tensor
+
+from . import _lib
+
+MAX_DRAFTS = 7  # K: T = K + 1 <= 8 tokens per row and step
+MAX_SEGMENTS = _lib.DRAFT_MAX_SEGMENTS  # of a lookup's table: the levels given to the call, the rows' prompts, the generated tokens
+
+
+class DraftStats(NamedTuple):
+    """Statistics of a speculative generation: decode steps run, and per row (int64 [B]) the drafts proposed to running rows and
+    the drafts that became output."""
+    steps: int
+    proposed: Tensor
+    accepted: Tensor
+
+
+class Segment(NamedTuple):
+    """One piece of the rows' logical token sequences: ids int64 [rows, width]; lens int [rows] or None (= width); row b of a batch
+    of B reads row b // (B // rows)."""
+    ids: Tensor
+    lens: Optional[Tensor] = None
+
+
+def check_ngram(ngram) -> tuple:
+    lo, hi = (int(x) for x in ngram)
+    if not 1 <= lo <= hi <= _lib.DRAFT_MAX_NGRAM:
+        raise ValueError(f"ngram = ({lo}, {hi}): 1 <= min <= max <= {_lib.DRAFT_MAX_NGRAM}")
+    return lo, hi
+
+
+def check_draft_tokens(k) -> int:
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_DRAFTS:
+        raise ValueError(f"draft_tokens = {k!r}: an int from 1 to {MAX_DRAFTS} (None or 0 switches speculative decoding off)")
+    return k
+
+
+def _check_segments(segments: Sequence[Segment], batch: int):
+    if not 1 <= len(segments) <= _lib.DRAFT_MAX_SEGMENTS:
+        raise ValueError(f"{len(segments)} segments: 1 to {_lib.DRAFT_MAX_SEGMENTS}")
+    for i, (ids, lens) in enumerate(segments):
+        if ids.ndim != 2 or ids.dtype != torch.int64 or ids.shape[0] < 1 or batch % ids.shape[0]:
+            raise ValueError(f"segment {i}: ids must be int64 [rows, width] with rows dividing the batch {batch}, got {tuple(ids.shape)} {ids.dtype}")
+        if lens is not None and (lens.shape != (ids.shape[0],) or lens.dtype not in (torch.int32, torch.int64)):
+            raise ValueError(f"segment {i}: lens must be int32 / int64 [{ids.shape[0]}], got {tuple(lens.shape)} {lens.dtype}")
+
+
+def logical_sequences(segments: Sequence[Segment], batch: int) -> list:
+    """The rows' logical sequences as Python lists (the definition's view; the kernel never builds them)."""
+    _check_segments(segments, batch)
+    rows = []
+    for b in range(batch):
+        seq = []
+        for ids, lens in segments:
+            r = b // (batch // ids.shape[0])
+            n = ids.shape[1] if lens is None else max(0, min(int(lens[r]), ids.shape[1]))
+            seq += ids[r, :n].tolist()
+        rows.append(seq)
+    return rows
+
+
+def prompt_lookup_reference(segments: Sequence[Segment], batch: int, k: int, ngram=(1, 3)):
+    """The rule hyd_draft_lookup implements -> (drafts int64 [batch, k], n_proposed int32 [batch]).  For n = ngram max down to min:
+    the last n tokens of the row's logical sequence (skipped when the sequence is shorter) are looked for among the earlier
+    positions; an occurrence must end strictly before the last position; the latest one wins and the up-to-k tokens behind it
+    are proposed, clipped at the sequence's end; the first n with an occurrence wins.  Slots without a proposal hold 0."""
+    k = check_draft_tokens(k)
+    lo, hi = check_ngram(ngram)
+    drafts = torch.zeros((batch, k), dtype=torch.int64)
+    n_prop = torch.zeros((batch,), dtype=torch.int32)
+    for b, seq in enumerate(logical_sequences(segments, batch)):
+        L = len(seq)
+        for n in range(hi, lo - 1, -1):
+            if L < n:
+                continue
+            tail = seq[L - n:]
+            ends = [e for e in range(n - 1, L - 1) if seq[e - n + 1: e + 1] == tail]  # e <= L - 2: the trivial match is excluded
+            if ends:
+                follow = seq[ends[-1] + 1: ends[-1] + 1 + k]
+                drafts[b, : len(follow)] = torch.tensor(follow, dtype=torch.int64)
+                n_prop[b] = len(follow)
+                break
+    return drafts, n_prop
+
+
+def draft_lookup(segments: Sequence[Segment], batch: int, k: int, ngram=(1, 3), out: Optional[Tensor] = None):
+    """hyd_draft_lookup, one launch, no host synchronisation -> (drafts int64 [batch, k], n_proposed int32 [batch]); CPU tensors
+    take prompt_lookup_reference.  out: an int64 [batch, >= k] tensor whose first k columns receive the drafts (a view of the
+    next step's input, columns 1 ..)."""
+    k = check_draft_tokens(k)
+    lo, hi = check_ngram(ngram)
+    _check_segments(segments, batch)
+    dev = segments[0].ids.device
+    if dev.type != "cuda":
+        d, n = prompt_lookup_reference(segments, batch, k, (lo, hi))
+        if out is not None:
+            out[:, :k] = d
+            d = out[:, :k]
+        return d, n
+    p = _lib.DraftLookupParams()
+    keep = []
+    for i, (ids, lens) in enumerate(segments):
+        if ids.device != dev or (lens is not None and lens.device != dev):
+            raise ValueError(f"segment {i} is not on {dev}")
+        if ids.stride(1) != 1:
+            ids = ids.contiguous()
+        s = p.segments[i]
+        s.ids, s.row_stride, s.len, s.div = (ids.data_ptr() if ids.numel() else None), ids.stride(0), ids.shape[1], batch // ids.shape[0]
+        if lens is not None:
+            lens = lens.contiguous()
+            if lens.dtype == torch.int64:
+                s.lens_i64 = lens.data_ptr()
+            else:
+                s.lens_i32 = lens.data_ptr()
+        if not ids.numel():
+            s.len, s.lens_i64, s.lens_i32 = 0, None, None
+        keep += [ids, lens]
+    if out is None:
+        out = torch.empty((batch, k), dtype=torch.int64, device=dev)
+    if out.dtype != torch.int64 or out.ndim != 2 or out.shape[0] != batch or out.shape[1] < k or out.stride(1) != 1 or out.device != dev:
+        raise ValueError(f"out must be int64 [{batch}, >= {k}] with a unit last stride on {dev}")
+    n_prop = torch.empty((batch,), dtype=torch.int32, device=dev)
+    p.drafts, p.n_proposed, p.drafts_stride = out.data_ptr(), n_prop.data_ptr(), out.stride(0) if batch > 1 else max(k, out.shape[1])
+    p.n_segments, p.B, p.K, p.ngram_min, p.ngram_max = len(segments), batch, k, lo, hi
+    _lib.check(_lib.load().hyd_draft_lookup(C.byref(p), torch.cuda.current_stream().cuda_stream))
+    del keep
+    return out[:, :k], n_prop
+
+
+# ---- acceptance ---------------------------------------------------------------------------------------------------------------
+def new_state(rows: int, max_new_tokens: int, pad: int, device=None, logprobs: bool = False):
+    """(out int64 [rows, max_new_tokens] of pad, length / reason int32 [rows] = 0, stop_index int32 [rows] = -1, out_logprobs f32
+    [rows, max_new_tokens] = 0 or None): the state hyd_draft_accept keeps, as a generation starts it."""
+    return (torch.full((rows, max_new_tokens), pad, dtype=torch.int64, device=device),
+            torch.zeros((rows,), dtype=torch.int32, device=device), torch.zeros((rows,), dtype=torch.int32, device=device),
+            torch.full((rows,), -1, dtype=torch.int32, device=device),
+            torch.zeros((rows, max_new_tokens), dtype=torch.float32, device=device) if logprobs else None)
+
+
+def accept_reference(fed: Tensor, sampled: Tensor, out: Tensor, length: Tensor, reason: Tensor, stop_index: Tensor, start_pos: Tensor,
+                     shared_len: Optional[Tensor], eos: Sequence[int], pad: int, max_new_tokens: int, retire: bool = True,
+                     logprobs: Optional[Tensor] = None, out_logprobs: Optional[Tensor] = None):
+    """The rule hyd_draft_accept implements, row by row on CPU tensors, updating out / length / reason / stop_index (/ out_logprobs)
+    in place -> (feed int64 [rows], next_pos int64 [rows], accepted int32 [rows], running rows).  fed / sampled int64 [rows, T]:
+    column 0 of fed is the last emitted token, the others are drafts; sampled[b, i] was drawn behind fed[b, i].  A row with
+    reason != 0 or length >= max_new_tokens has finished and does not change.  Otherwise n = the leading i < T - 1 with
+    fed[b, i + 1] == sampled[b, i]; sampled[b, 0 .. n] is emitted, cut behind its first EOS id (kept, reason 1) and at
+    max_new_tokens (reason 0); the next step feeds the last emitted token at start_pos + length - 1.  A finished row is fed pad
+    at shared_len - 1 (retire), the position that takes it out of the unique K/V stream."""
+    rows, T = fed.shape
+    eos = list(eos)
+    feed = torch.empty((rows,), dtype=torch.int64)
+    next_pos = torch.empty((rows,), dtype=torch.int64)
+    accepted = torch.zeros((rows,), dtype=torch.int32)
+    live = 0
+    for b in range(rows):
+        ln, r, last = int(length[b]), int(reason[b]), pad
+        if r == 0 and ln < max_new_tokens:
+            n = 0
+            while n < T - 1 and int(fed[b, n + 1]) == int(sampled[b, n]):
+                n += 1
+            toks = sampled[b, : min(n + 1, max_new_tokens - ln)].tolist()
+            for i, t in enumerate(toks):
+                if t in eos:
+                    toks = toks[: i + 1]
+                    r = 1
+                    reason[b], stop_index[b] = 1, eos.index(t)
+                    break
+            e = len(toks)
+            out[b, ln: ln + e] = torch.tensor(toks, dtype=torch.int64)
+            if logprobs is not None and out_logprobs is not None:
+                out_logprobs[b, ln: ln + e] = logprobs[b, :e]
+            ln += e
+            length[b] = ln
+            accepted[b] = e - 1
+            last = toks[-1]
+        running = r == 0 and ln < max_new_tokens
+        live += int(running)
+        feed[b] = last if running else pad
+        if running or not retire:
+            next_pos[b] = int(start_pos[b]) + ln - 1
+        else:
+            next_pos[b] = (int(shared_len[b]) if shared_len is not None else 0) - 1
+    return feed, next_pos, accepted, live
+
+
+def draft_accept(fed: Tensor, sampled: Tensor, out: Tensor, length: Tensor, reason: Tensor, stop_index: Tensor, live: Tensor,
+                 start_pos: Tensor, shared_len: Optional[Tensor], eos: Sequence[int], pad: int, max_new_tokens: int,
+                 retire: bool = True, logprobs: Optional[Tensor] = None, out_logprobs: Optional[Tensor] = None):
+    """hyd_draft_accept, one launch -> (feed, next_pos int64 [rows], accepted int32 [rows]); the rows still running are ADDED to
+    live (int32 [1], a slot the caller zeroed).  The state tensors are those of new_state; CPU tensors take accept_reference.
+    Nothing synchronises."""
+    rows, T = fed.shape
+    if fed.dtype != torch.int64 or sampled.dtype != torch.int64 or sampled.shape != fed.shape:
+        raise ValueError(f"fed / sampled must be int64 [rows, T], got {tuple(fed.shape)} {fed.dtype} / {tuple(sampled.shape)} {sampled.dtype}")
+    if not 1 <= T <= MAX_DRAFTS + 1:
+        raise ValueError(f"T = {T} tokens per row: 1 to {MAX_DRAFTS + 1}")
+    if out.dtype != torch.int64 or out.ndim != 2 or out.shape[0] != rows or out.stride(1) != 1 or not 1 <= max_new_tokens <= out.shape[1]:
+        raise ValueError(f"out must be int64 [{rows}, >= max_new_tokens = {max_new_tokens}] with a unit last stride, got {tuple(out.shape)} {out.dtype}")
+    dev = fed.device
+    for name, x, n in (("length", length, rows), ("reason", reason, rows), ("stop_index", stop_index, rows), ("live", live, 1)):
+        if x.dtype != torch.int32 or x.shape != (n,) or not x.is_contiguous() or x.device != dev:
+            raise ValueError(f"{name} must be a contiguous int32 [{n}] on {dev}, got {tuple(x.shape)} {x.dtype} on {x.device}")
+    for name, x in (("start_pos", start_pos), ("shared_len", shared_len)):
+        if x is not None and (x.dtype != torch.int64 or x.shape != (rows,) or not x.is_contiguous() or x.device != dev):
+            raise ValueError(f"{name} must be a contiguous int64 [{rows}] on {dev}")
+    if len(eos) > _lib.STOP_MAX_EOS:
+        raise ValueError(f"{len(eos)} EOS ids: at most {_lib.STOP_MAX_EOS}")
+    if (logprobs is None) != (out_logprobs is None):
+        raise ValueError("logprobs and out_logprobs go together")
+    if logprobs is not None and (logprobs.dtype != torch.float32 or logprobs.shape != fed.shape or out_logprobs.dtype != torch.float32
+                                 or out_logprobs.shape != out.shape or out_logprobs.stride() != out.stride()):
+        raise ValueError("logprobs must be float32 [rows, T] and out_logprobs float32 with out's shape and strides")
+    if dev.type != "cuda":
+        feed, pos, acc, n = accept_reference(fed, sampled, out, length, reason, stop_index, start_pos, shared_len, eos, pad,
+                                             max_new_tokens, retire, logprobs, out_logprobs)
+        live += n
+        return feed, pos, acc
+    fed, sampled = fed.contiguous(), sampled.contiguous()
+    feed = torch.empty((rows,), dtype=torch.int64, device=dev)
+    next_pos = torch.empty((rows,), dtype=torch.int64, device=dev)
+    accepted = torch.empty((rows,), dtype=torch.int32, device=dev)
+    p = _lib.DraftAcceptParams()
+    p.fed, p.sampled, p.out, p.length, p.reason = fed.data_ptr(), sampled.data_ptr(), out.data_ptr(), length.data_ptr(), reason.data_ptr()
+    p.stop_index, p.accepted, p.live, p.start_pos = stop_index.data_ptr(), accepted.data_ptr(), live.data_ptr(), start_pos.data_ptr()
+    if shared_len is not None:
+        p.shared_len = shared_len.data_ptr()
+    if logprobs is not None:
+        logprobs = logprobs.contiguous()
+        p.logprobs, p.out_logprobs = logprobs.data_ptr(), out_logprobs.data_ptr()
+    p.feed, p.next_pos = feed.data_ptr(), next_pos.data_ptr()
+    p.out_stride, p.pad = (out.stride(0) if rows > 1 else out.shape[1]), pad
+    for i, e in enumerate(eos):
+        p.eos[i] = e
+    p.rows, p.T, p.n_eos, p.max_new_tokens, p.retire = rows, T, len(eos), max_new_tokens, int(bool(retire))
+    _lib.check(_lib.load().hyd_draft_accept(C.byref(p), torch.cuda.current_stream().cuda_stream))
+    return feed, next_pos, accepted
+
+
+# ---- the multi-token attention, assembled from existing operators ------------------------------------------------------------
+def _hip_ops():
+    from . import attention, flash
+
+    return dict(
+        seqlen=flash.flash_attention_seqlen,
+        causal=lambda q, k, v: flash.flash_attention(q, k, v, causal=True),
+        level=attention._level_pass,
+        combine=attention._combine_many,
+    )
+
+
+def assembled_causal_tail_attention(q: Tensor, k: Tensor, v: Tensor, seq_lens: Tensor, shared_ks=(), shared_vs=(), shared_cu_seq_lens=None,
+                                    shared_max_seq_lens=None, use_varlens=None, ops: Optional[dict] = None) -> Tensor:
+    """The DEFINITION of a multi-token decode step's attention, from launches that existed before the causal-tail kernels: q
+    [B, T, Hq, D] are the last T tokens of their sequences, k / v [B, S, Hkv, D] the unique caches with the T new keys already
+    in place, seq_lens [B] their lengths (new keys included; a row shorter than T takes no part in the unique passes).
+      1. the OLD keys: every query over the first seq_lens - T keys (flash_attention_seqlen, non-causal -- all of them are visible);
+      2. the NEW keys: the T x T block k[b, seq_lens - T : seq_lens], causal (flash_attention(causal=True));
+      3. one non-causal pass per shared level;
+    merged by log-sum-exp (combine_lse).  Two launches per layer more than the fused causal call, and a gather: this is what
+    the kernels are tested against and what shapes they refuse fall back on, not the product path.
+    ops: the four operators (seqlen, causal, level, combine) -- the HIP ones by default; a test passes torch ones to check
+    the assembly itself on the CPU."""
+    ops = ops or _hip_ops()
+    B, T, Hq, D = q.shape
+    n_levels = len(shared_ks)
+    shared_cu_seq_lens = shared_cu_seq_lens or [None] * n_levels
+    shared_max_seq_lens = shared_max_seq_lens or [None] * n_levels
+    use_varlens = use_varlens or [False] * n_levels
+    sl = seq_lens.long()
+    part = sl >= T  # rows that take part in the unique passes
+    old = torch.where(part, sl - T, torch.zeros_like(sl))
+    outs, lses = [], []
+    for sk, sv, scu, smax, uv in zip(shared_ks, shared_vs, shared_cu_seq_lens, shared_max_seq_lens, use_varlens):
+        o, l = ops["level"](q, sk, sv, scu, smax, uv)
+        outs.append(o)
+        lses.append(l)
+    o_old, l_old = ops["seqlen"](q, k, v, old.to(seq_lens.dtype))
+    outs.append(o_old)
+    lses.append(l_old)
+    idx = (old[:, None] + torch.arange(T, device=q.device)[None, :]).clamp_(max=k.shape[1] - 1)  # [B, T] (rows out of it: masked below)
+    gi = idx[:, :, None, None].expand(B, T, k.shape[2], k.shape[3])
+    o_new, l_new = ops["causal"](q, k.gather(1, gi), v.gather(1, gi))  # lse [B, Hq, T]
+    l_new = l_new.transpose(1, 2).contiguous()
+    o_new = torch.where(part[:, None, None, None], o_new, torch.zeros_like(o_new))
+    l_new = torch.where(part[:, None, None], l_new, torch.full_like(l_new, float("-inf")))
+    outs.append(o_new)
+    lses.append(l_new)
+    return ops["combine"](outs, lses)

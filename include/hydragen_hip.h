@@ -151,6 +151,14 @@ typedef struct hyd_suffix_params {
 } hyd_suffix_params;
 
 HYD_API int hyd_suffix_attn_fwd(const hyd_suffix_params* p, void* stream);
+/* The suffix pass of a MULTI-TOKEN decode step (speculative decoding: hydragen_amd/speculative.py), causal tail: the nq = T query
+ * tokens of sequence b (2 <= T <= 8) are its last T tokens and their K/V are already in the cache, so query token i attends the
+ * keys below clamp(seq_len[b], 0, kv_len) - (T - 1 - i), clamped at 0 -- bottom-right aligned, what a causal attention over the
+ * whole sequence gives its last T rows.  The struct and everything else (partials, lse, seq_order) are hyd_suffix_attn_fwd's; the
+ * unique K/V is streamed once for all T tokens.  A row whose limit is 0 (seq_len < T) comes out as zeros with lse = -inf, like a
+ * sequence of length 0.  16-bit caches with rows of D elements only: kv_dim (narrow rows) returns HYD_ERR_UNSUPPORTED, and there is
+ * no _kvq form.  T outside 2..8 is HYD_ERR_BAD_ARG.  A causal call never runs on a kernel without the limit. */
+HYD_API int hyd_suffix_attn_causal_fwd(const hyd_suffix_params* p, void* stream);
 /* Shapes only (capture-safe, no device read): 1 exactly when the suffix pass and the whole decode operator take the call with
  * its kv_dim -- always for kv_dim 0 / D; for narrow rows: one query row (nq == 1), Hq == Hkv, Hkv a multiple of the 64 / (D / 8)
  * heads one wave instruction covers, a sequence's cache within 2 GiB (the token-row kernel; the other suffix kernels have no
@@ -219,7 +227,11 @@ typedef struct hyd_decode_params {
                                     * prefix).  The result then differs from the phase-split forms by their roundings of
                                     * the partial.  Not taken when suffix.lse is set (that is the LSE of the unique
                                     * keys alone in every form).  0: always the prefix pass + suffix pass pair.       */
-    int32_t reserved;
+    int32_t causal_tail;           /* (was reserved, 0) 0: the operator as it always was.  1: a multi-token decode step -- the
+                                    * unique part of HYD_PHASE_ALL / UNIQUE / UNIQUE_PARTIAL follows hyd_suffix_attn_causal_fwd's
+                                    * rule (suffix.nq = T in 2..8; every query sees every shared key, as before); the one-launch
+                                    * form is not taken.  Refused with HYD_ERR_UNSUPPORTED for narrow rows (suffix.kv_dim) and by
+                                    * hyd_decode_attn_fused_kvq for fp8 caches.                                        */
 } hyd_decode_params;
 
 HYD_API size_t hyd_decode_workspace_bytes(const hyd_decode_params* p);
@@ -270,6 +282,38 @@ typedef struct hyd_rope_params {
 } hyd_rope_params;
 
 HYD_API int hyd_rope_append_decode(const hyd_rope_params* p, void* stream);
+
+/* The same preamble for a MULTI-TOKEN decode step: q / k / v are [B, T, H, D] (2 <= T <= 8; heads contiguous, batch and token
+ * strides given), position_ids[b] is the absolute position of the row's FIRST token and token i uses position + i.  K (rotated)
+ * and V of token i go to cache index idx + i with idx = position - shared_len, q_out is [B, T, Hq, D] contiguous, and
+ * seq_lens[b] = idx + T: the T new keys are part of the sequence (hyd_suffix_attn_causal_fwd reads them back).
+ * Contract, as above: a cache index < 0 or >= cache_len writes nothing.  A row fed position shared_len - 1 (idx = -1, a retired
+ * row) takes no part: NONE of its T tokens is written and seq_lens[b] = 0 -- seq_lens[b] is idx + T only when idx >= 0, else 0.
+ * K/V rows of drafts a step rejects stay in the cache behind the row's next length; they are never read, and the next step,
+ * which starts behind the last accepted token and writes T rows again, overwrites them.
+ * 16-bit caches with D 64 / 128 / 256 (no fp8 form, no narrow head dims). */
+typedef struct hyd_rope_multi_params {
+    const void* q;               /* token i of row b at q + b*q_batch_stride + i*q_tok_stride, [Hq, D] contiguous   */
+    const void* k;               /* [B, T, Hkv, D] likewise                                                         */
+    const void* v;
+    void* q_out;                 /* [B, T, Hq, D] contiguous                                                        */
+    void* k_cache;               /* [maxB, cache_len, Hkv, D] with the strides below                                */
+    void* v_cache;
+    const float* cos;            /* [max_pos, D] fp32, row stride cs_stride                                         */
+    const float* sin;
+    const int64_t* position_ids; /* [B] position of the first token, element stride pos_stride                      */
+    const int64_t* shared_len;   /* [B] or NULL (= 0)                                                               */
+    int32_t* seq_lens;           /* out [B]                                                                         */
+    int64_t q_batch_stride, k_batch_stride, v_batch_stride;
+    int64_t q_tok_stride, k_tok_stride, v_tok_stride;
+    int64_t kc_batch_stride, kc_tok_stride, kc_head_stride;
+    int64_t vc_batch_stride, vc_tok_stride, vc_head_stride;
+    int64_t pos_stride, cs_stride;
+    int32_t dtype, B, T, Hq, Hkv, D, cache_len;
+    int32_t max_pos;             /* rows of the cos/sin tables; positions are clamped to it                         */
+} hyd_rope_multi_params;
+
+HYD_API int hyd_rope_append_multi(const hyd_rope_multi_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Elementwise glue of the decoder layer around the attention block (the model shell); rows are
@@ -555,6 +599,82 @@ typedef struct hyd_stop_params {
 } hyd_stop_params;
 
 HYD_API int hyd_stop_update(const hyd_stop_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Speculative decoding (hydragen_amd/speculative.py states both definitions in torch): drafts by prompt lookup, and the
+ * acceptance of a verified step.  Neither launch synchronises with the host.
+ *
+ * hyd_draft_lookup: row b's LOGICAL sequence is the concatenation of n_segments segments -- the shared levels given to this
+ * generation on the row's path, its own prompt, its generated tokens.  Segment s contributes the first len tokens of row
+ * b / div of ids (lens_i64[b / div], else lens_i32[b / div], clamped to [0, len], the columns of a row; without either, len):
+ * there is no per-row copy of shared tokens.  With L the total length: for n = ngram_max down to ngram_min, the last n tokens of the
+ * sequence are looked for among its earlier positions; an occurrence must END strictly before the last position (the trivial
+ * match is excluded) and the LATEST one wins; the first n with an occurrence wins.  With e the end position of the winner,
+ * drafts[b, j] = token e + 1 + j for j < n_proposed[b] = min(K, L - 1 - e), the other slots hold 0 (any token is a valid draft:
+ * it is only verified); no occurrence, or L < 2: n_proposed[b] = 0.  Matches and proposals may cross segment boundaries.
+ * One wave per row: lanes scan candidate end positions, a wave reduction picks the maximum of (match length, position).
+ * HYD_ERR_BAD_ARG: null or misaligned pointers, B < 0, K outside [1, 7], 1 <= ngram_min <= ngram_max <= HYD_DRAFT_MAX_NGRAM
+ * violated, n_segments outside [1, HYD_DRAFT_MAX_SEGMENTS], a segment with div < 1 or a null ids with a non-zero length. */
+#define HYD_DRAFT_MAX_SEGMENTS (HYD_MAX_LEVELS + 2)
+#define HYD_DRAFT_MAX_NGRAM 8
+typedef struct hyd_draft_segment {
+    const int64_t* ids;      /* [rows of the segment, row_stride]                                          */
+    const int64_t* lens_i64; /* [rows of the segment] or NULL                                              */
+    const int32_t* lens_i32; /* [rows of the segment] or NULL; both NULL: every row holds `len` tokens     */
+    int64_t row_stride;      /* elements                                                                   */
+    int32_t len;             /* columns of a row: the uniform length, and the cap of the per-row lengths   */
+    int32_t div;             /* row b of the batch reads row b / div of the segment (the fan-out)          */
+} hyd_draft_segment;
+
+typedef struct hyd_draft_lookup_params {
+    hyd_draft_segment segments[HYD_DRAFT_MAX_SEGMENTS];
+    int64_t* drafts;         /* out [B, drafts_stride]: columns 0 .. K - 1 are written                     */
+    int32_t* n_proposed;     /* out [B]                                                                    */
+    int64_t drafts_stride;   /* elements                                                                   */
+    int32_t n_segments, B, K, ngram_min, ngram_max;
+    int32_t reserved;
+} hyd_draft_lookup_params;
+
+HYD_API int hyd_draft_lookup(const hyd_draft_lookup_params* p, void* stream);
+
+/* hyd_draft_accept: after a step that fed row b the T = K + 1 tokens fed[b, :] (its last emitted token, then K drafts) and drew
+ * sampled[b, i] from the logits behind fed[b, i].  A row with reason[b] != 0 or length[b] >= max_new_tokens has finished: nothing
+ * of it changes and accepted[b] = 0.  Otherwise, in this order: n = the number of leading i < K with fed[b, i + 1] ==
+ * sampled[b, i]; the row emits sampled[b, 0 .. n]; the run is cut behind its first EOS id (kept: reason 1, stop_index = the
+ * lowest matching i < n_eos) and at max_new_tokens - length[b] tokens (reason stays 0); the e emitted tokens (and their
+ * log-probs, when both logprobs and out_logprobs are given) go to out[b, length[b] ..), length[b] += e and accepted[b] = e - 1,
+ * the drafts that became output.  For the next step: a row that still runs is fed its last emitted token at position
+ * start_pos[b] + length[b] - 1 (start_pos: the position of the token in column 0); a finished row is fed pad at position
+ * shared_len[b] - 1 (-1 with shared_len NULL), which retires it from the K/V stream (hyd_rope_append_multi), or -- retire == 0
+ * -- at start_pos[b] + length[b] - 1 like a running one.  *live += the rows still running after the step (the caller zeroes it).
+ * The caller fills out with pad and zeroes length / reason before the first call; a generation's first token (drawn from the
+ * prefill logits) is entered by a call with T = 1 -- the one case in which K = 0 is accepted.
+ * HYD_ERR_BAD_ARG: null or misaligned pointers, rows < 0, T outside [1, 8], n_eos outside [0, HYD_STOP_MAX_EOS],
+ * max_new_tokens outside [1, out_stride]. */
+typedef struct hyd_draft_accept_params {
+    const int64_t* fed;         /* [rows, T]                                                                 */
+    const int64_t* sampled;     /* [rows, T]                                                                 */
+    const float* logprobs;      /* [rows, T] or NULL                                                         */
+    int64_t* out;               /* [rows, out_stride]                                                        */
+    float* out_logprobs;        /* [rows, out_stride] or NULL                                                */
+    int32_t* length;            /* [rows] tokens emitted so far                                              */
+    int32_t* reason;            /* [rows] 0 = running or cut at max_new_tokens, 1 = EOS                      */
+    int32_t* stop_index;        /* [rows] which EOS id matched; the caller starts it at -1                   */
+    int32_t* accepted;          /* [rows] out: drafts of this step that became output                        */
+    int32_t* live;              /* [1] rows still running after the step are ADDED; zeroed by the caller     */
+    const int64_t* start_pos;   /* [rows]                                                                    */
+    const int64_t* shared_len;  /* [rows] or NULL (= 0)                                                      */
+    int64_t* feed;              /* [rows] out: the first token of the next step                              */
+    int64_t* next_pos;          /* [rows] out: its position                                                  */
+    int64_t out_stride;         /* elements                                                                  */
+    int64_t pad;
+    int64_t eos[HYD_STOP_MAX_EOS];  /* HOST values                                                           */
+    int32_t rows, T, n_eos, max_new_tokens;
+    int32_t retire;
+    int32_t reserved;
+} hyd_draft_accept_params;
+
+HYD_API int hyd_draft_accept(const hyd_draft_accept_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * All-reduce(sum) of the tensor-parallel block output (hydragen/tp.py:83-87 after down_proj, :108-112 after

@@ -1,0 +1,143 @@
+"""Speculative decoding on a Llama-2-7B shell (random weights, bf16, P = 2048): what a T-token decode step costs and what acceptance
+rate pays for it.  Writes the tables of profiles/speculative.md to stdout (markdown) -- nothing here is promised in advance.
+
+    python tools/spec_bench.py [--batches 32,128,1024] [--new 33] [--prefix 2048] [--layers 32] [--no-graph]
+
+Step time: generate() with GIVEN drafts that are all wrong (every step emits exactly one token, so decode time / steps is the step
+time of a T-token step); T = 1 is the plain path.  Break-even acceptance per T: the fraction a of the K drafts that has to be
+accepted per step for tokens/s to equal the plain path, (1 + a K) / step_T = 1 / step_1.  Tokens/s at forced acceptance: the tokens
+of the all-wrong run at the same T (same kernels, same shapes -- plain decoding's tokens do not serve: a random-weight bf16 model has
+near ties in its logits, and a T-token step breaks them differently) are handed back as drafts, each kept with the given rate and
+corrupted otherwise; the acceptance a run actually reached is printed beside its tokens/s.  Prompt lookup on random weights
+accepts next to nothing by nature (a random model does not copy its prompt): reported as measured, not tuned for."""
+from __future__ import annotations
+
+import argparse
+import sys
+import time
+from pathlib import Path
+
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+
+DEV = "cuda:0"
+
+
+def timed(fn, iters=20, warm=3):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / iters * 1e6
+
+
+def kernel_times(B, T, Hq, Hkv, D, P, S):
+    """us per launch of the four new kernels, and of the assembled four-launch attention against the fused causal call."""
+    from hydragen_amd import speculative
+    from hydragen_amd.attention import hydragen_attention
+    from hydragen_amd.flash import flash_attention_seqlen
+    from hydragen_amd.fused_decode import rope_append_multi
+    from hydragen_amd.llama import RotaryTable
+
+    dt = torch.bfloat16
+    q, k, v = (torch.randn(B, T, h, D, device=DEV, dtype=dt) for h in (Hq, Hkv, Hkv))
+    kc, vc = (torch.randn(B, S + 16, Hkv, D, device=DEV, dtype=dt) for _ in range(2))
+    sk, sv = (torch.randn(1, P, Hkv, D, device=DEV, dtype=dt) for _ in range(2))
+    rot = RotaryTable(D, P + S + 64, 10000.0, device=DEV)
+    pos = torch.full((B,), P + S - T, device=DEV, dtype=torch.int64)
+    shared = torch.full((B,), P, device=DEV, dtype=torch.int64)
+    lens = torch.full((B,), S, device=DEV, dtype=torch.int32)
+    ids = torch.randint(0, 32000, (1, P), device=DEV)
+    gen = torch.randint(0, 32000, (B, S), device=DEV)
+    glen = torch.full((B,), S // 2, device=DEV, dtype=torch.int32)
+    fed = torch.randint(0, 32000, (B, T), device=DEV)
+    state = speculative.new_state(B, S, 0, DEV)
+    live = torch.zeros((1,), dtype=torch.int32, device=DEV)
+    start = torch.full((B,), P, device=DEV, dtype=torch.int64)
+    lv = dict(shared_ks=[sk], shared_vs=[sv], shared_cu_seq_lens=[None], shared_max_seq_lens=[None], use_varlens=[False])
+
+    def accept():
+        state[1].zero_()
+        speculative.draft_accept(fed, fed, *state[:4], live, start, shared, (), 0, S)
+
+    return {
+        "hyd_rope_append_multi": timed(lambda: rope_append_multi(q, k, v, rot.cos_cached, rot.sin_cached, pos, shared, kc, vc)),
+        "hyd_suffix_attn_causal_fwd": timed(lambda: flash_attention_seqlen(q, kc, vc, lens, causal_tail=True)),
+        "hyd_draft_lookup": timed(lambda: speculative.draft_lookup([speculative.Segment(ids), speculative.Segment(gen, glen)], B, T - 1)),
+        "hyd_draft_accept (+ a memset)": timed(accept),
+        "fused causal call (levels + causal tail)": timed(lambda: hydragen_attention(q, kc, vc, **lv, seq_lens=lens, causal_tail=True)),
+        "assembled (level, old keys, causal block, combine)": timed(lambda: speculative.assembled_causal_tail_attention(q, kc, vc, lens, [sk], [sv])),
+    }
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="32,128,1024")
+    ap.add_argument("--new", type=int, default=33)
+    ap.add_argument("--prefix", type=int, default=2048)
+    ap.add_argument("--layers", type=int, default=32)
+    ap.add_argument("--no-graph", action="store_true")
+    args = ap.parse_args()
+    from hydragen_amd.llama import HydragenLlamaForCausalLM, LlamaConfig
+
+    cfg = LlamaConfig.llama2_7b()
+    cfg.num_hidden_layers = args.layers
+    cfg.max_position_embeddings = max(cfg.max_position_embeddings, args.prefix + args.new + 32)
+    model = HydragenLlamaForCausalLM.from_config(cfg, dtype=torch.bfloat16, device=DEV, seed=0)
+    model.graph(not args.no_graph)
+    prompt = torch.randint(1, cfg.vocab_size, (1, args.prefix), device=DEV)
+    N, steps = args.new, args.new - 1
+    print(f"# Speculative decoding: measurements\n\nLlama-2-7B shell ({args.layers} layers, random weights, bf16), P = {args.prefix}, {N} new tokens, "
+          f"{'eager' if args.no_graph else 'HIP-graph'} decode, temperature 0.\n")
+    for B in (int(b) for b in args.batches.split(",")):
+        model.setup_caches(max_unique_batch_size=B, max_unique_seq_length=N + 16, max_shared_batch_sizes=[1], max_shared_seq_lengths=[args.prefix])
+
+        def run(n, **kw):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = model.generate(input_ids=prompt, num_return_sequences=B, max_new_tokens=n, temperature=0.0, **kw)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0, out
+
+        run(4)
+        pre = min(run(1)[0] for _ in range(2))
+        full, G = min((run(N) for _ in range(2)), key=lambda r: r[0])
+        step1 = (full - pre) / steps
+        wrong = (G + 1) % cfg.vocab_size
+        print(f"## B = {B}\n\nplain path (T = 1): {step1 * 1e3:.3f} ms per step, {B / step1:.0f} tokens/s\n")
+        print("| T | ms per step | x plain | break-even acceptance | tokens/s at 0 % | drafts kept 50 %: tokens/s (accepted / proposed) | "
+              "drafts kept 100 % | prompt lookup |")
+        print("|---|---|---|---|---|---|---|---|")
+        for T in range(2, 9):
+            K = T - 1
+            kw = dict(draft_tokens=K, return_draft_stats=True)
+            run(4, **dict(kw, draft=wrong[:, :4]))
+            t_wrong, (W, _) = min((run(N, draft=wrong, **kw) for _ in range(2)), key=lambda r: r[0])
+            step_t = (t_wrong - pre) / steps
+            # the tokens of the all-wrong run come from the same kernels at the same shapes as the runs below: handed back as
+            # drafts they are accepted as long as the run reproduces them (the acceptance it reached is printed beside the rate)
+            cells = []
+            for rate in (0.5, 1.0):
+                keep = torch.rand(W.shape, device=DEV) < rate
+                d = torch.where(keep, W, (W + 1) % cfg.vocab_size)
+                t, (_, st) = min((run(N, draft=d, **kw) for _ in range(2)), key=lambda r: r[0])
+                cells.append(f"{B * steps / (t - pre):.0f} ({int(st.accepted.sum())} / {int(st.proposed.sum())})")
+            t_pl, (_, st) = min((run(N, **kw) for _ in range(2)), key=lambda r: r[0])
+            print(f"| {T} | {step_t * 1e3:.3f} | {step_t / step1:.2f} | {(step_t / step1 - 1) / K * 100:.0f} % | {B / step_t:.0f} | {cells[0]} | {cells[1]} | "
+                  f"{B * steps / (t_pl - pre):.0f} ({int(st.accepted.sum())} / {int(st.proposed.sum())}) |")
+        print()
+        model.graph(False)
+        kt = kernel_times(B, 4, cfg.num_attention_heads, cfg.num_key_value_heads, cfg.hidden_size // cfg.num_attention_heads, args.prefix, 64)
+        model.graph(not args.no_graph)
+        print("per launch at T = 4, suffix 64 (us, eager, host-timed back to back):\n")
+        for name, us in kt.items():
+            print(f"- {name}: {us:.1f}")
+        print()
+
+
+if __name__ == "__main__":
+    main()
