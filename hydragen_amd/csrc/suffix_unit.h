@@ -239,6 +239,7 @@ __global__ __launch_bounds__(256, OCC) void HYD_UNIT_KERNEL(const SuffixArgs a) 
     };
     int it = 0;
     if constexpr (PIPE != 0) {
+        static_assert(!(CT && PIPE != 0), "the rotated full-chunk path masks with `valid` only: it has no per-row key limit");
         // Long caches (more than 1024 rows: the token-row kernel does not take them): the full chunks with rotated requests, as in the
         // token-row kernel -- K of chunk c + 1 goes out as soon as the scores of chunk c have left the K registers, V of chunk c + 1
         // behind P.V of chunk c -- the same registers, never an empty queue.  2176-row caches, C2 heads, one process, alternating

@@ -84,8 +84,8 @@ def assert_close_l2(got, want, dtype, what=""):
     return err, l2
 
 
-def suffix_fwd_with_partials(tq, tk, tv, tsl, groups, dt, want_lse):
-    """hyd_suffix_attn_fwd with prefix partials handed in directly.  groups: [(is_f32, [(out [B, nq, Hq, D], lse [B, nq, Hq]), ...])],
+def suffix_fwd_with_partials(tq, tk, tv, tsl, groups, dt, want_lse, causal=False):
+    """hyd_suffix_attn_fwd (causal: hyd_suffix_attn_causal_fwd, the same struct) with prefix partials handed in directly.  groups: [(is_f32, [(out [B, nq, Hq, D], lse [B, nq, Hq]), ...])],
     float32 numpy; a group of several partials is marshalled as stacked slices (256-byte aligned strides, as a split prefix pass
     leaves them), a group of one as a plain partial.  Returns (out, the suffix pass's own LSE or None)."""
     import ctypes as C
@@ -118,7 +118,7 @@ def suffix_fwd_with_partials(tq, tk, tv, tsl, groups, dt, want_lse):
         sp.partials[n].out, sp.partials[n].lse, sp.partials[n].count, sp.partials[n].is_f32 = ob.data_ptr(), lb.data_ptr(), cnt, int(f32)
         keep += [ob, lb]
     sp.n_partials = len(groups)
-    _lib.check(lib.hyd_suffix_attn_fwd(C.byref(sp), torch.cuda.current_stream().cuda_stream))
+    _lib.check((lib.hyd_suffix_attn_causal_fwd if causal else lib.hyd_suffix_attn_fwd)(C.byref(sp), torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
     del keep
     return out, (lse if want_lse else None)

@@ -427,3 +427,198 @@ def operator_case(shape: str, mass: str, P: int, hot_at: int, dt: str, levels: i
         sks.append(_round((np.full((2, 24, 1, 1), low) * unit).astype(np.float32).repeat(Hkv, 2) + noise(2, 24, Hkv, D), dt))
         svs.append(_round(rng.standard_normal((2, 24, Hkv, D), dtype=np.float32), dt))
     return dict(q=q, k=k, v=v, lens=lens, shared_ks=sks, shared_vs=svs, dt=dt)
+
+
+# ---- the causal tail (hyd_suffix_attn_causal_fwd): a per-row key limit in the score mask ------------------------------------------
+def causal_route(B, Hq, Hkv, cap, D, T) -> str:
+    """The kernel hyd_suffix_attn_causal_fwd picks, restated from suffix_attn_causal.hip (shapes only, as there):
+    `suffix_causal_eligible` (2..8 tokens; the matrix-core kernel's shapes, 2-row units, or D = 256), `launch_causal_t` ->
+    suffix_attn_gqa.hip `suffix_gqa_eligible` (rows >= 3; not D = 256 with gqa_few_units) -> `launch_causal_gqa_t` with
+    suffix_gqa_common.h `gqa_launch_plan` (gqa_few_units: units * chunks < 1024 and kv_len >= 128 -> four waves per unit; else 4 / 2 / 1
+    kv heads per workgroup, at most 2 at D = 256); what is left -> `launch_causal_unit_r` with R = 2 (rows <= 2), 4 or 8 (D = 256),
+    four waves per unit when units * row_chunks < 2048 and kv_len >= 64."""
+    g = Hq // Hkv
+    rows, units = T * g, B * Hkv
+    chunks = (rows + 15) // 16
+    few = units * chunks < 256 * 4 and cap >= 128
+    gqa = rows >= 3 and not (D == 256 and few)
+    if not (2 <= T <= 8) or D not in (64, 128, 256) or not (gqa or rows <= 2 or D == 256):
+        return "refused"
+    if gqa:
+        if few:
+            return "gqa/4-waves"
+        hpw = (4 if Hkv % 4 == 0 else 2 if Hkv % 2 == 0 else 1) if Hkv <= 8 else 1
+        return f"gqa/1-wave/hpw{min(hpw, 2) if D == 256 else hpw}"
+    R = 2 if rows <= 2 else 4 if rows <= 4 else 8
+    few = units * ((rows + R - 1) // R) < 2 * 256 * 4 and cap >= 64
+    return f"unit/R{R}/" + ("4-waves" if few else "1-wave")
+
+
+# name -> (B, Hq, Hkv, cap, D, T, route key, what); B = 0: one sequence per listed length (causal_lengths), no more
+CAUSAL_ROUTES = {
+    "gqa_hpw4": (0, 8, 4, 40, 64, 3, "gqa/1-wave/hpw4", "matrix-core kernel, one wave per unit, 4 kv heads per workgroup (kv_len < 128)"),
+    "gqa_hpw2": (0, 6, 2, 70, 128, 8, "gqa/1-wave/hpw2",
+                 "matrix-core kernel, one wave per unit, 2 kv heads per workgroup; g = 3: a 16-row chunk boundary falls inside a token"),
+    "gqa_hpw1": (0, 8, 1, 40, 128, 4, "gqa/1-wave/hpw1", "matrix-core kernel, one wave per unit, 1 kv head per workgroup"),
+    "gqa_4waves": (0, 8, 1, 132, 128, 5, "gqa/4-waves", "matrix-core kernel, four waves per unit (gqa_few_units), three row chunks"),
+    "gqa_4waves_tiles": (0, 8, 2, 300, 128, 8, "gqa/4-waves", "matrix-core kernel, four waves per unit, every wave walks several tiles"),
+    "gqa_1wave_long": (520, 8, 2, 132, 128, 3, "gqa/1-wave/hpw2",
+                       "matrix-core kernel, one wave per unit on a cache of >= 128 keys (1040 units x 1 chunk >= 1024): a repeated block"),
+    "unit_r2_1wave": (0, 4, 4, 40, 64, 2, "unit/R2/1-wave", "dot-product kernel, R = 2, one wave per unit (kv_len < 64)"),
+    "unit_r2_4waves": (0, 4, 4, 132, 128, 2, "unit/R2/4-waves", "dot-product kernel, R = 2, four waves per unit"),
+    "unit_d256_r2": (0, 4, 4, 132, 256, 2, "unit/R2/4-waves", "dot-product kernel at D = 256, R = 2, four waves per unit"),
+    "unit_d256_r4": (0, 4, 4, 132, 256, 3, "unit/R4/4-waves", "dot-product kernel at D = 256, R = 4 (3 rows; the matrix-core kernel refuses D = 256 with few units)"),
+    "unit_d256_r8": (0, 8, 2, 132, 256, 3, "unit/R8/4-waves", "dot-product kernel at D = 256, R = 8 in two row chunks (12 rows)"),
+    "gqa_d256": (0, 8, 2, 40, 256, 3, "gqa/1-wave/hpw2", "matrix-core kernel at D = 256, one wave per unit (kv_len < 128)"),
+}
+CAUSAL_PATTERNS = SCORE_PATTERNS + ("tail_staircase", "giants_behind_row_limit")
+CAUSAL_MERGE_ROUTES = ("gqa_4waves", "unit_r2_4waves")  # one matrix-core and one dot-product route, four waves per unit
+CAUSAL_LSE_PATTERNS = ("far_apart", "suffix_empty", "partials_empty", "all_empty", "near_ties")
+
+
+def causal_lengths(T: int, cap: int) -> list:
+    """Lengths at which a token's limit lands on a tile or wave boundary, just before and just after it; 0 and a negative length;
+    0 < len < T (rows whose limit is <= 0); the capacity and a length beyond it.  33 with T = 8 is the kernel header's own example:
+    wave 1 starts beyond row 0's limit."""
+    want = [0, -2, 1, T - 1, T, T + 1, 25, 26, 31, 32, 33, 33 + T - 1, 63, 64, 65, 127, 128, 129, 128 + T - 1, cap - 1, cap, cap + 3]
+    return list(dict.fromkeys(x for x in want if x <= cap + 3))
+
+
+def causal_shape(route: str):
+    """(B, Hq, Hkv, cap, D, T) with B resolved"""
+    B, Hq, Hkv, cap, D, T = CAUSAL_ROUTES[route][:6]
+    return (B or len(causal_lengths(T, cap))), Hq, Hkv, cap, D, T
+
+
+def causal_block_lens(route: str, seed: int) -> np.ndarray:
+    """the block's lengths as given to the kernel (unclamped): the listed ones, filled up to BLOCK for a repeated block"""
+    B, _, _, cap, _, T = causal_shape(route)
+    lens = causal_lengths(T, cap)
+    nb = block_size(B)
+    assert nb >= len(lens), (route, nb, len(lens))
+    lens += np.random.default_rng(seed).integers(1, cap + 1, nb - len(lens)).tolist()
+    return np.asarray(lens, np.int32)
+
+
+def causal_limits(lens: np.ndarray, cap: int, T: int) -> np.ndarray:
+    """[nb, T]: keys token i of each sequence sees -- max(0, clamp(len, 0, cap) - (T - 1 - i))"""
+    n = np.clip(np.asarray(lens, np.int64), 0, cap)
+    return np.maximum(0, n[:, None] - (T - 1 - np.arange(T))[None, :])
+
+
+def causal_amplitudes(pattern: str, lens: np.ndarray, cap: int, D: int, T: int, rng) -> np.ndarray:
+    """`amplitudes` laid out by the sequence's (clamped) length, plus the two patterns that only a per-row limit gives a meaning."""
+    n_of = np.clip(lens, 0, cap)
+    if pattern in SCORE_PATTERNS:
+        return amplitudes(pattern, n_of, cap, D, rng)
+    p = per(D)
+    amp = np.zeros((len(lens), cap))
+    for b, n in enumerate(int(x) for x in n_of):
+        if pattern == "tail_staircase":  # token i's newest visible key outweighs everything older by 2^24: out = v[len - T + i]
+            amp[b, n:] = 196.0 / p
+            for i in range(T):
+                if n - T + i >= 0:
+                    amp[b, n - T + i] = 24.0 * (i + 1) / p
+        elif pattern == "giants_behind_row_limit":  # this step's draft keys and the stale keys behind the length: token 0 sees none
+            amp[b, max(n - (T - 1), 0):] = 90.0 / p
+            if n - T >= 0:
+                amp[b, n - T] = 10.0 / p
+        else:
+            raise KeyError(pattern)
+    assert np.abs(amp).max() * p <= MAX_SCORE, pattern
+    return amp
+
+
+def causal_case(route: str, pattern: str, dt: str) -> dict:
+    """One block of a CAUSAL_ROUTES row: q [nb, T, Hq, D], k / v [nb, cap, Hkv, D] (float32, rounded to dt), lens [nb] as given to
+    the kernel.  The sequence of length cap + 3 holds the data of the one of length cap, the one of length -2 that of length 0: the
+    clamps must give the same bits."""
+    B, Hq, Hkv, cap, D, T = causal_shape(route)
+    seed = _seed("causal", route, pattern)
+    rng = np.random.default_rng(seed)
+    lens = causal_block_lens(route, seed)
+    nb = len(lens)
+    unit = unit_vector(D)
+    amp = causal_amplitudes(pattern, lens, cap, D, T, rng)
+    noise = lambda *s: 0.01 * rng.standard_normal(s, dtype=np.float32)  # noqa: E731
+    q = np.broadcast_to(unit, (nb, T, Hq, D)) + noise(nb, T, Hq, D)
+    k = (amp[:, :, None, None] * unit).astype(np.float32).repeat(Hkv, 2) + noise(nb, cap, Hkv, D)
+    if pattern == "ties":
+        q = np.zeros_like(q)
+    v = rng.standard_normal((nb, cap, Hkv, D), dtype=np.float32)
+    twins = [(list(lens).index(cap + 3), list(lens).index(cap)), (list(lens).index(-2), list(lens).index(0))]
+    for dst, src in twins:
+        q[dst], k[dst], v[dst] = q[src], k[src], v[src]
+    return dict(q=_round(q, dt), k=_round(k, dt), v=_round(v, dt), lens=lens, lim=causal_limits(lens, cap, T), twins=twins, B=B, cap=cap,
+                D=D, T=T, Hq=Hq, pattern=pattern, dt=dt)
+
+
+def causal_reference(q, k, v, lens, round_p=None):
+    """float64: per token i, O.flash_attention_seqlen over max(0, clamp(len, 0, cap) - (T - 1 - i)) keys; zeros and -inf where that
+    count is 0 (the rule tests/test_speculative.py::dense_causal_tail states)."""
+    nb, T, Hq, D = q.shape
+    lim = causal_limits(lens, k.shape[1], T)
+    out, lse = np.zeros((nb, T, Hq, D)), np.full((nb, T, Hq), -np.inf)
+    for i in range(T):
+        has = lim[:, i] > 0
+        if has.any():
+            o, l = O.flash_attention_seqlen(q[has, i:i + 1], k[has], v[has], lim[has, i], round_p=round_p)
+            out[has, i], lse[has, i] = o[:, 0], l[:, 0]
+    return out, lse
+
+
+def zero_from(k: np.ndarray, first: np.ndarray) -> np.ndarray:
+    """k with the keys from first[b] on zeroed"""
+    z = k.copy()
+    for b, n in enumerate(first):
+        z[b, max(int(n), 0):] = 0.0
+    return z
+
+
+def causal_ties_closed_form(v: np.ndarray, lim: np.ndarray, Hq: int):
+    """q = 0: token i returns the mean of v[:lim_i] with lse = ln(lim_i) -- every token's key count, exactly"""
+    nb, _, Hkv, D = v.shape
+    T = lim.shape[1]
+    out, lse = np.zeros((nb, T, Hq, D)), np.full((nb, T, Hq), -np.inf)
+    for b in range(nb):
+        for i in range(T):
+            n = int(lim[b, i])
+            if n:
+                out[b, i] = np.repeat(v[b, :n].astype(np.float64).mean(0), Hq // Hkv, axis=0)
+                lse[b, i] = np.log(n)
+    return out, lse
+
+
+def staircase_closed_form(v: np.ndarray, lim: np.ndarray, Hq: int) -> np.ndarray:
+    """tail_staircase: token i returns v[lim_i - 1] = v[len - T + i], to the 2^-24 every older key leaks"""
+    nb, _, Hkv, D = v.shape
+    out = np.zeros((nb, lim.shape[1], Hq, D))
+    for b in range(nb):
+        for i in range(lim.shape[1]):
+            if lim[b, i]:
+                out[b, i] = np.repeat(v[b, int(lim[b, i]) - 1].astype(np.float64), Hq // Hkv, axis=0)
+    return out
+
+
+CAUSAL_MERGE_LAYOUT = [("h", 1), ("f", 1), ("s", 5)]  # one 16-bit partial (prefetched), one fp32 partial, five stacked fp32 slices
+
+
+def causal_merge_case(route: str, pattern: str, dt: str) -> dict:
+    """merge_case through the causal entry point: standard normal q / k / v at the route's listed lengths (0 < len < T among them: a
+    token without a unique key), seven hand-made partials of an LSE pattern, `want` = O.combine_lse(partials + causal_reference)."""
+    B, Hq, Hkv, cap, D, T = causal_shape(route)
+    seed = _seed("causal merge", route, pattern)
+    rng = np.random.default_rng(seed)
+    lens = causal_block_lens(route, seed)
+    nb = len(lens)
+    rnd = lambda *s: _round(rng.standard_normal(s, dtype=np.float32), dt)  # noqa: E731
+    q, k, v = rnd(nb, T, Hq, D), rnd(nb, cap, Hkv, D), rnd(nb, cap, Hkv, D)
+    lens = merge_lens(pattern, lens)
+    kinds = layout_kinds(CAUSAL_MERGE_LAYOUT)
+    so, slse = causal_reference(q, k, v, lens)
+    lses = partial_lses(pattern, len(kinds), slse.shape, slse, rng)
+    outs = partial_outs(pattern, kinds, so.shape, lses, dt, rng)
+    ok = np.isfinite(np.stack(lses + [slse]).max(0))
+    want = np.where(ok[..., None], O.combine_lse(outs + [so], lses + [slse]), 0.0)
+    return dict(q=q, k=k, v=v, lens=lens, lim=causal_limits(lens, cap, T), parts=CAUSAL_MERGE_LAYOUT, kinds=kinds, outs=outs, lses=lses,
+                suffix_out=so, suffix_lse=slse, want=want, ok=ok, B=B, dt=dt, pattern=pattern)

@@ -159,3 +159,125 @@ def test_operator_cases_put_the_mass_where_they_say(mass):
         assert d.max() < -40.0
     else:
         assert np.abs(d).max() <= 1e-3
+
+
+# ---- the causal tail ----------------------------------------------------------------------------------------------------------
+def test_causal_route_labels_follow_the_launcher_rules():
+    for name, row in S.CAUSAL_ROUTES.items():
+        assert S.causal_route(*S.causal_shape(name)) == row[6], name
+        B, _, _, cap, _, T = S.causal_shape(name)
+        assert B == len(S.causal_lengths(T, cap)) or (B > 64 and S.block_size(B) >= len(S.causal_lengths(T, cap))), name
+    by_key = {}
+    for name, row in S.CAUSAL_ROUTES.items():
+        by_key.setdefault(row[6], []).append(row)
+    # the matrix-core kernel with 4 / 2 / 1 kv heads per workgroup and four waves per unit, the dot-product kernel R = 2 with one and
+    # four waves, R = 4 and R = 8 (D = 256 only)
+    assert {"gqa/1-wave/hpw4", "gqa/1-wave/hpw2", "gqa/1-wave/hpw1", "gqa/4-waves", "unit/R2/1-wave", "unit/R2/4-waves", "unit/R4/4-waves",
+            "unit/R8/4-waves"} <= set(by_key)
+    assert any(r[3] >= 128 for r in by_key["gqa/1-wave/hpw2"])  # one wave per unit on a cache four-wave units would take
+    assert any(r[3] >= 256 for r in by_key["gqa/4-waves"])  # every wave walks several 32-key tiles
+    assert {r[4] for r in S.CAUSAL_ROUTES.values() if r[6].startswith("gqa")} == {64, 128, 256}
+    assert {r[6] for r in S.CAUSAL_ROUTES.values() if r[4] == 256} == {"unit/R2/4-waves", "unit/R4/4-waves", "unit/R8/4-waves", "gqa/1-wave/hpw2"}
+    assert all(S.CAUSAL_ROUTES[r][6].endswith("4-waves") for r in S.CAUSAL_MERGE_ROUTES)
+    # a token count outside 2..8 is refused, never run without the limit
+    assert S.causal_route(8, 4, 4, 40, 128, 1) == "refused" and S.causal_route(8, 4, 4, 40, 128, 9) == "refused"
+
+
+@pytest.mark.parametrize("route", list(S.CAUSAL_ROUTES))
+def test_causal_tables_hold_the_listed_lengths(route):
+    B, Hq, Hkv, cap, D, T = S.causal_shape(route)
+    c = S.causal_case(route, "ties", "f16")
+    lens = c["lens"].tolist()
+    want = {0, -2, 1, T - 1, T, T + 1, cap - 1, cap, cap + 3} | {x for x in (25, 26, 31, 32, 33, 33 + T - 1, 63, 64, 65, 127, 128, 129, 128 + T - 1) if x <= cap + 3}
+    assert want <= set(lens) and len(lens) == S.block_size(B)
+    assert any(0 < n < T for n in lens)  # a sequence shorter than the step: tokens whose limit is <= 0 beside tokens that see keys
+    lim = c["lim"]
+    assert lim.min() == 0 and lim.max() == cap and (lim[:, -1] == np.clip(c["lens"], 0, cap)).all() and (np.diff(lim, axis=1) >= 0).all()
+    for dst, src in c["twins"]:  # the clamps: the same data at length cap + 3 / cap and at -2 / 0
+        assert all(np.array_equal(c[x][dst], c[x][src]) for x in "qkv") and (lim[dst] == lim[src]).all()
+
+
+@pytest.mark.parametrize("dt", ["f16", "bf16"])
+def test_causal_patterns_have_their_closed_forms(dt):
+    for route in ("gqa_hpw2", "unit_r2_4waves", "gqa_4waves_tiles", "unit_d256_r8"):
+        B, Hq, Hkv, cap, D, T = S.causal_shape(route)
+        c = S.causal_case(route, "ties", dt)
+        has = c["lim"] > 0
+        out, lse = S.causal_reference(c["q"], c["k"], c["v"], c["lens"])
+        want, wlse = S.causal_ties_closed_form(c["v"], c["lim"], Hq)
+        assert np.abs(out - want).max() <= 1e-12 and np.abs(lse[has] - wlse[has]).max() <= 1e-12 and np.isneginf(lse[~has]).all()
+        c = S.causal_case(route, "tail_staircase", dt)
+        out, lse = S.causal_reference(c["q"], c["k"], c["v"], c["lens"])
+        cf = S.staircase_closed_form(c["v"], c["lim"], Hq)
+        assert np.abs(out - cf).max() <= 2e-4, (route, np.abs(out - cf).max())
+        # an off-by-one limit in either direction returns another V row: the neighbours differ by far more than any bound
+        for b, i in zip(*np.nonzero(c["lim"] > 1)):
+            n = int(c["lim"][b, i])
+            assert np.abs(c["v"][b, n - 1] - c["v"][b, n - 2]).max() > 0.5 and (n == cap or np.abs(c["v"][b, n - 1] - c["v"][b, n]).max() > 0.5)
+        # the reference does not look behind a sequence's length, nor behind token 0's limit
+        z = S.zero_behind_length(c["k"], np.clip(c["lens"], 0, cap))
+        out0, lse0 = S.causal_reference(c["q"], z, c["v"], c["lens"])
+        assert np.array_equal(out0, out) and np.array_equal(lse0, lse)
+        c = S.causal_case(route, "giants_behind_row_limit", dt)
+        out, lse = S.causal_reference(c["q"], c["k"], c["v"], c["lens"])
+        out0, lse0 = S.causal_reference(c["q"], S.zero_from(c["k"], c["lim"][:, 0]), c["v"], c["lens"])
+        assert np.array_equal(out0[:, 0], out[:, 0]) and np.array_equal(lse0[:, 0], lse[:, 0])
+        assert T == 2 or not np.array_equal(out0[:, 1:], out[:, 1:])  # (the later tokens do see giants)
+
+
+def test_causal_patterns_put_finite_giants_behind_the_limits():
+    for route, pattern, low in (("gqa_hpw2", "giants_behind_row_limit", 80.0), ("gqa_hpw2", "tail_staircase", 180.0), ("unit_r2_4waves", "last_key_spike", 25.0)):
+        B, Hq, Hkv, cap, D, T = S.causal_shape(route)
+        c = S.causal_case(route, pattern, "bf16")
+        g = Hq // Hkv
+        s = np.einsum("bhd,bkhd->bhk", c["q"][:, 0].astype(np.float64), c["k"].astype(np.float64).repeat(g, 2)) * D ** -0.5 * S.LOG2E
+        assert np.abs(s).max() <= S.MAX_SCORE
+        seen = 0
+        for b, n in enumerate(c["lim"][:, 0]):  # token 0: everything it sees is small, and a giant sits right behind its limit
+            n_len = int(np.clip(c["lens"][b], 0, cap))
+            if pattern == "last_key_spike":
+                if n_len >= T:
+                    assert s[b, :, n_len - 1].min() > low and s[b, :, :n].max() < 1.0
+                    seen += 1
+            elif n < cap:
+                assert s[b, :, n:].min() > (low if pattern == "giants_behind_row_limit" else 20.0) and (n == 0 or s[b, :, :n].max() < 28.0)
+                assert pattern != "tail_staircase" or n_len == cap or s[b, :, n_len:].min() > low
+                seen += 1
+        assert seen >= 10
+
+
+@pytest.mark.parametrize("dt", ["f16", "bf16"])
+@pytest.mark.parametrize("pattern", S.CAUSAL_PATTERNS)
+@pytest.mark.parametrize("route", list(S.CAUSAL_ROUTES))
+def test_reference_rounding_model_meets_half_the_bounds_on_causal_cases(route, pattern, dt):
+    c = S.causal_case(route, pattern, dt)
+    has = c["lim"] > 0
+    want, wlse = S.causal_reference(c["q"], c["k"], c["v"], c["lens"])
+    assert np.isfinite(want).all() and np.isfinite(wlse[has]).all() and np.isneginf(wlse[~has]).all() and not want[~has].any()
+    assert has.any() and (~has).any() and np.abs(wlse[has]).max() <= (S.MAX_SCORE + 8) * np.log(2.0)
+    model, _ = S.causal_reference(c["q"], c["k"], c["v"], c["lens"], round_p=ROUND[dt])
+    ra, rl = err_over_bound(ROUND[dt](model)[has], want[has], dt)
+    print(f"model-ratio {route} {pattern} {dt}: {ra:.3f} {rl:.3f}")
+    assert ra <= 0.5 and rl <= 0.5, f"{route} {pattern} {dt}: max abs at {ra:.2f} of its bound, relative L2 at {rl:.2f}"
+
+
+@pytest.mark.parametrize("dt", ["f16", "bf16"])
+@pytest.mark.parametrize("pattern", S.CAUSAL_LSE_PATTERNS)
+@pytest.mark.parametrize("route", S.CAUSAL_MERGE_ROUTES)
+def test_reference_rounding_model_meets_half_the_bounds_on_causal_merges(route, pattern, dt):
+    c = S.causal_merge_case(route, pattern, dt)
+    ok, fin = c["ok"], np.isfinite(c["suffix_lse"])
+    model = ROUND[dt](np.where(ok[..., None], O.combine_lse(c["outs"] + [c["suffix_out"]], c["lses"] + [c["suffix_lse"]]), 0.0))
+    if pattern == "all_empty":
+        assert not ok.any() and not c["want"].any()
+        return
+    ra, rl = err_over_bound(model[ok], c["want"][ok], dt)
+    assert ra <= 0.5 and rl <= 0.5, f"{route} {pattern} {dt}: {ra:.2f} {rl:.2f}"
+    assert (fin == (c["lim"] > 0)[..., None]).all()
+    if pattern == "partials_empty":
+        assert np.array_equal(c["want"][ok], c["suffix_out"][ok]) and (ok == fin).all()
+    else:  # tokens without a unique key (0 < len < T among them) that have finite partials: the merge of the partials alone
+        lone = ok & ~fin
+        assert lone.any() and (pattern == "suffix_empty" or (lone.any(1).any(1) & fin.any(1).any(1)).any())
+        alone = O.combine_lse(c["outs"], c["lses"])
+        assert np.abs(c["want"][lone] - alone[lone]).max() <= 1e-12

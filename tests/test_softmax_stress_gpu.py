@@ -130,7 +130,7 @@ def test_fp8_suffix_kernels_on_adversarial_scores(monkeypatch, route, pattern, d
 
 
 # ---- c. hand-made partials into hyd_suffix_attn_fwd ----------------------------------------------------------------------------
-def _run_merge(c, route, dt, what):
+def _run_merge(c, route, dt, what, causal=False):
     B = c["B"]
     groups, at = [], 0
     for kind, cnt in c["parts"]:
@@ -140,7 +140,7 @@ def _run_merge(c, route, dt, what):
     ok, want, slse = _full(c["ok"], B), _full(c["want"], B), _full(c["suffix_lse"], B)
     fin = np.isfinite(slse)
     for want_lse in (False, True):
-        out, lse = suffix_fwd_with_partials(tq, tk, tv, tsl, groups, dt, want_lse)
+        out, lse = suffix_fwd_with_partials(tq, tk, tv, tsl, groups, dt, want_lse, causal)
         got = out.float().cpu().numpy()
         assert np.isfinite(got).all(), what
         if ok.any():
@@ -181,6 +181,65 @@ def test_far_apart_partials_over_a_negligible_suffix(route, dt):
     """far_apart LSEs on far_below scores: the suffix pass's own state (LSE about -41) is the negligible one of the merge"""
     c = S.merge_case(route, "far_apart", dt, scores="far_below")
     _run_merge(c, route, dt, f"{route} far_apart on far_below {dt}")
+
+
+# ---- c2. the causal tail: a per-row key limit in the score mask -----------------------------------------------------------------
+def _bits(t):
+    return t.view(torch.int16 if t.element_size() == 2 else torch.int32)
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+@pytest.mark.parametrize("pattern", S.CAUSAL_PATTERNS)
+@pytest.mark.parametrize("route", list(S.CAUSAL_ROUTES))
+def test_causal_tail_kernels_on_adversarial_scores(route, pattern, dt):
+    """hyd_suffix_attn_causal_fwd on every route of CAUSAL_ROUTES: the score patterns laid out by the sequence's length (so that
+    last_key_spike is a giant behind the limit of every token but the last), tail_staircase and giants_behind_row_limit, at lengths
+    whose limits land on, before and after the tile and wave boundaries, with 0 < len < T, len > kv_len and len < 0."""
+    from hydragen_amd.flash import flash_attention_seqlen
+
+    B, Hq, Hkv, cap, D, T = S.causal_shape(route)
+    c = S.causal_case(route, pattern, dt)
+    tq, tk, tv, tsl = _tile(c["q"], B, dt), _tile(c["k"], B, dt), _tile(c["v"], B, dt), _tile(c["lens"], B)
+    assert tuple(tq.shape) == (B, T, Hq, D) and tuple(tk.shape) == (B, cap, Hkv, D)
+    out, lse = flash_attention_seqlen(tq, tk, tv, seq_len=tsl, causal_tail=True)
+    torch.cuda.synchronize()
+    want, wlse = S.causal_reference(c["q"], c["k"], c["v"], c["lens"])
+    got, gl = out.float().cpu().numpy(), lse.cpu().numpy()
+    assert np.isfinite(got).all() and not np.isnan(gl).any()
+    has = _full(c["lim"], B) > 0  # [B, T]: the (sequence, token) pairs with a visible key
+    want, wlse = _full(want, B), _full(wlse, B)
+    what = f"causal {route} {pattern} {dt}"
+    _check_out(got[has], want[has], dt, what)
+    _check_lse(gl[has], wlse[has], what)
+    # no visible key (length <= 0, and the first tokens of a sequence shorter than the step): exact zeros, lse = -inf
+    assert (~has).any() and not got[~has].any() and np.all(np.isneginf(gl[~has])), what
+    for dst, src in c["twins"]:  # length cap + 3 is length cap, length -2 is length 0: the same data, the same bits
+        assert torch.equal(_bits(out[dst]), _bits(out[src])) and torch.equal(_bits(lse[dst]), _bits(lse[src])), (what, dst, src)
+    n_of = np.clip(c["lens"], 0, cap)
+    if pattern in ("spike_behind_length", "tail_staircase"):  # the giants behind the length against zeros there: not one bit may move
+        out0, lse0 = flash_attention_seqlen(tq, _tile(S.zero_behind_length(c["k"], n_of), B, dt), tv, seq_len=tsl, causal_tail=True)
+        assert torch.equal(_bits(out0), _bits(out)) and torch.equal(_bits(lse0), _bits(lse)), what
+    if pattern == "giants_behind_row_limit":  # ... and behind token 0's limit: this step's draft keys are nothing to token 0
+        out0, lse0 = flash_attention_seqlen(tq, _tile(S.zero_from(c["k"], c["lim"][:, 0]), B, dt), tv, seq_len=tsl, causal_tail=True)
+        assert torch.equal(_bits(out0[:, 0]), _bits(out[:, 0])) and torch.equal(_bits(lse0[:, 0]), _bits(lse[:, 0])), what
+    if pattern == "ties":  # every token's key count, exactly
+        cf, cl = S.causal_ties_closed_form(c["v"], c["lim"], Hq)
+        _check_out(got[has], _full(cf, B)[has], dt, what + " closed form")
+        _check_lse(gl[has], _full(cl, B)[has], what + " closed form")
+    if pattern == "tail_staircase":  # token i returns v[len - T + i]: a limit off by one key returns another row
+        _check_out(got[has], _full(S.staircase_closed_form(c["v"], c["lim"], Hq), B)[has], dt, what + " closed form")
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+@pytest.mark.parametrize("pattern", S.CAUSAL_LSE_PATTERNS)
+@pytest.mark.parametrize("route", S.CAUSAL_MERGE_ROUTES)
+def test_causal_tail_kernels_merge_partials_on_adversarial_lses(route, pattern, dt):
+    """Hand-made partials through hyd_suffix_attn_causal_fwd, bounds as test_suffix_kernels_merge_partials_on_adversarial_lses.  A
+    token without a unique key (length 0, or 0 < len < T) that has a finite partial returns the merge of the partials alone."""
+    c = S.causal_merge_case(route, pattern, dt)
+    got = _run_merge(c, route, dt, f"causal {route} {pattern} {dt}", causal=True)
+    if pattern == "all_empty":
+        assert not got.any()
 
 
 # ---- d. combine_lse (combine.hip) and _combine_many ------------------------------------------------------------------------------

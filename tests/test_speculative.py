@@ -317,6 +317,29 @@ def test_end_to_end_seeds_keep_every_greedy_decision_clear_of_the_gap(heads, kv_
     assert min(gaps) >= 2 * tg.GAP, (min(gaps), tg.GAP)  # (twice: plain decoding's own error may move a gap by up to GAP)
 
 
+@pytest.mark.parametrize("heads, kv_heads", [(4, 4), (4, 2)])
+def test_ragged_seeds_keep_five_rows_in_six_clear_of_the_gap(heads, kv_heads):
+    """The same for the ragged inputs of tests/test_speculative_paths_gpu.py, whose condition allows one cut row in six: per row the
+    smallest top-2 gap of the float64 greedy decode; every row is above GAP and all but one above 2 GAP."""
+    from tests import test_speculative_gpu as tg
+    from tests import test_speculative_paths_gpu as tp
+
+    seed = tp.RAGGED_SEEDS[(heads, kv_heads)]
+    model = tg.cpu_model(heads, kv_heads, seed)
+    shared, uniq = tp.ragged_inputs(seed)
+    rows = []
+    for b, n in enumerate(tp.RAGGED_LENS):
+        seq, gaps = torch.cat([shared[b // 3], uniq[b, :n]])[None], []
+        for _ in range(tp.RAGGED_NEW):
+            top = tg.ref_logits64(model, seq)[:, -1].topk(2, -1)
+            gaps.append(float(top.values[0, 0] - top.values[0, 1]))
+            seq = torch.cat([seq, top.indices[:, :1]], 1)
+        rows.append(min(gaps))
+    assert min(rows) > tg.GAP and sorted(rows)[1] >= 2 * tg.GAP, rows
+    assert [round(x, 4) for x in sorted(rows)[:2]] == list(tp.RAGGED_GAPS[(heads, kv_heads)]) and (heads, kv_heads) in tp.RAGGED_GEOMETRIES
+    assert min(tp.RAGGED_LENS) < 16 < max(tp.RAGGED_LENS) and 32 < max(tp.RAGGED_LENS) and len(set(tp.RAGGED_LENS)) == 6
+
+
 # ---- the C ABI: additive, validated without a launch ----------------------------------------------------------------------------
 def test_symbols_declared_exported_and_version_stays():
     lib = _lib.load()

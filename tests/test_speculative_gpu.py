@@ -135,21 +135,23 @@ def test_causal_tail_is_never_silently_non_causal():
 
 
 # ---- hyd_rope_append_multi against exact float64 arithmetic ---------------------------------------------------------------------
-@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
-@pytest.mark.parametrize("T", [2, 8])
-@pytest.mark.parametrize("D", [64, 128])
-def test_rope_append_multi_exact(dtype, T, D):
+def _rope_append_multi_exact(dtype, T, D, fused=False, table_end=False):
+    """fused: q / k / v are views into one [B, T, (Hq + 2 Hkv) D] projection buffer (token stride (Hq + 2 Hkv) D, heads contiguous).
+    table_end: a fifth row whose later tokens' positions reach and pass max_pos -- they take the table's last row (the header:
+    positions are clamped to it) and are written all the same."""
     from hydragen_amd.fused_decode import rope_append_multi
 
-    B, Hq, Hkv, cache_len, G = 4, 8, 2, 12, glue_ref.GUARD
+    B, Hq, Hkv, cache_len, G = 5 if table_end else 4, 8, 2, 12, glue_ref.GUARD
     cos, sin = glue_ref.exact_tables(D)
     q, k, v = (x.reshape(B, T, -1, D) for x in glue_ref.exact_inputs(B * T, Hq, Hkv, D))
     shared = np.array([3, 7, 5, 0], dtype=np.int64)
     # row 1: position shared_len - 1 (retired); row 2: its last tokens (1 of 2, 3 of 8) fall past the cache
     idx0 = np.array([0, -1, cache_len - T + min(3, T - 1), 2], dtype=np.int64)
+    if table_end:  # row 4: first position max_pos - 2 at cache index 3 -- tokens 2 .. T - 1 are at max_pos and beyond
+        shared, idx0 = np.append(shared, glue_ref.EXACT_MAX_POS - 5), np.append(idx0, 3)
     pos0 = shared + idx0
     pos = pos0[:, None] + np.arange(T)[None, :]
-    assert pos.max() < glue_ref.EXACT_MAX_POS
+    assert pos[:4].max() < glue_ref.EXACT_MAX_POS and (not table_end or (pos[4, 1] == glue_ref.EXACT_MAX_POS - 1 and pos[4, 2] == glue_ref.EXACT_MAX_POS))
     rows = np.clip(pos, 0, glue_ref.EXACT_MAX_POS - 1).reshape(-1)
     want_q = glue_ref.to_dtype_exact(glue_ref.rope_ref64(q.reshape(B * T, Hq, D), cos[rows], sin[rows]), dtype).reshape(B, T, Hq, D)
     want_k = glue_ref.to_dtype_exact(glue_ref.rope_ref64(k.reshape(B * T, Hkv, D), cos[rows], sin[rows]), dtype).reshape(B, T, Hkv, D)
@@ -158,7 +160,12 @@ def test_rope_append_multi_exact(dtype, T, D):
     kbuf = glue_ref.sentinel16((B + 1, cache_len + G, Hkv, D), dtype, 1)
     vbuf = glue_ref.sentinel16((B + 1, cache_len + G, Hkv, D), dtype, 2)
     dk, dv = kbuf.to(DEV), vbuf.to(DEV)
-    q_out, sl = rope_append_multi(tq.to(DEV), tk.to(DEV), tv.to(DEV), torch.from_numpy(cos).to(DEV), torch.from_numpy(sin).to(DEV),
+    dq, dkk, dvv = tq.to(DEV), tk.to(DEV), tv.to(DEV)
+    if fused:
+        buf = torch.cat([x.reshape(B, T, -1) for x in (dq, dkk, dvv)], -1)
+        dq, dkk, dvv = (x.unflatten(-1, (-1, D)) for x in buf.split([Hq * D, Hkv * D, Hkv * D], -1))
+        assert dq.stride(1) == (Hq + 2 * Hkv) * D and not dkk.is_contiguous() and dvv.data_ptr() == buf.data_ptr() + 2 * (Hq + Hkv) * D
+    q_out, sl = rope_append_multi(dq, dkk, dvv, torch.from_numpy(cos).to(DEV), torch.from_numpy(sin).to(DEV),
                                   torch.from_numpy(pos0).to(DEV), torch.from_numpy(shared).to(DEV), dk[:B, :cache_len], dv[:B, :cache_len])
     torch.cuda.synchronize()
     bits = glue_ref.bits
@@ -173,6 +180,24 @@ def test_rope_append_multi_exact(dtype, T, D):
     assert torch.equal(bits(dk.cpu()), bits(exp_k)), "K: written rows hold the rotated keys, every other byte (guards, the retired row) is untouched"
     assert torch.equal(bits(dv.cpu()), bits(exp_v)), "V likewise"
     assert not torch.equal(bits(exp_k[2, cache_len - 1]), bits(kbuf[2, cache_len - 1])) and torch.equal(bits(exp_k[1]), bits(kbuf[1]))
+    if table_end:  # the tokens past the table were rotated by its LAST row, not by their predecessor's and not skipped
+        last = np.array([glue_ref.EXACT_MAX_POS - 1])
+        for i in range(2, T):
+            alone = glue_ref.to_dtype_exact(glue_ref.rope_ref64(k[4, i][None], cos[last], sin[last]), dtype)[0]
+            assert torch.equal(bits(dk.cpu()[4, 3 + i]), bits(alone)) and not torch.equal(bits(alone), bits(tk[4, i]))
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("T", [2, 8])
+@pytest.mark.parametrize("D", [64, 128, 256])
+def test_rope_append_multi_exact(dtype, T, D):
+    _rope_append_multi_exact(dtype, T, D)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("T, D, fused, table_end", [(3, 128, True, False), (8, 256, True, True), (3, 64, False, True)])
+def test_rope_append_multi_on_fused_views_and_at_the_end_of_the_tables(dtype, T, D, fused, table_end):
+    _rope_append_multi_exact(dtype, T, D, fused, table_end)
 
 
 # ---- hyd_draft_lookup and hyd_draft_accept: exactly their definitions ----------------------------------------------------------
