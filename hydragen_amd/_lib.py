@@ -133,6 +133,18 @@ class DraftAcceptParams(C.Structure):
     ]
 
 
+class DfaForcedParams(C.Structure):
+    _fields_ = [("allowed", C.c_void_p), ("forced", C.c_void_p), ("allowed_stride", C.c_int64), ("n_states", C.c_int32), ("n", C.c_int32)]
+
+
+class DraftConstrainParams(C.Structure):
+    _fields_ = [
+        ("state", C.c_void_p), ("fed", C.c_void_p), ("n_proposed", C.c_void_p), ("forced", C.c_void_p), ("next", C.c_void_p),
+        ("step_state", C.c_void_p), ("n_forced", C.c_void_p), ("fed_stride", C.c_int64), ("next_stride", C.c_int64),
+        ("B", C.c_int32), ("K", C.c_int32), ("n_states", C.c_int32), ("n", C.c_int32), ("only_forced", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 class AddRmsnormParams(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("residual", C.c_void_p), ("weight", C.c_void_p), ("sum_out", C.c_void_p), ("norm_out", C.c_void_p),
@@ -331,6 +343,9 @@ EXPORTS = {
     "hyd_rope_append_multi": (C.c_int, [C.POINTER(RopeMultiParams), C.c_void_p]),
     "hyd_draft_lookup": (C.c_int, [C.POINTER(DraftLookupParams), C.c_void_p]),
     "hyd_draft_accept": (C.c_int, [C.POINTER(DraftAcceptParams), C.c_void_p]),
+    "hyd_dfa_forced_tokens": (C.c_int, [C.POINTER(DfaForcedParams), C.c_void_p]),
+    "hyd_draft_constrain": (C.c_int, [C.POINTER(DraftConstrainParams), C.c_void_p]),
+    "hyd_draft_accept_states": (C.c_int, [C.POINTER(DraftAcceptParams), C.c_void_p, C.c_void_p, C.c_void_p]),
     "hyd_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }

@@ -35,14 +35,53 @@ def pack_allowed(nxt: Tensor) -> Tensor:
     return torch.where(packed >= 2 ** 31, packed - 2 ** 32, packed).to(torch.int32)
 
 
+def forced_tokens_reference(allowed: Tensor, n: int) -> Tensor:
+    """The rule hyd_dfa_forced_tokens implements, in numpy -> forced int32 [S] on the CPU: forced[s] = the token of the ONE bit
+    at a position below n in row s of allowed (int32 [S, >= ceil(n / 32)] words, pack_allowed's layout), -1 for a row with no
+    such bit or with two and more.  Bits at positions >= n and words past ceil(n / 32) do not count."""
+    a = np.ascontiguousarray(allowed.detach().cpu().numpy())
+    if a.ndim != 2 or a.dtype != np.int32 or n <= 0 or a.shape[1] < (n + 31) // 32:
+        raise ValueError(f"allowed must be int32 [S, >= ceil(n / 32) = {(n + 31) // 32}] with n > 0, got {a.shape} {a.dtype}, n = {n}")
+    S, words = a.shape[0], (n + 31) // 32
+    forced = np.full(S, -1, dtype=np.int32)
+    rows = max(1, (64 << 20) // (words * 32))  # (rows unpacked at a time: one byte per bit)
+    for r in range(0, S, rows):
+        w = np.ascontiguousarray(a[r : r + rows, :words]).astype("<u4").view(np.uint8)
+        bits = np.unpackbits(w, axis=1, bitorder="little")[:, :n]
+        forced[r : r + rows] = np.where(bits.sum(1) == 1, bits.argmax(1), -1)
+    return torch.from_numpy(forced)
+
+
+def forced_tokens(allowed: Tensor, n: int) -> Tensor:
+    """hyd_dfa_forced_tokens, one launch -> forced int32 [S] on allowed's device; CPU tensors take forced_tokens_reference.
+    allowed int32 [S, stride >= ceil(n / 32)] with a unit last stride (a row stride wider than the row is honoured)."""
+    if allowed.device.type != "cuda":
+        return forced_tokens_reference(allowed, n)
+    import ctypes as C
+
+    from . import _lib
+
+    if allowed.ndim != 2 or allowed.dtype != torch.int32 or allowed.stride(1) != 1 or n <= 0 or allowed.shape[1] < (n + 31) // 32:
+        raise ValueError(f"allowed must be int32 [S, >= ceil(n / 32)] with a unit last stride, got {tuple(allowed.shape)} {allowed.dtype}")
+    S = allowed.shape[0]
+    forced = torch.empty((S,), dtype=torch.int32, device=allowed.device)
+    p = _lib.DfaForcedParams()
+    p.allowed, p.forced, p.allowed_stride = allowed.data_ptr(), forced.data_ptr(), allowed.stride(0) if S > 1 else allowed.shape[1]
+    p.n_states, p.n = S, n
+    with torch.cuda.device(allowed.device):
+        _lib.check(_lib.load().hyd_dfa_forced_tokens(C.byref(p), torch.cuda.current_stream().cuda_stream))
+    return forced
+
+
 class TokenDFA:
     """A token automaton: next int32 [S, n] (>= 0: the next state, DFA_REJECT, DFA_FREE) and the bitmap allowed int32
     [S, ceil(n / 32)] derived from it once.  accepting: bool [S] or None (all False): the states in which the output so far is
     complete.  meta: whatever the constructor wants to remember (from_choices keeps the choice of every state).
-    start_states: the entry states (one per group of choices; [0] otherwise)."""
+    start_states: the entry states (one per group of choices; [0] otherwise).  forced int32 [S]: the one token a state
+    allows, or -1 (speculative decoding's certain drafts), made from the bitmap on first use and kept."""
 
     def __init__(self, next: Tensor, accepting: Optional[Tensor] = None, meta: Optional[dict] = None,
-                 max_table_bytes: int = MAX_TABLE_BYTES, _allowed: Optional[Tensor] = None):
+                 max_table_bytes: int = MAX_TABLE_BYTES, _allowed: Optional[Tensor] = None, _forced: Optional[Tensor] = None):
         nxt = torch.as_tensor(next)
         if nxt.ndim != 2 or nxt.shape[0] <= 0 or nxt.shape[1] <= 0:
             raise ValueError(f"next must be [S, n] with S, n > 0, got {tuple(nxt.shape)}")
@@ -58,6 +97,7 @@ class TokenDFA:
                              f"{int(nxt.min())} .. {int(nxt.max())}")
         self.next = nxt.to(torch.int32).contiguous()
         self.allowed = pack_allowed(self.next) if _allowed is None else _allowed
+        self._forced = _forced
         if accepting is None:
             accepting = torch.zeros(S, dtype=torch.bool)
         accepting = torch.as_tensor(accepting).bool().reshape(-1)
@@ -72,9 +112,18 @@ class TokenDFA:
     vocab_size = property(lambda self: self.next.shape[1])
     device = property(lambda self: self.next.device)
 
+    @property
+    def forced(self) -> Tensor:
+        """int32 [S] on the automaton's device: the token of a state that allows exactly one, else -1 (hyd_dfa_forced_tokens on
+        the GPU, forced_tokens_reference on the CPU; computed once)."""
+        if self._forced is None:
+            self._forced = forced_tokens(self.allowed, self.vocab_size)
+        return self._forced
+
     def to(self, device) -> "TokenDFA":
-        """The same automaton with both tensors on `device` (the bitmap is copied, not rebuilt)."""
-        return TokenDFA(self.next.to(device), self.accepting, self.meta, self.max_table_bytes, _allowed=self.allowed.to(device))
+        """The same automaton with its tensors on `device` (the bitmap, and forced once it exists, are copied, not rebuilt)."""
+        return TokenDFA(self.next.to(device), self.accepting, self.meta, self.max_table_bytes, _allowed=self.allowed.to(device),
+                        _forced=None if self._forced is None else self._forced.to(device))
 
     def choice_of(self, states) -> Tensor:
         """from_choices automata: for every state, the index (within its group) of the choice that has been completed there --

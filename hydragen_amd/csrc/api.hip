@@ -1062,7 +1062,48 @@ int hyd_draft_lookup(const hyd_draft_lookup_params* p, void* stream) {
     return launched(launch_draft_lookup(*p, static_cast<hipStream_t>(stream)), "draft_lookup kernel launch");
 }
 
+int hyd_dfa_forced_tokens(const hyd_dfa_forced_params* p, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    if (p->n_states <= 0 || p->n <= 0) return fail(HYD_ERR_BAD_ARG, "n_states %d, n %d must be > 0", p->n_states, p->n);
+    if (p->allowed_stride < (p->n + 31) / 32)
+        return fail(HYD_ERR_BAD_ARG, "allowed_stride %lld < ceil(n / 32) = %d words", (long long)p->allowed_stride, (p->n + 31) / 32);
+    if (!p->allowed || !p->forced) return fail(HYD_ERR_BAD_ARG, "allowed / forced is null");
+    if (misaligned(p->allowed, 4) || misaligned(p->forced, 4)) return fail(HYD_ERR_BAD_ARG, "allowed / forced is not aligned to its element size");
+    return launched(launch_dfa_forced(*p, static_cast<hipStream_t>(stream)), "dfa_forced kernel launch");
+}
+
+int hyd_draft_constrain(const hyd_draft_constrain_params* p, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    if (p->B < 0) return fail(HYD_ERR_BAD_ARG, "B %d", p->B);
+    if (p->K < 1 || p->K > 7) return fail(HYD_ERR_BAD_ARG, "K = %d drafts per row, 1 to 7 are taken", p->K);
+    if (p->n_states <= 0 || p->n <= 0) return fail(HYD_ERR_BAD_ARG, "n_states %d, n %d must be > 0", p->n_states, p->n);
+    if (p->next_stride < p->n) return fail(HYD_ERR_BAD_ARG, "next_stride %lld < n %d", (long long)p->next_stride, p->n);
+    if (p->fed_stride < p->K + 1) return fail(HYD_ERR_BAD_ARG, "fed_stride %lld < K + 1 = %d", (long long)p->fed_stride, p->K + 1);
+    if (!p->state || !p->fed || !p->forced || !p->next || !p->step_state || !p->n_forced)
+        return fail(HYD_ERR_BAD_ARG, "state / fed / forced / next / step_state / n_forced is null");
+    if (misaligned(p->fed, 8) || misaligned(p->state, 4) || misaligned(p->n_proposed, 4) || misaligned(p->forced, 4) ||
+        misaligned(p->next, 4) || misaligned(p->step_state, 4) || misaligned(p->n_forced, 4))
+        return fail(HYD_ERR_BAD_ARG, "state / fed / n_proposed / forced / next / step_state / n_forced is not aligned to its element size");
+    return launched(launch_draft_constrain(*p, static_cast<hipStream_t>(stream)), "draft_constrain kernel launch");
+}
+
+static int check_draft_accept(const hyd_draft_accept_params* p);
+
+int hyd_draft_accept_states(const hyd_draft_accept_params* p, const int32_t* step_state_after, int32_t* state, void* stream) {
+    if (!step_state_after && !state) return hyd_draft_accept(p, stream);
+    const int rc = check_draft_accept(p);
+    if (rc) return rc;
+    if (!step_state_after || !state) return fail(HYD_ERR_BAD_ARG, "step_state_after and state go together: one of them is null");
+    if (misaligned(step_state_after, 4) || misaligned(state, 4)) return fail(HYD_ERR_BAD_ARG, "step_state_after / state is not aligned to its element size");
+    return launched(launch_draft_accept_states(*p, step_state_after, state, static_cast<hipStream_t>(stream)), "draft_accept kernel launch");
+}
+
 int hyd_draft_accept(const hyd_draft_accept_params* p, void* stream) {
+    const int rc = check_draft_accept(p);
+    return rc ? rc : launched(launch_draft_accept(*p, static_cast<hipStream_t>(stream)), "draft_accept kernel launch");
+}
+
+static int check_draft_accept(const hyd_draft_accept_params* p) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
     if (p->rows < 0) return fail(HYD_ERR_BAD_ARG, "rows %d", p->rows);
     if (p->T < 1 || p->T > 8) return fail(HYD_ERR_BAD_ARG, "T = %d tokens per row (K = %d drafts): 1 to 8 tokens are taken", p->T, p->T - 1);
@@ -1078,7 +1119,7 @@ int hyd_draft_accept(const hyd_draft_accept_params* p, void* stream) {
     if (misaligned(p->length, 4) || misaligned(p->reason, 4) || misaligned(p->stop_index, 4) || misaligned(p->accepted, 4) ||
         misaligned(p->live, 4) || misaligned(p->logprobs, 4) || misaligned(p->out_logprobs, 4))
         return fail(HYD_ERR_BAD_ARG, "length / reason / stop_index / accepted / live / logprobs / out_logprobs is not aligned to its element size");
-    return launched(launch_draft_accept(*p, static_cast<hipStream_t>(stream)), "draft_accept kernel launch");
+    return HYD_OK;
 }
 
 int hyd_kv_promote(const hyd_kv_promote_params* p, void* stream) {

@@ -10,7 +10,10 @@
 
 namespace hyd {
 
-__global__ __launch_bounds__(64) void draft_accept_kernel(const hyd_draft_accept_params a) {
+// STATES (hyd_draft_accept_states): a row that emits e >= 1 tokens also takes the automaton state behind its last emitted token,
+// state[b] = after[b, e - 1] -- the constrained sampler has advanced the step's states in place, one per logits row.
+template <bool STATES>
+__global__ __launch_bounds__(64) void draft_accept_kernel(const hyd_draft_accept_params a, const int32_t* after, int32_t* state) {
     const int b = (int)blockIdx.x * 64 + (int)threadIdx.x;
     bool running = false;
     if (b < a.rows) {
@@ -48,6 +51,7 @@ __global__ __launch_bounds__(64) void draft_accept_kernel(const hyd_draft_accept
             len += e;
             emitted = e;
             a.length[b] = len;
+            if (STATES) state[b] = after[(int64_t)b * T + e - 1];
             if (which >= 0) {
                 r = 1;
                 a.reason[b] = 1;
@@ -67,7 +71,14 @@ __global__ __launch_bounds__(64) void draft_accept_kernel(const hyd_draft_accept
 int launch_draft_accept(const hyd_draft_accept_params& p, hipStream_t s) {
     const int grid = (p.rows + 63) / 64;
     if (grid == 0) return 0;
-    hipLaunchKernelGGL(draft_accept_kernel, dim3(grid), dim3(64), 0, s, p);
+    hipLaunchKernelGGL(draft_accept_kernel<false>, dim3(grid), dim3(64), 0, s, p, (const int32_t*)nullptr, (int32_t*)nullptr);
+    return (int)hipGetLastError();
+}
+
+int launch_draft_accept_states(const hyd_draft_accept_params& p, const int32_t* step_state_after, int32_t* state, hipStream_t s) {
+    const int grid = (p.rows + 63) / 64;
+    if (grid == 0) return 0;
+    hipLaunchKernelGGL(draft_accept_kernel<true>, dim3(grid), dim3(64), 0, s, p, step_state_after, state);
     return (int)hipGetLastError();
 }
 

@@ -324,6 +324,9 @@ int launch_suffix_causal(const SuffixArgs& a, int dtype, int D, hipStream_t s); 
 int launch_rope_append_multi(const hyd_rope_multi_params& p, hipStream_t s);          // rope_append.hip
 int launch_draft_lookup(const hyd_draft_lookup_params& p, hipStream_t s);             // draft_lookup.hip
 int launch_draft_accept(const hyd_draft_accept_params& p, hipStream_t s);             // draft_accept.hip
+int launch_draft_accept_states(const hyd_draft_accept_params& p, const int32_t* step_state_after, int32_t* state, hipStream_t s);
+int launch_dfa_forced(const hyd_dfa_forced_params& p, hipStream_t s);                 // draft_constrain.hip
+int launch_draft_constrain(const hyd_draft_constrain_params& p, hipStream_t s);       // draft_constrain.hip
 int launch_combine(const CombineArgs& a, hipStream_t s);
 size_t allreduce_block_bytes(int world, size_t max_bytes);
 int launch_allreduce(char* const* blocks, size_t block_bytes, const void* in, void* out, int64_t count, int dtype,

@@ -1335,9 +1335,15 @@ class HydragenLlamaForCausalLM(nn.Module):
         amounts; EOS ids and max_new_tokens are applied on the device (hyd_draft_accept) and the result is [B, max(lengths)] padded
         with pad_token_id, as on the stop path (an int eos_token_id is treated as a list of one).  return_draft_stats appends a
         speculative.DraftStats(steps, proposed, accepted) as the last return value.  Works with temperature, top_k / top_p /
-        min_p, return_logprobs, eos_token_id, pad_token_id, return_finish, num_return_sequences, seq_lens and shared_cache_op;
-        refused (before any launch): penalties and logit_bias, constraint, stop, token_overrides, top_logprobs, return_logits,
+        min_p, return_logprobs, eos_token_id, pad_token_id, return_finish, num_return_sequences, seq_lens, shared_cache_op and
+        constraint; refused (before any launch): penalties and logit_bias, stop, token_overrides, top_logprobs, return_logits,
         disable_hydragen / disable_attention / disable_hierarchy, fp8 or narrow unique caches, a model on the CPU.
+        With constraint= every step walks its drafts through the automaton (hyd_draft_constrain): a state that allows exactly
+        one token replaces the draft by that token -- accepted with probability 1, the masked sampler can draw nothing else --,
+        a draft the automaton rejects ends the row's proposal, each of the step's K + 1 draws is masked by the state behind the
+        tokens fed in front of it, and the accept (hyd_draft_accept_states) hands the row the state behind its last emitted
+        token.  draft = "constraint" (needs constraint=) proposes that forced chain and nothing else: no lookup launch.
+        DraftStats.forced then holds, per row, the proposed drafts that were forced.
         Sampling: top_k / top_p / min_p cut the UNSCALED softmax(logits) (the reference's top-p order; HF applies the
         temperature first), then a token is drawn from softmax(logits / temperature) over the kept tokens.  Returns the
         tokens [B, generated]; return_logits adds the per-step fp32 logits, return_logprobs the fp32 [B, generated]
@@ -1395,10 +1401,11 @@ class HydragenLlamaForCausalLM(nn.Module):
                 draft_tokens, draft, ngram, max_new_tokens,
                 {"repetition / presence / frequency penalties or logit_bias": sampling.penalties_active(
                     repetition_penalty, presence_penalty, frequency_penalty, logit_bias),
-                 "constraint": constraint is not None, "stop": stop is not None, "token_overrides": token_overrides is not None,
+                 "stop": stop is not None, "token_overrides": token_overrides is not None,
                  "top_logprobs": bool(top_logprobs), "return_logits": return_logits, "disable_hydragen": disable_hydragen,
                  "disable_attention": disable_attention, "disable_hierarchy": disable_hierarchy},
-                n_given=0 if input_ids is None else 1 if isinstance(input_ids, Tensor) else len(input_ids))
+                n_given=0 if input_ids is None else 1 if isinstance(input_ids, Tensor) else len(input_ids),
+                constrained=constraint is not None)
             if eos_token_id is not None and not isinstance(eos_token_id, (list, tuple, Tensor)):
                 eos_token_id = [eos_token_id]
         elif return_draft_stats:
@@ -1818,21 +1825,26 @@ class HydragenLlamaForCausalLM(nn.Module):
         return call.result(out[:, :width], past, stopping.Finish(length, reason, stop_index) if return_finish else None)
 
     # ---- speculative decoding (hydragen_amd/speculative.py) -----------------------------------------------------------------
-    def _check_draft(self, draft_tokens, draft, ngram, max_new_tokens, refused: dict, n_given: int = 0) -> dict:
-        """generate()'s draft arguments, checked before any launch -> dict(k, given, ngram).  n_given: the prompt levels given to
-        the call (each is a segment of the lookup's table, beside the generated tokens)."""
+    def _check_draft(self, draft_tokens, draft, ngram, max_new_tokens, refused: dict, n_given: int = 0, constrained: bool = False) -> dict:
+        """generate()'s draft arguments, checked before any launch -> dict(k, given, ngram, only_forced).  n_given: the prompt
+        levels given to the call (each is a segment of the lookup's table, beside the generated tokens); constrained: the call
+        has a constraint= (what draft="constraint" proposes from)."""
         k = speculative.check_draft_tokens(draft_tokens)
         for what, on in refused.items():
             if on:
                 raise NotImplementedError(f"draft_tokens cannot be combined with {what}: a speculative step draws and accepts "
                                           "several tokens per row in launches that do not carry it")
         given = None
+        only_forced = isinstance(draft, str) and draft == "constraint"
         if isinstance(draft, Tensor):
             if draft.ndim != 2 or draft.shape[1] != max_new_tokens or draft.is_floating_point() or draft.dtype == torch.bool:
                 raise ValueError(f"draft: an int tensor [batch, max_new_tokens = {max_new_tokens}], got {tuple(draft.shape)} {draft.dtype}")
             given = draft
+        elif only_forced:
+            if not constrained:
+                raise ValueError("draft='constraint' proposes the tokens the automaton forces: it needs constraint=")
         elif not isinstance(draft, str) or draft != "prompt_lookup":
-            raise ValueError(f"draft = {draft!r}: 'prompt_lookup' or an int tensor [batch, max_new_tokens]")
+            raise ValueError(f"draft = {draft!r}: 'prompt_lookup', 'constraint' or an int tensor [batch, max_new_tokens]")
         elif n_given + 1 > speculative.MAX_SEGMENTS:
             raise ValueError(f"draft='prompt_lookup' searches {n_given} given levels and the generated tokens: at most "
                              f"{speculative.MAX_SEGMENTS} segments (hyd_draft_lookup)")
@@ -1841,10 +1853,14 @@ class HydragenLlamaForCausalLM(nn.Module):
         if attn.kv_cache.fp8 or attn.kv_cache.narrow or attn.head_dim not in (64, 128, 256):
             raise NotImplementedError("draft_tokens with fp8 unique caches or a head dim other than 64 / 128 / 256: the multi-token "
                                       "preamble and the causal-tail suffix pass take 16-bit caches of those head dims only")
+        if constrained and not self.lm_head.weight.is_cuda:
+            raise NotImplementedError("draft_tokens with constraint= is not implemented for a model on the CPU: the drafts are walked "
+                                      "through the automaton and accepted with their states by HIP kernels (speculative."
+                                      "constrain_drafts_reference / accept_states_reference state the rules in torch)")
         if not self.lm_head.weight.is_cuda:
             raise ValueError("draft_tokens: drafts are proposed, verified and accepted by HIP kernels, the model must be on the GPU "
                              "(speculative.prompt_lookup_reference / accept_reference state the rules in torch)")
-        return dict(k=k, given=given, ngram=ngram)
+        return dict(k=k, given=given, ngram=ngram, only_forced=only_forced)
 
     def _decode_steps_draft(self, call: _DecodeCall, first, start, spec, return_finish):
         """The decode loop with draft_tokens = K: per step the drafts (hyd_draft_lookup, or a gather from the given ones), ONE
@@ -1866,9 +1882,20 @@ class HydragenLlamaForCausalLM(nn.Module):
         live = torch.zeros((mx,), dtype=torch.int32, device=dev)
         eos = spec.eos
 
-        def accept(fed, sampled, lp, slot):
+        def accept(fed, sampled, lp, slot, states=None):
             return speculative.draft_accept(fed, sampled, out, length, reason, stop_index, live[slot : slot + 1], start_pos, shared_len,
-                                            eos, spec.pad, mx, retire, lp, out_lp if lp is not None else None)
+                                            eos, spec.pad, mx, retire, lp, out_lp if lp is not None else None, states)
+
+        # constraint=: the rows' automaton states (already advanced by the first draw) and, per step, the state behind every fed
+        # token -- the sampler's state array over the step's B * T logits rows, advanced in place, then read by the accept
+        dfa, state = call.sample.get("constraint") or (None, None)
+        sample = call.sample
+        if dfa is not None:
+            step_state = torch.empty((B, T), dtype=torch.int32, device=dev)
+            n_forced = torch.empty((B,), dtype=torch.int32, device=dev)
+            forced = torch.zeros((B,), dtype=torch.int64, device=dev)
+            sample = dict(call.sample, constraint=(dfa, step_state.view(-1)))
+            dfa.forced  # (made once per automaton, before the loop)
 
         # the first token, drawn from the prefill logits, enters like a step of one token
         first = first.reshape(B, 1).long()
@@ -1895,15 +1922,29 @@ class HydragenLlamaForCausalLM(nn.Module):
             # a draft counts as proposed when accepting it can add a token: the one for output position p lets the draw for p + 1
             # out, so a row with `length` tokens has room for max_new_tokens - 1 - length of them (0 for a finished row)
             room = (mx - 1 - length).clamp_(min=0) * (reason == 0)
+            n_prop = None
             if given is not None:
                 fed[:, 1:] = given.gather(1, (length.long()[:, None] + cols).clamp_(max=mx - 1))
-                proposed += room.clamp(max=K)
+                if dfa is not None:
+                    n_prop = torch.full((B,), K, dtype=torch.int32, device=dev)
+            elif d["only_forced"]:
+                n_prop = torch.zeros((B,), dtype=torch.int32, device=dev)
             else:
                 _, n_prop = speculative.draft_lookup(segments, B, K, d["ngram"], out=fed[:, 1:])
-                proposed += torch.minimum(n_prop, room)
+            compare, states = fed, None
+            if dfa is not None:
+                # forced states replace drafts, a draft the automaton rejects ends the row's proposal (hyd_draft_constrain)
+                speculative.constrain_drafts(dfa, state, fed, n_prop, d["only_forced"], step_state, n_forced)
+                forced += torch.minimum(n_forced, room)
+                states = (step_state, state)
+                if d["only_forced"]:
+                    # behind the end of the forced chain the columns hold whatever an earlier step left and their draws are
+                    # unconstrained: the accept compares them with a value no token equals, so none of those draws is kept
+                    compare = torch.where(offs <= n_prop[:, None], fed, torch.full_like(fed, -1))
+            proposed += room.clamp(max=K) if n_prop is None else torch.minimum(n_prop, room)
             logits = self(input_ids=fed, position_ids=pos[:, None] + offs, use_graph=call.graphed, full_logits=True, raw_logits=call.raw)
-            tok, lp = draw_tokens(call.route, logits.reshape(B * T, -1), **call.sample)
-            feed, pos, acc = accept(fed, tok.reshape(B, T), lp.reshape(B, T).float() if want_lp else None, step)
+            tok, lp = draw_tokens(call.route, logits.reshape(B * T, -1), **sample)
+            feed, pos, acc = accept(compare, tok.reshape(B, T), lp.reshape(B, T).float() if want_lp else None, step, states)
             accepted += acc
             steps += 1
             if pending is not None:
@@ -1925,5 +1966,5 @@ class HydragenLlamaForCausalLM(nn.Module):
             call.logprobs = [out_lp]
         ret = call.result(out[:, :width], past, stopping.Finish(length, reason, stop_index) if return_finish else None)
         if d["stats"]:
-            ret = (ret if isinstance(ret, tuple) else (ret,)) + (speculative.DraftStats(steps, proposed, accepted),)
+            ret = (ret if isinstance(ret, tuple) else (ret,)) + (speculative.DraftStats(steps, proposed, accepted, forced if dfa is not None else None),)
         return ret

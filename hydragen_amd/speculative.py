@@ -19,10 +19,14 @@ one prompt copy from their shared prompt, so the tokens that followed the latest
 proposed -- no draft model.  Levels kept from EARLIER generate() calls (shared_cache_op="extend") are not searched: their token
 ids are not given to the call that decodes.
 
-This module holds the definitions in torch (`prompt_lookup_reference`, `accept_reference`,
-`assembled_causal_tail_attention`) and the Python faces of the kernels (`draft_lookup`, `draft_accept`; the multi-token RoPE +
-append is fused_decode.rope_append_multi, the causal-tail attention flash.flash_attention_seqlen / attention.hydragen_attention
-with causal_tail=True)."""
+Under a token automaton (generate(constraint=)) the drafts are first walked through it: a state that allows exactly one token forces
+that token as the draft -- accepted with probability 1, the masked sampler can draw nothing else -- and `draft="constraint"` proposes
+nothing but those (`constrain_drafts`, the states in `draft_accept`).
+
+This module holds the definitions in torch (`prompt_lookup_reference`, `accept_reference`, `constrain_drafts_reference`,
+`accept_states_reference`, `assembled_causal_tail_attention`) and the Python faces of the kernels (`draft_lookup`, `draft_accept`,
+`constrain_drafts`; the multi-token RoPE + append is fused_decode.rope_append_multi, the causal-tail attention
+flash.flash_attention_seqlen / attention.hydragen_attention with causal_tail=True)."""
 
 from __future__ import annotations
 
@@ -33,17 +37,27 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from .sampling import DFA_FREE, DFA_REJECT
 
 MAX_DRAFTS = 7  # K: T = K + 1 <= 8 tokens per row and step
 MAX_SEGMENTS = _lib.DRAFT_MAX_SEGMENTS  # of a lookup's table: the levels given to the call, the rows' prompts, the generated tokens
 
 
-class DraftStats(NamedTuple):
-    """Statistics of a speculative generation: decode steps run, and per row (int64 [B]) the drafts proposed to running rows and
-    the drafts that became output."""
+class _DraftStats(NamedTuple):
     steps: int
     proposed: Tensor
     accepted: Tensor
+
+
+class DraftStats(_DraftStats):
+    """Statistics of a speculative generation: decode steps run, and per row (int64 [B]) the drafts proposed to running rows and
+    the drafts that became output -- a tuple of these three.  `forced` (an attribute, not a field: code that unpacks the three
+    keeps working): per row the proposed drafts a forced automaton state wrote, None without constraint=."""
+
+    def __new__(cls, steps, proposed, accepted, forced: Optional[Tensor] = None):
+        self = super().__new__(cls, steps, proposed, accepted)
+        self.forced = forced
+        return self
 
 
 class Segment(NamedTuple):
@@ -217,11 +231,18 @@ def accept_reference(fed: Tensor, sampled: Tensor, out: Tensor, length: Tensor, 
 
 def draft_accept(fed: Tensor, sampled: Tensor, out: Tensor, length: Tensor, reason: Tensor, stop_index: Tensor, live: Tensor,
                  start_pos: Tensor, shared_len: Optional[Tensor], eos: Sequence[int], pad: int, max_new_tokens: int,
-                 retire: bool = True, logprobs: Optional[Tensor] = None, out_logprobs: Optional[Tensor] = None):
+                 retire: bool = True, logprobs: Optional[Tensor] = None, out_logprobs: Optional[Tensor] = None,
+                 states: Optional[tuple] = None):
     """hyd_draft_accept, one launch -> (feed, next_pos int64 [rows], accepted int32 [rows]); the rows still running are ADDED to
     live (int32 [1], a slot the caller zeroed).  The state tensors are those of new_state; CPU tensors take accept_reference.
-    Nothing synchronises."""
+    states = (step_state_after int32 [rows, T], state int32 [rows]): hyd_draft_accept_states -- a row that emits e >= 1 tokens
+    also gets state[b] = step_state_after[b, e - 1] (accept_states_reference).  Nothing synchronises."""
     rows, T = fed.shape
+    if states is not None:
+        after, st = states
+        if (after.dtype != torch.int32 or after.shape != (rows, T) or not after.is_contiguous() or after.device != fed.device
+                or st.dtype != torch.int32 or st.shape != (rows,) or not st.is_contiguous() or st.device != fed.device):
+            raise ValueError(f"states must be contiguous int32 ([{rows}, {T}], [{rows}]) on {fed.device}")
     if fed.dtype != torch.int64 or sampled.dtype != torch.int64 or sampled.shape != fed.shape:
         raise ValueError(f"fed / sampled must be int64 [rows, T], got {tuple(fed.shape)} {fed.dtype} / {tuple(sampled.shape)} {sampled.dtype}")
     if not 1 <= T <= MAX_DRAFTS + 1:
@@ -243,8 +264,9 @@ def draft_accept(fed: Tensor, sampled: Tensor, out: Tensor, length: Tensor, reas
                                  or out_logprobs.shape != out.shape or out_logprobs.stride() != out.stride()):
         raise ValueError("logprobs must be float32 [rows, T] and out_logprobs float32 with out's shape and strides")
     if dev.type != "cuda":
-        feed, pos, acc, n = accept_reference(fed, sampled, out, length, reason, stop_index, start_pos, shared_len, eos, pad,
-                                             max_new_tokens, retire, logprobs, out_logprobs)
+        rest = (out, length, reason, stop_index, start_pos, shared_len, eos, pad, max_new_tokens, retire, logprobs, out_logprobs)
+        feed, pos, acc, n = (accept_reference(fed, sampled, *rest) if states is None else
+                             accept_states_reference(fed, sampled, *states, *rest))
         live += n
         return feed, pos, acc
     fed, sampled = fed.contiguous(), sampled.contiguous()
@@ -264,8 +286,124 @@ def draft_accept(fed: Tensor, sampled: Tensor, out: Tensor, length: Tensor, reas
     for i, e in enumerate(eos):
         p.eos[i] = e
     p.rows, p.T, p.n_eos, p.max_new_tokens, p.retire = rows, T, len(eos), max_new_tokens, int(bool(retire))
-    _lib.check(_lib.load().hyd_draft_accept(C.byref(p), torch.cuda.current_stream().cuda_stream))
+    if states is None:
+        _lib.check(_lib.load().hyd_draft_accept(C.byref(p), torch.cuda.current_stream().cuda_stream))
+    else:
+        _lib.check(_lib.load().hyd_draft_accept_states(C.byref(p), states[0].data_ptr(), states[1].data_ptr(), torch.cuda.current_stream().cuda_stream))
     return feed, next_pos, accepted
+
+
+# ---- drafts under a token automaton (constraint.TokenDFA) ---------------------------------------------------------------------
+# A state that allows exactly one token FORCES it: a draft of that token is accepted with probability 1, because the masked sampler
+# can draw nothing else (jump-forward decoding).  Per step: the drafts go into fed[:, 1:], constrain_drafts walks them through the
+# automaton -- forced states replace drafts, a rejected draft ends the row's proposal -- and gives step_state [B, T], the state
+# from which the draw behind each fed token is taken; the sampler draws the B * T logits rows with step_state flattened as its
+# state array and advances it in place; accept (states=) then hands every row the state behind its last emitted token.
+def constrain_drafts_reference(dfa, state: Tensor, fed: Tensor, n_proposed: Optional[Tensor] = None, only_forced: bool = False):
+    """The rule hyd_draft_constrain implements, row by row on CPU tensors -> (step_state int32 [B, T], n_forced int32 [B]); fed
+    (int64 [B, T], column 0 the last emitted token, whose effect is already in state) and n_proposed (int32 [B] or None) are
+    updated in place.  Row b, s = state[b], step_state[b, 0] = s; for j = 0 .. K - 1:
+      1. s is a state and dfa.forced[s] >= 0: fed[b, j + 1] = forced[s]; n_forced counts it; n_proposed[b] = max(., j + 1);
+      2. otherwise, only_forced: the chain ends -- n_proposed[b] = min(., j), the remaining drafts keep what they hold, the
+         remaining step states are -1;
+      3. s is a state: t = fed[b, j + 1], e = next[s, t] (REJECT for t outside [0, n)).  REJECT: the draft can never be drawn --
+         n_proposed[b] = min(., j), every later step state is -1; FREE: s = -2; e in [0, S): s = e; anything else: s = -1;
+      4. s is no state: the row is unconstrained, s and the draft stay;
+      5. step_state[b, j + 1] = s."""
+    B, T = fed.shape
+    S, n = dfa.next.shape
+    nxt, forced = dfa.next.cpu(), dfa.forced.cpu()
+    step_state = torch.empty((B, T), dtype=torch.int32)
+    n_forced = torch.zeros((B,), dtype=torch.int32)
+    for b in range(B):
+        s = int(state[b])
+        step_state[b, 0] = s
+        np_ = int(n_proposed[b]) if n_proposed is not None else 0
+        ended = False
+        for j in range(T - 1):
+            if not ended:
+                inside = 0 <= s < S
+                t = int(forced[s]) if inside else -1
+                if t >= 0:
+                    fed[b, j + 1] = t
+                    n_forced[b] += 1
+                    np_ = max(np_, j + 1)
+                elif only_forced:
+                    ended = True
+                else:
+                    t = int(fed[b, j + 1])
+                if not ended and inside:
+                    e = int(nxt[s, t]) if 0 <= t < n else DFA_REJECT
+                    if e == DFA_REJECT:
+                        ended = True
+                    else:
+                        s = -2 if e == DFA_FREE else e if 0 <= e < S else -1
+                if ended:
+                    np_ = min(np_, j)
+            step_state[b, j + 1] = -1 if ended else s
+        if n_proposed is not None:
+            n_proposed[b] = np_
+    return step_state, n_forced
+
+
+def constrain_drafts(dfa, state: Tensor, fed: Tensor, n_proposed: Optional[Tensor] = None, only_forced: bool = False,
+                     step_state: Optional[Tensor] = None, n_forced: Optional[Tensor] = None):
+    """hyd_draft_constrain, one launch, no host synchronisation -> (step_state int32 [B, T], n_forced int32 [B]); CPU tensors take
+    constrain_drafts_reference.  fed int64 [B, T] with a unit last stride (a row stride wider than T is honoured) and n_proposed
+    are updated in place; step_state / n_forced: buffers to write (a generation allocates them once)."""
+    B, T = fed.shape
+    if fed.dtype != torch.int64 or fed.ndim != 2 or not 2 <= T <= MAX_DRAFTS + 1:
+        raise ValueError(f"fed must be int64 [B, T] with T = K + 1 in 2 .. {MAX_DRAFTS + 1}, got {tuple(fed.shape)} {fed.dtype}")
+    dev = fed.device
+    for name, x in (("state", state), ("n_proposed", n_proposed)):
+        if x is not None and (x.dtype != torch.int32 or x.shape != (B,) or not x.is_contiguous() or x.device != dev):
+            raise ValueError(f"{name} must be a contiguous int32 [{B}] on {dev}")
+    if dev.type != "cuda":
+        ss, nf = constrain_drafts_reference(dfa, state, fed, n_proposed, only_forced)
+        if step_state is not None:
+            step_state.copy_(ss)
+            ss = step_state
+        if n_forced is not None:
+            n_forced.copy_(nf)
+            nf = n_forced
+        return ss, nf
+    if fed.stride(1) != 1 or (B > 1 and fed.stride(0) < T):
+        raise ValueError("fed must have a unit last stride and rows that do not overlap")
+    if dfa.next.device != dev:
+        raise ValueError(f"the automaton is on {dfa.next.device}, fed on {dev}")
+    if step_state is None:
+        step_state = torch.empty((B, T), dtype=torch.int32, device=dev)
+    if n_forced is None:
+        n_forced = torch.empty((B,), dtype=torch.int32, device=dev)
+    if step_state.shape != (B, T) or step_state.dtype != torch.int32 or not step_state.is_contiguous() or step_state.device != dev:
+        raise ValueError(f"step_state must be a contiguous int32 [{B}, {T}] on {dev}")
+    if n_forced.shape != (B,) or n_forced.dtype != torch.int32 or not n_forced.is_contiguous() or n_forced.device != dev:
+        raise ValueError(f"n_forced must be a contiguous int32 [{B}] on {dev}")
+    forced = dfa.forced
+    p = _lib.DraftConstrainParams()
+    p.state, p.fed, p.forced, p.next = state.data_ptr(), fed.data_ptr(), forced.data_ptr(), dfa.next.data_ptr()
+    if n_proposed is not None:
+        p.n_proposed = n_proposed.data_ptr()
+    p.step_state, p.n_forced = step_state.data_ptr(), n_forced.data_ptr()
+    p.fed_stride, p.next_stride = (fed.stride(0) if B > 1 else max(T, fed.stride(0))), dfa.next.stride(0) if dfa.next.shape[0] > 1 else dfa.next.shape[1]
+    p.B, p.K, p.n_states, p.n, p.only_forced = B, T - 1, dfa.next.shape[0], dfa.next.shape[1], int(bool(only_forced))
+    _lib.check(_lib.load().hyd_draft_constrain(C.byref(p), torch.cuda.current_stream().cuda_stream))
+    return step_state, n_forced
+
+
+def accept_states_reference(fed: Tensor, sampled: Tensor, step_state_after: Tensor, state: Tensor, out: Tensor, length: Tensor,
+                            reason: Tensor, stop_index: Tensor, *args, **kw):
+    """The rule hyd_draft_accept_states implements: accept_reference (same arguments behind `state`, same return value), and a
+    row that emits e >= 1 tokens in this call also gets state[b] = step_state_after[b, e - 1] -- step_state_after int32
+    [rows, T] is the step's state array after the sampler advanced it: entry (b, i) is the state behind sampled[b, i].  A
+    finished row, or one that emits nothing, keeps its state."""
+    before = length.clone()
+    ret = accept_reference(fed, sampled, out, length, reason, stop_index, *args, **kw)
+    for b in range(fed.shape[0]):
+        e = int(length[b]) - int(before[b])
+        if e >= 1:
+            state[b] = step_state_after[b, e - 1]
+    return ret
 
 
 # ---- the multi-token attention, assembled from existing operators ------------------------------------------------------------

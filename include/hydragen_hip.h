@@ -676,6 +676,65 @@ typedef struct hyd_draft_accept_params {
 
 HYD_API int hyd_draft_accept(const hyd_draft_accept_params* p, void* stream);
 
+/* Speculative decoding under a token automaton (hyd_token_dfa's tables): drafts a state FORCES are accepted with probability 1,
+ * because the masked sampler can draw nothing else.  Three launches around the step, none synchronises with the host.
+ *
+ * hyd_dfa_forced_tokens, once per automaton: state s is FORCED when exactly one bit at a position below n is set in row s of
+ * `allowed`; forced[s] = that token, else -1 (no bit, or two and more).  Bits at positions >= n are ignored and words past
+ * ceil(n / 32) of a row are not read.  Only the bitmap is read (one wave per state, 16-byte loads where allowed is 16-byte aligned
+ * and allowed_stride a multiple of 4 words); no workspace.
+ * HYD_ERR_BAD_ARG: null or misaligned (4 bytes) pointers, n_states <= 0, n <= 0, allowed_stride < ceil(n / 32). */
+typedef struct hyd_dfa_forced_params {
+    const uint32_t* allowed;   /* [n_states, allowed_stride] words                                           */
+    int32_t* forced;           /* out [n_states]                                                             */
+    int64_t allowed_stride;    /* words                                                                      */
+    int32_t n_states, n;
+} hyd_dfa_forced_params;
+
+HYD_API int hyd_dfa_forced_tokens(const hyd_dfa_forced_params* p, void* stream);
+
+/* hyd_draft_constrain: after the drafts of a step are in fed[b, 1 .. K] (fed[b, 0] is the row's last emitted token, whose effect
+ * is already in state[b]) and before the forward pass.  Row b, with s = state[b] and step_state[b, 0] = s, for j = 0 .. K - 1:
+ *   1. s in [0, n_states) and forced[s] >= 0: fed[b, j + 1] = forced[s], n_forced[b] counts it, n_proposed[b] = max(., j + 1);
+ *   2. otherwise, with only_forced != 0, the chain ends: n_proposed[b] = min(., j), the remaining drafts keep what they hold and
+ *      step_state[b, j + 1 ..] = -1;
+ *   3. s in [0, n_states): with t = fed[b, j + 1], e = next[s, t] (HYD_DFA_REJECT for t outside [0, n)).  e == HYD_DFA_REJECT:
+ *      the draft can never be drawn -- n_proposed[b] = min(., j) and step_state[b, j + 1 ..] = -1, their draws are never kept;
+ *      e == HYD_DFA_FREE: s = -2; e in [0, n_states): s = e; any other value: s = -1 (as in hyd_sample_tokens_constrained);
+ *   4. s outside [0, n_states): the row is unconstrained, s and the draft stay;
+ *   5. step_state[b, j + 1] = s.
+ * step_state, flattened to [B * T], is the state array of the step's hyd_sample_tokens_constrained call over its B * T logits
+ * rows (advance != 0): logits row (b, i) predicts the token behind fed[b, i] and is masked by step_state[b, i].  A draw behind a
+ * column at or past an ended chain is unconstrained: the caller must not keep it (a draft rejected in 3. can never equal the
+ * draw in front of it; behind 2. the caller compares columns past n_proposed[b] with a value no token equals).
+ * state is read only; n_proposed may be NULL (nothing is counted).  One row per lane; no read uses a state outside
+ * [0, n_states) or a token outside [0, n).
+ * HYD_ERR_BAD_ARG: null or misaligned pointers, B < 0, K outside [1, 7], n_states <= 0, n <= 0, next_stride < n,
+ * fed_stride < K + 1.  B == 0 succeeds without a launch. */
+typedef struct hyd_draft_constrain_params {
+    const int32_t* state;      /* [B]                                                                        */
+    int64_t* fed;              /* [B, fed_stride]: columns 1 .. K are read and, where a state is forced, written */
+    int32_t* n_proposed;       /* [B] in / out, or NULL                                                      */
+    const int32_t* forced;     /* [n_states] hyd_dfa_forced_tokens' output                                   */
+    const int32_t* next;       /* [n_states, next_stride]                                                    */
+    int32_t* step_state;       /* out [B, K + 1]                                                             */
+    int32_t* n_forced;         /* out [B] drafts of this step a forced state wrote                           */
+    int64_t fed_stride;        /* elements, >= K + 1                                                         */
+    int64_t next_stride;       /* elements, >= n                                                             */
+    int32_t B, K, n_states, n;
+    int32_t only_forced;       /* != 0: the drafts are the forced chain alone                                */
+    int32_t reserved;
+} hyd_draft_constrain_params;
+
+HYD_API int hyd_draft_constrain(const hyd_draft_constrain_params* p, void* stream);
+
+/* hyd_draft_accept_states: hyd_draft_accept, bit for bit, and for a row that emits e >= 1 tokens also
+ * state[b] = step_state_after[b, e - 1] -- step_state_after [rows, T] is the step's state array AFTER the constrained sampler
+ * advanced it, so its entry (b, i) is the state behind sampled[b, i].  A finished row, or one that emits nothing, keeps its
+ * state.  With step_state_after and state both NULL the call IS hyd_draft_accept; one of them NULL, or misaligned (4 bytes), is
+ * HYD_ERR_BAD_ARG, as is everything hyd_draft_accept refuses. */
+HYD_API int hyd_draft_accept_states(const hyd_draft_accept_params* p, const int32_t* step_state_after, int32_t* state, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * All-reduce(sum) of the tensor-parallel block output (hydragen/tp.py:83-87 after down_proj, :108-112 after
  * o_proj; the reference calls torch.distributed / NCCL there) as a two-shot direct exchange over
