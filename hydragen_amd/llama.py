@@ -23,13 +23,13 @@ from typing import List, Optional, Union
 import torch
 from torch import Tensor, nn
 
-from . import layer_ops, placement, sampling, scoring, speculative, stopping
+from . import generation, layer_ops, placement, sampling, scoring, speculative
 from .attention import hydragen_attention
 from . import flash as _flash
 from .flash import flash_attention, flash_attention_seqlen, padded_head_dim
 from . import kv_quant as _kv_quant
 from .kv_quant import FP8_DTYPE, dequantize_kv, quantize_kv, scale_constant
-from .tp import all_reduce_sum, check_collectives
+from .tp import all_reduce_sum
 
 
 @dataclass
@@ -805,85 +805,6 @@ class SharedCacheOp:
     PRESERVE = "preserve"
 
 
-def draw_tokens(route: sampling.SampleRoute, logits, temperature, num_samples=1, top_p=None, top_k=None, min_p=None,
-                return_logprobs=False, penalties=None, constraint=None):
-    """Run one draw along `route` (sampling.sample_route's table): (tokens [B, num_samples], their fp32 log-probs
-    [B, num_samples] or, for a draw in torch that needs none, None).  The other arguments are sample_from_logits'."""
-    x, n = logits, num_samples
-    if route.torch_penalties:  # the definition, float64 through [B, V] tables
-        x = penalties.apply(x, n).float()
-    if route.torch_mask:
-        x, n = sampling.constrain_logits(x.repeat_interleave(n, 0), *constraint), 1
-    if route.draw in (sampling.PLAIN, sampling.TORCH):
-        src = x
-        # (a top_p of 1.0 is no cut to the kernels, but in torch it still passes through apply_top_p, as in the reference)
-        if route.torch_cuts or top_p is not None:
-            x = sampling.filter_logits(x, top_k, top_p, min_p) if top_k or min_p else sampling.apply_top_p(x, top_p)
-        if route.draw == sampling.PLAIN:
-            # argmax(logits / T + Gumbel noise) draws exactly from softmax(logits / T) -- what the softmax + torch.multinomial
-            # chain below draws, in one pass over the logits instead of ~12 launches over [B, vocab]
-            tok = layer_ops.sample_tokens(x, temperature)
-        elif temperature == 0:
-            assert x.ndim == 2
-            tok = x.argmax(dim=-1, keepdim=True).repeat_interleave(n, dim=-1)
-        else:
-            tok = torch.multinomial(nn.functional.softmax(x / temperature, dim=-1), num_samples=n, replacement=True)
-        lp = torch.log_softmax(src.float(), dim=-1).gather(-1, tok) if return_logprobs or route.torch_mask else None
-    else:
-        # one launch (CPU rows: its definition in torch): mask, penalties, cuts, draw, log-prob, the append and the state update
-        tok, lp = layer_ops.sample_tokens(
-            x, temperature, top_k=top_k, top_p=top_p, min_p=min_p, return_logprobs=True,
-            penalties=None if route.draw == sampling.FILTERED else penalties,
-            constraint=(*constraint, True) if route.draw == sampling.CONSTRAINED else None)
-    if route.torch_mask:  # a row drew something iff its log-prob is a number
-        dfa, state = constraint
-        state.copy_(sampling.advance_state(dfa, state, tok, ~torch.isnan(lp.reshape(-1))))
-    if route.torch_penalties and penalties.append and num_samples == 1:
-        penalties.push(tok)
-    return tok.reshape(-1, num_samples), None if lp is None else lp.reshape(-1, num_samples)
-
-
-@dataclass
-class _DecodeCall:
-    """What the decode half of one generate() call shares between _decode and its two step loops.  generate() sets the
-    fields down to `top`; _decode sets `route`, `pen`, `raw` and `graphed` before the steps; _decode, _step and keep() fill
-    the lists."""
-    sample: dict                               # sample_from_logits' arguments but the logits and num_samples
-    fan: int
-    max_new_tokens: int
-    top_n: int = 0
-    state: Optional[Tensor] = None             # the automaton states, if they are returned
-    logits: Optional[list] = None              # kept per step, if they are returned: [B, V] each
-    logprobs: Optional[list] = None            # [B, 1] each
-    top: Optional[tuple] = None                # (ids, log-probs) lists of [B, 1, top_n] each
-    route: Optional[sampling.SampleRoute] = None  # of the steps' draws (the first draw, which may fan out, has its own)
-    pen: Optional[layer_ops.Penalties] = None  # the penalties, if they keep a list of generated tokens (a bias alone does not)
-    raw: bool = False                          # the steps' logits stay in the lm_head's dtype
-    graphed: bool = False
-    draft: Optional[dict] = None               # speculative decoding: k, given drafts or None, ngram, the call's segments, stats
-
-    def keep(self, logits, tok, lp):
-        """Record a step's returned log-probs and alternatives."""
-        if self.logprobs is not None:
-            self.logprobs.append(lp)
-        if self.top is not None:  # the same logits the sampler read; the sampled token's log-prob stays the sampler's
-            for kept, t in zip(self.top, layer_ops.token_logprobs(logits, tok[:, 0], self.top_n)[2:]):
-                kept.append(t[:, None])
-
-    def result(self, tokens, past=None, finish=None):
-        """generate()'s (tokens[, logits][, logprobs][, top_ids, top_logprobs][, finish][, state]), or the tokens alone.
-        past [B, width] bool (the stop path): what was kept is trimmed to the tokens' width and blanked at or past a row's
-        length."""
-        width = None if past is None else tokens.shape[1]
-        ret = (tokens,) if self.logits is None else (tokens, self.logits[:width])
-        for kept, blank in zip((self.logprobs,) + (self.top or ()), (0.0, -1, float("-inf"))):
-            if kept is not None:
-                t = torch.cat(kept, dim=1)
-                ret += (t if past is None else t[:, :width].masked_fill(past if t.ndim == 2 else past[:, :, None], blank),)
-        ret += tuple(x for x in (finish, self.state) if x is not None)
-        return ret if len(ret) > 1 else tokens
-
-
 class HydragenLlamaForCausalLM(nn.Module):
     """llama.py:875-1422."""
 
@@ -1102,7 +1023,7 @@ class HydragenLlamaForCausalLM(nn.Module):
         is sampling.sample_route's table; generate() decides it once for its first draw and once for its steps."""
         args = (temperature, num_samples, top_p, top_k, min_p, return_logprobs, penalties, constraint)
         route = self.sample_route(logits.is_cuda, logits.ndim == 2 and logits.stride(-1) == 1, *args)
-        tok, lp = draw_tokens(route, logits, *args)
+        tok, lp = generation.draw_tokens(route, logits, *args)
         return (tok, lp) if return_logprobs else tok
 
     def _positions(self, input_ids):
@@ -1272,6 +1193,21 @@ class HydragenLlamaForCausalLM(nn.Module):
         self.set_mode(AttentionMode.UNIQUE_PREFILL)
         return self(input_ids=input_ids, position_ids=self._positions(input_ids), seq_lens=seq_lens)
 
+    # ---- switches of the decode loops (hydragen_amd/generation.py): class attributes, set on a model by tests and tools ------------
+    schedule_longest_first = True  # (tests switch it off to compare: only the schedule may depend on it, never a token)
+    # top-k / top-p / min-p in the sampling kernel (hyd_sample_tokens_filtered); False: torch cuts + hyd_sample_tokens, the
+    # path before the kernel existed (tests switch it off to compare)
+    fused_sampling_filters = True
+    # penalties in the sampling kernel (hyd_sample_tokens_penalized); False: sampling.penalize_logits in torch, then the paths
+    # above (tests and tools/sampler_bench.py switch it off to compare)
+    fused_sampling_penalties = True
+    # hyd_stop_update path: every this many decode steps the host starts a non-blocking copy of the running-row count of the
+    # step just enqueued and looks at it one step later (tests shrink it)
+    stop_poll_steps = 8
+    # None: finished rows are retired from the unique K/V stream whenever the fused decode preamble is in use; False: never
+    # (tools/stop_bench.py and the tests compare the two: only the step time may depend on it, never a token)
+    stop_retire: Optional[bool] = None
+
     # ---- generation -----------------------------------------------------------------------------------
     # Contract (README.md:183-289 of the reference; llama.py:1156-1396): prompts form a hierarchy, outermost level
     # first.  With num_return_sequences > 1 every given level is shared and the completions hang off the last one;
@@ -1324,33 +1260,13 @@ class HydragenLlamaForCausalLM(nn.Module):
                  stop=None, pad_token_id: Optional[int] = None, include_stop: bool = False, return_finish: bool = False,
                  constraint=None, constraint_state: Optional[Tensor] = None, return_constraint_state: bool = False,
                  draft_tokens: Optional[int] = None, draft="prompt_lookup", ngram=(1, 3), return_draft_stats: bool = False):
-        """Speculative decoding (hydragen_amd/speculative.py states the scheme and why it is lossless): draft_tokens = K in 1..7
-        makes every decode step feed each row its last token and K drafts, verify them in ONE forward pass over [B, K + 1] (the
-        multi-token RoPE + append, the causal-tail attention) and keep the draws up to the first wrong draft; None or 0 runs
-        exactly the launches generate() runs without it.  draft = "prompt_lookup": drafts are the tokens that followed the latest
-        earlier occurrence of the row's last n-gram (ngram = (min, max) lengths, longest first) in the prompt levels GIVEN TO THIS
-        CALL on the row's path, its own prompt and its generated tokens (hyd_draft_lookup; levels kept by earlier calls with
-        shared_cache_op="extend" are not searched -- their ids are not given to this call); or an int tensor [B, max_new_tokens]
-        whose column p is the draft for output position p (tests, benchmarks; no lookup launch).  Rows advance by different
-        amounts; EOS ids and max_new_tokens are applied on the device (hyd_draft_accept) and the result is [B, max(lengths)] padded
-        with pad_token_id, as on the stop path (an int eos_token_id is treated as a list of one).  return_draft_stats appends a
-        speculative.DraftStats(steps, proposed, accepted) as the last return value.  Works with temperature, top_k / top_p /
-        min_p, return_logprobs, eos_token_id, pad_token_id, return_finish, num_return_sequences, seq_lens, shared_cache_op and
-        constraint; refused (before any launch): penalties and logit_bias, stop, token_overrides, top_logprobs, return_logits,
-        disable_hydragen / disable_attention / disable_hierarchy, fp8 or narrow unique caches, a model on the CPU.
-        With constraint= every step walks its drafts through the automaton (hyd_draft_constrain): a state that allows exactly
-        one token replaces the draft by that token -- accepted with probability 1, the masked sampler can draw nothing else --,
-        a draft the automaton rejects ends the row's proposal, each of the step's K + 1 draws is masked by the state behind the
-        tokens fed in front of it, and the accept (hyd_draft_accept_states) hands the row the state behind its last emitted
-        token.  draft = "constraint" (needs constraint=) proposes that forced chain and nothing else: no lookup launch.
-        DraftStats.forced then holds, per row, the proposed drafts that were forced.
+        """Prompts and caches: input_ids is one level or a list of levels, outermost first, seq_lens their lengths (right padding;
+        the contract above _prompt_levels); starting_logits instead of input_ids continues from levels kept by an earlier call.
+        shared_cache_op: "wipe" / "preserve" / "extend".  disable_hydragen / disable_hierarchy / disable_attention are the
+        reference's baselines.  The decode half -- argument checks, first draw, step loops -- is hydragen_amd/generation.py.
+
         Sampling: top_k / top_p / min_p cut the UNSCALED softmax(logits) (the reference's top-p order; HF applies the
-        temperature first), then a token is drawn from softmax(logits / temperature) over the kept tokens.  Returns the
-        tokens [B, generated]; return_logits adds the per-step fp32 logits, return_logprobs the fp32 [B, generated]
-        log softmax(logits) of every returned token (unscaled, unfiltered): (out, logits, logprobs) in that order.
-        top_logprobs = N > 0 (needs return_logprobs) also returns, for every returned token, the N best alternatives of that
-        step's distribution (hyd_token_logprobs, hydragen_amd/scoring.py): (..., top_ids [B, generated, N] int64,
-        top_logprobs [B, generated, N] f32) after the other return values.
+        temperature first), then a token is drawn from softmax(logits / temperature) over the kept tokens.
         Penalties (hydragen_amd/sampling.py states the rules; None = off): repetition_penalty r > 0 (HF / vLLM: l / r if l > 0
         else l * r for every token of the row's context -- all shared levels on its path, levels kept by earlier calls included,
         and its own prompt -- or of its generated tokens), frequency_penalty / presence_penalty (OpenAI / vLLM: generated
@@ -1359,21 +1275,6 @@ class HydragenLlamaForCausalLM(nn.Module):
         (log softmax of the penalised, unscaled, unfiltered logits: the distribution the draw's policy is defined by);
         return_logits and top_logprobs keep reporting the model's raw distribution.  With every penalty off, generate()
         runs exactly the launches it runs without these arguments.
-        Stop conditions decided on the device (hyd_stop_update; hydragen_amd/stopping.py states the rules): eos_token_id given as a
-        LIST or tuple of ids (a list of one included), stop = a list of token-id sequences (lists, tuples or 1-d tensors, ragged; up
-        to 32 of 1..16 tokens), pad_token_id (default: the first EOS id if any, else 0) or return_finish select this path; an int
-        eos_token_id alone keeps the loop and the result it always had.  No tokenizer is involved: stop sequences match TOKEN ids,
-        which is not string matching across tokenisation boundaries (a stop string the tokenizer merges with its neighbours in
-        context is not found: pass every tokenisation that should stop).  A row finishes at its first EOS id (kept) or stop sequence
-        (cut unless include_stop); from then on its columns hold pad_token_id, it is fed pad, and -- with the fused decode preamble
-        -- it leaves the unique K/V stream: no K/V is appended for it and the suffix pass sees length 0 (what that gives back of
-        a step is measured in profiles/stopping.md).  The host does not look at a token per step:
-        it polls the count of running rows every stop_poll_steps steps and leaves the loop when that is 0.  The returned matrix is
-        [B, max(lengths)], whenever the exit was noticed.  return_finish appends a stopping.Finish(lengths, reasons, stop_index)
-        (int32 [B] each; reason 0 = ran to max_new_tokens, 1 = EOS, 2 = stop sequence) as the last return value.  With
-        return_logprobs, entries at or past a row's length are 0.0; with top_logprobs, id -1 / -inf; the return_logits rows of a
-        finished sequence past its length are unspecified.  Penalties keep working (what a finished row draws is ignored).
-        token_overrides cannot be combined with these arguments.
         Constrained decoding (hydragen_amd/sampling.py states the rules, hydragen_amd/constraint.py builds the automata):
         constraint = a constraint.TokenDFA over the model's vocabulary restricts what every row may emit by what it has emitted
         so far; constraint_state = the rows' start states, int [leaf batch] (repeated for num_return_sequences) or [batch],
@@ -1383,58 +1284,62 @@ class HydragenLlamaForCausalLM(nn.Module):
         row).  It composes with the cuts, the penalties and the stop conditions: with TokenDFA.from_choices /
         from_regex(eos=ids) and eos_token_id=ids a row ends through the stop kernel once its output is
         complete.  return_logprobs reports the CONSTRAINED distribution (the same rule as for penalties); return_logits and
-        top_logprobs stay raw.  return_constraint_state appends the final int32 [B] states as the last return value.  Not
-        with token_overrides.  With constraint=None, generate() runs exactly the launches it runs without these arguments."""
+        top_logprobs stay raw.  Not with token_overrides.  With constraint=None, generate() runs exactly the launches it runs
+        without these arguments.
+
+        Stopping, decided on the device (hyd_stop_update; hydragen_amd/stopping.py states the rules): eos_token_id given as a
+        LIST or tuple of ids (a list of one included), stop = a list of token-id sequences (lists, tuples or 1-d tensors, ragged; up
+        to 32 of 1..16 tokens), pad_token_id (default: the first EOS id if any, else 0) or return_finish select this path; an int
+        eos_token_id alone keeps the loop and the result it always had.  No tokenizer is involved: stop sequences match TOKEN ids,
+        which is not string matching across tokenisation boundaries (a stop string the tokenizer merges with its neighbours in
+        context is not found: pass every tokenisation that should stop).  A row finishes at its first EOS id (kept) or stop sequence
+        (cut unless include_stop); from then on its columns hold pad_token_id, it is fed pad, and -- with the fused decode preamble
+        -- it leaves the unique K/V stream: no K/V is appended for it and the suffix pass sees length 0 (what that gives back of
+        a step is measured in profiles/stopping.md).  The host does not look at a token per step:
+        it polls the count of running rows every stop_poll_steps steps and leaves the loop when that is 0.  The returned matrix is
+        [B, max(lengths)], whenever the exit was noticed.  With return_logprobs, entries at or past a row's length are 0.0; with
+        top_logprobs, id -1 / -inf; the return_logits rows of a finished sequence past its length are unspecified.  Penalties keep
+        working (what a finished row draws is ignored).  token_overrides cannot be combined with these arguments.
+
+        Drafts (hydragen_amd/speculative.py states the scheme and why it is lossless): draft_tokens = K in 1..7
+        makes every decode step feed each row its last token and K drafts, verify them in ONE forward pass over [B, K + 1] (the
+        multi-token RoPE + append, the causal-tail attention) and keep the draws up to the first wrong draft; None or 0 runs
+        exactly the launches generate() runs without it.  draft = "prompt_lookup": drafts are the tokens that followed the latest
+        earlier occurrence of the row's last n-gram (ngram = (min, max) lengths, longest first) in the prompt levels GIVEN TO THIS
+        CALL on the row's path, its own prompt and its generated tokens (hyd_draft_lookup; levels kept by earlier calls with
+        shared_cache_op="extend" are not searched -- their ids are not given to this call); or an int tensor [B, max_new_tokens]
+        whose column p is the draft for output position p (tests, benchmarks; no lookup launch).  Rows advance by different
+        amounts; EOS ids and max_new_tokens are applied on the device (hyd_draft_accept) and the result is [B, max(lengths)] padded
+        with pad_token_id, as on the stop path (an int eos_token_id is treated as a list of one).  Works with temperature, top_k /
+        top_p / min_p, return_logprobs, eos_token_id, pad_token_id, return_finish, num_return_sequences, seq_lens, shared_cache_op
+        and constraint; refused (before any launch): penalties and logit_bias, stop, token_overrides, top_logprobs, return_logits,
+        disable_hydragen / disable_attention / disable_hierarchy, fp8 or narrow unique caches, a model on the CPU.
+        With constraint= every step walks its drafts through the automaton (hyd_draft_constrain): a state that allows exactly
+        one token replaces the draft by that token -- accepted with probability 1, the masked sampler can draw nothing else --,
+        a draft the automaton rejects ends the row's proposal, each of the step's K + 1 draws is masked by the state behind the
+        tokens fed in front of it, and the accept (hyd_draft_accept_states) hands the row the state behind its last emitted
+        token.  draft = "constraint" (needs constraint=) proposes that forced chain and nothing else: no lookup launch.
+
+        Returns the tokens [B, generated] alone, or a tuple in this order, each part only if asked for: (tokens, the per-step
+        fp32 logits (return_logits), the fp32 [B, generated] log softmax(logits) of every returned token, unscaled and unfiltered
+        (return_logprobs), top_ids [B, generated, N] int64 and top_logprobs [B, generated, N] f32: for every returned token the N
+        best alternatives of that step's distribution (top_logprobs = N > 0, needs return_logprobs; hyd_token_logprobs,
+        hydragen_amd/scoring.py), a stopping.Finish(lengths, reasons, stop_index) (return_finish; int32 [B] each; reason 0 = ran
+        to max_new_tokens, 1 = EOS, 2 = stop sequence), the final int32 [B] automaton states (return_constraint_state), a
+        speculative.DraftStats(steps, proposed, accepted) whose .forced holds, per row, the proposed drafts that were forced
+        under a constraint (return_draft_stats))."""
         if not self.kv_cache_allocated:
             raise RuntimeError("call setup_caches() before generate()")
-        if constraint is None and (constraint_state is not None or return_constraint_state):
-            raise ValueError("constraint_state / return_constraint_state need constraint=")
-        if constraint is not None:
-            if token_overrides is not None:
-                raise ValueError("constraint cannot be combined with token_overrides (teacher forcing draws nothing to constrain)")
-            sampling.check_constraint(constraint, self.vocab_size)
-            if constraint.next.device != self.lm_head.weight.device:
-                constraint = constraint.to(self.lm_head.weight.device)
-        spec_draft = None
-        if draft_tokens:
-            spec_draft = self._check_draft(
-                draft_tokens, draft, ngram, max_new_tokens,
-                {"repetition / presence / frequency penalties or logit_bias": sampling.penalties_active(
-                    repetition_penalty, presence_penalty, frequency_penalty, logit_bias),
-                 "stop": stop is not None, "token_overrides": token_overrides is not None,
-                 "top_logprobs": bool(top_logprobs), "return_logits": return_logits, "disable_hydragen": disable_hydragen,
-                 "disable_attention": disable_attention, "disable_hierarchy": disable_hierarchy},
-                n_given=0 if input_ids is None else 1 if isinstance(input_ids, Tensor) else len(input_ids),
-                constrained=constraint is not None)
-            if eos_token_id is not None and not isinstance(eos_token_id, (list, tuple, Tensor)):
-                eos_token_id = [eos_token_id]
-        elif return_draft_stats:
-            raise ValueError("return_draft_stats needs draft_tokens")
-        stop_spec = None
-        if isinstance(eos_token_id, (list, tuple)) or stop is not None or pad_token_id is not None or return_finish or spec_draft:
-            if token_overrides is not None:
-                raise ValueError("token_overrides (teacher forcing) has nothing to stop: it cannot be combined with a list of EOS ids, "
-                                 "stop, pad_token_id or return_finish")
-            stop_spec = stopping.check_stop(eos_token_id, stop, pad_token_id, include_stop, self.vocab_size)
-            if not self.lm_head.weight.is_cuda:
-                raise ValueError("stop conditions are decided by a HIP kernel (hyd_stop_update): the model must be on the GPU; "
-                                 "stopping.truncate_reference applies the same rules to CPU tokens")
-            eos_token_id = None
-        if (input_ids is None) == (starting_logits is None):
-            raise ValueError("pass exactly one of input_ids and starting_logits")
-        if temperature < 0:
-            raise ValueError(f"temperature must be non-negative, {temperature} is invalid")
-        sampling.check_filters(top_k, top_p, min_p)
-        top_n = scoring.check_top_n(top_logprobs)
-        if top_n and not return_logprobs:
-            raise ValueError("top_logprobs needs return_logprobs=True")
-        sampling.check_penalties(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, self.vocab_size)
-        penalised = sampling.penalties_active(repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
-        # only the three penalties read the generated tokens; a bias / ban list alone needs no list and has no length limit
-        counted = sampling.penalties_active(repetition_penalty, presence_penalty, frequency_penalty)
-        if counted and max_new_tokens > sampling.GEN_MAX:
-            raise ValueError(f"repetition / presence / frequency penalties count up to {sampling.GEN_MAX} generated tokens per "
-                             f"sequence, max_new_tokens is {max_new_tokens}")
+        call = generation.check_arguments(
+            self, input_ids=input_ids, starting_logits=starting_logits, num_return_sequences=num_return_sequences,
+            max_new_tokens=max_new_tokens, temperature=temperature, top_p=top_p, top_k=top_k, min_p=min_p, eos_token_id=eos_token_id,
+            return_logits=return_logits, disable_hydragen=disable_hydragen, disable_attention=disable_attention,
+            disable_hierarchy=disable_hierarchy, token_overrides=token_overrides, return_logprobs=return_logprobs,
+            top_logprobs=top_logprobs, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+            frequency_penalty=frequency_penalty, logit_bias=logit_bias, stop=stop, pad_token_id=pad_token_id, include_stop=include_stop,
+            return_finish=return_finish, constraint=constraint, constraint_state=constraint_state,
+            return_constraint_state=return_constraint_state, draft_tokens=draft_tokens, draft=draft, ngram=ngram,
+            return_draft_stats=return_draft_stats)
         fan_out = num_return_sequences > 1
         flatten = disable_hierarchy or disable_hydragen  # the baselines keep the last level per sequence
         if shared_cache_op == SharedCacheOp.WIPE:
@@ -1464,44 +1369,13 @@ class HydragenLlamaForCausalLM(nn.Module):
             self.repeat_per_completion_cache_for_num_samples(unique[0].shape[0], num_return_sequences)
 
         try:
-            samp = dict(temperature=temperature, top_p=top_p, top_k=top_k, min_p=min_p, return_logprobs=return_logprobs)
-            if penalised:
-                samp["penalties"] = self._penalties(batch, unique, num_return_sequences, max_new_tokens, repetition_penalty,
-                                                    presence_penalty, frequency_penalty, logit_bias, counted)
-            state = None
-            if constraint is not None:
-                state = self._constraint_state(constraint_state, leaf_batch, num_return_sequences)
-                samp["constraint"] = (constraint, state)
-            call = _DecodeCall(sample=samp, fan=num_return_sequences, max_new_tokens=max_new_tokens, top_n=top_n,
-                               state=state if return_constraint_state else None, logits=[] if return_logits else None,
-                               logprobs=[] if return_logprobs else None, top=([], []) if top_n else None)
-            if spec_draft is not None:
-                # the logical context of the lookup: the levels given to THIS call, outermost first, then the rows' own prompts
-                # (moved to the model's device: hyd_draft_lookup reads them there every step, whatever device the caller's ids are on)
-                dev = self.lm_head.weight.device
-                given = [speculative.Segment(ids.to(dev).long(), None if lens is None else lens.to(dev).long())
-                         for ids, lens in shared + ([unique] if unique is not None else [])]
-                call.draft = dict(spec_draft, segments=given, stats=return_draft_stats)
-            return self._decode(logits[:, -1], unique, call, eos_token_id, token_overrides, stop_spec, return_finish)
+            return generation.decode(self, call, logits[:, -1], shared, unique)
         finally:
             self._scale_windows("close_scale_window", write=False)  # (a call that raised before its first write)
             if shared_cache_op == SharedCacheOp.PRESERVE:
                 self.truncate_shared_caches(levels_before)
             self.model.set_disable_hydragen(False)
             self.model.set_disable_attention(False)
-
-    def _constraint_state(self, constraint_state, leaf_batch, fan):
-        """The call's automaton states, int32 [batch] on the device: the given start states ([leaf batch], repeated per sample, or
-        [batch]), default 0."""
-        dev = self.lm_head.weight.device
-        batch = leaf_batch * fan
-        if constraint_state is None:
-            return torch.zeros((batch,), dtype=torch.int32, device=dev)
-        st = torch.as_tensor(constraint_state)
-        if st.ndim != 1 or st.dtype.is_floating_point or st.dtype == torch.bool or st.shape[0] not in (leaf_batch, batch):
-            raise ValueError(f"constraint_state must hold {leaf_batch} or {batch} integer states, got {tuple(st.shape)} {st.dtype}")
-        st = st.to(device=dev, dtype=torch.int32)
-        return (st.repeat_interleave(fan, 0) if st.shape[0] != batch else st.clone()).contiguous()
 
     @torch.no_grad()
     def choose(self, input_ids, choices, eos_token_id: int, seq_lens=None, temperature: float = 0.0, **kw):
@@ -1518,25 +1392,6 @@ class HydragenLlamaForCausalLM(nn.Module):
         out = self.generate(input_ids, seq_lens=seq_lens, max_new_tokens=longest, temperature=temperature,
                             eos_token_id=[int(eos_token_id)], constraint=dfa, constraint_state=start, return_constraint_state=True, **kw)
         return dfa.choice_of(out[-1]), out[0]
-
-    def _penalties(self, batch, unique, fan, max_new_tokens, repetition_penalty, presence_penalty, frequency_penalty, logit_bias, counted):
-        """The call's layer_ops.Penalties: the used shared levels' bitmaps (one row per shared sequence, read by its
-        batch / sb rows: the same token set whether the keys sit in shared or -- disable_hydragen -- unique caches), the unique
-        prompts' bitmap shared by the samples of a leaf, and -- `counted`: a penalty that reads them is on -- an empty
-        [batch, max_new_tokens] list of generated tokens."""
-        if len(self.shared_bitmaps) != self.get_num_used_shared_caches():
-            raise RuntimeError(f"{self.get_num_used_shared_caches()} shared levels in use but {len(self.shared_bitmaps)} recorded token "
-                               "sets: a level was added or dropped behind append_shared / truncate_shared_caches")
-        context = [(bits, batch // bits.shape[0]) for bits in self.shared_bitmaps]
-        if unique is not None:
-            context.append((layer_ops.token_bitmap(unique[0].long(), unique[1].to(unique[0].device), self.vocab_size), fan))
-        if len(context) > sampling.MAX_CONTEXT:
-            raise ValueError(f"{len(context)} prompt levels: penalties take up to {sampling.MAX_CONTEXT}")
-        dev = self.lm_head.weight.device
-        return layer_ops.Penalties(
-            repetition_penalty, presence_penalty, frequency_penalty, sampling.normalize_logit_bias(logit_bias, dev), context,
-            gen=torch.zeros((batch, max_new_tokens), dtype=torch.int32, device=dev) if counted else None,
-            gen_len=torch.zeros((batch,), dtype=torch.int32, device=dev) if counted else None)
 
     # ---- scoring ----------------------------------------------------------------------------------------
     score_chunk_bytes = 1 << 30  # lm_head output per chunk of score()'s scored rows (tests shrink it)
@@ -1674,297 +1529,3 @@ class HydragenLlamaForCausalLM(nn.Module):
         return scoring.ScoreResult(
             logprobs=lp, token_greedy=greedy, sum=torch.where(live, lp.double(), torch.zeros_like(lp, dtype=torch.float64)).sum(1),
             is_greedy=(greedy | ~live).all(1), top_ids=top_ids if top_n else None, top_logprobs=top_lp if top_n else None)
-
-    def _decode(self, prefill_logits, unique, call: _DecodeCall, eos_token_id, token_overrides, stop_spec, return_finish):
-        samp, fan = call.sample, call.fan
-        pen = samp.get("penalties")
-        if pen is not None and pen.gen is not None:  # (a bias alone keeps no list of generated tokens)
-            # the list of generated tokens follows what is FED: the sampler appends its own draws unless overrides replace them
-            # (or the first token fans out: one row of logits, `fan` rows of tokens)
-            call.pen = pen
-            pen.append = token_overrides is None and fan == 1
-        first = self.sample_from_logits(prefill_logits, num_samples=fan, **samp)
-        if call.logprobs is not None:
-            first, lp = first
-            call.logprobs.append(lp.reshape(-1, 1))
-        if call.top is not None:
-            # the alternatives do not depend on the drawn token: once over the leaf_batch prefill rows, repeated per sample
-            rows = prefill_logits if prefill_logits.stride(-1) == 1 else prefill_logits.contiguous()
-            none = torch.full((rows.shape[0],), -1, dtype=torch.int64, device=rows.device)
-            for kept, t in zip(call.top, layer_ops.token_logprobs(rows, none, call.top_n)[2:]):
-                kept.append(t.repeat_interleave(fan, 0)[:, None])
-        first = first.reshape(-1, 1)
-        if call.logits is not None:
-            call.logits.append(prefill_logits.repeat_interleave(fan, 0))
-        start = self.get_shared_cache_len(first.shape[0])[:, None]
-        if unique is not None:
-            start = start + unique[1].long().repeat_interleave(fan, 0)[:, None]
-        self._check_room(start, call.max_new_tokens, extra=call.draft["k"] if call.draft else 0)
-        feed = first if token_overrides is None else token_overrides[:, 0:1]
-        if call.pen is not None and not pen.append:
-            pen.push(feed)
-            pen.append = token_overrides is None
-        self.set_mode(AttentionMode.DECODE)
-        # calibrated fp8 scales: a call without unique prompts first writes the unique cache in its first decode step (the fused
-        # preamble does not pass through update_per_completion_kvs): the scales are written here, once, outside any captured graph
-        self._scale_windows("close_scale_window")
-        # 16-bit logits straight into the sampler unless the caller wants them (fp32, as the reference returns them) or
-        # the cuts run in torch
-        call.graphed = self.graphed_model is not None
-        call.route = self.sample_route(prefill_logits.is_cuda, True, **samp)  # (a step's logits are rows of the lm_head's output)
-        call.raw = call.logits is None and (self.fused_sampling_filters or not sampling.filters_active(
-            samp["top_k"], samp["top_p"], samp["min_p"]))
-        # Ragged unique prompts: hand the longest sequences to the chip first.  Every length grows by one per step, so the order of
-        # this generation's first step is the order of all of them (C2 heads, lengths 1..128 at random: suffix pass 184 -> 169 us).
-        order = None
-        if unique is not None:
-            lens0 = unique[1].repeat_interleave(fan, 0)
-            if self.schedule_longest_first and lens0.numel() > 1 and bool((lens0 != lens0[0]).any()):
-                order = self.seq_order_buf[: lens0.numel()]
-                order.copy_(_flash.longest_first(lens0))
-        with _flash.seq_order(order, check=False):
-            if call.draft is not None:
-                return self._decode_steps_draft(call, first, start, stop_spec, return_finish)
-            if stop_spec is not None:
-                return self._decode_steps_stop(call, first, start, stop_spec, return_finish)
-            return self._decode_steps(call, first, feed, start, eos_token_id, token_overrides)
-
-    schedule_longest_first = True  # (tests switch it off to compare: only the schedule may depend on it, never a token)
-    # top-k / top-p / min-p in the sampling kernel (hyd_sample_tokens_filtered); False: torch cuts + hyd_sample_tokens, the
-    # path before the kernel existed (tests switch it off to compare)
-    fused_sampling_filters = True
-    # penalties in the sampling kernel (hyd_sample_tokens_penalized); False: sampling.penalize_logits in torch, then the paths
-    # above (tests and tools/sampler_bench.py switch it off to compare)
-    fused_sampling_penalties = True
-
-    def _step(self, call: _DecodeCall, input_ids, position_ids):
-        """One decode step along the call's route: (logits [B, V], tokens [B, 1], log-probs or None)."""
-        logits = self(input_ids=input_ids, position_ids=position_ids, use_graph=call.graphed, raw_logits=call.raw)[:, -1]
-        if call.logits is not None:
-            call.logits.append(logits)
-        return (logits,) + draw_tokens(call.route, logits, **call.sample)
-
-    def _decode_steps(self, call: _DecodeCall, first, feed, start, eos, overrides):
-        done = (first == eos) if eos is not None else None
-        tokens = [first]
-        for step in range(call.max_new_tokens - 1):
-            logits, nxt, lp = self._step(call, feed, start + step)
-            if done is not None:
-                done = done | (nxt == eos)
-                if bool(done.all()):
-                    break
-            tokens.append(nxt)
-            call.keep(logits, nxt, lp)
-            feed = nxt if overrides is None else overrides[:, step + 1 : step + 2]
-            if call.pen is not None and not call.pen.append and feed.shape[1]:
-                call.pen.push(feed)
-        check_collectives()  # no-op without the direct xGMI all-reduce; raises if a rank ever gave up on a peer
-        return call.result(torch.cat(tokens, dim=-1))
-
-    # hyd_stop_update path: every this many decode steps the host starts a non-blocking copy of the running-row count of the
-    # step just enqueued and looks at it one step later (tests shrink it)
-    stop_poll_steps = 8
-    # None: finished rows are retired from the unique K/V stream whenever the fused decode preamble is in use; False: never
-    # (tools/stop_bench.py and the tests compare the two: only the step time may depend on it, never a token)
-    stop_retire: Optional[bool] = None
-
-    def _decode_steps_stop(self, call: _DecodeCall, first, start, spec, return_finish):
-        """_decode_steps with the stop conditions of `spec` decided by hyd_stop_update after every sampling launch: the kernel
-        writes the output matrix, keeps lengths and finish reasons, and hands back the token and the position to feed next."""
-        # (penalties: _decode has switched the sampler's own append on -- nothing is overridden here -- so the list of generated
-        # tokens follows the draws; what a finished row draws goes nowhere else)
-        dev = first.device
-        B = first.shape[0]
-        attn = self.model.layers[0].self_attn
-        # a retired row is fed position shared_len - 1: cache index -1, which the fused preamble skips and the torch scatter of
-        # update_per_completion_kvs would not
-        retire = all(l.self_attn.use_fused_decode for l in self.model.layers) if self.stop_retire is None else bool(self.stop_retire)
-        if retire and not all(l.self_attn.use_fused_decode for l in self.model.layers):
-            raise ValueError("stop_retire needs the fused decode preamble (use_fused_decode) in every layer")
-        shared_len = None if attn.disable_hydragen else self.get_shared_cache_len(B).contiguous()
-        start_pos = start.reshape(-1).long().contiguous()
-        out, length, reason, stop_index, live = stopping.new_state(B, call.max_new_tokens, spec, dev)
-        stop_tokens = spec.stop_table(dev)[0] if spec.stops else None
-        poll = max(1, int(self.stop_poll_steps))
-        # (page-locked once per model, not once per call: every slot is written by its copy before it is read, and no copy
-        # is left in flight when a generation returns)
-        polled = getattr(self, "_stop_polled", None)
-        if polled is None or polled.numel() < call.max_new_tokens // poll + 1:
-            polled = self._stop_polled = torch.empty((max(call.max_new_tokens // poll + 1, 512),), dtype=torch.int32).pin_memory()
-        pending = None  # (slot, event) of the copy started at the previous step
-
-        def update(tok, t):
-            return layer_ops.stop_update(tok, t, spec, out, length, reason, stop_index, live, start_pos, shared_len, retire, stop_tokens)
-
-        feed, pos = update(first, 0)
-        steps = 1  # columns of `out` written
-        for step in range(call.max_new_tokens - 1):
-            logits, nxt, lp = self._step(call, feed[:, None], pos[:, None])
-            call.keep(logits, nxt, lp)
-            feed, pos = update(nxt, steps)
-            steps += 1
-            # The count of running rows, without draining the launch queue: the copy started after step c is waited for after step
-            # c + 1 has been enqueued, so the device always has a step of work queued behind what the host waits for, and an
-            # exit is noticed at most stop_poll_steps steps late.  (Only looking at events that happen to be complete would let
-            # the host run ahead by the whole launch queue before it notices anything.)
-            if pending is not None:
-                slot, ev = pending
-                ev.synchronize()
-                pending = None
-                if int(polled[slot]) == 0:
-                    break
-            if steps % poll == 0 and steps < call.max_new_tokens:
-                slot = steps // poll
-                polled[slot : slot + 1].copy_(live[steps - 1 : steps], non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-                pending = (slot, ev)
-        check_collectives()
-        width = int(length.max().item()) if B else 0  # (the one synchronisation of the generation)
-        past = torch.arange(width, device=dev)[None, :] >= length[:, None]
-        return call.result(out[:, :width], past, stopping.Finish(length, reason, stop_index) if return_finish else None)
-
-    # ---- speculative decoding (hydragen_amd/speculative.py) -----------------------------------------------------------------
-    def _check_draft(self, draft_tokens, draft, ngram, max_new_tokens, refused: dict, n_given: int = 0, constrained: bool = False) -> dict:
-        """generate()'s draft arguments, checked before any launch -> dict(k, given, ngram, only_forced).  n_given: the prompt
-        levels given to the call (each is a segment of the lookup's table, beside the generated tokens); constrained: the call
-        has a constraint= (what draft="constraint" proposes from)."""
-        k = speculative.check_draft_tokens(draft_tokens)
-        for what, on in refused.items():
-            if on:
-                raise NotImplementedError(f"draft_tokens cannot be combined with {what}: a speculative step draws and accepts "
-                                          "several tokens per row in launches that do not carry it")
-        given = None
-        only_forced = isinstance(draft, str) and draft == "constraint"
-        if isinstance(draft, Tensor):
-            if draft.ndim != 2 or draft.shape[1] != max_new_tokens or draft.is_floating_point() or draft.dtype == torch.bool:
-                raise ValueError(f"draft: an int tensor [batch, max_new_tokens = {max_new_tokens}], got {tuple(draft.shape)} {draft.dtype}")
-            given = draft
-        elif only_forced:
-            if not constrained:
-                raise ValueError("draft='constraint' proposes the tokens the automaton forces: it needs constraint=")
-        elif not isinstance(draft, str) or draft != "prompt_lookup":
-            raise ValueError(f"draft = {draft!r}: 'prompt_lookup', 'constraint' or an int tensor [batch, max_new_tokens]")
-        elif n_given + 1 > speculative.MAX_SEGMENTS:
-            raise ValueError(f"draft='prompt_lookup' searches {n_given} given levels and the generated tokens: at most "
-                             f"{speculative.MAX_SEGMENTS} segments (hyd_draft_lookup)")
-        ngram = speculative.check_ngram(ngram)
-        attn = self.model.layers[0].self_attn
-        if attn.kv_cache.fp8 or attn.kv_cache.narrow or attn.head_dim not in (64, 128, 256):
-            raise NotImplementedError("draft_tokens with fp8 unique caches or a head dim other than 64 / 128 / 256: the multi-token "
-                                      "preamble and the causal-tail suffix pass take 16-bit caches of those head dims only")
-        if constrained and not self.lm_head.weight.is_cuda:
-            raise NotImplementedError("draft_tokens with constraint= is not implemented for a model on the CPU: the drafts are walked "
-                                      "through the automaton and accepted with their states by HIP kernels (speculative."
-                                      "constrain_drafts_reference / accept_states_reference state the rules in torch)")
-        if not self.lm_head.weight.is_cuda:
-            raise ValueError("draft_tokens: drafts are proposed, verified and accepted by HIP kernels, the model must be on the GPU "
-                             "(speculative.prompt_lookup_reference / accept_reference state the rules in torch)")
-        return dict(k=k, given=given, ngram=ngram, only_forced=only_forced)
-
-    def _decode_steps_draft(self, call: _DecodeCall, first, start, spec, return_finish):
-        """The decode loop with draft_tokens = K: per step the drafts (hyd_draft_lookup, or a gather from the given ones), ONE
-        forward over [B, K + 1] with all its logits, one draw per logits row along the call's route, then hyd_draft_accept, which
-        keeps the output matrix, the lengths and the finish reasons and hands back each row's next token and position.  The host
-        polls the running-row count every stop_poll_steps steps, exactly like _decode_steps_stop."""
-        dev, B = first.device, first.shape[0]
-        d = call.draft
-        K, mx = d["k"], call.max_new_tokens
-        T = K + 1
-        fused = all(l.self_attn.use_fused_decode for l in self.model.layers)
-        retire = fused if self.stop_retire is None else bool(self.stop_retire)
-        if retire and not fused:
-            raise ValueError("stop_retire needs the fused decode preamble (use_fused_decode) in every layer")
-        shared_len = self.get_shared_cache_len(B).contiguous()
-        start_pos = start.reshape(-1).long().contiguous()
-        want_lp = call.logprobs is not None
-        out, length, reason, stop_index, out_lp = speculative.new_state(B, mx, spec.pad, dev, want_lp)
-        live = torch.zeros((mx,), dtype=torch.int32, device=dev)
-        eos = spec.eos
-
-        def accept(fed, sampled, lp, slot, states=None):
-            return speculative.draft_accept(fed, sampled, out, length, reason, stop_index, live[slot : slot + 1], start_pos, shared_len,
-                                            eos, spec.pad, mx, retire, lp, out_lp if lp is not None else None, states)
-
-        # constraint=: the rows' automaton states (already advanced by the first draw) and, per step, the state behind every fed
-        # token -- the sampler's state array over the step's B * T logits rows, advanced in place, then read by the accept
-        dfa, state = call.sample.get("constraint") or (None, None)
-        sample = call.sample
-        if dfa is not None:
-            step_state = torch.empty((B, T), dtype=torch.int32, device=dev)
-            n_forced = torch.empty((B,), dtype=torch.int32, device=dev)
-            forced = torch.zeros((B,), dtype=torch.int64, device=dev)
-            sample = dict(call.sample, constraint=(dfa, step_state.view(-1)))
-            dfa.forced  # (made once per automaton, before the loop)
-
-        # the first token, drawn from the prefill logits, enters like a step of one token
-        first = first.reshape(B, 1).long()
-        feed, pos, _ = accept(first, first, call.logprobs[0].reshape(B, 1).float() if want_lp else None, 0)
-        given = d["given"]
-        if given is not None:
-            if given.shape[0] != B:
-                raise ValueError(f"draft holds {given.shape[0]} rows for a batch of {B}")
-            given = given.to(dev).long()
-        segments = d["segments"] + [speculative.Segment(out, length)]
-        cols = torch.arange(K, device=dev)[None, :]
-        offs = torch.arange(T, device=dev)[None, :]
-        fed = torch.full((B, T), spec.pad, dtype=torch.int64, device=dev)
-        proposed = torch.zeros((B,), dtype=torch.int64, device=dev)
-        accepted = torch.zeros((B,), dtype=torch.int64, device=dev)
-        poll = max(1, int(self.stop_poll_steps))
-        polled = getattr(self, "_stop_polled", None)
-        if polled is None or polled.numel() < mx // poll + 1:
-            polled = self._stop_polled = torch.empty((max(mx // poll + 1, 512),), dtype=torch.int32).pin_memory()
-        pending = None
-        steps = 0
-        for step in range(1, mx):
-            fed[:, 0] = feed
-            # a draft counts as proposed when accepting it can add a token: the one for output position p lets the draw for p + 1
-            # out, so a row with `length` tokens has room for max_new_tokens - 1 - length of them (0 for a finished row)
-            room = (mx - 1 - length).clamp_(min=0) * (reason == 0)
-            n_prop = None
-            if given is not None:
-                fed[:, 1:] = given.gather(1, (length.long()[:, None] + cols).clamp_(max=mx - 1))
-                if dfa is not None:
-                    n_prop = torch.full((B,), K, dtype=torch.int32, device=dev)
-            elif d["only_forced"]:
-                n_prop = torch.zeros((B,), dtype=torch.int32, device=dev)
-            else:
-                _, n_prop = speculative.draft_lookup(segments, B, K, d["ngram"], out=fed[:, 1:])
-            compare, states = fed, None
-            if dfa is not None:
-                # forced states replace drafts, a draft the automaton rejects ends the row's proposal (hyd_draft_constrain)
-                speculative.constrain_drafts(dfa, state, fed, n_prop, d["only_forced"], step_state, n_forced)
-                forced += torch.minimum(n_forced, room)
-                states = (step_state, state)
-                if d["only_forced"]:
-                    # behind the end of the forced chain the columns hold whatever an earlier step left and their draws are
-                    # unconstrained: the accept compares them with a value no token equals, so none of those draws is kept
-                    compare = torch.where(offs <= n_prop[:, None], fed, torch.full_like(fed, -1))
-            proposed += room.clamp(max=K) if n_prop is None else torch.minimum(n_prop, room)
-            logits = self(input_ids=fed, position_ids=pos[:, None] + offs, use_graph=call.graphed, full_logits=True, raw_logits=call.raw)
-            tok, lp = draw_tokens(call.route, logits.reshape(B * T, -1), **sample)
-            feed, pos, acc = accept(compare, tok.reshape(B, T), lp.reshape(B, T).float() if want_lp else None, step, states)
-            accepted += acc
-            steps += 1
-            if pending is not None:
-                slot, ev = pending
-                ev.synchronize()
-                pending = None
-                if int(polled[slot]) == 0:
-                    break
-            if steps % poll == 0 and step + 1 < mx:
-                slot = steps // poll
-                polled[slot : slot + 1].copy_(live[step : step + 1], non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-                pending = (slot, ev)
-        check_collectives()
-        width = int(length.max().item()) if B else 0  # (the one synchronisation of the generation)
-        past = torch.arange(width, device=dev)[None, :] >= length[:, None]
-        if want_lp:
-            call.logprobs = [out_lp]
-        ret = call.result(out[:, :width], past, stopping.Finish(length, reason, stop_index) if return_finish else None)
-        if d["stats"]:
-            ret = (ret if isinstance(ret, tuple) else (ret,)) + (speculative.DraftStats(steps, proposed, accepted, forced if dfa is not None else None),)
-        return ret

@@ -293,7 +293,7 @@ class SampleRoute(NamedTuple):
 
 def sample_route(cuda: bool, eligible: bool, rewritten: bool, num_samples: int, constraint: bool, penalties: bool, filters: bool,
                  logprobs: bool, fused_filters: bool = True, fused_penalties: bool = True) -> SampleRoute:
-    """THE table of the sampling routes: llama.draw_tokens runs a route, layer_ops.sample_tokens picks its entry point from one.
+    """THE table of the sampling routes: generation.draw_tokens runs a route, layer_ops.sample_tokens picks its entry point from one.
     cuda: the rows are on the GPU; rewritten: and 2-D with temperature >= 0, what a kernel needs of rows a torch stage has
     rewritten (contiguous); eligible: and of unit last stride as they are (a kernel takes them when num_samples == 1);
     constraint / penalties / filters: given / active; logprobs: wanted; fused_*: the model's two switches.  The penalties in

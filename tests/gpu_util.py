@@ -122,3 +122,21 @@ def suffix_fwd_with_partials(tq, tk, tv, tsl, groups, dt, want_lse, causal=False
     torch.cuda.synchronize()
     del keep
     return out, (lse if want_lse else None)
+
+
+class Recorder:
+    """The loaded library with the name of every entry point that is called noted down."""
+
+    def __init__(self, lib):
+        self._lib, self.calls = lib, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.startswith("hyd_"):
+            return fn
+
+        def call(*args):
+            self.calls.append(name)
+            return fn(*args)
+
+        return call

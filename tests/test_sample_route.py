@@ -1,5 +1,5 @@
 """sampling.sample_route against an independent restatement of its table, over every combination of its inputs, and the
-executor (llama.draw_tokens behind sample_from_logits) on CPU logits against the direct composition of the float64 definitions."""
+executor (generation.draw_tokens behind sample_from_logits) on CPU logits against the direct composition of the float64 definitions."""
 import itertools
 import math
 

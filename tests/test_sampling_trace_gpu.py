@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from hydragen_amd import _lib
+from tests.gpu_util import Recorder
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -12,24 +13,6 @@ PLAIN, FILTERED, PENALIZED, CONSTRAINED = (
 LOGPROBS, STOP, BITMAP = "hyd_token_logprobs", "hyd_stop_update", "hyd_token_bitmap_build"
 COUNTED = (PLAIN, FILTERED, PENALIZED, CONSTRAINED, LOGPROBS, STOP, BITMAP)
 EOS = 511
-
-
-class _Recorder:
-    """The loaded library with the name of every entry point that is called noted down."""
-
-    def __init__(self, lib):
-        self._lib, self.calls = lib, []
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        if not name.startswith("hyd_"):
-            return fn
-
-        def call(*args):
-            self.calls.append(name)
-            return fn(*args)
-
-        return call
 
 
 @pytest.fixture(scope="module")
@@ -65,7 +48,7 @@ def _trace(model, monkeypatch, unique=False, switches=(), **kw):
     with monkeypatch.context() as m:
         for name in switches:
             m.setattr(model, name, False)
-        rec = _Recorder(_lib.load())
+        rec = Recorder(_lib.load())
         m.setattr(_lib, "_lib", rec)
         torch.manual_seed(1234)
         model.generate(input_ids=ids, num_return_sequences=1 if unique else 4, max_new_tokens=3, temperature=0.7, **kw)

@@ -22,8 +22,8 @@ def corrupted(G, K):
 
 
 def simulate(G, draft, K, start=None, poll=1):
-    """generate()'s draft loop on the host with G as every draw: speculative.accept_reference driven the way _decode_steps_draft
-    drives hyd_draft_accept -> (steps, proposed [B], accepted [B], the accepted counts of every step of every running row).  A draw
+    """generate()'s draft loop on the host with G as every draw: speculative.accept_reference driven the way
+    generation._decode_steps_draft drives hyd_draft_accept -> (steps, proposed [B], accepted [B], the accepted counts of every step of every running row).  A draw
     behind a wrong draft is thrown away whatever it is, so G stands for it as well."""
     B, mx = G.shape
     T = K + 1
