@@ -292,6 +292,21 @@ class KvScalesParams(C.Structure):
     ]
 
 
+class LinearW8Params(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("w8", C.c_void_p), ("scale", C.c_void_p), ("y", C.c_void_p), ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_size_t), ("x_row_stride", C.c_int64), ("y_row_stride", C.c_int64),
+        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("dtype", C.c_int32),
+    ]
+
+
+class WeightWidenParams(C.Structure):
+    _fields_ = [
+        ("w8", C.c_void_p), ("scale", C.c_void_p), ("out", C.c_void_p), ("out_row_stride", C.c_int64),
+        ("N", C.c_int32), ("K", C.c_int32), ("dtype", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 class AllReduceParams(C.Structure):
     _fields_ = [
         ("blocks", C.POINTER(C.c_void_p)), ("in_", C.c_void_p), ("out", C.c_void_p), ("count", C.c_int64),
@@ -346,6 +361,9 @@ EXPORTS = {
     "hyd_dfa_forced_tokens": (C.c_int, [C.POINTER(DfaForcedParams), C.c_void_p]),
     "hyd_draft_constrain": (C.c_int, [C.POINTER(DraftConstrainParams), C.c_void_p]),
     "hyd_draft_accept_states": (C.c_int, [C.POINTER(DraftAcceptParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hyd_linear_w8_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "hyd_linear_w8": (C.c_int, [C.POINTER(LinearW8Params), C.c_void_p]),
+    "hyd_weight_widen": (C.c_int, [C.POINTER(WeightWidenParams), C.c_void_p]),
     "hyd_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }

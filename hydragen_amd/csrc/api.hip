@@ -1309,6 +1309,63 @@ int hyd_kv_scales_from_absmax(const hyd_kv_scales_params* p, void* stream) {
     return launched(launch_kv_scales(a, static_cast<hipStream_t>(stream)), "kv_scales kernel launch");
 }
 
+// ---- fp8 linear-layer weights (linear_w8.hip) --------------------------------------------------------------------------------
+static int check_w8_common(const void* w8, const float* scale, int32_t N, int32_t K, int32_t dtype, int k_multiple) {
+    if (dtype != HYD_F16 && dtype != HYD_BF16) return fail(HYD_ERR_UNSUPPORTED, "dtype %d: f16 / bf16 activations (the weights are e4m3fn)", dtype);
+    if (N < 1 || K < 1) return fail(HYD_ERR_BAD_ARG, "N %d / K %d must be >= 1", N, K);
+    if (K % k_multiple != 0) return fail(HYD_ERR_BAD_ARG, "K %d must be a multiple of %d", K, k_multiple);
+    if (int rc = check_ptr_align(w8, "w8")) return rc;
+    if (!scale) return fail(HYD_ERR_BAD_ARG, "scale is null");
+    if (misaligned(scale, 4)) return fail(HYD_ERR_BAD_ARG, "scale is not aligned to its element size");
+    return HYD_OK;
+}
+
+size_t hyd_linear_w8_workspace_bytes(int32_t M, int32_t N, int32_t K) {
+    if (M < 1 || N < 1 || K < 1) return 0;
+    return plan_linear_w8(M, N, K).bytes;
+}
+
+int hyd_linear_w8(const hyd_linear_w8_params* p, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    if (p->M < 1) return fail(HYD_ERR_BAD_ARG, "M %d must be >= 1", p->M);
+    if (int rc = check_w8_common(p->w8, p->scale, p->N, p->K, p->dtype, 16)) return rc;
+    if (int rc = check_ptr_align(p->x, "x")) return rc;
+    if (int rc = check_ptr_align(p->y, "y")) return rc;
+    if (int rc = check_stride8(p->x_row_stride, "x_row_stride")) return rc;
+    if (int rc = check_stride8(p->y_row_stride, "y_row_stride")) return rc;
+    if (p->x_row_stride < p->K || p->y_row_stride < p->N)
+        return fail(HYD_ERR_BAD_ARG, "x_row_stride %lld < K %d or y_row_stride %lld < N %d", (long long)p->x_row_stride, p->K, (long long)p->y_row_stride, p->N);
+    const LinearW8Plan pl = plan_linear_w8(p->M, p->N, p->K);
+    if ((int64_t)pl.ngroups * pl.mtiles > 0x7fffffffLL || ((int64_t)p->M * (pl.np / 4) + 255) / 256 > 0x7fffffffLL)
+        return fail(HYD_ERR_UNSUPPORTED, "M %d x N %d: more workgroups than one launch takes", p->M, p->N);
+    if (pl.bytes) {
+        if (!p->workspace || p->workspace_bytes < pl.bytes)
+            return fail(HYD_ERR_WORKSPACE, "linear_w8 needs %zu workspace bytes for M %d N %d K %d, got %zu", pl.bytes, p->M, p->N, p->K, p->workspace ? p->workspace_bytes : (size_t)0);
+        if (misaligned(p->workspace, 16)) return fail(HYD_ERR_WORKSPACE, "workspace must be 16-byte aligned");
+    }
+    LinearW8Args a;
+    memset(&a, 0, sizeof(a));
+    a.x = p->x; a.w8 = static_cast<const uint8_t*>(p->w8); a.scale = p->scale; a.y = p->y;
+    a.ws = pl.bytes ? static_cast<float*>(p->workspace) : nullptr;
+    a.xs = p->x_row_stride; a.ys = p->y_row_stride; a.np = pl.np;
+    a.M = p->M; a.N = p->N; a.K = p->K;
+    a.mtiles = pl.mtiles; a.steps = pl.steps; a.splits = pl.splits;
+    return launched(launch_linear_w8(a, pl, p->dtype, static_cast<hipStream_t>(stream)), "linear_w8 kernel launch");
+}
+
+int hyd_weight_widen(const hyd_weight_widen_params* p, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    if (int rc = check_w8_common(p->w8, p->scale, p->N, p->K, p->dtype, 8)) return rc;
+    if (int rc = check_ptr_align(p->out, "out")) return rc;
+    if (int rc = check_stride8(p->out_row_stride, "out_row_stride")) return rc;
+    if (p->out_row_stride < p->K) return fail(HYD_ERR_BAD_ARG, "out_row_stride %lld < K %d", (long long)p->out_row_stride, p->K);
+    WeightWidenArgs a;
+    memset(&a, 0, sizeof(a));
+    a.w8 = static_cast<const uint8_t*>(p->w8); a.scale = p->scale; a.out = p->out; a.os = p->out_row_stride;
+    a.N = p->N; a.K = p->K;
+    return launched(launch_weight_widen(a, p->dtype, static_cast<hipStream_t>(stream)), "weight_widen kernel launch");
+}
+
 int hyd_ipc_get_handle(const void* dev_ptr, void* handle_out) {
     static_assert(sizeof(hipIpcMemHandle_t) == HYD_IPC_HANDLE_BYTES, "IPC handle size");
     if (!dev_ptr || !handle_out) return fail(HYD_ERR_BAD_ARG, "null pointer");

@@ -291,7 +291,39 @@ struct KvScalesArgs {  // kv_scale.hip: amax [2, Hkv] -> k_scale / v_scale [Hkv]
     float c;
 };
 
+struct LinearW8Plan {  // linear_w8.hip: the launch plan of hyd_linear_w8, from M, N and K alone
+    int32_t mt;       // 16-row MFMA tiles of x a workgroup carries: 1 / 2 (linear_w8_kernel), 4 / 8 (linear_w8_rows_kernel)
+    int32_t mtiles;   // workgroups along M: ceil(M / (16 * mt))
+    int32_t ngroups;  // workgroups along N: ceil(N / 32), or ceil(N / 128) for the rows kernel
+    int32_t steps;    // 128-deep steps along K: ceil(K / 128)
+    int32_t splits;   // workgroups along K; > 1: fp32 partial sums in the workspace, reduced by a second launch
+    int64_t np;       // N rounded up to 4: the row length of a partial-sum slice
+    size_t bytes;     // workspace: splits > 1 ? splits * M * np * 4 : 0
+};
+
+struct LinearW8Args {  // linear_w8.hip: y = round16(scale * (x . w8^T))
+    const void* x;
+    const uint8_t* w8;
+    const float* scale;
+    void* y;
+    float* ws;
+    int64_t xs, ys, np;  // row strides of x / y (elements) and of a partial-sum slice (floats)
+    int32_t M, N, K;
+    int32_t mtiles, steps, splits;
+};
+
+struct WeightWidenArgs {  // linear_w8.hip: out = dequantize_weight(w8, scale)
+    const uint8_t* w8;
+    const float* scale;
+    void* out;
+    int64_t os;
+    int32_t N, K;
+};
+
 // launchers (defined next to the kernels); return hipError_t as int
+LinearW8Plan plan_linear_w8(int M, int N, int K);                                        // linear_w8.hip, shapes only
+int launch_linear_w8(const LinearW8Args& a, const LinearW8Plan& pl, int dtype, hipStream_t s);  // linear_w8.hip
+int launch_weight_widen(const WeightWidenArgs& a, int dtype, hipStream_t s);             // linear_w8.hip
 int launch_kv_absmax(const KvAbsmaxArgs& a, int dtype, hipStream_t s);  // kv_scale.hip
 int launch_kv_scales(const KvScalesArgs& a, hipStream_t s);             // kv_scale.hip
 int launch_kv_promote(const KvPromoteArgs& a, int src_dtype, int dst_dtype, hipStream_t s);  // kv_promote.hip

@@ -30,6 +30,7 @@ from .flash import flash_attention, flash_attention_seqlen, padded_head_dim
 from . import kv_quant as _kv_quant
 from .kv_quant import FP8_DTYPE, dequantize_kv, quantize_kv, scale_constant
 from .tp import all_reduce_sum
+from .weight_quant import Fp8Linear, W8Scratch
 
 
 @dataclass
@@ -138,8 +139,13 @@ class LlamaMLP(nn.Module):
         self.down_proj = nn.Linear(config.intermediate_size, config.hidden_size, bias=False)
         self.tp_reduce = False  # row-parallel down_proj needs the all-reduce of tp.py:83-87
         self._gate_up: Optional[Tensor] = None
+        self.gate_up_proj = None  # weight_quant.Fp8Linear once the model is quantized (gate_proj / up_proj are then None)
 
     def forward(self, x):
+        if self.gate_up_proj is not None:  # fp8 weights (quantize_weights): gate|up is one module, _fused_weight has nothing to fuse
+            g, u = self.gate_up_proj(x).split(self.gate_up_proj.out_features // 2, dim=-1)
+            y = self.down_proj(layer_ops.swiglu(g, u) if layer_ops.supported(g) else nn.functional.silu(g) * u)
+            return all_reduce_sum(y) if self.tp_reduce else y
         self._gate_up = w = _fused_weight(self._gate_up, (self.gate_proj, self.up_proj))
         if w is not None:
             g, u = nn.functional.linear(x, w).split(self.gate_proj.weight.shape[0], dim=-1)
@@ -523,6 +529,7 @@ class HydragenLlamaAttention(nn.Module):
         self.tp_reduce = False  # row-parallel o_proj needs the all-reduce of tp.py:108-112
         self.use_fused_decode = True
         self._qkv: Optional[Tensor] = None
+        self.qkv_proj = None  # weight_quant.Fp8Linear once the model is quantized (q_proj / k_proj / v_proj are then None)
 
     def _decode_multi(self, q, k, v, cos, sin, position_ids, shared_len):
         """Attention of a MULTI-TOKEN decode step (speculative.py): q / k / v [B, T, H, D] are T consecutive tokens per row,
@@ -563,12 +570,16 @@ class HydragenLlamaAttention(nn.Module):
         """shared_len: the per-sequence total shared length [B] (get_shared_len) when the caller already has it -- it is
         the same for every layer of a forward pass, and computing it is three small launches (~17 us) per layer."""
         bsz, q_len, _ = hidden_states.shape
-        self._qkv = w = _fused_weight(self._qkv, (self.q_proj, self.k_proj, self.v_proj))
-        if w is not None:
-            nq, nk = self.q_proj.weight.shape[0], self.k_proj.weight.shape[0]
-            q, k, v = nn.functional.linear(hidden_states, w).split([nq, nk, nk], dim=-1)
+        if self.qkv_proj is not None:  # fp8 weights (quantize_weights): q|k|v is one module, _fused_weight has nothing to fuse
+            nq, nk = self.num_heads * self.head_dim, self.num_key_value_heads * self.head_dim
+            q, k, v = self.qkv_proj(hidden_states).split([nq, nk, nk], dim=-1)
         else:
-            q, k, v = self.q_proj(hidden_states), self.k_proj(hidden_states), self.v_proj(hidden_states)
+            self._qkv = w = _fused_weight(self._qkv, (self.q_proj, self.k_proj, self.v_proj))
+            if w is not None:
+                nq, nk = self.q_proj.weight.shape[0], self.k_proj.weight.shape[0]
+                q, k, v = nn.functional.linear(hidden_states, w).split([nq, nk, nk], dim=-1)
+            else:
+                q, k, v = self.q_proj(hidden_states), self.k_proj(hidden_states), self.v_proj(hidden_states)
         q = q.view(bsz, q_len, self.num_heads, self.head_dim)
         k = k.view(bsz, q_len, self.num_key_value_heads, self.head_dim)
         v = v.view(bsz, q_len, self.num_key_value_heads, self.head_dim)
@@ -815,6 +826,7 @@ class HydragenLlamaForCausalLM(nn.Module):
         self.vocab_size = config.vocab_size
         self.lm_head = nn.Linear(config.hidden_size, config.vocab_size, bias=False)
         self.kv_cache_allocated = False
+        self.weights_quantized = False  # quantize_weights()
         self.graphed_model: Optional[GraphedHydragenLlamaModel] = None
         self.mode: Optional[str] = None
         # one presence bitmap [sb, ceil(V / 32)] int32 per used shared level, recorded by append_shared (the penalties' context)
@@ -898,6 +910,47 @@ class HydragenLlamaForCausalLM(nn.Module):
         else:
             self.graphed_model = None
 
+    def quantize_weights(self, dtype: torch.dtype = FP8_DTYPE, skip=("lm_head",)) -> None:
+        """Store the decoder layers' linear weights in fp8 (weight_quant.py: e4m3fn codes with one power-of-two scale per output
+        channel; activations, accumulators and outputs stay 16-bit) and release the 16-bit storage.  q|k|v and gate|up become one
+        Fp8Linear each (`self_attn.qkv_proj`, `mlp.gate_up_proj`: the projections are quantized one by one and concatenated, so
+        fusing changes no value; `q_proj` ... `up_proj` become None), o_proj and down_proj are replaced in place.  `skip` names
+        modules to leave alone: "lm_head" (the default; remove it to quantize the head too), or any of "qkv_proj", "o_proj",
+        "gate_up_proj", "down_proj".  The embedding is never quantized.  Call it after the weights are loaded and after apply_tp
+        (a rank quantizes its own shards); a second call, and apply_tp / make_tp_files afterwards, raise.  A step with up to
+        weight_quant.W8_MAX_ROWS rows (batch x tokens per row) runs hyd_linear_w8, larger ones widen the weight into one scratch
+        buffer of the model (sized here for the largest quantized weight, so that no forward allocates and captured graphs hold
+        static addresses) and run the 16-bit GEMM on it.  state_dict() carries `weight` / `weight_scale` of the new modules;
+        loading it into a model quantized the same way restores it bit for bit."""
+        if dtype != FP8_DTYPE:
+            raise NotImplementedError(f"quantize_weights(dtype={dtype}): {FP8_DTYPE} is the one format")
+        if self.weights_quantized:
+            raise RuntimeError("quantize_weights() was already called on this model")
+        skip = set(skip)
+        unknown = skip - {"lm_head", "qkv_proj", "o_proj", "gate_up_proj", "down_proj"}
+        if unknown:
+            raise ValueError(f"quantize_weights(skip=...): unknown module names {sorted(unknown)}")
+        if any(p.device.type == "meta" for p in self.parameters()):
+            raise RuntimeError("quantize_weights() needs loaded weights (the model is on the meta device)")
+        self.maybe_invalidate()
+        unfuse_weights(self.model)  # every projection owns its rows again: the fused 16-bit tensors are released with them
+        scratch = W8Scratch()
+        for layer in self.model.layers:
+            attn, mlp = layer.self_attn, layer.mlp
+            if "qkv_proj" not in skip:
+                attn.qkv_proj = Fp8Linear.from_linears((attn.q_proj, attn.k_proj, attn.v_proj), scratch)
+                attn.q_proj = attn.k_proj = attn.v_proj = None
+            if "o_proj" not in skip:
+                attn.o_proj = Fp8Linear.from_linears((attn.o_proj,), scratch)
+            if "gate_up_proj" not in skip:
+                mlp.gate_up_proj = Fp8Linear.from_linears((mlp.gate_proj, mlp.up_proj), scratch)
+                mlp.gate_proj = mlp.up_proj = None
+            if "down_proj" not in skip:
+                mlp.down_proj = Fp8Linear.from_linears((mlp.down_proj,), scratch)
+        if "lm_head" not in skip:
+            self.lm_head = Fp8Linear.from_linears((self.lm_head,), scratch)
+        self.weights_quantized = True
+
     def maybe_invalidate(self):
         if self.graphed_model is not None:
             self.graphed_model.invalidate()
@@ -931,7 +984,7 @@ class HydragenLlamaForCausalLM(nn.Module):
         self.maybe_invalidate()
         max_unique_seq_length = (max_unique_seq_length + 15) // 16 * 16
         head_dim = self.config.hidden_size // self.get_num_heads()
-        device, dtype = self.lm_head.weight.device, self.lm_head.weight.dtype
+        device, dtype = self.lm_head.weight.device, self.model.embed_tokens.weight.dtype  # (the lm_head's weight may be fp8)
         # the layers' unique caches, placed where the suffix pass streams them fastest (placement.py: more candidates than layers
         # are allocated, each timed once with the suffix pass over all of its keys, the slowest go back; off the data path)
         self.kv_cache_allocated = False
@@ -1496,6 +1549,7 @@ class HydragenLlamaForCausalLM(nn.Module):
         top_ids = torch.full((B, T, top_n), -1, dtype=torch.int64, device=dev)
         top_lp = torch.full((B, T, top_n), float("-inf"), dtype=torch.float32, device=dev)
         V = self.lm_head.weight.shape[0]
+        fp8_head = isinstance(self.lm_head, Fp8Linear)  # quantize_weights(skip=()): the module's own routes, block by block
 
         G = self.score_gemm_rows
 
@@ -1517,10 +1571,13 @@ class HydragenLlamaForCausalLM(nn.Module):
             h = torch.cat([h, h.new_zeros(((-r) % G, h.shape[1]))]) if r % G else h
             out = h.new_empty((h.shape[0], V))
             for k in range(0, h.shape[0], G):
-                torch.mm(h[k : k + G], self.lm_head.weight.t(), out=out[k : k + G])
+                if fp8_head:
+                    out[k : k + G] = self.lm_head(h[k : k + G])
+                else:
+                    torch.mm(h[k : k + G], self.lm_head.weight.t(), out=out[k : k + G])
             return out[:r]
 
-        run(hb, hj, head, self.lm_head.weight.element_size())
+        run(hb, hj, head, hidden.element_size() if fp8_head else self.lm_head.weight.element_size())
         sb_, sj = (live & (pos == 0)).nonzero(as_tuple=True)
         if sb_.numel():
             sh = shared_logits[:, -1]

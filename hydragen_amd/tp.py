@@ -124,6 +124,14 @@ def _apply_tp_attn(attn, rank: int, world_size: int) -> None:
     attn.tp_reduce = True
 
 
+def _refuse_quantized(model, what: str) -> None:
+    from .weight_quant import Fp8Linear
+
+    if any(isinstance(m, Fp8Linear) for m in model.modules()):
+        raise RuntimeError(f"{what} on a model with fp8 weights: the scales are per output channel of the weights as they were when "
+                           "quantize_weights() ran -- shard first (apply_tp / from_pretrained_tp), then quantize each rank's shard")
+
+
 def apply_tp(model, rank: Optional[int] = None, world_size: Optional[int] = None) -> None:
     """Shard a `HydragenLlamaModel` (or the `.model` of a `HydragenLlamaForCausalLM`) in place for this rank
     (tp.py:115-132).  The config is overwritten BEFORE `setup_caches`, so every rank allocates caches for its own
@@ -131,6 +139,7 @@ def apply_tp(model, rank: Optional[int] = None, world_size: Optional[int] = None
     rank = get_rank() if rank is None else rank
     world_size = get_world_size() if world_size is None else world_size
     model = getattr(model, "model", model)
+    _refuse_quantized(model, "apply_tp")
     if world_size == 1:
         return
     c = model.config
@@ -147,6 +156,7 @@ def make_tp_files(model, outdir: Union[Path, str], num_splits: int = 8) -> None:
     """make_tp_files.py:12-38: one `{rank}.pt` state dict per rank, holding that rank's shard of every
     parallel layer and a full copy of the replicated ones (+ `config.json`, the unsharded architecture,
     because there is no model hub to read it from offline)."""
+    _refuse_quantized(model, "make_tp_files")
     outdir = Path(outdir)
     outdir.mkdir(exist_ok=True, parents=True)
     (outdir / "config.json").write_text(json.dumps(asdict(model.config)))

@@ -48,7 +48,7 @@ extern "C" {
 
 /* 0.5.0 also carries the fp8 unique-cache entry points (hyd_kv_quant, hyd_*_kvq, hyd_kv_quant_supported) and the filtered
  * sampler (hyd_sample_filter_params, hyd_sample_tokens_filtered), the scoring entry point (hyd_token_logprob_params,
- * hyd_token_logprobs) and the penalised sampler (hyd_sample_penalty_params, hyd_sample_tokens_penalized, hyd_token_bitmap_build) and the stop-condition entry point (hyd_stop_params, hyd_stop_update) and the unique-to-shared K/V copy (hyd_kv_promote_params, hyd_kv_promote) and the path gather of a fork with merged levels (hyd_kv_gather_params, hyd_kv_gather_paths) and the fp8 scale calibration (hyd_kv_absmax_params, hyd_kv_absmax, hyd_kv_scales_params, hyd_kv_scales_from_absmax): they are new symbols and new structs only -- no existing struct, entry point or result changed -- so a caller built against 0.5.0 without them is
+ * hyd_token_logprobs) and the penalised sampler (hyd_sample_penalty_params, hyd_sample_tokens_penalized, hyd_token_bitmap_build) and the stop-condition entry point (hyd_stop_params, hyd_stop_update) and the unique-to-shared K/V copy (hyd_kv_promote_params, hyd_kv_promote) and the path gather of a fork with merged levels (hyd_kv_gather_params, hyd_kv_gather_paths) and the fp8 scale calibration (hyd_kv_absmax_params, hyd_kv_absmax, hyd_kv_scales_params, hyd_kv_scales_from_absmax) and the fp8 linear-layer weights (hyd_linear_w8_params, hyd_linear_w8, hyd_linear_w8_workspace_bytes, hyd_weight_widen_params, hyd_weight_widen): they are new symbols and new structs only -- no existing struct, entry point or result changed -- so a caller built against 0.5.0 without them is
  * unaffected and the version stays 500. */
 #define HYD_VERSION 500 /* 0.5.0: hyd_suffix_params.seq_order (schedule hint for ragged lengths); 0.4.0: hyd_add_rmsnorm, hyd_swiglu, hyd_sample_tokens (model-shell glue); 0.3.0: two-stream phases + hyd_decode_params.shared_max_workgroups, hyd_decode_two_stream_ok; 0.2.2: hyd_allreduce_params.timeout_log2_polls; 0.2.1: softmax_scale; 0.2.0: hyd_decode_params.phase, hyd_rope_params.max_pos, hyd_allreduce_* */
 #define HYD_MAX_LEVELS 8
@@ -981,6 +981,51 @@ typedef struct hyd_kv_scales_params {
 
 HYD_API int hyd_kv_absmax(const hyd_kv_absmax_params* p, void* stream);
 HYD_API int hyd_kv_scales_from_absmax(const hyd_kv_scales_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * fp8 linear-layer weights (hydragen_amd/weight_quant.py is the definition): W is stored as e4m3fn codes w8 [N, K] with one
+ * fp32 scale per output channel, activations and outputs stay 16-bit.  New symbols and structs only: the version stays 500.
+ *
+ * The skinny GEMM:  y[m, n] = round16(scale[n] * sum_k x[m, k] * w8[n, k]),  fp32 accumulation on the 16-bit matrix cores (the
+ * codes are widened in registers, exactly), the scale applied to the fp32 sum, one rounding to the dtype of x (ties to even).
+ * x [M, K] and y [M, N] are row-strided views (strides in elements, multiples of 8; unit last stride; 16-byte aligned), w8 is
+ * contiguous and 16-byte aligned, K % 16 == 0; M >= 1 and N >= 1 of any size.  Shallow shapes are split along K: the partial
+ * sums go to `workspace` as fp32 and a second launch adds them in a fixed order, so a call is bitwise reproducible; the split
+ * is planned from M, N and K alone and the workspace-size query below says how many bytes it needs (0 when the plan does not
+ * split).  A row of y depends on its own row of x only.  Nothing is allocated: capture-safe.
+ * HYD_ERR_BAD_ARG: null params / x / w8 / scale / y, a pointer that is not 16-byte aligned (scale: 4), M / N / K < 1,
+ * K % 16 != 0, x_row_stride < K, y_row_stride < N, a stride that is no multiple of 8.  HYD_ERR_UNSUPPORTED: dtype other
+ * than HYD_F16 / HYD_BF16, more than 2^31 - 1 workgroups.  HYD_ERR_WORKSPACE: workspace null, misaligned or too small.
+ *
+ * The widening (the route of calls with more rows than the skinny kernel should take): out[n, k] = float(w8[n, k]) * scale[n]
+ * as an fp32 product, rounded once to dtype -- weight_quant.dequantize_weight bit for bit.  out: [N, K] 16-bit with a row
+ * stride (elements, a multiple of 8, >= K), 16-byte aligned; K % 8 == 0.  The refusals are those of the GEMM where they apply.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct hyd_linear_w8_params {
+    const void* x;           /* [M, K] dtype, row m at x + m * x_row_stride                                   */
+    const void* w8;          /* [N, K] e4m3fn, contiguous                                                     */
+    const float* scale;      /* [N]                                                                           */
+    void* y;                 /* [M, N] dtype, row m at y + m * y_row_stride                                   */
+    void* workspace;         /* fp32 partial sums of a split plan; may be NULL when the query answers 0       */
+    size_t workspace_bytes;
+    int64_t x_row_stride, y_row_stride;
+    int32_t M, N, K;
+    int32_t dtype;           /* HYD_F16 | HYD_BF16                                                            */
+} hyd_linear_w8_params;
+
+typedef struct hyd_weight_widen_params {
+    const void* w8;          /* [N, K] e4m3fn, contiguous                                                     */
+    const float* scale;      /* [N]                                                                           */
+    void* out;               /* [N, K] dtype, row n at out + n * out_row_stride                               */
+    int64_t out_row_stride;
+    int32_t N, K;
+    int32_t dtype;           /* HYD_F16 | HYD_BF16                                                            */
+    int32_t reserved;
+} hyd_weight_widen_params;
+
+HYD_API size_t hyd_linear_w8_workspace_bytes(int32_t M, int32_t N, int32_t K);
+HYD_API int hyd_linear_w8(const hyd_linear_w8_params* p, void* stream);
+HYD_API int hyd_weight_widen(const hyd_weight_widen_params* p, void* stream);
 
 HYD_API int hyd_version(void);
 HYD_API const char* hyd_last_error_string(void);
