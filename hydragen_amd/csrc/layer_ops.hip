@@ -10,7 +10,7 @@
 //     torch.multinomial, ~12 launches over the [B, vocab] fp32 matrix per decode step) by the Gumbel-max identity
 //     argmax_v(logits_v / T + g_v), g_v = -ln(-ln u_v): one pass over the 16-bit logits, counter-based Philox4x32-10
 //     noise keyed by (seed, call offset, row, column) -- reproducible for a seed, independent of the launch geometry.
-#include "hyd_kernels.h"
+#include "vocab_row.h"  // philox10, gumbel_noise: the noise of every sampling draw
 
 namespace hyd {
 
@@ -125,34 +125,6 @@ __global__ __launch_bounds__(256) void swiglu_kernel(const SwigluArgs a) {
     *reinterpret_cast<u32x4*>(static_cast<uint16_t*>(a.out) + row * a.o_rs + 8 * c) = pack8<T>(o);
 }
 
-namespace {
-
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t lo0 = 0xD2511F53u * c[0], hi0 = __umulhi(0xD2511F53u, c[0]);
-        const uint32_t lo1 = 0xCD9E8D57u * c[2], hi1 = __umulhi(0xCD9E8D57u, c[2]);
-        c[0] = hi1 ^ c[1] ^ k0;
-        c[1] = lo1;
-        c[2] = hi0 ^ c[3] ^ k1;
-        c[3] = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
-// standard Gumbel noise from 23 random bits: u = (k + 1/2) 2^-23 for k in [0, 2^23), strictly inside (0, 1) and exact in
-// fp32 (24 significant bits).  (The former 24-bit form (k 2^-24 + 2^-25) rounded to exactly 1.0 for k = 2^24 - 1 -- a tie
-// that rounds to even -- where -ln u = 0 and the noise is +inf: that column won the argmax whatever its logit, about two
-// tokens per decode step at a batch of 1024 and a vocabulary of 32000.)  g = -ln(-ln u), finite for every k -- also on
-// hardware whose approximate log2 returns 0 for the largest u (1 - 2^-24, true -ln u = 2^-24): -ln u is held at >= 2^-25.
-__device__ __forceinline__ float gumbel(uint32_t bits) {
-    const float u = ((float)(bits >> 9) + 0.5f) * 0x1p-23f;
-    const float e = fmaxf(-kLn2 * fast_log2(u), 0x1p-25f);
-    return -kLn2 * fast_log2(e);
-}
-
-}  // namespace
-
 // One workgroup of 256 threads per row; thread t walks the 8-element chunks t, t + 256, ...; ties go to the lowest index.
 template <int DT>
 __global__ __launch_bounds__(256) void sample_kernel(const SampleArgs a) {
@@ -184,9 +156,9 @@ __global__ __launch_bounds__(256) void sample_kernel(const SampleArgs a) {
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 uint32_t ctr[4] = {(uint32_t)(2 * c + k), (uint32_t)row, (uint32_t)a.offset, (uint32_t)(a.offset >> 32)};
-                philox4x32_10(ctr, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+                philox10(ctr, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
 #pragma unroll
-                for (int i = 0; i < 4; ++i) f[4 * k + i] = f[4 * k + i] * a.inv_temperature + gumbel(ctr[i]);
+                for (int i = 0; i < 4; ++i) f[4 * k + i] = f[4 * k + i] * a.inv_temperature + gumbel_noise(ctr[i]);
             }
         }
 #pragma unroll

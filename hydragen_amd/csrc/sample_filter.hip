@@ -16,194 +16,11 @@
 // Mapping: 1024 threads; thread t owns the 8-element chunks t + 1024 j (16-byte loads when the row allows).  Every pass
 // re-reads the row: it is 64-512 KB, so the passes after the first hit L2 / MALL.  (Keeping 16-bit rows in VGPRs across
 // the passes -- up to 16 chunks per thread -- spilled to scratch at 4 and 8 chunks with this hipcc: DESIGN.md 4.11.)
-// NOTE: sample_select.h holds a COPY of everything below (helpers and kernel body, the body as a template over a logit map) for
-// sample_penalty.hip; this file's assembly is pinned by tests/test_scoring.py, so the text is not shared.  A change to the
-// sampling rules here must be made there too (tests/test_sampling_penalties_gpu.py compares the two bit for bit).
-#include "hyd_kernels.h"
+// The helpers are vocab_row.h's (through sample_select.h); the kernel body below is also sample_select.h's sample_row, there as a
+// template over a logit map: a change to the passes is made in both (why: sample_select.h's header comment).
+#include "sample_select.h"
 
 namespace hyd {
-
-namespace {
-
-constexpr int kFT = 1024;  // threads per row
-constexpr int kFW = kFT / 64;
-constexpr float kBinScale = 8.0f;     // first-level bins per unit of (max - l)
-constexpr float kBinLast = 31.875f;   // 255 / kBinScale: from here on, the last bin
-constexpr uint64_t kOne = 1ull << 40; // the max's mass
-
-__device__ __forceinline__ void philox10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {  // = layer_ops.hip philox4x32_10
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t lo0 = 0xD2511F53u * c[0], hi0 = __umulhi(0xD2511F53u, c[0]);
-        const uint32_t lo1 = 0xCD9E8D57u * c[2], hi1 = __umulhi(0xCD9E8D57u, c[2]);
-        c[0] = hi1 ^ c[1] ^ k0;
-        c[1] = lo1;
-        c[2] = hi0 ^ c[3] ^ k1;
-        c[3] = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
-__device__ __forceinline__ float gumbel_noise(uint32_t bits) {  // = layer_ops.hip gumbel
-    const float u = ((float)(bits >> 9) + 0.5f) * 0x1p-23f;
-    const float e = fmaxf(-kLn2 * fast_log2(u), 0x1p-25f);
-    return -kLn2 * fast_log2(e);
-}
-
-// order-preserving unsigned keys of the logit's bits; -0 is folded onto +0 (equal values, equal keys)
-__device__ __forceinline__ uint32_t key16(uint32_t h) {
-    h = h == 0x8000u ? 0u : h;
-    return (h & 0x8000u) ? (~h & 0xffffu) : (h | 0x8000u);
-}
-__device__ __forceinline__ uint32_t key32(uint32_t b) {
-    b = b == 0x80000000u ? 0u : b;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ bool valid(float f) { return f == f && f != -INFINITY; }
-
-template <int DT>
-__device__ __forceinline__ float h2f(uint32_t h) {
-    return DT == HYD_F16 ? Traits<F16>::lo(h) : Traits<BF16>::lo(h);
-}
-
-// one 8-element chunk of 16-bit logits as 4 packed words (positions past n hold -inf)
-template <int DT>
-__device__ __forceinline__ u32x4 load16(const uint16_t* row, int c, int n, int vec) {
-    if (vec && 8 * c + 8 <= n) return reinterpret_cast<const u32x4*>(row)[c];
-    const uint32_t pad = DT == HYD_F16 ? 0xfc00u : 0xff80u;
-    uint32_t h[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) h[i] = 8 * c + i < n ? row[8 * c + i] : pad;
-    return u32x4{h[0] | h[1] << 16, h[2] | h[3] << 16, h[4] | h[5] << 16, h[6] | h[7] << 16};
-}
-template <int DT>
-__device__ __forceinline__ void decode16(const u32x4& u, float (&f)[8], uint32_t (&k)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint32_t lo = u[i] & 0xffffu, hi = u[i] >> 16;
-        f[2 * i] = h2f<DT>(lo);
-        f[2 * i + 1] = h2f<DT>(hi);
-        k[2 * i] = key16(lo);
-        k[2 * i + 1] = key16(hi);
-    }
-}
-__device__ __forceinline__ void load32(const float* row, int c, int n, int vec, float (&f)[8], uint32_t (&k)[8]) {
-    uint32_t b[8];
-    if (vec && 8 * c + 8 <= n) {
-        const u32x4 u0 = reinterpret_cast<const u32x4*>(row)[2 * c], u1 = reinterpret_cast<const u32x4*>(row)[2 * c + 1];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            b[i] = u0[i];
-            b[4 + i] = u1[i];
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) b[i] = 8 * c + i < n ? __builtin_bit_cast(uint32_t, row[8 * c + i]) : 0xff800000u;
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        f[i] = __builtin_bit_cast(float, b[i]);
-        k[i] = key32(b[i]);
-    }
-}
-
-// Calls fn(chunk, f[8], key[8]) for every chunk this thread owns, read from memory (L2 / MALL after the first pass).
-template <int DT, typename F>
-__device__ __forceinline__ void visit(const void* row, int n, int vec, F&& fn) {
-    const int nchunk = (n + 7) >> 3;
-    for (int c = threadIdx.x; c < nchunk; c += kFT) {
-        float f[8];
-        uint32_t k[8];
-        if constexpr (DT == HYD_F32) load32(static_cast<const float*>(row), c, n, vec, f, k);
-        else decode16<DT>(load16<DT>(static_cast<const uint16_t*>(row), c, n, vec), f, k);
-        fn(c, f, k);
-    }
-}
-
-__device__ __forceinline__ float block_max(float x, float* red) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x = fmaxf(x, __shfl_xor(x, off));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-    __syncthreads();
-    x = red[0];
-#pragma unroll
-    for (int w = 1; w < kFW; ++w) x = fmaxf(x, red[w]);
-    __syncthreads();
-    return x;
-}
-__device__ __forceinline__ uint64_t block_sum(uint64_t x, uint64_t* red) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-    __syncthreads();
-    x = 0;
-#pragma unroll
-    for (int w = 0; w < kFW; ++w) x += red[w];
-    __syncthreads();
-    return x;
-}
-
-// distance-to-max bin of the first select level; monotone: a larger logit never lands in a later bin
-__device__ __forceinline__ int bin0(float f, float m) {
-    const float d = f == m ? 0.f : m - f;
-    return d < kBinLast ? (int)(d * kBinScale) : 255;
-}
-__device__ __forceinline__ uint64_t mass(float f, float m) {
-    return f == m ? kOne : (uint64_t)(fast_exp2((f - m) * kLog2e) * 0x1p40f);
-}
-
-struct Pick {
-    int bin;
-    uint64_t above;  // weight of the bins before `bin`, cum included
-};
-
-// First bin b (bin 0 = the largest logits) with cum + hist[0..b] >= target, by the first wave (4 bins per lane, one scan
-// over the lanes); fill_last: hist[255] is not counted, it is `total` minus the other 255 bins.  Every thread gets it.
-__device__ Pick pick_bin(const uint64_t* hist, uint64_t cum, uint64_t target, bool fill_last, uint64_t total, Pick* shared_pick) {
-    if (threadIdx.x < 64) {
-        const int lane = threadIdx.x;
-        uint64_t h[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) h[i] = hist[4 * lane + i];
-        if (fill_last && lane == 63) h[3] = 0;
-        uint64_t s = h[0] + h[1] + h[2] + h[3];
-        uint64_t incl = s;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint64_t t = __shfl_up(incl, off);
-            if (lane >= off) incl += t;
-        }
-        if (fill_last) {
-            const uint64_t all = __shfl(incl, 63);
-            if (lane == 63) {
-                h[3] = total - all;
-                incl += h[3];
-            }
-        }
-        const uint64_t cross = __ballot(cum + incl >= target);
-        const int first = cross ? __ffsll((long long)cross) - 1 : 63;
-        if (lane == first) {
-            uint64_t c = cum + incl - (h[0] + h[1] + h[2] + h[3]);
-            int b = 4 * lane + 3;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (c + h[i] >= target) {
-                    b = 4 * lane + i;
-                    break;
-                }
-                if (i < 3) c += h[i];
-            }
-            shared_pick->bin = b;
-            shared_pick->above = c;
-        }
-    }
-    __syncthreads();
-    const Pick p = *shared_pick;
-    __syncthreads();
-    return p;
-}
-
-}  // namespace
 
 template <int DT>
 __global__ __launch_bounds__(1024) void sample_filter_kernel(const FilterArgs a) {

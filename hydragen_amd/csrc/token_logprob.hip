@@ -16,46 +16,14 @@
 // Mapping: 1024 threads; thread t owns the 8-element chunks t + 1024 j (16-byte loads when the row allows), read kU chunks at a
 // time so that several loads are in flight.  Every pass re-reads the row (64-512 KB): the passes after the first hit L2 /
 // MALL.  N = 0 is its own instantiation: no histogram, no LDS beyond the reductions.
-#include "hyd_kernels.h"
+#include "vocab_row.h"  // keys, masses, bins, block_sum, pick_bin, logprob_of: the samplers' own
 
 namespace hyd {
 
 namespace {
 
-constexpr int kT = 1024;  // threads per row
-constexpr int kW = kT / 64;
-constexpr int kU = 4;     // chunks loaded per thread before any is used
-constexpr int kCap = 1024;              // LDS candidates of the top-N gather
-constexpr float kBinScale = 8.0f;       // = sample_filter.hip
-constexpr float kBinLast = 31.875f;
-constexpr uint64_t kOne = 1ull << 40;
-
-// = sample_filter.hip: order-preserving keys (-0 folded onto +0), validity, 16-bit decode, fixed-point mass, bins
-__device__ __forceinline__ uint32_t key16(uint32_t h) {
-    h = h == 0x8000u ? 0u : h;
-    return (h & 0x8000u) ? (~h & 0xffffu) : (h | 0x8000u);
-}
-__device__ __forceinline__ uint32_t key32(uint32_t b) {
-    b = b == 0x80000000u ? 0u : b;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ bool valid(float f) { return f == f && f != -INFINITY; }
-template <int DT>
-__device__ __forceinline__ float h2f(uint32_t h) {
-    return DT == HYD_F16 ? Traits<F16>::lo(h) : Traits<BF16>::lo(h);
-}
-__device__ __forceinline__ uint64_t mass(float f, float m) {
-    return f == m ? kOne : (uint64_t)(fast_exp2((f - m) * kLog2e) * 0x1p40f);
-}
-__device__ __forceinline__ int bin0(float f, float m) {
-    const float d = f == m ? 0.f : m - f;
-    return d < kBinLast ? (int)(d * kBinScale) : 255;
-}
-// l - m - ln(total 2^-40): sample_filter_kernel's closing expression
-__device__ __forceinline__ float logprob_of(float l, float m, uint64_t total) {
-    const double d = l == m ? 0.0 : (double)l - (double)m;
-    return (float)(d - (log((double)total) - 40.0 * 0.6931471805599453));
-}
+constexpr int kU = 4;       // chunks loaded per thread before any is used
+constexpr int kCap = 1024;  // LDS candidates of the top-N gather
 
 // Raw words of one 8-element chunk: 16-bit logits as 4 packed words (w[4..7] unused), fp32 as 8 words; past n: -inf.
 template <int DT>
@@ -113,36 +81,25 @@ __device__ __forceinline__ void decode_chunk(const uint32_t (&w)[8], float (&f)[
 
 // Calls fn(first index, f[8], key[8]) for every chunk this thread owns, in increasing index order, kU loads ahead.
 template <int DT, typename F>
-__device__ __forceinline__ void visit(const void* row, int n, int vec, F&& fn) {
+__device__ __forceinline__ void visit_ahead(const void* row, int n, int vec, F&& fn) {
     const int nchunk = (n + 7) >> 3;
-    for (int c0 = threadIdx.x; c0 < nchunk; c0 += kU * kT) {
+    for (int c0 = threadIdx.x; c0 < nchunk; c0 += kU * kFT) {
         uint32_t w[kU][8];
 #pragma unroll
         for (int u = 0; u < kU; ++u)
-            if (c0 + u * kT < nchunk) load_chunk<DT>(row, c0 + u * kT, n, vec, w[u]);
+            if (c0 + u * kFT < nchunk) load_chunk<DT>(row, c0 + u * kFT, n, vec, w[u]);
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
-            if (c0 + u * kT < nchunk) {
+            if (c0 + u * kFT < nchunk) {
                 float f[8];
                 uint32_t k[8];
                 decode_chunk<DT>(w[u], f, k);
-                fn(8 * (c0 + u * kT), f, k);
+                fn(8 * (c0 + u * kFT), f, k);
             }
         }
     }
 }
 
-__device__ __forceinline__ uint64_t block_sum(uint64_t x, uint64_t* red) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-    __syncthreads();
-    x = 0;
-#pragma unroll
-    for (int w = 0; w < kW; ++w) x += red[w];
-    __syncthreads();
-    return x;
-}
 // (value, index) with the larger value, the lower index on equal values (valid values only: no NaN reaches here)
 __device__ __forceinline__ void better(float& v, int& i, float ov, int oi) {
     if (ov > v || (ov == v && oi < i)) {
@@ -151,69 +108,14 @@ __device__ __forceinline__ void better(float& v, int& i, float ov, int oi) {
     }
 }
 
-struct Pick {
-    int bin;
-    uint64_t above;  // weight of the bins before `bin`, cum included
-};
-
-// = sample_filter.hip pick_bin: first bin b with cum + hist[0..b] >= target (fill_last: hist[255] = total - the other bins);
-// also returns hist[b] (`at`).  Every thread gets it.
-__device__ Pick pick_bin(const uint64_t* hist, uint64_t cum, uint64_t target, bool fill_last, uint64_t total, Pick* shared_pick,
-                         uint64_t* at) {
-    if (threadIdx.x < 64) {
-        const int lane = threadIdx.x;
-        uint64_t h[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) h[i] = hist[4 * lane + i];
-        if (fill_last && lane == 63) h[3] = 0;
-        uint64_t s = h[0] + h[1] + h[2] + h[3];
-        uint64_t incl = s;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint64_t t = __shfl_up(incl, off);
-            if (lane >= off) incl += t;
-        }
-        if (fill_last) {
-            const uint64_t all = __shfl(incl, 63);
-            if (lane == 63) {
-                h[3] = total - all;
-                incl += h[3];
-            }
-        }
-        const uint64_t cross = __ballot(cum + incl >= target);
-        const int first = cross ? __ffsll((long long)cross) - 1 : 63;
-        if (lane == first) {
-            uint64_t c = cum + incl - (h[0] + h[1] + h[2] + h[3]);
-            int b = 4 * lane + 3;
-            uint64_t hb = h[3];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (c + h[i] >= target) {
-                    b = 4 * lane + i;
-                    hb = h[i];
-                    break;
-                }
-                if (i < 3) c += h[i];
-            }
-            shared_pick->bin = b;
-            shared_pick->above = c;
-            *at = hb;
-        }
-    }
-    __syncthreads();
-    const Pick p = *shared_pick;
-    __syncthreads();
-    return p;
-}
-
 }  // namespace
 
 template <int DT, bool TOPN>
 __global__ __launch_bounds__(1024) void token_logprob_kernel(const TokenLogprobArgs a) {
     constexpr int KB = DT == HYD_F32 ? 32 : 16;  // key bits
-    __shared__ uint64_t redu[kW];
-    __shared__ float bestv[kW];
-    __shared__ int besti_w[kW];
+    __shared__ uint64_t redu[kFW];
+    __shared__ float bestv[kFW];
+    __shared__ int besti_w[kFW];
     const int64_t row = a.row0 + blockIdx.x;
     const int n = a.n;
     const int esz = DT == HYD_F32 ? 4 : 2;
@@ -223,7 +125,7 @@ __global__ __launch_bounds__(1024) void token_logprob_kernel(const TokenLogprobA
     float best = -INFINITY;
     int besti = 0x7fffffff;
     uint64_t nvalid = 0;
-    visit<DT>(rowp, n, a.vec_ok, [&](int i0, const float (&f)[8], const uint32_t (&)[8]) {
+    visit_ahead<DT>(rowp, n, a.vec_ok, [&](int i0, const float (&f)[8], const uint32_t (&)[8]) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             if (valid(f[i])) {
@@ -245,7 +147,7 @@ __global__ __launch_bounds__(1024) void token_logprob_kernel(const TokenLogprobA
     best = bestv[0];
     besti = besti_w[0];
 #pragma unroll
-    for (int w = 1; w < kW; ++w) better(best, besti, bestv[w], besti_w[w]);
+    for (int w = 1; w < kFW; ++w) better(best, besti, bestv[w], besti_w[w]);
     nvalid = block_sum(nvalid, redu);  // (its barriers also retire bestv / besti_w)
     const float m = best;
     const int64_t t = a.targets[row];
@@ -269,11 +171,11 @@ __global__ __launch_bounds__(1024) void token_logprob_kernel(const TokenLogprobA
     __shared__ uint64_t pick_at;
     const bool select = TOPN && nvalid > (uint64_t)N;  // fewer valid logits than N: every valid logit is a candidate
     if (select) {
-        for (int i = threadIdx.x; i < 256; i += kT) hist[i] = 0;
+        for (int i = threadIdx.x; i < 256; i += kFT) hist[i] = 0;
         __syncthreads();
     }
     uint64_t total = 0;
-    visit<DT>(rowp, n, a.vec_ok, [&](int, const float (&f)[8], const uint32_t (&)[8]) {
+    visit_ahead<DT>(rowp, n, a.vec_ok, [&](int, const float (&f)[8], const uint32_t (&)[8]) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             if (valid(f[i])) {
@@ -308,10 +210,10 @@ __global__ __launch_bounds__(1024) void token_logprob_kernel(const TokenLogprobA
                 uint32_t prefix = 0;
 #pragma unroll
                 for (int lvl = 0; lvl < KB / 8; ++lvl) {
-                    for (int i = threadIdx.x; i < 256; i += kT) hist[i] = 0;
+                    for (int i = threadIdx.x; i < 256; i += kFT) hist[i] = 0;
                     __syncthreads();
                     const int sh = KB - 8 * (lvl + 1);
-                    visit<DT>(rowp, n, a.vec_ok, [&](int, const float (&f)[8], const uint32_t (&key)[8]) {
+                    visit_ahead<DT>(rowp, n, a.vec_ok, [&](int, const float (&f)[8], const uint32_t (&key)[8]) {
 #pragma unroll
                         for (int i = 0; i < 8; ++i) {
                             if (valid(f[i]) && bin0(f[i], m) == b && (lvl == 0 || (key[i] >> (sh + 8)) == prefix))
@@ -330,10 +232,10 @@ __global__ __launch_bounds__(1024) void token_logprob_kernel(const TokenLogprobA
                     uint32_t ip = 0;
 #pragma unroll
                     for (int lvl = 0; lvl < 3; ++lvl) {  // indices < 2^22 <= 2^24
-                        for (int i = threadIdx.x; i < 256; i += kT) hist[i] = 0;
+                        for (int i = threadIdx.x; i < 256; i += kFT) hist[i] = 0;
                         __syncthreads();
                         const int sh = 16 - 8 * lvl;
-                        visit<DT>(rowp, n, a.vec_ok, [&](int i0, const float (&f)[8], const uint32_t (&key)[8]) {
+                        visit_ahead<DT>(rowp, n, a.vec_ok, [&](int i0, const float (&f)[8], const uint32_t (&key)[8]) {
 #pragma unroll
                             for (int i = 0; i < 8; ++i) {
                                 const uint32_t idx = (uint32_t)(i0 + i);
@@ -358,7 +260,7 @@ __global__ __launch_bounds__(1024) void token_logprob_kernel(const TokenLogprobA
         __shared__ int ccount;
         if (threadIdx.x == 0) ccount = 0;
         __syncthreads();
-        visit<DT>(rowp, n, a.vec_ok, [&](int i0, const float (&f)[8], const uint32_t (&key)[8]) {
+        visit_ahead<DT>(rowp, n, a.vec_ok, [&](int i0, const float (&f)[8], const uint32_t (&key)[8]) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 bool take = valid(f[i]);
@@ -377,7 +279,7 @@ __global__ __launch_bounds__(1024) void token_logprob_kernel(const TokenLogprobA
         });
         __syncthreads();
         const int cnt = ccount < kCap ? ccount : kCap;
-        for (int s = threadIdx.x; s < cnt; s += kT) {
+        for (int s = threadIdx.x; s < cnt; s += kFT) {
             const uint32_t ks = ckey[s];
             const int is = cidx[s];
             int rank = 0;
@@ -387,7 +289,7 @@ __global__ __launch_bounds__(1024) void token_logprob_kernel(const TokenLogprobA
                 a.top_logprobs[row * N + rank] = logprob_of(cval[s], m, total);
             }
         }
-        for (int r = cnt + (int)threadIdx.x; r < N; r += kT) {  // fewer valid logits than N
+        for (int r = cnt + (int)threadIdx.x; r < N; r += kFT) {  // fewer valid logits than N
             a.top_ids[row * N + r] = -1;
             a.top_logprobs[row * N + r] = -INFINITY;
         }
@@ -400,7 +302,7 @@ int launch_token_logprob(const TokenLogprobArgs& args, int dtype, hipStream_t s)
         TokenLogprobArgs a = args;
         a.row0 = r0;
         const int64_t rows = args.rows - r0 < kRowsPerLaunch ? args.rows - r0 : kRowsPerLaunch;
-        const dim3 grid((unsigned)rows), block(kT);
+        const dim3 grid((unsigned)rows), block(kFT);
         const bool topn = a.top_n > 0;
         if (dtype == HYD_F16) {
             if (topn) hipLaunchKernelGGL((token_logprob_kernel<HYD_F16, true>), grid, block, 0, s, a);

@@ -1,6 +1,6 @@
 // Hardware probe: how far is the samplers' Gumbel noise from its float64 definition?
-// The four sampling kernels draw argmax(l / T + g) with g = gumbel(bits) of layer_ops.hip (copied into sample_filter.hip and
-// sample_select.h), built on fast_log2 = the hardware's approximate log2.  tests/sampler_mirror.py evaluates the same noise in
+// The four sampling kernels draw argmax(l / T + g) with g = gumbel_noise(bits) of hydragen_amd/csrc/vocab_row.h (the one
+// text all of them include), built on fast_log2 = the hardware's approximate log2.  tests/sampler_mirror.py evaluates the same noise in
 // float64 on the host and compares drawn tokens; the margin below which it does not compare a row (its EPS) rests on the number
 // this program prints.  It measures the log instruction, not the samplers: one kernel evaluates the expression for every one of
 // the 2^23 values of k = bits >> 9, the host evaluates
@@ -21,7 +21,8 @@
 
 static const uint32_t kN = 1u << 23;
 
-// = layer_ops.hip gumbel / sample_filter.hip gumbel_noise (tests/test_sampler_noise.py pins the text of its first two lines)
+// = vocab_row.h gumbel_noise, restated so that this program builds alone (tests/test_sampler_noise.py pins the text of the header's
+// first two lines)
 __device__ __forceinline__ float gumbel(uint32_t bits) {
     const float u = ((float)(bits >> 9) + 0.5f) * 0x1p-23f;
     const float e = fmaxf(-hyd::kLn2 * hyd::fast_log2(u), 0x1p-25f);

@@ -2,7 +2,8 @@
 
 The four sampling launches (hyd_sample_tokens: sample_kernel in csrc/layer_ops.hip; hyd_sample_tokens_filtered: csrc/sample_filter.hip;
 hyd_sample_tokens_penalized / _constrained: sample_row in csrc/sample_select.h) draw  token = argmax_j ( l_j * (1/T) + g_j )  over the
-kept, valid columns (lowest index on ties) with Gumbel noise g from Philox4x32-10.  The suite holds them bit-equal to each other; this
+kept, valid columns (lowest index on ties) with Gumbel noise g from Philox4x32-10, all four from one text (philox10 / gumbel_noise in
+csrc/vocab_row.h).  The suite holds them bit-equal to each other; this
 module is the independent side: Philox from its published definition (checked against the Random123 known-answer vectors), the
 counter / key / word layout from the kernels' headers, the noise in float64.
 

@@ -1,6 +1,6 @@
 """-m gpu: the four sampling launches -- hyd_sample_tokens (csrc/layer_ops.hip), hyd_sample_tokens_filtered (csrc/sample_filter.hip),
-hyd_sample_tokens_penalized / hyd_sample_tokens_constrained (csrc/sample_select.h) -- against an independent host mirror of their
-noise (tests/sampler_mirror.py) and, on the adversarial rows of tests/sampling_stress_cases.py, against the float64 definition of
+hyd_sample_tokens_penalized / hyd_sample_tokens_constrained (csrc/sample_select.h), all on the row primitives of csrc/vocab_row.h --
+against an independent host mirror of their noise (tests/sampler_mirror.py) and, on the adversarial rows of tests/sampling_stress_cases.py, against the float64 definition of
 the cuts (hydragen_amd/sampling.py).  tests/test_sampling_stress.py checks without a device what these tests rest on.
 
   1. mirror draws at vocabulary size: the drawn token is the mirror's on every row whose margin exceeds EPS (derived in
