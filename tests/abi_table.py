@@ -3,12 +3,14 @@ recorded once and compared exactly (tests/test_abi_table.py against tests/golden
 
     python tests/abi_table.py --write     record the table from the library that is built in the tree
 
-The fixture is a recording of the library BEFORE a change to csrc/api.hip, not a product of the code under test: record it from
+The fixture is a recording of the library BEFORE a change to csrc/api_*.hip (the C ABI layer), not a product of the code under test: record it from
 the parent commit, commit it as data, and let the changed library answer to it.
 
-Two kinds of case.  A "query" never launches (plans, workspace sizes, support answers).  A "refusal" goes through a launch entry
+Three kinds of case.  A "query" never launches (plans, workspace sizes, support answers).  A "refusal" goes through a launch entry
 point with made-up addresses and must come back with an error before anything is enqueued: its record is the return code and the
-whole error string.  --write does not record a refusal that the library accepts (HYD_OK) or tries to launch (HYD_ERR_LAUNCH).
+whole error string.  A "noop" goes through a launch entry point as well and must come back with HYD_OK before any HIP call (an empty
+batch, an empty destination, a phase with nothing left to do): its record is the return code alone.  --write records nothing when a
+refusal is accepted (HYD_OK) or tries to launch (HYD_ERR_LAUNCH), or when a noop does not answer HYD_OK.
 """
 import ctypes as C
 import json
@@ -165,6 +167,118 @@ def stop(**kw):
     return _fill(p, kw)
 
 
+def rope_multi(**kw):
+    p = _lib.RopeMultiParams()
+    p.dtype, p.B, p.T, p.Hq, p.Hkv, p.D, p.cache_len, p.max_pos = 1, 4, 2, 8, 8, 128, 64, 128
+    p.q = p.k = p.v = p.q_out = p.k_cache = p.v_cache = p.cos = p.sin = p.position_ids = p.seq_lens = PTR
+    p.q_tok_stride = p.k_tok_stride = p.v_tok_stride = 1024
+    p.q_batch_stride = p.k_batch_stride = p.v_batch_stride = 2048
+    p.kc_head_stride = p.vc_head_stride = 128
+    p.kc_tok_stride = p.vc_tok_stride = 1024
+    p.kc_batch_stride = p.vc_batch_stride = 64 * 1024
+    p.pos_stride, p.cs_stride = 2, 128
+    return _fill(p, kw)
+
+
+def token_dfa(**kw):
+    c = _lib.TokenDfa()
+    c.allowed = c.next = c.state = PTR
+    c.allowed_stride, c.next_stride, c.n_states = 2, 64, 4   # (sample_penalty's n = 64: two bitmap words per state)
+    return _fill(c, kw)
+
+
+def draft_lookup(**kw):
+    p = _lib.DraftLookupParams()
+    p.drafts = p.n_proposed = PTR
+    p.drafts_stride, p.n_segments, p.B, p.K, p.ngram_min, p.ngram_max = 3, 2, 4, 3, 1, 3
+    for g in p.segments:   # (all of them, so that a case may raise n_segments)
+        g.ids, g.row_stride, g.len, g.div = PTR, 16, 16, 1
+    return _fill(p, kw)
+
+
+def dfa_forced(**kw):
+    p = _lib.DfaForcedParams()
+    p.allowed = p.forced = PTR
+    p.allowed_stride, p.n_states, p.n = 2, 4, 64
+    return _fill(p, kw)
+
+
+def draft_constrain(**kw):
+    p = _lib.DraftConstrainParams()
+    p.state = p.fed = p.forced = p.next = p.step_state = p.n_forced = PTR
+    p.fed_stride, p.next_stride, p.B, p.K, p.n_states, p.n = 4, 64, 4, 3, 4, 64
+    return _fill(p, kw)
+
+
+def draft_accept(**kw):
+    p = _lib.DraftAcceptParams()
+    p.fed = p.sampled = p.out = p.length = p.reason = p.stop_index = p.accepted = p.live = p.start_pos = p.feed = p.next_pos = PTR
+    p.out_stride, p.rows, p.T, p.max_new_tokens = 8, 4, 4, 8
+    return _fill(p, kw)
+
+
+def _kv_unique(p, kw):
+    """The unique segment of hyd_kv_promote / hyd_kv_gather_paths: the fields the two blocks share by name."""
+    p.k_src = p.v_src = p.k_dst = p.v_dst = p.rows = p.lens = PTR
+    p.k_head_stride = p.v_head_stride = 128
+    p.k_tok_stride = p.v_tok_stride = 1024
+    p.k_batch_stride = p.v_batch_stride = 64 * 1024
+    p.src_dtype, p.dst_dtype, p.n, p.B, p.src_rows, p.Hkv, p.d_src, p.d_dst, p.capacity = 1, 1, 4, 4, 64, 8, 128, 128, 256
+    return _fill(p, kw)
+
+
+def kv_promote(**kw):
+    p = _lib.KvPromoteParams()
+    p.cu = PTR
+    return _kv_unique(p, kw)
+
+
+def kv_gather(**kw):
+    p = _lib.KvGatherParams()
+    p.cu_dst, p.n_levels = PTR, 2
+    for j in range(_lib.HYD_MAX_LEVELS):   # (all of them, so that a case may raise n_levels)
+        p.level_k[j] = p.level_v[j] = p.level_cu[j] = PTR
+        p.level_s[j], p.level_cap[j], p.level_div[j] = 1, 64, 4
+    return _kv_unique(p, kw)
+
+
+def kv_absmax(**kw):
+    p = _lib.KvAbsmaxParams()
+    p.k = p.v = p.amax = PTR
+    p.k_head_stride = p.v_head_stride = 128
+    p.k_row_stride = p.v_row_stride = 1024
+    p.k_outer_stride = p.v_outer_stride = 64 * 1024
+    p.dtype, p.Hkv, p.d, p.n_outer, p.n_rows = 1, 8, 128, 4, 64
+    return _fill(p, kw)
+
+
+def kv_scales(**kw):
+    p = _lib.KvScalesParams()
+    p.amax = p.k_scale = p.v_scale = PTR
+    p.Hkv, p.c = 8, 1.0 / 448.0
+    return _fill(p, kw)
+
+
+W8_SPLIT = dict(M=4, N=64, K=4096)   # a shape whose plan splits K: hyd_linear_w8_workspace_bytes(4, 64, 4096) > 0
+
+
+def linear_w8(**kw):
+    p = _lib.LinearW8Params()
+    p.x = p.w8 = p.scale = p.y = p.workspace = PTR
+    p.workspace_bytes = 1 << 40
+    p.M, p.N, p.K, p.dtype = 4, 64, 256, 1
+    _fill(p, {k: kw.pop(k) for k in list(kw) if k in ("M", "N", "K")})
+    p.x_row_stride, p.y_row_stride = p.K, p.N
+    return _fill(p, kw)
+
+
+def weight_widen(**kw):
+    p = _lib.WeightWidenParams()
+    p.w8 = p.scale = p.out = PTR
+    p.out_row_stride, p.N, p.K, p.dtype = 256, 64, 256, 1
+    return _fill(p, kw)
+
+
 # ---- runners: one per kind of record ----------------------------------------------------------------------------------------
 def _err(lib):
     return lib.hyd_last_error_string().decode()
@@ -220,6 +334,23 @@ def _q_block(lib, kw):
     return {"bytes": lib.hyd_allreduce_block_bytes(kw["world"], kw["max_bytes"])}
 
 
+def _q_narrow(lib, kw):
+    """hyd_narrow_kv_supported as hydragen_amd/flash.py asks it: contiguous [B, kv_len, Hkv, kv_dim] caches."""
+    kw = dict(kw)
+    if kw.pop("null", False):
+        return {"supported": lib.hyd_narrow_kv_supported(None)}
+    s = suffix(**kw)
+    d = s.kv_dim or s.D
+    s.k_head_stride = s.v_head_stride = d
+    s.k_tok_stride = s.v_tok_stride = s.Hkv * d
+    s.k_batch_stride = s.v_batch_stride = max(s.kv_len, 1) * s.Hkv * d
+    return {"supported": lib.hyd_narrow_kv_supported(C.byref(s))}
+
+
+def _q_w8_workspace(lib, kw):
+    return {"bytes": lib.hyd_linear_w8_workspace_bytes(kw["M"], kw["N"], kw["K"])}
+
+
 def _refusal(lib, rc):
     return {"rc": rc, "error": _err(lib) if rc else ""}
 
@@ -266,8 +397,24 @@ def _r_allreduce(lib, kw):
     return _refusal(lib, lib.hyd_allreduce_sum(C.byref(p), None))
 
 
+def _r_constrained(lib, kw):
+    """hyd_sample_tokens_constrained: "c.<field>" breaks the hyd_token_dfa, no_dfa passes none (the penalised sampler's call)."""
+    kw = dict(kw)
+    null, no_dfa = kw.pop("null", False), kw.pop("no_dfa", False)
+    c = token_dfa(**{k[2:]: kw.pop(k) for k in list(kw) if k.startswith("c.")})
+    p = None if null else C.byref(sample_penalty(**kw))
+    return _refusal(lib, lib.hyd_sample_tokens_constrained(p, None if no_dfa else C.byref(c), None))
+
+
+def _r_accept_states(lib, kw):
+    kw = dict(kw)
+    null, after, state = kw.pop("null", False), kw.pop("step_state_after", PTR), kw.pop("state", PTR)
+    p = None if null else C.byref(draft_accept(**kw))
+    return _refusal(lib, lib.hyd_draft_accept_states(p, after, state, None))
+
+
 QUERIES = {"prefix": _q_prefix, "decode": _q_decode, "workspace": _q_workspace, "kv_quant": _q_kvq, "null": _q_null,
-           "allreduce_block": _q_block}
+           "allreduce_block": _q_block, "narrow_kv": _q_narrow, "linear_w8_workspace": _q_w8_workspace}
 REFUSALS = {
     "hyd_prefix_attn_fwd": _params_runner("hyd_prefix_attn_fwd", lambda **kw: prefix(ptrs=True, **kw)),
     "hyd_suffix_attn_fwd": _params_runner("hyd_suffix_attn_fwd", suffix),
@@ -286,10 +433,24 @@ REFUSALS = {
     "hyd_stop_update": _params_runner("hyd_stop_update", stop),
     "hyd_combine_lse": _r_combine,
     "hyd_allreduce_sum": _r_allreduce,
+    "hyd_suffix_attn_causal_fwd": _params_runner("hyd_suffix_attn_causal_fwd", lambda **kw: suffix(**{"nq": 2, **kw})),
+    "hyd_rope_append_multi": _params_runner("hyd_rope_append_multi", rope_multi),
+    "hyd_sample_tokens_constrained": _r_constrained,
+    "hyd_draft_lookup": _params_runner("hyd_draft_lookup", draft_lookup),
+    "hyd_dfa_forced_tokens": _params_runner("hyd_dfa_forced_tokens", dfa_forced),
+    "hyd_draft_constrain": _params_runner("hyd_draft_constrain", draft_constrain),
+    "hyd_draft_accept": _params_runner("hyd_draft_accept", draft_accept),
+    "hyd_draft_accept_states": _r_accept_states,
+    "hyd_kv_promote": _params_runner("hyd_kv_promote", kv_promote),
+    "hyd_kv_gather_paths": _params_runner("hyd_kv_gather_paths", kv_gather),
+    "hyd_kv_absmax": _params_runner("hyd_kv_absmax", kv_absmax),
+    "hyd_kv_scales_from_absmax": _params_runner("hyd_kv_scales_from_absmax", kv_scales),
+    "hyd_linear_w8": _params_runner("hyd_linear_w8", linear_w8),
+    "hyd_weight_widen": _params_runner("hyd_weight_widen", weight_widen),
 }
 
 # ---- the cases: (kind, entry, arguments) ------------------------------------------------------------------------------------
-_Q, _R = [], []
+_Q, _R, _N = [], [], []
 
 
 def q(entry, **kw):
@@ -298,6 +459,25 @@ def q(entry, **kw):
 
 def r(entry, **kw):
     _R.append((entry, kw))
+
+
+def noop(entry, **kw):
+    """A call that returns HYD_OK before any HIP call (through the entry's refusal runner); its record is the return code alone."""
+    _N.append((entry, kw))
+
+
+def chain(entry, steps, pairs=True, **base):
+    """steps: one breaking dict per check, in the order of the checks; a list of dicts where one check (one message) reads several
+    fields.  Every dict alone, and every two neighbouring checks together: the earlier one answers, so swapping two adjacent checks
+    changes a record.  (Neighbours that can only be broken through the same field are not paired.)"""
+    steps = [s if isinstance(s, list) else [s] for s in steps]
+    for i, alts in enumerate(steps):
+        for s in alts:
+            r(entry, **base, **s)
+        if pairs and i + 1 < len(steps):
+            both = [(a, b) for a in reversed(alts) for b in steps[i + 1] if not set(a) & set(b)]
+            if both:
+                r(entry, **base, **both[0][0], **both[0][1])
 
 
 # the prefix planner (hyd_prefix_plan + hyd_prefix_workspace_bytes)
@@ -628,13 +808,215 @@ for bad in (dict(no_blocks=True), dict(world=0), dict(world=9), dict(rank=-1), d
     r("hyd_allreduce_sum", **bad)
 
 
+def _ptrs16(*names):
+    """null, then aligned to the element but not to 16 bytes, for each pointer in turn"""
+    return [{n: v} for n in names for v in (None, MIS8)]
+
+
+# hyd_suffix_attn_causal_fwd (the builder's nq is 2: two rows per unit, which the causal kernel takes at every head count)
+r("hyd_suffix_attn_causal_fwd", null=True)
+chain("hyd_suffix_attn_causal_fwd",
+      [dict(dtype=2), dict(D=96), dict(B=0), dict(Hq=8, Hkv=3), dict(softmax_scale=-0.5), dict(kv_dim=8), dict(kv_len=-1)]
+      + _ptrs16("q", "out", "k", "v") + [{t.format(g): 4} for t in _STRIDES6 for g in ("batch", "tok", "head")]
+      + [dict(nq=1), dict(nq=9), dict(kv_dim=96), dict(n_partials=-1), dict(n_partials=9), dict(kv_len=0), dict(n_partials=1),
+         dict(kv_len=1 << 21, k_tok_stride=1024), dict(Hq=4 * 65535 + 1, Hkv=4 * 65535 + 1)])
+for bad in (dict(kv_dim=136), dict(kv_dim=24), dict(softmax_scale=INF), dict(kv_len=0, k=None), dict(kv_len=0, kv_dim=96, n_partials=9),
+            dict(kv_len=1 << 21, v_tok_stride=512), dict(Hq=65536, Hkv=1, nq=8), dict(Hq=65536, Hkv=65536, nq=3),
+            dict(Hq=4 * 65535 + 1, Hkv=4 * 65535 + 1, nq=3), dict(Hq=65536, Hkv=65536, nq=3, kv_len=1 << 21, k_tok_stride=1024),
+            dict(n_partials=1, **{"partials.0.out": PTR, "partials.0.lse": PTR, "partials.0.count": 0}),
+            dict(n_partials=1, nq=3, Hq=65536, Hkv=65536)):
+    r("hyd_suffix_attn_causal_fwd", **bad)
+r("hyd_suffix_attn_causal_fwd", n_partials=8, **_MANY)
+# (the causal tail's fp8 refusal is out of this entry point's reach -- it passes no hyd_kv_quant; the decode call reaches it)
+for bad in (dict(), dict(nq=9), dict(**{"suffix.kv_dim": 96}), dict(phase=2)):
+    r("hyd_decode_attn_fused_kvq", kq=dict(flags=1), causal_tail=1, Hq=32, **{"nq": 2, **bad})   # (8-row grouped-query units: native fp8 shapes)
+r("hyd_decode_attn_fused", causal_tail=2)
+r("hyd_decode_attn_fused", causal_tail=1)
+r("hyd_decode_attn_fused", causal_tail=1, nq=2, **{"suffix.kv_dim": 96})
+r("hyd_decode_attn_fused", causal_tail=1, nq=3, Hq=65536, Hkv=65536)
+
+# hyd_rope_append_multi
+_ROPE_MULTI_STRIDES = ("q_batch_stride", "k_batch_stride", "v_batch_stride", "q_tok_stride", "k_tok_stride", "v_tok_stride") + _ROPE_STRIDES[3:]
+r("hyd_rope_append_multi", null=True)
+chain("hyd_rope_append_multi",
+      [dict(T=1), dict(T=9), dict(dtype=2), dict(D=96), dict(B=0), dict(Hq=8, Hkv=3)] + _ptrs16(*_ROPE_PTRS)
+      + [[dict(position_ids=None), dict(seq_lens=None)], [dict(position_ids=PTR + 4), dict(shared_len=PTR + 4), dict(seq_lens=PTR + 2)]]
+      + [{n: 4} for n in _ROPE_MULTI_STRIDES] + [dict(cs_stride=6), dict(cache_len=0), dict(max_pos=0)])
+r("hyd_rope_append_multi", sin=MIS8, seq_lens=None)
+
+# hyd_sample_tokens_constrained: without an automaton the penalised sampler's call; with one, every check of that call, then its own
+r("hyd_sample_tokens_constrained", null=True)
+r("hyd_sample_tokens_constrained", null=True, no_dfa=True)
+r("hyd_sample_tokens_constrained", null=True, **{"c.allowed": None})
+for bad in (dict(dtype=3), dict(top_p=0.0), dict(n_bias=1), dict(gen=PTR + 2, gen_len=PTR)):
+    r("hyd_sample_tokens_constrained", no_dfa=True, **bad)
+for bad in (dict(dtype=3), dict(rows=-1), dict(n=MAX_N + 1, row_stride=MAX_N + 1), dict(logits=None), dict(temperature=-1.0), dict(top_k=-1), dict(top_p=0.0),
+            dict(min_p=1.5), dict(row_stride=63), dict(repetition_penalty=0.0), dict(frequency_penalty=INF), dict(n_context=10), dict(n_context=1),
+            dict(n_context=2, **{"context.0.bits": PTR, "context.0.rows_per_group": 1, "context.1.bits": PTR}),
+            dict(n_context=1, **{"context.0.bits": PTR + 2, "context.0.rows_per_group": 1}), dict(gen=PTR), dict(gen_stride=-1), dict(gen_stride=2049),
+            dict(append_out=1), dict(n_bias=1025), dict(n_bias=1), dict(kept=PTR + 1), dict(gen=PTR, gen_len=PTR + 2)):   # (each is in _PENALTY_BAD)
+    r("hyd_sample_tokens_constrained", **bad)
+_DFA_CHAIN = [[{"c.allowed": None}, {"c.next": None}, {"c.state": None}], {"c.n_states": 0}, {"c.allowed_stride": 1}, {"c.next_stride": 63},
+              [{"c.allowed": PTR + 2}, {"c.next": PTR + 2}, {"c.state": PTR + 2}]]
+chain("hyd_sample_tokens_constrained", _DFA_CHAIN)
+r("hyd_sample_tokens_constrained", n_bias=1, bias_ids=PTR, bias_values=PTR + 2, **{"c.allowed": None})   # the sampler's last check first
+r("hyd_sample_tokens_constrained", n=65, row_stride=72, **{"c.allowed_stride": 2, "c.next_stride": 64})   # three words, 65 entries
+r("hyd_sample_tokens_constrained", n=65, row_stride=72, **{"c.allowed_stride": 3, "c.next_stride": 64})
+r("hyd_sample_tokens_constrained", **{"c.n_states": -1, "c.state": None})
+
+# hyd_draft_lookup, with its per-segment loop (the first segment, the last of the two in use, the last there can be)
+r("hyd_draft_lookup", null=True)
+
+
+def _segment(i):
+    g = f"segments.{i}."
+    return [{g + "div": 0}, {g + "len": -1}, {g + "ids": None}, [{g + "ids": PTR + 4}, {g + "lens_i64": PTR + 4}, {g + "lens_i32": PTR + 2}]]
+
+
+chain("hyd_draft_lookup",
+      [dict(B=-1), dict(K=0), dict(K=8), dict(ngram_min=0), dict(ngram_max=0), dict(ngram_max=9), dict(n_segments=0), dict(n_segments=11),
+       [dict(drafts=None), dict(n_proposed=None)], [dict(drafts=PTR + 4), dict(n_proposed=PTR + 2)], dict(drafts_stride=2)]
+      + [s for i in (0, 1) for s in _segment(i)])
+chain("hyd_draft_lookup", _segment(9), pairs=False, n_segments=10)
+r("hyd_draft_lookup", **{"segments.0.ids": None, "segments.0.len": 0, "segments.1.len": -1})   # no ids and no length: taken
+r("hyd_draft_lookup", **{"segments.2.div": 0, "segments.1.len": -1})                            # a segment past n_segments is not read
+r("hyd_draft_lookup", K=4)                                                                      # drafts_stride 3 < K
+
+# hyd_dfa_forced_tokens and hyd_draft_constrain
+r("hyd_dfa_forced_tokens", null=True)
+chain("hyd_dfa_forced_tokens", [[dict(n_states=0), dict(n=0)], dict(allowed_stride=1), [dict(allowed=None), dict(forced=None)],
+                                [dict(allowed=PTR + 2), dict(forced=PTR + 2)]])
+r("hyd_dfa_forced_tokens", n=65, allowed_stride=2)
+r("hyd_dfa_forced_tokens", n_states=-1, allowed=None)
+r("hyd_draft_constrain", null=True)
+chain("hyd_draft_constrain",
+      [dict(B=-1), [dict(K=0), dict(K=8)], [dict(n_states=0), dict(n=0)], dict(next_stride=63), dict(fed_stride=3),
+       [{n: None} for n in ("state", "fed", "forced", "next", "step_state", "n_forced")],
+       [dict(fed=PTR + 4)] + [{n: PTR + 2} for n in ("state", "n_proposed", "forced", "next", "step_state", "n_forced")]])
+r("hyd_draft_constrain", K=4)   # fed_stride 4 < K + 1
+
+# hyd_draft_accept and hyd_draft_accept_states (the same row-state block; the second adds the automaton's two arrays)
+_ACCEPT_CHAIN = [dict(rows=-1), [dict(T=0), dict(T=9)], [dict(n_eos=-1), dict(n_eos=17)], [dict(max_new_tokens=0), dict(max_new_tokens=9)],
+                 [{n: None} for n in ("fed", "sampled", "out", "length", "reason", "stop_index", "accepted", "live")],
+                 [{n: None} for n in ("start_pos", "feed", "next_pos")],
+                 [{n: PTR + 4} for n in ("fed", "sampled", "out", "start_pos", "shared_len", "feed", "next_pos")],
+                 [{n: PTR + 2} for n in ("length", "reason", "stop_index", "accepted", "live", "logprobs", "out_logprobs")]]
+r("hyd_draft_accept", null=True)
+chain("hyd_draft_accept", _ACCEPT_CHAIN)
+r("hyd_draft_accept_states", null=True)
+r("hyd_draft_accept_states", null=True, step_state_after=None, state=None)
+chain("hyd_draft_accept_states", _ACCEPT_CHAIN, pairs=False)   # (the order of these is pinned through hyd_draft_accept)
+chain("hyd_draft_accept_states", [dict(out_logprobs=PTR + 2, live=PTR + 2), [dict(state=None), dict(step_state_after=None)],
+                                  [dict(step_state_after=PTR + 2), dict(state=PTR + 2)]])
+for bad in (dict(rows=-1), dict(live=None), dict(next_pos=PTR + 4), dict(out_logprobs=PTR + 2)):   # neither array: hyd_draft_accept's call
+    r("hyd_draft_accept_states", step_state_after=None, state=None, **bad)
+
+# hyd_kv_promote and hyd_kv_gather_paths: the unique segment they share, then the path's levels
+_KV_SHAPE = [[dict(dst_dtype=2), dict(dst_dtype=3)], dict(src_dtype=2), dict(src_dtype=0), dict(n=0)]
+_KV_SIZES = [dict(Hkv=0), [dict(B=0), dict(src_rows=0), dict(capacity=-1)], [dict(d_src=0), dict(d_src=12)], dict(d_dst=64), dict(d_dst=192),
+             [dict(max_len=-1), dict(max_len=65)]]
+
+
+def _kv_tail(cu):
+    return ([dict(n=65536)] + _ptrs16("k_src", "v_src", "k_dst", "v_dst") + [[dict(rows=None), dict(lens=None), {cu: None}]]
+            + [[{n: PTR + 2} for n in ("rows", "lens", cu, "k_scale", "v_scale")]]
+            + [{t.format(g): 4} for t in _STRIDES6 for g in ("batch", "tok", "head")] + [[dict(k_head_stride=64), dict(v_head_stride=64)]])
+
+
+r("hyd_kv_promote", null=True)
+chain("hyd_kv_promote", _KV_SHAPE + _KV_SIZES + _kv_tail("cu") + [dict(src_rows=1 << 24)])
+r("hyd_kv_promote", src_dtype=3, dst_dtype=3)
+r("hyd_kv_promote", src_dtype=3, k_scale=PTR + 2)
+r("hyd_kv_promote", d_src=96, d_dst=120)
+r("hyd_kv_promote", max_len=64, src_rows=1 << 24, Hkv=1 << 21)           # max_len, not src_rows, bounds the sequence
+
+
+def _level(j):
+    return [{f"level_k.{j}": None}, {f"level_k.{j}": MIS8}, {f"level_v.{j}": None}, {f"level_v.{j}": MIS8},
+            [{f"level_cu.{j}": None}, {f"level_cu.{j}": PTR + 2}], {f"level_div.{j}": 0}, [{f"level_s.{j}": 0}, {f"level_cap.{j}": -1}]]
+
+
+r("hyd_kv_gather_paths", null=True)
+chain("hyd_kv_gather_paths",
+      _KV_SHAPE + [[dict(n_levels=-1), dict(n_levels=9)]] + _KV_SIZES + [[dict(max_path=-1), dict(max_path=257)]] + _kv_tail("cu_dst")
+      + _level(0) + _level(1) + [dict(src_rows=1 << 24), dict(capacity=1 << 24)])
+chain("hyd_kv_gather_paths", _level(7), pairs=False, n_levels=8)
+r("hyd_kv_gather_paths", n_levels=8, src_rows=1 << 24, **{"level_cap.7": -1})
+r("hyd_kv_gather_paths", **{"level_k.2": None, "level_cap.1": -1})       # a level past n_levels is not read
+r("hyd_kv_gather_paths", n_levels=0, **{"level_k.0": None}, src_rows=1 << 24)
+r("hyd_kv_gather_paths", max_path=64, src_rows=32, capacity=1 << 24, Hkv=1 << 21)    # max_path, not capacity, bounds the path
+r("hyd_kv_gather_paths", capacity=0, src_rows=1 << 24)
+r("hyd_kv_gather_paths", capacity=0, max_path=1)
+noop("hyd_kv_gather_paths", capacity=0)
+noop("hyd_kv_gather_paths", capacity=0, n_levels=0)
+
+# hyd_kv_absmax and hyd_kv_scales_from_absmax
+r("hyd_kv_absmax", null=True)
+chain("hyd_kv_absmax",
+      [dict(dtype=2), dict(Hkv=0), [dict(d=4), dict(d=264), dict(d=12)], [dict(n_outer=-1), dict(n_rows=-1)], dict(amax=None), dict(k=None, v=None),
+       dict(k=MIS8), dict(v=MIS8), [dict(amax=PTR + 2), dict(row_lens=PTR + 2)]]
+      + [{f"{t}_{g}_stride": 4} for t in "kv" for g in ("outer", "row", "head")]
+      + [dict(n_rows=(1 << 30) + 1), dict(Hkv=(1 << 19) + 1, d=256), dict(n_rows=1 << 30, n_outer=64)])
+r("hyd_kv_absmax", Hkv=1 << 19, d=256)                                   # 2^24 vectors per row: 65536 column blocks
+r("hyd_kv_absmax", k=None, k_outer_stride=4, v_head_stride=4)            # an absent tensor's strides are not read
+r("hyd_kv_absmax", v=None, v_outer_stride=4, k_head_stride=4)
+r("hyd_kv_absmax", n_outer=0, n_rows=(1 << 30) + 1)                      # refused before the empty call returns
+r("hyd_kv_absmax", n_rows=0, Hkv=(1 << 19) + 1, d=256)
+for empty in (dict(n_outer=0), dict(n_rows=0), dict(n_outer=0, n_rows=0), dict(n_rows=0, k=None)):
+    noop("hyd_kv_absmax", **empty)
+r("hyd_kv_scales_from_absmax", null=True)
+chain("hyd_kv_scales_from_absmax", [[{n: None} for n in ("amax", "k_scale", "v_scale")], [{n: PTR + 2} for n in ("amax", "k_scale", "v_scale")],
+                                    dict(Hkv=0), [dict(c=0.0), dict(c=-1.0), dict(c=INF), dict(c=NAN)]])
+
+# hyd_linear_w8 (with the workspace of a plan that splits K) and hyd_weight_widen
+r("hyd_linear_w8", null=True)
+chain("hyd_linear_w8",
+      [dict(M=0), dict(dtype=2), [dict(N=0), dict(K=0)], dict(K=24)] + _ptrs16("w8") + [dict(scale=None), dict(scale=PTR + 2)] + _ptrs16("x", "y")
+      + [dict(x_row_stride=4), dict(y_row_stride=4), [dict(x_row_stride=248), dict(y_row_stride=56)]])
+r("hyd_linear_w8", M=1 << 30, N=1 << 30, K=16)
+r("hyd_linear_w8", M=1 << 30, N=1 << 30, K=16, y_row_stride=56)
+r("hyd_linear_w8", M=1 << 30, N=1 << 30, K=4096, workspace=None)
+chain("hyd_linear_w8", [dict(y_row_stride=56), dict(workspace=None), dict(workspace_bytes=16), dict(workspace=MIS8)], **W8_SPLIT)
+r("hyd_linear_w8", workspace=None, workspace_bytes=0, **W8_SPLIT)
+r("hyd_weight_widen", null=True)
+chain("hyd_weight_widen", [dict(dtype=2), [dict(N=0), dict(K=0)], dict(K=12)] + _ptrs16("w8") + [dict(scale=None), dict(scale=PTR + 2)]
+      + _ptrs16("out") + [dict(out_row_stride=4), dict(out_row_stride=248)])
+
+# hyd_narrow_kv_supported over the head dims and shapes of tests/test_narrow_head_dim_gpu.py: (kv_dim, Hkv, rows) of nine sequences, the
+# 2052-sequence call, the few-unit and no-copy calls, the operator sizes (B, longest unique cache) at 80 / 96 / 192 on 8 heads
+_PAD_D = {48: 64, 80: 128, 96: 128, 112: 128, 160: 256, 192: 256}
+_NARROW = ([(9, 1, H, d, rows) for d, H, rows in ((96, 4, 40), (96, 8, 40), (96, 12, 40), (96, 20, 40), (96, 4, 16), (80, 8, 40), (112, 8, 40),
+                                                 (48, 8, 40), (48, 16, 40), (160, 2, 40), (160, 6, 40), (192, 2, 40), (192, 6, 40))]
+           + [(2052, 1, 4, 96, 32), (3, 1, 8, 96, 80), (3, 1, 8, 96, 1040), (64, 1, 32, 96, 512)]
+           + [(B, 1, 8, d, S) for d in (80, 96, 192) for B, S in ((4, 4), (8, 6), (4, 5), (8, 8))])
+for i, (B, nq, H, d, S) in enumerate(_NARROW):
+    for dtype in ((0, 1) if i < 2 else (1,)):   # (the answer does not look at which of the two 16-bit dtypes it is)
+        q("narrow_kv", dtype=dtype, B=B, nq=nq, Hq=H, Hkv=H, D=_PAD_D[d], kv_dim=d, kv_len=S)
+for shape in (dict(kv_dim=0), dict(kv_dim=128), dict(kv_dim=8), dict(kv_dim=24), dict(kv_dim=136), dict(kv_dim=96, kv_len=0), dict(kv_dim=96, kv_len=-1),
+              dict(kv_dim=0, kv_len=-1), dict(kv_dim=96, nq=2), dict(kv_dim=96, Hq=16), dict(kv_dim=96, Hq=6, Hkv=6), dict(kv_dim=96, dtype=2),
+              dict(kv_dim=48, D=96), dict(kv_dim=96, B=0), dict(kv_dim=96, kv_len=1 << 21), dict(kv_dim=96, Hq=4 * 65535 + 4, Hkv=4 * 65535 + 4)):
+    q("narrow_kv", **shape)
+q("narrow_kv", null=True)
+for M in (-1, 0, 1, 16, 17, 33, 65):         # (every row-tile class of the plan, and a non-positive size in each place)
+    for N in (0, 30, 4096):
+        for K in (0, 128, 4096, 16384):
+            q("linear_w8_workspace", M=M, N=N, K=K)
+
+# calls that return HYD_OK before any HIP call
+noop("hyd_stop_update", rows=0)
+noop("hyd_allreduce_sum", count=0)
+noop("hyd_allreduce_sum", count=0, in_=None, out=None)
+noop("hyd_decode_attn_fused", kv_len=0, phase=_lib.HYD_PHASE_UNIQUE)
+
+
 def _case_id(kind, entry, kw):
     return f"{kind}:{entry}:" + json.dumps(kw, sort_keys=True, default=str)
 
 
 QUERY_CASES = [(_case_id("query", e, kw), e, kw) for e, kw in _Q]
 REFUSAL_CASES = [(_case_id("refusal", e, kw), e, kw) for e, kw in _R]
-_ids = [c[0] for c in QUERY_CASES + REFUSAL_CASES]
+NOOP_CASES = [(_case_id("noop", e, kw), e, kw) for e, kw in _N]
+_ids = [c[0] for c in QUERY_CASES + REFUSAL_CASES + NOOP_CASES]
 assert len(set(_ids)) == len(_ids), sorted(i for i in set(_ids) if _ids.count(i) > 1)
 
 
@@ -642,7 +1024,10 @@ def run_case(case):
     """One case through ctypes -> a plain record (ints and strings only)."""
     cid, entry, kw = case
     lib = _lib.load()
-    return (QUERIES[entry] if cid.startswith("query:") else REFUSALS[entry])(lib, kw)
+    if cid.startswith("query:"):
+        return QUERIES[entry](lib, kw)
+    rec = REFUSALS[entry](lib, kw)
+    return {"rc": rec["rc"]} if cid.startswith("noop:") else rec  # (the error string is not cleared on success)
 
 
 def load_fixture():
@@ -653,16 +1038,21 @@ def write():
     table = {}
     for case in QUERY_CASES:
         table[case[0]] = run_case(case)
-    accepted = []
+    wrong = []
     for case in REFUSAL_CASES:
         rec = run_case(case)
         if rec["rc"] in (HYD_OK, HYD_ERR_LAUNCH):
-            accepted.append(f"{case[0]}: the library answers {rec['rc']} ({rec['error']!r})")
+            wrong.append(f"{case[0]}: the library answers {rec['rc']} ({rec['error']!r}): not a refusal")
         table[case[0]] = rec
-    if accepted:
-        raise SystemExit("\n".join(accepted) + "\nnot refusals: nothing recorded")
+    for case in NOOP_CASES:
+        rec = run_case(case)
+        if rec["rc"] != HYD_OK:
+            wrong.append(f"{case[0]}: the library answers {rec['rc']} ({_err(_lib.load())!r}): not a call that returns HYD_OK")
+        table[case[0]] = rec
+    if wrong:
+        raise SystemExit("\n".join(wrong) + "\nnothing recorded")
     FIXTURE.write_text(json.dumps(table, indent=0, sort_keys=True) + "\n")
-    print(f"{FIXTURE}: {len(QUERY_CASES)} queries, {len(REFUSAL_CASES)} refusals")
+    print(f"{FIXTURE}: {len(QUERY_CASES)} queries, {len(REFUSAL_CASES)} refusals, {len(NOOP_CASES)} no-ops")
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
 """One launch vs the prefix pass + suffix pass pair for small problems: us per call (graph replays), to place
-kSingleLaunchMaxKeys (api.hip)."""
+kSingleLaunchMaxKeys (api_attn.hip)."""
 import sys, ctypes as C
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parents[2]))

@@ -36,17 +36,37 @@ def test_dynamic_symbol_table_is_exactly_the_header():
     assert "getenv" not in undefined, "the product library must not read environment variables"
 
 
+# every ctypes mirror of hydragen_amd/_lib.py beside the C type it mirrors
+STRUCT_MIRRORS = [
+    ("hyd_prefix_params", _lib.PrefixParams), ("hyd_partial", _lib.Partial), ("hyd_suffix_params", _lib.SuffixParams), ("hyd_level", _lib.Level),
+    ("hyd_decode_params", _lib.DecodeParams), ("hyd_rope_params", _lib.RopeParams), ("hyd_rope_multi_params", _lib.RopeMultiParams),
+    ("hyd_add_rmsnorm_params", _lib.AddRmsnormParams), ("hyd_swiglu_params", _lib.SwigluParams), ("hyd_sample_params", _lib.SampleParams),
+    ("hyd_sample_filter_params", _lib.SampleFilterParams), ("hyd_token_bitmap", _lib.TokenBitmap),
+    ("hyd_sample_penalty_params", _lib.SamplePenaltyParams), ("hyd_token_bitmap_params", _lib.TokenBitmapParams), ("hyd_token_dfa", _lib.TokenDfa),
+    ("hyd_token_logprob_params", _lib.TokenLogprobParams), ("hyd_stop_params", _lib.StopParams), ("hyd_draft_segment", _lib.DraftSegment),
+    ("hyd_draft_lookup_params", _lib.DraftLookupParams), ("hyd_draft_accept_params", _lib.DraftAcceptParams),
+    ("hyd_dfa_forced_params", _lib.DfaForcedParams), ("hyd_draft_constrain_params", _lib.DraftConstrainParams),
+    ("hyd_allreduce_params", _lib.AllReduceParams), ("hyd_kv_quant", _lib.KvQuant), ("hyd_kv_promote_params", _lib.KvPromoteParams),
+    ("hyd_kv_gather_params", _lib.KvGatherParams), ("hyd_kv_absmax_params", _lib.KvAbsmaxParams), ("hyd_kv_scales_params", _lib.KvScalesParams),
+    ("hyd_linear_w8_params", _lib.LinearW8Params), ("hyd_weight_widen_params", _lib.WeightWidenParams),
+]
+
+
 def test_struct_layout_matches_c():
-    """ctypes mirrors must have the C compiler's sizes (checked against a gcc build of the header)."""
+    """ctypes mirrors must have the C compiler's sizes (checked against a gcc build of the header): every struct the header
+    declares and every Structure _lib.py defines is in STRUCT_MIRRORS."""
     import subprocess, tempfile
-    src = '#include "hydragen_hip.h"\n#include <stdio.h>\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(hyd_prefix_params), sizeof(hyd_partial), sizeof(hyd_suffix_params), sizeof(hyd_level), sizeof(hyd_decode_params), sizeof(hyd_rope_params), sizeof(hyd_add_rmsnorm_params), sizeof(hyd_swiglu_params), sizeof(hyd_sample_params));return 0;}\n'
+    header = (REPO / "include" / "hydragen_hip.h").read_text()
+    assert sorted(n for n, _ in STRUCT_MIRRORS) == sorted(re.findall(r"^} (hyd_\w+);", header, flags=re.M))
+    mirrors = {c for c in vars(_lib).values() if isinstance(c, type) and issubclass(c, C.Structure) and c is not C.Structure}
+    assert {c for _, c in STRUCT_MIRRORS} == mirrors
+    prints = "".join(f'printf("%zu\\n", sizeof({n}));' for n, _ in STRUCT_MIRRORS)
+    src = '#include "hydragen_hip.h"\n#include <stdio.h>\nint main(){' + prints + 'return 0;}\n'
     with tempfile.TemporaryDirectory() as d:
         (Path(d) / "s.c").write_text(src)
         subprocess.check_call(["gcc", "-I", str(REPO / "include"), str(Path(d) / "s.c"), "-o", str(Path(d) / "s")])
         sizes = list(map(int, subprocess.check_output([str(Path(d) / "s")]).split()))
-    assert sizes == [C.sizeof(PrefixParams), C.sizeof(_lib.Partial), C.sizeof(SuffixParams), C.sizeof(_lib.Level),
-                     C.sizeof(DecodeParams), C.sizeof(_lib.RopeParams), C.sizeof(_lib.AddRmsnormParams),
-                     C.sizeof(_lib.SwigluParams), C.sizeof(_lib.SampleParams)]
+    assert dict(zip((n for n, _ in STRUCT_MIRRORS), sizes)) == {n: C.sizeof(c) for n, c in STRUCT_MIRRORS}
 
 
 def _prefix(**kw):

@@ -1,6 +1,7 @@
 """-m "not gpu": the host side of the C ABI answers exactly what tests/golden/abi_table.json recorded -- every plan, workspace size and
-support answer as the same integers, every refusal with the same return code and the same error string, character for character.
-The table was recorded (python tests/abi_table.py --write) from the library before csrc/api.hip was restructured; it is data, and
+support answer as the same integers, every refusal with the same return code and the same error string, character for character, every call that has nothing
+to do with HYD_OK.
+The table was recorded (python tests/abi_table.py --write) from the parent of the last change to csrc/api_*.hip; it is data, and
 is not regenerated from the code it checks."""
 import pytest
 
@@ -13,9 +14,10 @@ def table():
 
 
 def test_table_and_case_list_are_the_same_set(table):
-    ids = [c[0] for c in abi_table.QUERY_CASES + abi_table.REFUSAL_CASES]
+    ids = [c[0] for c in abi_table.QUERY_CASES + abi_table.REFUSAL_CASES + abi_table.NOOP_CASES]
     assert sorted(ids) == sorted(table)
     assert all(rec["rc"] not in (abi_table.HYD_OK, abi_table.HYD_ERR_LAUNCH) for cid, rec in table.items() if cid.startswith("refusal:"))
+    assert all(rec == {"rc": abi_table.HYD_OK} for cid, rec in table.items() if cid.startswith("noop:"))
 
 
 def test_shapes_only_queries_match_the_record(table):
@@ -40,3 +42,18 @@ def test_refusals_match_the_record(table):
         if got != table[case[0]]:
             wrong[case[0]] = (got, table[case[0]])
     assert not wrong, f"{len(wrong)} of {len(abi_table.REFUSAL_CASES)} differ (got, recorded): {dict(list(wrong.items())[:5])}"
+
+
+def test_noops_match_the_record(table):
+    """Calls that return HYD_OK before any HIP call.  Runs only without a device, like the refusals: a regression that launches comes
+    back as HYD_ERR_LAUNCH there instead of the recorded HYD_OK, and would run a kernel on made-up addresses where a device is."""
+    import torch
+
+    if torch.cuda.is_available():
+        pytest.skip("no-op calls are replayed on machines without a device only")
+    wrong = {}
+    for case in abi_table.NOOP_CASES:
+        got = abi_table.run_case(case)
+        if got != table[case[0]]:
+            wrong[case[0]] = (got, table[case[0]], abi_table._lib.load().hyd_last_error_string().decode())
+    assert not wrong, f"{len(wrong)} of {len(abi_table.NOOP_CASES)} differ (got, recorded, last error): {wrong}"

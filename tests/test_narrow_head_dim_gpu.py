@@ -138,7 +138,7 @@ def _oracle(case):
                                 case["shared_max_seq_lens"], case["use_varlens"], case["seq_lens"])
 
 
-# [[64], [4] * 4]: the smallest; [[200], [6] * 8]: above api.hip's one-launch rule (8 * 8 * 206 keys > 8192); a ragged level; four
+# [[64], [4] * 4]: the smallest; [[200], [6] * 8]: above api_attn.hip's one-launch rule (8 * 8 * 206 keys > 8192); a ragged level; four
 # levels (the kernel prefetches two partials, the others are fetched behind the key loop); one group of 4096 keys for 8 sequences:
 # split-KV, stacked fp32 slices
 OPERATOR_SIZES = [
