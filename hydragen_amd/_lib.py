@@ -348,8 +348,10 @@ EXPORTS = {
     "hyd_sample_tokens_penalized": (C.c_int, [C.POINTER(SamplePenaltyParams), C.c_void_p]),
     "hyd_token_bitmap_build": (C.c_int, [C.POINTER(TokenBitmapParams), C.c_void_p]),
     "hyd_sample_tokens_constrained": (C.c_int, [C.POINTER(SamplePenaltyParams), C.POINTER(TokenDfa), C.c_void_p]),
+    "hyd_sample_tokens_rows": (C.c_int, [C.POINTER(SamplePenaltyParams), C.POINTER(TokenDfa)] + [C.c_void_p] * 9),
     "hyd_token_logprobs": (C.c_int, [C.POINTER(TokenLogprobParams), C.c_void_p]),
     "hyd_stop_update": (C.c_int, [C.POINTER(StopParams), C.c_void_p]),
+    "hyd_stop_update_rows": (C.c_int, [C.POINTER(StopParams), C.c_void_p, C.c_void_p]),
     "hyd_kv_promote": (C.c_int, [C.POINTER(KvPromoteParams), C.c_void_p]),
     "hyd_kv_gather_paths": (C.c_int, [C.POINTER(KvGatherParams), C.c_void_p]),
     "hyd_kv_absmax": (C.c_int, [C.POINTER(KvAbsmaxParams), C.c_void_p]),

@@ -31,11 +31,8 @@ int check_draft_accept(const hyd_draft_accept_params* p) {
     return rc;
 }
 
-}  // namespace
-
-extern "C" {
-
-int hyd_stop_update(const hyd_stop_params* p, void* stream) {
+// hyd_stop_update, and with a row limit array hyd_stop_update_rows
+int stop_update(const hyd_stop_params* p, const int32_t* max_len, void* stream) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
     if (p->rows < 0) return fail(HYD_ERR_BAD_ARG, "rows %d", p->rows);
     if (int rc = check_n_eos(p->n_eos)) return rc;
@@ -51,6 +48,7 @@ int hyd_stop_update(const hyd_stop_params* p, void* stream) {
     rc = check_elem_align({{p->tok, 8, "tok"}, {p->out, 8, "out"}, {p->stop_tokens, 8, "stop_tokens"}, {p->start_pos, 8, "start_pos"},
                            {p->shared_len, 8, "shared_len"}, {p->feed, 8, "feed"}, {p->next_pos, 8, "next_pos"}});
     if (!rc) rc = check_elem_align({{p->length, 4, "length"}, {p->reason, 4, "reason"}, {p->stop_index, 4, "stop_index"}, {p->live, 4, "live"}});
+    if (!rc) rc = check_elem_align({{max_len, 4, "max_len"}});
     if (rc) return rc;
     if (p->rows == 0) return HYD_OK;
     StopArgs a;
@@ -62,8 +60,17 @@ int hyd_stop_update(const hyd_stop_params* p, void* stream) {
     for (int k = 0; k < p->n_stop; ++k) a.stop_lens[k] = p->stop_lens[k];
     a.rows = p->rows; a.t = p->t; a.n_eos = p->n_eos; a.n_stop = p->n_stop;
     a.include_stop = p->include_stop ? 1 : 0; a.retire = p->retire ? 1 : 0;
+    a.max_len = max_len;
     return launched(launch_stop_update(a, static_cast<hipStream_t>(stream)), "stop_update kernel launch");
 }
+
+}  // namespace
+
+extern "C" {
+
+int hyd_stop_update(const hyd_stop_params* p, void* stream) { return stop_update(p, nullptr, stream); }
+
+int hyd_stop_update_rows(const hyd_stop_params* p, const int32_t* max_len, void* stream) { return stop_update(p, max_len, stream); }
 
 int hyd_draft_lookup(const hyd_draft_lookup_params* p, void* stream) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");

@@ -1,4 +1,4 @@
-// C ABI, the [rows, n] logits calls: the four samplers (plain, filtered, penalised, under a token automaton), the token bitmaps
+// C ABI, the [rows, n] logits calls: the samplers (plain, filtered, penalised, under a token automaton, with per-row values), the token bitmaps
 // the penalties read, and the log-probs of given tokens.
 #include "api_core.h"
 
@@ -87,6 +87,25 @@ int fill_penalty_args(const hyd_sample_penalty_params* p, PenaltyArgs* ap) {
     return HYD_OK;
 }
 
+// What hyd_sample_tokens_constrained checks of its automaton, and the kernels' argument block of it
+int fill_constrain_args(const hyd_sample_penalty_params* p, const hyd_token_dfa* c, ConstrainArgs* ca) {
+    int rc = check_not_null({{c->allowed, "allowed"}, {c->next, "next"}, {c->state, "state"}}, "hyd_token_dfa: ");
+    if (rc) return rc;
+    if (c->n_states <= 0) return fail(HYD_ERR_BAD_ARG, "hyd_token_dfa: n_states %d must be > 0", c->n_states);
+    if ((rc = check_allowed_stride(c->allowed_stride, p->n, "hyd_token_dfa: "))) return rc;
+    if ((rc = check_next_stride(c->next_stride, p->n, "hyd_token_dfa: "))) return rc;
+    if ((rc = check_elem_align({{c->allowed, 4, "allowed"}, {c->next, 4, "next"}, {c->state, 4, "state"}}, "hyd_token_dfa: "))) return rc;
+    memset(ca, 0, sizeof(*ca));
+    ca->allowed = c->allowed; ca->next = c->next; ca->state = c->state;
+    ca->allowed_stride = c->allowed_stride; ca->next_stride = c->next_stride;
+    ca->n_states = c->n_states; ca->advance = c->advance ? 1 : 0;
+    return HYD_OK;
+}
+// every penalty neutral (and nothing to append): x = l, so the row keeps the keys of its own width (sample_filter.hip's cost)
+bool penalties_neutral(const hyd_sample_penalty_params* p) {
+    return p->repetition_penalty == 1.0 && p->frequency_penalty == 0.0 && p->presence_penalty == 0.0 && p->n_bias == 0 && !p->append_out;
+}
+
 }  // namespace
 
 extern "C" {
@@ -124,21 +143,29 @@ int hyd_sample_tokens_penalized(const hyd_sample_penalty_params* p, void* stream
 int hyd_sample_tokens_constrained(const hyd_sample_penalty_params* p, const hyd_token_dfa* c, void* stream) {
     if (!c) return hyd_sample_tokens_penalized(p, stream);
     PenaltyArgs a;
-    int rc = fill_penalty_args(p, &a);
-    if (!rc) rc = check_not_null({{c->allowed, "allowed"}, {c->next, "next"}, {c->state, "state"}}, "hyd_token_dfa: ");
-    if (rc) return rc;
-    if (c->n_states <= 0) return fail(HYD_ERR_BAD_ARG, "hyd_token_dfa: n_states %d must be > 0", c->n_states);
-    if ((rc = check_allowed_stride(c->allowed_stride, p->n, "hyd_token_dfa: "))) return rc;
-    if ((rc = check_next_stride(c->next_stride, p->n, "hyd_token_dfa: "))) return rc;
-    if ((rc = check_elem_align({{c->allowed, 4, "allowed"}, {c->next, 4, "next"}, {c->state, 4, "state"}}, "hyd_token_dfa: "))) return rc;
     ConstrainArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.allowed = c->allowed; ca.next = c->next; ca.state = c->state;
-    ca.allowed_stride = c->allowed_stride; ca.next_stride = c->next_stride;
-    ca.n_states = c->n_states; ca.advance = c->advance ? 1 : 0;
-    // every penalty neutral (and nothing to append): x = l, so the row keeps the keys of its own width (sample_filter.hip's cost)
-    const bool neutral = p->repetition_penalty == 1.0 && p->frequency_penalty == 0.0 && p->presence_penalty == 0.0 && p->n_bias == 0 && !p->append_out;
-    return launched(launch_sample_constrain(a, ca, neutral, p->dtype, static_cast<hipStream_t>(stream)), "sample_constrain kernel launch");
+    int rc = fill_penalty_args(p, &a);
+    if (!rc) rc = fill_constrain_args(p, c, &ca);
+    if (rc) return rc;
+    return launched(launch_sample_constrain(a, ca, penalties_neutral(p), p->dtype, static_cast<hipStream_t>(stream)), "sample_constrain kernel launch");
+}
+
+int hyd_sample_tokens_rows(const hyd_sample_penalty_params* p, const hyd_token_dfa* c, const float* temperature, const int32_t* top_k,
+                           const float* top_p, const float* min_p, const float* repetition_penalty, const float* frequency_penalty,
+                           const float* presence_penalty, const uint64_t* seed, void* stream) {
+    if (!temperature && !top_k && !top_p && !min_p && !repetition_penalty && !frequency_penalty && !presence_penalty && !seed)
+        return hyd_sample_tokens_constrained(p, c, stream);
+    PenaltyArgs a;
+    ConstrainArgs ca;
+    int rc = fill_penalty_args(p, &a);
+    if (!rc && c) rc = fill_constrain_args(p, c, &ca);
+    if (!rc) rc = check_elem_align({{temperature, 4, "temperature"}, {top_k, 4, "top_k"}, {top_p, 4, "top_p"}, {min_p, 4, "min_p"},
+                                    {repetition_penalty, 4, "repetition_penalty"}, {frequency_penalty, 4, "frequency_penalty"},
+                                    {presence_penalty, 4, "presence_penalty"}, {seed, 8, "seed"}}, "hyd_sample_tokens_rows: ");
+    if (rc) return rc;
+    const RowParams r{temperature, top_k, top_p, min_p, repetition_penalty, frequency_penalty, presence_penalty, seed};
+    const bool neutral = penalties_neutral(p) && !repetition_penalty && !frequency_penalty && !presence_penalty;
+    return launched(launch_sample_rows(a, c ? &ca : nullptr, r, neutral, p->dtype, static_cast<hipStream_t>(stream)), "sample_rows kernel launch");
 }
 
 int hyd_token_bitmap_build(const hyd_token_bitmap_params* p, void* stream) {

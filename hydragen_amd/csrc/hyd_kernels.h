@@ -202,6 +202,18 @@ struct ConstrainArgs {  // sample_constrain.hip: the token automaton of hyd_samp
     int32_t n_states, advance;
 };
 
+struct RowParams {  // sample_rows.hip: per-row sampling values (hyd_sample_tokens_rows), each [rows] or null = the launch's scalar
+    const float* temperature;
+    const int32_t* top_k;
+    const float* top_p;
+    const float* min_p;
+    const float* rep;
+    const float* freq;
+    const float* pres;
+    const uint64_t* seed;
+};
+struct NoRowParams {};  // the scalar launches: every value is the argument block's
+
 struct BitmapArgs {  // sample_penalty.hip: token ids -> presence bitmap (hyd_token_bitmap_build)
     const int64_t* ids;
     const int64_t* lens;  // may be null
@@ -239,6 +251,7 @@ struct StopArgs {  // stop_update.hip: EOS ids / stop sequences judged per row, 
     int64_t eos[HYD_STOP_MAX_EOS];
     int32_t stop_lens[HYD_STOP_MAX_SEQS];
     int32_t rows, t, n_eos, n_stop, include_stop, retire;
+    const int32_t* max_len;      // [rows] or null: a row's own token limit (hyd_stop_update_rows)
 };
 
 struct KvPromoteArgs {  // kv_promote.hip: chosen rows of the unique K/V caches -> a packed shared level (hyd_kv_promote)
@@ -337,6 +350,7 @@ int launch_sample(const SampleArgs& a, int dtype, hipStream_t s);
 int launch_sample_filter(const FilterArgs& a, int dtype, hipStream_t s);  // sample_filter.hip
 int launch_sample_penalty(const PenaltyArgs& a, int dtype, hipStream_t s);     // sample_penalty.hip
 int launch_sample_constrain(const PenaltyArgs& a, const ConstrainArgs& c, bool neutral, int dtype, hipStream_t s);  // sample_constrain.hip
+int launch_sample_rows(const PenaltyArgs& a, const ConstrainArgs* c, const RowParams& r, bool neutral, int dtype, hipStream_t s);  // sample_rows.hip
 int launch_token_bitmap(const BitmapArgs& a, hipStream_t s);                     // sample_penalty.hip
 int launch_token_logprob(const TokenLogprobArgs& a, int dtype, hipStream_t s);  // token_logprob.hip
 int launch_stop_update(const StopArgs& a, hipStream_t s);                          // stop_update.hip

@@ -18,13 +18,50 @@ static_assert(HYD_SAMPLE_GEN_MAX < (1 << 16) && HYD_SAMPLE_BIAS_MAX < (1 << 15),
 
 __device__ __forceinline__ uint32_t slot_of(int v) { return ((uint32_t)v * 0x9E3779B1u) >> 20; }  // top 12 bits
 
-struct PenaltyMap {
+// The three penalties of a row of hyd_sample_tokens_rows, block-uniform: the row's fp32 entries widened to double exactly (so
+// that a per-row f behaves bit for bit like the scalar (double)f) and sanitised -- a repetition penalty that is <= 0 or not
+// finite -> 1, a frequency / presence penalty that is not finite -> 0 --, inv_rep = 1.0 / rep (one IEEE fp64 division per row:
+// the host's expression).  An array that is not given leaves the launch's scalar.
+struct PenVals {
+    double rep, inv_rep, freq, pres;
+};
+struct ArgPen {  // the scalar launches: the argument block's (these are never read)
+    static constexpr double rep = 0, inv_rep = 0, freq = 0, pres = 0;
+};
+__device__ __forceinline__ double uniform_d(double x) {
+    const uint64_t u = __builtin_bit_cast(uint64_t, x);
+    return __builtin_bit_cast(double, (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u) |
+                                          (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32)) << 32);
+}
+__device__ __forceinline__ PenVals pen_vals(const PenaltyArgs& a, const RowParams& r, int row) {
+    PenVals v{a.rep, a.inv_rep, a.freq, a.pres};
+    if (r.rep) {
+        const float f = r.rep[row];
+        v.rep = uniform_d((f > 0.f && f < INFINITY) ? (double)f : 1.0);
+        v.inv_rep = uniform_d(1.0 / v.rep);
+    }
+    if (r.freq) {
+        const float f = r.freq[row];
+        v.freq = uniform_d(fabsf(f) < INFINITY ? (double)f : 0.0);
+    }
+    if (r.pres) {
+        const float f = r.pres[row];
+        v.pres = uniform_d(fabsf(f) < INFINITY ? (double)f : 0.0);
+    }
+    return v;
+}
+
+// Pen: ArgPen, or the row's PenVals (pen_vals)
+template <typename Pen>
+struct PenaltyMapP {
     const PenaltyArgs& a;
     const uint32_t* ctx;   // LDS, or null: read the levels in global memory
     const uint32_t* slow;  // LDS
     const int* keys;       // LDS
     const uint32_t* vals;  // LDS: count | (bias position + 1) << 16
     int row;
+    Pen pen;
+    static constexpr bool kRows = !__is_same(Pen, ArgPen);  // (constant conditions below: the other arm is not compiled)
 
     __device__ __forceinline__ uint32_t ctx_byte(int c) const {
         if (ctx) return reinterpret_cast<const uint8_t*>(ctx)[c];
@@ -44,8 +81,8 @@ struct PenaltyMap {
     __device__ __forceinline__ float apply(float l, bool in_ctx, uint32_t val) const {
         const uint32_t cnt = val & 0xffffu, bpos = val >> 16;
         double x = (double)l;
-        if (in_ctx || cnt) x = x * (x > 0.0 ? a.inv_rep : a.rep);  // (1 / r in double: 2^-53 relative, far below the fp32 rounding)
-        if (cnt) x -= a.freq * (double)cnt + a.pres;
+        if (in_ctx || cnt) x = x * (x > 0.0 ? (kRows ? pen.inv_rep : a.inv_rep) : (kRows ? pen.rep : a.rep));  // (1 / r in double: 2^-53 relative, far below the fp32 rounding)
+        if (cnt) x -= (kRows ? pen.freq : a.freq) * (double)cnt + (kRows ? pen.pres : a.pres);
         if (bpos && bpos <= (uint32_t)a.n_bias) x += (double)a.bias_values[bpos - 1];  // (repeated ids OR their positions)
         return (float)x;
     }
@@ -59,18 +96,20 @@ struct PenaltyMap {
 };
 
 // 16-bit rows come with 16-bit keys: every key becomes the fp32 one.  fp32 rows: only the touched tokens' keys change.
-template <int DT>
-struct PenaltyMapT : PenaltyMap {
+using PenaltyMap = PenaltyMapP<ArgPen>;
+template <int DT, typename Pen = ArgPen>
+struct PenaltyMapT : PenaltyMapP<Pen> {
     __device__ __forceinline__ void chunk(int c, float (&f)[8], uint32_t (&k)[8]) const {
-        const uint32_t cb = ctx_byte(c);
+        const uint32_t cb = this->ctx_byte(c);
+        const uint32_t* slow = this->slow;
         const bool s = (slow[(c & (kSlowBits - 1)) >> 5] >> (c & 31)) & 1u;
         if (cb || s) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const bool in_ctx = (cb >> i) & 1u;
-                const uint32_t val = s ? find(8 * c + i) : 0u;
+                const uint32_t val = s ? this->find(8 * c + i) : 0u;
                 if (in_ctx || val) {
-                    f[i] = apply(f[i], in_ctx, val);
+                    f[i] = this->apply(f[i], in_ctx, val);
                     if (DT == HYD_F32) k[i] = key32(__builtin_bit_cast(uint32_t, f[i]));
                 }
             }

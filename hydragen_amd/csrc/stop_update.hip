@@ -43,6 +43,7 @@ __global__ __launch_bounds__(64) void stop_update_kernel(const StopArgs a) {
                     kept = t + 1 - len;
                 }
             }
+            if (r == 0 && a.max_len && t + 1 >= a.max_len[b]) r = 3;  // the row's own limit (hyd_stop_update_rows): length t + 1, stop_index stays -1
             a.length[b] = kept;  // (d) a running row: t + 1
             if (r != 0) {
                 a.reason[b] = r;

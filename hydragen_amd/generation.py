@@ -15,11 +15,25 @@ from . import layer_ops, sampling, scoring, speculative, stopping
 from .tp import check_collectives
 
 
+def per_row_sampling(temperature, top_k=None, top_p=None, min_p=None, penalties=None, seed=None) -> bool:
+    """A sampling value is given per row, or the rows draw with seeds of their own (sampling.sample_route's per_row)."""
+    return (seed is not None or any(sampling.is_per_row(v) for v in (temperature, top_k, top_p, min_p))
+            or (penalties is not None and penalties.per_row()))
+
+
 def draw_tokens(route: sampling.SampleRoute, logits, temperature, num_samples=1, top_p=None, top_k=None, min_p=None,
-                return_logprobs=False, penalties=None, constraint=None):
+                return_logprobs=False, penalties=None, constraint=None, seed=None, offset=0):
     """Run one draw along `route` (sampling.sample_route's table): (tokens [B, num_samples], their fp32 log-probs
     [B, num_samples] or, for a draw in torch that needs none, None).  The other arguments are sample_from_logits'."""
     x, n = logits, num_samples
+    if per_row_sampling(temperature, top_k, top_p, min_p, penalties, seed):
+        # the per_row routes: one launch over one row per sample (the values and seeds are the batch rows'), rows a kernel cannot
+        # take as they are made contiguous; CPU rows: the definition in torch (layer_ops.sample_tokens routes both)
+        x = x.repeat_interleave(n, 0) if n > 1 else x if x.stride(-1) == 1 else x.contiguous()
+        tok, lp = layer_ops.sample_tokens(
+            x, temperature, None if seed is None else (0, offset), top_k=top_k, top_p=top_p, min_p=min_p, return_logprobs=True,
+            penalties=penalties, constraint=(*constraint, True) if constraint is not None else None, seed=seed)
+        return tok.reshape(-1, num_samples), lp.reshape(-1, num_samples)
     if route.torch_penalties:  # the definition, float64 through [B, V] tables
         x = penalties.apply(x, n).float()
     if route.torch_mask:
@@ -83,6 +97,9 @@ class _DecodeCall:
     penalty_args: Optional[tuple] = None       # (repetition, presence, frequency, logit_bias, one of the first three is on), if any is on
     constraint_args: Optional[tuple] = None    # (dfa, the given start states or None, return the final states)
     draft: Optional[_Draft] = None             # speculative decoding
+    rows: Optional[dict] = None                # per-row arguments as the caller gave them, host-checked: sampling values, "seed", "limits"
+    max_len: Optional[Tensor] = None           # per-row max_new_tokens: int32 [batch] on the model's device (the stop loop)
+    seeded: bool = False                       # seed=: the draw of output position t uses offset t and the rows' seeds
     state: Optional[Tensor] = None             # the automaton states, if they are returned
     route: Optional[sampling.SampleRoute] = None  # of the steps' draws (the first draw, which may fan out, has its own)
     pen: Optional[layer_ops.Penalties] = None  # the penalties, if they keep a list of generated tokens (a bias alone does not)
@@ -115,9 +132,40 @@ def check_arguments(model, *, input_ids, starting_logits, num_return_sequences, 
                     return_logits, disable_hydragen, disable_attention, disable_hierarchy, token_overrides, return_logprobs,
                     top_logprobs, repetition_penalty, presence_penalty, frequency_penalty, logit_bias, stop, pad_token_id,
                     include_stop, return_finish, constraint, constraint_state, return_constraint_state, draft_tokens, draft,
-                    ngram, return_draft_stats) -> _DecodeCall:
+                    ngram, return_draft_stats, seed=None) -> _DecodeCall:
     """generate()'s arguments but the prompt levels, checked on the host before any launch -> the call's _DecodeCall."""
     vocab, on_gpu = model.vocab_size, model.lm_head.weight.is_cuda
+    # per-row arguments: lists / 1-d tensors become host lists here (checked element by element); decode() repeats them per
+    # sample and uploads them once
+    rows = {}
+    given = dict(temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
+                 presence_penalty=presence_penalty, frequency_penalty=frequency_penalty)
+    for name, v in given.items():
+        if sampling.is_per_row(v):
+            vals = sampling.row_values(v.cpu() if isinstance(v, Tensor) else v, None, name)
+            if not vals:
+                raise ValueError(f"{name}: an empty list of per-row values")
+            if all(x == vals[0] for x in vals) and not (name == "temperature" and vals[0] is None):
+                given[name] = vals[0]  # every row equal: the scalar, and exactly the scalar call's launches
+            else:
+                rows[name] = vals
+    if seed is not None:
+        rows["seed"] = [int(v) for v in sampling.row_values(seed.cpu() if isinstance(seed, Tensor) else seed, None, "seed")]
+    if sampling.is_per_row(max_new_tokens):
+        limits = sampling.row_values(max_new_tokens.cpu() if isinstance(max_new_tokens, Tensor) else max_new_tokens, None, "max_new_tokens")
+        if not limits or any(isinstance(v, bool) or int(v) != v or v < 1 for v in limits):
+            raise ValueError(f"max_new_tokens per row: integers >= 1, got {limits}")
+        rows["limits"] = [int(v) for v in limits]
+        max_new_tokens = max(rows["limits"])
+    if rows and (draft_tokens or token_overrides is not None):
+        raise NotImplementedError("per-row sampling values, seed= and a per-row max_new_tokens cannot be combined with draft_tokens or "
+                                  "token_overrides: the draft loop draws several positions per step with one offset, and teacher "
+                                  f"forcing draws nothing (per row here: {', '.join(rows)})")
+    if "temperature" in rows:
+        if any(t is None or not t >= 0 for t in rows["temperature"]):
+            raise ValueError(f"temperature must be non-negative for every row, {rows['temperature']} is invalid")
+    temperature, top_k, top_p, min_p, repetition_penalty, presence_penalty, frequency_penalty = (
+        rows.get(name, v) for name, v in dict(given, temperature=0.0 if "temperature" in rows else given["temperature"]).items())
     penalties = (repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
     if constraint is None and (constraint_state is not None or return_constraint_state):
         raise ValueError("constraint_state / return_constraint_state need constraint=")
@@ -143,18 +191,20 @@ def check_arguments(model, *, input_ids, starting_logits, num_return_sequences, 
     elif return_draft_stats:
         raise ValueError("return_draft_stats needs draft_tokens")
     stop_spec = None
-    if isinstance(eos_token_id, (list, tuple)) or stop is not None or pad_token_id is not None or return_finish or spec_draft:
+    if isinstance(eos_token_id, (list, tuple)) or stop is not None or pad_token_id is not None or return_finish or spec_draft or "limits" in rows:
         if token_overrides is not None:
             raise ValueError("token_overrides (teacher forcing) has nothing to stop: it cannot be combined with a list of EOS ids, "
                              "stop, pad_token_id or return_finish")
+        if "limits" in rows and eos_token_id is not None and not isinstance(eos_token_id, (list, tuple, Tensor)):
+            eos_token_id = [eos_token_id]  # (the device-side stop path takes lists)
         stop_spec = stopping.check_stop(eos_token_id, stop, pad_token_id, include_stop, vocab)
-        if not on_gpu:
+        if not on_gpu and "limits" not in rows:  # (per-row limits on a CPU model: the stop loop on the torch definition)
             raise ValueError("stop conditions are decided by a HIP kernel (hyd_stop_update): the model must be on the GPU; "
                              "stopping.truncate_reference applies the same rules to CPU tokens")
         eos_token_id = None
     if (input_ids is None) == (starting_logits is None):
         raise ValueError("pass exactly one of input_ids and starting_logits")
-    if temperature < 0:
+    if "temperature" not in rows and temperature < 0:
         raise ValueError(f"temperature must be non-negative, {temperature} is invalid")
     sampling.check_filters(top_k, top_p, min_p)
     top_n = scoring.check_top_n(top_logprobs)
@@ -171,7 +221,8 @@ def check_arguments(model, *, input_ids, starting_logits, num_return_sequences, 
         fan=num_return_sequences, max_new_tokens=max_new_tokens, top_n=top_n, logits=[] if return_logits else None, logprobs=[] if return_logprobs else None,
         top=([], []) if top_n else None, eos=eos_token_id, overrides=token_overrides, stop=stop_spec, finish=return_finish,
         penalty_args=(*penalties, counted) if sampling.penalties_active(*penalties) else None,
-        constraint_args=None if constraint is None else (constraint, constraint_state, return_constraint_state), draft=spec_draft)
+        constraint_args=None if constraint is None else (constraint, constraint_state, return_constraint_state), draft=spec_draft,
+        rows=rows or None, seeded=seed is not None)
 
 
 def _check_draft(model, draft_tokens, draft, ngram, max_new_tokens, refused: dict, n_given: int = 0, constrained: bool = False) -> _Draft:
@@ -232,6 +283,33 @@ def _penalties(model, batch, unique, fan, max_new_tokens, repetition_penalty, pr
         gen_len=torch.zeros((batch,), dtype=torch.int32, device=dev) if counted else None)
 
 
+def _upload_rows(model, call: _DecodeCall, leaf_batch, fan):
+    """The call's per-row arguments, [leaf batch] (repeated per sample) or [batch] -- constraint_state's rule --, uploaded once:
+    they live on the model's device for the whole call (fp32 / int32 arrays as hyd_sample_tokens_rows reads them, the seeds as
+    int64 bit patterns, the limits as int32)."""
+    dev, batch = model.lm_head.weight.device, leaf_batch * fan
+    dtypes = {name: (dtype, off) for name, dtype, off in layer_ops.ROW_FIELDS}
+    dtypes.update(seed=(torch.int64, 0), limits=(torch.int32, 1))
+    for name, vals in call.rows.items():
+        if len(vals) == 1:
+            vals = vals * batch
+        if len(vals) not in (leaf_batch, batch):
+            raise ValueError(f"{'max_new_tokens' if name == 'limits' else name} holds {len(vals)} per-row values: {leaf_batch} "
+                             f"(one per prompt, repeated for num_return_sequences) or {batch}")
+        if len(vals) != batch:
+            vals = [v for v in vals for _ in range(fan)]
+        arr = layer_ops.row_array(vals, batch, dev, *dtypes[name], name)
+        if name == "limits":
+            call.max_len = arr
+        elif name in ("repetition_penalty", "presence_penalty", "frequency_penalty"):
+            if call.penalty_args is None:  # (a list of values that are all off)
+                continue
+            slot = dict(repetition_penalty=0, presence_penalty=1, frequency_penalty=2)[name]
+            call.penalty_args = tuple(arr if i == slot else v for i, v in enumerate(call.penalty_args))
+        else:
+            call.sample[name] = arr
+
+
 def _constraint_state(model, constraint_state, leaf_batch, fan):
     """The call's automaton states, int32 [batch] on the device: the given start states ([leaf batch], repeated per sample, or
     [batch]), default 0."""
@@ -253,6 +331,8 @@ def decode(model, call: _DecodeCall, prefill_logits, shared, unique):
 
     samp, fan = call.sample, call.fan
     leaf_batch = prefill_logits.shape[0]
+    if call.rows is not None:
+        _upload_rows(model, call, leaf_batch, fan)
     if call.penalty_args is not None:
         samp["penalties"] = _penalties(model, leaf_batch * fan, unique, fan, call.max_new_tokens, *call.penalty_args)
     if call.constraint_args is not None:
@@ -320,12 +400,13 @@ def decode(model, call: _DecodeCall, prefill_logits, shared, unique):
         return _decode_steps(model, call, first, feed, start)
 
 
-def _step(model, call: _DecodeCall, input_ids, position_ids):
-    """One decode step along the call's route: (logits [B, V], tokens [B, 1], log-probs or None)."""
+def _step(model, call: _DecodeCall, input_ids, position_ids, t=0):
+    """One decode step along the call's route: (logits [B, V], tokens [B, 1], log-probs or None).  t: the output position the
+    step draws (the offset of a seeded draw)."""
     logits = model(input_ids=input_ids, position_ids=position_ids, use_graph=call.graphed, raw_logits=call.raw)[:, -1]
     if call.logits is not None:
         call.logits.append(logits)
-    return (logits,) + draw_tokens(call.route, logits, **call.sample)
+    return (logits,) + draw_tokens(call.route, logits, **call.sample, **(dict(offset=t) if call.seeded else {}))
 
 
 def _decode_steps(model, call: _DecodeCall, first, feed, start):
@@ -333,7 +414,7 @@ def _decode_steps(model, call: _DecodeCall, first, feed, start):
     done = (first == eos) if eos is not None else None
     tokens = [first]
     for step in range(call.max_new_tokens - 1):
-        logits, nxt, lp = _step(model, call, feed, start + step)
+        logits, nxt, lp = _step(model, call, feed, start + step, step + 1)
         if done is not None:
             done = done | (nxt == eos)
             if bool(done.all()):
@@ -415,18 +496,23 @@ def _decode_steps_stop(model, call: _DecodeCall, first, start):
     retire, shared_len, start_pos = _row_origin(model, start)
     out, length, reason, stop_index, live = stopping.new_state(first.shape[0], call.max_new_tokens, spec, dev)
     stop_tokens = spec.stop_table(dev)[0] if spec.stops else None
-    poll = _RunningPoll(model, call.max_new_tokens)
+    poll = _RunningPoll(model, call.max_new_tokens) if dev.type == "cuda" else None  # (CPU rows: live is read as it is)
 
     def update(tok, t):
-        return layer_ops.stop_update(tok, t, spec, out, length, reason, stop_index, live, start_pos, shared_len, retire, stop_tokens)
+        return layer_ops.stop_update(tok, t, spec, out, length, reason, stop_index, live, start_pos, shared_len, retire, stop_tokens,
+                                     max_len=call.max_len)
 
     feed, pos = update(first, 0)
     steps = 1  # columns of `out` written
     for step in range(call.max_new_tokens - 1):
-        logits, nxt, lp = _step(model, call, feed[:, None], pos[:, None])
+        logits, nxt, lp = _step(model, call, feed[:, None], pos[:, None], steps)
         call.keep(logits, nxt, lp)
         feed, pos = update(nxt, steps)
         steps += 1
+        if poll is None:
+            if int(live[steps - 1]) == 0:
+                break
+            continue
         if poll.none_running():
             break
         poll.start(live, steps, steps - 1)

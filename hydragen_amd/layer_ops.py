@@ -1,4 +1,4 @@
-"""Python face of `hyd_add_rmsnorm` / `hyd_swiglu` / `hyd_sample_tokens[_filtered]` / `hyd_token_logprobs` / `hyd_stop_update` (include/hydragen_hip.h): the elementwise glue of the decoder layer
+"""Python face of `hyd_add_rmsnorm` / `hyd_swiglu` / `hyd_sample_tokens[_filtered | _rows]` / `hyd_token_logprobs` / `hyd_stop_update[_rows]` (include/hydragen_hip.h): the elementwise glue of the decoder layer
 around the attention block -- residual add + RMSNorm (/root/reference/hydragen/llama.py:615-631 with transformers'
 LlamaRMSNorm, llama.py:605-608,656) and the SwiGLU gate (transformers' LlamaMLP, llama.py:2,604) -- each as one
 HIP kernel instead of two torch launches."""
@@ -117,6 +117,40 @@ def _fill_rows(p, logits: Tensor, outs: tuple, temperature: float, key: Optional
         p.top_k, p.top_p, p.min_p = int(top_k or 0), 1.0 if top_p is None else float(top_p), float(min_p or 0.0)
 
 
+def row_array(v, rows: int, device, dtype, off, what: str = "value") -> Optional[Tensor]:
+    """A per-row sampling argument as the [rows] device array hyd_sample_tokens_rows reads, or None for a scalar (which stays
+    in the parameter block).  Lists / tuples (None inside = `off`) and tensors of 1 or `rows` entries are taken; a tensor that
+    already is a contiguous [rows] array of `dtype` on the device is passed as it is (generate() uploads its arrays once per
+    call).  Nothing synchronises."""
+    if not sampling.is_per_row(v):
+        return None
+    if isinstance(v, Tensor):
+        t = v.reshape(-1)
+        if dtype == torch.int64 and t.dtype == torch.uint64:
+            t = t.view(torch.int64)
+        t = t.to(device=device, dtype=dtype)
+    else:
+        vals = [off if x is None else x for x in v]
+        if dtype == torch.int64:  # seeds: 64 bits, carried as their two's-complement pattern
+            vals = [((int(x) & 0xFFFFFFFFFFFFFFFF) ^ (1 << 63)) - (1 << 63) for x in vals]
+        t = torch.tensor(vals, dtype=dtype).to(device)
+    if t.numel() == 1 and rows != 1:
+        t = t.expand(rows)
+    if t.shape != (rows,):
+        raise ValueError(f"{what}: {t.numel()} per-row values for {rows} rows")
+    return t.contiguous()
+
+
+ROW_FIELDS = (("temperature", torch.float32, 0.0), ("top_k", torch.int32, 0), ("top_p", torch.float32, 1.0), ("min_p", torch.float32, 0.0),
+              ("repetition_penalty", torch.float32, 1.0), ("frequency_penalty", torch.float32, 0.0), ("presence_penalty", torch.float32, 0.0))
+
+
+def _scalar_or(v, off):
+    """What goes into the parameter block's scalar: the value, or `off` where an array overrides it (the entry point checks the
+    scalars whatever the arrays are)."""
+    return off if v is None or sampling.is_per_row(v) else v
+
+
 @dataclass
 class Penalties:
     """What sampling.py's penalty definition needs for a batch of rows: the scalars, the bias list as (ids int64 [K], values fp32
@@ -135,6 +169,10 @@ class Penalties:
 
     def active(self) -> bool:
         return sampling.penalties_active(self.repetition_penalty, self.presence_penalty, self.frequency_penalty, self.logit_bias)
+
+    def per_row(self) -> bool:
+        """One of the three scalars is a list or a tensor of per-row values."""
+        return any(sampling.is_per_row(v) for v in (self.repetition_penalty, self.presence_penalty, self.frequency_penalty))
 
     def apply(self, logits: Tensor, rows_per_sample: int = 1) -> Tensor:
         """sampling.penalize_logits of these penalties (float64).  rows_per_sample = s > 1: `logits` holds one row for every s
@@ -187,14 +225,19 @@ def token_bitmap(ids: Tensor, lens: Optional[Tensor], n: int, out: Optional[Tens
     return bits
 
 
-def sample_tokens_penalized(logits: Tensor, temperature: float, key: Optional[tuple] = None, *, penalties: Penalties,
-                            top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None,
-                            constraint: Optional[tuple] = None):
+def sample_tokens_penalized(logits: Tensor, temperature, key: Optional[tuple] = None, *, penalties: Penalties,
+                            top_k=None, top_p=None, min_p=None, constraint: Optional[tuple] = None, seed=None):
     """hyd_sample_tokens_penalized, one launch whatever the penalties are (neutral ones included): ([B, 1] int64 tokens, [B] fp32
     log-probs under softmax(penalised logits), [B] int32 number of kept tokens).  hydragen_amd/sampling.py states the
     definition.  Nothing of size [B, V] is allocated and nothing synchronises; the bias list must already be checked
     (sampling.check_penalties) and on the device.  constraint = (dfa, state int32 [B], advance): hyd_sample_tokens_constrained
-    instead -- the same launch behind the automaton's mask (sample_tokens_constrained)."""
+    instead -- the same launch behind the automaton's mask (sample_tokens_constrained).
+    temperature, top_k, top_p, min_p and the penalties' three scalars may each be PER ROW (a list with None = off, or a tensor of
+    [B] entries; sampling.py), and seed= one integer per row: hyd_sample_tokens_rows, one launch, each row bit for bit what a
+    scalar call with its values returns for it.  Per-row values reach the kernel as fp32 (top_k int32); they are checked on
+    the host only where they are host values (lists), the kernel sanitises what it reads (include/hydragen_hip.h).  With seed=
+    row r's noise is that of row 0 of a call with key = (seed[r], offset): its draw does not depend on its place in the batch,
+    and the device's generator is not advanced (key = (anything, offset); None: offset 0)."""
     outs = _draw_outputs(logits, stats=True)
     rows, n = logits.shape
     dev, pen = logits.device, penalties
@@ -229,40 +272,51 @@ def sample_tokens_penalized(logits: Tensor, temperature: float, key: Optional[tu
                 or ids.device != dev or values.device != dev or not ids.is_contiguous() or not values.is_contiguous()):
             raise ValueError(f"logit_bias must be (ids int64 [K], values fp32 [K]) on {dev}: sampling.normalize_logit_bias")
         p.bias_ids, p.bias_values, p.n_bias = ids.data_ptr(), values.data_ptr(), ids.numel()
-    p.repetition_penalty = 1.0 if pen.repetition_penalty is None else float(pen.repetition_penalty)
-    p.frequency_penalty, p.presence_penalty = float(pen.frequency_penalty or 0.0), float(pen.presence_penalty or 0.0)
-    _fill_rows(p, logits, outs, temperature, key, top_k, top_p, min_p)
-    if constraint is None:
+    given = dict(temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, repetition_penalty=pen.repetition_penalty,
+                 frequency_penalty=pen.frequency_penalty, presence_penalty=pen.presence_penalty)
+    arrays = [row_array(given[name], rows, dev, dtype, off, name) for name, dtype, off in ROW_FIELDS]
+    arrays.append(row_array(seed, rows, dev, torch.int64, 0, "seed"))
+    per_row = any(a is not None for a in arrays)
+    p.repetition_penalty = float(_scalar_or(pen.repetition_penalty, 1.0))
+    p.frequency_penalty, p.presence_penalty = float(_scalar_or(pen.frequency_penalty, 0.0)), float(_scalar_or(pen.presence_penalty, 0.0))
+    if seed is not None and key is None:
+        key = (0, 0)
+    _fill_rows(p, logits, outs, _scalar_or(temperature, 0.0), key, _scalar_or(top_k, 0), _scalar_or(top_p, 1.0), _scalar_or(min_p, 0.0))
+    c = None
+    if constraint is not None:
+        dfa, state, advance = constraint
+        c = _lib.TokenDfa()
+        c.allowed, c.next, c.state = dfa.allowed.data_ptr(), dfa.next.data_ptr(), state.data_ptr()
+        c.allowed_stride, c.next_stride, c.n_states, c.advance = dfa.allowed.shape[1], n, dfa.next.shape[0], int(bool(advance))
+    if per_row:
+        _lib.check(_lib.load().hyd_sample_tokens_rows(C.byref(p), None if c is None else C.byref(c),
+                                                     *(None if a is None else a.data_ptr() for a in arrays), _stream()))
+    elif c is None:
         _lib.check(_lib.load().hyd_sample_tokens_penalized(C.byref(p), _stream()))
-        return outs
-    dfa, state, advance = constraint
-    c = _lib.TokenDfa()
-    c.allowed, c.next, c.state = dfa.allowed.data_ptr(), dfa.next.data_ptr(), state.data_ptr()
-    c.allowed_stride, c.next_stride, c.n_states, c.advance = dfa.allowed.shape[1], n, dfa.next.shape[0], int(bool(advance))
-    _lib.check(_lib.load().hyd_sample_tokens_constrained(C.byref(p), C.byref(c), _stream()))
+    else:
+        _lib.check(_lib.load().hyd_sample_tokens_constrained(C.byref(p), C.byref(c), _stream()))
     return outs
 
 
 def sample_tokens_constrained(logits: Tensor, temperature: float, key: Optional[tuple] = None, *, constraint: tuple,
-                              penalties: Optional[Penalties] = None, top_k: Optional[int] = None, top_p: Optional[float] = None,
-                              min_p: Optional[float] = None):
+                              penalties: Optional[Penalties] = None, top_k=None, top_p=None, min_p=None, seed=None):
     """hyd_sample_tokens_constrained, one launch: sample_tokens_penalized (penalties None: neutral ones, which is
     sample_tokens_filtered) on the logits with the tokens that a row's automaton state does not allow at -inf -- bit for bit --
     without a [B, V] mask.  constraint = (dfa, state, advance): dfa a constraint.TokenDFA on the logits' device, state int32 [B]
     on the device (rows outside [0, S) are unconstrained); advance: state[row] = next[state[row], token] after the draw, in place.
     hydragen_amd/sampling.py states the definition.  Returns ([B, 1] int64 tokens, [B] fp32 log-probs of the constrained
-    distribution, [B] int32 kept counts)."""
+    distribution, [B] int32 kept counts).  Per-row values and seed=: as sample_tokens_penalized."""
     dfa, state, _ = constraint
     sampling.check_constraint(dfa, logits.shape[-1], logits.shape[0], state)
     if dfa.next.device != logits.device or state.device != logits.device:
         raise ValueError(f"constraint: the automaton is on {dfa.next.device}, the state on {state.device}, the logits on {logits.device}")
     return sample_tokens_penalized(logits, temperature, key, penalties=Penalties() if penalties is None else penalties, top_k=top_k,
-                                   top_p=top_p, min_p=min_p, constraint=constraint)
+                                   top_p=top_p, min_p=min_p, constraint=constraint, seed=seed)
 
 
-def sample_tokens(logits: Tensor, temperature: float, key: Optional[tuple] = None, *, top_k: Optional[int] = None,
-                  top_p: Optional[float] = None, min_p: Optional[float] = None, return_logprobs: bool = False,
-                  penalties: Optional[Penalties] = None, constraint: Optional[tuple] = None):
+def sample_tokens(logits: Tensor, temperature, key: Optional[tuple] = None, *, top_k=None, top_p=None, min_p=None,
+                  return_logprobs: bool = False, penalties: Optional[Penalties] = None, constraint: Optional[tuple] = None,
+                  seed=None):
     """[B, V] logits (fp16 / bf16 / fp32, rows contiguous) -> [B, 1] int64 tokens drawn from softmax(logits / temperature)
     (temperature 0: argmax) in one kernel.  top_k / top_p / min_p cut the UNSCALED softmax(logits) first (hydragen_amd/
     sampling.py states the rules); return_logprobs also returns the [B, 1] fp32 log softmax(logits) of each drawn token.
@@ -272,11 +326,21 @@ def sample_tokens(logits: Tensor, temperature: float, key: Optional[tuple] = Non
     then log softmax(penalised logits), the distribution the draw's policy is defined by.  constraint = (dfa, state, advance)
     (sample_tokens_constrained): hyd_sample_tokens_constrained, which also advances `state` in place.  CPU logits with
     penalties or a constraint: their float64 definition in torch (no HIP kernel takes CPU tensors).  constraint None or
-    neutral penalties: exactly the calls made without them."""
+    neutral penalties: exactly the calls made without them.
+    Per-row values (temperature, the cuts, the penalties' scalars as lists or [B] tensors) or seed= (one integer per row):
+    sample_route's per_row routes -- always a kernel on GPU rows, through hyd_sample_tokens_rows (sample_tokens_penalized says
+    what a row then returns); CPU rows: the per-row definition, sampling.reference_draw."""
     pen = penalties if penalties is not None and penalties.active() else None
     cuts = dict(top_k=top_k, top_p=top_p, min_p=min_p)
+    per_row = seed is not None or any(sampling.is_per_row(v) for v in (temperature, top_k, top_p, min_p)) or (pen is not None and pen.per_row())
     draw = sampling.sample_route(logits.is_cuda, True, True, 1, constraint is not None, pen is not None,
-                                 filters_active(top_k, top_p, min_p), return_logprobs).draw
+                                 filters_active(top_k, top_p, min_p), return_logprobs, per_row=per_row).draw
+    if per_row and not logits.is_cuda:
+        draw = sampling.CONSTRAINED if constraint is not None else sampling.PENALIZED  # CPU rows: the definition in torch, below
+    if per_row and logits.is_cuda:
+        tok, lp, _ = sample_tokens_penalized(logits, temperature, key, penalties=Penalties() if pen is None else pen,
+                                             constraint=constraint if draw == sampling.CONSTRAINED else None, seed=seed, **cuts)
+        return (tok, lp[:, None]) if return_logprobs else tok
     if draw == sampling.PLAIN:
         outs = _draw_outputs(logits, stats=False)
         if logits.shape[0] > 0:
@@ -293,7 +357,8 @@ def sample_tokens(logits: Tensor, temperature: float, key: Optional[tuple] = Non
     else:
         dfa, state, advance = constraint if constraint is not None else (None, None, False)
         x = logits if pen is None else pen.apply(logits)
-        tok, lp, drawn = sampling.reference_draw(x, temperature, dfa=dfa, state=state, **cuts)
+        tok, lp, drawn = sampling.reference_draw(x, temperature, dfa=dfa, state=state, seed=seed,
+                                                 offset=0 if key is None else key[1], **cuts)
         if advance:
             state.copy_(sampling.advance_state(dfa, state, tok, drawn))
         if pen is not None and pen.append:
@@ -353,13 +418,14 @@ def token_logprobs(logits: Tensor, targets: Tensor, top_n: int = 0):
 
 def stop_update(tok: Tensor, t: int, spec: stopping.StopSpec, out: Tensor, length: Tensor, reason: Tensor, stop_index: Tensor,
                 live: Tensor, start_pos: Tensor, shared_len: Optional[Tensor] = None, retire: bool = True,
-                stop_tokens: Optional[Tensor] = None):
+                stop_tokens: Optional[Tensor] = None, max_len: Optional[Tensor] = None):
     """hyd_stop_update, one launch: judge the tokens `tok` [rows] (or [rows, 1]) int64 just drawn as step t of a generation whose
     state is (out int64 [rows, steps], length / reason / stop_index int32 [rows], live int32 [steps]; stopping.new_state), update
     that state in place and return (feed, next_pos) int64 [rows] for the next decode step; hydragen_amd/stopping.py states the
     rules.  start_pos int64 [rows]: the position step 0's token is fed at; shared_len int64 [rows] or None and retire: a finished
     row's position becomes shared_len - 1, which retires it from the unique K/V stream.  stop_tokens: spec.stop_table(device)[0]
-    made once per generation (None: made here, one host-to-device copy).  Nothing synchronises.  CPU tensors take
+    made once per generation (None: made here, one host-to-device copy).  max_len int32 [rows] on the device: a limit per row
+    (hyd_stop_update_rows, reason 3; stopping.py rule (c')).  Nothing synchronises.  CPU tensors take
     stopping.stop_update_reference."""
     tok = tok.reshape(-1)
     rows = tok.shape[0]
@@ -377,8 +443,10 @@ def stop_update(tok: Tensor, t: int, spec: stopping.StopSpec, out: Tensor, lengt
         raise ValueError(f"out is on {out.device}, tok on {tok.device}")
     if not 0 <= t < steps:
         raise ValueError(f"t {t} outside [0, {steps})")
+    if max_len is not None and (max_len.dtype != torch.int32 or max_len.shape != (rows,) or not max_len.is_contiguous() or max_len.device != tok.device):
+        raise ValueError(f"max_len must be a contiguous int32 [{rows}] on {tok.device}, got {tuple(max_len.shape)} {max_len.dtype} on {max_len.device}")
     if not tok.is_cuda:
-        return stopping.stop_update_reference(tok, t, spec, out, length, reason, stop_index, live, start_pos, shared_len, retire)
+        return stopping.stop_update_reference(tok, t, spec, out, length, reason, stop_index, live, start_pos, shared_len, retire, max_len)
     _require_gpu(tok)
     lib = _lib.load()
     tok = tok.contiguous()
@@ -406,5 +474,8 @@ def stop_update(tok: Tensor, t: int, spec: stopping.StopSpec, out: Tensor, lengt
     p.out_stride, p.pad = out.stride(0) if rows > 1 else steps, spec.pad
     p.rows, p.t, p.n_eos, p.n_stop = rows, t, len(spec.eos), len(spec.stops)
     p.include_stop, p.retire = int(spec.include_stop), int(bool(retire))
-    _lib.check(lib.hyd_stop_update(C.byref(p), _stream()))
+    if max_len is None:
+        _lib.check(lib.hyd_stop_update(C.byref(p), _stream()))
+    else:
+        _lib.check(lib.hyd_stop_update_rows(C.byref(p), max_len.data_ptr(), _stream()))
     return feed, next_pos

@@ -1058,23 +1058,28 @@ class HydragenLlamaForCausalLM(nn.Module):
         return sampling.apply_top_p(logits, top_p, min_tokens_to_keep, filter_value)
 
     def sample_route(self, cuda, unit_rows, temperature, num_samples=1, top_p=None, top_k=None, min_p=None, return_logprobs=False,
-                     penalties=None, constraint=None) -> sampling.SampleRoute:
+                     penalties=None, constraint=None, seed=None, offset=0) -> sampling.SampleRoute:
         """sampling.sample_route of a sample_from_logits call on logits that are on the GPU (cuda) and 2-D of unit last stride
         (unit_rows), with the model's two switches as they are now."""
+        if generation.per_row_sampling(temperature, top_k, top_p, min_p, penalties, seed):
+            return sampling.sample_route(cuda, cuda and unit_rows, cuda, num_samples, constraint is not None,
+                                         penalties is not None and penalties.active(), True, return_logprobs, per_row=True)
         ok = cuda and temperature >= 0
         return sampling.sample_route(cuda, ok and unit_rows, ok, num_samples, constraint is not None,
                                      penalties is not None and penalties.active(), sampling.filters_active(top_k, top_p, min_p),
                                      return_logprobs, self.fused_sampling_filters, self.fused_sampling_penalties)
 
     def sample_from_logits(self, logits, temperature, num_samples=1, top_p=None, top_k=None, min_p=None,
-                           return_logprobs=False, penalties=None, constraint=None):
+                           return_logprobs=False, penalties=None, constraint=None, seed=None, offset=0):
         """Tokens [B, num_samples] (and, with return_logprobs, their fp32 log softmax(logits) [B, num_samples]).  The cuts
         act on the unscaled softmax(logits), before the temperature (hydragen_amd/sampling.py).  penalties (a
         layer_ops.Penalties with something switched on): cuts, draw and log-prob act on the penalised logits instead; the
         drawn tokens are appended to its list when it says so.  constraint = (dfa, state int32 [B * num_samples]): every rule
         acts on the logits behind the automaton's mask and `state` advances in place.  Which kernel or torch stage does what
-        is sampling.sample_route's table; generate() decides it once for its first draw and once for its steps."""
-        args = (temperature, num_samples, top_p, top_k, min_p, return_logprobs, penalties, constraint)
+        is sampling.sample_route's table; generate() decides it once for its first draw and once for its steps.  temperature,
+        the cuts and the penalties' scalars may be per row (lists or [B * num_samples] tensors), seed one integer per row with
+        offset (layer_ops.sample_tokens): the per_row routes, one launch whatever num_samples is."""
+        args = (temperature, num_samples, top_p, top_k, min_p, return_logprobs, penalties, constraint, seed, offset)
         route = self.sample_route(logits.is_cuda, logits.ndim == 2 and logits.stride(-1) == 1, *args)
         tok, lp = generation.draw_tokens(route, logits, *args)
         return (tok, lp) if return_logprobs else tok
@@ -1312,7 +1317,8 @@ class HydragenLlamaForCausalLM(nn.Module):
                  presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None, logit_bias=None,
                  stop=None, pad_token_id: Optional[int] = None, include_stop: bool = False, return_finish: bool = False,
                  constraint=None, constraint_state: Optional[Tensor] = None, return_constraint_state: bool = False,
-                 draft_tokens: Optional[int] = None, draft="prompt_lookup", ngram=(1, 3), return_draft_stats: bool = False):
+                 draft_tokens: Optional[int] = None, draft="prompt_lookup", ngram=(1, 3), return_draft_stats: bool = False,
+                 seed=None):
         """Prompts and caches: input_ids is one level or a list of levels, outermost first, seq_lens their lengths (right padding;
         the contract above _prompt_levels); starting_logits instead of input_ids continues from levels kept by an earlier call.
         shared_cache_op: "wipe" / "preserve" / "extend".  disable_hydragen / disable_hierarchy / disable_attention are the
@@ -1339,6 +1345,21 @@ class HydragenLlamaForCausalLM(nn.Module):
         complete.  return_logprobs reports the CONSTRAINED distribution (the same rule as for penalties); return_logits and
         top_logprobs stay raw.  Not with token_overrides.  With constraint=None, generate() runs exactly the launches it runs
         without these arguments.
+
+        Per row (hyd_sample_tokens_rows, hyd_stop_update_rows; requests of different settings batched behind one shared
+        prompt): temperature, top_k, top_p, min_p, repetition_penalty, presence_penalty and frequency_penalty may each be a list
+        or 1-d tensor instead of a scalar, with one entry per prompt of the innermost level (repeated for num_return_sequences)
+        or one per row of the batch -- constraint_state's rule; None inside a list switches the value off for that row (not for
+        temperature).  The values are checked on the host, uploaded once and stay on the device for the call; every draw, the
+        first one with its fan-out included, is then ONE launch in which each row samples with its own values, bit for bit what
+        a call with that row's values in every row would give that row.  seed = one integer per row (same shape rule): the draw
+        of output position t uses the row's seed and offset t, torch's generator is not advanced, and a row's tokens depend
+        neither on its place in the batch nor on what torch drew earlier (on a CPU model the seeded draws come from torch
+        generators of their own: the same property, other tokens than on the GPU).  max_new_tokens as a list or tensor gives
+        every row a limit of its own (>= 1): the device-side stop path runs with it, a row that reaches its limit finishes
+        with reason 3 and is padded, fed pad and retired like a row that met an EOS id, the result is [B, max(lengths)], and the
+        penalties' list of generated tokens is sized by the largest limit.  A call that passes only scalars runs exactly the
+        launches it ran without these forms.  Refused (before any launch): any of them with draft_tokens or token_overrides.
 
         Stopping, decided on the device (hyd_stop_update; hydragen_amd/stopping.py states the rules): eos_token_id given as a
         LIST or tuple of ids (a list of one included), stop = a list of token-id sequences (lists, tuples or 1-d tensors, ragged; up
@@ -1378,7 +1399,7 @@ class HydragenLlamaForCausalLM(nn.Module):
         (return_logprobs), top_ids [B, generated, N] int64 and top_logprobs [B, generated, N] f32: for every returned token the N
         best alternatives of that step's distribution (top_logprobs = N > 0, needs return_logprobs; hyd_token_logprobs,
         hydragen_amd/scoring.py), a stopping.Finish(lengths, reasons, stop_index) (return_finish; int32 [B] each; reason 0 = ran
-        to max_new_tokens, 1 = EOS, 2 = stop sequence), the final int32 [B] automaton states (return_constraint_state), a
+        to max_new_tokens, 1 = EOS, 2 = stop sequence, 3 = the row's own limit), the final int32 [B] automaton states (return_constraint_state), a
         speculative.DraftStats(steps, proposed, accepted) whose .forced holds, per row, the proposed drafts that were forced
         under a constraint (return_draft_stats))."""
         if not self.kv_cache_allocated:
@@ -1392,7 +1413,7 @@ class HydragenLlamaForCausalLM(nn.Module):
             frequency_penalty=frequency_penalty, logit_bias=logit_bias, stop=stop, pad_token_id=pad_token_id, include_stop=include_stop,
             return_finish=return_finish, constraint=constraint, constraint_state=constraint_state,
             return_constraint_state=return_constraint_state, draft_tokens=draft_tokens, draft=draft, ngram=ngram,
-            return_draft_stats=return_draft_stats)
+            return_draft_stats=return_draft_stats, seed=seed)
         fan_out = num_return_sequences > 1
         flatten = disable_hierarchy or disable_hydragen  # the baselines keep the last level per sequence
         if shared_cache_op == SharedCacheOp.WIPE:

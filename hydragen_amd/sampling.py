@@ -21,11 +21,64 @@ import torch
 from torch import Tensor
 
 
-def filters_active(top_k: Optional[int], top_p: Optional[float], min_p: Optional[float]) -> bool:
-    return bool(top_k) or (top_p is not None and top_p < 1.0) or bool(min_p)
+# ---- per-row values ---------------------------------------------------------------------------------------------------------
+# Every sampling parameter below -- temperature, top_k, top_p, min_p and the three penalties -- is a scalar (or None = off) for
+# all rows, or PER ROW: a list / tuple (None inside = off for that row) or a 1-d tensor with one entry per row; one entry
+# alone is broadcast.  Row r of a per-row call is, by definition, row r of the scalar call with row r's values: the functions
+# group the rows by their values and run the scalar definition on each group (every step of it acts on rows independently).
+def is_per_row(v) -> bool:
+    return isinstance(v, (list, tuple, Tensor))
 
 
-def check_filters(top_k: Optional[int], top_p: Optional[float], min_p: Optional[float]) -> None:
+def row_values(v, rows: Optional[int] = None, what: str = "value") -> list:
+    """A per-row argument as a list of `rows` Python scalars (None kept); a scalar is repeated."""
+    if not is_per_row(v):
+        return [v] * (1 if rows is None else rows)
+    if isinstance(v, Tensor):
+        if v.ndim > 1:
+            raise ValueError(f"{what}: per-row values are 1-d, got {tuple(v.shape)}")
+        v = v.reshape(-1).tolist()
+    v = list(v)
+    if rows is not None and len(v) == 1:
+        v = v * rows
+    if rows is not None and len(v) != rows:
+        raise ValueError(f"{what}: {len(v)} per-row values for {rows} rows")
+    return v
+
+
+def row_groups(rows: int, **params) -> Optional[list]:
+    """None if every parameter is a scalar; else [(row indices int64 [k], {name: that group's scalar})], the rows with equal
+    values together, in order of first appearance (one group if every row is equal)."""
+    if not any(is_per_row(v) for v in params.values()):
+        return None
+    cols = {k: row_values(v, rows, k) for k, v in params.items()}
+    groups: dict = {}
+    for r in range(rows):
+        groups.setdefault(tuple(cols[k][r] for k in params), []).append(r)
+    return [(torch.tensor(idx, dtype=torch.int64), dict(zip(params, key))) for key, idx in groups.items()]
+
+
+def _each(v):
+    """The host values of an argument: a scalar, the entries of a list, and nothing of a tensor (tensors may live on a device and
+    are not read back: the kernel sanitises what it reads, the torch definition checks each group's scalars)."""
+    return () if isinstance(v, Tensor) else row_values(v) if is_per_row(v) else (v,)
+
+
+def filters_active(top_k, top_p, min_p) -> bool:
+    if any(isinstance(v, Tensor) for v in (top_k, top_p, min_p)):
+        return True
+    return any(bool(k) for k in _each(top_k)) or any(p is not None and p < 1.0 for p in _each(top_p)) or any(bool(m) for m in _each(min_p))
+
+
+def check_filters(top_k, top_p, min_p) -> None:
+    if is_per_row(top_k) or is_per_row(top_p) or is_per_row(min_p):  # element by element, the same messages
+        for k in _each(top_k):
+            check_filters(k, None, None)
+        for p_ in _each(top_p):
+            check_filters(None, p_, None)
+        for m in _each(min_p):
+            check_filters(None, None, m)
+        return
     if top_k is not None and top_k < 0:
         raise ValueError(f"top_k {top_k} must be >= 0 (0 or None = off)")
     if top_p is not None and not (0.0 < top_p <= 1.0):
@@ -35,10 +88,16 @@ def check_filters(top_k: Optional[int], top_p: Optional[float], min_p: Optional[
 
 
 @torch.no_grad()
-def kept_mask(logits: Tensor, top_k: Optional[int] = None, top_p: Optional[float] = None,
-              min_p: Optional[float] = None) -> Tensor:
-    """[..., n] bool: the tokens the cuts keep (module docstring), computed in float64."""
+def kept_mask(logits: Tensor, top_k=None, top_p=None, min_p=None) -> Tensor:
+    """[..., n] bool: the tokens the cuts keep (module docstring), computed in float64.  Per-row values: logits [B, n]."""
     check_filters(top_k, top_p, min_p)
+    groups = row_groups(logits.shape[0], top_k=top_k, top_p=top_p, min_p=min_p) if logits.ndim == 2 else None
+    if groups is not None:
+        keep = torch.empty(logits.shape, dtype=torch.bool, device=logits.device)
+        for idx, vals in groups:
+            idx = idx.to(logits.device)
+            keep[idx] = kept_mask(logits[idx], **vals)
+        return keep
     x = logits.double()
     valid = ~(torch.isnan(x) | (x == -math.inf))
     xm = torch.where(valid, x, torch.full_like(x, -math.inf))
@@ -65,8 +124,7 @@ def kept_mask(logits: Tensor, top_k: Optional[int] = None, top_p: Optional[float
 
 
 @torch.no_grad()
-def filter_logits(logits: Tensor, top_k: Optional[int] = None, top_p: Optional[float] = None,
-                  min_p: Optional[float] = None) -> Tensor:
+def filter_logits(logits: Tensor, top_k=None, top_p=None, min_p=None) -> Tensor:
     """`logits` with every token the cuts remove (and every NaN) set to -inf, in the input dtype."""
     return logits.masked_fill(~kept_mask(logits, top_k, top_p, min_p), -math.inf)
 
@@ -109,25 +167,28 @@ def normalize_logit_bias(logit_bias, device=None):
     return ids.contiguous(), values.contiguous()
 
 
-def penalties_active(repetition_penalty: Optional[float] = None, presence_penalty: Optional[float] = None,
-                     frequency_penalty: Optional[float] = None, logit_bias=None) -> bool:
+def penalties_active(repetition_penalty=None, presence_penalty=None, frequency_penalty=None, logit_bias=None) -> bool:
     if isinstance(logit_bias, dict):
         has_bias = len(logit_bias) > 0
     else:
         has_bias = logit_bias is not None and len(logit_bias[0]) > 0
-    return ((repetition_penalty is not None and repetition_penalty != 1.0) or bool(presence_penalty) or bool(frequency_penalty)
-            or has_bias)
+    if any(isinstance(v, Tensor) for v in (repetition_penalty, presence_penalty, frequency_penalty)):
+        return True  # (per-row values on a device are not read back to find out)
+    return (any(r is not None and r != 1.0 for r in _each(repetition_penalty)) or any(bool(v) for v in _each(presence_penalty))
+            or any(bool(v) for v in _each(frequency_penalty)) or has_bias)
 
 
-def check_penalties(repetition_penalty: Optional[float] = None, presence_penalty: Optional[float] = None,
-                    frequency_penalty: Optional[float] = None, logit_bias=None, n: Optional[int] = None) -> None:
-    """Host validation (reads the bias list: call it before the decode loop, not inside).  n: the vocabulary size, if known."""
-    r = repetition_penalty
-    if r is not None and not (r > 0 and math.isfinite(r)):
-        raise ValueError(f"repetition_penalty {r} must be a finite number > 0 (1 or None = off)")
-    for name, v in (("presence_penalty", presence_penalty), ("frequency_penalty", frequency_penalty)):
-        if v is not None and not math.isfinite(v):
-            raise ValueError(f"{name} {v} must be finite (0 or None = off)")
+def check_penalties(repetition_penalty=None, presence_penalty=None, frequency_penalty=None, logit_bias=None,
+                    n: Optional[int] = None) -> None:
+    """Host validation (reads the bias list: call it before the decode loop, not inside).  n: the vocabulary size, if known.
+    Per-row lists are checked element by element, with the same messages."""
+    for r in _each(repetition_penalty):
+        if r is not None and not (r > 0 and math.isfinite(r)):
+            raise ValueError(f"repetition_penalty {r} must be a finite number > 0 (1 or None = off)")
+    for name, vs in (("presence_penalty", presence_penalty), ("frequency_penalty", frequency_penalty)):
+        for v in _each(vs):
+            if v is not None and not math.isfinite(v):
+                raise ValueError(f"{name} {v} must be finite (0 or None = off)")
     if logit_bias is None:
         return
     if not isinstance(logit_bias, dict) and not (isinstance(logit_bias, (tuple, list)) and len(logit_bias) == 2):
@@ -180,12 +241,30 @@ def context_mask(context, rows: int, n: int) -> Tensor:
 
 
 @torch.no_grad()
-def penalize_logits(logits: Tensor, repetition_penalty: Optional[float] = None, presence_penalty: Optional[float] = None,
-                    frequency_penalty: Optional[float] = None, logit_bias=None, context=(), gen: Optional[Tensor] = None,
-                    gen_len: Optional[Tensor] = None) -> Tensor:
+def penalize_logits(logits: Tensor, repetition_penalty=None, presence_penalty=None, frequency_penalty=None, logit_bias=None,
+                    context=(), gen: Optional[Tensor] = None, gen_len: Optional[Tensor] = None) -> Tensor:
     """[rows, n] logits -> the penalised logits x in float64 (the comment block above), on the logits' device.  context:
-    [(bits, rows_per_group)]; gen [rows, stride] integer tokens with gen_len [rows] (None: no generated tokens)."""
+    [(bits, rows_per_group)]; gen [rows, stride] integer tokens with gen_len [rows] (None: no generated tokens).  The three
+    penalties may be per row (evaluated in float64 as given; the kernel takes per-row values as fp32, layer_ops.sample_tokens)."""
     check_penalties(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, logits.shape[-1])
+    rows, n = logits.shape
+    groups = row_groups(rows, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty)
+    if groups is not None:
+        ctx = context_mask([(b.to(logits.device), k) for b, k in context], rows, n) if len(context) else None
+        out = torch.empty(logits.shape, dtype=torch.float64, device=logits.device)
+        for idx, vals in groups:
+            idx = idx.to(logits.device)
+            check_penalties(**vals)
+            out[idx] = _penalize(logits[idx], vals["repetition_penalty"], vals["presence_penalty"], vals["frequency_penalty"],
+                                 logit_bias, None if ctx is None else ctx[idx], None if gen is None else gen.to(logits.device)[idx],
+                                 None if gen is None else gen_len.to(logits.device)[idx])
+        return out
+    ctx = context_mask([(b.to(logits.device), k) for b, k in context], rows, n) if len(context) and (repetition_penalty or 1.0) != 1.0 else None
+    return _penalize(logits, repetition_penalty, presence_penalty, frequency_penalty, logit_bias, ctx, gen, gen_len)
+
+
+def _penalize(logits, repetition_penalty, presence_penalty, frequency_penalty, logit_bias, ctx, gen, gen_len) -> Tensor:
+    """penalize_logits with scalar penalties and the context as a [rows, n] bool mask (or None)."""
     rows, n = logits.shape
     x = logits.double()
     dev = x.device
@@ -198,7 +277,6 @@ def penalize_logits(logits: Tensor, repetition_penalty: Optional[float] = None, 
     seen = counts > 0
     r = 1.0 if repetition_penalty is None else float(repetition_penalty)
     if r != 1.0:
-        ctx = context_mask([(b.to(dev), k) for b, k in context], rows, n) if len(context) else None
         hit = seen if ctx is None else (seen | ctx)
         x = torch.where(hit, torch.where(x > 0, x / r, x * r), x)
     f, a = float(frequency_penalty or 0.0), float(presence_penalty or 0.0)
@@ -292,13 +370,19 @@ class SampleRoute(NamedTuple):
 
 
 def sample_route(cuda: bool, eligible: bool, rewritten: bool, num_samples: int, constraint: bool, penalties: bool, filters: bool,
-                 logprobs: bool, fused_filters: bool = True, fused_penalties: bool = True) -> SampleRoute:
+                 logprobs: bool, fused_filters: bool = True, fused_penalties: bool = True, per_row: bool = False) -> SampleRoute:
     """THE table of the sampling routes: generation.draw_tokens runs a route, layer_ops.sample_tokens picks its entry point from one.
     cuda: the rows are on the GPU; rewritten: and 2-D with temperature >= 0, what a kernel needs of rows a torch stage has
     rewritten (contiguous); eligible: and of unit last stride as they are (a kernel takes them when num_samples == 1);
     constraint / penalties / filters: given / active; logprobs: wanted; fused_*: the model's two switches.  The penalties in
     torch hand on fp32 rows; mask and cuts keep the dtype: other rows reach the kernels in their own.  Penalties.push happens
-    only for one sample per row and a Penalties that appends."""
+    only for one sample per row and a Penalties that appends.
+    per_row: a sampling value is given per row, or the rows have seeds of their own.  GPU rows: always a kernel route (FILTERED,
+    PENALIZED or CONSTRAINED by what is given; no torch stage), drawn through hyd_sample_tokens_rows -- the caller makes rows a
+    kernel cannot take as they are contiguous and, for num_samples > 1, repeats them per sample first, as the masked route does.
+    CPU rows: the same three names, which on CPU rows mean the torch definition (reference_draw)."""
+    if per_row:
+        return SampleRoute(CONSTRAINED if constraint else PENALIZED if penalties else FILTERED)
     kernel = eligible and num_samples == 1
     if constraint and num_samples == 1 and (not cuda or (kernel and (not penalties or fused_penalties))):
         return SampleRoute(CONSTRAINED)  # one launch with everything in it
@@ -325,15 +409,39 @@ def apply_top_p(logits: Tensor, top_p: float, min_tokens_to_keep: int = 1, filte
 
 
 @torch.no_grad()
-def reference_draw(x: Tensor, temperature: float, top_k: Optional[int] = None, top_p: Optional[float] = None,
-                   min_p: Optional[float] = None, dfa=None, state: Optional[Tensor] = None):
+def reference_draw(x: Tensor, temperature, top_k=None, top_p=None, min_p=None, dfa=None, state: Optional[Tensor] = None,
+                   seed=None, offset: int = 0):
     """PENALIZED / CONSTRAINED in torch, for CPU rows: x [B, n] the (penalised: float64) logits, masked here if an automaton is
-    given -> (tokens int64 [B, 1], fp32 log-probs [B], drawn bool [B]); a row without a valid logit: token 0, NaN, not drawn."""
+    given -> (tokens int64 [B, 1], fp32 log-probs [B], drawn bool [B]); a row without a valid logit: token 0, NaN, not drawn.
+    temperature and the cuts may be per row: the rows that share a temperature are drawn by one torch.multinomial call, groups in
+    order of first appearance (every row equal: the scalar call's single draw).  seed (one int per row) with offset: each row
+    draws from a torch.Generator of its own, seeded from (seed[row], offset) alone -- the global generator is not advanced and
+    the draw does not depend on the row's place in the batch.  (The kernels' Philox noise is another stream: seeded CPU and GPU
+    draws agree in distribution, not in tokens.)"""
     xc = x if dfa is None else constrain_logits(x, dfa, state)
     keep = kept_mask(xc, top_k, top_p, min_p)
     drawn = keep.any(-1, keepdim=True)
     xf = xc.masked_fill(~keep, -math.inf)
-    if temperature == 0:
+    seeds = None if seed is None else [int(v) for v in row_values(seed, x.shape[0], "seed")]
+    groups = row_groups(x.shape[0], temperature=temperature)
+    if seeds is not None:  # one draw per row, from the row's own generator
+        temps = row_values(temperature, x.shape[0], "temperature")
+        groups = [(torch.tensor([r], dtype=torch.int64), dict(temperature=temps[r])) for r in range(x.shape[0])]
+    if groups is not None:
+        tok = torch.zeros((x.shape[0], 1), dtype=torch.int64, device=x.device)
+        for idx, vals in groups:
+            t = vals["temperature"] or 0.0
+            idx = idx.to(x.device)
+            if t == 0:
+                tok[idx] = xf[idx].argmax(-1, keepdim=True)
+                continue
+            pr = torch.softmax(xf[idx].double() / t, -1)
+            gen = None
+            if seeds is not None:
+                gen = torch.Generator(device=x.device)
+                gen.manual_seed((seeds[int(idx[0])] * 0x9E3779B97F4A7C15 + int(offset)) % (1 << 63))
+            tok[idx] = torch.multinomial(torch.where(drawn[idx], pr, torch.ones_like(pr)), 1, generator=gen)
+    elif temperature == 0:
         tok = xf.argmax(-1, keepdim=True)
     else:
         pr = torch.softmax(xf.double() / temperature, -1)

@@ -11,6 +11,10 @@ Rules for row b's token of step t (t = 0: the token drawn from the prefill logit
       equals it (never reaching back into the prompt, never across columns a finished row has padded); the lowest matching k
       gives reason 2, stop_index = k; include_stop False: the matched columns become pad and length = t + 1 - len, True: they
       stay and length = t + 1;
+  (c') with a limit per row (hyd_stop_update_rows): otherwise, if t + 1 >= max_len[b], the row finishes at its own limit: reason 3,
+      length = t + 1, stop_index stays -1 (an entry <= 0 finishes the row at step 0 with length 1; generate() refuses limits < 1).
+      Rules (b) and (c) win at the same step: an EOS exactly at the limit is reason 1, and a stop sequence that would complete a
+      step after the limit is never matched;
   (d) otherwise the row keeps running: length = t + 1.
 Matching is on token ids.  It is not string matching: a stop string that the tokenizer splits differently in context (a merged
 " \\n\\n" token, a word boundary inside a token) is not found; pass every tokenisation that should stop."""
@@ -24,12 +28,13 @@ import torch
 from torch import Tensor
 
 MAX_EOS, MAX_SEQS, MAX_LEN = 16, 32, 16  # HYD_STOP_MAX_EOS, HYD_STOP_MAX_SEQS, HYD_STOP_MAX_LEN
-RUNNING, EOS, STOP = 0, 1, 2             # finish reasons
+RUNNING, EOS, STOP, LIMIT = 0, 1, 2, 3    # finish reasons
 
 
 class Finish(NamedTuple):
     """Per-row result of a generation with stop conditions, int32 [B] each: kept tokens, finish reason (0 = ran to
-    max_new_tokens, 1 = EOS, 2 = stop sequence) and which EOS id / stop sequence matched (-1: none)."""
+    max_new_tokens, 1 = EOS, 2 = stop sequence, 3 = the row's own limit of a per-row max_new_tokens) and which EOS id / stop
+    sequence matched (-1: none)."""
     lengths: Tensor
     reasons: Tensor
     stop_index: Tensor
@@ -103,10 +108,11 @@ def new_state(rows: int, steps: int, spec: StopSpec, device=None):
 
 
 def stop_update_reference(tok: Tensor, t: int, spec: StopSpec, out: Tensor, length: Tensor, reason: Tensor, stop_index: Tensor,
-                          live: Tensor, start_pos: Tensor, shared_len: Optional[Tensor] = None, retire: bool = True):
+                          live: Tensor, start_pos: Tensor, shared_len: Optional[Tensor] = None, retire: bool = True,
+                          max_len: Optional[Tensor] = None):
     """One step of the rules, row by row, updating out / length / reason / stop_index / live in place -> (feed, next_pos) int64
     [rows]: the token and the position of the next step (a finished row: pad, and -- retire -- shared_len - 1, the position at
-    which hyd_rope_append_decode skips the row; -1 without shared_len)."""
+    which hyd_rope_append_decode skips the row; -1 without shared_len).  max_len int [rows] or None: rule (c')."""
     rows = tok.shape[0]
     if not 0 <= t < out.shape[1]:
         raise ValueError(f"t {t} outside [0, {out.shape[1]})")
@@ -130,6 +136,8 @@ def stop_update_reference(tok: Tensor, t: int, spec: StopSpec, out: Tensor, leng
                             out[b, t + 1 - n : t + 1] = spec.pad
                             length[b] = t + 1 - n
                         break
+            if int(reason[b]) == RUNNING and max_len is not None and t + 1 >= int(max_len[b]):
+                reason[b] = LIMIT
         running = int(reason[b]) == RUNNING
         live[t] += int(running)
         feed[b] = tk if running else spec.pad
@@ -140,8 +148,9 @@ def stop_update_reference(tok: Tensor, t: int, spec: StopSpec, out: Tensor, leng
     return feed, next_pos
 
 
-def finish_steps(tokens: Tensor, spec: StopSpec):
-    """For sampled tokens [B, T] (what a generation without stop conditions returns): (step int64 [B] at which each row
+def finish_steps(tokens: Tensor, spec: StopSpec, max_len: Optional[Tensor] = None):
+    """max_len int [B] or None: rule (c'), a row not finished before step max(max_len, 1) - 1 finishes there with reason 3.
+    For sampled tokens [B, T] (what a generation without stop conditions returns): (step int64 [B] at which each row
     finishes, T for a row that never does; reason int32 [B]; stop_index int32 [B]).  A scan over whole rows: every (step,
     condition) hit is computed at once and the earliest step -- at that step EOS before stops, then the lowest k -- is taken.
     Before a row finishes its output equals its tokens, so hits may be looked for in `tokens` itself."""
@@ -171,14 +180,20 @@ def finish_steps(tokens: Tensor, spec: StopSpec):
         is_eos = first_c < len(spec.eos)
         reason = torch.where(fin, torch.where(is_eos, EOS, STOP), 0).to(torch.int32)
         index = torch.where(fin, torch.where(is_eos, first_c, first_c - len(spec.eos)), -1).to(torch.int32)
+    if max_len is not None and T:
+        at = max_len.reshape(-1).long().clamp(min=1) - 1  # the step of the limit
+        cut = (at < step) & (at < T)                      # (a condition met AT the limit's step wins)
+        step = torch.where(cut, at, step)
+        reason = torch.where(cut, torch.full_like(reason, LIMIT), reason)
+        index = torch.where(cut, torch.full_like(index, -1), index)
     return step, reason, index
 
 
-def truncate_reference(tokens: Tensor, spec: StopSpec):
+def truncate_reference(tokens: Tensor, spec: StopSpec, max_len: Optional[Tensor] = None):
     """The whole-generation definition: sampled tokens [B, T] -> (out int64 [B, T], length, reason, stop_index int32 [B]), what a
     generation with `spec` keeps of them.  Columns at and past a row's length hold pad."""
     B, T = tokens.shape
-    step, reason, index = finish_steps(tokens, spec)
+    step, reason, index = finish_steps(tokens, spec, max_len)
     lens = torch.tensor([len(s) for s in spec.stops] + [0], dtype=torch.int64)
     cut = torch.zeros((B,), dtype=torch.int64)
     if not spec.include_stop:
@@ -189,7 +204,7 @@ def truncate_reference(tokens: Tensor, spec: StopSpec):
     return out, length.to(torch.int32), reason, index
 
 
-def live_reference(tokens: Tensor, spec: StopSpec) -> Tensor:
+def live_reference(tokens: Tensor, spec: StopSpec, max_len: Optional[Tensor] = None) -> Tensor:
     """int32 [T]: the rows still running after each step (hyd_stop_params.live), from the scan."""
-    step, _, _ = finish_steps(tokens, spec)
+    step, _, _ = finish_steps(tokens, spec, max_len)
     return (step[None, :] > torch.arange(tokens.shape[1])[:, None]).sum(1).to(torch.int32)

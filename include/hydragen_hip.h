@@ -523,6 +523,35 @@ typedef struct hyd_token_dfa {
 
 HYD_API int hyd_sample_tokens_constrained(const hyd_sample_penalty_params* p, const hyd_token_dfa* c, void* stream);
 
+/* hyd_sample_tokens_constrained with PER-ROW sampling values and seeds: the rows of one launch may each sample with their own
+ * temperature, cuts, penalties and noise key (requests of different settings batched behind one shared prompt).  Every array is a
+ * device pointer to p->rows entries, or NULL = the scalar in p for every row; with every array NULL the call is exactly
+ * hyd_sample_tokens_constrained(p, c) (c == NULL: hyd_sample_tokens_penalized(p)).  Row r uses entry r, and each value means what
+ * the scalar of the same name in p means: a row's tokens, kept counts, log-probs, appended tokens and advanced states are, bit
+ * for bit, what a scalar launch with that row's values gives that row.  The penalties arrive as fp32 and are widened to double
+ * exactly: a per-row value f behaves like the scalar (double)f.
+ * The arrays are read on the device at launch time, once per row, and the host cannot check them, so the kernel replaces what
+ * the scalar entry points refuse, and no value ever forms an address:
+ *   temperature          NaN or < 0 -> 0 (argmax);  the noise scale is temperature > 0 ? 1.0f / temperature : 0 (fp32)
+ *   top_k                < 0 -> 0 (off);  >= n: no cut
+ *   top_p                outside (0, 1] or NaN -> 1 (off)
+ *   min_p                outside [0, 1] or NaN -> 0 (off);  the threshold is min_p > 0 ? (float)log((double)min_p) : -inf
+ *   repetition_penalty   <= 0, NaN or inf -> 1 (off);  positive logits are multiplied by 1.0 / (double)repetition_penalty
+ *   frequency_penalty, presence_penalty   NaN or +-inf -> 0 (off)
+ * -- the expressions the host evaluates for the scalars of the other entry points.
+ * seed != NULL: row r draws with the noise hyd_sample_tokens_filtered gives ROW 0 of a launch with seed = seed[r] and the same
+ * p->offset -- Philox counter (chunk, 0, offset lo, offset hi), key seed[r]; p->seed is not used.  A row's draw is then a function
+ * of its own logits, values, seed and offset: neither its position in the batch nor the other rows play a part.
+ * One launch, one workgroup per row; no workspace, no allocation, no synchronisation: capture-safe like the call it extends.  A call
+ * in which no penalty can act (neutral scalars in p, no penalty array, no bias, append_out == 0) costs what
+ * hyd_sample_tokens_filtered costs; any other pays hyd_sample_tokens_penalized's prologue.
+ * HYD_ERR_BAD_ARG / HYD_ERR_UNSUPPORTED: everything hyd_sample_tokens_constrained refuses (the scalars in p are checked even where
+ * an array overrides them), and an array pointer that is not aligned to its element size (4 bytes; seed: 8).  rows == 0 succeeds
+ * without a launch. */
+HYD_API int hyd_sample_tokens_rows(const hyd_sample_penalty_params* p, const hyd_token_dfa* c, const float* temperature,
+                                   const int32_t* top_k, const float* top_p, const float* min_p, const float* repetition_penalty,
+                                   const float* frequency_penalty, const float* presence_penalty, const uint64_t* seed, void* stream);
+
 /* Log-probabilities of GIVEN tokens (scoring, teacher forcing) and the top-N alternatives of every row.  For one row l (length n)
  * and its target token t, with the valid logits those that are neither NaN nor -inf and m = their max:
  *   - logprobs[row] = l_t - m - ln sum_j exp(l_j - m) over the valid logits (fp32), with hyd_sample_tokens_filtered's fixed-point
@@ -581,7 +610,7 @@ typedef struct hyd_stop_params {
     const int64_t* tok;         /* [rows] the tokens just drawn                                              */
     int64_t* out;               /* [rows, out_stride] the generation's output matrix; column t is written     */
     int32_t* length;            /* [rows] kept tokens                                                        */
-    int32_t* reason;            /* [rows] 0 = running, 1 = EOS, 2 = stop sequence                            */
+    int32_t* reason;            /* [rows] 0 = running, 1 = EOS, 2 = stop sequence, 3 = the row's own limit   */
     int32_t* stop_index;        /* [rows] which EOS id / stop sequence matched; the caller starts it at -1   */
     int32_t* live;              /* [out_stride] rows still running after each step; zeroed by the caller     */
     const int64_t* stop_tokens; /* [n_stop, HYD_STOP_MAX_LEN] device, or NULL when n_stop == 0               */
@@ -599,6 +628,16 @@ typedef struct hyd_stop_params {
 } hyd_stop_params;
 
 HYD_API int hyd_stop_update(const hyd_stop_params* p, void* stream);
+
+/* hyd_stop_update with a token limit PER ROW.  max_len: a device pointer to p->rows int32 entries, or NULL = exactly
+ * hyd_stop_update(p).  With max_len, after rules (a) to (c) and before (d):
+ *   (c') a row still running at step t with t + 1 >= max_len[b] finishes: reason 3 (the row's own limit), length t + 1, stop_index
+ *        stays -1.
+ * Rules (a) to (c) win when they apply at the same step (an EOS exactly at the limit gives reason 1; a stop sequence that would
+ * complete a step after the limit is never matched).  A row finished this way is padded, fed pad and retired from the unique K/V
+ * stream exactly like a row finished by EOS.  An entry <= 0 finishes the row at step 0 with length 1.  max_len is read on the
+ * device; entries are only compared.  Refusals as hyd_stop_update, and a max_len that is not 4-byte aligned: HYD_ERR_BAD_ARG. */
+HYD_API int hyd_stop_update_rows(const hyd_stop_params* p, const int32_t* max_len, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Speculative decoding (hydragen_amd/speculative.py states both definitions in torch): drafts by prompt lookup, and the
