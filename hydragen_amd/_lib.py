@@ -366,6 +366,9 @@ EXPORTS = {
     "hyd_linear_w8_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "hyd_linear_w8": (C.c_int, [C.POINTER(LinearW8Params), C.c_void_p]),
     "hyd_weight_widen": (C.c_int, [C.POINTER(WeightWidenParams), C.c_void_p]),
+    # hyd_qk_norm* travels as a plain pointer: its mirror is fused_decode.QkNorm (pass C.byref of one, or None)
+    "hyd_rope_append_decode_qkn": (C.c_int, [C.POINTER(RopeParams), C.POINTER(KvQuant), C.c_void_p, C.c_void_p]),
+    "hyd_rope_append_multi_qkn": (C.c_int, [C.POINTER(RopeMultiParams), C.c_void_p, C.c_void_p]),
     "hyd_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }

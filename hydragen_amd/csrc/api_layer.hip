@@ -24,6 +24,17 @@ int check_rope(const P* p, std::initializer_list<SizedPtr> index_arrays, std::in
     return HYD_OK;
 }
 
+// hyd_qk_norm beside a call whose kernels run at head dim D on rows of `head_dim` (0 or D: native) elements
+int check_qk_norm(const hyd_qk_norm* qn, int head_dim, int D) {
+    if (!qn) return HYD_OK;
+    if (int rc = check_ptrs_align({{qn->q_weight, "q_weight"}, {qn->k_weight, "k_weight"}})) return rc;
+    if (!std::isfinite(qn->eps) || qn->eps <= 0.f) return fail(HYD_ERR_BAD_ARG, "qk_norm eps %g must be finite and > 0", (double)qn->eps);
+    if (qn->flags != 0) return fail(HYD_ERR_BAD_ARG, "qk_norm flags %d must be 0", qn->flags);
+    if (head_dim != 0 && head_dim != D)
+        return fail(HYD_ERR_UNSUPPORTED, "qk_norm with head_dim %d: the per-head norm is implemented for rows of D = %d elements (64 / 128 / 256) only", head_dim, D);
+    return HYD_OK;
+}
+
 int check_w8_common(const void* w8, const float* scale, int32_t N, int32_t K, int32_t dtype, int k_multiple) {
     if (dtype != HYD_F16 && dtype != HYD_BF16) return fail(HYD_ERR_UNSUPPORTED, "dtype %d: f16 / bf16 activations (the weights are e4m3fn)", dtype);
     if (N < 1 || K < 1) return fail(HYD_ERR_BAD_ARG, "N %d / K %d must be >= 1", N, K);
@@ -37,7 +48,7 @@ int check_w8_common(const void* w8, const float* scale, int32_t N, int32_t K, in
 
 extern "C" {
 
-int hyd_rope_append_decode_kvq(const hyd_rope_params* p, const hyd_kv_quant* kq, void* stream) {
+int hyd_rope_append_decode_qkn(const hyd_rope_params* p, const hyd_kv_quant* kq, const hyd_qk_norm* qn, void* stream) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
     int rc = check_common(p->dtype, p->B, 1, p->Hq, p->Hkv, p->D);
     if (rc) return rc;
@@ -47,6 +58,7 @@ int hyd_rope_append_decode_kvq(const hyd_rope_params* p, const hyd_kv_quant* kq,
     if (narrow && kq) return fail_narrow_fp8();
     if ((rc = check_rope(p, {}, {{p->q_batch_stride, "q_batch_stride"}, {p->k_batch_stride, "k_batch_stride"}, {p->v_batch_stride, "v_batch_stride"}})))
         return rc;
+    if ((rc = check_qk_norm(qn, p->head_dim, p->D))) return rc;
     RopeArgs a;
     memset(&a, 0, sizeof(a));
     a.q = p->q; a.k = p->k; a.v = p->v; a.q_out = p->q_out; a.k_cache = p->k_cache; a.v_cache = p->v_cache;
@@ -56,6 +68,14 @@ int hyd_rope_append_decode_kvq(const hyd_rope_params* p, const hyd_kv_quant* kq,
     a.vc_bs = p->vc_batch_stride; a.vc_ts = p->vc_tok_stride; a.vc_hs = p->vc_head_stride;
     a.pos_stride = p->pos_stride; a.cs_stride = p->cs_stride;
     a.B = p->B; a.Hq = p->Hq; a.Hkv = p->Hkv; a.cache_len = p->cache_len; a.max_pos = p->max_pos;
+    if (qn) {
+        RopeKvqArgs ka;
+        ka.a = a;
+        ka.k_scale = kq ? kq->k_scale : nullptr;
+        ka.v_scale = kq ? kq->v_scale : nullptr;
+        return launched(launch_rope_append_norm(a, kq ? &ka : nullptr, qn->q_weight, qn->k_weight, qn->eps, p->dtype, p->D, static_cast<hipStream_t>(stream)),
+                        "rope_append (q/k norm) kernel launch");
+    }
     if (narrow) {
         RopeNarrowArgs na;
         na.a = a;
@@ -73,9 +93,11 @@ int hyd_rope_append_decode_kvq(const hyd_rope_params* p, const hyd_kv_quant* kq,
     return launched(launch_rope_append(a, p->dtype, p->D, static_cast<hipStream_t>(stream)), "rope_append kernel launch");
 }
 
-int hyd_rope_append_decode(const hyd_rope_params* p, void* stream) { return hyd_rope_append_decode_kvq(p, nullptr, stream); }
+int hyd_rope_append_decode_kvq(const hyd_rope_params* p, const hyd_kv_quant* kq, void* stream) { return hyd_rope_append_decode_qkn(p, kq, nullptr, stream); }
 
-int hyd_rope_append_multi(const hyd_rope_multi_params* p, void* stream) {
+int hyd_rope_append_decode(const hyd_rope_params* p, void* stream) { return hyd_rope_append_decode_qkn(p, nullptr, nullptr, stream); }
+
+int hyd_rope_append_multi_qkn(const hyd_rope_multi_params* p, const hyd_qk_norm* qn, void* stream) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
     if (p->T < 2 || p->T > 8) return fail(HYD_ERR_BAD_ARG, "T = %d tokens per row, 2 to 8 are taken (hyd_rope_append_decode takes one)", p->T);
     int rc = check_common(p->dtype, p->B, p->T, p->Hq, p->Hkv, p->D);
@@ -84,8 +106,14 @@ int hyd_rope_append_multi(const hyd_rope_multi_params* p, void* stream) {
                          {{p->q_batch_stride, "q_batch_stride"}, {p->k_batch_stride, "k_batch_stride"}, {p->v_batch_stride, "v_batch_stride"},
                           {p->q_tok_stride, "q_tok_stride"}, {p->k_tok_stride, "k_tok_stride"}, {p->v_tok_stride, "v_tok_stride"}})))
         return rc;
+    if ((rc = check_qk_norm(qn, 0, p->D))) return rc;
+    if (qn)
+        return launched(launch_rope_append_norm_multi(*p, qn->q_weight, qn->k_weight, qn->eps, static_cast<hipStream_t>(stream)),
+                        "rope_append (multi-token, q/k norm) kernel launch");
     return launched(launch_rope_append_multi(*p, static_cast<hipStream_t>(stream)), "rope_append (multi-token) kernel launch");
 }
+
+int hyd_rope_append_multi(const hyd_rope_multi_params* p, void* stream) { return hyd_rope_append_multi_qkn(p, nullptr, stream); }
 
 int hyd_add_rmsnorm(const hyd_add_rmsnorm_params* p, void* stream) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");

@@ -368,6 +368,10 @@ bool suffix_causal_eligible(const SuffixArgs& a, int D);                        
 int launch_suffix_causal(const SuffixArgs& a, int dtype, int D, hipStream_t s);       // the causal-tail suffix pass (nq = 2..8)
 // speculative decoding: these kernels take the validated public parameter blocks as they are
 int launch_rope_append_multi(const hyd_rope_multi_params& p, hipStream_t s);          // rope_append.hip
+// ... and with the per-head q/k RMSNorm in front of the rotation (hyd_qk_norm: gains [D] of the q dtype); ka null = 16-bit caches
+int launch_rope_append_norm(const RopeArgs& a, const RopeKvqArgs* ka, const void* q_weight, const void* k_weight, float eps, int dtype, int D,
+                            hipStream_t s);
+int launch_rope_append_norm_multi(const hyd_rope_multi_params& p, const void* q_weight, const void* k_weight, float eps, hipStream_t s);
 int launch_draft_lookup(const hyd_draft_lookup_params& p, hipStream_t s);             // draft_lookup.hip
 int launch_draft_accept(const hyd_draft_accept_params& p, hipStream_t s);             // draft_accept.hip
 int launch_draft_accept_states(const hyd_draft_accept_params& p, const int32_t* step_state_after, int32_t* state, hipStream_t s);

@@ -371,4 +371,240 @@ int launch_rope_append(const RopeArgs& a, int dtype, int D, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
+// Per-head q/k RMSNorm in front of the rotation (hyd_qk_norm; Qwen3's self_attn.q_norm / k_norm): for a q row and a k row
+//   r = rsqrt(mean_d(x_d^2) + eps),  n_d = x_d * r * w_d,  out = the rotation above applied to n,
+// everything in fp32 on the widened 16-bit GEMM output and ONE rounding to the 16-bit dtype at the end (the RMSNorm convention of
+// layer_ops.hip: multiply in fp32, round once).  v rows are copied as they are.  A thread holds 16 of its row's D elements, so the
+// sum of squares is 16 terms per lane and a butterfly over the row's TPR = D / 16 adjacent lanes -- DPP moves inside one 16-lane
+// row of the wave, no LDS --, after which every lane of the row holds the same bits.  The lanes of a row enter the butterfly
+// together: the bounds exit and the q / k / v branch are decided per row, and every cache-index guard sits behind it.  A ragged
+// last wave ends on a row boundary (256 % TPR == 0), so no live lane reads one that has left.
+struct RopeNormArgs {
+    const void* q_weight;  // [D], the q dtype
+    const void* k_weight;
+    float eps;
+};
+
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v) {
+    const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true);
+    return v + __builtin_bit_cast(float, o);
+}
+// every stage adds the value of the lane's mirror image inside 2 / 4 / 8 / 16 lanes; the earlier stages made each half uniform, so
+// the mirror lane holds what lane ^ 4 (^ 8) holds and both partners form the same sum a + b
+template <int TPR>
+__device__ __forceinline__ float row_sum(float v) {
+    static_assert(TPR == 4 || TPR == 8 || TPR == 16, "a row is 4, 8 or 16 adjacent lanes");
+    v = dpp_add<0xB1>(v);                  // quad_perm [1, 0, 3, 2]
+    v = dpp_add<0x4E>(v);                  // quad_perm [2, 3, 0, 1]
+    if (TPR >= 8) v = dpp_add<0x141>(v);   // row_half_mirror
+    if (TPR >= 16) v = dpp_add<0x140>(v);  // row_mirror
+    return v;
+}
+
+// The normalised, rotated row the three kernels below share: a token gets the same bits from each of them.  src: the row's D
+// elements, w: the gain vector, cr / sr: the position's table rows.  The products of the rotation are rope8's.
+template <typename T, int D>
+__device__ __forceinline__ void rope_norm_row(const uint16_t* src, const uint16_t* w, float eps, const float* cr, const float* sr, int d0,
+                                              u32x4& olo, u32x4& ohi) {
+    using TR = Traits<T>;
+    const u32x4 lo = *reinterpret_cast<const u32x4*>(src + d0);
+    const u32x4 hi = *reinterpret_cast<const u32x4*>(src + D / 2 + d0);
+    const u32x4 wlo = *reinterpret_cast<const u32x4*>(w + d0);
+    const u32x4 whi = *reinterpret_cast<const u32x4*>(w + D / 2 + d0);
+    const f32x4 c0 = *reinterpret_cast<const f32x4*>(cr + d0), c1 = *reinterpret_cast<const f32x4*>(cr + d0 + 4);
+    const f32x4 s0 = *reinterpret_cast<const f32x4*>(sr + d0), s1 = *reinterpret_cast<const f32x4*>(sr + d0 + 4);
+    float x[8], y[8], gx[8], gy[8];
+    widen8x<T>(lo, x);
+    widen8x<T>(hi, y);
+    widen8x<T>(wlo, gx);
+    widen8x<T>(whi, gy);
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ss += x[i] * x[i] + y[i] * y[i];
+    ss = row_sum<D / 16>(ss);
+    const float r = __builtin_amdgcn_rsqf(ss * (1.0f / D) + eps);  // v_rsq_f32: 1 ulp
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        x[i] = x[i] * r * gx[i];
+        y[i] = y[i] * r * gy[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float ca = i < 2 ? c0[2 * i] : c1[2 * i - 4], cb = i < 2 ? c0[2 * i + 1] : c1[2 * i - 3];
+        const float sa = i < 2 ? s0[2 * i] : s1[2 * i - 4], sb = i < 2 ? s0[2 * i + 1] : s1[2 * i - 3];
+        olo[i] = TR::pack2(x[2 * i] * ca - y[2 * i] * sa, x[2 * i + 1] * cb - y[2 * i + 1] * sb);
+        ohi[i] = TR::pack2(y[2 * i] * ca + x[2 * i] * sa, y[2 * i + 1] * cb + x[2 * i + 1] * sb);
+    }
+}
+
+template <typename T, int D>
+__global__ __launch_bounds__(256) void rope_append_norm_kernel(const RopeArgs a, const RopeNormArgs n) {
+    constexpr int TPR = D / 16;
+    const int rows_per_b = a.Hq + 2 * a.Hkv;
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t row = gid / TPR;
+    const int sub = (int)(gid % TPR);
+    if (row >= (int64_t)a.B * rows_per_b) return;
+    const int b = (int)(row / rows_per_b);
+    const int h = (int)(row % rows_per_b);
+    const int64_t pos_raw = a.pos[(int64_t)b * a.pos_stride];
+    const int64_t idx = pos_raw - (a.shared_len ? a.shared_len[b] : 0);
+    const int64_t pos = pos_raw < 0 ? 0 : (pos_raw >= a.max_pos ? (int64_t)a.max_pos - 1 : pos_raw);
+    if (h == 0 && sub == 0) a.seq_lens[b] = (int32_t)(idx + 1);
+    const int d0 = sub * 8;
+    if (h < a.Hq + a.Hkv) {
+        const bool isq = h < a.Hq;
+        const uint16_t* src = isq ? static_cast<const uint16_t*>(a.q) + (int64_t)b * a.q_bs + (int64_t)h * D
+                                  : static_cast<const uint16_t*>(a.k) + (int64_t)b * a.k_bs + (int64_t)(h - a.Hq) * D;
+        u32x4 olo, ohi;
+        rope_norm_row<T, D>(src, static_cast<const uint16_t*>(isq ? n.q_weight : n.k_weight), n.eps, a.cos + pos * a.cs_stride,
+                            a.sin + pos * a.cs_stride, d0, olo, ohi);
+        uint16_t* dst;
+        if (isq) {
+            dst = static_cast<uint16_t*>(a.q_out) + ((int64_t)b * a.Hq + h) * D;
+        } else {
+            if (idx < 0 || idx >= a.cache_len) return;  // out of the allocated cache: never write out of bounds
+            dst = static_cast<uint16_t*>(a.k_cache) + (int64_t)b * a.kc_bs + idx * a.kc_ts + (int64_t)(h - a.Hq) * a.kc_hs;
+        }
+        *reinterpret_cast<u32x4*>(dst + d0) = olo;
+        *reinterpret_cast<u32x4*>(dst + D / 2 + d0) = ohi;
+    } else {
+        if (idx < 0 || idx >= a.cache_len) return;
+        const int hv = h - a.Hq - a.Hkv;
+        const uint16_t* src = static_cast<const uint16_t*>(a.v) + (int64_t)b * a.v_bs + (int64_t)hv * D;
+        uint16_t* dst = static_cast<uint16_t*>(a.v_cache) + (int64_t)b * a.vc_bs + idx * a.vc_ts + (int64_t)hv * a.vc_hs;
+        *reinterpret_cast<u32x4*>(dst + d0) = *reinterpret_cast<const u32x4*>(src + d0);
+        *reinterpret_cast<u32x4*>(dst + D / 2 + d0) = *reinterpret_cast<const u32x4*>(src + D / 2 + d0);
+    }
+}
+
+template <typename T, int D>
+__global__ __launch_bounds__(256) void rope_append_norm_fp8_kernel(const RopeKvqArgs ka, const RopeNormArgs n) {
+    const RopeArgs& a = ka.a;
+    constexpr int TPR = D / 16;
+    const int rows_per_b = a.Hq + 2 * a.Hkv;
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t row = gid / TPR;
+    const int sub = (int)(gid % TPR);
+    if (row >= (int64_t)a.B * rows_per_b) return;
+    const int b = (int)(row / rows_per_b);
+    const int h = (int)(row % rows_per_b);
+    const int64_t pos_raw = a.pos[(int64_t)b * a.pos_stride];
+    const int64_t idx = pos_raw - (a.shared_len ? a.shared_len[b] : 0);
+    const int64_t pos = pos_raw < 0 ? 0 : (pos_raw >= a.max_pos ? (int64_t)a.max_pos - 1 : pos_raw);
+    if (h == 0 && sub == 0) a.seq_lens[b] = (int32_t)(idx + 1);
+    const int d0 = sub * 8;
+    u32x4 olo, ohi;
+    float s;
+    uint8_t* dst8;
+    if (h < a.Hq + a.Hkv) {
+        const bool isq = h < a.Hq;
+        const uint16_t* src = isq ? static_cast<const uint16_t*>(a.q) + (int64_t)b * a.q_bs + (int64_t)h * D
+                                  : static_cast<const uint16_t*>(a.k) + (int64_t)b * a.k_bs + (int64_t)(h - a.Hq) * D;
+        rope_norm_row<T, D>(src, static_cast<const uint16_t*>(isq ? n.q_weight : n.k_weight), n.eps, a.cos + pos * a.cs_stride,
+                            a.sin + pos * a.cs_stride, d0, olo, ohi);
+        if (isq) {
+            uint16_t* dst = static_cast<uint16_t*>(a.q_out) + ((int64_t)b * a.Hq + h) * D;
+            *reinterpret_cast<u32x4*>(dst + d0) = olo;
+            *reinterpret_cast<u32x4*>(dst + D / 2 + d0) = ohi;
+            return;
+        }
+        if (idx < 0 || idx >= a.cache_len) return;  // out of the allocated cache: never write out of bounds
+        const int hk = h - a.Hq;
+        s = ka.k_scale ? ka.k_scale[hk] : 1.0f;
+        dst8 = static_cast<uint8_t*>(a.k_cache) + (int64_t)b * a.kc_bs + idx * a.kc_ts + (int64_t)hk * a.kc_hs;
+    } else {
+        if (idx < 0 || idx >= a.cache_len) return;
+        const int hv = h - a.Hq - a.Hkv;
+        const uint16_t* src = static_cast<const uint16_t*>(a.v) + (int64_t)b * a.v_bs + (int64_t)hv * D;
+        olo = *reinterpret_cast<const u32x4*>(src + d0);
+        ohi = *reinterpret_cast<const u32x4*>(src + D / 2 + d0);
+        s = ka.v_scale ? ka.v_scale[hv] : 1.0f;
+        dst8 = static_cast<uint8_t*>(a.v_cache) + (int64_t)b * a.vc_bs + idx * a.vc_ts + (int64_t)hv * a.vc_hs;
+    }
+    float xl[8], xh[8];
+    widen8x<T>(olo, xl);
+    widen8x<T>(ohi, xh);
+    *reinterpret_cast<u32x2*>(dst8 + d0) = quant_fp8x8(xl, s);
+    *reinterpret_cast<u32x2*>(dst8 + D / 2 + d0) = quant_fp8x8(xh, s);
+}
+
+template <typename T, int D>
+__global__ __launch_bounds__(256) void rope_append_norm_multi_kernel(const hyd_rope_multi_params a, const RopeNormArgs n) {
+    constexpr int TPR = D / 16;
+    const int rows_per_t = a.Hq + 2 * a.Hkv;
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t row = gid / TPR;
+    const int sub = (int)(gid % TPR);
+    if (row >= (int64_t)a.B * a.T * rows_per_t) return;
+    const int h = (int)(row % rows_per_t);
+    const int64_t bt = row / rows_per_t;
+    const int b = (int)(bt / a.T), i = (int)(bt % a.T);
+    const int64_t pos0 = a.position_ids[(int64_t)b * a.pos_stride];
+    const int64_t idx0 = pos0 - (a.shared_len ? a.shared_len[b] : 0);
+    const int64_t idx = idx0 + i, pos_raw = pos0 + i;
+    const int64_t pos = pos_raw < 0 ? 0 : (pos_raw >= a.max_pos ? (int64_t)a.max_pos - 1 : pos_raw);
+    if (h == 0 && sub == 0 && i == 0) a.seq_lens[b] = idx0 >= 0 ? (int32_t)(idx0 + a.T) : 0;
+    const bool store_kv = idx0 >= 0 && idx < a.cache_len;  // never write out of bounds, never for a retired row
+    const int d0 = sub * 8;
+    if (h < a.Hq + a.Hkv) {
+        const bool isq = h < a.Hq;
+        const uint16_t* src = isq ? static_cast<const uint16_t*>(a.q) + (int64_t)b * a.q_batch_stride + (int64_t)i * a.q_tok_stride + (int64_t)h * D
+                                  : static_cast<const uint16_t*>(a.k) + (int64_t)b * a.k_batch_stride + (int64_t)i * a.k_tok_stride + (int64_t)(h - a.Hq) * D;
+        u32x4 olo, ohi;
+        rope_norm_row<T, D>(src, static_cast<const uint16_t*>(isq ? n.q_weight : n.k_weight), n.eps, a.cos + pos * a.cs_stride,
+                            a.sin + pos * a.cs_stride, d0, olo, ohi);
+        if (!isq && !store_kv) return;
+        uint16_t* dst = isq ? static_cast<uint16_t*>(a.q_out) + (bt * a.Hq + h) * D
+                            : static_cast<uint16_t*>(a.k_cache) + (int64_t)b * a.kc_batch_stride + idx * a.kc_tok_stride + (int64_t)(h - a.Hq) * a.kc_head_stride;
+        *reinterpret_cast<u32x4*>(dst + d0) = olo;
+        *reinterpret_cast<u32x4*>(dst + D / 2 + d0) = ohi;
+    } else {
+        if (!store_kv) return;
+        const int hv = h - a.Hq - a.Hkv;
+        const uint16_t* src = static_cast<const uint16_t*>(a.v) + (int64_t)b * a.v_batch_stride + (int64_t)i * a.v_tok_stride + (int64_t)hv * D;
+        uint16_t* dst = static_cast<uint16_t*>(a.v_cache) + (int64_t)b * a.vc_batch_stride + idx * a.vc_tok_stride + (int64_t)hv * a.vc_head_stride;
+        *reinterpret_cast<u32x4*>(dst + d0) = *reinterpret_cast<const u32x4*>(src + d0);
+        *reinterpret_cast<u32x4*>(dst + D / 2 + d0) = *reinterpret_cast<const u32x4*>(src + D / 2 + d0);
+    }
+}
+
+// one dispatch over {f16, bf16} x {64, 128, 256} for the three norm kernels: KERNEL is the template's name, the rest its arguments
+#define HYD_ROPE_NORM_DISPATCH(KERNEL, dtype, D, grid, s, ...)                                            \
+    do {                                                                                                  \
+        if ((dtype) == HYD_F16) {                                                                         \
+            if ((D) == 128) hipLaunchKernelGGL((KERNEL<F16, 128>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);       \
+            else if ((D) == 64) hipLaunchKernelGGL((KERNEL<F16, 64>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);    \
+            else if ((D) == 256) hipLaunchKernelGGL((KERNEL<F16, 256>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);  \
+            else return (int)hipErrorInvalidValue;                                                        \
+        } else {                                                                                          \
+            if ((D) == 128) hipLaunchKernelGGL((KERNEL<BF16, 128>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);      \
+            else if ((D) == 64) hipLaunchKernelGGL((KERNEL<BF16, 64>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);   \
+            else if ((D) == 256) hipLaunchKernelGGL((KERNEL<BF16, 256>), dim3(grid), dim3(256), 0, s, __VA_ARGS__); \
+            else return (int)hipErrorInvalidValue;                                                        \
+        }                                                                                                 \
+    } while (0)
+
+int launch_rope_append_norm(const RopeArgs& a, const RopeKvqArgs* ka, const void* q_weight, const void* k_weight, float eps, int dtype, int D,
+                            hipStream_t s) {
+    const RopeNormArgs n = {q_weight, k_weight, eps};
+    const int64_t threads = (int64_t)a.B * (a.Hq + 2 * a.Hkv) * (D / 16);
+    const int grid = (int)((threads + 255) / 256);
+    if (grid == 0) return 0;
+    if (ka) HYD_ROPE_NORM_DISPATCH(rope_append_norm_fp8_kernel, dtype, D, grid, s, *ka, n);
+    else HYD_ROPE_NORM_DISPATCH(rope_append_norm_kernel, dtype, D, grid, s, a, n);
+    return (int)hipGetLastError();
+}
+
+int launch_rope_append_norm_multi(const hyd_rope_multi_params& p, const void* q_weight, const void* k_weight, float eps, hipStream_t s) {
+    const RopeNormArgs n = {q_weight, k_weight, eps};
+    const int64_t threads = (int64_t)p.B * p.T * (p.Hq + 2 * p.Hkv) * (p.D / 16);
+    const int grid = (int)((threads + 255) / 256);
+    if (grid == 0) return 0;
+    HYD_ROPE_NORM_DISPATCH(rope_append_norm_multi_kernel, p.dtype, p.D, grid, s, p, n);
+    return (int)hipGetLastError();
+}
+#undef HYD_ROPE_NORM_DISPATCH
+
 }  // namespace hyd

@@ -13,13 +13,37 @@ from ._lib import RopeParams
 from .flash import _dtype_code, _require_gpu, _stream, check_kv_pair, kv_quant_params, padded_head_dim
 
 
+class QkNorm(C.Structure):
+    """hyd_qk_norm: the per-head q/k RMSNorm block of the _qkn entry points."""
+    _fields_ = [("q_weight", C.c_void_p), ("k_weight", C.c_void_p), ("eps", C.c_float), ("flags", C.c_int32)]
+
+
+def qk_norm_params(q, D: int, q_norm: Tensor | None, k_norm: Tensor | None, norm_eps: float | None):
+    """None without gains, else the QkNorm of two gain vectors [D] of q's dtype (both or neither; norm_eps is required)."""
+    if q_norm is None and k_norm is None:
+        if norm_eps is not None:
+            raise ValueError("norm_eps without q_norm / k_norm")
+        return None
+    if q_norm is None or k_norm is None:
+        raise ValueError("q_norm and k_norm come together: both gain vectors, or neither")
+    if norm_eps is None:
+        raise ValueError("q_norm / k_norm need norm_eps")
+    for w in (q_norm, k_norm):
+        _require_gpu(w)
+        if w.shape != (D,) or w.dtype != q.dtype or not w.is_contiguous():
+            raise ValueError(f"q_norm / k_norm: contiguous [{D}] gains of {q.dtype}, got {tuple(w.shape)} {w.dtype}")
+    return QkNorm(q_norm.data_ptr(), k_norm.data_ptr(), float(norm_eps), 0)
+
+
 def rope_append_multi(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, position_ids: Tensor,
-                      shared_len: Tensor | None, k_cache: Tensor, v_cache: Tensor):
+                      shared_len: Tensor | None, k_cache: Tensor, v_cache: Tensor, q_norm: Tensor | None = None,
+                      k_norm: Tensor | None = None, norm_eps: float | None = None):
     """hyd_rope_append_multi: the preamble of a MULTI-TOKEN decode step (speculative.py).  q [B,T,Hq,D], k/v [B,T,Hkv,D] with
     2 <= T <= 8, position_ids int64 [B] or [B, T] (column 0 is read: the first token's absolute position, token i uses + i),
     shared_len int64 [B] or None, 16-bit caches [maxB, maxS, Hkv, D] with D 64 / 128 / 256.  Returns (rotated q [B,T,Hq,D],
     seq_lens int32 [B] = cache index of the first token + T); K (rotated) and V of token i are written at that index + i.  A
-    row at position shared_len - 1 writes nothing and reports length 0."""
+    row at position shared_len - 1 writes nothing and reports length 0.  q_norm / k_norm [D] of q's dtype with norm_eps: the
+    per-head RMSNorm of q and k in front of the rotation (hyd_rope_append_multi_qkn), as in rope_append_decode."""
     _require_gpu(q, k, v, cos, sin, position_ids, k_cache, v_cache)
     if check_kv_pair(k_cache, v_cache, None, None):
         raise NotImplementedError("multi-token decode steps with fp8 unique caches: 16-bit caches only")
@@ -51,13 +75,18 @@ def rope_append_multi(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor,
     p.pos_stride, p.cs_stride = position_ids.stride(0), cos.stride(0)
     p.dtype, p.B, p.T, p.Hq, p.Hkv, p.D, p.cache_len = _dtype_code(q), B, T, Hq, Hkv, D, k_cache.shape[1]
     p.max_pos = cos.shape[0]
-    _lib.check(_lib.load().hyd_rope_append_multi(C.byref(p), _stream()))
+    qn = qk_norm_params(q, D, q_norm, k_norm, norm_eps)
+    if qn is not None:
+        _lib.check(_lib.load().hyd_rope_append_multi_qkn(C.byref(p), C.byref(qn), _stream()))
+    else:
+        _lib.check(_lib.load().hyd_rope_append_multi(C.byref(p), _stream()))
     return q_out, seq_lens
 
 
 def rope_append_decode(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, position_ids: Tensor,
                        shared_len: Tensor | None, k_cache: Tensor, v_cache: Tensor, *, k_scale: Tensor | None = None,
-                       v_scale: Tensor | None = None):
+                       v_scale: Tensor | None = None, q_norm: Tensor | None = None, k_norm: Tensor | None = None,
+                       norm_eps: float | None = None):
     """q [B,1,Hq,D], k/v [B,1,Hkv,D] (this step's projections), cos/sin fp32 [max_pos, D],
     position_ids int64 [B,1] absolute, shared_len int64 [B] or None, caches [maxB, maxS, Hkv, D].
     Returns (rotated q [B,1,Hq,D], seq_lens int32 [B]); k (rotated) and v are written into the caches
@@ -65,7 +94,10 @@ def rope_append_decode(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor
     quantize_kv(v, v_scale) (kv_quant.py), k_rot being the 16-bit rotated k a 16-bit cache would hold.
     Narrow head dims (d % 16 == 0, not 64 / 128 / 256; 16-bit caches): q / k / v, the cos / sin tables and the caches are d wide,
     the returned q is padded_head_dim(d) wide with zero pad columns -- what the attention operators take beside narrow unique
-    caches (hyd_rope_params.head_dim)."""
+    caches (hyd_rope_params.head_dim).
+    q_norm / k_norm [D] of q's dtype with norm_eps (both gains or neither): every q head and every k head is RMS-normalised with
+    its gain vector in front of the rotation, in fp32 with one rounding at the end (hyd_rope_append_decode_qkn); 16-bit and fp8
+    caches, head dims 64 / 128 / 256 only."""
     _require_gpu(q, k, v, cos, sin, position_ids, k_cache, v_cache)
     fp8 = check_kv_pair(k_cache, v_cache, k_scale, v_scale)
     lib = _lib.load()
@@ -102,7 +134,13 @@ def rope_append_decode(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor
     p.dtype, p.B, p.Hq, p.Hkv, p.D, p.cache_len = _dtype_code(q), B, Hq, Hkv, D, k_cache.shape[1]
     p.max_pos = cos.shape[0]
     p.head_dim = head_dim
-    if fp8:
+    qn = qk_norm_params(q, q.shape[-1], q_norm, k_norm, norm_eps)
+    if qn is not None:
+        if head_dim:
+            raise NotImplementedError(f"q_norm / k_norm with head_dim {head_dim}: the per-head norm takes head dims 64 / 128 / 256")
+        kq = kv_quant_params(k_scale, v_scale) if fp8 else None
+        _lib.check(lib.hyd_rope_append_decode_qkn(C.byref(p), None if kq is None else C.byref(kq), C.byref(qn), _stream()))
+    elif fp8:
         kq = kv_quant_params(k_scale, v_scale)
         _lib.check(lib.hyd_rope_append_decode_kvq(C.byref(p), C.byref(kq), _stream()))
     else:

@@ -48,10 +48,23 @@ class LlamaConfig:
     max_position_embeddings: int = 4096
     attention_bias: bool = False
     pad_token_id: Optional[int] = None
+    # Qwen3-style attention (new fields stay at the END: from_hf_model and callers build the config positionally)
+    head_dim: Optional[int] = None  # None: hidden_size // num_attention_heads
+    qk_norm: bool = False           # RMSNorm over every query head and every key head between the projection and RoPE
+
+    def get_head_dim(self) -> int:
+        """The one place that knows a head's width: `head_dim` when the checkpoint states it, else hidden_size // heads."""
+        return self.hidden_size // self.num_attention_heads if self.head_dim is None else self.head_dim
 
     @staticmethod
     def llama2_7b(**kw):
         return LlamaConfig(**kw)
+
+    @staticmethod
+    def qwen3_8b(**kw):
+        return LlamaConfig(hidden_size=4096, intermediate_size=12288, num_hidden_layers=36, num_attention_heads=32,
+                           num_key_value_heads=8, vocab_size=151936, rms_norm_eps=1e-6, rope_theta=1000000.0,
+                           max_position_embeddings=40960, head_dim=128, qk_norm=True, **kw)
 
     @staticmethod
     def llama3_70b(**kw):
@@ -512,17 +525,25 @@ class HydragenLlamaAttention(nn.Module):
         self.config = config
         self.hidden_size = config.hidden_size
         self.num_heads = config.num_attention_heads
-        self.head_dim = self.hidden_size // self.num_heads
+        self.head_dim = config.get_head_dim()
         self.num_key_value_heads = config.num_key_value_heads
         self.disable_hydragen = False
         self.disable_attention = False
-        if self.head_dim * self.num_heads != self.hidden_size:
+        if config.head_dim is None and self.head_dim * self.num_heads != self.hidden_size:
             raise ValueError(f"hidden_size must be divisible by num_heads (got `hidden_size`: {self.hidden_size} and `num_heads`: {self.num_heads}).")
         b = config.attention_bias
         self.q_proj = nn.Linear(self.hidden_size, self.num_heads * self.head_dim, bias=b)
         self.k_proj = nn.Linear(self.hidden_size, self.num_key_value_heads * self.head_dim, bias=b)
         self.v_proj = nn.Linear(self.hidden_size, self.num_key_value_heads * self.head_dim, bias=b)
         self.o_proj = nn.Linear(self.num_heads * self.head_dim, self.hidden_size, bias=b)
+        # per-head q/k RMSNorm (Qwen3; HF's state-dict names): one gain vector of head_dim elements for all query heads, one for
+        # all key heads.  The fused decode preambles apply them inside the kernel, every other path calls the modules.
+        self.q_norm = self.k_norm = None
+        if config.qk_norm:
+            if self.head_dim not in (64, 128, 256):
+                raise NotImplementedError(f"qk_norm with head_dim {self.head_dim}: the per-head norm is implemented for 64 / 128 / 256")
+            self.q_norm = RMSNorm(self.head_dim, eps=config.rms_norm_eps)
+            self.k_norm = RMSNorm(self.head_dim, eps=config.rms_norm_eps)
         self.kv_cache: Optional[PerLayerKVCache] = None
         self.mode: Optional[str] = None
         self.rotary_emb: Optional[RotaryTable] = None
@@ -530,6 +551,12 @@ class HydragenLlamaAttention(nn.Module):
         self.use_fused_decode = True
         self._qkv: Optional[Tensor] = None
         self.qkv_proj = None  # weight_quant.Fp8Linear once the model is quantized (q_proj / k_proj / v_proj are then None)
+
+    def _qk_norm_args(self) -> dict:
+        """The gains and eps the fused preambles take (nothing without qk_norm)."""
+        if self.q_norm is None:
+            return {}
+        return dict(q_norm=self.q_norm.weight, k_norm=self.k_norm.weight, norm_eps=self.q_norm.variance_epsilon)
 
     def _decode_multi(self, q, k, v, cos, sin, position_ids, shared_len):
         """Attention of a MULTI-TOKEN decode step (speculative.py): q / k / v [B, T, H, D] are T consecutive tokens per row,
@@ -551,7 +578,8 @@ class HydragenLlamaAttention(nn.Module):
         if self.use_fused_decode:
             from .fused_decode import rope_append_multi
 
-            q, seq_lens = rope_append_multi(q, k, v, cos, sin, position_ids, shared_len, kvc.per_completion_k_cache, kvc.per_completion_v_cache)
+            q, seq_lens = rope_append_multi(q, k, v, cos, sin, position_ids, shared_len, kvc.per_completion_k_cache, kvc.per_completion_v_cache,
+                                            **self._qk_norm_args())
             ks, vs = kvc.per_completion_k_cache[:bsz], kvc.per_completion_v_cache[:bsz]
             try:
                 if not shared:
@@ -561,6 +589,8 @@ class HydragenLlamaAttention(nn.Module):
                 pass
         else:
             unique_position_ids = position_ids if shared_len is None else position_ids - shared_len.unsqueeze(-1)
+            if self.q_norm is not None:
+                q, k = self.q_norm(q), self.k_norm(k)
             q, k = apply_rotary_pos_emb(q, k, cos, sin, position_ids)
             ks, vs = kvc.update_per_completion_kvs(unique_position_ids, k, v)
             seq_lens = unique_position_ids[:, -1] + 1
@@ -605,7 +635,8 @@ class HydragenLlamaAttention(nn.Module):
             # narrow unique caches: the preamble takes head_dim-wide q / k / v and caches and returns q at the kernels' head dim with
             # zero pad columns; the operators then copy nothing (shared caches that wide, the unique cache as it is) and so is their output
             q, seq_lens = rope_append_decode(q, k, v, cos, sin, position_ids, shared_len,
-                                             self.kv_cache.per_completion_k_cache, self.kv_cache.per_completion_v_cache, **sc)
+                                             self.kv_cache.per_completion_k_cache, self.kv_cache.per_completion_v_cache, **sc,
+                                             **self._qk_norm_args())
             key_states = self.kv_cache.per_completion_k_cache[:bsz]
             value_states = self.kv_cache.per_completion_v_cache[:bsz]
             if self.disable_attention:
@@ -626,6 +657,8 @@ class HydragenLlamaAttention(nn.Module):
             unique_position_ids = position_ids
         else:
             unique_position_ids = position_ids - self.kv_cache.get_shared_len(position_ids.shape[0]).unsqueeze(-1)
+        if self.q_norm is not None:  # prefill, use_fused_decode = False, CPU models: the modules, then the rotation
+            q, k = self.q_norm(q), self.k_norm(k)
         q, k = apply_rotary_pos_emb(q, k, cos, sin, position_ids)
         if self.kv_cache is not None and self.kv_cache.kv_amax is not None and self.mode in (AttentionMode.SHARED_PREFILL, AttentionMode.UNIQUE_PREFILL):
             # calibrated fp8 scales: this prefill's K / V before any of it is stored.  A shared level stores the rows inside the
@@ -693,8 +726,7 @@ class HydragenLlamaModel(nn.Module):
         self.embed_tokens = nn.Embedding(config.vocab_size, config.hidden_size, config.pad_token_id)
         self.layers = nn.ModuleList([HydragenLlamaDecoderLayer(config) for _ in range(config.num_hidden_layers)])
         self.norm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
-        self.rotary_emb = RotaryTable(config.hidden_size // config.num_attention_heads,
-                                      config.max_position_embeddings, config.rope_theta)
+        self.rotary_emb = RotaryTable(config.get_head_dim(), config.max_position_embeddings, config.rope_theta)
         for layer in self.layers:
             layer.self_attn.rotary_emb = self.rotary_emb
 
@@ -847,8 +879,7 @@ class HydragenLlamaForCausalLM(nn.Module):
             apply_tp(model.model, rank=tp_shard[0], world_size=tp_shard[1])
             model.to_empty(device=device)
             c = model.config
-            model.model.rotary_emb = RotaryTable(c.hidden_size // c.num_attention_heads, c.max_position_embeddings,
-                                                 c.rope_theta, device=device)
+            model.model.rotary_emb = RotaryTable(c.get_head_dim(), c.max_position_embeddings, c.rope_theta, device=device)
             for layer in model.model.layers:
                 layer.self_attn.rotary_emb = model.model.rotary_emb
             with torch.no_grad():
@@ -870,31 +901,44 @@ class HydragenLlamaForCausalLM(nn.Module):
 
     @classmethod
     def from_pretrained(cls, model_name_or_path: str, **kwargs):
-        """llama.py:1398-1422.  Needs `transformers` weights on disk; not exercised offline."""
-        from transformers import LlamaForCausalLM  # pragma: no cover
+        """llama.py:1398-1422.  Needs `transformers` weights on disk; not exercised offline.  Llama and Qwen3 checkpoints."""
+        from transformers import AutoModelForCausalLM  # pragma: no cover
 
-        hf = LlamaForCausalLM.from_pretrained(model_name_or_path, **kwargs)  # pragma: no cover
-        if hf.dtype not in (torch.float16, torch.bfloat16):  # pragma: no cover
+        return cls.from_hf_model(AutoModelForCausalLM.from_pretrained(model_name_or_path, **kwargs))  # pragma: no cover
+
+    @classmethod
+    def from_hf_model(cls, hf):
+        """The model of an in-memory transformers `LlamaForCausalLM` or `Qwen3ForCausalLM` (fp16 / bf16): its config mapped onto
+        LlamaConfig -- `head_dim` where the config states one, `qk_norm` when the state dict carries `self_attn.q_norm` or the
+        model type is qwen3 -- and its state dict loaded, every tensor accounted for."""
+        if hf.dtype not in (torch.float16, torch.bfloat16):
             raise ValueError(f"Model must be in float16 or bfloat16, not {hf.dtype}")
-        c = hf.config  # pragma: no cover
+        c = hf.config
+        kind = getattr(c, "model_type", "llama")
+        if kind not in ("llama", "qwen3"):
+            raise NotImplementedError(f"model type '{kind}': llama and qwen3 are implemented")
+        if getattr(c, "use_sliding_window", False):
+            raise NotImplementedError("sliding-window attention is not implemented")
+        sd = hf.state_dict()
         rp = getattr(c, "rope_parameters", None) or {}
         cfg = LlamaConfig(c.hidden_size, c.intermediate_size, c.num_hidden_layers, c.num_attention_heads,
                           c.num_key_value_heads, c.vocab_size, c.rms_norm_eps,
                           getattr(c, "rope_theta", rp.get("rope_theta", 10000.0)), c.max_position_embeddings,
-                          getattr(c, "attention_bias", False), c.pad_token_id)  # pragma: no cover
-        scaling = getattr(c, "rope_scaling", None) or {}  # pragma: no cover
-        kind = scaling.get("rope_type", scaling.get("type", "default")) or rp.get("rope_type", "default")  # pragma: no cover
-        if kind not in ("default", None):  # pragma: no cover
-            raise NotImplementedError(f"rope scaling '{kind}' is not implemented (plain theta-only RoPE tables)")
-        model = cls(cfg)  # pragma: no cover
-        report = model.load_state_dict(hf.state_dict(), strict=False)  # pragma: no cover
-        extra = [k for k in report.unexpected_keys if "inv_freq" not in k]  # pragma: no cover
-        if report.missing_keys or extra:  # pragma: no cover
+                          getattr(c, "attention_bias", False), c.pad_token_id, getattr(c, "head_dim", None),
+                          kind == "qwen3" or any(k.endswith("self_attn.q_norm.weight") for k in sd))
+        scaling = getattr(c, "rope_scaling", None) or {}
+        rope = scaling.get("rope_type", scaling.get("type", "default")) or rp.get("rope_type", "default")
+        if rope not in ("default", None):
+            raise NotImplementedError(f"rope scaling '{rope}' is not implemented (plain theta-only RoPE tables)")
+        model = cls(cfg)
+        report = model.load_state_dict(sd, strict=False)
+        extra = [k for k in report.unexpected_keys if "inv_freq" not in k]
+        if report.missing_keys or extra:
             raise RuntimeError(f"checkpoint does not match: missing {report.missing_keys[:5]}, unexpected {extra[:5]}")
-        model.to(device=hf.device, dtype=hf.dtype)  # pragma: no cover
-        model.model.rotary_emb.float()  # pragma: no cover
-        model.device, model.dtype = hf.device, hf.dtype  # pragma: no cover
-        return model  # pragma: no cover
+        model.to(device=hf.device, dtype=hf.dtype)
+        model.model.rotary_emb.float()
+        model.device, model.dtype = hf.device, hf.dtype
+        return model
 
     # ---- cache / graph management -------------------------------------------------------------------
     def set_mode(self, mode):
@@ -983,7 +1027,7 @@ class HydragenLlamaForCausalLM(nn.Module):
         quantizer's clamp at +-448 * scale applies, as with scale 1.  Calibration fixes range, not mantissa (kv_quant.py)."""
         self.maybe_invalidate()
         max_unique_seq_length = (max_unique_seq_length + 15) // 16 * 16
-        head_dim = self.config.hidden_size // self.get_num_heads()
+        head_dim = self.config.get_head_dim()
         device, dtype = self.lm_head.weight.device, self.model.embed_tokens.weight.dtype  # (the lm_head's weight may be fp8)
         # the layers' unique caches, placed where the suffix pass streams them fastest (placement.py: more candidates than layers
         # are allocated, each timed once with the suffix pass over all of its keys, the slowest go back; off the data path)

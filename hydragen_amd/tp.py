@@ -117,9 +117,9 @@ def _apply_tp_attn(attn, rank: int, world_size: int) -> None:
     _apply_tp_linear(attn.k_proj, "colwise", rank, world_size)
     _apply_tp_linear(attn.v_proj, "colwise", rank, world_size)
     _apply_tp_linear(attn.o_proj, "rowwise", rank, world_size)
+    # (whole heads per rank: head_dim stays what LlamaConfig.get_head_dim gave the module; q_norm / k_norm gains are replicated)
     attn.hidden_size //= world_size
     attn.num_heads //= world_size
-    attn.head_dim = attn.hidden_size // attn.num_heads
     attn.num_key_value_heads //= world_size
     attn.tp_reduce = True
 
@@ -144,9 +144,11 @@ def apply_tp(model, rank: Optional[int] = None, world_size: Optional[int] = None
         return
     c = model.config
     assert c.num_attention_heads % world_size == 0 and c.num_key_value_heads % world_size == 0
+    head_dim = c.get_head_dim()
     c.num_attention_heads //= world_size
     c.num_key_value_heads //= world_size
-    c.hidden_size //= world_size  # keeps hidden_size // num_attention_heads = head_dim (tp.py:122-124)
+    c.hidden_size //= world_size  # keeps hidden_size // num_attention_heads = head_dim (tp.py:122-124); an explicit head_dim stays
+    assert c.get_head_dim() == head_dim
     for block in model.layers:
         _apply_tp_ffn(block.mlp, rank, world_size)
         _apply_tp_attn(block.self_attn, rank, world_size)
@@ -193,7 +195,7 @@ def from_pretrained_tp(config_or_dir, load_dir: Union[Path, str, None] = None, d
     # non-persistent buffers (rotary tables) are not in the state dict: rebuild them on the target device
     from .llama import RotaryTable
 
-    head_dim = config.hidden_size // config.num_attention_heads
+    head_dim = config.get_head_dim()
     model.model.rotary_emb = RotaryTable(head_dim, config.max_position_embeddings, config.rope_theta, device=device)
     for layer in model.model.layers:
         layer.self_attn.rotary_emb = model.model.rotary_emb

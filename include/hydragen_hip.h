@@ -864,6 +864,22 @@ HYD_API int hyd_kv_quant_supported(const hyd_suffix_params* p, const hyd_kv_quan
  * cache dtype -- phase, single_launch_small and the levels as given (always 1 for kq == NULL or kv_dtype == dtype) --, else 0. */
 HYD_API int hyd_decode_kv_quant_supported(const hyd_decode_params* p, const hyd_kv_quant* kq);
 
+/* Per-head q/k RMSNorm inside the preamble (Qwen3's self_attn.q_norm / k_norm: one gain vector of D elements for every query
+ * head, one for every key head, applied between the projection and RoPE).  The _qkn entry points take the existing parameter
+ * structs unchanged plus a hyd_qk_norm; qn == NULL is the existing call and launches the existing kernels.  With qn, for every
+ * q row and k row x (the 16-bit input widened to fp32)
+ *     r = rsqrt(mean_d(x_d^2) + eps),   n_d = x_d * r * w_d,   out = the rotation applied to n,
+ * all in fp32 with ONE rounding to the 16-bit dtype at the end (the convention of hyd_add_rmsnorm); v rows are copied as before,
+ * fp8 caches receive the quantized 16-bit value as before, and a token gets the same bits from the one-token and the multi-token
+ * form.  D 64 / 128 / 256 only: a norm together with a narrow hyd_rope_params.head_dim is HYD_ERR_UNSUPPORTED.  A null or
+ * misaligned weight, an eps that is not finite or not > 0, and flags != 0 are HYD_ERR_BAD_ARG. */
+typedef struct hyd_qk_norm { const void* q_weight; const void* k_weight; /* [D], the q dtype, 16-byte aligned */
+                             float eps; int32_t flags; /* 0 */ } hyd_qk_norm;
+
+HYD_API int hyd_rope_append_decode_qkn(const hyd_rope_params* p, const hyd_kv_quant* kq /* nullable */, const hyd_qk_norm* qn /* nullable */,
+                                       void* stream);
+HYD_API int hyd_rope_append_multi_qkn(const hyd_rope_multi_params* p, const hyd_qk_norm* qn /* nullable */, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Fork completions: promote rows of the UNIQUE K/V caches to a packed SHARED level, K and V in one launch (no forward pass: the
  * rotated K/V of the chosen completions already sit in the unique caches, and a level that comes directly after the levels in
