@@ -35,6 +35,27 @@ int check_qk_norm(const hyd_qk_norm* qn, int head_dim, int D) {
     return HYD_OK;
 }
 
+// RopeArgs from either public struct: what the one-token and the multi-token form name alike, and the norm's gains.  Each form
+// adds its own fields: fp8 scales and a narrow row width, or T and the token strides.
+template <typename P>
+RopeArgs rope_args(const P* p, const hyd_qk_norm* qn) {
+    RopeArgs a;
+    a.q = p->q; a.k = p->k; a.v = p->v; a.q_out = p->q_out; a.k_cache = p->k_cache; a.v_cache = p->v_cache;
+    a.cos = p->cos; a.sin = p->sin; a.pos = p->position_ids; a.shared_len = p->shared_len; a.seq_lens = p->seq_lens;
+    a.q_bs = p->q_batch_stride; a.k_bs = p->k_batch_stride; a.v_bs = p->v_batch_stride;
+    a.kc_bs = p->kc_batch_stride; a.kc_ts = p->kc_tok_stride; a.kc_hs = p->kc_head_stride;
+    a.vc_bs = p->vc_batch_stride; a.vc_ts = p->vc_tok_stride; a.vc_hs = p->vc_head_stride;
+    a.pos_stride = p->pos_stride; a.cs_stride = p->cs_stride;
+    a.B = p->B; a.Hq = p->Hq; a.Hkv = p->Hkv; a.cache_len = p->cache_len; a.max_pos = p->max_pos;
+    a.D = a.d = p->D;
+    if (qn) {
+        a.q_weight = qn->q_weight;
+        a.k_weight = qn->k_weight;
+        a.eps = qn->eps;
+    }
+    return a;
+}
+
 int check_w8_common(const void* w8, const float* scale, int32_t N, int32_t K, int32_t dtype, int k_multiple) {
     if (dtype != HYD_F16 && dtype != HYD_BF16) return fail(HYD_ERR_UNSUPPORTED, "dtype %d: f16 / bf16 activations (the weights are e4m3fn)", dtype);
     if (N < 1 || K < 1) return fail(HYD_ERR_BAD_ARG, "N %d / K %d must be >= 1", N, K);
@@ -59,38 +80,16 @@ int hyd_rope_append_decode_qkn(const hyd_rope_params* p, const hyd_kv_quant* kq,
     if ((rc = check_rope(p, {}, {{p->q_batch_stride, "q_batch_stride"}, {p->k_batch_stride, "k_batch_stride"}, {p->v_batch_stride, "v_batch_stride"}})))
         return rc;
     if ((rc = check_qk_norm(qn, p->head_dim, p->D))) return rc;
-    RopeArgs a;
-    memset(&a, 0, sizeof(a));
-    a.q = p->q; a.k = p->k; a.v = p->v; a.q_out = p->q_out; a.k_cache = p->k_cache; a.v_cache = p->v_cache;
-    a.cos = p->cos; a.sin = p->sin; a.pos = p->position_ids; a.shared_len = p->shared_len; a.seq_lens = p->seq_lens;
-    a.q_bs = p->q_batch_stride; a.k_bs = p->k_batch_stride; a.v_bs = p->v_batch_stride;
-    a.kc_bs = p->kc_batch_stride; a.kc_ts = p->kc_tok_stride; a.kc_hs = p->kc_head_stride;
-    a.vc_bs = p->vc_batch_stride; a.vc_ts = p->vc_tok_stride; a.vc_hs = p->vc_head_stride;
-    a.pos_stride = p->pos_stride; a.cs_stride = p->cs_stride;
-    a.B = p->B; a.Hq = p->Hq; a.Hkv = p->Hkv; a.cache_len = p->cache_len; a.max_pos = p->max_pos;
-    if (qn) {
-        RopeKvqArgs ka;
-        ka.a = a;
-        ka.k_scale = kq ? kq->k_scale : nullptr;
-        ka.v_scale = kq ? kq->v_scale : nullptr;
-        return launched(launch_rope_append_norm(a, kq ? &ka : nullptr, qn->q_weight, qn->k_weight, qn->eps, p->dtype, p->D, static_cast<hipStream_t>(stream)),
-                        "rope_append (q/k norm) kernel launch");
-    }
-    if (narrow) {
-        RopeNarrowArgs na;
-        na.a = a;
-        na.D = p->D;
-        na.d = narrow;
-        return launched(launch_rope_append_narrow(na, p->dtype, static_cast<hipStream_t>(stream)), "rope_append (narrow head dim) kernel launch");
-    }
+    RopeArgs a = rope_args(p, qn);
+    if (narrow) a.d = narrow;
     if (kq) {
-        RopeKvqArgs ka;
-        ka.a = a;
-        ka.k_scale = kq->k_scale;
-        ka.v_scale = kq->v_scale;
-        return launched(launch_rope_append_fp8(ka, p->dtype, p->D, static_cast<hipStream_t>(stream)), "rope_append (fp8 caches) kernel launch");
+        a.fp8 = 1;
+        a.k_scale = kq->k_scale;
+        a.v_scale = kq->v_scale;
     }
-    return launched(launch_rope_append(a, p->dtype, p->D, static_cast<hipStream_t>(stream)), "rope_append kernel launch");
+    return launched(launch_rope_append(a, p->dtype, static_cast<hipStream_t>(stream)),
+                    qn ? "rope_append (q/k norm) kernel launch" : narrow ? "rope_append (narrow head dim) kernel launch"
+                    : kq ? "rope_append (fp8 caches) kernel launch" : "rope_append kernel launch");
 }
 
 int hyd_rope_append_decode_kvq(const hyd_rope_params* p, const hyd_kv_quant* kq, void* stream) { return hyd_rope_append_decode_qkn(p, kq, nullptr, stream); }
@@ -107,10 +106,11 @@ int hyd_rope_append_multi_qkn(const hyd_rope_multi_params* p, const hyd_qk_norm*
                           {p->q_tok_stride, "q_tok_stride"}, {p->k_tok_stride, "k_tok_stride"}, {p->v_tok_stride, "v_tok_stride"}})))
         return rc;
     if ((rc = check_qk_norm(qn, 0, p->D))) return rc;
-    if (qn)
-        return launched(launch_rope_append_norm_multi(*p, qn->q_weight, qn->k_weight, qn->eps, static_cast<hipStream_t>(stream)),
-                        "rope_append (multi-token, q/k norm) kernel launch");
-    return launched(launch_rope_append_multi(*p, static_cast<hipStream_t>(stream)), "rope_append (multi-token) kernel launch");
+    RopeArgs a = rope_args(p, qn);
+    a.T = p->T;
+    a.q_ts = p->q_tok_stride; a.k_ts = p->k_tok_stride; a.v_ts = p->v_tok_stride;
+    return launched(launch_rope_append(a, p->dtype, static_cast<hipStream_t>(stream)),
+                    qn ? "rope_append (multi-token, q/k norm) kernel launch" : "rope_append (multi-token) kernel launch");
 }
 
 int hyd_rope_append_multi(const hyd_rope_multi_params* p, void* stream) { return hyd_rope_append_multi_qkn(p, nullptr, stream); }

@@ -104,33 +104,31 @@ struct CombineArgs {
     int32_t scalar_only;  // force the element-wise kernel (unaligned tensors)
 };
 
-struct RopeArgs {
-    const void* q;
-    const void* k;
-    const void* v;
-    void* q_out;
-    void* k_cache;
-    void* v_cache;
-    const float* cos;
-    const float* sin;
-    const int64_t* pos;
-    const int64_t* shared_len;  // may be null
-    int32_t* seq_lens;
-    int64_t q_bs, k_bs, v_bs;          // batch strides of q/k/v (elements); heads contiguous
-    int64_t kc_bs, kc_ts, kc_hs, vc_bs, vc_ts, vc_hs;
-    int64_t pos_stride, cs_stride;
-    int32_t B, Hq, Hkv, cache_len, max_pos;
-};
-
-struct RopeKvqArgs {  // rope_append.hip, fp8 caches: k_cache / v_cache hold e4m3fn bytes (strides in bytes)
-    RopeArgs a;
-    const float* k_scale;  // [Hkv] or null = 1
-    const float* v_scale;
-};
-
-struct RopeNarrowArgs {  // rope_append.hip, narrow head dims: q / k / v and the cache rows hold d elements per head, q_out D (zero pad columns)
-    RopeArgs a;
-    int32_t D, d;
+struct RopeArgs {  // rope_append.hip, every form of the preamble; the defaults describe the plain one-token call on 16-bit caches
+    const void* q = nullptr;
+    const void* k = nullptr;
+    const void* v = nullptr;
+    void* q_out = nullptr;
+    void* k_cache = nullptr;
+    void* v_cache = nullptr;
+    const float* cos = nullptr;
+    const float* sin = nullptr;
+    const int64_t* pos = nullptr;
+    const int64_t* shared_len = nullptr;  // may be null
+    int32_t* seq_lens = nullptr;
+    int64_t q_bs = 0, k_bs = 0, v_bs = 0;  // batch strides of q/k/v (elements); heads contiguous
+    int64_t q_ts = 0, k_ts = 0, v_ts = 0;  // their token strides (T > 1)
+    int64_t kc_bs = 0, kc_ts = 0, kc_hs = 0, vc_bs = 0, vc_ts = 0, vc_hs = 0;  // elements; bytes with fp8
+    int64_t pos_stride = 0, cs_stride = 0;
+    const float* k_scale = nullptr;  // fp8: [Hkv] or null = 1
+    const float* v_scale = nullptr;
+    const void* q_weight = nullptr;  // per-head q/k RMSNorm in front of the rotation: gains [D] of the q dtype, or both null = no norm
+    const void* k_weight = nullptr;
+    float eps = 0.f;
+    int32_t B = 0, Hq = 0, Hkv = 0, cache_len = 0, max_pos = 0;
+    int32_t T = 1;         // tokens per batch row; q / k / v are [B, T, H, d]
+    int32_t D = 0, d = 0;  // the kernels' head dim (64 / 128 / 256) and the rows' width: d < D = narrow rows, q_out keeps the pitch D (zero pad columns)
+    int32_t fp8 = 0;       // k_cache / v_cache hold e4m3fn bytes
 };
 
 struct NormArgs {  // layer_ops.hip: h = residual + x; normed = RMSNorm(h) * weight
@@ -343,7 +341,7 @@ int launch_kv_promote(const KvPromoteArgs& a, int src_dtype, int dst_dtype, hipS
 int launch_kv_gather(const KvGatherArgs& a, int src_dtype, int dst_dtype, hipStream_t s);    // kv_gather.hip
 int launch_prefix_w64(const PrefixArgs& a, int dtype, int D, bool causal, int grid, hipStream_t s);
 int launch_prefix_w64_f16(const PrefixArgs& a, int D, bool causal, int grid, hipStream_t s);  // prefix_attn_w64_f16.hip
-int launch_rope_append(const RopeArgs& a, int dtype, int D, hipStream_t s);
+int launch_rope_append(const RopeArgs& a, int dtype, hipStream_t s);  // rope_append.hip: the kernel is picked from a's fields
 int launch_add_rmsnorm(const NormArgs& a, int dtype, hipStream_t s);
 int launch_swiglu(const SwigluArgs& a, int dtype, hipStream_t s);
 int launch_sample(const SampleArgs& a, int dtype, hipStream_t s);
@@ -361,17 +359,10 @@ bool suffix_fp8_eligible(const SuffixArgs& a, int D);                           
 int launch_suffix_fp8(const SuffixKvqArgs& a, int dtype, int D, hipStream_t s);       // q dtype; K/V e4m3fn
 bool suffix_gqa_fp8_eligible(const SuffixArgs& a, int D);                             // suffix_attn_gqa_fp8.hip, shapes only
 int launch_suffix_gqa_fp8(const SuffixKvqArgs& a, int dtype, int D, hipStream_t s);   // q dtype; K/V e4m3fn, grouped-query shapes
-int launch_rope_append_fp8(const RopeKvqArgs& a, int dtype, int D, hipStream_t s);
-int launch_rope_append_narrow(const RopeNarrowArgs& a, int dtype, hipStream_t s);      // 16-bit caches, head_dim d < D
 int launch_suffix_gqa(const SuffixArgs& a, int dtype, int D, hipStream_t s);
 bool suffix_causal_eligible(const SuffixArgs& a, int D);                              // suffix_attn_causal.hip, shapes only
 int launch_suffix_causal(const SuffixArgs& a, int dtype, int D, hipStream_t s);       // the causal-tail suffix pass (nq = 2..8)
 // speculative decoding: these kernels take the validated public parameter blocks as they are
-int launch_rope_append_multi(const hyd_rope_multi_params& p, hipStream_t s);          // rope_append.hip
-// ... and with the per-head q/k RMSNorm in front of the rotation (hyd_qk_norm: gains [D] of the q dtype); ka null = 16-bit caches
-int launch_rope_append_norm(const RopeArgs& a, const RopeKvqArgs* ka, const void* q_weight, const void* k_weight, float eps, int dtype, int D,
-                            hipStream_t s);
-int launch_rope_append_norm_multi(const hyd_rope_multi_params& p, const void* q_weight, const void* k_weight, float eps, hipStream_t s);
 int launch_draft_lookup(const hyd_draft_lookup_params& p, hipStream_t s);             // draft_lookup.hip
 int launch_draft_accept(const hyd_draft_accept_params& p, hipStream_t s);             // draft_accept.hip
 int launch_draft_accept_states(const hyd_draft_accept_params& p, const int32_t* step_state_after, int32_t* state, hipStream_t s);
