@@ -16,13 +16,15 @@
 //   V:    the landing tile is widened into a wave-private 16-bit tile in the 16-bit kernel's swizzled layout, and V^T is read from it
 //         with the 16-bit transposing reads.  (ds_read_b64_tr_b8 exists on gfx950, but whether its lane map fits the
 //         accumulator-permuted key order of P^T has not been established; one more LDS pass buys the unchanged, tested layout.)
-// The body is this file's own, not a shared header with suffix_attn_gqa.hip: the tiles, the DMA geometry, the number of steps in
-// flight and the collect differ, which is most of what the stream loop is; what the two kernels share as code is
-// suffix_gqa_common.h.  Partials, softmax, the four-wave merge and the epilogue follow the 16-bit kernel line by line, and
-// tests/test_fp8_gqa_gpu.py holds the two bit-equal.
+// The stream is this file's own: the tiles, the DMA geometry, the number of steps in flight, the collect with its widening, the
+// scale loads and their settle point differ from the 16-bit kernel's, which is most of what the stream loop is.  What is around
+// it -- requesting, fetching and folding the prefix partials, the softmax step on a collected tile, the four-wave merge, the
+// epilogue and the raise-the-LDS-limit launch -- is the 16-bit kernel's own code, shared through suffix_gqa_unit.h (the asm
+// primitives: suffix_gqa_common.h).  Written out here as there: the two loops over a wave's partials; here only: the query load
+// (profiles/gqa_unit_frame.md has the measurements behind both).  tests/test_fp8_gqa_gpu.py holds the two kernels bit-equal.
 #include <type_traits>
 
-#include "suffix_gqa_common.h"
+#include "suffix_gqa_unit.h"
 
 namespace hyd {
 
@@ -52,7 +54,6 @@ __global__ __launch_bounds__(64 * WPU * HPW) __attribute__((amdgpu_waves_per_eu(
     constexpr int NWV = WPU * HPW;  // waves per workgroup
     warm_kernargs_256();
     const SuffixArgs& a = ka.a;
-    using TR = Traits<T>;
     constexpr int RB8 = D;           // bytes per fp8 K/V row
     constexpr int RB = D * 2;        // bytes per row of the widened V tile
     constexpr int NCH = D / 32;      // 32-dim chunks of the QK^T contraction
@@ -90,10 +91,12 @@ __global__ __launch_bounds__(64 * WPU * HPW) __attribute__((amdgpu_waves_per_eu(
     float vsc = ka.v_scale ? ka.v_scale[hk] : 1.0f;
 
     // ---- this lane's query row (B operand of S^T = K Q^T: column = row l15, 8 dims of every 32-dim chunk) ----
+    // (written out: through gqa_load_query, as in the 16-bit kernel, the one-wave instantiations lost 1.6 % at the C5 whole job)
     const int row = row0 + l15;
     const bool rvalid = row < a.rows;
     const int iq = a.nq == 1 ? 0 : (rvalid ? row / a.g : 0), gq = a.nq == 1 ? (rvalid ? row : 0) : (rvalid ? row % a.g : 0);
     const int64_t ridx = ((int64_t)b * a.nq + iq) * a.Hq + hk * a.g + gq;  // [B, nq, Hq]
+    const int back = 0;  // (no causal-tail form)
     u32x4 qf[NCH];
     {
         const uint16_t* qr = static_cast<const uint16_t*>(a.q) + ridx * D + 8 * g4;
@@ -104,9 +107,10 @@ __global__ __launch_bounds__(64 * WPU * HPW) __attribute__((amdgpu_waves_per_eu(
         }
     }
 
-    // ---- prefix partials: dealt to the unit's waves, the wave's first NPRE requested in front of the K/V stream (suffix_attn_gqa.hip) ----
+    // ---- prefix partials: dealt to the unit's waves, the wave's first NPRE requested in front of the K/V stream (suffix_gqa_unit.h) ----
+    // (this loop and the one behind the stream are written out, as in the 16-bit kernel)
     const int np = a.n_partials;
-    constexpr int NPRE = D == 256 ? 1 : 2;
+    constexpr int NPRE = gqa_npre<D>();
     const int npre = a.lse != nullptr ? 0 : min(NPRE, (np - wave + WPU - 1) / WPU);  // (np <= wave: 0)
     bool pre_folded = npre <= 0;
     bool pre_f32[NPRE];
@@ -118,23 +122,7 @@ __global__ __launch_bounds__(64 * WPU * HPW) __attribute__((amdgpu_waves_per_eu(
         plse[k] = -INFINITY;
 #pragma unroll
         for (int db = 0; db < NDB; ++db) pbuf[k][db] = u32x4{0u, 0u, 0u, 0u};
-        if (k < npre) {
-            const PartialDev& pd = a.partials[wave + k * WPU];
-            pre_f32[k] = pd.is_f32 != 0;
-            plse[k] = pd.lse[ridx];
-            if (pre_f32[k]) {
-                const float* po = static_cast<const float*>(pd.out) + ridx * D + 4 * g4;
-#pragma unroll
-                for (int db = 0; db < NDB; ++db) pbuf[k][db] = *reinterpret_cast<const u32x4*>(po + 16 * db);
-            } else {
-                const uint16_t* po = static_cast<const uint16_t*>(pd.out) + ridx * D + 4 * g4;
-#pragma unroll
-                for (int db = 0; db < NDB; ++db) {
-                    const u32x2 u = *reinterpret_cast<const u32x2*>(po + 16 * db);
-                    pbuf[k][db] = __builtin_shufflevector(u, u, 0, 1, -1, -1);
-                }
-            }
-        }
+        if (k < npre) gqa_request_partial<D>(a.partials[wave + k * WPU], ridx, g4, pre_f32[k], pbuf[k], plse[k]);
     }
 
     // ---- K / V windows of this unit (strides count bytes): rows [0, len) are in range, everything else reads as zero bytes = +0 ----
@@ -228,104 +216,25 @@ __global__ __launch_bounds__(64 * WPU * HPW) __attribute__((amdgpu_waves_per_eu(
         // every read has returned before the landing set is handed to the next DMA (asm: hipcc does not order it against them otherwise)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     };
-    // a step that reaches past the keys: zero the V rows of keys >= seg_len (as the 16-bit kernel does)
-    auto sanitize = [&](int key0) __attribute__((always_inline)) {
-        const int kb = key0 + 4 * g4;
-        unsigned msk[4];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const int ka_ = kb + (w >> 1) * 16 + (w & 1) * 2;
-            msk[w] = (ka_ < seg_len ? 0x0000ffffu : 0u) | (ka_ + 1 < seg_len ? 0xffff0000u : 0u);
-        }
-#pragma unroll
-        for (int db = 0; db < NDB; ++db)
-#pragma unroll
-            for (int w = 0; w < 4; ++w) vf[db][w] &= msk[w];
-    };
-    auto compute = [&](int key0) __attribute__((always_inline)) {
-        f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            mfma16_acc<T>(s0, kf[0][c], qf[c]);
-            mfma16_acc<T>(s1, kf[1][c], qf[c]);
-        }
-        asm volatile("s_nop 7\n\ts_nop 7" : "+v"(s0), "+v"(s1));
-        float p[8];
-        const int kb = key0 + 4 * g4;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            p[i] = (kb + i < seg_len) ? s0[i] * sc : -INFINITY;
-            p[4 + i] = (kb + 16 + i < seg_len) ? s1[i] * sc : -INFINITY;
-        }
-        float tmax = fmaxf(fmaxf(fmaxf(p[0], p[1]), fmaxf(p[2], p[3])), fmaxf(fmaxf(p[4], p[5]), fmaxf(p[6], p[7])));
-        tmax = quad_max(tmax);
-        const float m_new = fmaxf(m_run, tmax);
-        const float alpha = fast_exp2(m_run - m_new);
-        float ps = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            p[i] = fast_exp2(p[i] - m_new);
-            ps += p[i];
-        }
-        ps = quad_sum(ps);
-        l_run = l_run * alpha + ps;
-        m_run = m_new;
-        const u32x4 pf = {TR::pack2(p[0], p[1]), TR::pack2(p[2], p[3]), TR::pack2(p[4], p[5]), TR::pack2(p[6], p[7])};
-#pragma unroll
-        for (int db = 0; db < NDB; ++db) {
-            o[db] *= alpha;
-            mfma16_acc<T>(o[db], vf[db], pf);
-        }
-        asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
-    };
-
-    // ---- folding a prefix partial into this wave's state ----
+    // ---- folding a prefix partial into this wave's state: the shared pieces behind lambdas of this kernel (called straight, the
+    // four-wave instantiations lost 2 % at C3, profiles/gqa_unit_frame.md) ----
     auto fold = [&](float lse_p, const f32x4(&x)[NDB]) __attribute__((always_inline)) {
-        const float m_p = lse_p * 1.4426950408889634f;
-        const float mf = fmaxf(m_run, m_p);
-        const float ms = (mf == -INFINITY) ? 0.f : mf;
-        const float a1 = fast_exp2(m_run - ms), a2 = fast_exp2(m_p - ms);
-        l_run = l_run * a1 + a2;
-        m_run = mf;
-#pragma unroll
-        for (int db = 0; db < NDB; ++db) o[db] = o[db] * a1 + x[db] * a2;
-    };
-    auto widen = [&](const u32x2(&u)[NDB], f32x4(&x)[NDB]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int db = 0; db < NDB; ++db) x[db] = f32x4{TR::lo(u[db][0]), TR::hi(u[db][0]), TR::lo(u[db][1]), TR::hi(u[db][1])};
+        gqa_fold<D>(lse_p, x, o, m_run, l_run);
     };
     auto fetch = [&](const PartialDev& pd, f32x4(&x)[NDB]) __attribute__((always_inline)) {
-        if (pd.is_f32) {
-#pragma unroll
-            for (int db = 0; db < NDB; ++db)
-                x[db] = *reinterpret_cast<const f32x4*>(static_cast<const float*>(pd.out) + ridx * D + 16 * db + 4 * g4);
-        } else {
-            u32x2 u[NDB];
-#pragma unroll
-            for (int db = 0; db < NDB; ++db)
-                u[db] = *reinterpret_cast<const u32x2*>(static_cast<const uint16_t*>(pd.out) + ridx * D + 16 * db + 4 * g4);
-            widen(u, x);
-        }
+        gqa_fetch<T, D>(pd, ridx, g4, x);
     };
     auto fold_pre = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int k = 0; k < NPRE; ++k) {
-            // opaque: hipcc must not hoist the conversions below (and with them its wait for the request) in front of the stream
-            asm volatile("" : "+v"(plse[k]));
-#pragma unroll
-            for (int db = 0; db < NDB; ++db) asm volatile("" : "+v"(pbuf[k][db]));
-            if (k < npre) {
-                f32x4 x[NDB];
-#pragma unroll
-                for (int db = 0; db < NDB; ++db) {
-                    const f32x4 xf = __builtin_bit_cast(f32x4, pbuf[k][db]);
-                    const f32x4 xh = f32x4{TR::lo(pbuf[k][db][0]), TR::hi(pbuf[k][db][0]), TR::lo(pbuf[k][db][1]), TR::hi(pbuf[k][db][1])};
-                    x[db] = pre_f32[k] ? xf : xh;
-                }
-                fold(plse[k], x);
-            }
-        }
+        gqa_fold_pre<T, D>(npre, pre_f32, pbuf, plse, o, m_run, l_run);
         pre_folded = true;
+    };
+    // (a lambda around the three pieces: called straight from the loop, hipcc grows the bf16 kernels by more than 1 %)
+    auto compute = [&](int key0) __attribute__((always_inline)) {
+        float p[8];
+        u32x4 pf;
+        const float tmax = gqa_scores<T, D, false>(key0, g4, seg_len, back, sc, kf, qf, p);
+        const float alpha = gqa_softmax_update<T, false>(tmax, p, m_run, l_run, pf);
+        gqa_pv<T, D>(alpha, pf, vf, o);
     };
     {
         constexpr int stride = 32 * WPU;
@@ -343,7 +252,7 @@ __global__ __launch_bounds__(64 * WPU * HPW) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
         for (int c = 0; c < NCH; ++c) asm volatile("" ::"v"(qf[c]));
         asm volatile("" : "+v"(ksc), "+v"(vsc));
-        if (!pre_folded) fold_pre();
+        if (!pre_folded) fold_pre();  // the pre-requested partials have landed
         // the second set's first step goes out BEHIND the drain: hipcc's own wait for q and the partials is a full one and must not
         // find a key step it does not know about in the queue
         if (NSET == 2 && nst > 1) issue(k_first + stride, SETB);
@@ -355,7 +264,7 @@ __global__ __launch_bounds__(64 * WPU * HPW) __attribute__((amdgpu_waves_per_eu(
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
             collect(so);
-            if (key0 + 32 > seg_len) sanitize(key0);
+            if (key0 + 32 > seg_len) gqa_sanitize<D>(key0, g4, seg_len, vf);
             if (j + NSET < nst) issue(key0 + NSET * stride, so);  // in flight while steps j (and j + 1) are computed
             compute(key0);
         }
@@ -363,7 +272,7 @@ __global__ __launch_bounds__(64 * WPU * HPW) __attribute__((amdgpu_waves_per_eu(
     // the keys-only state (the LSE output is the suffix pass's own; when it is asked for, no partial was folded above)
     const float m_s = m_run, l_s = l_run;
 
-    // ---- this wave's other partials (all of them when the LSE output is asked for) ----
+    // ---- this wave's other partials (all of them when the LSE output is asked for), two per round trip ----
     for (int i = wave + max(npre, 0) * WPU; i < np; i += 2 * WPU) {
         const bool two = i + WPU < np;
         const int i1 = two ? i + WPU : i;
@@ -376,51 +285,13 @@ __global__ __launch_bounds__(64 * WPU * HPW) __attribute__((amdgpu_waves_per_eu(
         fold(lse1, x1);
     }
 
-    // ---- merge the WPU waves of the unit: every wave leaves (m, l, O^T) in its own widened V tile, wave 0 folds them ----
+    // ---- merge the WPU waves of the unit through their widened V tiles ----
     float ms_run = m_s, ls_run = l_s;
     if constexpr (WPU > 1) {
-        float* mine = reinterpret_cast<float*>(vtile);  // [16 rows][D]: O (unnormalised)
-#pragma unroll
-        for (int db = 0; db < NDB; ++db)
-            *reinterpret_cast<f32x4*>(mine + l15 * D + 16 * db + 4 * g4) = o[db];
-        if (g4 == 0) {
-            mlx[wave][0][l15] = m_run;
-            mlx[wave][1][l15] = l_run;
-            mlx[wave][2][l15] = m_s;
-            mlx[wave][3][l15] = l_s;
-        }
-        __syncthreads();
-        if (wave != 0) return;
-#pragma unroll
-        for (int w = 1; w < WPU; ++w) {
-            const float* oth = reinterpret_cast<const float*>(gqa8_smem + w * WB + NSET * SETB);
-            const float m2 = mlx[w][0][l15], l2 = mlx[w][1][l15];
-            const float mf = fmaxf(m_run, m2);
-            const float ms = (mf == -INFINITY) ? 0.f : mf;
-            const float a1 = fast_exp2(m_run - ms), a2 = fast_exp2(m2 - ms);
-            l_run = l_run * a1 + l2 * a2;
-            m_run = mf;
-            const float m3 = mlx[w][2][l15], l3 = mlx[w][3][l15];
-            const float mg = fmaxf(ms_run, m3);
-            const float mgs = (mg == -INFINITY) ? 0.f : mg;
-            ls_run = ls_run * fast_exp2(ms_run - mgs) + l3 * fast_exp2(m3 - mgs);
-            ms_run = mg;
-#pragma unroll
-            for (int db = 0; db < NDB; ++db) o[db] = o[db] * a1 + *reinterpret_cast<const f32x4*>(oth + l15 * D + 16 * db + 4 * g4) * a2;
-            asm volatile("" ::: "memory");  // one wave's tile at a time
-        }
+        auto tile_of = [&](int w) { return reinterpret_cast<const float*>(gqa8_smem + w * WB + NSET * SETB); };
+        if (!gqa_merge_waves<D, WPU>(wave, l15, g4, reinterpret_cast<float*>(vtile), tile_of, mlx, m_s, l_s, o, m_run, l_run, ms_run, ls_run)) return;
     }
-
-    // ---- epilogue: normalise and store (the prefix partials are already in) ----
-    if (!rvalid) return;
-    if (a.lse && g4 == 0) a.lse[ridx] = ls_run > 0.f ? ms_run * kLn2 + __logf(ls_run) : -INFINITY;
-    const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;
-#pragma unroll
-    for (int db = 0; db < NDB; ++db) {
-        const f32x4 x = o[db] * inv;
-        const u32x2 pk = {TR::pack2(x[0], x[1]), TR::pack2(x[2], x[3])};
-        *reinterpret_cast<u32x2*>(static_cast<uint16_t*>(a.out) + ridx * D + 16 * db + 4 * g4) = pk;
-    }
+    gqa_epilogue<T, D>(a, rvalid, ridx, g4, o, l_run, ms_run, ls_run);
 }
 
 // Shapes only (capture-safe): exactly the shapes launch_suffix sends to the grouped-query kernel for a sequence's own 16-bit cache
@@ -435,21 +306,8 @@ static int launch_gqa8_k(const SuffixKvqArgs& ka, dim3 grid, hipStream_t s) {
     constexpr size_t wave_bytes = (size_t)(D <= 128 ? 2 : 1) * 2 * 32 * D + (size_t)32 * D * 2;  // landing sets + widened V tile
     constexpr size_t lds = NWV * wave_bytes + (WPU > 1 ? (size_t)NWV * 4 * 16 * sizeof(float) : 0);
     static_assert(lds <= 160 * 1024, "LDS of one workgroup");
-    auto kern = suffix_attn_gqa_fp8_kernel<T, D, WPU, HPW>;
-    if (lds > 64 * 1024) {
-        // more than the default dynamic-LDS limit: raise it, once per DEVICE and instantiation (suffix_attn_gqa.hip)
-        static hipError_t attr_rc[16];
-        static bool attr_set[16];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return (int)hipErrorInvalidDevice;
-        if (!__atomic_load_n(&attr_set[dev], __ATOMIC_ACQUIRE)) {  // idempotent: two threads racing both set the same value
-            attr_rc[dev] = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            __atomic_store_n(&attr_set[dev], true, __ATOMIC_RELEASE);
-        }
-        if (attr_rc[dev] != hipSuccess) return (int)attr_rc[dev];
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(64 * NWV), lds, s, ka);
-    return (int)hipGetLastError();
+    // more than the default dynamic-LDS limit: raised to exactly what the launch needs
+    return gqa_launch_lds<suffix_attn_gqa_fp8_kernel<T, D, WPU, HPW>>(ka, grid, 64 * NWV, lds, lds > 64 * 1024, (int)lds, s);
 }
 
 template <typename T, int D>

@@ -1,10 +1,13 @@
-// The matrix-core suffix kernel of suffix_attn_gqa.hip (the design notes are there): its body, the kernels that wrap it and their launcher,
-// in a header so that suffix_attn_causal.hip can instantiate the causal-tail form without touching the instantiations of suffix_attn_gqa.hip.
+// The matrix-core suffix kernel of suffix_attn_gqa.hip (the design notes are there) and its launcher, in a header so that
+// suffix_attn_causal.hip can instantiate the causal-tail form without touching the instantiations of suffix_attn_gqa.hip.  What is
+// written out here is the 16-bit K/V stream: the LDS layout, the DMA geometry and swizzles, issue / collect, the steps in flight with
+// their counted waits, and the two-segment walk.  The lane's query row, the prefix partials, the softmax step on a collected tile, the
+// four-wave merge, the epilogue and the raise-the-LDS-limit launch are suffix_gqa_unit.h's, shared with the fp8 kernel.
 #pragma once
 #include <cstdlib>
 #include <type_traits>
 
-#include "suffix_gqa_common.h"
+#include "suffix_gqa_unit.h"
 
 namespace hyd {
 
@@ -24,8 +27,8 @@ namespace hyd {
 // in the plain form.  That does NOT hold for every wave: with four waves per unit wave w starts at key 32 w, and a tile that
 // begins below len can lie wholly beyond a row's limit (len = 33, nq = 8: row 0 sees keys < 26, wave 1 starts at key 32), so a
 // row's maximum in that wave is -inf until the merge; so is every row's whose sequence is shorter than nq.  The rescale in
-// compute() therefore guards the -inf maximum in every CT instantiation, unconditionally -- it must stay; such a state merges as
-// (m = -inf, l = 0), and a row without any key ends as zeros with lse = -inf.
+// gqa_softmax_update() (suffix_gqa_unit.h) therefore guards the -inf maximum in every CT instantiation, unconditionally -- it must
+// stay; such a state merges as (m = -inf, l = 0), and a row without any key ends as zeros with lse = -inf.
 // The including source picks the form with HYD_SUFFIX_CAUSAL_TAIL (one form per translation unit): the plain kernel keeps the name,
 // the template arguments and the text it has always had, so the instantiations of suffix_attn_gqa.hip compile as before.
 #ifndef HYD_SUFFIX_CAUSAL_TAIL
@@ -45,7 +48,6 @@ __global__ __launch_bounds__(64 * WPU * HPW) __attribute__((amdgpu_waves_per_eu(
     // a unit's dependent chain (C5 slice 7.17 -> 7.00 us at S = 16, 25.6 -> 24.9 at S = 128 in an A/B within one run; the dot-product
     // kernel, whose 32768 waves all pay the four extra loads, lost 2-7 % at S <= 4 with it and does not have it)
     warm_kernargs_256();
-    using TR = Traits<T>;
     constexpr int RB = D * 2;        // bytes per K/V row
     constexpr int NCH = D / 32;      // 32-dim chunks of the QK^T contraction
     constexpr int NDB = D / 16;      // 16-wide d blocks of O^T
@@ -80,37 +82,21 @@ __global__ __launch_bounds__(64 * WPU * HPW) __attribute__((amdgpu_waves_per_eu(
     if (a.sl32) len_raw = a.sl32[b];
     else if (a.sl64) len_raw = (int)a.sl64[b];
 
-    // ---- this lane's query row (B operand of S^T = K Q^T: column = row l15, 8 dims of every 32-dim chunk) ----
-    const int row = row0 + l15;
-    const bool rvalid = row < a.rows;
-    const int iq = a.nq == 1 ? 0 : (rvalid ? row / a.g : 0), gq = a.nq == 1 ? (rvalid ? row : 0) : (rvalid ? row % a.g : 0);
-    const int64_t ridx = ((int64_t)b * a.nq + iq) * a.Hq + hk * a.g + gq;  // [B, nq, Hq]
-    [[maybe_unused]] const int back = CT && rvalid ? a.nq - 1 - iq : 0;  // CT: the newest keys this row's token does not see
+    bool rvalid;
+    int64_t ridx;
+    [[maybe_unused]] int back;
     u32x4 qf[NCH];
-    {
-        const uint16_t* qr = static_cast<const uint16_t*>(a.q) + ridx * D + 8 * g4;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const u32x4 z = {0u, 0u, 0u, 0u};
-            qf[c] = rvalid ? *reinterpret_cast<const u32x4*>(qr + 32 * c) : z;
-        }
-    }
+    gqa_load_query<D, CT>(a, b, hk, row0, l15, g4, rvalid, ridx, back, qf);
 
-    // ---- prefix partials (attention.py:21-43) are dealt to the unit's waves: wave w folds partials w, w + WPU, ... into
-    // its own (m, l, O) state -- a normalised partial (O_p, lse_p) IS a state (m = lse_p * log2 e, l = 1, O = O_p) -- and the
-    // merge of the waves then combines everything; no partial is left for the final epilogue.  The wave's first TWO partials (16-bit,
-    // fp32, or a split level's fp32 slices) are requested here, in front of the K/V stream, and folded when the first key step
-    // has landed; the others are fetched behind the loop, two per round trip.  (hipcc counts only its own loads.  A plain load
-    // that is still pending inside the loop makes it insert counted waits that also wait for the next step's DMAs, which it
-    // does not know about -- one plain request before the stream, settled at the first wait, is what stays exact.  Round 5
-    // tried one partial per key step through an asm-owned register buffer: 1 us at the paper default, nothing at C3 / C5.)
-    // Not when the suffix pass's own LSE is asked for (a.lse: the unfused form), which needs the keys-only state at the end.
+    // ---- prefix partials: dealt to the unit's waves, the wave's first NPRE requested in front of the K/V stream (suffix_gqa_unit.h) ----
+    // (this loop and the one behind the stream are written out: as functions of the header they moved hipcc's own waits and grew
+    // the D = 64 kernels by more than 1 %, profiles/gqa_unit_frame.md)
     const int np = a.n_partials;
-    constexpr int NPRE = D == 256 ? 1 : 2;  // partials of this wave requested in front of the stream (a split level's two slices at C5; 2 of 4 at C3)
+    constexpr int NPRE = gqa_npre<D>();
     const int npre = a.lse != nullptr ? 0 : min(NPRE, (np - wave + WPU - 1) / WPU);  // (np <= wave: 0)
     bool pre_folded = npre <= 0;
     bool pre_f32[NPRE];
-    u32x4 pbuf[NPRE][NDB];  // a partial's row piece of this lane: dims [16 db + 4 g4, +4) as fp32, or as 16-bit in the low half
+    u32x4 pbuf[NPRE][NDB];
     float plse[NPRE];
 #pragma unroll
     for (int k = 0; k < NPRE; ++k) {
@@ -118,23 +104,7 @@ __global__ __launch_bounds__(64 * WPU * HPW) __attribute__((amdgpu_waves_per_eu(
         plse[k] = -INFINITY;
 #pragma unroll
         for (int db = 0; db < NDB; ++db) pbuf[k][db] = u32x4{0u, 0u, 0u, 0u};
-        if (k < npre) {
-            const PartialDev& pd = a.partials[wave + k * WPU];
-            pre_f32[k] = pd.is_f32 != 0;
-            plse[k] = pd.lse[ridx];
-            if (pre_f32[k]) {
-                const float* po = static_cast<const float*>(pd.out) + ridx * D + 4 * g4;
-#pragma unroll
-                for (int db = 0; db < NDB; ++db) pbuf[k][db] = *reinterpret_cast<const u32x4*>(po + 16 * db);
-            } else {
-                const uint16_t* po = static_cast<const uint16_t*>(pd.out) + ridx * D + 4 * g4;
-#pragma unroll
-                for (int db = 0; db < NDB; ++db) {  // (upper half undefined: no move, hence no wait, between the load and its register)
-                    const u32x2 u = *reinterpret_cast<const u32x2*>(po + 16 * db);
-                    pbuf[k][db] = __builtin_shufflevector(u, u, 0, 1, -1, -1);
-                }
-            }
-        }
+        if (k < npre) gqa_request_partial<D>(a.partials[wave + k * WPU], ridx, g4, pre_f32[k], pbuf[k], plse[k]);
     }
 
     // ---- K / V windows of this unit: rows [0, len) are in range, everything else reads as zero ------------------
@@ -200,7 +170,7 @@ __global__ __launch_bounds__(64 * WPU * HPW) __attribute__((amdgpu_waves_per_eu(
     // issue:   2 NVD LDS-DMA instructions, K rows -> K tile, V rows -> V tile (zero fill past the segment's end)
     // collect: the landed tiles -> registers (K: 2 NCH ds_read_b128 in the A-operand layout; V^T: 2 NDB transposing reads), after
     //          which both tiles are free for the next step's DMA
-    // compute: S^T = K Q^T, online softmax, O^T += V^T P^T, all from registers
+    // compute: S^T = K Q^T, online softmax, O^T += V^T P^T, all from registers (gqa_sanitize / gqa_compute, suffix_gqa_unit.h)
     // The loop keeps ONE step in flight per wave while the previous one is computed (collect(j); issue(j + 1); compute(j); head dim 64: TWO, NSET):
     // 16 KiB per wave, 8 waves per CU.  (Round 4's form loaded K straight into MFMA operand layout -- 16 rows x 64 B per
     // instruction, every quarter wave 16 different cache lines -- and ran 10 % below this one on 8-kv-head shapes.)
@@ -229,112 +199,13 @@ __global__ __launch_bounds__(64 * WPU * HPW) __attribute__((amdgpu_waves_per_eu(
         // every read has returned before the tiles are handed to the next DMA (asm: hipcc does not order it against them otherwise)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     };
-    // a step that reaches past the segment's keys: zero the V rows of keys >= seg_len (dword w of a V^T fragment holds keys
-    // key0 + 4 g4 + {0,1} / {2,3} / 16 + {0,1} / 16 + {2,3}, the first in its low half)
-    auto sanitize = [&](int key0) __attribute__((always_inline)) {
-        const int kb = key0 + 4 * g4;
-        unsigned msk[4];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const int ka = kb + (w >> 1) * 16 + (w & 1) * 2;
-            msk[w] = (ka < seg_len ? 0x0000ffffu : 0u) | (ka + 1 < seg_len ? 0xffff0000u : 0u);
-        }
-#pragma unroll
-        for (int db = 0; db < NDB; ++db)
-#pragma unroll
-            for (int w = 0; w < 4; ++w) vf[db][w] &= msk[w];
-    };
+    // (a lambda around the three pieces: called straight from the loop, hipcc grows the bf16 kernels by more than 1 %)
     auto compute = [&](int key0) __attribute__((always_inline)) {
-        f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            mfma16_acc<T>(s0, kf[0][c], qf[c]);
-            mfma16_acc<T>(s1, kf[1][c], qf[c]);
-        }
-        // the MFMAs above are asm: hipcc's hazard recogniser does not see that their results need the pipeline drained
-        asm volatile("s_nop 7\n\ts_nop 7" : "+v"(s0), "+v"(s1));
-        // scores of this lane: keys key0 + 4 g4 + i (s0) and key0 + 16 + 4 g4 + i (s1), query row l15
         float p[8];
-        const int kb = key0 + 4 * g4;
-        int lim = seg_len;  // keys of the segment this lane's row sees (CT: the launcher sends no shared segment, seg_len = len)
-        if constexpr (CT) lim = seg_len - back;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            p[i] = (kb + i < lim) ? s0[i] * sc : -INFINITY;
-            p[4 + i] = (kb + 16 + i < lim) ? s1[i] * sc : -INFINITY;
-        }
-        float tmax = fmaxf(fmaxf(fmaxf(p[0], p[1]), fmaxf(p[2], p[3])), fmaxf(fmaxf(p[4], p[5]), fmaxf(p[6], p[7])));
-        tmax = quad_max(tmax);
-        const float m_max = fmaxf(m_run, tmax);  // finite: key0 < len guarantees one valid key per row (CT: not guaranteed, guarded next)
-        const float m_new = (CT && m_max == -INFINITY) ? 0.f : m_max;  // (CT: a row with no visible key in this wave's tiles so far -- see the note at the kernel)
-        const float alpha = fast_exp2(m_run - m_new);
-        float ps = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            p[i] = fast_exp2(p[i] - m_new);
-            ps += p[i];
-        }
-        ps = quad_sum(ps);
-        l_run = l_run * alpha + ps;
-        m_run = m_max;
-        const u32x4 pf = {TR::pack2(p[0], p[1]), TR::pack2(p[2], p[3]), TR::pack2(p[4], p[5]), TR::pack2(p[6], p[7])};
-#pragma unroll
-        for (int db = 0; db < NDB; ++db) {
-            o[db] *= alpha;
-            mfma16_acc<T>(o[db], vf[db], pf);
-        }
-        // the accumulators are read by plain VALU code next (the rescale of the next step, a fold, the epilogue): drain the matrix pipeline
-        asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
-    };
-
-    // ---- folding a prefix partial into this wave's state -----------------------------------------------------------------
-    auto fold = [&](float lse_p, const f32x4(&x)[NDB]) __attribute__((always_inline)) {
-        const float m_p = lse_p * 1.4426950408889634f;
-        const float mf = fmaxf(m_run, m_p);
-        const float ms = (mf == -INFINITY) ? 0.f : mf;
-        const float a1 = fast_exp2(m_run - ms), a2 = fast_exp2(m_p - ms);
-        l_run = l_run * a1 + a2;
-        m_run = mf;
-#pragma unroll
-        for (int db = 0; db < NDB; ++db) o[db] = o[db] * a1 + x[db] * a2;
-    };
-    auto widen = [&](const u32x2(&u)[NDB], f32x4(&x)[NDB]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int db = 0; db < NDB; ++db) x[db] = f32x4{TR::lo(u[db][0]), TR::hi(u[db][0]), TR::lo(u[db][1]), TR::hi(u[db][1])};
-    };
-    auto fetch = [&](const PartialDev& pd, f32x4(&x)[NDB]) __attribute__((always_inline)) {
-        if (pd.is_f32) {
-#pragma unroll
-            for (int db = 0; db < NDB; ++db)
-                x[db] = *reinterpret_cast<const f32x4*>(static_cast<const float*>(pd.out) + ridx * D + 16 * db + 4 * g4);
-        } else {
-            u32x2 u[NDB];
-#pragma unroll
-            for (int db = 0; db < NDB; ++db)
-                u[db] = *reinterpret_cast<const u32x2*>(static_cast<const uint16_t*>(pd.out) + ridx * D + 16 * db + 4 * g4);
-            widen(u, x);
-        }
-    };
-    // the pre-requested partials have landed (the caller waited for every outstanding load): fold them
-    auto fold_pre = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int k = 0; k < NPRE; ++k) {
-            // opaque: hipcc must not hoist the conversions below (and with them its wait for the request) in front of the stream
-            asm volatile("" : "+v"(plse[k]));
-#pragma unroll
-            for (int db = 0; db < NDB; ++db) asm volatile("" : "+v"(pbuf[k][db]));
-            if (k < npre) {
-                f32x4 x[NDB];
-#pragma unroll
-                for (int db = 0; db < NDB; ++db) {
-                    const f32x4 xf = __builtin_bit_cast(f32x4, pbuf[k][db]);
-                    const f32x4 xh = f32x4{TR::lo(pbuf[k][db][0]), TR::hi(pbuf[k][db][0]), TR::lo(pbuf[k][db][1]), TR::hi(pbuf[k][db][1])};
-                    x[db] = pre_f32[k] ? xf : xh;
-                }
-                fold(plse[k], x);
-            }
-        }
-        pre_folded = true;
+        u32x4 pf;
+        const float tmax = gqa_scores<T, D, CT>(key0, g4, seg_len, back, sc, kf, qf, p);
+        const float alpha = gqa_softmax_update<T, CT>(tmax, p, m_run, l_run, pf);
+        gqa_pv<T, D>(alpha, pf, vf, o);
     };
     int len = 0;
     for (int seg = has_pre ? 0 : 1; seg < 2; ++seg) {  // every segment drains its own pipeline
@@ -379,7 +250,10 @@ __global__ __launch_bounds__(64 * WPU * HPW) __attribute__((amdgpu_waves_per_eu(
             learn_len();
             nst = seg_len > k_first ? (seg_len - k_first + stride - 1) / stride : 0;
         }
-        if (!pre_folded) fold_pre();
+        if (!pre_folded) {  // the pre-requested partials have landed
+            gqa_fold_pre<T, D>(npre, pre_f32, pbuf, plse, o, m_run, l_run);
+            pre_folded = true;
+        }
         // the second set's first step goes out BEHIND the drain: hipcc's own wait for q and the partials (it lands at the settle point
         // above) is a full one and must not find a key step it does not know about in the queue
         if (NSET == 2 && nst > 1) issue(k_first + stride, SETB);
@@ -391,7 +265,7 @@ __global__ __launch_bounds__(64 * WPU * HPW) __attribute__((amdgpu_waves_per_eu(
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
             collect(so);
-            if (key0 + 32 > seg_len) sanitize(key0);
+            if (key0 + 32 > seg_len) gqa_sanitize<D>(key0, g4, seg_len, vf);
             if (j + NSET < nst) issue(key0 + NSET * stride, so);  // in flight while steps j (and j + 1) are computed
             compute(key0);
         }
@@ -399,7 +273,7 @@ __global__ __launch_bounds__(64 * WPU * HPW) __attribute__((amdgpu_waves_per_eu(
     // the keys-only state (the LSE output is the suffix pass's own; when it is asked for, no partial was folded above)
     const float m_s = m_run, l_s = l_run;
 
-    // ---- this wave's other partials (all of them when the LSE output is asked for) ---------------------------------------
+    // ---- this wave's other partials (all of them when the LSE output is asked for) ----
     for (int i = wave + max(npre, 0) * WPU; i < np; i += 2 * WPU) {
         // two partials per round trip: their lse values and 2 * D/16 row pieces are all requested before the first use
         const bool two = i + WPU < np;
@@ -407,58 +281,19 @@ __global__ __launch_bounds__(64 * WPU * HPW) __attribute__((amdgpu_waves_per_eu(
         const float lse0 = a.partials[i].lse[ridx];
         const float lse1 = two ? a.partials[i1].lse[ridx] : -INFINITY;
         f32x4 x0[NDB], x1[NDB];
-        fetch(a.partials[i], x0);
-        fetch(a.partials[i1], x1);
-        fold(lse0, x0);
-        fold(lse1, x1);
+        gqa_fetch<T, D>(a.partials[i], ridx, g4, x0);
+        gqa_fetch<T, D>(a.partials[i1], ridx, g4, x1);
+        gqa_fold<D>(lse0, x0, o, m_run, l_run);
+        gqa_fold<D>(lse1, x1, o, m_run, l_run);
     }
 
-    // ---- merge the WPU waves of the unit: every wave leaves (m, l, O^T) in its own V tile, wave 0 folds them -------
+    // ---- merge the WPU waves of the unit through their V tiles ----
     float ms_run = m_s, ls_run = l_s;
     if constexpr (WPU > 1) {
-        float* mine = reinterpret_cast<float*>(vtile);  // [16 rows][D]: O (unnormalised)
-        // lane (row l15, key group g4) holds O^T[d = 16 db + 4 g4 + i][row l15] in o[db][i]; m / l are equal over g4
-#pragma unroll
-        for (int db = 0; db < NDB; ++db)
-            *reinterpret_cast<f32x4*>(mine + l15 * D + 16 * db + 4 * g4) = o[db];
-        if (g4 == 0) {
-            mlx[wave][0][l15] = m_run;
-            mlx[wave][1][l15] = l_run;
-            mlx[wave][2][l15] = m_s;
-            mlx[wave][3][l15] = l_s;
-        }
-        __syncthreads();
-        if (wave != 0) return;
-#pragma unroll
-        for (int w = 1; w < WPU; ++w) {
-            const float* oth = reinterpret_cast<const float*>(tiles[w][0][1]);
-            const float m2 = mlx[w][0][l15], l2 = mlx[w][1][l15];
-            const float mf = fmaxf(m_run, m2);
-            const float ms = (mf == -INFINITY) ? 0.f : mf;
-            const float a1 = fast_exp2(m_run - ms), a2 = fast_exp2(m2 - ms);
-            l_run = l_run * a1 + l2 * a2;
-            m_run = mf;
-            const float m3 = mlx[w][2][l15], l3 = mlx[w][3][l15];
-            const float mg = fmaxf(ms_run, m3);
-            const float mgs = (mg == -INFINITY) ? 0.f : mg;
-            ls_run = ls_run * fast_exp2(ms_run - mgs) + l3 * fast_exp2(m3 - mgs);
-            ms_run = mg;
-#pragma unroll
-            for (int db = 0; db < NDB; ++db) o[db] = o[db] * a1 + *reinterpret_cast<const f32x4*>(oth + l15 * D + 16 * db + 4 * g4) * a2;
-            asm volatile("" ::: "memory");  // one wave's tile at a time: hoisting all three costs 96 registers
-        }
+        auto tile_of = [&](int w) { return reinterpret_cast<const float*>(tiles[w][0][1]); };
+        if (!gqa_merge_waves<D, WPU>(wave, l15, g4, reinterpret_cast<float*>(vtile), tile_of, mlx, m_s, l_s, o, m_run, l_run, ms_run, ls_run)) return;
     }
-
-    // ---- epilogue: normalise and store (the prefix partials are already in) -----------------------------------------
-    if (!rvalid) return;
-    if (a.lse && g4 == 0) a.lse[ridx] = ls_run > 0.f ? ms_run * kLn2 + __logf(ls_run) : -INFINITY;
-    const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;
-#pragma unroll
-    for (int db = 0; db < NDB; ++db) {
-        const f32x4 x = o[db] * inv;
-        const u32x2 pk = {TR::pack2(x[0], x[1]), TR::pack2(x[2], x[3])};
-        *reinterpret_cast<u32x2*>(static_cast<uint16_t*>(a.out) + ridx * D + 16 * db + 4 * g4) = pk;
-    }
+    gqa_epilogue<T, D>(a, rvalid, ridx, g4, o, l_run, ms_run, ls_run);
 }
 
 template <typename T, int D, int WPU, bool NT, int HPW>
@@ -467,22 +302,8 @@ static int launch_gqa_k(const SuffixArgs& a, dim3 grid, size_t pad, hipStream_t 
     // the K/V landing tiles, plus the (m, l) exchange area that only the cross-wave merge of WPU > 1 touches: one-wave units ask
     // for the tiles alone, which is at most 64 KB for every shape picked from shapes (HPW = 4 at D = 128, HPW = 2 at D = 256)
     constexpr size_t lds = (size_t)NWV * (D == 64 ? 2 : 1) * 2 * 32 * D * 2 + (WPU > 1 ? (size_t)NWV * 4 * 16 * sizeof(float) : 0);
-    auto kern = HYD_GQA_KERNEL<T, D, WPU, NT, HPW>;
-    if (lds + pad > 64 * 1024) {
-        // more than the default dynamic-LDS limit (four-wave units; development pads): raise it, once per DEVICE and instantiation --
-        // the attribute belongs to the function as loaded on the current device, and a process may launch on several
-        static hipError_t attr_rc[16];
-        static bool attr_set[16];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return (int)hipErrorInvalidDevice;
-        if (!__atomic_load_n(&attr_set[dev], __ATOMIC_ACQUIRE)) {  // idempotent: two threads racing both set the same value
-            attr_rc[dev] = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-            __atomic_store_n(&attr_set[dev], true, __ATOMIC_RELEASE);
-        }
-        if (attr_rc[dev] != hipSuccess) return (int)attr_rc[dev];
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(64 * NWV), lds + pad, s, a);
-    return (int)hipGetLastError();
+    // more than the default dynamic-LDS limit (four-wave units; development pads): raised to 150 KiB
+    return gqa_launch_lds<HYD_GQA_KERNEL<T, D, WPU, NT, HPW>>(a, grid, 64 * NWV, lds + pad, lds + pad > 64 * 1024, 150 * 1024, s);
 }
 
 }  // namespace hyd

@@ -18,12 +18,17 @@ LIMITS = {
     "prefix_attn_w64_f16.hip": [(r"prefix_attn_w64_kernel", 512), (r"prefix_attn_w64x8_kernel", 256)],  # the fp16 instantiations
     # 2 waves / SIMD: K and V fragments of a step live in registers (one K and one V landing tile of LDS per wave)
     "suffix_attn_gqa.hip": [(r"suffix_attn_gqa_kernel", 256)],
+    # the same frame around an fp8 stream, and with the causal tail's per-row key limit (the grouped-query kernels of the file only)
+    "suffix_attn_gqa_fp8.hip": [(r"suffix_attn_gqa_fp8_kernel", 256)],
+    "suffix_attn_causal.hip": [(r"suffix_attn_gqa_causal_kernel", 256)],
     # <T, D, R = 1, WPU = 1, NPRE, U, OCC>, one-unit-per-wave MHA decode: 6 waves / SIMD; the token-row kernel: 4 waves / SIMD (8 tokens x 2 tensors, requests rotated)
     "suffix_attn.hip": [(r"suffix_attn_kernel", 512), (r"suffix_attn_kernelINS_\d\w+?ELi(64|128|256)ELi1ELi1ELi\dELi\dELi\d(ELi\d)?EEv", 80),
                         (r"suffix_attn_rows_kernel", 128)],
     "combine.hip": [(r"combine", 128)],
     "rope_append.hip": [(r"rope_append", 128)],
 }
+GQA_SOURCES = ("suffix_attn_gqa.hip", "suffix_attn_gqa_fp8.hip", "suffix_attn_causal.hip")
+ONLY = {"suffix_attn_causal.hip": "suffix_attn_gqa_causal_kernel"}  # file -> the kernels of it that LIMITS speaks of
 
 
 _ASM_CACHE = {}
@@ -56,8 +61,11 @@ def test_hot_kernels_have_no_scratch_and_keep_their_occupancy():
         results = list(ex.map(_metadata, LIMITS))
     for src, kernels in results:
         assert kernels, src
+        if src in ONLY:
+            kernels = [k for k in kernels if ONLY[src] in k["name"]]
+            assert len(kernels) == 20, (src, len(kernels))
         for k in kernels:
-            d256_gqa = src == "suffix_attn_gqa.hip" and "ELi256E" in k["name"]  # one wave per SIMD; hipcc parks 3 values in AGPRs, nothing in memory
+            d256_gqa = src in GQA_SOURCES and "ELi256E" in k["name"]  # one wave per SIMD; hipcc parks a few values in AGPRs, nothing in memory
             assert (k["spill"] == 0 or d256_gqa) and k["scratch"] == 0, f"{src}: {k}"
             for pat, lim in LIMITS[src]:
                 if re.search(pat, k["name"]):
@@ -189,6 +197,30 @@ def test_gqa_suffix_kernel_names_no_register_by_hand():
         assert not counted, (m.group(1), counted[:3])
 
 
+@pytest.mark.skipif(not Path(HIPCC).exists(), reason="hipcc not installed")
+@pytest.mark.parametrize("src, kernel, row_bytes", [("suffix_attn_causal.hip", "suffix_attn_gqa_causal_kernel", 2),
+                                                     ("suffix_attn_gqa_fp8.hip", "suffix_attn_gqa_fp8_kernel", 1)])
+def test_causal_and_fp8_gqa_streams_have_only_their_hand_placed_waits(src, kernel, row_bytes):
+    """The rule of the plain kernel above for the two other streams built on the same frame (suffix_gqa_unit.h): between the first
+    and the last LDS-DMA hipcc adds no counted vector-memory wait of its own.  The one counted wait is the hand-placed one of the
+    instantiations that keep two key steps in flight -- 16-bit rows at D = 64, fp8 rows at D <= 128 -- which leaves the younger
+    step's 2 * NVD requests out (NVD = 32 keys / (1024 bytes / row bytes) DMA instructions per tile)."""
+    seen = 0
+    for m in re.finditer(rf"^(_ZN3hyd\d+{kernel}\w+):(.*?)^\.Lfunc_end", _device_asm(src), flags=re.S | re.M):
+        seen += 1
+        body = m.group(2)
+        first_dma = body.find(" lds")
+        assert first_dma > 0, m.group(1)
+        lines = body[first_dma:].splitlines()
+        last_dma = max(i for i, ln in enumerate(lines) if ln.rstrip().endswith(" lds") or " lds " in ln)
+        counted = [ln.strip() for ln in lines[:last_dma] if re.search(r"s_waitcnt vmcnt\((?!0\))", ln)]
+        d = int(re.search(r"ELi(64|128|256)E", m.group(1)).group(1))
+        if d * row_bytes <= 128:  # two tile sets
+            counted = [ln for ln in counted if ln != f"s_waitcnt vmcnt({2 * (32 * d * row_bytes // 1024)})"]
+        assert not counted, (m.group(1), counted[:3])
+    assert seen == 20
+
+
 def _sregs(tok: str):
     tok = tok.strip().rstrip(",")
     m = re.fullmatch(r"s\[(\d+):(\d+)\]", tok)
@@ -230,7 +262,8 @@ def valu_sgpr_to_vmem_hazards(asm: str, need: int = 5):
 
 
 @pytest.mark.skipif(not Path(HIPCC).exists(), reason="hipcc not installed")
-@pytest.mark.parametrize("src", ["prefix_attn_w64.hip", "prefix_attn_w64_f16.hip", "suffix_attn_gqa.hip", "suffix_attn.hip"])
+@pytest.mark.parametrize("src", ["prefix_attn_w64.hip", "prefix_attn_w64_f16.hip", "suffix_attn_gqa.hip", "suffix_attn.hip",
+                                 "suffix_attn_gqa_fp8.hip", "suffix_attn_causal.hip"])
 def test_asm_memory_instructions_keep_their_distance_from_valu_written_scalars(src):
     """Found the hard way: the persistent prefix kernel restores spilled scalars with v_readlane right in front of the
     LDS-DMA asm statements; without wait states the DMA read a stale offset (timing-dependent garbage in the ragged
