@@ -15,6 +15,7 @@ HYD_MAX_LEVELS = 8
 HYD_F16, HYD_BF16, HYD_F32 = 0, 1, 2
 HYD_FP8_E4M3 = 3  # hyd_kv_quant.kv_dtype: e4m3fn unique caches
 HYD_KVQ_GQA = 1    # hyd_kv_quant.flags: grouped-query shapes run on the fp8 matrix-core kernel
+HYD_KVQ_CAUSAL = 2  # hyd_kv_quant.flags: causal-tail calls (multi-token decode steps) run on the fp8 causal matrix-core kernel
 HYD_LSE_BQH, HYD_LSE_BHQ = 0, 1
 HYD_PHASE_ALL, HYD_PHASE_SHARED, HYD_PHASE_UNIQUE, HYD_PHASE_UNIQUE_PARTIAL, HYD_PHASE_MERGE = 0, 1, 2, 3, 4
 
@@ -369,6 +370,8 @@ EXPORTS = {
     # hyd_qk_norm* travels as a plain pointer: its mirror is fused_decode.QkNorm (pass C.byref of one, or None)
     "hyd_rope_append_decode_qkn": (C.c_int, [C.POINTER(RopeParams), C.POINTER(KvQuant), C.c_void_p, C.c_void_p]),
     "hyd_rope_append_multi_qkn": (C.c_int, [C.POINTER(RopeMultiParams), C.c_void_p, C.c_void_p]),
+    "hyd_rope_append_multi_kvq": (C.c_int, [C.POINTER(RopeMultiParams), C.POINTER(KvQuant), C.c_void_p, C.c_void_p]),
+    "hyd_suffix_attn_causal_fwd_kvq": (C.c_int, [C.POINTER(SuffixParams), C.POINTER(KvQuant), C.c_void_p]),
     "hyd_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }

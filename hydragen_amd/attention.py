@@ -105,7 +105,9 @@ def hydragen_attention(
     float8_e4m3fn with per-kv-head fp32 scales k_scale / v_scale ([Hkv], None = 1; kv_quant.py).
     causal_tail=True (needs seq_lens): a multi-token decode step -- the qlen = T queries (2..8) are the last T tokens of their
     sequences, their keys already in k / v, and query i sees the unique keys below seq_lens[b] - (T - 1 - i) and every shared
-    key (hyd_decode_params.causal_tail).  16-bit caches of head dim 64 / 128 / 256; anything else raises NotImplementedError.
+    key (hyd_decode_params.causal_tail).  Head dim 64 / 128 / 256; 16-bit caches, or fp8 caches with both scale tensors given
+    (HYD_KVQ_CAUSAL: the fp8 matrix-core kernel with the per-row key limit).  Anything else, and an fp8 shape the library refuses,
+    raises NotImplementedError -- a causal call is never dequantized into a non-causal one.
 
     Args:
         q: attention queries, shape [batch, qlen, qheads, head_dim]
@@ -135,12 +137,20 @@ def hydragen_attention(
     fp8 = _flash.check_kv_pair(k, v, k_scale, v_scale)
     fused_ok = seq_lens is not None or nq == 1 or k.shape[1] == 0
     if causal_tail:
-        if seq_lens is None or fp8 or d not in (64, 128, 256) or k.shape[-1] != d or n_levels > HYD_MAX_LEVELS or not 2 <= nq <= 8:
-            raise NotImplementedError("causal_tail: seq_lens, 2..8 queries per sequence, 16-bit unique caches of head dim 64 / 128 / 256 "
-                                      f"and at most {HYD_MAX_LEVELS} levels (got q {tuple(q.shape)}, k {tuple(k.shape)} {k.dtype})")
-        return _decode_fused(_q_contig(q), _lastdim_contig(k), _lastdim_contig(v), [_lastdim_contig(x) for x in shared_ks],
-                             [_lastdim_contig(x) for x in shared_vs], shared_cu_seq_lens, shared_max_seq_lens, use_varlens, seq_lens,
-                             causal_tail=True)
+        if seq_lens is None or (fp8 and (k_scale is None or v_scale is None)) or d not in (64, 128, 256) or k.shape[-1] != d \
+                or n_levels > HYD_MAX_LEVELS or not 2 <= nq <= 8:
+            raise NotImplementedError("causal_tail: seq_lens, 2..8 queries per sequence, unique caches of head dim 64 / 128 / 256 (16-bit, or "
+                                      f"fp8 with k_scale and v_scale given) and at most {HYD_MAX_LEVELS} levels (got q {tuple(q.shape)}, "
+                                      f"k {tuple(k.shape)} {k.dtype})")
+        if not fp8:
+            k, v = _lastdim_contig(k), _lastdim_contig(v)
+        out = _decode_fused(_q_contig(q), k, v, [_lastdim_contig(x) for x in shared_ks],
+                            [_lastdim_contig(x) for x in shared_vs], shared_cu_seq_lens, shared_max_seq_lens, use_varlens, seq_lens,
+                            (k_scale, v_scale) if fp8 else None, causal_tail=True)
+        if out is None:  # fp8 caches, and the library refuses the call (hyd_decode_kv_quant_supported): never dequantized into a non-causal one
+            raise NotImplementedError(f"causal_tail with fp8 unique caches: no fp8 kernel with the per-row key limit takes q {tuple(q.shape)}, "
+                                      f"k {tuple(k.shape)}")
+        return out
 
     def dequantized():  # 16-bit temporaries and the existing path (functional, not fast)
         return hydragen_attention(q, _flash.dequantize_kv(k, k_scale, q.dtype), _flash.dequantize_kv(v, v_scale, q.dtype),
@@ -403,7 +413,7 @@ def _decode_fused(q, k, v, shared_ks, shared_vs, shared_cu_seq_lens, shared_max_
             _launch_decode(lib, p, two_stream, stream, *hit[3:])
             return out
     p = DecodeParams()
-    kq = None if scales is None else _flash.kv_quant_params(*scales)
+    kq = None if scales is None else _flash.kv_quant_params(*scales, causal_tail=bool(causal_tail))
     keep = [fill_suffix_params(p.suffix, q, k, v, seq_lens, out), order]
     if scales is not None:
         keep.extend(scales)

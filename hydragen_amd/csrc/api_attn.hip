@@ -294,18 +294,27 @@ int fail_kvq_shapes(int D) {
                 "multiple of %d at D = %d; D 64 / 128 / 256)", D >= 8 ? 64 / (D / 8) : 0, D);
 }
 
-// The causal tail (hyd_suffix_attn_causal_fwd, hyd_decode_params.causal_tail): 2..8 query tokens, 16-bit caches with rows of D elements.
+// HYD_KVQ_CAUSAL: the caller takes the fp8 causal-tail kernel; without it a causal call with fp8 caches keeps the refusal it has always had
+bool kvq_takes_causal(const hyd_kv_quant* kq) { return kq && (kq->flags & HYD_KVQ_CAUSAL) != 0; }
+
+// The causal tail (hyd_suffix_attn_causal_fwd[_kvq], hyd_decode_params.causal_tail): 2..8 query tokens, caches with rows of D elements.
 int check_causal_tail(const hyd_suffix_params* p, const hyd_kv_quant* kq) {
     if (p->nq < 2 || p->nq > 8) return fail(HYD_ERR_BAD_ARG, "causal tail: nq = %d query tokens per sequence, 2 to 8 are taken", p->nq);
-    if (kq) return fail(HYD_ERR_UNSUPPORTED, "causal tail with fp8 unique caches: implemented for 16-bit caches only");
+    if (kq && !kvq_takes_causal(kq)) return fail(HYD_ERR_UNSUPPORTED, "causal tail with fp8 unique caches: implemented for 16-bit caches only");
     if (p->kv_len > 0 && narrow_kv_dim(p)) return fail(HYD_ERR_UNSUPPORTED, "causal tail with kv_dim %d: narrow unique rows run on the token-row kernel, which has no causal form", p->kv_dim);
     return HYD_OK;
 }
 
 int fail_causal_shapes() { return fail(HYD_ERR_UNSUPPORTED, "causal tail: no kernel with the per-row key limit takes these shapes"); }
 
+// shapes only: a kernel with the per-row key limit takes the call -- with fp8 caches the matrix-core one, which also takes the 2-row units
+// that 16-bit caches give the one-unit-per-wave kernel (suffix_attn_gqa_fp8_causal.hip: there is no fp8 kernel of that kind)
+bool causal_eligible(const SuffixArgs& a, int D, const hyd_kv_quant* kq) {
+    return kq ? suffix_gqa_fp8_causal_eligible(a, D) : suffix_causal_eligible(a, D);
+}
+
 // kq: null, or fp8 unique caches (validated by check_kvq; K/V strides in bytes).  causal: the causal tail (check_causal_tail passed) --
-// such a call goes to launch_suffix_causal or fails, never to a kernel without the per-row key limit.
+// such a call goes to launch_suffix_causal / launch_suffix_gqa_fp8_causal or fails, never to a kernel without the per-row key limit.
 int run_suffix(const hyd_suffix_params* p, const hyd_partial* parts, int n_parts, hipStream_t s, const hyd_kv_quant* kq = nullptr, bool causal = false) {
     SuffixArgs a;
     fill_suffix_args(p, &a);
@@ -321,9 +330,14 @@ int run_suffix(const hyd_suffix_params* p, const hyd_partial* parts, int n_parts
     if ((int64_t)p->kv_len * p->k_tok_stride * esz >= (1ll << 31) || (int64_t)p->kv_len * p->v_tok_stride * esz >= (1ll << 31))
         return fail(HYD_ERR_UNSUPPORTED, "unique K/V of one sequence spans >= 2 GiB (32-bit in-sequence offsets)");
     if (p->Hkv > 4 * 65535 || a.rows > 8 * 65535) return fail(HYD_ERR_UNSUPPORTED, "too many kv heads / query rows for the suffix grid");
+    SuffixKvqArgs ka;  // (fp8 caches only)
+    ka.k_scale = kq ? kq->k_scale : nullptr;
+    ka.v_scale = kq ? kq->v_scale : nullptr;
     if (causal) {
-        if (kq || !suffix_causal_eligible(a, p->D)) return fail_causal_shapes();
-        return launched(launch_suffix_causal(a, p->dtype, p->D, s), "causal-tail suffix kernel launch");
+        if ((kq && !kvq_takes_causal(kq)) || !causal_eligible(a, p->D, kq)) return fail_causal_shapes();
+        if (!kq) return launched(launch_suffix_causal(a, p->dtype, p->D, s), "causal-tail suffix kernel launch");
+        ka.a = a;
+        return launched(launch_suffix_gqa_fp8_causal(ka, p->dtype, p->D, s), "fp8 causal-tail suffix kernel launch");
     }
     if (a.kv_dim) {
         if (kq) return fail_narrow_fp8();
@@ -333,9 +347,6 @@ int run_suffix(const hyd_suffix_params* p, const hyd_partial* parts, int n_parts
         // the 16-bit launcher's order: grouped-query shapes to the matrix-core kernel, one-row units to the token-row kernel
         const bool gqa = kvq_takes_gqa(kq) && suffix_gqa_fp8_eligible(a, p->D);
         if (!gqa && !suffix_fp8_eligible(a, p->D)) return fail_kvq_shapes(p->D);
-        SuffixKvqArgs ka;
-        ka.k_scale = kq->k_scale;
-        ka.v_scale = kq->v_scale;
         ka.a = a;
         return launched(gqa ? launch_suffix_gqa_fp8(ka, p->dtype, p->D, s) : launch_suffix_fp8(ka, p->dtype, p->D, s), "fp8 suffix kernel launch");
     }
@@ -527,14 +538,17 @@ int hyd_suffix_attn_fwd_kvq(const hyd_suffix_params* p, const hyd_kv_quant* kq, 
 
 int hyd_suffix_attn_fwd(const hyd_suffix_params* p, void* stream) { return hyd_suffix_attn_fwd_kvq(p, nullptr, stream); }
 
-int hyd_suffix_attn_causal_fwd(const hyd_suffix_params* p, void* stream) {
+int hyd_suffix_attn_causal_fwd_kvq(const hyd_suffix_params* p, const hyd_kv_quant* kq, void* stream) {
     int rc = check_suffix(p);
     if (rc) return rc;
-    if ((rc = check_causal_tail(p, nullptr))) return rc;
+    if ((rc = check_kvq(&kq, p->dtype))) return rc;
+    if ((rc = check_causal_tail(p, kq))) return rc;
     if (p->n_partials < 0 || p->n_partials > HYD_MAX_LEVELS) return fail(HYD_ERR_BAD_ARG, "n_partials %d", p->n_partials);
     if (p->kv_len == 0 && p->n_partials == 0) return fail(HYD_ERR_BAD_ARG, "kv_len == 0 and no partials");
-    return run_suffix(p, p->partials, p->n_partials, static_cast<hipStream_t>(stream), nullptr, /*causal=*/true);
+    return run_suffix(p, p->partials, p->n_partials, static_cast<hipStream_t>(stream), p->kv_len > 0 ? kq : nullptr, /*causal=*/true);
 }
+
+int hyd_suffix_attn_causal_fwd(const hyd_suffix_params* p, void* stream) { return hyd_suffix_attn_causal_fwd_kvq(p, nullptr, stream); }
 
 int hyd_kv_quant_supported(const hyd_suffix_params* p, const hyd_kv_quant* kq) {
     if (!p) return 0;
@@ -626,7 +640,10 @@ int hyd_decode_attn_fused_kvq(const hyd_decode_params* p, const hyd_kv_quant* kq
     // fp8 unique caches: validated up front (every phase, also those that do not read the unique cache) so that the phases of one
     // call agree; kv_len == 0 reads no unique key and takes the existing path
     if (p->suffix.kv_len > 0 && narrow_kv_dim(&p->suffix)) return fail_narrow_fp8();
-    if (p->suffix.kv_len > 0 && !kvq_native(&p->suffix, kq)) return fail_kvq_shapes(p->suffix.D);
+    // a causal call of a caller that takes the fp8 causal kernel (HYD_KVQ_CAUSAL) is judged by that kernel's shapes, in decode_impl, behind
+    // the checks of causal_tail itself; every other call keeps the order of answers it has always had
+    const bool causal_kq = p->causal_tail != 0 && kvq_takes_causal(kq);
+    if (p->suffix.kv_len > 0 && !causal_kq && !kvq_native(&p->suffix, kq)) return fail_kvq_shapes(p->suffix.D);
     if (decode_kvq_is_one_launch(p, kq))
         return fail(HYD_ERR_UNSUPPORTED, "fp8 unique caches: a grouped-query call this small runs as ONE launch with 16-bit caches "
                                          "(single_launch_small), which has no fp8 form: clear the flag, or pass 16-bit caches");
@@ -639,6 +656,13 @@ int hyd_decode_kv_quant_supported(const hyd_decode_params* p, const hyd_kv_quant
     if (kind != kKvqFp8) return kind == kKvqNone ? 1 : 0;
     if (!levels_in_range(p)) return 0;
     if (p->suffix.kv_len <= 0) return p->suffix.kv_len == 0 ? 1 : 0;  // no unique key is read: the existing path
+    if (p->causal_tail != 0) {  // the causal tail: the launch's own rules (check_causal_tail, then the fp8 causal kernel's shapes)
+        const hyd_suffix_params& sp = p->suffix;
+        if (p->causal_tail != 1 || !kvq_takes_causal(kq) || check_common(sp.dtype, sp.B, sp.nq, sp.Hq, sp.Hkv, sp.D) || narrow_kv_dim(&sp)) return 0;
+        SuffixArgs a;
+        fill_suffix_args(&sp, &a);
+        return suffix_gqa_fp8_causal_eligible(a, sp.D) ? 1 : 0;  // (2..8 query tokens included)
+    }
     return kvq_native(&p->suffix, kq) && !decode_kvq_is_one_launch(p, kq) ? 1 : 0;
 }
 
@@ -664,7 +688,7 @@ static int decode_impl(const hyd_decode_params* p, const hyd_kv_quant* kq, void*
     if (causal && sp.kv_len > 0) {  // ... and so is a shape no kernel with the per-row key limit takes: before the level passes go out
         SuffixArgs ca;
         fill_suffix_args(&sp, &ca);
-        if (!suffix_causal_eligible(ca, sp.D)) return fail_causal_shapes();
+        if (!causal_eligible(ca, sp.D, kq)) return fail_causal_shapes();
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t rows = (size_t)sp.B * sp.nq * sp.Hq;

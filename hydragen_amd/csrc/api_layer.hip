@@ -96,11 +96,12 @@ int hyd_rope_append_decode_kvq(const hyd_rope_params* p, const hyd_kv_quant* kq,
 
 int hyd_rope_append_decode(const hyd_rope_params* p, void* stream) { return hyd_rope_append_decode_qkn(p, nullptr, nullptr, stream); }
 
-int hyd_rope_append_multi_qkn(const hyd_rope_multi_params* p, const hyd_qk_norm* qn, void* stream) {
+int hyd_rope_append_multi_kvq(const hyd_rope_multi_params* p, const hyd_kv_quant* kq, const hyd_qk_norm* qn, void* stream) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
     if (p->T < 2 || p->T > 8) return fail(HYD_ERR_BAD_ARG, "T = %d tokens per row, 2 to 8 are taken (hyd_rope_append_decode takes one)", p->T);
     int rc = check_common(p->dtype, p->B, p->T, p->Hq, p->Hkv, p->D);
     if (rc) return rc;
+    if ((rc = check_kvq(&kq, p->dtype))) return rc;  // (where the one-token form checks it: behind the shapes, in front of the pointers)
     if ((rc = check_rope(p, {{p->position_ids, 8, "position_ids"}, {p->shared_len, 8, "shared_len"}, {p->seq_lens, 4, "seq_lens"}},
                          {{p->q_batch_stride, "q_batch_stride"}, {p->k_batch_stride, "k_batch_stride"}, {p->v_batch_stride, "v_batch_stride"},
                           {p->q_tok_stride, "q_tok_stride"}, {p->k_tok_stride, "k_tok_stride"}, {p->v_tok_stride, "v_tok_stride"}})))
@@ -109,11 +110,19 @@ int hyd_rope_append_multi_qkn(const hyd_rope_multi_params* p, const hyd_qk_norm*
     RopeArgs a = rope_args(p, qn);
     a.T = p->T;
     a.q_ts = p->q_tok_stride; a.k_ts = p->k_tok_stride; a.v_ts = p->v_tok_stride;
+    if (kq) {
+        a.fp8 = 1;
+        a.k_scale = kq->k_scale;
+        a.v_scale = kq->v_scale;
+    }
     return launched(launch_rope_append(a, p->dtype, static_cast<hipStream_t>(stream)),
-                    qn ? "rope_append (multi-token, q/k norm) kernel launch" : "rope_append (multi-token) kernel launch");
+                    qn ? "rope_append (multi-token, q/k norm) kernel launch"
+                    : kq ? "rope_append (multi-token, fp8 caches) kernel launch" : "rope_append (multi-token) kernel launch");
 }
 
-int hyd_rope_append_multi(const hyd_rope_multi_params* p, void* stream) { return hyd_rope_append_multi_qkn(p, nullptr, stream); }
+int hyd_rope_append_multi_qkn(const hyd_rope_multi_params* p, const hyd_qk_norm* qn, void* stream) { return hyd_rope_append_multi_kvq(p, nullptr, qn, stream); }
+
+int hyd_rope_append_multi(const hyd_rope_multi_params* p, void* stream) { return hyd_rope_append_multi_kvq(p, nullptr, nullptr, stream); }
 
 int hyd_add_rmsnorm(const hyd_add_rmsnorm_params* p, void* stream) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");

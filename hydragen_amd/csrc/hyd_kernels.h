@@ -359,6 +359,8 @@ bool suffix_fp8_eligible(const SuffixArgs& a, int D);                           
 int launch_suffix_fp8(const SuffixKvqArgs& a, int dtype, int D, hipStream_t s);       // q dtype; K/V e4m3fn
 bool suffix_gqa_fp8_eligible(const SuffixArgs& a, int D);                             // suffix_attn_gqa_fp8.hip, shapes only
 int launch_suffix_gqa_fp8(const SuffixKvqArgs& a, int dtype, int D, hipStream_t s);   // q dtype; K/V e4m3fn, grouped-query shapes
+bool suffix_gqa_fp8_causal_eligible(const SuffixArgs& a, int D);                      // suffix_attn_gqa_fp8_causal.hip, shapes only
+int launch_suffix_gqa_fp8_causal(const SuffixKvqArgs& a, int dtype, int D, hipStream_t s);  // the causal tail over fp8 caches (nq = 2..8)
 int launch_suffix_gqa(const SuffixArgs& a, int dtype, int D, hipStream_t s);
 bool suffix_causal_eligible(const SuffixArgs& a, int D);                              // suffix_attn_causal.hip, shapes only
 int launch_suffix_causal(const SuffixArgs& a, int dtype, int D, hipStream_t s);       // the causal-tail suffix pass (nq = 2..8)

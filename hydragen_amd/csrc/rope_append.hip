@@ -6,8 +6,8 @@
 //   * emits seq_lens[b] = index + 1 as int32 for the suffix kernel (llama.py:569, flash.py:220),
 // replacing ~10 small torch kernels per layer per token.  HBM-bound and tiny: B*(Hq+2*Hkv)*D elements.
 //
-// ONE row body, rope_append_row<T, D, MULTI, NORM, FP8>, for rows of D = 64 / 128 / 256 elements; six of the seven __global__ names
-// below are its instantiations.  The seventh, "narrow" (hyd_rope_params.head_dim = d < D, d % 16 == 0; 16-bit caches), keeps its own
+// ONE row body, rope_append_row<T, D, MULTI, NORM, FP8>, for rows of D = 64 / 128 / 256 elements; eight of the nine __global__ names
+// below are its instantiations (every combination of the three switches).  The ninth, "narrow" (hyd_rope_params.head_dim = d < D, d % 16 == 0; 16-bit caches), keeps its own
 // preamble behind them and shares rotated_row: q / k / v arrive from the GEMM as rows of d elements with head stride d, the rotate-half pairs are
 // (i, i + d / 2) -- 8-element vectors, hence d % 16 == 0 --, K (rotated) and V go into the caches as rows of d elements at the caches'
 // strides, and q_out keeps the attention kernels' pitch of D with exact zeros in its pad columns.  The body's switches:
@@ -58,8 +58,8 @@ __device__ __forceinline__ float row_sum(float v) {
 }
 
 // The thread's 8 + 8 elements of a rotated q or k row: loaded at src + d0 and src + half + d0, widened, normalised with the gains w
-// when NORM (rows of DC elements; DC is not read otherwise), rotated by the table rows cr / sr, rounded once.  All seven kernels
-// rotate here.
+// when NORM (rows of DC elements; DC is not read otherwise), rotated by the table rows cr / sr, rounded once.  Every kernel of the file
+// rotates here.
 template <typename T, int DC, bool NORM>
 __device__ __forceinline__ void rotated_row(const uint16_t* src, const uint16_t* w, float eps, const float* cr, const float* sr, int d0, int half,
                                             u32x4& olo, u32x4& ohi) {
@@ -184,13 +184,16 @@ __device__ __forceinline__ void rope_append_row(const RopeArgs& a) {
     }
 }
 
-// the six kernels of the row body: rope_append_row<T, D, MULTI, NORM, FP8>
+// the kernels of the row body: rope_append_row<T, D, MULTI, NORM, FP8>
 template <typename T, int D> __global__ __launch_bounds__(256) void rope_append_kernel(const RopeArgs a) { rope_append_row<T, D, false, false, false>(a); }
 template <typename T, int D> __global__ __launch_bounds__(256) void rope_append_fp8_kernel(const RopeArgs a) { rope_append_row<T, D, false, false, true>(a); }
 template <typename T, int D> __global__ __launch_bounds__(256) void rope_append_multi_kernel(const RopeArgs a) { rope_append_row<T, D, true, false, false>(a); }
 template <typename T, int D> __global__ __launch_bounds__(256) void rope_append_norm_kernel(const RopeArgs a) { rope_append_row<T, D, false, true, false>(a); }
 template <typename T, int D> __global__ __launch_bounds__(256) void rope_append_norm_fp8_kernel(const RopeArgs a) { rope_append_row<T, D, false, true, true>(a); }
 template <typename T, int D> __global__ __launch_bounds__(256) void rope_append_norm_multi_kernel(const RopeArgs a) { rope_append_row<T, D, true, true, false>(a); }
+// ... and fp8 caches under several tokens (hyd_rope_append_multi_kvq): token i is quantized with its kv head's scale and written at idx0 + i
+template <typename T, int D> __global__ __launch_bounds__(256) void rope_append_multi_fp8_kernel(const RopeArgs a) { rope_append_row<T, D, true, false, true>(a); }
+template <typename T, int D> __global__ __launch_bounds__(256) void rope_append_norm_multi_fp8_kernel(const RopeArgs a) { rope_append_row<T, D, true, true, true>(a); }
 
 // Narrow head dims keep a preamble of their own.  As an instantiation of rope_append_row with a runtime row width the kernel measured
 // +0.17 us on 7.4 us per layer against a parent spread of 0.07 us (profiles/rope_append_body.md, "First attempt"), so the thread
@@ -250,11 +253,12 @@ __global__ __launch_bounds__(256) void rope_append_narrow_kernel(const RopeArgs 
 
 using RopeKernel = void (*)(const RopeArgs);
 
-// the kernel of a.D-element rows for the call's features, null for a combination that has none (fp8 caches under several tokens)
+// the kernel of a.D-element rows for the call's features
 template <typename T, int D>
 static RopeKernel rope_kernel_of(const RopeArgs& a) {
     const bool norm = a.q_weight != nullptr, multi = a.T > 1;
-    if (a.fp8) return multi ? nullptr : norm ? rope_append_norm_fp8_kernel<T, D> : rope_append_fp8_kernel<T, D>;
+    if (a.fp8 && multi) return norm ? rope_append_norm_multi_fp8_kernel<T, D> : rope_append_multi_fp8_kernel<T, D>;
+    if (a.fp8) return norm ? rope_append_norm_fp8_kernel<T, D> : rope_append_fp8_kernel<T, D>;
     if (multi) return norm ? rope_append_norm_multi_kernel<T, D> : rope_append_multi_kernel<T, D>;
     return norm ? rope_append_norm_kernel<T, D> : rope_append_kernel<T, D>;
 }

@@ -20,7 +20,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import HYD_BF16, HYD_F16, HYD_FP8_E4M3, HYD_KVQ_GQA, HYD_LSE_BHQ, HYD_LSE_BQH, KvQuant, PrefixParams, SuffixParams
+from ._lib import HYD_BF16, HYD_F16, HYD_FP8_E4M3, HYD_KVQ_CAUSAL, HYD_KVQ_GQA, HYD_LSE_BHQ, HYD_LSE_BQH, KvQuant, PrefixParams, SuffixParams
 from .kv_quant import FP8_DTYPE, dequantize_kv, quantize_kv  # noqa: F401  (quantize_kv: part of this module's face)
 
 
@@ -299,6 +299,9 @@ def fill_suffix_params(p: SuffixParams, q: Tensor, k: Tensor, v: Tensor, seq_len
 # (the cache is read, widened and written on every call), in the spirit of pad_head_dim.  The whole operator
 # (attention.hydragen_attention) asks hyd_decode_kv_quant_supported as well: grouped-query calls so small that 16-bit caches
 # would run them as one launch stay on the fallback, whose results they keep.
+# causal_tail=True (multi-token decode steps) is the exception to the fallback: the fp8 causal matrix-core kernel (HYD_KVQ_CAUSAL, set
+# by kv_quant_params(causal_tail=True); units of 2 rows included) takes the call or it raises NotImplementedError -- a dequantized
+# temporary would have to go through a causal kernel too, and the caller (llama._decode_multi) has the assembled definition for that.
 def check_kv_pair(k: Tensor, v: Tensor, k_scale: Tensor | None, v_scale: Tensor | None) -> bool:
     """True for fp8 caches (and validates their scales); scales given for 16-bit caches are an error."""
     fp8 = k.dtype == FP8_DTYPE
@@ -316,10 +319,12 @@ def check_kv_pair(k: Tensor, v: Tensor, k_scale: Tensor | None, v_scale: Tensor 
     return True
 
 
-def kv_quant_params(k_scale: Tensor | None, v_scale: Tensor | None) -> KvQuant:
+def kv_quant_params(k_scale: Tensor | None, v_scale: Tensor | None, causal_tail: bool = False) -> KvQuant:
     kq = KvQuant()
     kq.kv_dtype = HYD_FP8_E4M3
     kq.flags = HYD_KVQ_GQA  # grouped-query shapes run on the fp8 matrix-core kernel (without the flag the library refuses them)
+    if causal_tail:  # ... and so do causal-tail calls, on its form with the per-row key limit
+        kq.flags |= HYD_KVQ_CAUSAL
     kq.k_scale = k_scale.data_ptr() if k_scale is not None else None
     kq.v_scale = v_scale.data_ptr() if v_scale is not None else None
     return kq
@@ -391,15 +396,31 @@ def flash_attention_seqlen(raw_q: Tensor, raw_k: Tensor, raw_v: Tensor, seq_len=
     k / v may be float8_e4m3fn caches (kv_quant.py) with per-kv-head fp32 scales k_scale / v_scale ([Hkv], None = 1).
     causal_tail=True (a multi-token decode step, hyd_suffix_attn_causal_fwd): the T = qseq_len queries (2..8) are the LAST T
     tokens of their sequences and their keys are in k / v already, so query i sees the keys below seq_len[b] - (T - 1 - i).
-    16-bit caches of head dim 64 / 128 / 256 only; everything else raises NotImplementedError (never a non-causal result).
+    Head dim 64 / 128 / 256; 16-bit caches, or fp8 caches with BOTH scale tensors given (hyd_suffix_attn_causal_fwd_kvq: the fp8
+    matrix-core kernel with the per-row key limit, bit-identical to the 16-bit causal call on the dequantized caches where both take
+    the shape).  Everything else, and every shape the library refuses, raises NotImplementedError: a causal call is never dequantized
+    into, or run as, a non-causal one.
     """
     _require_gpu(raw_q, raw_k, raw_v, seq_len)
     assert raw_q.ndim == 4 and raw_k.ndim == 4 and raw_v.ndim == 4
     assert raw_k.shape == raw_v.shape
     fp8 = check_kv_pair(raw_k, raw_v, k_scale, v_scale)
-    if causal_tail and (fp8 or raw_k.shape[-1] not in (64, 128, 256) or raw_q.shape[-1] != raw_k.shape[-1]):
-        raise NotImplementedError(f"causal_tail: 16-bit caches of head dim 64 / 128 / 256 only (got {raw_k.dtype}, head dims "
-                                  f"{raw_q.shape[-1]} / {raw_k.shape[-1]})")
+    if causal_tail and ((fp8 and (k_scale is None or v_scale is None)) or raw_k.shape[-1] not in (64, 128, 256)
+                        or raw_q.shape[-1] != raw_k.shape[-1]):
+        raise NotImplementedError(f"causal_tail: caches of head dim 64 / 128 / 256, 16-bit or fp8 with k_scale and v_scale given (got "
+                                  f"{raw_k.dtype}, head dims {raw_q.shape[-1]} / {raw_k.shape[-1]})")
+    if causal_tail and fp8:
+        q = _q_contig(raw_q)
+        out = torch.empty_like(q)
+        lse = torch.empty(q.shape[:3], dtype=torch.float32, device=q.device)
+        p = SuffixParams()
+        keep = fill_suffix_params(p, q, raw_k, raw_v, seq_len, out)  # (strides in bytes; what the library cannot address it refuses)
+        p.lse = lse.data_ptr()
+        p.n_partials = 0
+        kq = kv_quant_params(k_scale, v_scale, causal_tail=True)
+        _lib.check(_lib.load().hyd_suffix_attn_causal_fwd_kvq(C.byref(p), C.byref(kq), _stream()))  # (-2: NotImplementedError)
+        del keep
+        return out, lse
     narrow = not fp8 and narrow_kv_native(raw_q, raw_k, raw_v)
     # (narrow unique caches: q may arrive padded to the kernels' head dim already, with zero pad columns)
     assert raw_q.shape[-1] == raw_k.shape[-1] or narrow, (

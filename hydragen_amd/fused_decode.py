@@ -37,16 +37,18 @@ def qk_norm_params(q, D: int, q_norm: Tensor | None, k_norm: Tensor | None, norm
 
 def rope_append_multi(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, position_ids: Tensor,
                       shared_len: Tensor | None, k_cache: Tensor, v_cache: Tensor, q_norm: Tensor | None = None,
-                      k_norm: Tensor | None = None, norm_eps: float | None = None):
+                      k_norm: Tensor | None = None, norm_eps: float | None = None, *, k_scale: Tensor | None = None,
+                      v_scale: Tensor | None = None):
     """hyd_rope_append_multi: the preamble of a MULTI-TOKEN decode step (speculative.py).  q [B,T,Hq,D], k/v [B,T,Hkv,D] with
     2 <= T <= 8, position_ids int64 [B] or [B, T] (column 0 is read: the first token's absolute position, token i uses + i),
-    shared_len int64 [B] or None, 16-bit caches [maxB, maxS, Hkv, D] with D 64 / 128 / 256.  Returns (rotated q [B,T,Hq,D],
+    shared_len int64 [B] or None, caches [maxB, maxS, Hkv, D] with D 64 / 128 / 256.  Returns (rotated q [B,T,Hq,D],
     seq_lens int32 [B] = cache index of the first token + T); K (rotated) and V of token i are written at that index + i.  A
     row at position shared_len - 1 writes nothing and reports length 0.  q_norm / k_norm [D] of q's dtype with norm_eps: the
-    per-head RMSNorm of q and k in front of the rotation (hyd_rope_append_multi_qkn), as in rope_append_decode."""
+    per-head RMSNorm of q and k in front of the rotation (hyd_rope_append_multi_qkn), as in rope_append_decode.
+    float8_e4m3fn caches (hyd_rope_append_multi_kvq) receive quantize_kv(k_rot, k_scale) / quantize_kv(v, v_scale) as in
+    rope_append_decode: the bytes T one-token calls at positions + i would leave."""
     _require_gpu(q, k, v, cos, sin, position_ids, k_cache, v_cache)
-    if check_kv_pair(k_cache, v_cache, None, None):
-        raise NotImplementedError("multi-token decode steps with fp8 unique caches: 16-bit caches only")
+    fp8 = check_kv_pair(k_cache, v_cache, k_scale, v_scale)
     B, T, Hq, D = q.shape
     if D not in (64, 128, 256) or k_cache.shape[-1] != D:
         raise NotImplementedError(f"head_dim {D} (caches {k_cache.shape[-1]}): the multi-token preamble takes 64 / 128 / 256")
@@ -76,7 +78,10 @@ def rope_append_multi(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor,
     p.dtype, p.B, p.T, p.Hq, p.Hkv, p.D, p.cache_len = _dtype_code(q), B, T, Hq, Hkv, D, k_cache.shape[1]
     p.max_pos = cos.shape[0]
     qn = qk_norm_params(q, D, q_norm, k_norm, norm_eps)
-    if qn is not None:
+    if fp8:
+        kq = kv_quant_params(k_scale, v_scale)
+        _lib.check(_lib.load().hyd_rope_append_multi_kvq(C.byref(p), C.byref(kq), None if qn is None else C.byref(qn), _stream()))
+    elif qn is not None:
         _lib.check(_lib.load().hyd_rope_append_multi_qkn(C.byref(p), C.byref(qn), _stream()))
     else:
         _lib.check(_lib.load().hyd_rope_append_multi(C.byref(p), _stream()))

@@ -250,9 +250,12 @@ def _check_draft(model, draft_tokens, draft, ngram, max_new_tokens, refused: dic
                          f"{speculative.MAX_SEGMENTS} segments (hyd_draft_lookup)")
     ngram = speculative.check_ngram(ngram)
     attn = model.model.layers[0].self_attn
-    if attn.kv_cache.fp8 or attn.kv_cache.narrow or attn.head_dim not in (64, 128, 256):
-        raise NotImplementedError("draft_tokens with fp8 unique caches or a head dim other than 64 / 128 / 256: the multi-token "
-                                  "preamble and the causal-tail suffix pass take 16-bit caches of those head dims only")
+    if attn.kv_cache.narrow or attn.head_dim not in (64, 128, 256):
+        raise NotImplementedError("draft_tokens with a head dim other than 64 / 128 / 256: the multi-token preamble and the causal-tail "
+                                  "suffix pass take caches of those head dims only")
+    if attn.kv_cache.fp8 and not model.lm_head.weight.is_cuda:
+        raise NotImplementedError("draft_tokens with fp8 unique caches is not implemented for a model on the CPU: the multi-token "
+                                  "preamble quantizes and the causal-tail suffix pass widens the cache rows in HIP kernels")
     if constrained and not model.lm_head.weight.is_cuda:
         raise NotImplementedError("draft_tokens with constraint= is not implemented for a model on the CPU: the drafts are walked "
                                   "through the automaton and accepted with their states by HIP kernels (speculative."

@@ -562,14 +562,17 @@ class HydragenLlamaAttention(nn.Module):
         """Attention of a MULTI-TOKEN decode step (speculative.py): q / k / v [B, T, H, D] are T consecutive tokens per row,
         position_ids [B, T] their absolute positions (column 0 + i).  With the fused preamble: hyd_rope_append_multi, then the
         causal-tail operator; otherwise, and for a call the library refuses, the definition assembled from existing operators
-        (speculative.assembled_causal_tail_attention).  Every token sees all shared keys and the unique keys up to itself."""
+        (speculative.assembled_causal_tail_attention).  Every token sees all shared keys and the unique keys up to itself.
+        fp8 unique caches: the preamble quantizes the T new rows (hyd_rope_append_multi_kvq) and the fp8 causal-tail kernel reads
+        the cache as it is; the assembled route -- a shape the library refuses, or use_fused_decode = False -- runs on
+        dequantize_kv of the whole cache rows with the scales they were written with: functional, not fast."""
         bsz, q_len = q.shape[:2]
         kvc = self.kv_cache
         if not 2 <= q_len <= speculative.MAX_DRAFTS + 1:
             raise NotImplementedError(f"a decode step feeds 1 to {speculative.MAX_DRAFTS + 1} tokens per row, got {q_len}")
-        if kvc.fp8 or kvc.narrow or self.head_dim not in (64, 128, 256) or self.disable_attention:
-            raise NotImplementedError("multi-token decode steps take 16-bit unique caches of head dim 64 / 128 / 256 (no fp8 caches, no "
-                                      "narrow head dims, no disable_attention)")
+        if kvc.narrow or self.head_dim not in (64, 128, 256) or self.disable_attention:
+            raise NotImplementedError("multi-token decode steps take unique caches of head dim 64 / 128 / 256 (no narrow head dims, no "
+                                      "disable_attention)")
         if self.disable_hydragen:
             shared_len = None
         elif shared_len is None:
@@ -579,12 +582,12 @@ class HydragenLlamaAttention(nn.Module):
             from .fused_decode import rope_append_multi
 
             q, seq_lens = rope_append_multi(q, k, v, cos, sin, position_ids, shared_len, kvc.per_completion_k_cache, kvc.per_completion_v_cache,
-                                            **self._qk_norm_args())
+                                            **self._qk_norm_args(), **kvc.scales())
             ks, vs = kvc.per_completion_k_cache[:bsz], kvc.per_completion_v_cache[:bsz]
             try:
                 if not shared:
-                    return flash_attention_seqlen(q, ks, vs, seq_len=seq_lens, causal_tail=True)[0]
-                return hydragen_attention_on_caches(q, ks, vs, shared, seq_len=seq_lens, causal_tail=True)
+                    return flash_attention_seqlen(q, ks, vs, seq_len=seq_lens, causal_tail=True, **kvc.scales())[0]
+                return hydragen_attention_on_caches(q, ks, vs, shared, seq_len=seq_lens, causal_tail=True, **kvc.scales())
             except NotImplementedError:  # a shape the library refuses: the same attention from the existing launches
                 pass
         else:
@@ -594,6 +597,8 @@ class HydragenLlamaAttention(nn.Module):
             q, k = apply_rotary_pos_emb(q, k, cos, sin, position_ids)
             ks, vs = kvc.update_per_completion_kvs(unique_position_ids, k, v)
             seq_lens = unique_position_ids[:, -1] + 1
+        if kvc.fp8:  # the assembled route reads 16-bit rows (its T x T block is a prefix-kernel pass)
+            ks, vs = dequantize_kv(ks, kvc.k_scale, q.dtype), dequantize_kv(vs, kvc.v_scale, q.dtype)
         return speculative.assembled_causal_tail_attention(q, ks, vs, seq_lens, **shared_level_args(shared))
 
     def forward(self, hidden_states: Tensor, position_ids: Tensor, shared_len: Optional[Tensor] = None):
@@ -1431,7 +1436,10 @@ class HydragenLlamaForCausalLM(nn.Module):
         with pad_token_id, as on the stop path (an int eos_token_id is treated as a list of one).  Works with temperature, top_k /
         top_p / min_p, return_logprobs, eos_token_id, pad_token_id, return_finish, num_return_sequences, seq_lens, shared_cache_op
         and constraint; refused (before any launch): penalties and logit_bias, stop, token_overrides, top_logprobs, return_logits,
-        disable_hydragen / disable_attention / disable_hierarchy, fp8 or narrow unique caches, a model on the CPU.
+        disable_hydragen / disable_attention / disable_hierarchy, narrow unique caches, a model on the CPU.  fp8 unique caches
+        (setup_caches(kv_cache_dtype=torch.float8_e4m3fn), with or without kv_scales="calibrate") work: the preamble quantizes
+        the T new rows and the causal-tail pass is the fp8 matrix-core kernel (head dim 256 with few units, which it does not
+        take, runs the assembled attention on dequantized rows: functional, not fast).
         With constraint= every step walks its drafts through the automaton (hyd_draft_constrain): a state that allows exactly
         one token replaces the draft by that token -- accepted with probability 1, the masked sampler can draw nothing else --,
         a draft the automaton rejects ends the row's proposal, each of the step's K + 1 draws is masked by the state behind the

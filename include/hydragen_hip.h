@@ -156,8 +156,8 @@ HYD_API int hyd_suffix_attn_fwd(const hyd_suffix_params* p, void* stream);
  * keys below clamp(seq_len[b], 0, kv_len) - (T - 1 - i), clamped at 0 -- bottom-right aligned, what a causal attention over the
  * whole sequence gives its last T rows.  The struct and everything else (partials, lse, seq_order) are hyd_suffix_attn_fwd's; the
  * unique K/V is streamed once for all T tokens.  A row whose limit is 0 (seq_len < T) comes out as zeros with lse = -inf, like a
- * sequence of length 0.  16-bit caches with rows of D elements only: kv_dim (narrow rows) returns HYD_ERR_UNSUPPORTED, and there is
- * no _kvq form.  T outside 2..8 is HYD_ERR_BAD_ARG.  A causal call never runs on a kernel without the limit. */
+ * sequence of length 0.  Rows of D elements only: kv_dim (narrow rows) returns HYD_ERR_UNSUPPORTED; fp8 caches go through
+ * hyd_suffix_attn_causal_fwd_kvq with HYD_KVQ_CAUSAL.  T outside 2..8 is HYD_ERR_BAD_ARG.  A causal call never runs on a kernel without the limit. */
 HYD_API int hyd_suffix_attn_causal_fwd(const hyd_suffix_params* p, void* stream);
 /* Shapes only (capture-safe, no device read): 1 exactly when the suffix pass and the whole decode operator take the call with
  * its kv_dim -- always for kv_dim 0 / D; for narrow rows: one query row (nq == 1), Hq == Hkv, Hkv a multiple of the 64 / (D / 8)
@@ -231,7 +231,7 @@ typedef struct hyd_decode_params {
                                     * unique part of HYD_PHASE_ALL / UNIQUE / UNIQUE_PARTIAL follows hyd_suffix_attn_causal_fwd's
                                     * rule (suffix.nq = T in 2..8; every query sees every shared key, as before); the one-launch
                                     * form is not taken.  Refused with HYD_ERR_UNSUPPORTED for narrow rows (suffix.kv_dim) and by
-                                    * hyd_decode_attn_fused_kvq for fp8 caches.                                        */
+                                    * hyd_decode_attn_fused_kvq for fp8 caches without HYD_KVQ_CAUSAL in hyd_kv_quant.flags. */
 } hyd_decode_params;
 
 HYD_API size_t hyd_decode_workspace_bytes(const hyd_decode_params* p);
@@ -291,7 +291,7 @@ HYD_API int hyd_rope_append_decode(const hyd_rope_params* p, void* stream);
  * row) takes no part: NONE of its T tokens is written and seq_lens[b] = 0 -- seq_lens[b] is idx + T only when idx >= 0, else 0.
  * K/V rows of drafts a step rejects stay in the cache behind the row's next length; they are never read, and the next step,
  * which starts behind the last accepted token and writes T rows again, overwrites them.
- * 16-bit caches with D 64 / 128 / 256 (no fp8 form, no narrow head dims). */
+ * D 64 / 128 / 256 (no narrow head dims); fp8 caches: hyd_rope_append_multi_kvq. */
 typedef struct hyd_rope_multi_params {
     const void* q;               /* token i of row b at q + b*q_batch_stride + i*q_tok_stride, [Hq, D] contiguous   */
     const void* k;               /* [B, T, Hkv, D] likewise                                                         */
@@ -847,9 +847,17 @@ HYD_API const uint32_t* hyd_allreduce_status(const void* own_block);
  * hyd_decode_kv_quant_supported answers for a whole decode call, flags and phase included.
  * ------------------------------------------------------------------------------------------ */
 #define HYD_KVQ_GQA 1 /* hyd_kv_quant.flags: grouped-query shapes run on the fp8 matrix-core kernel instead of being refused */
+/* hyd_kv_quant.flags: the caller takes the fp8 CAUSAL-TAIL kernel (hyd_suffix_attn_causal_fwd_kvq, hyd_decode_params.causal_tail
+ * with hyd_decode_attn_fused_kvq), which is always the matrix-core one: 2..8 query tokens, rows of D bytes, every unit shape the
+ * 16-bit matrix-core kernel takes AND units of 2 rows (there is no fp8 one-unit-per-wave kernel); D = 256 only with at least 1024
+ * units or fewer than 128 keys.  `out` and `lse` are bit-identical to the 16-bit causal matrix-core kernel on the dequantized
+ * caches wherever both take the shape.  Without the flag a causal call with fp8 caches answers what it always has:
+ * HYD_ERR_UNSUPPORTED.  With it, a shape no fp8 causal kernel takes is HYD_ERR_UNSUPPORTED: a causal call never runs without
+ * the per-row key limit.  The one-launch small form stays off for causal calls. */
+#define HYD_KVQ_CAUSAL 2
 typedef struct hyd_kv_quant {
     int32_t kv_dtype;     /* HYD_FP8_E4M3, or the q dtype = no quantization                       */
-    int32_t flags;        /* 0, or HYD_KVQ_GQA (formerly `reserved`)                             */
+    int32_t flags;        /* 0, or HYD_KVQ_GQA | HYD_KVQ_CAUSAL (formerly `reserved`)            */
     const float* k_scale; /* [Hkv] device, or NULL = 1                                           */
     const float* v_scale; /* [Hkv] device, or NULL = 1                                           */
 } hyd_kv_quant;
@@ -857,6 +865,9 @@ typedef struct hyd_kv_quant {
 HYD_API int hyd_suffix_attn_fwd_kvq(const hyd_suffix_params* p, const hyd_kv_quant* kq, void* stream);
 HYD_API int hyd_decode_attn_fused_kvq(const hyd_decode_params* p, const hyd_kv_quant* kq, void* stream);
 HYD_API int hyd_rope_append_decode_kvq(const hyd_rope_params* p, const hyd_kv_quant* kq, void* stream);
+/* The causal tail over fp8 unique caches.  kq == NULL or kv_dtype == the q dtype: exactly hyd_suffix_attn_causal_fwd.  fp8 caches
+ * need HYD_KVQ_CAUSAL in kq->flags (above); strides count bytes. */
+HYD_API int hyd_suffix_attn_causal_fwd_kvq(const hyd_suffix_params* p, const hyd_kv_quant* kq /* nullable */, void* stream);
 /* Shapes only (capture-safe, no device read): 1 when the suffix pass of these shapes runs natively with kq's cache dtype
  * (always 1 for kq == NULL or kv_dtype == dtype), else 0. */
 HYD_API int hyd_kv_quant_supported(const hyd_suffix_params* p, const hyd_kv_quant* kq);
@@ -879,6 +890,12 @@ typedef struct hyd_qk_norm { const void* q_weight; const void* k_weight; /* [D],
 HYD_API int hyd_rope_append_decode_qkn(const hyd_rope_params* p, const hyd_kv_quant* kq /* nullable */, const hyd_qk_norm* qn /* nullable */,
                                        void* stream);
 HYD_API int hyd_rope_append_multi_qkn(const hyd_rope_multi_params* p, const hyd_qk_norm* qn /* nullable */, void* stream);
+/* The multi-token preamble on fp8 caches: token i of a row is rotated at position + i, quantized with its kv head's scale as
+ * hyd_rope_append_decode_kvq quantizes it (the same bytes as T one-token calls at positions + i) and written at idx0 + i; a retired
+ * row writes nothing, nothing is written at or past cache_len.  kq is checked by hyd_rope_append_decode_kvq's rules (cache strides in
+ * bytes, scales 4-byte aligned, NULL scale = 1; its flags are not read); with kq and qn NULL the call is hyd_rope_append_multi. */
+HYD_API int hyd_rope_append_multi_kvq(const hyd_rope_multi_params* p, const hyd_kv_quant* kq /* nullable */, const hyd_qk_norm* qn /* nullable */,
+                                      void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Fork completions: promote rows of the UNIQUE K/V caches to a packed SHARED level, K and V in one launch (no forward pass: the

@@ -1,7 +1,10 @@
 """Speculative decoding on a Llama-2-7B shell (random weights, bf16, P = 2048): what a T-token decode step costs and what acceptance
 rate pays for it.  Writes the tables of profiles/speculative.md to stdout (markdown) -- nothing here is promised in advance.
 
-    python tools/spec_bench.py [--batches 32,128,1024] [--new 33] [--prefix 2048] [--layers 32] [--no-graph]
+    python tools/spec_bench.py [--batches 32,128,1024] [--new 33] [--prefix 2048] [--layers 32] [--no-graph] [--kv-cache-dtype fp8]
+
+--kv-cache-dtype fp8: the unique caches hold e4m3fn bytes with unit scales (setup_caches(kv_cache_dtype=torch.float8_e4m3fn)): the
+multi-token preamble quantizes, the causal-tail suffix pass is the fp8 matrix-core kernel (profiles/speculative_fp8.md).
 
 Step time: generate() with GIVEN drafts that are all wrong (every step emits exactly one token, so decode time / steps is the step
 time of a T-token step); T = 1 is the plain path.  Break-even acceptance per T: the fraction a of the K drafts that has to be
@@ -35,8 +38,9 @@ def timed(fn, iters=20, warm=3):
     return (time.perf_counter() - t0) / iters * 1e6
 
 
-def kernel_times(B, T, Hq, Hkv, D, P, S):
-    """us per launch of the four new kernels, and of the assembled four-launch attention against the fused causal call."""
+def kernel_times(B, T, Hq, Hkv, D, P, S, fp8=False):
+    """us per launch of the four new kernels, and of the assembled four-launch attention against the fused causal call.  fp8: the
+    unique caches hold e4m3fn bytes with unit scales (the assembled route reads 16-bit rows: timed on the caches they were quantized from)."""
     from hydragen_amd import speculative
     from hydragen_amd.attention import hydragen_attention
     from hydragen_amd.flash import flash_attention_seqlen
@@ -59,18 +63,26 @@ def kernel_times(B, T, Hq, Hkv, D, P, S):
     live = torch.zeros((1,), dtype=torch.int32, device=DEV)
     start = torch.full((B,), P, device=DEV, dtype=torch.int64)
     lv = dict(shared_ks=[sk], shared_vs=[sv], shared_cu_seq_lens=[None], shared_max_seq_lens=[None], use_varlens=[False])
+    sc = {}
+    if fp8:
+        from hydragen_amd.kv_quant import quantize_kv
+
+        kc16, vc16 = kc, vc
+        kc, vc = quantize_kv(kc), quantize_kv(vc)
+        sc = dict(k_scale=torch.ones(Hkv, device=DEV), v_scale=torch.ones(Hkv, device=DEV))
 
     def accept():
         state[1].zero_()
         speculative.draft_accept(fed, fed, *state[:4], live, start, shared, (), 0, S)
 
     return {
-        "hyd_rope_append_multi": timed(lambda: rope_append_multi(q, k, v, rot.cos_cached, rot.sin_cached, pos, shared, kc, vc)),
-        "hyd_suffix_attn_causal_fwd": timed(lambda: flash_attention_seqlen(q, kc, vc, lens, causal_tail=True)),
+        "hyd_rope_append_multi": timed(lambda: rope_append_multi(q, k, v, rot.cos_cached, rot.sin_cached, pos, shared, kc, vc, **sc)),
+        "hyd_suffix_attn_causal_fwd": timed(lambda: flash_attention_seqlen(q, kc, vc, lens, causal_tail=True, **sc)),
         "hyd_draft_lookup": timed(lambda: speculative.draft_lookup([speculative.Segment(ids), speculative.Segment(gen, glen)], B, T - 1)),
         "hyd_draft_accept (+ a memset)": timed(accept),
-        "fused causal call (levels + causal tail)": timed(lambda: hydragen_attention(q, kc, vc, **lv, seq_lens=lens, causal_tail=True)),
-        "assembled (level, old keys, causal block, combine)": timed(lambda: speculative.assembled_causal_tail_attention(q, kc, vc, lens, [sk], [sv])),
+        "fused causal call (levels + causal tail)": timed(lambda: hydragen_attention(q, kc, vc, **lv, seq_lens=lens, causal_tail=True, **sc)),
+        "assembled (level, old keys, causal block, combine)" + (" on 16-bit caches" if fp8 else ""): timed(
+            lambda: speculative.assembled_causal_tail_attention(q, kc16 if fp8 else kc, vc16 if fp8 else vc, lens, [sk], [sv])),
     }
 
 
@@ -81,7 +93,9 @@ def main():
     ap.add_argument("--prefix", type=int, default=2048)
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--kv-cache-dtype", choices=("16-bit", "fp8"), default="16-bit")
     args = ap.parse_args()
+    fp8 = args.kv_cache_dtype == "fp8"
     from hydragen_amd.llama import HydragenLlamaForCausalLM, LlamaConfig
 
     cfg = LlamaConfig.llama2_7b()
@@ -92,9 +106,10 @@ def main():
     prompt = torch.randint(1, cfg.vocab_size, (1, args.prefix), device=DEV)
     N, steps = args.new, args.new - 1
     print(f"# Speculative decoding: measurements\n\nLlama-2-7B shell ({args.layers} layers, random weights, bf16), P = {args.prefix}, {N} new tokens, "
-          f"{'eager' if args.no_graph else 'HIP-graph'} decode, temperature 0.\n")
+          f"{'eager' if args.no_graph else 'HIP-graph'} decode, temperature 0, {'fp8 (e4m3fn, unit scales)' if fp8 else '16-bit'} unique caches.\n")
     for B in (int(b) for b in args.batches.split(",")):
-        model.setup_caches(max_unique_batch_size=B, max_unique_seq_length=N + 16, max_shared_batch_sizes=[1], max_shared_seq_lengths=[args.prefix])
+        model.setup_caches(max_unique_batch_size=B, max_unique_seq_length=N + 16, max_shared_batch_sizes=[1], max_shared_seq_lengths=[args.prefix],
+                           **(dict(kv_cache_dtype=torch.float8_e4m3fn) if fp8 else {}))
 
         def run(n, **kw):
             torch.cuda.synchronize()
@@ -131,7 +146,7 @@ def main():
                   f"{B * steps / (t_pl - pre):.0f} ({int(st.accepted.sum())} / {int(st.proposed.sum())}) |")
         print()
         model.graph(False)
-        kt = kernel_times(B, 4, cfg.num_attention_heads, cfg.num_key_value_heads, cfg.hidden_size // cfg.num_attention_heads, args.prefix, 64)
+        kt = kernel_times(B, 4, cfg.num_attention_heads, cfg.num_key_value_heads, cfg.hidden_size // cfg.num_attention_heads, args.prefix, 64, fp8)
         model.graph(not args.no_graph)
         print("per launch at T = 4, suffix 64 (us, eager, host-timed back to back):\n")
         for name, us in kt.items():
