@@ -1,5 +1,6 @@
-// C ABI, attention: the prefix / suffix / causal-tail / combine entry points, the decode call with its one plan, the workspace and
-// support queries.
+// C ABI, attention: the prefix / suffix / causal-tail / combine entry points with the unique pass's one plan, the decode call with
+// its one plan (which holds the former), the workspace and support queries.
+#include <cstddef>
 #include <cstdlib>
 
 #include "api_core.h"
@@ -262,9 +263,8 @@ int check_suffix(const hyd_suffix_params* p) {
                            {p->v_batch_stride, "v_batch_stride"}, {p->v_tok_stride, "v_tok_stride"}, {p->v_head_stride, "v_head_stride"}});
 }
 
-void fill_suffix_args(const hyd_suffix_params* p, SuffixArgs* ap) {
+void fill_suffix_args(const hyd_suffix_params* p, SuffixArgs* ap) {  // *ap is zeroed (plan_suffix, the one caller)
     SuffixArgs& a = *ap;
-    memset(&a, 0, sizeof(a));
     a.q = p->q; a.k = p->k; a.v = p->v; a.out = p->out; a.lse = p->lse; a.sl32 = p->seq_lens_i32; a.sl64 = p->seq_lens_i64; a.order = p->seq_order;
     a.k_bs = p->k_batch_stride; a.k_ts = p->k_tok_stride; a.k_hs = p->k_head_stride; a.v_bs = p->v_batch_stride; a.v_ts = p->v_tok_stride; a.v_hs = p->v_head_stride;
     a.B = p->B; a.nq = p->nq; a.Hq = p->Hq; a.Hkv = p->Hkv;
@@ -273,15 +273,9 @@ void fill_suffix_args(const hyd_suffix_params* p, SuffixArgs* ap) {
     a.kv_dim = p->kv_len > 0 ? narrow_kv_dim(p) : 0;  // (no unique key, nothing narrow to read: the merge-only call of the D-wide kernels)
 }
 
-int fail_narrow_shapes(const hyd_suffix_params* p) {
+int fail_narrow_shapes(int kv_dim, int D) {
     return fail(HYD_ERR_UNSUPPORTED, "kv_dim %d: narrow unique caches run on the token-row kernel only (nq == 1, Hq == Hkv, Hkv a multiple of %d at D = %d, "
-                                     "a sequence's cache within 2 GiB)", p->kv_dim, 64 / (p->D / 8), p->D);
-}
-// shapes only: a narrow call (kv_dim set, unique keys present) the narrow token-row kernel takes
-bool narrow_native(const hyd_suffix_params* p) {
-    SuffixArgs a;
-    fill_suffix_args(p, &a);
-    return suffix_narrow_eligible(a, p->D);
+                                     "a sequence's cache within 2 GiB)", kv_dim, 64 / (D / 8), D);
 }
 
 // HYD_KVQ_GQA: the caller takes the grouped-query fp8 kernel; without it the entry points keep the shapes of ABI 0.5.0 as first
@@ -307,65 +301,85 @@ int check_causal_tail(const hyd_suffix_params* p, const hyd_kv_quant* kq) {
 
 int fail_causal_shapes() { return fail(HYD_ERR_UNSUPPORTED, "causal tail: no kernel with the per-row key limit takes these shapes"); }
 
-// shapes only: a kernel with the per-row key limit takes the call -- with fp8 caches the matrix-core one, which also takes the 2-row units
-// that 16-bit caches give the one-unit-per-wave kernel (suffix_attn_gqa_fp8_causal.hip: there is no fp8 kernel of that kind)
-bool causal_eligible(const SuffixArgs& a, int D, const hyd_kv_quant* kq) {
-    return kq ? suffix_gqa_fp8_causal_eligible(a, D) : suffix_causal_eligible(a, D);
+// ---- one plan per unique pass -----------------------------------------------------------------------------------------
+// Which suffix kernel takes a call, if any: asked of the kernels' own *_eligible functions HERE and nowhere else in this file.  The
+// support queries, the entry points' refusals and the launch all read a SuffixPlan, so they cannot disagree.  The plan holds facts,
+// not a first refusal: each entry point answers bad input in an order of its own (tests/golden/abi_table.json pins every one).
+enum SuffixRoute {
+    kRoute16,         // launch_suffix, which goes on choosing between its grouped-query / token-row / narrow / one-unit-per-wave kernels
+    kRouteFp8Rows,    // launch_suffix_fp8: the token-row kernel
+    kRouteFp8Gqa,     // launch_suffix_gqa_fp8: the matrix-core kernel
+    kRouteCausal16,   // launch_suffix_causal
+    kRouteCausalFp8,  // launch_suffix_gqa_fp8_causal
+    kRouteMergeOnly,  // no unique key, 16-bit, not causal: launch_suffix merges the partials (an fp8 or a causal call keeps its launcher)
+};
+struct SuffixPlan {
+    bool valid;          // the shapes are what check_suffix takes (the queries ask about shapes nobody validated); false: nothing below is set
+    const hyd_suffix_params* p;  // the call as planned ...
+    const hyd_kv_quant* kq;      // ... null, or fp8 unique caches (K/V strides in bytes)
+    bool causal;         // ... the causal tail
+    SuffixRoute route;  // where the call goes once the verdicts its entry point answers for hold
+    bool narrow;         // narrow rows are read (kv_dim set, unique keys present); with fp8 caches: no kernel
+    bool narrow_native;  // ... and the narrow token-row kernel takes the shapes
+    bool fp8_native;     // an fp8 kernel takes the shapes, with the caller's HYD_KVQ_GQA as it stands
+    bool fp8_gqa;        // ... and it is the grouped-query one (whose 16-bit twin tiny decode calls fold into one launch)
+    bool causal_native;  // a kernel with the per-row key limit takes the shapes; fp8: HYD_KVQ_CAUSAL given, and 2-row units are taken as well
+    bool gqa_any_rows;   // the grouped-query kernel can walk these units at any row count (the one-launch decode form)
+    bool span_ok, grid_ok;  // a sequence's K/V span is below 2 GiB at the cache's element size; kv heads and query rows fit the suffix grid
+    SuffixArgs args;     // filled once; run_suffix adds the partial slices
+};
+
+// Shapes only: no HIP call, and no word to the error string unless the shapes themselves are invalid (which every launch entry point
+// has refused before it plans).
+void plan_suffix(const hyd_suffix_params* p, const hyd_kv_quant* kq, bool causal, SuffixPlan* pl) {
+    memset(pl, 0, sizeof(*pl));
+    if (check_common(p->dtype, p->B, p->nq, p->Hq, p->Hkv, p->D) || check_narrow_dim(p->kv_dim, p->D, "kv_dim")) return;
+    pl->valid = true; pl->p = p; pl->kq = kq; pl->causal = causal;
+    fill_suffix_args(p, &pl->args);
+    const SuffixArgs& a = pl->args;
+    const int D = p->D, esz = kq ? 1 : 2;
+    pl->narrow = a.kv_dim != 0;
+    pl->narrow_native = pl->narrow && suffix_narrow_eligible(a, D);
+    // the 16-bit launcher's order: grouped-query shapes to the matrix-core kernel, one-row units to the token-row kernel
+    pl->fp8_gqa = !pl->narrow && kvq_takes_gqa(kq) && suffix_gqa_fp8_eligible(a, D);
+    pl->fp8_native = !pl->narrow && (pl->fp8_gqa || suffix_fp8_eligible(a, D));
+    pl->causal_native = causal && (kq ? kvq_takes_causal(kq) && suffix_gqa_fp8_causal_eligible(a, D) : suffix_causal_eligible(a, D));
+    pl->gqa_any_rows = suffix_gqa_eligible(a, D, /*any_shape=*/true);
+    pl->span_ok = (int64_t)p->kv_len * p->k_tok_stride * esz < (1ll << 31) && (int64_t)p->kv_len * p->v_tok_stride * esz < (1ll << 31);
+    pl->grid_ok = p->Hkv <= 4 * 65535 && a.rows <= 8 * 65535;
+    pl->route = causal ? (kq ? kRouteCausalFp8 : kRouteCausal16) : kq ? (pl->fp8_gqa ? kRouteFp8Gqa : kRouteFp8Rows) : p->kv_len == 0 ? kRouteMergeOnly : kRoute16;
 }
 
-// kq: null, or fp8 unique caches (validated by check_kvq; K/V strides in bytes).  causal: the causal tail (check_causal_tail passed) --
-// such a call goes to launch_suffix_causal / launch_suffix_gqa_fp8_causal or fails, never to a kernel without the per-row key limit.
-int run_suffix(const hyd_suffix_params* p, const hyd_partial* parts, int n_parts, hipStream_t s, const hyd_kv_quant* kq = nullptr, bool causal = false) {
-    SuffixArgs a;
-    fill_suffix_args(p, &a);
-    int rc = for_each_slice(parts, n_parts, (size_t)p->B * p->nq * p->Hq, p->D, &a.n_partials, [&a](int n, const void* out, const float* lse, int is_f32) {
-        a.partials[n].out = out;
-        a.partials[n].lse = lse;
-        a.partials[n].is_f32 = is_f32;
+int check_suffix_limits(const SuffixPlan& pl) {
+    if (!pl.span_ok) return fail(HYD_ERR_UNSUPPORTED, "unique K/V of one sequence spans >= 2 GiB (32-bit in-sequence offsets)");
+    if (!pl.grid_ok) return fail(HYD_ERR_UNSUPPORTED, "too many kv heads / query rows for the suffix grid");
+    return HYD_OK;
+}
+
+// The unique pass of a validated call (check_suffix, check_kvq, and check_causal_tail where it is causal): the partials, then the
+// limits, then what no kernel takes, in the order the suffix entry points have always answered; then the launch the plan names.
+int run_suffix(const SuffixPlan& pl, const hyd_partial* parts, int n_parts, hipStream_t s) {
+    SuffixKvqArgs ka = {pl.kq ? pl.kq->k_scale : nullptr, pl.kq ? pl.kq->v_scale : nullptr, pl.args};  // (the scales: fp8 caches only)
+    SuffixArgs& a = ka.a;
+    const int dtype = pl.p->dtype, D = pl.p->D;
+    int rc = for_each_slice(parts, n_parts, (size_t)a.B * a.nq * a.Hq, D, &a.n_partials, [&a](int n, const void* out, const float* lse, int is_f32) {
+        a.partials[n] = {out, lse, is_f32, /*pad=*/0};
     });
     if (rc) return rc;
     a.n_pre = 0;
     while (a.n_pre < 2 && a.n_pre < a.n_partials && !a.partials[a.n_pre].is_f32) ++a.n_pre;
-    const int64_t esz = kq ? 1 : 2;
-    if ((int64_t)p->kv_len * p->k_tok_stride * esz >= (1ll << 31) || (int64_t)p->kv_len * p->v_tok_stride * esz >= (1ll << 31))
-        return fail(HYD_ERR_UNSUPPORTED, "unique K/V of one sequence spans >= 2 GiB (32-bit in-sequence offsets)");
-    if (p->Hkv > 4 * 65535 || a.rows > 8 * 65535) return fail(HYD_ERR_UNSUPPORTED, "too many kv heads / query rows for the suffix grid");
-    SuffixKvqArgs ka;  // (fp8 caches only)
-    ka.k_scale = kq ? kq->k_scale : nullptr;
-    ka.v_scale = kq ? kq->v_scale : nullptr;
-    if (causal) {
-        if ((kq && !kvq_takes_causal(kq)) || !causal_eligible(a, p->D, kq)) return fail_causal_shapes();
-        if (!kq) return launched(launch_suffix_causal(a, p->dtype, p->D, s), "causal-tail suffix kernel launch");
-        ka.a = a;
-        return launched(launch_suffix_gqa_fp8_causal(ka, p->dtype, p->D, s), "fp8 causal-tail suffix kernel launch");
+    if ((rc = check_suffix_limits(pl))) return rc;
+    if (pl.causal && !pl.causal_native) return fail_causal_shapes();  // the causal tail: to a kernel with the per-row key limit or nowhere
+    if (!pl.causal && pl.narrow && pl.kq) return fail_narrow_fp8();
+    if (!pl.causal && pl.narrow && !pl.narrow_native) return fail_narrow_shapes(a.kv_dim, D);
+    if (!pl.causal && pl.kq && !pl.fp8_native) return fail_kvq_shapes(D);
+    switch (pl.route) {
+        case kRouteFp8Rows: return launched(launch_suffix_fp8(ka, dtype, D, s), "fp8 suffix kernel launch");
+        case kRouteFp8Gqa: return launched(launch_suffix_gqa_fp8(ka, dtype, D, s), "fp8 suffix kernel launch");
+        case kRouteCausal16: return launched(launch_suffix_causal(a, dtype, D, s), "causal-tail suffix kernel launch");
+        case kRouteCausalFp8: return launched(launch_suffix_gqa_fp8_causal(ka, dtype, D, s), "fp8 causal-tail suffix kernel launch");
+        default: return launched(launch_suffix(a, dtype, D, s), "suffix kernel launch");  // kRoute16, kRouteMergeOnly
     }
-    if (a.kv_dim) {
-        if (kq) return fail_narrow_fp8();
-        if (!suffix_narrow_eligible(a, p->D)) return fail_narrow_shapes(p);
-    }
-    if (kq) {
-        // the 16-bit launcher's order: grouped-query shapes to the matrix-core kernel, one-row units to the token-row kernel
-        const bool gqa = kvq_takes_gqa(kq) && suffix_gqa_fp8_eligible(a, p->D);
-        if (!gqa && !suffix_fp8_eligible(a, p->D)) return fail_kvq_shapes(p->D);
-        ka.a = a;
-        return launched(gqa ? launch_suffix_gqa_fp8(ka, p->dtype, p->D, s) : launch_suffix_fp8(ka, p->dtype, p->D, s), "fp8 suffix kernel launch");
-    }
-    return launched(launch_suffix(a, p->dtype, p->D, s), "suffix kernel launch");
-}
-
-// shapes-only: does an fp8 suffix kernel take these shapes (nothing is launched, no device memory read)
-bool kvq_native(const hyd_suffix_params* p, const hyd_kv_quant* kq) {
-    if (check_common(p->dtype, p->B, p->nq, p->Hq, p->Hkv, p->D) || narrow_kv_dim(p)) return false;
-    SuffixArgs a;
-    fill_suffix_args(p, &a);
-    return (kvq_takes_gqa(kq) && suffix_gqa_fp8_eligible(a, p->D)) || suffix_fp8_eligible(a, p->D);
-}
-// ... and is it the grouped-query kernel that takes them (the one whose 16-bit twin tiny decode calls fold into one launch)
-bool kvq_native_gqa(const hyd_suffix_params* p, const hyd_kv_quant* kq) {
-    if (!kvq_takes_gqa(kq) || check_common(p->dtype, p->B, p->nq, p->Hq, p->Hkv, p->D)) return false;
-    SuffixArgs a;
-    fill_suffix_args(p, &a);
-    return suffix_gqa_fp8_eligible(a, p->D);
 }
 
 void level_to_prefix(const hyd_decode_params* p, int i, hyd_prefix_params* pp) {
@@ -413,7 +427,7 @@ int level_split_cap(int n_levels) { return n_levels > 0 ? kMaxCombine / n_levels
 
 // ---- one plan per decode call -----------------------------------------------------------------------------------------
 // Everything the shapes of a hyd_decode_params decide, derived in ONE place: the size queries, the support queries and the
-// launch all read a DecodePlan and plan nothing of their own, so they cannot disagree.
+// launch all read a DecodePlan -- the levels, and the call's one SuffixPlan -- and plan nothing of their own, so they cannot disagree.
 enum DecodeForm {
     kPrefixOnly,  // attention.py:273-274: a single shared level and no unique keys -> the prefix result IS the answer
     kOneLaunch,   // single_launch_small applies (16-bit caches): one grouped-query kernel walks both segments
@@ -436,6 +450,7 @@ struct DecodePlan {
     int n_parts;          // slices of all levels' partials
     size_t levels_bytes;  // the levels' regions (kPrefixOnly: the split-KV slices of the one pass, which writes straight to `out`)
     SliceLayout unique;   // behind them, the unique pass's own 16-bit partial of the two-stream form; bytes = 0 without both parts
+    SuffixPlan suffix;    // the unique pass, once for every phase; without unique keys the merge-only pass (last: plan_suffix zeroes it)
 };
 
 // hyd_decode_params.single_launch_small: one uniform shared level that already counts as small (few query rows per
@@ -444,28 +459,27 @@ struct DecodePlan {
 // units x keys = B * Hkv * (P + S)): 1152 keys (BASELINE config 1) 6.8 -> 4.1 us, 2176 keys 11.4 -> 8.1, 8072 keys (two
 // sequences on a 1000-key prefix) 19.5 -> 16.5, 8704 keys (32 sequences) 14.0 -> 14.1: even.  Shapes only: capture-safe.
 constexpr int64_t kSingleLaunchMaxKeys = 8192;
-bool decode_runs_as_one_launch(const hyd_decode_params* p, const LevelPlan& lv) {
+bool decode_runs_as_one_launch(const hyd_decode_params* p, const LevelPlan& lv, const SuffixPlan& u) {
     const hyd_suffix_params& sp = p->suffix;
     if (p->phase != HYD_PHASE_ALL || !p->single_launch_small || p->n_levels != 1 || !lv.small || sp.kv_len <= 0) return false;
     if (p->causal_tail) return false;  // the walk over both segments has no per-row key limit: the pair of launches runs
-    if (narrow_kv_dim(&sp)) return false;  // narrow unique caches: the pair of launches runs (the rule Hq == Hkv fp8 calls have)
+    if (u.narrow) return false;  // narrow unique caches: the pair of launches runs (the rule Hq == Hkv fp8 calls have)
     if (sp.lse) return false;  // suffix.lse is the LSE of the unique keys alone in every form; one walk over both segments cannot give it
     const hyd_prefix_params& pp = lv.pp;
     if (pp.cu_seqlens_k || pp.sb <= 0 || sp.B % pp.sb != 0) return false;  // (a small level runs unsplit whatever the plan says)
     if (pp.k_tok_stride != sp.k_tok_stride || pp.v_tok_stride != sp.v_tok_stride) return false;
     if ((int64_t)sp.B * sp.Hkv * ((int64_t)pp.kv_len + sp.kv_len) > kSingleLaunchMaxKeys) return false;
-    SuffixArgs a;
-    fill_suffix_args(&sp, &a);
-    return suffix_gqa_eligible(a, sp.D, /*any_shape=*/true);
+    return u.gqa_any_rows;
 }
 
 bool levels_in_range(const hyd_decode_params* p) { return p->n_levels >= 0 && p->n_levels <= HYD_MAX_LEVELS; }
 
-// Shapes only.  The caller has checked levels_in_range (each entry point has its own answer to that).  The prefix-only form
-// plans its one pass with the default split cap, every other form shares the merge budget among its levels.
-void plan_decode(const hyd_decode_params* p, DecodePlan* d) {
+// Shapes only: the levels and the sizes, all that the size queries ask (they leave d->suffix unplanned); nothing without levels_in_range (each entry
+// point has its own answer to that).  The prefix-only form plans its one pass with the default split cap, every other form shares the merge budget.
+void plan_levels(const hyd_decode_params* p, DecodePlan* d) {
     const hyd_suffix_params& sp = p->suffix;
-    memset(d, 0, sizeof(*d));
+    memset(d, 0, offsetof(DecodePlan, suffix));
+    if (!levels_in_range(p)) return;
     const bool prefix_only = p->n_levels == 1 && sp.kv_len == 0;
     d->two_stream_ok = p->n_levels > 0 && sp.kv_len > 0;
     // (a two-stream phase on prefix-only shapes is refused by the launch, and sized like the prefix-only form by the queries)
@@ -488,7 +502,16 @@ void plan_decode(const hyd_decode_params* p, DecodePlan* d) {
         d->n_parts += lv.count;
     }
     if (d->two_stream_ok) d->unique = slice_layout(rows, sp.D, 2, 1);
-    if (d->form == kInOrder && decode_runs_as_one_launch(p, d->level[0])) d->form = kOneLaunch;
+}
+
+// ... and the call's unique pass, planned once for every phase (kq: null, or fp8 unique caches).  Without unique keys it only merges:
+// no fp8, no causal tail, no sequence lengths.
+void plan_decode(const hyd_decode_params* p, const hyd_kv_quant* kq, DecodePlan* d) {
+    const bool unique = p->suffix.kv_len > 0;
+    plan_suffix(&p->suffix, unique ? kq : nullptr, unique && p->causal_tail != 0, &d->suffix);  // (first: plan_prefix's message, if any, stays the last)
+    if (!unique) d->suffix.args.sl32 = nullptr, d->suffix.args.sl64 = nullptr;
+    plan_levels(p, d);
+    if (d->form == kInOrder && decode_runs_as_one_launch(p, d->level[0], d->suffix)) d->form = kOneLaunch;
 }
 
 int check_prefix_ptrs(const hyd_prefix_params* p) {
@@ -527,39 +550,38 @@ int hyd_prefix_attn_fwd(const hyd_prefix_params* p, void* stream) {
     return run_prefix(p, pl, /*merge=*/true, static_cast<hipStream_t>(stream));
 }
 
-int hyd_suffix_attn_fwd_kvq(const hyd_suffix_params* p, const hyd_kv_quant* kq, void* stream) {
+static int suffix_fwd(const hyd_suffix_params* p, const hyd_kv_quant* kq, bool causal, void* stream) {
     int rc = check_suffix(p);
     if (rc) return rc;
     if ((rc = check_kvq(&kq, p->dtype))) return rc;
+    if (causal && (rc = check_causal_tail(p, kq))) return rc;
     if (p->n_partials < 0 || p->n_partials > HYD_MAX_LEVELS) return fail(HYD_ERR_BAD_ARG, "n_partials %d", p->n_partials);
     if (p->kv_len == 0 && p->n_partials == 0) return fail(HYD_ERR_BAD_ARG, "kv_len == 0 and no partials");
-    return run_suffix(p, p->partials, p->n_partials, static_cast<hipStream_t>(stream), kq);
+    SuffixPlan pl;  // (a causal call without unique keys drops its hyd_kv_quant, a plain one has always kept it)
+    plan_suffix(p, causal && p->kv_len == 0 ? nullptr : kq, causal, &pl);
+    return run_suffix(pl, p->partials, p->n_partials, static_cast<hipStream_t>(stream));
 }
 
-int hyd_suffix_attn_fwd(const hyd_suffix_params* p, void* stream) { return hyd_suffix_attn_fwd_kvq(p, nullptr, stream); }
-
-int hyd_suffix_attn_causal_fwd_kvq(const hyd_suffix_params* p, const hyd_kv_quant* kq, void* stream) {
-    int rc = check_suffix(p);
-    if (rc) return rc;
-    if ((rc = check_kvq(&kq, p->dtype))) return rc;
-    if ((rc = check_causal_tail(p, kq))) return rc;
-    if (p->n_partials < 0 || p->n_partials > HYD_MAX_LEVELS) return fail(HYD_ERR_BAD_ARG, "n_partials %d", p->n_partials);
-    if (p->kv_len == 0 && p->n_partials == 0) return fail(HYD_ERR_BAD_ARG, "kv_len == 0 and no partials");
-    return run_suffix(p, p->partials, p->n_partials, static_cast<hipStream_t>(stream), p->kv_len > 0 ? kq : nullptr, /*causal=*/true);
-}
-
-int hyd_suffix_attn_causal_fwd(const hyd_suffix_params* p, void* stream) { return hyd_suffix_attn_causal_fwd_kvq(p, nullptr, stream); }
+int hyd_suffix_attn_fwd_kvq(const hyd_suffix_params* p, const hyd_kv_quant* kq, void* stream) { return suffix_fwd(p, kq, false, stream); }
+int hyd_suffix_attn_fwd(const hyd_suffix_params* p, void* stream) { return suffix_fwd(p, nullptr, false, stream); }
+int hyd_suffix_attn_causal_fwd_kvq(const hyd_suffix_params* p, const hyd_kv_quant* kq, void* stream) { return suffix_fwd(p, kq, true, stream); }
+int hyd_suffix_attn_causal_fwd(const hyd_suffix_params* p, void* stream) { return suffix_fwd(p, nullptr, true, stream); }
 
 int hyd_kv_quant_supported(const hyd_suffix_params* p, const hyd_kv_quant* kq) {
     if (!p) return 0;
     const KvqKind kind = kvq_kind(kq, p->dtype);
-    return kind == kKvqNone || (kind == kKvqFp8 && kvq_native(p, kq)) ? 1 : 0;
+    if (kind != kKvqFp8) return kind == kKvqNone ? 1 : 0;
+    SuffixPlan pl;
+    plan_suffix(p, kq, /*causal=*/false, &pl);
+    return pl.valid && !narrow_kv_dim(p) && pl.fp8_native ? 1 : 0;  // (a narrow kv_dim answers 0 here even where no key is read)
 }
 
 int hyd_narrow_kv_supported(const hyd_suffix_params* p) {
-    if (!p || check_common(p->dtype, p->B, p->nq, p->Hq, p->Hkv, p->D) || check_narrow_dim(p->kv_dim, p->D, "kv_dim")) return 0;
-    if (!narrow_kv_dim(p) || p->kv_len <= 0) return p->kv_len >= 0 ? 1 : 0;  // nothing narrow is read: the existing call
-    return narrow_native(p) ? 1 : 0;
+    if (!p) return 0;
+    SuffixPlan pl;
+    plan_suffix(p, nullptr, /*causal=*/false, &pl);
+    if (!pl.narrow) return pl.valid && p->kv_len >= 0 ? 1 : 0;  // nothing narrow is read: the existing call
+    return pl.narrow_native ? 1 : 0;
 }
 
 int hyd_combine_lse(const void* const* outs, const float* const* lses, int32_t n, int64_t rows, int32_t D,
@@ -592,7 +614,7 @@ int hyd_combine_lse(const void* const* outs, const float* const* lses, int32_t n
 size_t hyd_decode_workspace_bytes(const hyd_decode_params* p) {
     if (!p || !levels_in_range(p)) return 0;
     DecodePlan d;
-    plan_decode(p, &d);
+    plan_levels(p, &d);
     return d.rc ? 0 : d.levels_bytes + d.unique.bytes;  // (the unique partial counts in every phase: one size for the whole call)
 }
 
@@ -617,38 +639,10 @@ size_t hyd_workspace_bytes(int32_t B, int32_t nq, int32_t Hq, int32_t Hkv, int32
     return hyd_decode_workspace_bytes(&p);
 }
 
-static int decode_impl(const hyd_decode_params* p, const hyd_kv_quant* kq, void* stream);
-
 // Shapes only: a grouped-query fp8 call whose 16-bit twin would run as ONE launch (decode_runs_as_one_launch).  The one-launch walk
-// does not round a 16-bit prefix partial, the two-kernel pair does: the pair is not what the caller's 16-bit results are, so such a
-// call is refused instead of quietly run as the pair.  (Hq == Hkv shapes keep ignoring the flag, as they always have.)
-static bool decode_kvq_is_one_launch(const hyd_decode_params* p, const hyd_kv_quant* kq) {
-    if (!levels_in_range(p) || !kvq_native_gqa(&p->suffix, kq)) return false;
-    DecodePlan d;
-    plan_decode(p, &d);
-    return !d.rc && d.form == kOneLaunch;  // (a level that does not plan: decode_impl reports it)
-}
-
-int hyd_decode_attn_fused(const hyd_decode_params* p, void* stream) { return decode_impl(p, nullptr, stream); }
-
-int hyd_decode_attn_fused_kvq(const hyd_decode_params* p, const hyd_kv_quant* kq, void* stream) {
-    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
-    int rc = check_suffix(&p->suffix);
-    if (rc) return rc;
-    if ((rc = check_kvq(&kq, p->suffix.dtype))) return rc;
-    if (!kq) return decode_impl(p, nullptr, stream);
-    // fp8 unique caches: validated up front (every phase, also those that do not read the unique cache) so that the phases of one
-    // call agree; kv_len == 0 reads no unique key and takes the existing path
-    if (p->suffix.kv_len > 0 && narrow_kv_dim(&p->suffix)) return fail_narrow_fp8();
-    // a causal call of a caller that takes the fp8 causal kernel (HYD_KVQ_CAUSAL) is judged by that kernel's shapes, in decode_impl, behind
-    // the checks of causal_tail itself; every other call keeps the order of answers it has always had
-    const bool causal_kq = p->causal_tail != 0 && kvq_takes_causal(kq);
-    if (p->suffix.kv_len > 0 && !causal_kq && !kvq_native(&p->suffix, kq)) return fail_kvq_shapes(p->suffix.D);
-    if (decode_kvq_is_one_launch(p, kq))
-        return fail(HYD_ERR_UNSUPPORTED, "fp8 unique caches: a grouped-query call this small runs as ONE launch with 16-bit caches "
-                                         "(single_launch_small), which has no fp8 form: clear the flag, or pass 16-bit caches");
-    return decode_impl(p, p->suffix.kv_len > 0 ? kq : nullptr, stream);
-}
+// does not round a 16-bit prefix partial, the two-kernel pair does: the pair is not what the caller's 16-bit results are, so such a call is
+// refused instead of quietly run as the pair.  (Hq == Hkv shapes keep ignoring the flag; a level that does not plan: decode_impl reports it.)
+static bool decode_kvq_is_one_launch(const DecodePlan& d) { return d.suffix.fp8_gqa && d.form == kOneLaunch; }
 
 int hyd_decode_kv_quant_supported(const hyd_decode_params* p, const hyd_kv_quant* kq) {
     if (!p) return 0;
@@ -656,46 +650,47 @@ int hyd_decode_kv_quant_supported(const hyd_decode_params* p, const hyd_kv_quant
     if (kind != kKvqFp8) return kind == kKvqNone ? 1 : 0;
     if (!levels_in_range(p)) return 0;
     if (p->suffix.kv_len <= 0) return p->suffix.kv_len == 0 ? 1 : 0;  // no unique key is read: the existing path
-    if (p->causal_tail != 0) {  // the causal tail: the launch's own rules (check_causal_tail, then the fp8 causal kernel's shapes)
-        const hyd_suffix_params& sp = p->suffix;
-        if (p->causal_tail != 1 || !kvq_takes_causal(kq) || check_common(sp.dtype, sp.B, sp.nq, sp.Hq, sp.Hkv, sp.D) || narrow_kv_dim(&sp)) return 0;
-        SuffixArgs a;
-        fill_suffix_args(&sp, &a);
-        return suffix_gqa_fp8_causal_eligible(a, sp.D) ? 1 : 0;  // (2..8 query tokens included)
-    }
-    return kvq_native(&p->suffix, kq) && !decode_kvq_is_one_launch(p, kq) ? 1 : 0;
+    DecodePlan d;
+    plan_decode(p, kq, &d);
+    if (!d.suffix.valid) return 0;
+    // the causal tail: the launch's own rules (check_causal_tail, then the fp8 causal kernel's shapes)
+    if (p->causal_tail != 0) return p->causal_tail == 1 && !check_causal_tail(&p->suffix, kq) && d.suffix.causal_native ? 1 : 0;
+    return d.suffix.fp8_native && !decode_kvq_is_one_launch(d) ? 1 : 0;
 }
 
-// kq: null, or validated fp8 unique caches (then the unique pass is an fp8 kernel and the call is never the one-launch form: Hq == Hkv
-// shapes ignore single_launch_small, grouped-query ones were refused by the caller where the flag would have applied)
+// kq: null, or fp8 unique caches that are read (kv_len > 0), validated with the suffix block by hyd_decode_attn_fused_kvq.  Such a call is
+// never the one-launch form: Hq == Hkv shapes ignore single_launch_small, grouped-query ones are refused where the flag would have applied.
 static int decode_impl(const hyd_decode_params* p, const hyd_kv_quant* kq, void* stream) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    const hyd_suffix_params& sp = p->suffix;
+    const bool causal = p->causal_tail != 0;
+    DecodePlan d;  // the one plan of the call: every check below and every phase reads it
+    plan_decode(p, kq, &d);
+    const SuffixPlan& u = d.suffix;
+    if (kq) {
+        // fp8 unique caches: judged up front, in every phase, so that the phases of one call agree.  A causal call that takes the fp8 causal
+        // kernel (HYD_KVQ_CAUSAL) is judged by that kernel's shapes, below, behind the checks of causal_tail itself
+        if (u.narrow) return fail_narrow_fp8();
+        if (!(causal && kvq_takes_causal(kq)) && !u.fp8_native) return fail_kvq_shapes(sp.D);
+        if (decode_kvq_is_one_launch(d))
+            return fail(HYD_ERR_UNSUPPORTED, "fp8 unique caches: a grouped-query call this small runs as ONE launch with 16-bit caches "
+                                             "(single_launch_small), which has no fp8 form: clear the flag, or pass 16-bit caches");
+    }
     if (!levels_in_range(p)) return fail(HYD_ERR_BAD_ARG, "n_levels %d", p->n_levels);
     if (p->phase < HYD_PHASE_ALL || p->phase > HYD_PHASE_MERGE) return fail(HYD_ERR_BAD_ARG, "phase %d", p->phase);
     if (p->shared_max_workgroups < 0) return fail(HYD_ERR_BAD_ARG, "shared_max_workgroups %d", p->shared_max_workgroups);
     if (p->f32_partials != 0 && p->f32_partials != 1) return fail(HYD_ERR_BAD_ARG, "f32_partials %d", p->f32_partials);
-    const hyd_suffix_params& sp = p->suffix;
     int rc = check_suffix(&sp);
     if (rc) return rc;
     if (p->n_levels == 0 && sp.kv_len == 0) return fail(HYD_ERR_BAD_ARG, "no shared levels and no unique keys");
-    if (narrow_kv_dim(&sp) && sp.kv_len > 0) {  // refused before the first launch, in every phase, so that the phases of one call agree
-        if (kq) return fail_narrow_fp8();
-        if (!narrow_native(&sp)) return fail_narrow_shapes(&sp);
-    }
+    if (u.narrow && !u.narrow_native) return fail_narrow_shapes(sp.kv_dim, sp.D);  // before the first launch, in every phase: the phases agree
     if (p->causal_tail != 0 && p->causal_tail != 1) return fail(HYD_ERR_BAD_ARG, "causal_tail %d", p->causal_tail);
-    const bool causal = p->causal_tail != 0;
-    if (causal && (rc = check_causal_tail(&sp, kq))) return rc;  // in every phase, so that the phases of one call agree
-    if (causal && sp.kv_len > 0) {  // ... and so is a shape no kernel with the per-row key limit takes: before the level passes go out
-        SuffixArgs ca;
-        fill_suffix_args(&sp, &ca);
-        if (!causal_eligible(ca, sp.D, kq)) return fail_causal_shapes();
-    }
+    if (causal && (rc = check_causal_tail(&sp, kq))) return rc;
+    if (u.causal && !u.causal_native) return fail_causal_shapes();  // (u.causal: the causal tail over unique keys)
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t rows = (size_t)sp.B * sp.nq * sp.Hq;
     const bool do_shared = p->phase == HYD_PHASE_ALL || p->phase == HYD_PHASE_SHARED;
     const bool do_unique = p->phase == HYD_PHASE_ALL || p->phase == HYD_PHASE_UNIQUE;
-    DecodePlan d;
-    plan_decode(p, &d);
     // The two-stream form needs both a shared and a unique part; without one of them the in-order phases already are
     // the whole operator (the caller asks hyd_decode_two_stream_ok first).
     if (d.form == kTwoStream && !d.two_stream_ok)
@@ -721,19 +716,19 @@ static int decode_impl(const hyd_decode_params* p, const hyd_kv_quant* kq, void*
     if (d.form == kOneLaunch && !kq) {
         // launch latency, not work: the grouped-query kernel walks the group's shared keys, then the sequence's own
         const hyd_prefix_params& pp = d.level[0].pp;
-        SuffixArgs a;
-        fill_suffix_args(&sp, &a);
+        SuffixArgs& a = d.suffix.args;  // (the planned arguments, plus the shared segment)
         a.pk = pp.k; a.pv = pp.v;
         a.pk_gs = pp.k_group_stride; a.pk_hs = pp.k_head_stride;
         a.pv_gs = pp.v_group_stride; a.pv_hs = pp.v_head_stride;
-        a.p_len = pp.kv_len;
-        a.p_per = sp.B / pp.sb;
+        a.p_len = pp.kv_len; a.p_per = sp.B / pp.sb;
         a.shared_kv = 1;  // p_per sequences read the same prefix keys: default cache policy, not the read-once hint
         return launched(launch_suffix_gqa(a, sp.dtype, sp.D, s), "single-launch decode kernel");
     }
     const size_t need = d.levels_bytes + (two_stream ? d.unique.bytes : 0);
     if (need > 0 && (!p->workspace || p->workspace_bytes < need))
         return fail(HYD_ERR_WORKSPACE, "decode needs %zu workspace bytes, got %zu", need, p->workspace_bytes);
+    // what the unique pass of this call would refuse by its shapes: known now, so said before the level passes go out
+    if ((do_unique || p->phase == HYD_PHASE_UNIQUE_PARTIAL) && (rc = check_suffix_limits(u))) return rc;
 
     hyd_partial parts[HYD_MAX_LEVELS];
     char* ws = static_cast<char*>(p->workspace);
@@ -761,10 +756,9 @@ static int decode_impl(const hyd_decode_params* p, const hyd_kv_quant* kq, void*
         char* u_out = static_cast<char*>(p->workspace) + d.levels_bytes;
         float* u_lse = reinterpret_cast<float*>(u_out + d.unique.lse_base);
         if (p->phase == HYD_PHASE_UNIQUE_PARTIAL) {
-            hyd_suffix_params su = sp;
-            su.out = u_out;
-            su.lse = u_lse;
-            return run_suffix(&su, nullptr, 0, s, kq, causal);
+            d.suffix.args.out = u_out;
+            d.suffix.args.lse = u_lse;
+            return run_suffix(u, nullptr, 0, s);
         }
         CombineArgs c;  // HYD_PHASE_MERGE: every level's partial(s) + the unique partial -> out
         memset(&c, 0, sizeof(c));
@@ -787,20 +781,24 @@ static int decode_impl(const hyd_decode_params* p, const hyd_kv_quant* kq, void*
         return launched(launch_combine(c, s), "combine kernel launch");
     }
     if (!do_unique) return HYD_OK;
-    if (sp.kv_len == 0) {
-        // several levels, no unique keys: merge the level partials only (suffix contributes lse = -inf)
-        hyd_suffix_params s0 = sp;
-        s0.seq_lens_i32 = nullptr;
-        s0.seq_lens_i64 = nullptr;
-        return run_suffix(&s0, parts, p->n_levels, s);
-    }
-    return run_suffix(&sp, parts, p->n_levels, s, kq, causal);
+    // (several levels and no unique keys: the plan is the merge-only pass, whose suffix contributes lse = -inf)
+    return run_suffix(u, parts, p->n_levels, s);
+}
+
+int hyd_decode_attn_fused(const hyd_decode_params* p, void* stream) { return decode_impl(p, nullptr, stream); }
+
+int hyd_decode_attn_fused_kvq(const hyd_decode_params* p, const hyd_kv_quant* kq, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    int rc = check_suffix(&p->suffix);
+    if (rc) return rc;
+    if ((rc = check_kvq(&kq, p->suffix.dtype))) return rc;
+    return decode_impl(p, p->suffix.kv_len > 0 ? kq : nullptr, stream);  // kv_len == 0 reads no unique key and takes the existing path
 }
 
 int hyd_decode_two_stream_ok(const hyd_decode_params* p) {
     if (!p || !levels_in_range(p)) return 0;
     DecodePlan d;
-    plan_decode(p, &d);
+    plan_levels(p, &d);
     return d.two_stream_ok ? 1 : 0;
 }
 

@@ -6,11 +6,15 @@ recorded once and compared exactly (tests/test_abi_table.py against tests/golden
 The fixture is a recording of the library BEFORE a change to csrc/api_*.hip (the C ABI layer), not a product of the code under test: record it from
 the parent commit, commit it as data, and let the changed library answer to it.
 
-Three kinds of case.  A "query" never launches (plans, workspace sizes, support answers).  A "refusal" goes through a launch entry
+Four kinds of case.  A "query" never launches (plans, workspace sizes, support answers).  A "refusal" goes through a launch entry
 point with made-up addresses and must come back with an error before anything is enqueued: its record is the return code and the
 whole error string.  A "noop" goes through a launch entry point as well and must come back with HYD_OK before any HIP call (an empty
-batch, an empty destination, a phase with nothing left to do): its record is the return code alone.  --write records nothing when a
-refusal is accepted (HYD_OK) or tries to launch (HYD_ERR_LAUNCH), or when a noop does not answer HYD_OK.
+batch, an empty destination, a phase with nothing left to do): its record is the return code alone.  A "launch" is a call that is
+ACCEPTED: where no device is present its first launch comes back as HYD_ERR_LAUNCH with "<what> failed: hip error N", and <what> names
+the launcher the call reached -- its record is the return code and <what> (N belongs to the runtime, not to the project).  Launch cases
+run only where no device is present: on one they would run kernels on made-up addresses.  --write records nothing when a
+refusal is accepted (HYD_OK) or tries to launch (HYD_ERR_LAUNCH), when a noop does not answer HYD_OK, or when a launch case does not
+answer HYD_ERR_LAUNCH.
 """
 import ctypes as C
 import json
@@ -307,6 +311,12 @@ def _q_decode(lib, kw):
     return rec
 
 
+def _q_decode_kvq(lib, kw):
+    """hyd_decode_kv_quant_supported under every combination of hyd_kv_quant.flags (the causal tail reads HYD_KVQ_CAUSAL)."""
+    d = decode(**kw)
+    return {f"supported_flags_{f}": lib.hyd_decode_kv_quant_supported(C.byref(d), C.byref(kvq(flags=f))) for f in (0, 1, 2, 3)}
+
+
 def _q_workspace(lib, kw):
     sb = [lv[0] for lv in kw["levels"]]
     ln = [lv[1] for lv in kw["levels"]]
@@ -413,7 +423,24 @@ def _r_accept_states(lib, kw):
     return _refusal(lib, lib.hyd_draft_accept_states(p, after, state, None))
 
 
-QUERIES = {"prefix": _q_prefix, "decode": _q_decode, "workspace": _q_workspace, "kv_quant": _q_kvq, "null": _q_null,
+_FAILED = " failed: hip error "
+
+
+def _launch(rec):
+    """A refusal runner's answer -> the record of a launch case: the code and the name of the launch that was reached."""
+    what, sep, _ = rec["error"].partition(_FAILED)
+    if rec["rc"] != HYD_ERR_LAUNCH or not sep:
+        return rec  # not a launch: the whole answer, which no recorded launch equals
+    return {"rc": rec["rc"], "what": what}
+
+
+def device_present():
+    import torch
+
+    return torch.cuda.is_available()
+
+
+QUERIES = {"prefix": _q_prefix, "decode": _q_decode, "decode_kvq": _q_decode_kvq, "workspace": _q_workspace, "kv_quant": _q_kvq, "null": _q_null,
            "allreduce_block": _q_block, "narrow_kv": _q_narrow, "linear_w8_workspace": _q_w8_workspace}
 REFUSALS = {
     "hyd_prefix_attn_fwd": _params_runner("hyd_prefix_attn_fwd", lambda **kw: prefix(ptrs=True, **kw)),
@@ -434,6 +461,7 @@ REFUSALS = {
     "hyd_combine_lse": _r_combine,
     "hyd_allreduce_sum": _r_allreduce,
     "hyd_suffix_attn_causal_fwd": _params_runner("hyd_suffix_attn_causal_fwd", lambda **kw: suffix(**{"nq": 2, **kw})),
+    "hyd_suffix_attn_causal_fwd_kvq": _params_runner("hyd_suffix_attn_causal_fwd_kvq", lambda **kw: suffix(**{"nq": 2, **kw}), with_kq=True),
     "hyd_rope_append_multi": _params_runner("hyd_rope_append_multi", rope_multi),
     "hyd_sample_tokens_constrained": _r_constrained,
     "hyd_draft_lookup": _params_runner("hyd_draft_lookup", draft_lookup),
@@ -450,7 +478,7 @@ REFUSALS = {
 }
 
 # ---- the cases: (kind, entry, arguments) ------------------------------------------------------------------------------------
-_Q, _R, _N = [], [], []
+_Q, _R, _N, _L = [], [], [], []
 
 
 def q(entry, **kw):
@@ -464,6 +492,11 @@ def r(entry, **kw):
 def noop(entry, **kw):
     """A call that returns HYD_OK before any HIP call (through the entry's refusal runner); its record is the return code alone."""
     _N.append((entry, kw))
+
+
+def launch(entry, **kw):
+    """A call that is accepted (through the entry's refusal runner): without a device its record is HYD_ERR_LAUNCH and the launch reached."""
+    _L.append((entry, kw))
 
 
 def chain(entry, steps, pairs=True, **base):
@@ -1008,6 +1041,100 @@ noop("hyd_allreduce_sum", count=0)
 noop("hyd_allreduce_sum", count=0, in_=None, out=None)
 noop("hyd_decode_attn_fused", kv_len=0, phase=_lib.HYD_PHASE_UNIQUE)
 
+# ---- the unique pass: which launch an accepted call reaches, on each side of every seam between two suffix kernels -----------------
+_ONE = {"n_partials": 1, "partials.0.out": PTR, "partials.0.lse": PTR, "partials.0.count": 1}
+_GQ = dict(Hq=32, Hkv=8)
+_ALL, _UNIQUE, _PARTIAL, _MERGE = _lib.HYD_PHASE_ALL, _lib.HYD_PHASE_UNIQUE, _lib.HYD_PHASE_UNIQUE_PARTIAL, _lib.HYD_PHASE_MERGE
+_GQA, _CAUSAL = _lib.HYD_KVQ_GQA, _lib.HYD_KVQ_CAUSAL
+# 16-bit caches: one-row units, 2-row units, grouped-query units, the other head dims, narrow rows
+_SHAPES16 = (dict(), dict(Hq=16, Hkv=8), _GQ, dict(D=64), dict(D=256), dict(D=256, **_GQ), dict(kv_dim=96), dict(kv_dim=96, Hq=4, Hkv=4))
+# fp8 caches: (hyd_kv_quant, shape) -- one-row units with and without HYD_KVQ_GQA, grouped-query units with it
+_SHAPES8 = ((dict(), dict()), (dict(flags=_GQA), dict()), (dict(flags=_GQA), _GQ), (dict(flags=_GQA | _CAUSAL), _GQ), (dict(), dict(D=64)),
+            (dict(flags=_GQA), dict(D=256, **_GQ)))
+# the causal tail: 2-row units, grouped-query units, the most query tokens, head dim 256
+_SHAPES_CAUSAL = (dict(), _GQ, dict(nq=8), dict(nq=8, **_GQ), dict(D=256), dict(D=64))
+_SAME_DTYPE = dict(kv_dtype=1)   # a hyd_kv_quant that names the q dtype: 16-bit caches through the _kvq entry points
+
+for shape in _SHAPES16:
+    launch("hyd_suffix_attn_fwd", **shape)
+launch("hyd_suffix_attn_fwd", kv_len=0, **_ONE)       # merge-only
+launch("hyd_suffix_attn_fwd", **_ONE)
+launch("hyd_suffix_attn_fwd_kvq", kq=None)
+launch("hyd_suffix_attn_fwd_kvq", kq=_SAME_DTYPE, **_GQ)
+for kq, shape in _SHAPES8:
+    launch("hyd_suffix_attn_fwd_kvq", kq=kq, **shape)
+launch("hyd_suffix_attn_fwd_kvq", kq=dict(), **_ONE)
+launch("hyd_suffix_attn_fwd_kvq", kq=dict(), kv_len=0, **_ONE)                 # no unique key to read
+launch("hyd_suffix_attn_fwd_kvq", kq=dict(flags=_GQA), kv_len=0, **_GQ, **_ONE)
+r("hyd_suffix_attn_fwd_kvq", kq=dict(), kv_len=0, Hq=4, Hkv=2, **_ONE)
+
+for shape in _SHAPES_CAUSAL:
+    launch("hyd_suffix_attn_causal_fwd", **shape)
+    launch("hyd_suffix_attn_causal_fwd_kvq", kq=_SAME_DTYPE, **shape)
+launch("hyd_suffix_attn_causal_fwd", kv_len=0, **_ONE)
+launch("hyd_suffix_attn_causal_fwd_kvq", kq=None)
+for flags in (_CAUSAL, _GQA | _CAUSAL):
+    for shape in (dict(), _GQ, dict(nq=8, **_GQ), dict(D=256, **_GQ)):   # (the fp8 causal kernel also takes the 2-row units)
+        launch("hyd_suffix_attn_causal_fwd_kvq", kq=dict(flags=flags), **shape)
+launch("hyd_suffix_attn_causal_fwd_kvq", kq=dict(flags=_GQA | _CAUSAL), kv_len=0, **_ONE)   # no unique key: the 16-bit call
+r("hyd_suffix_attn_causal_fwd_kvq", null=True)
+# fp8 caches and no HYD_KVQ_CAUSAL: this entry point answers for the causal tail, on shapes the fp8 kernels take and on others alike ...
+for kq in (dict(), dict(flags=_GQA)):
+    for shape in (_GQ, dict(), dict(nq=9), dict(kv_len=0, **_ONE)):
+        r("hyd_suffix_attn_causal_fwd_kvq", kq=kq, **shape)
+r("hyd_suffix_attn_causal_fwd_kvq", kq=dict(flags=_GQA | _CAUSAL), kv_dim=96)
+r("hyd_suffix_attn_causal_fwd_kvq", kq=dict(flags=_GQA | _CAUSAL), Hq=8, Hkv=1, D=256, kv_len=200)   # head dim 256 on few units
+# ... the decode call for the fp8 shapes first (2-row units are not native without the causal kernel)
+for kq in (dict(), dict(flags=_GQA)):
+    r("hyd_decode_attn_fused_kvq", kq=kq, causal_tail=1, nq=2)
+r("hyd_decode_attn_fused_kvq", kq=dict(), causal_tail=1, nq=2, **_GQ)
+r("hyd_decode_attn_fused_kvq", kq=dict(flags=_GQA | _CAUSAL), causal_tail=1, nq=2, Hq=8, Hkv=1, D=256, kv_len=200)
+
+# the decode call: every route with the unique pass as the first launch (HYD_PHASE_UNIQUE), then the other phases and forms
+_ONE_LAUNCH = dict(B=8, Hq=32, Hkv=8, kv_len=32, levels=((1, 96),), single_launch_small=1)
+_NOT_ONE_LAUNCH = (dict(kv_len=33), {"suffix.lse": PTR}, dict(levels=((1, 96, 512),)), dict(single_launch_small=0), dict(phase=_UNIQUE))
+_DECODE_FORMS = (dict(phase=_PARTIAL), dict(phase=_MERGE), dict(phase=_ALL), dict(phase=_ALL, levels=((1, 4096),)),
+                 dict(phase=_ALL, B=96, Hq=8, Hkv=2, levels=((1, 2048), (4, 96))), dict(kv_len=0), dict(kv_len=0, levels=((1, 4096),)),
+                 dict(kv_len=0, phase=_UNIQUE, levels=((1, 64), (2, 64))), dict(kv_len=0, phase=_ALL, levels=((1, 64), (2, 64))),
+                 dict(phase=_UNIQUE, levels=()), dict(phase=_ALL, levels=()))
+for entry, kq in (("hyd_decode_attn_fused", {}), ("hyd_decode_attn_fused_kvq", dict(kq=_SAME_DTYPE))):
+    for shape in _SHAPES16:
+        launch(entry, phase=_UNIQUE, **kq, **{("suffix.kv_dim" if k == "kv_dim" else k): v for k, v in shape.items()})
+    for form in _DECODE_FORMS:
+        launch(entry, **kq, **form)
+    launch(entry, **kq, **_ONE_LAUNCH)
+    for near in _NOT_ONE_LAUNCH:
+        launch(entry, **kq, **{**_ONE_LAUNCH, **near})
+    launch(entry, **kq, **_ONE_LAUNCH, causal_tail=1, nq=2)   # (the walk over both segments has no per-row key limit)
+    for shape in _SHAPES_CAUSAL:
+        launch(entry, phase=_UNIQUE, causal_tail=1, **kq, **{"nq": 2, **shape})
+    launch(entry, phase=_PARTIAL, causal_tail=1, nq=2, **kq)
+    launch(entry, phase=_UNIQUE, causal_tail=1, nq=2, kv_len=0, levels=((1, 64), (2, 64)), **kq)
+r("hyd_decode_attn_fused", **{**_ONE_LAUNCH, "levels": ((3, 96),)})
+for kq, shape in _SHAPES8:
+    launch("hyd_decode_attn_fused_kvq", kq=kq, phase=_UNIQUE, **shape)
+for form in _DECODE_FORMS:
+    launch("hyd_decode_attn_fused_kvq", kq=dict(), **{**form, "Hq": 8, "Hkv": 8})
+    launch("hyd_decode_attn_fused_kvq", kq=dict(flags=_GQA), **{**_GQ, **form})
+for near in _NOT_ONE_LAUNCH[:3] + _NOT_ONE_LAUNCH[4:]:
+    launch("hyd_decode_attn_fused_kvq", kq=dict(flags=_GQA), **{**_ONE_LAUNCH, **near})
+r("hyd_decode_attn_fused_kvq", kq=dict(), **_ONE_LAUNCH)                     # without HYD_KVQ_GQA these shapes are not native ...
+launch("hyd_decode_attn_fused_kvq", kq=dict(), **{**_ONE_LAUNCH, "Hq": 8})   # ... and Hq == Hkv shapes ignore single_launch_small
+for flags in (_CAUSAL, _GQA | _CAUSAL):
+    for shape in (dict(), _GQ, dict(nq=8, **_GQ), dict(D=256, **_GQ)):
+        launch("hyd_decode_attn_fused_kvq", kq=dict(flags=flags), phase=_UNIQUE, causal_tail=1, **{"nq": 2, **shape})
+launch("hyd_decode_attn_fused_kvq", kq=dict(flags=_GQA | _CAUSAL), phase=_PARTIAL, causal_tail=1, nq=2, **_GQ)
+launch("hyd_decode_attn_fused_kvq", kq=dict(flags=_GQA | _CAUSAL), causal_tail=1, nq=2, **_ONE_LAUNCH)
+launch("hyd_decode_attn_fused_kvq", kq=dict(), phase=_UNIQUE, causal_tail=1, nq=2, kv_len=0, levels=((1, 64), (2, 64)))
+
+# hyd_decode_kv_quant_supported under every hyd_kv_quant.flags: the causal tail's answer follows the launch's own rules
+for ct in (0, 1, 2):
+    for shape in (dict(), _GQ, dict(nq=2), dict(nq=2, **_GQ), dict(nq=8, **_GQ), dict(nq=9, **_GQ), dict(nq=2, D=256), dict(nq=2, D=64),
+                  dict(nq=2, Hq=8, Hkv=1, D=256, kv_len=200), dict(nq=2, kv_len=0), dict(nq=2, kv_len=-1), {"nq": 2, "suffix.kv_dim": 96},
+                  {"suffix.kv_dim": 96}, dict(nq=2, D=96), dict(nq=2, n_levels=9), dict(nq=2, kv_len=1 << 21), dict(nq=2, Hq=8, Hkv=3),
+                  dict(nq=2, **_ONE_LAUNCH), _ONE_LAUNCH):
+        q("decode_kvq", causal_tail=ct, **shape)
+
 
 def _case_id(kind, entry, kw):
     return f"{kind}:{entry}:" + json.dumps(kw, sort_keys=True, default=str)
@@ -1016,7 +1143,8 @@ def _case_id(kind, entry, kw):
 QUERY_CASES = [(_case_id("query", e, kw), e, kw) for e, kw in _Q]
 REFUSAL_CASES = [(_case_id("refusal", e, kw), e, kw) for e, kw in _R]
 NOOP_CASES = [(_case_id("noop", e, kw), e, kw) for e, kw in _N]
-_ids = [c[0] for c in QUERY_CASES + REFUSAL_CASES + NOOP_CASES]
+LAUNCH_CASES = [(_case_id("launch", e, kw), e, kw) for e, kw in _L]
+_ids = [c[0] for c in QUERY_CASES + REFUSAL_CASES + NOOP_CASES + LAUNCH_CASES]
 assert len(set(_ids)) == len(_ids), sorted(i for i in set(_ids) if _ids.count(i) > 1)
 
 
@@ -1026,6 +1154,9 @@ def run_case(case):
     lib = _lib.load()
     if cid.startswith("query:"):
         return QUERIES[entry](lib, kw)
+    if cid.startswith("launch:"):
+        assert not device_present(), "launch cases run where no device is present only: they would launch on made-up addresses"
+        return _launch(REFUSALS[entry](lib, kw))
     rec = REFUSALS[entry](lib, kw)
     return {"rc": rec["rc"]} if cid.startswith("noop:") else rec  # (the error string is not cleared on success)
 
@@ -1035,6 +1166,8 @@ def load_fixture():
 
 
 def write():
+    if device_present():
+        raise SystemExit("record the table where no device is present: a launch case would run a kernel on made-up addresses")
     table = {}
     for case in QUERY_CASES:
         table[case[0]] = run_case(case)
@@ -1049,10 +1182,15 @@ def write():
         if rec["rc"] != HYD_OK:
             wrong.append(f"{case[0]}: the library answers {rec['rc']} ({_err(_lib.load())!r}): not a call that returns HYD_OK")
         table[case[0]] = rec
+    for case in LAUNCH_CASES:
+        rec = run_case(case)
+        if set(rec) != {"rc", "what"}:
+            wrong.append(f"{case[0]}: the library answers {rec['rc']} ({rec['error']!r}): not a launch that fails for want of a device")
+        table[case[0]] = rec
     if wrong:
         raise SystemExit("\n".join(wrong) + "\nnothing recorded")
     FIXTURE.write_text(json.dumps(table, indent=0, sort_keys=True) + "\n")
-    print(f"{FIXTURE}: {len(QUERY_CASES)} queries, {len(REFUSAL_CASES)} refusals, {len(NOOP_CASES)} no-ops")
+    print(f"{FIXTURE}: {len(QUERY_CASES)} queries, {len(REFUSAL_CASES)} refusals, {len(NOOP_CASES)} no-ops, {len(LAUNCH_CASES)} launches")
 
 
 if __name__ == "__main__":
