@@ -364,6 +364,9 @@ EXPORTS = {
     "hyd_dfa_forced_tokens": (C.c_int, [C.POINTER(DfaForcedParams), C.c_void_p]),
     "hyd_draft_constrain": (C.c_int, [C.POINTER(DraftConstrainParams), C.c_void_p]),
     "hyd_draft_accept_states": (C.c_int, [C.POINTER(DraftAcceptParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hyd_draft_accept_stop": (C.c_int, [C.POINTER(DraftAcceptParams), C.POINTER(StopParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int32, C.c_void_p]),
+    "hyd_sample_tokens_penalized_drafts": (C.c_int, [C.POINTER(SamplePenaltyParams), C.c_void_p, C.c_int32, C.c_void_p]),
     "hyd_linear_w8_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "hyd_linear_w8": (C.c_int, [C.POINTER(LinearW8Params), C.c_void_p]),
     "hyd_weight_widen": (C.c_int, [C.POINTER(WeightWidenParams), C.c_void_p]),

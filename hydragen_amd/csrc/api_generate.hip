@@ -131,4 +131,31 @@ int hyd_draft_accept_states(const hyd_draft_accept_params* p, const int32_t* ste
     return launched(launch_draft_accept_states(*p, step_state_after, state, static_cast<hipStream_t>(stream)), "draft_accept kernel launch");
 }
 
+int hyd_draft_accept_stop(const hyd_draft_accept_params* p, const hyd_stop_params* stop, const int32_t* step_state_after, int32_t* state,
+                          int32_t* gen, int32_t* gen_len, int32_t gen_stride, void* stream) {
+    int rc = check_draft_accept(p);
+    if (rc) return rc;
+    if ((step_state_after == nullptr) != (state == nullptr)) return fail(HYD_ERR_BAD_ARG, "step_state_after and state go together: one of them is null");
+    if ((rc = check_elem_align({{step_state_after, 4, "step_state_after"}, {state, 4, "state"}}))) return rc;
+    const int n_stop = stop ? stop->n_stop : 0;
+    if (n_stop < 0 || n_stop > HYD_STOP_MAX_SEQS) return fail(HYD_ERR_BAD_ARG, "n_stop %d: 0 to %d stop sequences", n_stop, HYD_STOP_MAX_SEQS);
+    if (n_stop > 0 && !stop->stop_tokens) return fail(HYD_ERR_BAD_ARG, "n_stop %d needs stop_tokens (null)", n_stop);
+    for (int k = 0; k < n_stop; ++k)
+        if (stop->stop_lens[k] < 1 || stop->stop_lens[k] > HYD_STOP_MAX_LEN)
+            return fail(HYD_ERR_BAD_ARG, "stop_lens[%d] = %d: a stop sequence holds 1 to %d tokens", k, stop->stop_lens[k], HYD_STOP_MAX_LEN);
+    if ((gen == nullptr) != (gen_len == nullptr)) return fail(HYD_ERR_BAD_ARG, "gen and gen_len go together (one of them is null)");
+    if (gen_stride < 0 || gen_stride > HYD_SAMPLE_GEN_MAX) return fail(HYD_ERR_BAD_ARG, "gen_stride %d outside [0, %d]", gen_stride, HYD_SAMPLE_GEN_MAX);
+    if ((rc = check_elem_align({{n_stop > 0 ? stop->stop_tokens : nullptr, 8, "stop_tokens"}, {gen, 4, "gen"}, {gen_len, 4, "gen_len"}}))) return rc;
+    if (n_stop == 0 && !gen)  // nothing of this call's own is asked for: it IS the existing call
+        return launched(state ? launch_draft_accept_states(*p, step_state_after, state, static_cast<hipStream_t>(stream))
+                              : launch_draft_accept(*p, static_cast<hipStream_t>(stream)), "draft_accept kernel launch");
+    DraftStopArgs s;
+    memset(&s, 0, sizeof(s));
+    s.stop_tokens = n_stop > 0 ? stop->stop_tokens : nullptr;
+    s.gen = gen; s.gen_len = gen_len; s.gen_stride = gen_stride;
+    for (int k = 0; k < n_stop; ++k) s.stop_lens[k] = stop->stop_lens[k];
+    s.n_stop = n_stop; s.include_stop = (stop && stop->include_stop) ? 1 : 0;
+    return launched(launch_draft_accept_stop(*p, s, step_state_after, state, static_cast<hipStream_t>(stream)), "draft_accept_stop kernel launch");
+}
+
 }  // extern "C"

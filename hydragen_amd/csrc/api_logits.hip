@@ -140,6 +140,18 @@ int hyd_sample_tokens_penalized(const hyd_sample_penalty_params* p, void* stream
     return rc ? rc : launched(launch_sample_penalty(a, p->dtype, static_cast<hipStream_t>(stream)), "sample_penalty kernel launch");
 }
 
+int hyd_sample_tokens_penalized_drafts(const hyd_sample_penalty_params* p, const int64_t* fed, int32_t T, void* stream) {
+    PenaltyArgs a;
+    int rc = fill_penalty_args(p, &a);
+    if (rc) return rc;
+    if (T < 1 || T > 8) return fail(HYD_ERR_BAD_ARG, "T = %d tokens per sequence: 1 to 8 are taken", T);
+    if (p->rows % T != 0) return fail(HYD_ERR_BAD_ARG, "rows %d is not a multiple of T = %d", p->rows, T);
+    if (p->append_out) return fail(HYD_ERR_BAD_ARG, "append_out: the lists of a speculative step are kept by hyd_draft_accept_stop, not by the sampler");
+    if (p->gen && !fed) return fail(HYD_ERR_BAD_ARG, "gen needs fed (null): the drafts in front of a position count as generated tokens");
+    if ((rc = check_elem_align({{fed, 8, "fed"}}))) return rc;
+    return launched(launch_sample_penalty_drafts(a, fed, T, p->dtype, static_cast<hipStream_t>(stream)), "sample_penalty_drafts kernel launch");
+}
+
 int hyd_sample_tokens_constrained(const hyd_sample_penalty_params* p, const hyd_token_dfa* c, void* stream) {
     if (!c) return hyd_sample_tokens_penalized(p, stream);
     PenaltyArgs a;

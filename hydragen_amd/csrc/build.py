@@ -14,7 +14,7 @@ from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 HERE = Path(__file__).resolve().parent
-SOURCES = ["api_core.hip", "api_attn.hip", "api_layer.hip", "api_logits.hip", "api_generate.hip", "api_kv.hip", "api_comm.hip", "prefix_attn_w64.hip", "prefix_attn_w64_f16.hip", "suffix_attn.hip", "suffix_attn_fp8.hip", "suffix_attn_gqa.hip", "suffix_attn_gqa_fp8.hip", "suffix_attn_gqa_fp8_causal.hip", "suffix_attn_causal.hip", "draft_lookup.hip", "draft_accept.hip", "draft_constrain.hip", "combine.hip", "rope_append.hip", "layer_ops.hip", "sample_filter.hip", "sample_penalty.hip", "sample_constrain.hip", "sample_rows.hip", "token_logprob.hip", "stop_update.hip", "kv_promote.hip", "kv_gather.hip", "kv_scale.hip", "linear_w8.hip", "allreduce.hip"]
+SOURCES = ["api_core.hip", "api_attn.hip", "api_layer.hip", "api_logits.hip", "api_generate.hip", "api_kv.hip", "api_comm.hip", "prefix_attn_w64.hip", "prefix_attn_w64_f16.hip", "suffix_attn.hip", "suffix_attn_fp8.hip", "suffix_attn_gqa.hip", "suffix_attn_gqa_fp8.hip", "suffix_attn_gqa_fp8_causal.hip", "suffix_attn_causal.hip", "draft_lookup.hip", "draft_accept.hip", "draft_accept_stop.hip", "draft_constrain.hip", "combine.hip", "rope_append.hip", "layer_ops.hip", "sample_filter.hip", "sample_penalty.hip", "sample_penalty_drafts.hip", "sample_constrain.hip", "sample_rows.hip", "token_logprob.hip", "stop_update.hip", "kv_promote.hip", "kv_gather.hip", "kv_scale.hip", "linear_w8.hip", "allreduce.hip"]
 HEADERS = sorted(h.name for h in HERE.glob("*.h")) + ["../../include/hydragen_hip.h"]
 LIB = HERE / "libhydragen_hip.so"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

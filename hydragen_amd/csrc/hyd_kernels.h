@@ -252,6 +252,14 @@ struct StopArgs {  // stop_update.hip: EOS ids / stop sequences judged per row, 
     const int32_t* max_len;      // [rows] or null: a row's own token limit (hyd_stop_update_rows)
 };
 
+struct DraftStopArgs {  // draft_accept_stop.hip: what hyd_draft_accept_stop reads beside hyd_draft_accept_params
+    const int64_t* stop_tokens;  // [n_stop, HYD_STOP_MAX_LEN] or null
+    int32_t* gen;                // [rows, gen_stride] or null: the penalties' per-sequence token lists
+    int32_t* gen_len;
+    int32_t stop_lens[HYD_STOP_MAX_SEQS];
+    int32_t n_stop, include_stop, gen_stride, reserved;
+};
+
 struct KvPromoteArgs {  // kv_promote.hip: chosen rows of the unique K/V caches -> a packed shared level (hyd_kv_promote)
     const void* k_src;
     const void* v_src;
@@ -368,6 +376,9 @@ int launch_suffix_causal(const SuffixArgs& a, int dtype, int D, hipStream_t s); 
 int launch_draft_lookup(const hyd_draft_lookup_params& p, hipStream_t s);             // draft_lookup.hip
 int launch_draft_accept(const hyd_draft_accept_params& p, hipStream_t s);             // draft_accept.hip
 int launch_draft_accept_states(const hyd_draft_accept_params& p, const int32_t* step_state_after, int32_t* state, hipStream_t s);
+int launch_draft_accept_stop(const hyd_draft_accept_params& p, const DraftStopArgs& s, const int32_t* step_state_after, int32_t* state,
+                             hipStream_t st);                                          // draft_accept_stop.hip (state null: no states)
+int launch_sample_penalty_drafts(const PenaltyArgs& a, const int64_t* fed, int T, int dtype, hipStream_t s);  // sample_penalty_drafts.hip
 int launch_dfa_forced(const hyd_dfa_forced_params& p, hipStream_t s);                 // draft_constrain.hip
 int launch_draft_constrain(const hyd_draft_constrain_params& p, hipStream_t s);       // draft_constrain.hip
 int launch_combine(const CombineArgs& a, hipStream_t s);

@@ -22,10 +22,20 @@ def per_row_sampling(temperature, top_k=None, top_p=None, min_p=None, penalties=
 
 
 def draw_tokens(route: sampling.SampleRoute, logits, temperature, num_samples=1, top_p=None, top_k=None, min_p=None,
-                return_logprobs=False, penalties=None, constraint=None, seed=None, offset=0):
+                return_logprobs=False, penalties=None, constraint=None, seed=None, offset=0, drafts=None):
     """Run one draw along `route` (sampling.sample_route's table): (tokens [B, num_samples], their fp32 log-probs
-    [B, num_samples] or, for a draw in torch that needs none, None).  The other arguments are sample_from_logits'."""
+    [B, num_samples] or, for a draw in torch that needs none, None).  The other arguments are sample_from_logits'.
+    drafts = fed int64 [B, T]: the rows are the B * T logits rows of a speculative step; a PENALIZED route then draws through
+    hyd_sample_tokens_penalized_drafts, which counts the drafts in front of each position (the draft loop takes no other
+    penalised route)."""
     x, n = logits, num_samples
+    if drafts is not None and penalties is not None and penalties.active():
+        if route.draw != sampling.PENALIZED or route.torch_penalties or per_row_sampling(temperature, top_k, top_p, min_p, penalties, seed):
+            raise NotImplementedError("penalties in a speculative step are drawn by hyd_sample_tokens_penalized_drafts alone: scalar "
+                                      "values, no constraint, fused_penalties on")
+        tok, lp = layer_ops.sample_tokens(x if x.stride(-1) == 1 else x.contiguous(), temperature, top_k=top_k, top_p=top_p, min_p=min_p,
+                                          return_logprobs=True, penalties=penalties, drafts=drafts)
+        return tok.reshape(-1, 1), lp.reshape(-1, 1)
     if per_row_sampling(temperature, top_k, top_p, min_p, penalties, seed):
         # the per_row routes: one launch over one row per sample (the values and seeds are the batch rows'), rows a kernel cannot
         # take as they are made contiguous; CPU rows: the definition in torch (layer_ops.sample_tokens routes both)
@@ -179,12 +189,16 @@ def check_arguments(model, *, input_ids, starting_logits, num_return_sequences, 
     if draft_tokens:
         spec_draft = _check_draft(
             model, draft_tokens, draft, ngram, max_new_tokens,
-            {"repetition / presence / frequency penalties or logit_bias": sampling.penalties_active(*penalties),
-             "stop": stop is not None, "token_overrides": token_overrides is not None,
+            {"repetition / presence / frequency penalties or logit_bias together with constraint=":
+                 sampling.penalties_active(*penalties) and constraint is not None,
+             "stop together with constraint=": stop is not None and constraint is not None,
+             "token_overrides": token_overrides is not None,
              "top_logprobs": bool(top_logprobs), "return_logits": return_logits, "disable_hydragen": disable_hydragen,
              "disable_attention": disable_attention, "disable_hierarchy": disable_hierarchy},
             n_given=0 if input_ids is None else 1 if isinstance(input_ids, Tensor) else len(input_ids),
-            constrained=constraint is not None)
+            constrained=constraint is not None,
+            gpu_only={"repetition / presence / frequency penalties or logit_bias": sampling.penalties_active(*penalties),
+                      "stop": stop is not None})
         spec_draft.stats = return_draft_stats
         if eos_token_id is not None and not isinstance(eos_token_id, (list, tuple, Tensor)):
             eos_token_id = [eos_token_id]
@@ -225,15 +239,22 @@ def check_arguments(model, *, input_ids, starting_logits, num_return_sequences, 
         rows=rows or None, seeded=seed is not None)
 
 
-def _check_draft(model, draft_tokens, draft, ngram, max_new_tokens, refused: dict, n_given: int = 0, constrained: bool = False) -> _Draft:
+def _check_draft(model, draft_tokens, draft, ngram, max_new_tokens, refused: dict, n_given: int = 0, constrained: bool = False,
+                 gpu_only: Optional[dict] = None) -> _Draft:
     """generate()'s draft arguments, checked before any launch.  n_given: the prompt levels given to the call (each is a
     segment of the lookup's table, beside the generated tokens); constrained: the call has a constraint= (what
-    draft="constraint" proposes from)."""
+    draft="constraint" proposes from); gpu_only: what a speculative step carries in HIP kernels alone (stop sequences in
+    hyd_draft_accept_stop, penalties in hyd_sample_tokens_penalized_drafts)."""
     k = speculative.check_draft_tokens(draft_tokens)
     for what, on in refused.items():
         if on:
             raise NotImplementedError(f"draft_tokens cannot be combined with {what}: a speculative step draws and accepts "
                                       "several tokens per row in launches that do not carry it")
+    for what, on in (gpu_only or {}).items():
+        if on and not model.lm_head.weight.is_cuda:
+            raise NotImplementedError(f"draft_tokens with {what} is not implemented for a model on the CPU: a speculative step judges "
+                                      "and counts the several tokens it emits per row in HIP kernels (speculative.accept_stop_reference "
+                                      "/ sampling.draft_row_lists_reference state the rules in torch)")
     given = None
     only_forced = isinstance(draft, str) and draft == "constraint"
     if isinstance(draft, Tensor):
@@ -354,8 +375,10 @@ def decode(model, call: _DecodeCall, prefill_logits, shared, unique):
     if pen is not None and pen.gen is not None:  # (a bias alone keeps no list of generated tokens)
         # the list of generated tokens follows what is FED: the sampler appends its own draws unless overrides replace them
         # (or the first token fans out: one row of logits, `fan` rows of tokens)
+        # (a speculative step draws several positions per row and keeps some of them: there the sampler never appends, the
+        # accept writes the list -- the first token included, which enters through an accept of one token)
         call.pen = pen
-        pen.append = overrides is None and fan == 1
+        pen.append = overrides is None and fan == 1 and call.draft is None
     first = model.sample_from_logits(prefill_logits, num_samples=fan, **samp)
     if call.logprobs is not None:
         first, lp = first
@@ -374,7 +397,7 @@ def decode(model, call: _DecodeCall, prefill_logits, shared, unique):
         start = start + unique[1].long().repeat_interleave(fan, 0)[:, None]
     model._check_room(start, call.max_new_tokens, extra=call.draft.k if call.draft else 0)
     feed = first if overrides is None else overrides[:, 0:1]
-    if call.pen is not None and not pen.append:
+    if call.pen is not None and not pen.append and call.draft is None:
         pen.push(feed)
         pen.append = overrides is None
     model.set_mode(AttentionMode.DECODE)
@@ -536,10 +559,22 @@ def _decode_steps_draft(model, call: _DecodeCall, first, start):
     out, length, reason, stop_index, out_lp = speculative.new_state(B, mx, spec.pad, dev, want_lp)
     live = torch.zeros((mx,), dtype=torch.int32, device=dev)
     eos = spec.eos
+    # stop sequences and the penalties' token lists ride on the accept (hyd_draft_accept_stop): it judges every emitted token and
+    # is the one place that knows which draws became output.  Without either the calls are hyd_draft_accept(_states) as before.
+    extra = {}
+    if spec.stops:
+        extra.update(stop=spec, stop_tokens=spec.stop_table(dev)[0])
+    pen = call.pen
+    if pen is not None:
+        extra.update(gen=pen.gen, gen_len=pen.gen_len)
+    penalised = call.sample.get("penalties") is not None and call.sample["penalties"].active()
+    if penalised and (call.route.draw != sampling.PENALIZED or call.route.torch_penalties):
+        raise NotImplementedError("draft_tokens with penalties or logit_bias needs the fused penalty kernel (fused_penalties): the "
+                                  "draws of a speculative step count the drafts in front of them inside hyd_sample_tokens_penalized_drafts")
 
     def accept(fed, sampled, lp, slot, states=None):
         return speculative.draft_accept(fed, sampled, out, length, reason, stop_index, live[slot : slot + 1], start_pos, shared_len,
-                                        eos, spec.pad, mx, retire, lp, out_lp if lp is not None else None, states)
+                                        eos, spec.pad, mx, retire, lp, out_lp if lp is not None else None, states, **extra)
 
     # constraint=: the rows' automaton states (already advanced by the first draw) and, per step, the state behind every fed
     # token -- the sampler's state array over the step's B * T logits rows, advanced in place, then read by the accept
@@ -594,7 +629,7 @@ def _decode_steps_draft(model, call: _DecodeCall, first, start):
                 compare = torch.where(offs <= n_prop[:, None], fed, torch.full_like(fed, -1))
         proposed += room.clamp(max=K) if n_prop is None else torch.minimum(n_prop, room)
         logits = model(input_ids=fed, position_ids=pos[:, None] + offs, use_graph=call.graphed, full_logits=True, raw_logits=call.raw)
-        tok, lp = draw_tokens(call.route, logits.reshape(B * T, -1), **sample)
+        tok, lp = draw_tokens(call.route, logits.reshape(B * T, -1), **sample, **(dict(drafts=fed) if penalised else {}))
         feed, pos, acc = accept(compare, tok.reshape(B, T), lp.reshape(B, T).float() if want_lp else None, step, states)
         accepted += acc
         steps += 1

@@ -226,7 +226,8 @@ def token_bitmap(ids: Tensor, lens: Optional[Tensor], n: int, out: Optional[Tens
 
 
 def sample_tokens_penalized(logits: Tensor, temperature, key: Optional[tuple] = None, *, penalties: Penalties,
-                            top_k=None, top_p=None, min_p=None, constraint: Optional[tuple] = None, seed=None):
+                            top_k=None, top_p=None, min_p=None, constraint: Optional[tuple] = None, seed=None,
+                            drafts: Optional[Tensor] = None):
     """hyd_sample_tokens_penalized, one launch whatever the penalties are (neutral ones included): ([B, 1] int64 tokens, [B] fp32
     log-probs under softmax(penalised logits), [B] int32 number of kept tokens).  hydragen_amd/sampling.py states the
     definition.  Nothing of size [B, V] is allocated and nothing synchronises; the bias list must already be checked
@@ -237,12 +238,27 @@ def sample_tokens_penalized(logits: Tensor, temperature, key: Optional[tuple] = 
     scalar call with its values returns for it.  Per-row values reach the kernel as fp32 (top_k int32); they are checked on
     the host only where they are host values (lists), the kernel sanitises what it reads (include/hydragen_hip.h).  With seed=
     row r's noise is that of row 0 of a call with key = (seed[r], offset): its draw does not depend on its place in the batch,
-    and the device's generator is not advanced (key = (anything, offset); None: offset 0)."""
+    and the device's generator is not advanced (key = (anything, offset); None: offset 0).
+    drafts = fed int64 [B, T] (contiguous, on the device): hyd_sample_tokens_penalized_drafts -- the logits are the B * T rows of a
+    speculative step, penalties.gen / gen_len hold ONE list per sequence ([B, stride] / [B]), the context bitmaps cover B rows, and
+    the row behind fed[b, i] also counts the drafts fed[b, 1 .. i] (sampling.draft_row_lists_reference).  The sampler never
+    appends on this route, and neither per-row values nor a constraint are carried."""
     outs = _draw_outputs(logits, stats=True)
     rows, n = logits.shape
     dev, pen = logits.device, penalties
     if rows == 0:
         return outs
+    T = 1
+    if drafts is not None:
+        if (drafts.dtype != torch.int64 or drafts.ndim != 2 or not drafts.is_contiguous() or drafts.device != dev
+                or not 1 <= drafts.shape[1] <= 8 or drafts.numel() != rows):
+            raise ValueError(f"drafts must be the step's fed tokens, a contiguous int64 [B, T <= 8] with B * T = {rows} on {dev}, got "
+                             f"{tuple(drafts.shape)} {drafts.dtype}")
+        if constraint is not None or seed is not None or pen.append:
+            raise NotImplementedError("drafts= with a constraint, per-row seeds or an appending Penalties: "
+                                      "hyd_sample_tokens_penalized_drafts carries none of them")
+        T = drafts.shape[1]
+    seqs = rows // T
     check_filters(top_k, top_p, min_p)
     p = _lib.SamplePenaltyParams()
     words = (n + 31) // 32
@@ -250,16 +266,16 @@ def sample_tokens_penalized(logits: Tensor, temperature, key: Optional[tuple] = 
         raise ValueError(f"{len(pen.context)} context bitmaps: at most {_lib.SAMPLE_MAX_CONTEXT}")
     for i, (bits, rpg) in enumerate(pen.context):
         if (bits.dtype != torch.int32 or bits.ndim != 2 or bits.shape[1] != words or not bits.is_contiguous() or bits.device != dev
-                or rpg <= 0 or bits.shape[0] * rpg < rows):
-            raise ValueError(f"context bitmap {i}: int32 [groups, {words}] on {dev} with groups * rows_per_group >= {rows}, got "
+                or rpg <= 0 or bits.shape[0] * rpg < seqs):
+            raise ValueError(f"context bitmap {i}: int32 [groups, {words}] on {dev} with groups * rows_per_group >= {seqs}, got "
                              f"{tuple(bits.shape)} {bits.dtype} x {rpg}")
         p.context[i].bits, p.context[i].rows_per_group = bits.data_ptr(), int(rpg)
     p.n_context = len(pen.context)
     if pen.gen is not None:
         g, gl = pen.gen, pen.gen_len
-        if (g.dtype != torch.int32 or g.ndim != 2 or g.shape[0] != rows or not g.is_contiguous() or g.device != dev
-                or gl is None or gl.dtype != torch.int32 or gl.shape != (rows,) or gl.device != dev or not gl.is_contiguous()):
-            raise ValueError(f"gen must be int32 [{rows}, stride] and gen_len int32 [{rows}], contiguous on {dev}")
+        if (g.dtype != torch.int32 or g.ndim != 2 or g.shape[0] != seqs or not g.is_contiguous() or g.device != dev
+                or gl is None or gl.dtype != torch.int32 or gl.shape != (seqs,) or gl.device != dev or not gl.is_contiguous()):
+            raise ValueError(f"gen must be int32 [{seqs}, stride] and gen_len int32 [{seqs}], contiguous on {dev}")
         if g.shape[1] > _lib.SAMPLE_GEN_MAX:
             raise NotImplementedError(f"{g.shape[1]} generated tokens per row: the kernel counts up to {_lib.SAMPLE_GEN_MAX}")
         p.gen, p.gen_len, p.gen_stride = g.data_ptr(), gl.data_ptr(), g.shape[1]
@@ -277,6 +293,8 @@ def sample_tokens_penalized(logits: Tensor, temperature, key: Optional[tuple] = 
     arrays = [row_array(given[name], rows, dev, dtype, off, name) for name, dtype, off in ROW_FIELDS]
     arrays.append(row_array(seed, rows, dev, torch.int64, 0, "seed"))
     per_row = any(a is not None for a in arrays)
+    if per_row and drafts is not None:
+        raise NotImplementedError("drafts= with per-row sampling values: hyd_sample_tokens_penalized_drafts takes scalars")
     p.repetition_penalty = float(_scalar_or(pen.repetition_penalty, 1.0))
     p.frequency_penalty, p.presence_penalty = float(_scalar_or(pen.frequency_penalty, 0.0)), float(_scalar_or(pen.presence_penalty, 0.0))
     if seed is not None and key is None:
@@ -288,7 +306,9 @@ def sample_tokens_penalized(logits: Tensor, temperature, key: Optional[tuple] = 
         c = _lib.TokenDfa()
         c.allowed, c.next, c.state = dfa.allowed.data_ptr(), dfa.next.data_ptr(), state.data_ptr()
         c.allowed_stride, c.next_stride, c.n_states, c.advance = dfa.allowed.shape[1], n, dfa.next.shape[0], int(bool(advance))
-    if per_row:
+    if drafts is not None:
+        _lib.check(_lib.load().hyd_sample_tokens_penalized_drafts(C.byref(p), drafts.data_ptr(), T, _stream()))
+    elif per_row:
         _lib.check(_lib.load().hyd_sample_tokens_rows(C.byref(p), None if c is None else C.byref(c),
                                                      *(None if a is None else a.data_ptr() for a in arrays), _stream()))
     elif c is None:
@@ -316,7 +336,7 @@ def sample_tokens_constrained(logits: Tensor, temperature: float, key: Optional[
 
 def sample_tokens(logits: Tensor, temperature, key: Optional[tuple] = None, *, top_k=None, top_p=None, min_p=None,
                   return_logprobs: bool = False, penalties: Optional[Penalties] = None, constraint: Optional[tuple] = None,
-                  seed=None):
+                  seed=None, drafts: Optional[Tensor] = None):
     """[B, V] logits (fp16 / bf16 / fp32, rows contiguous) -> [B, 1] int64 tokens drawn from softmax(logits / temperature)
     (temperature 0: argmax) in one kernel.  top_k / top_p / min_p cut the UNSCALED softmax(logits) first (hydragen_amd/
     sampling.py states the rules); return_logprobs also returns the [B, 1] fp32 log softmax(logits) of each drawn token.
@@ -329,8 +349,16 @@ def sample_tokens(logits: Tensor, temperature, key: Optional[tuple] = None, *, t
     neutral penalties: exactly the calls made without them.
     Per-row values (temperature, the cuts, the penalties' scalars as lists or [B] tensors) or seed= (one integer per row):
     sample_route's per_row routes -- always a kernel on GPU rows, through hyd_sample_tokens_rows (sample_tokens_penalized says
-    what a row then returns); CPU rows: the per-row definition, sampling.reference_draw."""
+    what a row then returns); CPU rows: the per-row definition, sampling.reference_draw.
+    drafts = fed int64 [B, T]: the rows are the B * T logits rows of a speculative step and active penalties hold one list per
+    sequence -- hyd_sample_tokens_penalized_drafts (sample_tokens_penalized); without active penalties drafts changes nothing."""
     pen = penalties if penalties is not None and penalties.active() else None
+    if drafts is not None and pen is not None:
+        if not logits.is_cuda or constraint is not None:
+            raise NotImplementedError("drafts= with penalties: GPU rows without a constraint (hyd_sample_tokens_penalized_drafts)")
+        tok, lp, _ = sample_tokens_penalized(logits, temperature, key, penalties=pen, top_k=top_k, top_p=top_p, min_p=min_p, seed=seed,
+                                             drafts=drafts)
+        return (tok, lp[:, None]) if return_logprobs else tok
     cuts = dict(top_k=top_k, top_p=top_p, min_p=min_p)
     per_row = seed is not None or any(sampling.is_per_row(v) for v in (temperature, top_k, top_p, min_p)) or (pen is not None and pen.per_row())
     draw = sampling.sample_route(logits.is_cuda, True, True, 1, constraint is not None, pen is not None,

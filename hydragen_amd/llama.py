@@ -1435,7 +1435,13 @@ class HydragenLlamaForCausalLM(nn.Module):
         amounts; EOS ids and max_new_tokens are applied on the device (hyd_draft_accept) and the result is [B, max(lengths)] padded
         with pad_token_id, as on the stop path (an int eos_token_id is treated as a list of one).  Works with temperature, top_k /
         top_p / min_p, return_logprobs, eos_token_id, pad_token_id, return_finish, num_return_sequences, seq_lens, shared_cache_op
-        and constraint; refused (before any launch): penalties and logit_bias, stop, token_overrides, top_logprobs, return_logits,
+        and constraint, and with stop / include_stop and the penalties / logit_bias.  stop: the accept (hyd_draft_accept_stop) judges EVERY
+        token a row emits in the step, in order, against the row's output so far -- a sequence may complete at any of them and
+        may have begun in an earlier step --, so tokens, lengths and finish reasons are those of one-token decoding with the same
+        stop.  Penalties and logit_bias: the draw behind the i-th fed token counts the drafts fed in
+        front of it as already generated (hyd_sample_tokens_penalized_drafts), which keeps the scheme lossless; the sampler never
+        appends there, the accept keeps the lists of generated tokens.  Refused (before any launch): penalties, logit_bias
+        or stop together with constraint=, token_overrides, top_logprobs, return_logits, per-row values / seeds / limits,
         disable_hydragen / disable_attention / disable_hierarchy, narrow unique caches, a model on the CPU.  fp8 unique caches
         (setup_caches(kv_cache_dtype=torch.float8_e4m3fn), with or without kv_scales="calibrate") work: the preamble quantizes
         the T new rows and the causal-tail pass is the fp8 matrix-core kernel (head dim 256 with few units, which it does not

@@ -263,6 +263,29 @@ def penalize_logits(logits: Tensor, repetition_penalty=None, presence_penalty=No
     return _penalize(logits, repetition_penalty, presence_penalty, frequency_penalty, logit_bias, ctx, gen, gen_len)
 
 
+@torch.no_grad()
+def draft_row_lists_reference(gen: Optional[Tensor], gen_len: Optional[Tensor], fed: Tensor):
+    """The token lists behind the B * T logits rows of a speculative step (the definition hyd_sample_tokens_penalized_drafts
+    implements without building them): gen integer [B, stride] with gen_len [B] (None: empty lists), fed integer [B, T] ->
+    (lists int64 [B * T, stride + T - 1], lens int32 [B * T]), usable as penalize_logits' gen / gen_len.  Row r = b * T + i holds
+    gen[b, 0 .. min(gen_len[b], stride)) followed by fed[b, 1 .. i] -- the drafts fed in front of the position the row draws;
+    fed[b, 0] is the last emitted token and is already in gen.  Ids are copied as they are (the penalties ignore those outside
+    [0, n)); slots past a row's length hold -1."""
+    B, T = fed.shape
+    stride = 0 if gen is None else gen.shape[1]
+    lists = torch.full((B * T, stride + T - 1), -1, dtype=torch.int64, device=fed.device)
+    lens = torch.zeros((B * T,), dtype=torch.int32, device=fed.device)
+    for b in range(B):
+        n = 0 if gen is None else max(0, min(int(gen_len[b]), stride))
+        for i in range(T):
+            r = b * T + i
+            if n:
+                lists[r, :n] = gen[b, :n].long()
+            lists[r, n: n + i] = fed[b, 1: 1 + i].long()
+            lens[r] = n + i
+    return lists, lens
+
+
 def _penalize(logits, repetition_penalty, presence_penalty, frequency_penalty, logit_bias, ctx, gen, gen_len) -> Tensor:
     """penalize_logits with scalar penalties and the context as a [rows, n] bool mask (or None)."""
     rows, n = logits.shape

@@ -23,8 +23,13 @@ Under a token automaton (generate(constraint=)) the drafts are first walked thro
 that token as the draft -- accepted with probability 1, the masked sampler can draw nothing else -- and `draft="constraint"` proposes
 nothing but those (`constrain_drafts`, the states in `draft_accept`).
 
-This module holds the definitions in torch (`prompt_lookup_reference`, `accept_reference`, `constrain_drafts_reference`,
-`accept_states_reference`, `assembled_causal_tail_attention`) and the Python faces of the kernels (`draft_lookup`, `draft_accept`,
+Stop sequences and the penalties' token lists ride on the accept (`draft_accept(stop=, gen=, gen_len=)`, hyd_draft_accept_stop): a
+step emits several tokens per row, a stop sequence may complete at any of them, and only the accept knows which draws became output.
+The draw behind the i-th fed token counts the drafts fed in front of it as generated (sampling.draft_row_lists_reference,
+hyd_sample_tokens_penalized_drafts): it is conditioned on them, and a draw that ignored them would not be from the target distribution.
+
+This module holds the definitions in torch (`prompt_lookup_reference`, `accept_reference`, `accept_stop_reference`,
+`constrain_drafts_reference`, `accept_states_reference`, `assembled_causal_tail_attention`) and the Python faces of the kernels (`draft_lookup`, `draft_accept`,
 `constrain_drafts`; the multi-token RoPE + append is fused_decode.rope_append_multi, the causal-tail attention
 flash.flash_attention_seqlen / attention.hydragen_attention with causal_tail=True)."""
 
@@ -229,15 +234,101 @@ def accept_reference(fed: Tensor, sampled: Tensor, out: Tensor, length: Tensor, 
     return feed, next_pos, accepted, live
 
 
+def accept_stop_reference(fed: Tensor, sampled: Tensor, out: Tensor, length: Tensor, reason: Tensor, stop_index: Tensor, start_pos: Tensor,
+                          shared_len: Optional[Tensor], eos: Sequence[int], pad: int, max_new_tokens: int, retire: bool = True,
+                          logprobs: Optional[Tensor] = None, out_logprobs: Optional[Tensor] = None, *, stop=None,
+                          gen: Optional[Tensor] = None, gen_len: Optional[Tensor] = None, states: Optional[tuple] = None):
+    """The rule hyd_draft_accept_stop implements, row by row on CPU tensors: accept_reference's arguments and return value, plus
+    stop (a stopping.StopSpec of which only .stops and .include_stop are read -- EOS ids and pad are the arguments), the
+    penalties' lists gen int32 [rows, stride] / gen_len int32 [rows], and states = (step_state_after, state) as in
+    accept_states_reference; all updated in place.  A running row's CANDIDATE sequence is its kept output followed by the run
+    sampled[b, 0 .. e0), e0 = min(n + 1, max_new_tokens - length).  The run ends at the first of its columns c at which the
+    candidate holds an EOS id (reason 1, the lowest id index) or -- otherwise -- ends a stop sequence, window
+    candidate[c + 1 - len_k .. c] never reaching in front of column 0 (reason 2, the lowest k): e = tokens up to and including
+    that column, else e0.  The e tokens (and log-probs) are written; a stop match without include_stop pads its len_k columns
+    and the row's length becomes c + 1 - len_k, which may lie below the length before the step.  accepted = e - 1, state =
+    step_state_after[b, e - 1], gen receives the e tokens at gen_len .. (positions < stride only) and gen_len += e: all of the
+    final e, before the trim.  Finished rows do not change."""
+    rows, T = fed.shape
+    eos = list(eos)
+    stops = [list(s) for s in (stop.stops if stop is not None else ())]
+    include = bool(stop.include_stop) if stop is not None else False
+    feed = torch.empty((rows,), dtype=torch.int64)
+    next_pos = torch.empty((rows,), dtype=torch.int64)
+    accepted = torch.zeros((rows,), dtype=torch.int32)
+    live = 0
+    for b in range(rows):
+        ln, r, last = int(length[b]), int(reason[b]), pad
+        if r == 0 and ln < max_new_tokens:
+            n = 0
+            while n < T - 1 and int(fed[b, n + 1]) == int(sampled[b, n]):
+                n += 1
+            e = min(n + 1, max_new_tokens - ln)
+            cand = out[b, :ln].tolist() + sampled[b, :e].tolist()
+            which, trim = -1, 0
+            for c in range(ln, ln + e):
+                if cand[c] in eos:
+                    r, which = 1, eos.index(cand[c])
+                else:
+                    hit = [k for k, s in enumerate(stops) if c + 1 >= len(s) and cand[c + 1 - len(s): c + 1] == s]
+                    if hit:
+                        r, which = 2, hit[0]
+                        trim = 0 if include else len(stops[which])
+                if r != 0:
+                    e = c + 1 - ln
+                    break
+            out[b, ln: ln + e] = torch.tensor(cand[ln: ln + e], dtype=torch.int64)
+            if logprobs is not None and out_logprobs is not None:
+                out_logprobs[b, ln: ln + e] = logprobs[b, :e]
+            if gen is not None:
+                gl = int(gen_len[b])
+                for i in range(e):
+                    if 0 <= gl + i < gen.shape[1]:
+                        gen[b, gl + i] = cand[ln + i]
+                gen_len[b] = gl + e
+            if states is not None:
+                states[1][b] = states[0][b, e - 1]
+            accepted[b] = e - 1
+            last = cand[ln + e - 1]
+            ln += e
+            if trim:
+                out[b, ln - trim: ln] = pad
+                ln -= trim
+            length[b] = ln
+            if r != 0:
+                reason[b], stop_index[b] = r, which
+        running = r == 0 and ln < max_new_tokens
+        live += int(running)
+        feed[b] = last if running else pad
+        if running or not retire:
+            next_pos[b] = int(start_pos[b]) + ln - 1
+        else:
+            next_pos[b] = (int(shared_len[b]) if shared_len is not None else 0) - 1
+    return feed, next_pos, accepted, live
+
+
 def draft_accept(fed: Tensor, sampled: Tensor, out: Tensor, length: Tensor, reason: Tensor, stop_index: Tensor, live: Tensor,
                  start_pos: Tensor, shared_len: Optional[Tensor], eos: Sequence[int], pad: int, max_new_tokens: int,
                  retire: bool = True, logprobs: Optional[Tensor] = None, out_logprobs: Optional[Tensor] = None,
-                 states: Optional[tuple] = None):
+                 states: Optional[tuple] = None, stop=None, gen: Optional[Tensor] = None, gen_len: Optional[Tensor] = None,
+                 stop_tokens: Optional[Tensor] = None):
     """hyd_draft_accept, one launch -> (feed, next_pos int64 [rows], accepted int32 [rows]); the rows still running are ADDED to
     live (int32 [1], a slot the caller zeroed).  The state tensors are those of new_state; CPU tensors take accept_reference.
     states = (step_state_after int32 [rows, T], state int32 [rows]): hyd_draft_accept_states -- a row that emits e >= 1 tokens
-    also gets state[b] = step_state_after[b, e - 1] (accept_states_reference).  Nothing synchronises."""
+    also gets state[b] = step_state_after[b, e - 1] (accept_states_reference).  stop (a stopping.StopSpec: its stop sequences
+    and include_stop) or gen / gen_len (int32 [rows, stride <= GEN_MAX] / [rows], the penalties' lists) given:
+    hyd_draft_accept_stop, which judges every emitted token by the stop rules and appends the emitted tokens to the lists
+    (accept_stop_reference); without them the calls are exactly those made before.  stop_tokens: stop.stop_table(device)[0],
+    uploaded once by a loop that calls this every step (None: uploaded here).  Nothing else synchronises."""
     rows, T = fed.shape
+    if (gen is None) != (gen_len is None):
+        raise ValueError("gen and gen_len go together")
+    if gen is not None and (gen.dtype != torch.int32 or gen.ndim != 2 or gen.shape[0] != rows or not gen.is_contiguous() or gen.device != fed.device
+                            or gen.shape[1] > _lib.SAMPLE_GEN_MAX or gen_len.dtype != torch.int32 or gen_len.shape != (rows,)
+                            or not gen_len.is_contiguous() or gen_len.device != fed.device):
+        raise ValueError(f"gen must be a contiguous int32 [{rows}, <= {_lib.SAMPLE_GEN_MAX}] and gen_len int32 [{rows}] on {fed.device}")
+    if stop is not None and (len(stop.stops) > _lib.STOP_MAX_SEQS or any(not 1 <= len(s) <= _lib.STOP_MAX_LEN for s in stop.stops)):
+        raise ValueError(f"stop: at most {_lib.STOP_MAX_SEQS} sequences of 1 to {_lib.STOP_MAX_LEN} tokens")
     if states is not None:
         after, st = states
         if (after.dtype != torch.int32 or after.shape != (rows, T) or not after.is_contiguous() or after.device != fed.device
@@ -265,8 +356,11 @@ def draft_accept(fed: Tensor, sampled: Tensor, out: Tensor, length: Tensor, reas
         raise ValueError("logprobs must be float32 [rows, T] and out_logprobs float32 with out's shape and strides")
     if dev.type != "cuda":
         rest = (out, length, reason, stop_index, start_pos, shared_len, eos, pad, max_new_tokens, retire, logprobs, out_logprobs)
-        feed, pos, acc, n = (accept_reference(fed, sampled, *rest) if states is None else
-                             accept_states_reference(fed, sampled, *states, *rest))
+        if stop is not None or gen is not None:
+            feed, pos, acc, n = accept_stop_reference(fed, sampled, *rest, stop=stop, gen=gen, gen_len=gen_len, states=states)
+        else:
+            feed, pos, acc, n = (accept_reference(fed, sampled, *rest) if states is None else
+                                 accept_states_reference(fed, sampled, *states, *rest))
         live += n
         return feed, pos, acc
     fed, sampled = fed.contiguous(), sampled.contiguous()
@@ -286,7 +380,25 @@ def draft_accept(fed: Tensor, sampled: Tensor, out: Tensor, length: Tensor, reas
     for i, e in enumerate(eos):
         p.eos[i] = e
     p.rows, p.T, p.n_eos, p.max_new_tokens, p.retire = rows, T, len(eos), max_new_tokens, int(bool(retire))
-    if states is None:
+    if stop is not None or gen is not None:
+        sp, table = None, None
+        if stop is not None:
+            sp = _lib.StopParams()
+            lens = [len(s) for s in stop.stops]
+            table = stop_tokens if stop_tokens is not None else stop.stop_table(dev)[0] if lens else None
+            if table is not None and (table.dtype != torch.int64 or table.shape != (len(lens), _lib.STOP_MAX_LEN) or not table.is_contiguous()
+                                      or table.device != dev):
+                raise ValueError(f"stop_tokens must be stop.stop_table(device)[0]: a contiguous int64 [{len(lens)}, {_lib.STOP_MAX_LEN}] on {dev}")
+            sp.stop_tokens = table.data_ptr() if lens else None
+            for k, n in enumerate(lens):
+                sp.stop_lens[k] = n
+            sp.n_stop, sp.include_stop = len(lens), int(bool(stop.include_stop))
+        after, st = (None, None) if states is None else (states[0].data_ptr(), states[1].data_ptr())
+        _lib.check(_lib.load().hyd_draft_accept_stop(
+            C.byref(p), None if sp is None else C.byref(sp), after, st, None if gen is None else gen.data_ptr(),
+            None if gen is None else gen_len.data_ptr(), 0 if gen is None else gen.shape[1], torch.cuda.current_stream().cuda_stream))
+        del table
+    elif states is None:
         _lib.check(_lib.load().hyd_draft_accept(C.byref(p), torch.cuda.current_stream().cuda_stream))
     else:
         _lib.check(_lib.load().hyd_draft_accept_states(C.byref(p), states[0].data_ptr(), states[1].data_ptr(), torch.cuda.current_stream().cuda_stream))

@@ -774,6 +774,45 @@ HYD_API int hyd_draft_constrain(const hyd_draft_constrain_params* p, void* strea
  * HYD_ERR_BAD_ARG, as is everything hyd_draft_accept refuses. */
 HYD_API int hyd_draft_accept_states(const hyd_draft_accept_params* p, const int32_t* step_state_after, int32_t* state, void* stream);
 
+/* hyd_draft_accept_stop: hyd_draft_accept (hyd_draft_accept_states when the two state arrays are given) with hyd_stop_update's
+ * rules applied to EVERY token the row emits in the step, and the penalties' per-sequence token lists kept beside it.  Of `stop`
+ * only stop_tokens, stop_lens, n_stop and include_stop are read; its other fields may be null or zero.  A running row
+ * (reason == 0, length < max_new_tokens) computes n and e = min(n + 1, room) as hyd_draft_accept does.  Then, for i = 0 .. e - 1
+ * in order, with column c = length[b] + i:
+ *   1. out[b, c] = sampled[b, i];
+ *   2. it equals eos[j] for the lowest j: reason 1, stop_index j, the token is kept, the run ends with e = i + 1;
+ *   3. otherwise the stop sequences in list order: sequence k (len_k tokens) matches when c + 1 >= len_k and
+ *      out[b, c + 1 - len_k .. c] equals it -- never reaching in front of column 0, but possibly into columns written by earlier
+ *      steps; the lowest matching k gives reason 2, stop_index k, and the run ends with e = i + 1.  include_stop == 0: the len_k
+ *      matched columns become pad and length[b] = c + 1 - len_k; else they stay and length[b] = c + 1;
+ *   4. otherwise the row keeps running: length[b] += e.
+ * Draws behind the cut, and rejected draws, never reach out and are never matched.  accepted[b] = e - 1 with the final e, before
+ * any trim; out_logprobs is written for the e judged columns; state[b] = step_state_after[b, e - 1] when the state arrays are
+ * given.  gen != NULL: the e judged tokens go to gen[b, gen_len[b] ..) as int32, only at positions < gen_stride, and gen_len[b]
+ * += e (plain vector stores; a finished row's list does not change).  feed, next_pos (from the length after the trim), *live and
+ * finished rows behave exactly as in hyd_draft_accept.  In one sentence: for every row the result equals e successive one-token
+ * hyd_stop_update steps over the accepted draws.  stop == NULL (or n_stop == 0) with gen == NULL is byte for byte
+ * hyd_draft_accept / hyd_draft_accept_states.
+ * HYD_ERR_BAD_ARG: everything hyd_draft_accept_states refuses, n_stop outside [0, HYD_STOP_MAX_SEQS], n_stop > 0 without
+ * stop_tokens, a stop length outside [1, HYD_STOP_MAX_LEN], gen without gen_len (or gen_len without gen), gen_stride < 0 or
+ * > HYD_SAMPLE_GEN_MAX, misaligned pointers.  rows == 0 succeeds without a launch. */
+HYD_API int hyd_draft_accept_stop(const hyd_draft_accept_params* p, const hyd_stop_params* stop, const int32_t* step_state_after,
+                                  int32_t* state, int32_t* gen, int32_t* gen_len, int32_t gen_stride, void* stream);
+
+/* hyd_sample_tokens_penalized_drafts: hyd_sample_tokens_penalized over the p->rows = B * T logits rows of a speculative step, with
+ * ONE token list per sequence.  Logits row r belongs to sequence b = r / T and fed position i = r % T.  p->gen is
+ * [B, gen_stride] and p->gen_len [B].  The row's counts c[v] run over gen[b, 0 .. min(gen_len[b], gen_stride)) followed by
+ * fed[b, 1 .. i] (fed int64 [B, T]: the drafts fed in front of the position that row draws; fed[b, 0] is the last emitted token
+ * and is already in gen; ids outside [0, n) are ignored).  With gen NULL there are no lists and fed is not read.  The context
+ * bitmaps are read at row b / rows_per_group.  Everything else is hyd_sample_tokens_penalized's for logits row r: the bias list,
+ * penalties in double with one rounding, cuts, noise from (seed, offset, r), logprobs, kept.  Tokens, kept counts and log-probs
+ * are, bit for bit, what hyd_sample_tokens_penalized returns for the B * T-row call in which row r carries the explicit list
+ * gen[b] ++ fed[b, 1 .. i] and the context bitmaps have rows_per_group * T.  T == 1 is exactly hyd_sample_tokens_penalized(p).
+ * Capture-safe like that call; the kernel has no workspace and writes nothing but out / logprobs / kept.
+ * Refusals: everything hyd_sample_tokens_penalized refuses; HYD_ERR_BAD_ARG for T outside [1, 8], rows % T != 0, append_out != 0
+ * (hyd_draft_accept_stop owns the lists on this route), a null fed while gen != NULL, a misaligned fed. */
+HYD_API int hyd_sample_tokens_penalized_drafts(const hyd_sample_penalty_params* p, const int64_t* fed, int32_t T, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * All-reduce(sum) of the tensor-parallel block output (hydragen/tp.py:83-87 after down_proj, :108-112 after
  * o_proj; the reference calls torch.distributed / NCCL there) as a two-shot direct exchange over

@@ -86,6 +86,132 @@ def kernel_times(B, T, Hq, Hkv, D, P, S, fp8=False):
     }
 
 
+def alternating(fns: dict, repeats=7, iters=20):
+    """{name: (median, min, max) us per call}: the candidates take turns, `repeats` rounds of `iters` calls each, so that clock and
+    cache drift hits them alike; the spread is over the rounds."""
+    got = {name: [] for name in fns}
+    for r in range(repeats):
+        for name, fn in fns.items():
+            got[name].append(timed(fn, iters, warm=3 if r == 0 else 1))
+    return {name: (sorted(v)[len(v) // 2], min(v), max(v)) for name, v in got.items()}
+
+
+def cell(x):
+    return f"{x[0]:.1f} ({x[1]:.1f} - {x[2]:.1f})"
+
+
+def stop_accept_times():
+    """hyd_draft_accept_stop against hyd_draft_accept: us per launch (+ the memset that resets the lengths), random tokens over a
+    32000 vocabulary, stop sequences of 16 random tokens -- the common step, where the last token decides."""
+    from hydragen_amd import speculative, stopping
+
+    print("## 1. The accept launch\n\nus per launch with the memset that resets the lengths, median (min - max) of 7 alternating rounds of 20 "
+          "launches, eager, host-timed back to back.  Stop sequences: 16 random tokens each.\n")
+    print("| B | T | hyd_draft_accept | 0 stops + lists | 4 stops | 32 stops | 32 stops + lists |")
+    print("|---|---|---|---|---|---|---|")
+    S = 64
+    for B in (128, 1024):
+        for T in (4, 8):
+            fed = torch.randint(0, 32000, (B, T), device=DEV)
+            state = speculative.new_state(B, S, 0, DEV)
+            live = torch.zeros((1,), dtype=torch.int32, device=DEV)
+            start = torch.full((B,), 2048, device=DEV, dtype=torch.int64)
+            gen, gen_len = torch.zeros((B, S), dtype=torch.int32, device=DEV), torch.zeros((B,), dtype=torch.int32, device=DEV)
+
+            def call(n_stop=None, lists=False):
+                kw = {}
+                if n_stop is not None:
+                    spec = stopping.StopSpec(stops=tuple(tuple(torch.randint(0, 32000, (16,)).tolist()) for _ in range(n_stop)))
+                    kw.update(stop=spec, stop_tokens=spec.stop_table(DEV)[0] if n_stop else None)
+                if lists:
+                    kw.update(gen=gen, gen_len=gen_len)
+
+                def fn():
+                    state[1].zero_()
+                    if lists:
+                        gen_len.zero_()
+                    speculative.draft_accept(fed, fed, *state[:4], live, start, start, (2,), 0, S, **kw)
+                return fn
+
+            r = alternating({"old": call(), "lists": call(0, True), "4": call(4), "32": call(32), "32l": call(32, True)})
+            print(f"| {B} | {T} | {cell(r['old'])} | {cell(r['lists'])} | {cell(r['4'])} | {cell(r['32'])} | {cell(r['32l'])} |")
+    print()
+
+
+def penalized_drafts_times():
+    """hyd_sample_tokens_penalized_drafts against hyd_sample_tokens_penalized on the same B * T logits rows with the lists expanded
+    on the host beforehand (sampling.draft_row_lists_reference; the expansion itself is not timed)."""
+    from hydragen_amd import layer_ops, sampling
+
+    print("## 2. The penalised draw of a step\n\nus per launch, median (min - max) of 7 alternating rounds of 20 launches; bf16 logits, top-p 0.95, "
+          "temperature 1, repetition 1.1 / frequency 0.1 / presence 0.1, 64 generated tokens per sequence, B = 128.  The existing call "
+          "reads lists expanded to one per logits row beforehand (the expansion is not timed).\n")
+    print("| V | T | rows | hyd_sample_tokens_penalized, expanded lists | hyd_sample_tokens_penalized_drafts | ratio |")
+    print("|---|---|---|---|---|---|")
+    B = 128
+    for V in (32000, 128256):
+        for T in (4, 8):
+            x = (torch.randn(B * T, V, device=DEV) * 3).to(torch.bfloat16)
+            gen = torch.randint(0, V, (B, 64), dtype=torch.int32, device=DEV)
+            gen_len = torch.full((B,), 64, dtype=torch.int32, device=DEV)
+            fed = torch.randint(0, V, (B, T), device=DEV)
+            lists, lens = sampling.draft_row_lists_reference(gen.cpu(), gen_len.cpu(), fed.cpu())
+            seq = layer_ops.Penalties(1.1, 0.1, 0.1, gen=gen, gen_len=gen_len)
+            row = layer_ops.Penalties(1.1, 0.1, 0.1, gen=lists.to(torch.int32).to(DEV).contiguous(), gen_len=lens.to(DEV))
+            r = alternating({"old": lambda: layer_ops.sample_tokens_penalized(x, 1.0, (1, 0), penalties=row, top_p=0.95),
+                             "new": lambda: layer_ops.sample_tokens_penalized(x, 1.0, (1, 0), penalties=seq, top_p=0.95, drafts=fed)})
+            print(f"| {V} | {T} | {B * T} | {cell(r['old'])} | {cell(r['new'])} | {r['new'][0] / r['old'][0]:.3f} |")
+    print()
+
+
+def stop_penalties_report(args):
+    """The tables of profiles/speculative_stop_penalties.md, from one process."""
+    from hydragen_amd.llama import HydragenLlamaForCausalLM, LlamaConfig
+
+    print("# Speculative decoding with stop sequences and penalties: measurements\n\nOne process on one MI355X; every comparison alternates its "
+          "candidates and reports the spread.\n")
+    stop_accept_times()
+    penalized_drafts_times()
+    cfg = LlamaConfig.llama2_7b()
+    cfg.num_hidden_layers = args.layers
+    cfg.max_position_embeddings = max(cfg.max_position_embeddings, args.prefix + args.new + 32)
+    model = HydragenLlamaForCausalLM.from_config(cfg, dtype=torch.bfloat16, device=DEV, seed=0)
+    model.graph(not args.no_graph)
+    prompt = torch.randint(1, cfg.vocab_size, (1, args.prefix), device=DEV)
+    N, steps, K = args.new, args.new - 1, 3
+    print(f"## 3. The T-token step with penalties\n\nLlama-2-7B shell ({args.layers} layers, random weights, bf16), P = {args.prefix}, {N} new tokens, "
+          f"{'eager' if args.no_graph else 'HIP-graph'} decode, T = {K + 1}, all-wrong given drafts (every step emits one token: decode time / steps is "
+          "the step time), temperature 0.  Penalties: repetition 1.1, frequency 0.1.  ms per step, median (min - max) of 3 alternating runs.\n")
+    print("| B | without penalties | with penalties | with penalties and 4 stop sequences | penalties cost per step |")
+    print("|---|---|---|---|---|")
+    for B in (int(b) for b in args.batches.split(",")):
+        model.setup_caches(max_unique_batch_size=B, max_unique_seq_length=N + 16, max_shared_batch_sizes=[1], max_shared_seq_lengths=[args.prefix])
+
+        def run(n, **kw):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = model.generate(input_ids=prompt, num_return_sequences=B, max_new_tokens=n, temperature=0.0, **kw)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0, out
+
+        run(4)
+        pre = min(run(1)[0] for _ in range(2))
+        wrong = (run(N)[1] + 1) % cfg.vocab_size
+        pen = dict(repetition_penalty=1.1, frequency_penalty=0.1)
+        stops = [torch.randint(1, cfg.vocab_size, (16,)).tolist() for _ in range(4)]
+        variants = {"plain": {}, "pen": pen, "pen+stop": dict(pen, stop=stops)}
+        for kw in variants.values():
+            run(4, draft_tokens=K, draft=wrong[:, :4], **kw)
+        got = {name: [] for name in variants}
+        for _ in range(3):
+            for name, kw in variants.items():
+                got[name].append((run(N, draft_tokens=K, draft=wrong, **kw)[0] - pre) / steps * 1e3)
+        med = {name: (sorted(v)[1], min(v), max(v)) for name, v in got.items()}
+        c = lambda x: f"{x[0]:.3f} ({x[1]:.3f} - {x[2]:.3f})"  # noqa: E731
+        print(f"| {B} | {c(med['plain'])} | {c(med['pen'])} | {c(med['pen+stop'])} | {(med['pen'][0] - med['plain'][0]) * 1e3:.0f} us |")
+    print()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default="32,128,1024")
@@ -94,7 +220,12 @@ def main():
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--kv-cache-dtype", choices=("16-bit", "fp8"), default="16-bit")
+    ap.add_argument("--stop-penalties", action="store_true",
+                    help="write the tables of profiles/speculative_stop_penalties.md instead: the accept launch with stop sequences and "
+                         "lists, the penalised draw of a step, the T-token step with penalties (--batches 32,128)")
     args = ap.parse_args()
+    if args.stop_penalties:
+        return stop_penalties_report(args)
     fp8 = args.kv_cache_dtype == "fp8"
     from hydragen_amd.llama import HydragenLlamaForCausalLM, LlamaConfig
 
