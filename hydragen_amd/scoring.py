@@ -4,7 +4,8 @@ reference of the tests.
 
 For one row of logits l (length n) and its target token t, with the VALID logits those that are neither NaN nor -inf and
 m = their max:
-  * logprob = l_t - m - ln sum exp(l - m) over the valid logits; t outside [0, n): NaN (padding); l_t NaN: NaN; l_t -inf:
+  * logprob = l_t - m - ln sum exp(l - m) over the valid logits (the sum as 1, the first maximum's term, + the others, through
+    log1p: a log-prob of -1e-12 keeps its digits; tests/test_scoring_stress.py holds it to a plain ranking); t outside [0, n): NaN (padding); l_t NaN: NaN; l_t -inf:
     -inf; a row without a valid logit: NaN;
   * greedy = t is the lowest-index maximum of the valid logits (torch.argmax's tie rule: what generate(temperature=0) picks);
   * top-N: the N largest valid logits ordered by (value descending, index ascending) and their log-probs; rows with fewer
@@ -43,7 +44,11 @@ def token_logprobs_reference(logits: Tensor, targets: Tensor, top_n: int = 0):
     m = torch.where(has, xm.amax(-1), torch.zeros(R, dtype=x.dtype, device=x.device))
     # the max's own term is exactly 1 (l == m, also for m = +inf)
     w = torch.where(valid, torch.where(xm == m[:, None], torch.ones_like(x), torch.exp(xm - m[:, None])), torch.zeros_like(x))
-    lse = torch.log(w.sum(-1))
+    first_max = torch.argmax(((xm == m[:, None]) & valid).to(torch.int8), dim=-1)  # argmax returns the first: lowest index
+    # ln(1 + the other terms): where the maximum holds nearly all the mass (one logit 30 above the rest: ln sum = 1e-12), log(sum)
+    # keeps only the digits of the sum above 2^-52 and depends on the order of the additions -- 5e-4 relative in such a log-prob
+    w.scatter_(1, first_max[:, None], 0.0)
+    lse = torch.log1p(w.sum(-1))
 
     def lp_of(v):
         d = torch.where(v == m.reshape(-1, *([1] * (v.ndim - 1))), torch.zeros_like(v), v - m.reshape(-1, *([1] * (v.ndim - 1))))
@@ -53,7 +58,6 @@ def token_logprobs_reference(logits: Tensor, targets: Tensor, top_n: int = 0):
     tin = (t >= 0) & (t < n)
     lt = x.gather(1, t.clamp(0, n - 1)[:, None])[:, 0]
     lp = torch.where(tin & has, lp_of(lt), torch.full_like(lt, math.nan))
-    first_max = torch.argmax(((xm == m[:, None]) & valid).to(torch.int8), dim=-1)  # argmax returns the first: lowest index
     greedy = tin & has & (t == first_max)
     if top_n == 0:
         return lp.float(), greedy, torch.empty((R, 0), dtype=torch.int64, device=x.device), \

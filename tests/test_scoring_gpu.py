@@ -1,5 +1,8 @@
 """-m gpu: hyd_token_logprobs (csrc/token_logprob.hip) against the float64 definition (hydragen_amd/scoring.py) and against the
-sampler's log-prob, its determinism, and the model shell's score() / generate(top_logprobs=) against independent paths."""
+sampler's log-prob, its determinism, and the model shell's score() / generate(top_logprobs=) against independent paths.
+The rows of `_rows` take the top-N select's one-gather histogram path almost everywhere; the rows built for its key and index
+levels, its distance bin 255 and its full candidate buffer are tests/scoring_stress_cases.py, run by
+tests/test_scoring_stress_gpu.py (tests/test_scoring_stress.py records which path each row of `_rows` takes)."""
 import math
 
 import pytest
