@@ -1,5 +1,5 @@
 // C ABI, the layer around attention: RoPE + cache append (one token, fp8 caches, several tokens), add + RMSNorm, SwiGLU, and the
-// fp8 linear-layer weights (linear_w8.hip).
+// fp8 and 4-bit linear-layer weights (linear_w8.hip, linear_w4.hip).
 #include "api_core.h"
 
 using namespace hyd;
@@ -56,11 +56,13 @@ RopeArgs rope_args(const P* p, const hyd_qk_norm* qn) {
     return a;
 }
 
+// (k_multiple 32: the 4-bit calls, whose codes are "w4")
 int check_w8_common(const void* w8, const float* scale, int32_t N, int32_t K, int32_t dtype, int k_multiple) {
-    if (dtype != HYD_F16 && dtype != HYD_BF16) return fail(HYD_ERR_UNSUPPORTED, "dtype %d: f16 / bf16 activations (the weights are e4m3fn)", dtype);
+    if (dtype != HYD_F16 && dtype != HYD_BF16)
+        return fail(HYD_ERR_UNSUPPORTED, k_multiple == 32 ? "dtype %d: f16 / bf16 activations (the weights are e2m1)" : "dtype %d: f16 / bf16 activations (the weights are e4m3fn)", dtype);
     if (N < 1 || K < 1) return fail(HYD_ERR_BAD_ARG, "N %d / K %d must be >= 1", N, K);
     if (K % k_multiple != 0) return fail(HYD_ERR_BAD_ARG, "K %d must be a multiple of %d", K, k_multiple);
-    if (int rc = check_ptr_align(w8, "w8")) return rc;
+    if (int rc = check_ptr_align(w8, k_multiple == 32 ? "w4" : "w8")) return rc;
     if (int rc = check_not_null({{scale, "scale"}})) return rc;
     return check_elem_align({{scale, 4, "scale"}});
 }
@@ -205,6 +207,52 @@ int hyd_weight_widen(const hyd_weight_widen_params* p, void* stream) {
     a.w8 = static_cast<const uint8_t*>(p->w8); a.scale = p->scale; a.out = p->out; a.os = p->out_row_stride;
     a.N = p->N; a.K = p->K;
     return launched(launch_weight_widen(a, p->dtype, static_cast<hipStream_t>(stream)), "weight_widen kernel launch");
+}
+
+size_t hyd_linear_w4_workspace_bytes(int32_t M, int32_t N, int32_t K) {
+    if (M < 1 || N < 1 || K < 1) return 0;
+    return plan_linear_w4(M, N, K).bytes;
+}
+
+int hyd_linear_w4(const hyd_linear_w4_params* p, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    if (p->M < 1) return fail(HYD_ERR_BAD_ARG, "M %d must be >= 1", p->M);
+    int rc = check_w8_common(p->w4, p->scale, p->N, p->K, p->dtype, 32);
+    if (!rc) rc = check_ptrs_align({{p->shift, "shift"}, {p->x, "x"}, {p->y, "y"}});
+    if (!rc) rc = check_strides8({{p->x_row_stride, "x_row_stride"}, {p->y_row_stride, "y_row_stride"}});
+    if (rc) return rc;
+    if (p->x_row_stride < p->K || p->y_row_stride < p->N)
+        return fail(HYD_ERR_BAD_ARG, "x_row_stride %lld < K %d or y_row_stride %lld < N %d", (long long)p->x_row_stride, p->K, (long long)p->y_row_stride, p->N);
+    const LinearW8Plan pl = plan_linear_w4(p->M, p->N, p->K);
+    if ((int64_t)pl.ngroups * pl.mtiles > 0x7fffffffLL || ((int64_t)p->M * (pl.np / 4) + 255) / 256 > 0x7fffffffLL)
+        return fail(HYD_ERR_UNSUPPORTED, "M %d x N %d: more workgroups than one launch takes", p->M, p->N);
+    if (pl.bytes) {
+        if (!p->workspace || p->workspace_bytes < pl.bytes)
+            return fail(HYD_ERR_WORKSPACE, "linear_w4 needs %zu workspace bytes for M %d N %d K %d, got %zu", pl.bytes, p->M, p->N, p->K, p->workspace ? p->workspace_bytes : (size_t)0);
+        if (misaligned(p->workspace, 16)) return fail(HYD_ERR_WORKSPACE, "workspace must be 16-byte aligned");
+    }
+    LinearW4Args a;
+    memset(&a, 0, sizeof(a));
+    a.c.x = p->x; a.c.w8 = static_cast<const uint8_t*>(p->w4); a.c.scale = p->scale; a.c.y = p->y;
+    a.c.ws = pl.bytes ? static_cast<float*>(p->workspace) : nullptr;
+    a.c.xs = p->x_row_stride; a.c.ys = p->y_row_stride; a.c.np = pl.np;
+    a.c.M = p->M; a.c.N = p->N; a.c.K = p->K;
+    a.c.mtiles = pl.mtiles; a.c.steps = pl.steps; a.c.splits = pl.splits;
+    a.shift = static_cast<const uint8_t*>(p->shift); a.groups = p->K / 32; a.wide_shift = p->K % 256 == 0;
+    return launched(launch_linear_w4(a, pl, p->dtype, static_cast<hipStream_t>(stream)), "linear_w4 kernel launch");
+}
+
+int hyd_weight_widen_w4(const hyd_weight_widen_w4_params* p, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    if (int rc = check_w8_common(p->w4, p->scale, p->N, p->K, p->dtype, 32)) return rc;
+    if (int rc = check_ptrs_align({{p->shift, "shift"}, {p->out, "out"}})) return rc;
+    if (int rc = check_stride8(p->out_row_stride, "out_row_stride")) return rc;
+    if (p->out_row_stride < p->K) return fail(HYD_ERR_BAD_ARG, "out_row_stride %lld < K %d", (long long)p->out_row_stride, p->K);
+    WeightWidenW4Args a;
+    memset(&a, 0, sizeof(a));
+    a.w4 = static_cast<const uint8_t*>(p->w4); a.shift = static_cast<const uint8_t*>(p->shift); a.scale = p->scale; a.out = p->out;
+    a.os = p->out_row_stride; a.N = p->N; a.K = p->K;
+    return launched(launch_weight_widen_w4(a, p->dtype, static_cast<hipStream_t>(stream)), "weight_widen_w4 kernel launch");
 }
 
 }  // extern "C"

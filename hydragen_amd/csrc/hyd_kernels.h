@@ -339,10 +339,31 @@ struct WeightWidenArgs {  // linear_w8.hip: out = dequantize_weight(w8, scale)
     int32_t N, K;
 };
 
+struct LinearW4Args {  // linear_w4.hip: y = round16(scale * sum_k x * e2m1(w4) * 2^-shift); the plan is a LinearW8Plan with 256-deep steps
+    LinearW8Args c;        // x, scale, y, ws, strides, shapes and the plan's fields: what the fp8 call names alike (c.w8 = the w4 bytes);
+                           // linear_w8_reduce_kernel reads exactly this block
+    const uint8_t* shift;  // [N, K / 32]
+    int32_t groups;        // K / 32
+    int32_t wide_shift;    // K % 256 == 0: a step's 8 shift bytes of a row are one aligned 8-byte load
+};
+
+struct WeightWidenW4Args {  // linear_w4.hip: out = dequantize_weight_fp4(w4, shift, scale)
+    const uint8_t* w4;
+    const uint8_t* shift;
+    const float* scale;
+    void* out;
+    int64_t os;
+    int32_t N, K;
+};
+
 // launchers (defined next to the kernels); return hipError_t as int
 LinearW8Plan plan_linear_w8(int M, int N, int K);                                        // linear_w8.hip, shapes only
 int launch_linear_w8(const LinearW8Args& a, const LinearW8Plan& pl, int dtype, hipStream_t s);  // linear_w8.hip
+int launch_linear_w8_reduce(const LinearW8Args& a, int dtype, hipStream_t s);            // linear_w8.hip: the split slices' second launch alone
 int launch_weight_widen(const WeightWidenArgs& a, int dtype, hipStream_t s);             // linear_w8.hip
+LinearW8Plan plan_linear_w4(int M, int N, int K);                                        // linear_w4.hip, shapes only
+int launch_linear_w4(const LinearW4Args& a, const LinearW8Plan& pl, int dtype, hipStream_t s);  // linear_w4.hip
+int launch_weight_widen_w4(const WeightWidenW4Args& a, int dtype, hipStream_t s);        // linear_w4.hip
 int launch_kv_absmax(const KvAbsmaxArgs& a, int dtype, hipStream_t s);  // kv_scale.hip
 int launch_kv_scales(const KvScalesArgs& a, hipStream_t s);             // kv_scale.hip
 int launch_kv_promote(const KvPromoteArgs& a, int src_dtype, int dst_dtype, hipStream_t s);  // kv_promote.hip

@@ -349,8 +349,16 @@ static int launch_linear_w8_t(const LinearW8Args& a, const LinearW8Plan& pl, hip
         hipLaunchKernelGGL((linear_w8_rows_kernel<T, 8>), grid, block, 0, s, a);
     int rc = (int)hipGetLastError();
     if (rc || pl.splits == 1) return rc;
+    return launch_linear_w8_reduce(a, Traits<T>::kDtype, s);
+}
+
+int launch_linear_w8_reduce(const LinearW8Args& a, int dtype, hipStream_t s) {
     const int64_t quads = (int64_t)a.M * (a.np >> 2);
-    hipLaunchKernelGGL(linear_w8_reduce_kernel<T>, dim3((unsigned)((quads + kThreads - 1) / kThreads)), block, 0, s, a);
+    const dim3 grid((unsigned)((quads + kThreads - 1) / kThreads)), block(kThreads);
+    if (dtype == HYD_F16)
+        hipLaunchKernelGGL(linear_w8_reduce_kernel<F16>, grid, block, 0, s, a);
+    else
+        hipLaunchKernelGGL(linear_w8_reduce_kernel<BF16>, grid, block, 0, s, a);
     return (int)hipGetLastError();
 }
 

@@ -30,7 +30,7 @@ from .flash import flash_attention, flash_attention_seqlen, padded_head_dim
 from . import kv_quant as _kv_quant
 from .kv_quant import FP8_DTYPE, dequantize_kv, quantize_kv, scale_constant
 from .tp import all_reduce_sum
-from .weight_quant import Fp8Linear, W8Scratch
+from .weight_quant import FP4_DTYPE, Fp4Linear, Fp8Linear, W8Scratch
 
 
 @dataclass
@@ -970,9 +970,13 @@ class HydragenLlamaForCausalLM(nn.Module):
         weight_quant.W8_MAX_ROWS rows (batch x tokens per row) runs hyd_linear_w8, larger ones widen the weight into one scratch
         buffer of the model (sized here for the largest quantized weight, so that no forward allocates and captured graphs hold
         static addresses) and run the 16-bit GEMM on it.  state_dict() carries `weight` / `weight_scale` of the new modules;
-        loading it into a model quantized the same way restores it bit for bit."""
-        if dtype != FP8_DTYPE:
-            raise NotImplementedError(f"quantize_weights(dtype={dtype}): {FP8_DTYPE} is the one format")
+        loading it into a model quantized the same way restores it bit for bit.
+        dtype=torch.float4_e2m1fn_x2 stores 4-bit e2m1 codes with a shift per group of 32 and the per-channel scale instead
+        (weight_quant.Fp4Linear: buffers `weight` uint8 [N, K / 2], `weight_shift`, `weight_scale`; hyd_linear_w4 up to
+        weight_quant.W4_MAX_ROWS rows, hyd_weight_widen_w4 above); every in_features must be a multiple of 32."""
+        if dtype not in (FP8_DTYPE, FP4_DTYPE):
+            raise NotImplementedError(f"quantize_weights(dtype={dtype}): {FP8_DTYPE} and {FP4_DTYPE} are the formats")
+        cls = Fp4Linear if dtype == FP4_DTYPE else Fp8Linear
         if self.weights_quantized:
             raise RuntimeError("quantize_weights() was already called on this model")
         skip = set(skip)
@@ -987,17 +991,17 @@ class HydragenLlamaForCausalLM(nn.Module):
         for layer in self.model.layers:
             attn, mlp = layer.self_attn, layer.mlp
             if "qkv_proj" not in skip:
-                attn.qkv_proj = Fp8Linear.from_linears((attn.q_proj, attn.k_proj, attn.v_proj), scratch)
+                attn.qkv_proj = cls.from_linears((attn.q_proj, attn.k_proj, attn.v_proj), scratch)
                 attn.q_proj = attn.k_proj = attn.v_proj = None
             if "o_proj" not in skip:
-                attn.o_proj = Fp8Linear.from_linears((attn.o_proj,), scratch)
+                attn.o_proj = cls.from_linears((attn.o_proj,), scratch)
             if "gate_up_proj" not in skip:
-                mlp.gate_up_proj = Fp8Linear.from_linears((mlp.gate_proj, mlp.up_proj), scratch)
+                mlp.gate_up_proj = cls.from_linears((mlp.gate_proj, mlp.up_proj), scratch)
                 mlp.gate_proj = mlp.up_proj = None
             if "down_proj" not in skip:
-                mlp.down_proj = Fp8Linear.from_linears((mlp.down_proj,), scratch)
+                mlp.down_proj = cls.from_linears((mlp.down_proj,), scratch)
         if "lm_head" not in skip:
-            self.lm_head = Fp8Linear.from_linears((self.lm_head,), scratch)
+            self.lm_head = cls.from_linears((self.lm_head,), scratch)
         self.weights_quantized = True
 
     def maybe_invalidate(self):

@@ -1138,6 +1138,50 @@ HYD_API size_t hyd_linear_w8_workspace_bytes(int32_t M, int32_t N, int32_t K);
 HYD_API int hyd_linear_w8(const hyd_linear_w8_params* p, void* stream);
 HYD_API int hyd_weight_widen(const hyd_weight_widen_params* p, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 4-bit linear-layer weights (hydragen_amd/weight_quant.py is the definition): W [N, K], K % 32 == 0, is stored as
+ *   w4    uint8 [N, K / 2]   OCP e2m1 codes (sign, magnitudes 0 0.5 1 1.5 2 3 4 6): byte i of a row holds k = 2 i in its low
+ *                            nibble and k = 2 i + 1 in its high nibble;
+ *   shift uint8 [N, K / 32]  0..12, one per group of 32 consecutive k;
+ *   scale float [N]          a power of two per output channel;
+ * and means e2m1(code) * 2^-shift[n, k / 32] * scale[n].  e2m1 * 2^-shift is exact in bf16 and f16 whatever the row's magnitude;
+ * scale[n] is applied to the fp32 sum as in hyd_linear_w8.  New symbols and structs only: the version stays 500.
+ *
+ * hyd_linear_w4:  y[m, n] = round16(scale[n] * sum_k x[m, k] * e2m1(w4[n, k]) * 2^-shift[n, k / 32]),  fp32 accumulation on the
+ * 16-bit matrix cores, one rounding to the dtype of x.  x, y, the workspace, the split plan, reproducibility and row independence
+ * are hyd_linear_w8's; w4 and shift are contiguous and 16-byte aligned.  The refusals are hyd_linear_w8's with K % 32 != 0 in
+ * place of K % 16, and a null or misaligned shift.
+ * hyd_weight_widen_w4:  out[n, k] = (e2m1(code) * 2^-shift) * scale[n] as an fp32 product rounded once to dtype --
+ * weight_quant.dequantize_weight_fp4 bit for bit; out as in hyd_weight_widen.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct hyd_linear_w4_params {
+    const void* x;           /* [M, K] dtype, row m at x + m * x_row_stride                                   */
+    const void* w4;          /* [N, K / 2] bytes, contiguous                                                  */
+    const void* shift;       /* [N, K / 32] bytes, contiguous                                                 */
+    const float* scale;      /* [N]                                                                           */
+    void* y;                 /* [M, N] dtype, row m at y + m * y_row_stride                                   */
+    void* workspace;         /* fp32 partial sums of a split plan; may be NULL when the query answers 0       */
+    size_t workspace_bytes;
+    int64_t x_row_stride, y_row_stride;
+    int32_t M, N, K;
+    int32_t dtype;           /* HYD_F16 | HYD_BF16                                                            */
+    } hyd_linear_w4_params;
+
+typedef struct hyd_weight_widen_w4_params {
+    const void* w4;          /* [N, K / 2] bytes, contiguous                                                  */
+    const void* shift;       /* [N, K / 32] bytes, contiguous                                                 */
+    const float* scale;      /* [N]                                                                           */
+    void* out;               /* [N, K] dtype, row n at out + n * out_row_stride                               */
+    int64_t out_row_stride;
+    int32_t N, K;
+    int32_t dtype;           /* HYD_F16 | HYD_BF16                                                            */
+    int32_t reserved;
+    } hyd_weight_widen_w4_params;
+
+HYD_API size_t hyd_linear_w4_workspace_bytes(int32_t M, int32_t N, int32_t K);
+HYD_API int hyd_linear_w4(const hyd_linear_w4_params* p, void* stream);
+HYD_API int hyd_weight_widen_w4(const hyd_weight_widen_w4_params* p, void* stream);
+
 HYD_API int hyd_version(void);
 HYD_API const char* hyd_last_error_string(void);
 
