@@ -1,0 +1,62 @@
+// C ABI, the mixture-of-experts MLP (moe.hip): hyd_moe_workspace_bytes, hyd_moe_mlp.
+#include "api_core.h"
+
+using namespace hyd;
+
+namespace {
+
+// the ranges of moe.hip; `say` false: the size query's silent form
+int check_moe_shapes(int T, int E, int k, int H, int I, int dtype, bool say) {
+    const bool ok_dtype = dtype == HYD_F16 || dtype == HYD_BF16;
+    const bool ok = T >= 1 && T <= kMoeMaxRows && E >= 1 && E <= kMoeMaxExperts && k >= 1 && k <= kMoeMaxTopK && k <= E && H >= 64 && H % 64 == 0 &&
+                    I >= 32 && I % 32 == 0;
+    if (!say) return ok && ok_dtype ? HYD_OK : HYD_ERR_BAD_ARG;
+    if (!ok_dtype) return fail(HYD_ERR_UNSUPPORTED, "dtype %d: f16 / bf16 activations and expert weights", dtype);
+    if (T < 1 || T > kMoeMaxRows) return fail(HYD_ERR_BAD_ARG, "T %d: 1 to %d rows per call (longer inputs are chunked by the caller)", T, kMoeMaxRows);
+    if (E < 1 || E > kMoeMaxExperts) return fail(HYD_ERR_BAD_ARG, "E %d: 1 to %d experts", E, kMoeMaxExperts);
+    if (k < 1 || k > kMoeMaxTopK) return fail(HYD_ERR_BAD_ARG, "k %d: 1 to %d experts per row", k, kMoeMaxTopK);
+    if (k > E) return fail(HYD_ERR_BAD_ARG, "k %d exceeds E %d", k, E);
+    if (H < 64 || H % 64 != 0) return fail(HYD_ERR_BAD_ARG, "H %d must be a positive multiple of 64", H);
+    if (I < 32 || I % 32 != 0) return fail(HYD_ERR_BAD_ARG, "I %d must be a positive multiple of 32", I);
+    return HYD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t hyd_moe_workspace_bytes(int32_t T, int32_t E, int32_t k, int32_t H, int32_t I, int32_t dtype) {
+    if (check_moe_shapes(T, E, k, H, I, dtype, false)) return 0;
+    return moe_layout(T, E, k, H, I).bytes;
+}
+
+int hyd_moe_mlp(const hyd_moe_params* p, void* stream) {
+    if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
+    int rc = check_moe_shapes(p->T, p->E, p->k, p->H, p->I, p->dtype, true);
+    if (rc) return rc;
+    if (p->renormalize != 0 && p->renormalize != 1) return fail(HYD_ERR_BAD_ARG, "renormalize %d must be 0 or 1", p->renormalize);
+    if ((rc = check_ptrs_align({{p->x, "x"}, {p->gate_up, "gate_up"}, {p->down, "down"}, {p->y, "y"}}))) return rc;
+    if ((rc = check_not_null({{p->logits, "logits"}}))) return rc;
+    if ((rc = check_elem_align({{p->logits, 2, "logits"}, {p->ids_out, 4, "ids_out"}, {p->weights_out, 4, "weights_out"}}))) return rc;
+    if ((rc = check_strides8({{p->x_row_stride, "x_row_stride"}, {p->y_row_stride, "y_row_stride"}}))) return rc;
+    if (p->x_row_stride < p->H || p->y_row_stride < p->H)
+        return fail(HYD_ERR_BAD_ARG, "x_row_stride %lld or y_row_stride %lld < H %d", (long long)p->x_row_stride, (long long)p->y_row_stride, p->H);
+    const MoeLayout l = moe_layout(p->T, p->E, p->k, p->H, p->I);
+    if (!p->workspace || p->workspace_bytes < l.bytes)
+        return fail(HYD_ERR_WORKSPACE, "moe_mlp needs %zu workspace bytes for T %d E %d k %d H %d I %d, got %zu", l.bytes, p->T, p->E, p->k, p->H, p->I,
+                    p->workspace ? p->workspace_bytes : (size_t)0);
+    if (misaligned(p->workspace, 16)) return fail(HYD_ERR_WORKSPACE, "workspace must be 16-byte aligned");
+    char* ws = static_cast<char*>(p->workspace);
+    MoeArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = p->x; a.logits = p->logits; a.gate_up = p->gate_up; a.down = p->down; a.y = p->y;
+    a.ids = reinterpret_cast<int32_t*>(ws + l.ids); a.weights = reinterpret_cast<float*>(ws + l.weights);
+    a.counts = reinterpret_cast<int32_t*>(ws + l.counts); a.offsets = reinterpret_cast<int32_t*>(ws + l.offsets);
+    a.slots = reinterpret_cast<int32_t*>(ws + l.slots); a.act = ws + l.act; a.yslot = reinterpret_cast<float*>(ws + l.yslot);
+    a.ids_out = p->ids_out; a.weights_out = p->weights_out;
+    a.xs = p->x_row_stride; a.ys = p->y_row_stride;
+    a.T = p->T; a.E = p->E; a.k = p->k; a.H = p->H; a.I = p->I; a.renorm = p->renormalize;
+    return launched(launch_moe_mlp(a, p->dtype, static_cast<hipStream_t>(stream)), "moe_mlp kernel launches");
+}
+
+}  // extern "C"

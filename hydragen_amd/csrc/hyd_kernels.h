@@ -356,7 +356,36 @@ struct WeightWidenW4Args {  // linear_w4.hip: out = dequantize_weight_fp4(w4, sh
     int32_t N, K;
 };
 
+constexpr int kMoeMaxRows = 128;     // rows per hyd_moe_mlp call (HYD_MOE_MAX_ROWS)
+constexpr int kMoeMaxExperts = 256;  // one wave holds a row's logits, four per lane
+constexpr int kMoeMaxTopK = 8;
+
+struct MoeLayout {  // moe.hip: the slices of hyd_moe_mlp's workspace (byte offsets, each a multiple of 16), from the shapes alone
+    size_t ids, weights, counts, offsets, slots, act, yslot, bytes;
+};
+
+struct MoeArgs {  // moe.hip: route -> group -> gate|up + SwiGLU -> down * weight -> combine
+    const void* x;        // [T, H], row stride xs
+    const void* logits;   // [T, E] contiguous
+    const void* gate_up;  // [E, 2 I, H]
+    const void* down;     // [E, H, I]
+    void* y;              // [T, H], row stride ys
+    int32_t* ids;         // [T k] expert of slot t k + j
+    float* weights;       // [T k]
+    int32_t* counts;      // [E]
+    int32_t* offsets;     // [E + 1]
+    int32_t* slots;       // [T k] slot numbers grouped by expert, ascending inside an expert
+    void* act;            // [T k, I] 16-bit
+    float* yslot;         // [T k, H]
+    int32_t* ids_out;     // optional copies of ids / weights
+    float* weights_out;
+    int64_t xs, ys;
+    int32_t T, E, k, H, I, renorm;
+};
+
 // launchers (defined next to the kernels); return hipError_t as int
+MoeLayout moe_layout(int T, int E, int k, int H, int I);    // moe.hip, shapes only
+int launch_moe_mlp(const MoeArgs& a, int dtype, hipStream_t s);  // moe.hip: the five launches of one routed MLP
 LinearW8Plan plan_linear_w8(int M, int N, int K);                                        // linear_w8.hip, shapes only
 int launch_linear_w8(const LinearW8Args& a, const LinearW8Plan& pl, int dtype, hipStream_t s);  // linear_w8.hip
 int launch_linear_w8_reduce(const LinearW8Args& a, int dtype, hipStream_t s);            // linear_w8.hip: the split slices' second launch alone

@@ -17,7 +17,7 @@ Decode runs under a HIP graph exactly like the reference's CUDA-graph wrapper (l
 
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import InitVar, dataclass
 from typing import List, Optional, Union
 
 import torch
@@ -30,6 +30,7 @@ from .flash import flash_attention, flash_attention_seqlen, padded_head_dim
 from . import kv_quant as _kv_quant
 from .kv_quant import FP8_DTYPE, dequantize_kv, quantize_kv, scale_constant
 from .tp import all_reduce_sum
+from .moe import MoeMLP
 from .weight_quant import FP4_DTYPE, Fp4Linear, Fp8Linear, W8Scratch
 
 
@@ -51,6 +52,16 @@ class LlamaConfig:
     # Qwen3-style attention (new fields stay at the END: from_hf_model and callers build the config positionally)
     head_dim: Optional[int] = None  # None: hidden_size // num_attention_heads
     qk_norm: bool = False           # RMSNorm over every query head and every key head between the projection and RoPE
+    # mixture-of-experts MLPs (moe.py): every layer's `mlp` is a MoeMLP when num_experts > 0.  Constructor arguments and attributes,
+    # but not dataclass fields: fields() and asdict() -- the config.json that make_tp_files writes -- of a dense model stay as they were
+    num_experts: InitVar[int] = 0
+    num_experts_per_tok: InitVar[int] = 0
+    moe_intermediate_size: InitVar[Optional[int]] = None  # None: intermediate_size
+    norm_topk_prob: InitVar[bool] = True                  # the k route weights are divided by their sum
+
+    def __post_init__(self, num_experts, num_experts_per_tok, moe_intermediate_size, norm_topk_prob):
+        self.num_experts, self.num_experts_per_tok = num_experts, num_experts_per_tok
+        self.moe_intermediate_size, self.norm_topk_prob = moe_intermediate_size, norm_topk_prob
 
     def get_head_dim(self) -> int:
         """The one place that knows a head's width: `head_dim` when the checkpoint states it, else hidden_size // heads."""
@@ -713,7 +724,11 @@ class HydragenLlamaDecoderLayer(nn.Module):
     def __init__(self, config: LlamaConfig):
         super().__init__()
         self.self_attn = HydragenLlamaAttention(config)
-        self.mlp = LlamaMLP(config)
+        if config.num_experts > 0:
+            self.mlp = MoeMLP(config.hidden_size, config.moe_intermediate_size or config.intermediate_size, config.num_experts,
+                              config.num_experts_per_tok, config.norm_topk_prob)
+        else:
+            self.mlp = LlamaMLP(config)
         self.input_layernorm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
         self.post_attention_layernorm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
 
@@ -913,24 +928,40 @@ class HydragenLlamaForCausalLM(nn.Module):
 
     @classmethod
     def from_hf_model(cls, hf):
-        """The model of an in-memory transformers `LlamaForCausalLM` or `Qwen3ForCausalLM` (fp16 / bf16): its config mapped onto
-        LlamaConfig -- `head_dim` where the config states one, `qk_norm` when the state dict carries `self_attn.q_norm` or the
-        model type is qwen3 -- and its state dict loaded, every tensor accounted for."""
+        """The model of an in-memory transformers `LlamaForCausalLM`, `Qwen3ForCausalLM`, `MixtralForCausalLM` or
+        `Qwen3MoeForCausalLM` (fp16 / bf16): its config mapped onto LlamaConfig -- `head_dim` where the config states one, `qk_norm`
+        when the state dict carries `self_attn.q_norm` or the model type is qwen3 / qwen3_moe, the experts' count, top-k, width and
+        renormalisation (Mixtral always renormalises, Qwen3-MoE by `norm_topk_prob`) -- and its state dict loaded, every tensor
+        accounted for.  Every layer of a model with experts must be a routed one, without shared experts."""
         if hf.dtype not in (torch.float16, torch.bfloat16):
             raise ValueError(f"Model must be in float16 or bfloat16, not {hf.dtype}")
         c = hf.config
         kind = getattr(c, "model_type", "llama")
-        if kind not in ("llama", "qwen3"):
-            raise NotImplementedError(f"model type '{kind}': llama and qwen3 are implemented")
+        if kind not in ("llama", "qwen3", "mixtral", "qwen3_moe"):
+            raise NotImplementedError(f"model type '{kind}': llama, qwen3, mixtral and qwen3_moe are implemented")
         if getattr(c, "use_sliding_window", False):
             raise NotImplementedError("sliding-window attention is not implemented")
+        moe = {}
+        if kind in ("mixtral", "qwen3_moe"):
+            if getattr(c, "sliding_window", None) is not None and (kind == "mixtral" or getattr(c, "use_sliding_window", False)):
+                raise NotImplementedError(f"sliding_window = {c.sliding_window}: sliding-window attention is not implemented")
+            if getattr(c, "mlp_only_layers", None):
+                raise NotImplementedError(f"mlp_only_layers = {list(c.mlp_only_layers)}: every layer must carry experts")
+            if getattr(c, "decoder_sparse_step", 1) != 1:
+                raise NotImplementedError(f"decoder_sparse_step = {c.decoder_sparse_step}: every layer must carry experts")
+            if getattr(c, "shared_expert_intermediate_size", 0) or getattr(c, "n_shared_experts", 0):
+                raise NotImplementedError("shared experts are not implemented")
+            mixtral = kind == "mixtral"
+            moe = dict(num_experts=c.num_local_experts if mixtral else c.num_experts, num_experts_per_tok=c.num_experts_per_tok,
+                       moe_intermediate_size=c.intermediate_size if mixtral else c.moe_intermediate_size,
+                       norm_topk_prob=True if mixtral else bool(c.norm_topk_prob))
         sd = hf.state_dict()
         rp = getattr(c, "rope_parameters", None) or {}
         cfg = LlamaConfig(c.hidden_size, c.intermediate_size, c.num_hidden_layers, c.num_attention_heads,
                           c.num_key_value_heads, c.vocab_size, c.rms_norm_eps,
                           getattr(c, "rope_theta", rp.get("rope_theta", 10000.0)), c.max_position_embeddings,
                           getattr(c, "attention_bias", False), c.pad_token_id, getattr(c, "head_dim", None),
-                          kind == "qwen3" or any(k.endswith("self_attn.q_norm.weight") for k in sd))
+                          kind in ("qwen3", "qwen3_moe") or any(k.endswith("self_attn.q_norm.weight") for k in sd), **moe)
         scaling = getattr(c, "rope_scaling", None) or {}
         rope = scaling.get("rope_type", scaling.get("type", "default")) or rp.get("rope_type", "default")
         if rope not in ("default", None):
@@ -977,6 +1008,8 @@ class HydragenLlamaForCausalLM(nn.Module):
         if dtype not in (FP8_DTYPE, FP4_DTYPE):
             raise NotImplementedError(f"quantize_weights(dtype={dtype}): {FP8_DTYPE} and {FP4_DTYPE} are the formats")
         cls = Fp4Linear if dtype == FP4_DTYPE else Fp8Linear
+        if self.config.num_experts > 0:
+            raise NotImplementedError("quantize_weights() on a model with experts: the expert kernels take 16-bit weights only")
         if self.weights_quantized:
             raise RuntimeError("quantize_weights() was already called on this model")
         skip = set(skip)

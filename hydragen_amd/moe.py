@@ -1,7 +1,7 @@
 """
-Mixture-of-experts MLP: the DEFINITION of routing and of the expert products, and the elementwise error bound that goes with it.
-A preparatory module: nothing in the model shell uses it yet -- `from_hf_model` still refuses mixture-of-experts checkpoints and
-`LlamaConfig` has no experts -- because there is no GPU path.  This is what a device-routed expert kernel will be held to.
+Mixture-of-experts MLP: the DEFINITION of routing and of the expert products with the elementwise error bound that goes with it,
+and the device path that is held to them -- `moe_mlp` (hyd_moe_mlp, csrc/moe.hip: routing, grouping and the expert products on the
+device, capture-safe) and `MoeMLP`, the module a decoder layer of a model with experts carries (llama.py).
 
     logits = round16(x @ router_w^T)
     ids, weights = the k largest logits of a row, descending, ties to the lower index; softmax(logits)[ids], renormalized or not
@@ -13,8 +13,13 @@ The weight layouts are transformers 5's (`experts.gate_up_proj` [E, 2 I, H], `ex
 
 from __future__ import annotations
 
+import ctypes as C
+from typing import Optional
+
 import torch
-from torch import Tensor
+from torch import Tensor, nn
+
+from . import _lib
 
 
 # ---- the definition ----------------------------------------------------------------------------------------------------------------
@@ -54,22 +59,24 @@ def _slot_terms(x: Tensor, gate_up: Tensor, down: Tensor, ids: Tensor):
         yield j, y, s_act, s_gu, s_wd
 
 
-def _routed(x: Tensor, router_w: Tensor, k: int, renormalize: bool):
-    return route_reference(torch.nn.functional.linear(x, router_w), k, renormalize)  # the product stays a 16-bit F.linear
+def _routed(x: Tensor, router_w: Tensor, k: int, renormalize: bool, logits: Optional[Tensor] = None):
+    # the product stays a 16-bit F.linear; `logits`: the ones a device call routed by (a GEMM's last bit may depend on the device)
+    return route_reference(torch.nn.functional.linear(x, router_w) if logits is None else logits, k, renormalize)
 
 
-def moe_reference(x: Tensor, router_w: Tensor, gate_up: Tensor, down: Tensor, k: int, renormalize: bool) -> Tensor:
+def moe_reference(x: Tensor, router_w: Tensor, gate_up: Tensor, down: Tensor, k: int, renormalize: bool, logits: Optional[Tensor] = None) -> Tensor:
     """The definition in float64: x [T, H], router_w [E, H], gate_up [E, 2 I, H], down [E, H, I] (all of one 16-bit dtype) ->
     [T, H] float64.  Two 16-bit roundings per token and expert on the way -- the router logits and act -- exactly where the
-    kernels round; the output's own rounding is left to the caller of the comparison."""
-    ids, w = _routed(x, router_w, k, renormalize)
+    kernels round; the output's own rounding is left to the caller of the comparison.  `logits` [T, E], when given, are routed by
+    in place of round16(x @ router_w^T)."""
+    ids, w = _routed(x, router_w, k, renormalize, logits)
     out = x.new_zeros(x.shape, dtype=torch.float64)
     for j, y, *_ in _slot_terms(x, gate_up, down, ids):
         out += w[:, j, None] * y
     return out
 
 
-def moe_error_bound(x: Tensor, router_w: Tensor, gate_up: Tensor, down: Tensor, k: int, renormalize: bool) -> Tensor:
+def moe_error_bound(x: Tensor, router_w: Tensor, gate_up: Tensor, down: Tensor, k: int, renormalize: bool, logits: Optional[Tensor] = None) -> Tensor:
     """Elementwise bound [T, H] (float64) on |kernel output - moe_reference| that goes with the definition, from sums of absolute
     products; u16 = 2^-8 (bfloat16) or 2^-11 (float16) is half a 16-bit ulp, relative.  With y_j = act_j . wd (float64) and w_j the
     route weight, a kernel's out = round16(sum_j fl(w_j' * fl(act_j' . wd))) differs from sum_j w_j y_j by at most the sum of
@@ -83,8 +90,8 @@ def moe_error_bound(x: Tensor, router_w: Tensor, gate_up: Tensor, down: Tensor, 
       - the route weight (fp32 exponentials: within 4 2^-23 relative of the float64 softmax), its fp32 product with the row and the
         k - 1 fp32 additions of the combine: (k + 5) 2^-23 |w_j y_j| in all;
     all weighted by w_j and summed over j.  float16 adds the absolute half-steps below its normal range: 2^-25 sum_i |wd_i| per act
-    row and 2^-25 for the output."""
-    ids, w = _routed(x, router_w, k, renormalize)
+    row and 2^-25 for the output.  `logits` as in moe_reference."""
+    ids, w = _routed(x, router_w, k, renormalize, logits)
     H, I = x.shape[1], down.shape[2]
     u16, tiny = (2.0 ** -8, 0.0) if x.dtype == torch.bfloat16 else (2.0 ** -11, 2.0 ** -25)
     out = x.new_zeros(x.shape, dtype=torch.float64)
@@ -94,3 +101,105 @@ def moe_error_bound(x: Tensor, router_w: Tensor, gate_up: Tensor, down: Tensor, 
         out += wj * y
         bound += wj * ((I * 2.0 ** -23 + u16) * s_act + H * 2.0 ** -23 * s_gu + (k + 5) * 2.0 ** -23 * y.abs() + tiny * s_wd)
     return bound + u16 * out.abs() + tiny
+
+
+# ---- the device path ---------------------------------------------------------------------------------------------------------------
+MOE_MAX_ROWS = 128  # HYD_MOE_MAX_ROWS: rows per hyd_moe_mlp call; moe_mlp chunks longer inputs (the MLP is row-independent: exact)
+
+
+class MoeParams(C.Structure):  # hyd_moe_params
+    _fields_ = [
+        ("x", C.c_void_p), ("logits", C.c_void_p), ("gate_up", C.c_void_p), ("down", C.c_void_p), ("y", C.c_void_p), ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_size_t), ("ids_out", C.c_void_p), ("weights_out", C.c_void_p), ("x_row_stride", C.c_int64), ("y_row_stride", C.c_int64),
+        ("T", C.c_int32), ("E", C.c_int32), ("k", C.c_int32), ("H", C.c_int32), ("I", C.c_int32), ("renormalize", C.c_int32), ("dtype", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+_workspaces: dict = {}  # (device, rows, E, k, H, I, dtype) -> uint8 tensor: allocated on first use, so that a graph's replay allocates nothing
+
+
+def _workspace(device, T, E, k, H, I, dtype) -> Tensor:
+    key = (device, T, E, k, H, I, dtype)
+    ws = _workspaces.get(key)
+    if ws is None:
+        need = int(_lib.load().hyd_moe_workspace_bytes(T, E, k, H, I, _lib.HYD_F16 if dtype == torch.float16 else _lib.HYD_BF16))
+        ws = _workspaces[key] = torch.empty((max(need, 16),), dtype=torch.uint8, device=device)
+    return ws
+
+
+def moe_rows(x: Tensor, logits: Tensor, gate_up: Tensor, down: Tensor, k: int, renormalize: bool, out: Tensor, ids_out: Optional[Tensor] = None,
+             weights_out: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
+    """One hyd_moe_mlp call on the current stream: x [T, H] (T <= MOE_MAX_ROWS, unit last stride), logits [T, E] contiguous, into
+    out [T, H] (unit last stride); ids_out int32 / weights_out float32 [T, k] receive the routing.  The C layer refuses what is
+    out of range."""
+    from .flash import _require_gpu, _stream
+
+    _require_gpu(x, logits, gate_up, down, out, ids_out, weights_out, workspace)
+    (T, H), E, I = x.shape, gate_up.shape[0], down.shape[2]
+    if not (x.dtype == logits.dtype == gate_up.dtype == down.dtype == out.dtype) or x.dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError("x, logits, gate_up, down and out must share one of float16 / bfloat16")
+    if tuple(logits.shape) != (T, E) or tuple(gate_up.shape) != (E, 2 * I, H) or tuple(down.shape) != (E, H, I) or tuple(out.shape) != (T, H):
+        raise ValueError(f"shapes: x {tuple(x.shape)}, logits {tuple(logits.shape)}, gate_up {tuple(gate_up.shape)}, down {tuple(down.shape)}, out {tuple(out.shape)}")
+    if x.stride(1) != 1 or out.stride(1) != 1 or not (logits.is_contiguous() and gate_up.is_contiguous() and down.is_contiguous()):
+        raise ValueError("x and out need a unit last stride; logits, gate_up and down must be contiguous")
+    for name, t, dt in (("ids_out", ids_out, torch.int32), ("weights_out", weights_out, torch.float32)):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != (T, k) or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous [{T}, {k}] {dt} tensor")
+    if workspace is None:
+        workspace = _workspace(x.device, T, E, k, H, I, x.dtype)
+    p = MoeParams()
+    p.x, p.logits, p.gate_up, p.down, p.y = x.data_ptr(), logits.data_ptr(), gate_up.data_ptr(), down.data_ptr(), out.data_ptr()
+    p.workspace, p.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    p.ids_out = None if ids_out is None else ids_out.data_ptr()
+    p.weights_out = None if weights_out is None else weights_out.data_ptr()
+    p.x_row_stride, p.y_row_stride = (x.stride(0), out.stride(0)) if T > 1 else (H, H)  # (one row: the stride is never used)
+    p.T, p.E, p.k, p.H, p.I, p.renormalize = T, E, k, H, I, int(bool(renormalize))
+    p.dtype = _lib.HYD_F16 if x.dtype == torch.float16 else _lib.HYD_BF16
+    _lib.check(_lib.load().hyd_moe_mlp(C.byref(p), _stream()))
+    return out
+
+
+def moe_mlp(x: Tensor, router_w: Tensor, gate_up: Tensor, down: Tensor, k: int, renormalize: bool, *, return_routing: bool = False):
+    """The routed MLP of x [..., H]: logits = F.linear(x, router_w) in the 16-bit dtype, then one hyd_moe_mlp call per chunk of
+    MOE_MAX_ROWS rows (rows are independent, so chunking is exact).  The workspace is cached per (device, shapes): a captured graph
+    replays without allocating it.  CPU tensors run the definition, rounded once to the dtype.  `return_routing`: (y, ids [T, k]
+    int32, weights [T, k] float32)."""
+    x2 = x.reshape(-1, x.shape[-1])
+    T, E = x2.shape[0], gate_up.shape[0]
+    logits = nn.functional.linear(x2, router_w)
+    if not x.is_cuda:
+        y = moe_reference(x2, router_w, gate_up, down, k, renormalize, logits=logits).to(x.dtype).view(x.shape)
+        if not return_routing:
+            return y
+        ids, w = route_reference(logits, k, renormalize)
+        return y, ids.int(), w.float()
+    y = torch.empty_like(x2)
+    ids = torch.empty((T, k), dtype=torch.int32, device=x.device) if return_routing else None
+    w = torch.empty((T, k), dtype=torch.float32, device=x.device) if return_routing else None
+    for r in range(0, T, MOE_MAX_ROWS):
+        rows = slice(r, min(T, r + MOE_MAX_ROWS))
+        moe_rows(x2[rows], logits[rows], gate_up, down, k, renormalize, y[rows], None if ids is None else ids[rows], None if w is None else w[rows])
+    y = y.view(x.shape)
+    return (y, ids, w) if return_routing else y
+
+
+class _Experts(nn.Module):
+    def __init__(self, E: int, H: int, I: int):
+        super().__init__()
+        self.gate_up_proj = nn.Parameter(torch.empty(E, 2 * I, H))
+        self.down_proj = nn.Parameter(torch.empty(E, H, I))
+
+
+class MoeMLP(nn.Module):
+    """A decoder layer's routed MLP under transformers 5's parameter names and layouts (`gate.weight` [E, H],
+    `experts.gate_up_proj` [E, 2 I, H], `experts.down_proj` [E, H, I]: Mixtral's and Qwen3-MoE's alike under `model.layers.N.mlp.`)."""
+
+    def __init__(self, hidden_size: int, intermediate_size: int, num_experts: int, top_k: int, renormalize: bool):
+        super().__init__()
+        self.gate = nn.Linear(hidden_size, num_experts, bias=False)
+        self.experts = _Experts(num_experts, hidden_size, intermediate_size)
+        self.top_k, self.renormalize = top_k, renormalize
+
+    def forward(self, x: Tensor) -> Tensor:
+        return moe_mlp(x, self.gate.weight, self.experts.gate_up_proj, self.experts.down_proj, self.top_k, self.renormalize)

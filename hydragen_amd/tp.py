@@ -130,6 +130,8 @@ def _refuse_quantized(model, what: str) -> None:
     if any(isinstance(m, Fp8Linear) for m in model.modules()):
         raise RuntimeError(f"{what} on a model with fp8 weights: the scales are per output channel of the weights as they were when "
                            "quantize_weights() ran -- shard first (apply_tp / from_pretrained_tp), then quantize each rank's shard")
+    if getattr(getattr(model, "config", None), "num_experts", 0) > 0:
+        raise NotImplementedError(f"{what} on a model with experts: the expert kernels are not tensor-parallel")
 
 
 def apply_tp(model, rank: Optional[int] = None, world_size: Optional[int] = None) -> None:

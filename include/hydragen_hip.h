@@ -1182,6 +1182,48 @@ HYD_API size_t hyd_linear_w4_workspace_bytes(int32_t M, int32_t N, int32_t K);
 HYD_API int hyd_linear_w4(const hyd_linear_w4_params* p, void* stream);
 HYD_API int hyd_weight_widen_w4(const hyd_weight_widen_w4_params* p, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mixture-of-experts MLP for decode-sized calls (hydragen_amd/moe.py is the definition; csrc/moe.hip the kernels).  From the 16-bit
+ * router logits [T, E] of the rows x [T, H]:
+ *   ids, weights   the k largest logits of a row in descending order, equal logits to the lower expert; fp32 softmax over all E
+ *                  logits at the ids, divided by their sum when `renormalize`;
+ *   act[t, j]    = round16(silu(x[t] . Wg[e]^T) * (x[t] . Wu[e]^T)),  e = ids[t, j];  gate_up[e] = Wg[e] rows, then Wu[e] rows;
+ *   y[t]         = round16(sum_j weights[t, j] * (act[t, j] . Wd[e]^T))   fp32, added in j order, one rounding.
+ * Five launches on `stream` whose grids depend on the shapes alone; nothing is read back, nothing allocated, no float atomics:
+ * capture-safe, and two calls give the same bits.  Only the chosen experts' weights are read.  A row of y depends on its own
+ * row of x and of logits only.
+ * Ranges: 1 <= T <= HYD_MOE_MAX_ROWS (longer inputs: call per chunk of rows), 1 <= E <= 256, 1 <= k <= min(E, 8), H % 64 == 0,
+ * I % 32 == 0.  x and y are row-strided views (elements, multiples of 8, >= H; 16-byte aligned); logits, gate_up [E, 2 I, H]
+ * and down [E, H, I] are contiguous, the weights 16-byte aligned.  The workspace (16-byte aligned) holds, each slice rounded up
+ * to 16 bytes: ids int32 [T k], weights float [T k], counts int32 [E], offsets int32 [E + 1], slots int32 [T k], act 16-bit
+ * [T k, I], yslot float [T k, H]; hyd_moe_workspace_bytes answers their sum, or 0 for shapes outside the ranges.
+ * ids_out / weights_out (optional, [T, k]) receive the routing.
+ * HYD_ERR_BAD_ARG: null params / pointers, misalignment, a size outside its range, a short stride.  HYD_ERR_UNSUPPORTED: dtype
+ * other than HYD_F16 / HYD_BF16.  HYD_ERR_WORKSPACE: workspace null, misaligned or too small.  All before any launch.
+ * New symbols and a new struct only: the version stays 500.
+ * ------------------------------------------------------------------------------------------ */
+#define HYD_MOE_MAX_ROWS 128
+
+typedef struct hyd_moe_params {
+    const void* x;           /* [T, H] dtype, row t at x + t * x_row_stride                                   */
+    const void* logits;      /* [T, E] dtype, contiguous: the router product, rounded to dtype                */
+    const void* gate_up;     /* [E, 2 I, H] dtype, contiguous                                                 */
+    const void* down;        /* [E, H, I] dtype, contiguous                                                   */
+    void* y;                 /* [T, H] dtype, row t at y + t * y_row_stride                                   */
+    void* workspace;
+    size_t workspace_bytes;
+    int32_t* ids_out;        /* [T, k] or NULL                                                                */
+    float* weights_out;      /* [T, k] or NULL                                                                */
+    int64_t x_row_stride, y_row_stride;
+    int32_t T, E, k, H, I;
+    int32_t renormalize;     /* 0 | 1                                                                         */
+    int32_t dtype;           /* HYD_F16 | HYD_BF16                                                            */
+    int32_t reserved;
+    } hyd_moe_params;
+
+HYD_API size_t hyd_moe_workspace_bytes(int32_t T, int32_t E, int32_t k, int32_t H, int32_t I, int32_t dtype);
+HYD_API int hyd_moe_mlp(const hyd_moe_params* p, void* stream);
+
 HYD_API int hyd_version(void);
 HYD_API const char* hyd_last_error_string(void);
 

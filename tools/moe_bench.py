@@ -1,0 +1,151 @@
+"""Mixture-of-experts MLP: what one layer's moe_mlp (router GEMM + hyd_moe_mlp's five launches) costs at decode sizes, against the
+time to stream the weights it has to read and against transformers' own block.  Writes the tables of profiles/moe.md (markdown, to
+--out or stdout) -- nothing here is promised in advance.
+
+    python tools/moe_bench.py [--out profiles/moe.md] [--rows 1,8,32,128] [--rounds 5] [--skip-eager]
+
+Per shape -- a Mixtral-8x7B layer (E 8, k 2, H 4096, I 14336) and a Qwen3-30B-A3B layer (E 128, k 8, H 2048, I 768), bf16, random
+weights -- and per row count T: a ring of distinct layers whose ACTIVATED experts together exceed the 256 MB Infinity Cache, so every
+call streams its weights from HBM as it does inside a model; one pass over the ring is captured in a HIP graph (device time, no launch
+gaps), the figure is the median over the rounds, per layer.  Beside it: the floor -- the bytes of the distinct activated experts of a
+layer (mean over the ring: 3 H I 2 bytes each) at 8 TB/s -- and transformers' sparse block on the same weights, run eagerly (it
+synchronises with the host to loop over the experts that were hit, so it cannot be captured; wall time per layer with a device
+synchronisation at the end of the ring)."""
+from __future__ import annotations
+
+import argparse
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+
+DEV = "cuda:0"
+SHAPES = [("Mixtral-8x7B layer", "mixtral", 8, 2, 4096, 14336), ("Qwen3-30B-A3B layer", "qwen3_moe", 128, 8, 2048, 768)]
+RING_BYTES = 320 << 20  # activated bytes of a ring: beyond the 256 MB Infinity Cache
+HBM_TBS = 8.0
+
+
+def graph_of(fn):
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        fn()
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        fn()
+    return g
+
+
+def replay_us(g, calls, reps=3):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        g.replay()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e3 / (reps * calls)
+
+
+def hf_blocks(kind, layers, E, k, H, I):
+    """transformers' sparse block per ring layer, its parameters the ring's own tensors (no copy)."""
+    import transformers as tf
+
+    kw = dict(hidden_size=H, num_experts_per_tok=k, num_hidden_layers=1, num_attention_heads=4, num_key_value_heads=4, vocab_size=32)
+    if kind == "mixtral":
+        from transformers.models.mixtral.modeling_mixtral import MixtralSparseMoeBlock as Block
+        cfg = tf.MixtralConfig(num_local_experts=E, intermediate_size=I, **kw)
+    else:
+        from transformers.models.qwen3_moe.modeling_qwen3_moe import Qwen3MoeSparseMoeBlock as Block
+        cfg = tf.Qwen3MoeConfig(num_experts=E, moe_intermediate_size=I, intermediate_size=I, norm_topk_prob=True, **kw)
+    blocks = []
+    for router, gate_up, down in layers:
+        with torch.device("meta"):
+            b = Block(cfg).to(torch.bfloat16).eval()
+        b.load_state_dict({"gate.weight": router, "experts.gate_up_proj": gate_up, "experts.down_proj": down}, assign=True)
+        blocks.append(b)
+    return blocks
+
+
+def shape_table(name, kind, E, k, H, I, rows, rounds, eager, out):
+    from hydragen_amd import moe
+
+    expert_bytes = 3 * H * I * 2
+    n = max(2, RING_BYTES // (min(E, k * min(rows)) * expert_bytes) + 2)
+    gen = torch.Generator(device=DEV).manual_seed(E + H)
+    mk = lambda *s, sd: torch.randn(s, device=DEV, dtype=torch.bfloat16, generator=gen) * sd  # noqa: E731
+    layers = [(mk(E, H, sd=0.05), mk(E, 2 * I, H, sd=0.02), mk(E, H, I, sd=0.02)) for _ in range(n)]
+    blocks, why = None, "skipped"
+    if eager:
+        try:
+            blocks = hf_blocks(kind, layers, E, k, H, I)
+        except Exception as e:  # the comparison is information: say why it is missing
+            why = f"failed: {type(e).__name__}"
+    out(f"### {name}: E = {E}, k = {k}, H = {H}, I = {I} ({n} layers per ring, {E * expert_bytes / 2**20:.0f} MiB of experts per layer)\n")
+    out("| T | moe_mlp us | distinct experts hit | floor us (8 TB/s) | moe_mlp / floor | TB/s | transformers eager us | moe_mlp / eager |")
+    out("|---|---|---|---|---|---|---|---|")
+    for T in rows:
+        x = torch.randn((T, H), device=DEV, dtype=torch.bfloat16, generator=gen)
+        hit = statistics.mean(int(moe.moe_mlp(x, *l, k, True, return_routing=True)[1].unique().numel()) for l in layers)
+
+        def run():
+            for l in layers:
+                moe.moe_mlp(x, *l, k, True)
+
+        g = graph_of(run)
+        replay_us(g, n, 1)
+        us = statistics.median(replay_us(g, n) for _ in range(rounds))
+        floor = hit * expert_bytes / (HBM_TBS * 1e6)
+        eager_us = None
+        if blocks is not None:
+            try:
+                ts = []
+                with torch.no_grad():
+                    for _ in range(rounds + 1):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        for b in blocks:
+                            b(x[None])
+                        torch.cuda.synchronize()
+                        ts.append((time.perf_counter() - t0) * 1e6 / n)
+                eager_us = statistics.median(ts[1:])
+            except Exception as e:
+                blocks, why = None, f"failed: {type(e).__name__}"
+        out(f"| {T} | {us:.1f} | {hit:.1f} | {floor:.1f} | {us / floor:.2f} | {hit * expert_bytes / us * 1e-6:.2f} | "
+            + (f"{eager_us:.0f} | {us / eager_us:.3f} |" if eager_us else f"{why} | - |"))
+        del g
+    out("")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--rows", default="1,8,32,128")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--skip-eager", action="store_true")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("moe_bench.py measures on the GPU: no device found")
+    lines = []
+
+    def out(s):
+        lines.append(s)
+        print(s, flush=True)
+        if args.out:
+            Path(args.out).write_text("\n".join(lines) + "\n")
+
+    out("# Mixture-of-experts MLP: measurements\n")
+    out("One layer's `moe_mlp` (router GEMM, then route / group / gate|up + SwiGLU / down / combine) under a HIP graph, bf16, per layer of a ring "
+        "of distinct layers; the floor is the bytes of the distinct activated experts at 8 TB/s.\n")
+    for name, kind, E, k, H, I in SHAPES:
+        shape_table(name, kind, E, k, H, I, [int(r) for r in args.rows.split(",")], args.rounds, not args.skip_eager, out)
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
