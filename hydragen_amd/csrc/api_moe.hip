@@ -1,4 +1,4 @@
-// C ABI, the mixture-of-experts MLP (moe.hip): hyd_moe_workspace_bytes, hyd_moe_mlp.
+// C ABI, the mixture-of-experts MLP (moe.hip, moe_w8.hip): hyd_moe_workspace_bytes, hyd_moe_mlp, hyd_moe_mlp_w8.
 #include "api_core.h"
 
 using namespace hyd;
@@ -21,16 +21,9 @@ int check_moe_shapes(int T, int E, int k, int H, int I, int dtype, bool say) {
     return HYD_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t hyd_moe_workspace_bytes(int32_t T, int32_t E, int32_t k, int32_t H, int32_t I, int32_t dtype) {
-    if (check_moe_shapes(T, E, k, H, I, dtype, false)) return 0;
-    return moe_layout(T, E, k, H, I).bytes;
-}
-
-int hyd_moe_mlp(const hyd_moe_params* p, void* stream) {
+// the checks and the kernel arguments that hyd_moe_params and hyd_moe_w8_params share (P: either; the fields carry the same names)
+template <typename P>
+int moe_args(const P* p, MoeArgs& a) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
     int rc = check_moe_shapes(p->T, p->E, p->k, p->H, p->I, p->dtype, true);
     if (rc) return rc;
@@ -47,7 +40,6 @@ int hyd_moe_mlp(const hyd_moe_params* p, void* stream) {
                     p->workspace ? p->workspace_bytes : (size_t)0);
     if (misaligned(p->workspace, 16)) return fail(HYD_ERR_WORKSPACE, "workspace must be 16-byte aligned");
     char* ws = static_cast<char*>(p->workspace);
-    MoeArgs a;
     memset(&a, 0, sizeof(a));
     a.x = p->x; a.logits = p->logits; a.gate_up = p->gate_up; a.down = p->down; a.y = p->y;
     a.ids = reinterpret_cast<int32_t*>(ws + l.ids); a.weights = reinterpret_cast<float*>(ws + l.weights);
@@ -56,7 +48,34 @@ int hyd_moe_mlp(const hyd_moe_params* p, void* stream) {
     a.ids_out = p->ids_out; a.weights_out = p->weights_out;
     a.xs = p->x_row_stride; a.ys = p->y_row_stride;
     a.T = p->T; a.E = p->E; a.k = p->k; a.H = p->H; a.I = p->I; a.renorm = p->renormalize;
+    return HYD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t hyd_moe_workspace_bytes(int32_t T, int32_t E, int32_t k, int32_t H, int32_t I, int32_t dtype) {
+    if (check_moe_shapes(T, E, k, H, I, dtype, false)) return 0;
+    return moe_layout(T, E, k, H, I).bytes;
+}
+
+int hyd_moe_mlp(const hyd_moe_params* p, void* stream) {
+    MoeArgs a;
+    const int rc = moe_args(p, a);
+    if (rc) return rc;
     return launched(launch_moe_mlp(a, p->dtype, static_cast<hipStream_t>(stream)), "moe_mlp kernel launches");
+}
+
+int hyd_moe_mlp_w8(const hyd_moe_w8_params* p, void* stream) {
+    MoeW8Args a;
+    int rc = moe_args(p, a.c);
+    if (rc) return rc;
+    if ((rc = check_not_null({{p->gate_up_scale, "gate_up_scale"}, {p->down_scale, "down_scale"}}))) return rc;
+    if ((rc = check_elem_align({{p->gate_up_scale, 4, "gate_up_scale"}, {p->down_scale, 4, "down_scale"}}))) return rc;
+    a.gate_up_scale = p->gate_up_scale;
+    a.down_scale = p->down_scale;
+    return launched(launch_moe_mlp_w8(a, p->dtype, static_cast<hipStream_t>(stream)), "moe_mlp_w8 kernel launches");
 }
 
 }  // extern "C"

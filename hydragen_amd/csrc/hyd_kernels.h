@@ -383,9 +383,18 @@ struct MoeArgs {  // moe.hip: route -> group -> gate|up + SwiGLU -> down * weigh
     int32_t T, E, k, H, I, renorm;
 };
 
+struct MoeW8Args {  // moe_w8.hip: the same call on e4m3fn codes (c.gate_up / c.down = the code bytes) with a scale per expert and channel
+    MoeArgs c;
+    const float* gate_up_scale;  // [E, 2 I]
+    const float* down_scale;     // [E, H]
+};
+
 // launchers (defined next to the kernels); return hipError_t as int
 MoeLayout moe_layout(int T, int E, int k, int H, int I);    // moe.hip, shapes only
 int launch_moe_mlp(const MoeArgs& a, int dtype, hipStream_t s);  // moe.hip: the five launches of one routed MLP
+int launch_moe_route_group(const MoeArgs& a, int dtype, hipStream_t s);  // moe.hip: the first two of them (checks the ranges) ...
+int launch_moe_combine(const MoeArgs& a, int dtype, hipStream_t s);      // ... and the last, shared with
+int launch_moe_mlp_w8(const MoeW8Args& a, int dtype, hipStream_t s);     // moe_w8.hip: the same five launches on fp8 expert weights
 LinearW8Plan plan_linear_w8(int M, int N, int K);                                        // linear_w8.hip, shapes only
 int launch_linear_w8(const LinearW8Args& a, const LinearW8Plan& pl, int dtype, hipStream_t s);  // linear_w8.hip
 int launch_linear_w8_reduce(const LinearW8Args& a, int dtype, hipStream_t s);            // linear_w8.hip: the split slices' second launch alone

@@ -23,50 +23,19 @@
 // 16-deep chunk at or past K is replaced by zeros in both operands and never loaded.  A column of the B operand only ever meets its
 // own column of the accumulator: a row of y depends on its own row of x only.
 #include "kv_widen.h"  // widen8: hyd_weight_widen is dequantize_kv's product with the row's scale
+#include "mma_tiles.h"  // kThreads, kWaves, mfma16, widen_codes
 
 namespace hyd {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = 4;
-constexpr int kNT = 2;         // 16-channel tiles of W per wave
+constexpr int kNT = 2;        // 16-channel tiles of W per wave
 constexpr int kStepK = 128;    // k per step: two 64-deep halves, one 16-byte load of W per lane, tile and half
 constexpr int kTargetWgs = 512;  // two workgroups (eight waves) per CU before K stops being split further
 constexpr int kRowsTargetWgs = 256;  // linear_w8_rows_kernel: one workgroup per CU; 512 measured slower on four of five shapes (more split slices to write and add)
 constexpr int kXRow = 272;  // bytes of an x row of one step in LDS: 128 k x 2 B + 16 B, so that 16 rows' 16-byte reads cover all banks
 constexpr int kMinStepsPerWave = 2;
 constexpr int kMaxSplits = 16;
-
-template <typename T>
-__device__ __forceinline__ uint32_t pack_exact(float lo, float hi);
-template <>
-__device__ __forceinline__ uint32_t pack_exact<BF16>(float lo, float hi) {  // the values are bf16 values: the upper halves
-    return (__builtin_bit_cast(uint32_t, lo) >> 16) | (__builtin_bit_cast(uint32_t, hi) & 0xffff0000u);
-}
-template <>
-__device__ __forceinline__ uint32_t pack_exact<F16>(float lo, float hi) {
-    return Traits<F16>::pack2(lo, hi);
-}
-
-// 8 e4m3fn codes (the bytes of lo, then of hi) -> 8 values of T, element j in half j % 2 of dword j / 2
-template <typename T>
-__device__ __forceinline__ u32x4 widen_codes(uint32_t lo, uint32_t hi) {
-    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, true);
-    const f32x2 c = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, true);
-    return u32x4{pack_exact<T>(a[0], a[1]), pack_exact<T>(b[0], b[1]), pack_exact<T>(c[0], c[1]), pack_exact<T>(d[0], d[1])};
-}
-
-template <typename T>
-__device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c);
-template <>
-__device__ __forceinline__ f32x4 mfma16<BF16>(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4 mfma16<F16>(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 
 // the lane's W of step s: [t][j] = 16 codes of row t's tile at k = 128 s + 64 j + 16 g (wrow already points at + 16 g)
 __device__ __forceinline__ void load_w(u32x4 (&wv)[kNT][2], const uint8_t* (&wrow)[kNT], int s, int g, int K) {

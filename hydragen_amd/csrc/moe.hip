@@ -21,27 +21,14 @@
 //   MT tiles of 16 slots are carried per pass; an expert with more slots takes further passes over the same W (then in L2).  Rows
 // past the expert's count are clamped duplicates of its last slot and are never stored; a 16-deep chunk at or past K is zeros in
 // both operands and never loaded.  A column of B only meets its own column of the accumulator: a slot depends on its own row only.
-#include "hyd_kernels.h"
+#include "mma_tiles.h"  // kThreads, kWaves, mfma16, park_tiles, add_tiles
 
 namespace hyd {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = 4;
 constexpr int kStepK = 64;        // k per step: one 16-byte load of W per lane, tile and half
 constexpr int kGroupThreads = 1024;  // one thread per slot: T k <= 128 * 8
-
-template <typename T>
-__device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c);
-template <>
-__device__ __forceinline__ f32x4 mfma16<BF16>(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4 mfma16<F16>(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 
 // ---- routing -------------------------------------------------------------------------------------------------------------------
 // (logit, expert) as one integer whose order is "larger logit first, then lower expert": the float's bits made monotonic (-0 is
@@ -211,29 +198,6 @@ __device__ __forceinline__ void expert_product(f32x4 (&acc)[2][MT], const uint16
     }
 }
 
-// waves 1 .. 3 leave their tiles in LDS; wave 0 (after the barrier) adds them to its own in wave order
-template <int MT>
-__device__ __forceinline__ void park_tiles(float* red, const f32x4 (&acc)[2][MT], int wave, int lane) {
-    if (wave == 0) return;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) red[(((wave - 1) * 2 + t) * MT + i) * 256 + r * 64 + lane] = acc[t][i][r];
-}
-template <int MT>
-__device__ __forceinline__ void add_tiles(const float* red, f32x4 (&acc)[2][MT], int lane) {
-#pragma unroll
-    for (int w = 0; w < kWaves - 1; ++w)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[t][i][r] += red[((w * 2 + t) * MT + i) * 256 + r * 64 + lane];
-}
-
 }  // namespace
 
 // grid (I / 16, E).  The two W tiles are rows i0 .. i0 + 15 (gate) and I + i0 .. (up) of gate_up[e]; the four waves split H.
@@ -351,14 +315,40 @@ MoeLayout moe_layout(int T, int E, int k, int H, int I) {
     return l;
 }
 
+static bool moe_shapes_ok(const MoeArgs& a) {
+    return a.T >= 1 && a.T <= kMoeMaxRows && a.E >= 1 && a.E <= kMoeMaxExperts && a.k >= 1 && a.k <= kMoeMaxTopK && a.k <= a.E && a.H % 64 == 0 &&
+           a.I % 32 == 0 && a.H >= 64 && a.I >= 32;
+}
+
+// the launches around the two expert products, for every weight format (moe_w8.hip): route and group ...
+int launch_moe_route_group(const MoeArgs& a, int dtype, hipStream_t s) {
+    if (!moe_shapes_ok(a)) return (int)hipErrorInvalidValue;
+    const dim3 grid((unsigned)((a.T + kWaves - 1) / kWaves)), block(kThreads);
+    if (dtype == HYD_F16)
+        hipLaunchKernelGGL(moe_route_kernel<F16>, grid, block, 0, s, a);
+    else
+        hipLaunchKernelGGL(moe_route_kernel<BF16>, grid, block, 0, s, a);
+    const int rc = (int)hipGetLastError();
+    if (rc) return rc;
+    hipLaunchKernelGGL(moe_group_kernel, dim3(1), dim3(kGroupThreads), 0, s, a);
+    return (int)hipGetLastError();
+}
+
+// ... and combine
+int launch_moe_combine(const MoeArgs& a, int dtype, hipStream_t s) {
+    const dim3 grid((unsigned)((a.T * (a.H >> 2) + kThreads - 1) / kThreads)), block(kThreads);
+    if (dtype == HYD_F16)
+        hipLaunchKernelGGL(moe_combine_kernel<F16>, grid, block, 0, s, a);
+    else
+        hipLaunchKernelGGL(moe_combine_kernel<BF16>, grid, block, 0, s, a);
+    return (int)hipGetLastError();
+}
+
 template <typename T>
 static int launch_moe_mlp_t(const MoeArgs& a, hipStream_t s) {
     const dim3 block(kThreads);
-    hipLaunchKernelGGL(moe_route_kernel<T>, dim3((unsigned)((a.T + kWaves - 1) / kWaves)), block, 0, s, a);
-    int rc = (int)hipGetLastError();
+    int rc = launch_moe_route_group(a, Traits<T>::kDtype, s);
     if (rc) return rc;
-    hipLaunchKernelGGL(moe_group_kernel, dim3(1), dim3(kGroupThreads), 0, s, a);
-    if ((rc = (int)hipGetLastError())) return rc;
     const dim3 gu((unsigned)(a.I / 16), (unsigned)a.E), dn((unsigned)(a.H / 32), (unsigned)a.E);
     if (a.T * a.k <= 16) {  // no expert can hold more than one tile of slots
         hipLaunchKernelGGL((moe_gate_up_kernel<T, 1>), gu, block, 0, s, a);
@@ -370,14 +360,11 @@ static int launch_moe_mlp_t(const MoeArgs& a, hipStream_t s) {
         hipLaunchKernelGGL((moe_down_kernel<T, 2>), dn, block, 0, s, a);
     }
     if ((rc = (int)hipGetLastError())) return rc;
-    hipLaunchKernelGGL(moe_combine_kernel<T>, dim3((unsigned)((a.T * (a.H >> 2) + kThreads - 1) / kThreads)), block, 0, s, a);
-    return (int)hipGetLastError();
+    return launch_moe_combine(a, Traits<T>::kDtype, s);
 }
 
 int launch_moe_mlp(const MoeArgs& a, int dtype, hipStream_t s) {
-    if (a.T < 1 || a.T > kMoeMaxRows || a.E < 1 || a.E > kMoeMaxExperts || a.k < 1 || a.k > kMoeMaxTopK || a.k > a.E || a.H % 64 || a.I % 32 ||
-        a.H < 64 || a.I < 32)
-        return (int)hipErrorInvalidValue;
+    if (!moe_shapes_ok(a)) return (int)hipErrorInvalidValue;
     return dtype == HYD_F16 ? launch_moe_mlp_t<F16>(a, s) : launch_moe_mlp_t<BF16>(a, s);
 }
 

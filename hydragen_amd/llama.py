@@ -30,7 +30,7 @@ from .flash import flash_attention, flash_attention_seqlen, padded_head_dim
 from . import kv_quant as _kv_quant
 from .kv_quant import FP8_DTYPE, dequantize_kv, quantize_kv, scale_constant
 from .tp import all_reduce_sum
-from .moe import MoeMLP
+from .moe import Fp8Experts, MoeMLP
 from .weight_quant import FP4_DTYPE, Fp4Linear, Fp8Linear, W8Scratch
 
 
@@ -879,6 +879,7 @@ class HydragenLlamaForCausalLM(nn.Module):
         self.lm_head = nn.Linear(config.hidden_size, config.vocab_size, bias=False)
         self.kv_cache_allocated = False
         self.weights_quantized = False  # quantize_weights()
+        self.experts_quantized = False  # quantize_experts()
         self.graphed_model: Optional[GraphedHydragenLlamaModel] = None
         self.mode: Optional[str] = None
         # one presence bitmap [sb, ceil(V / 32)] int32 per used shared level, recorded by append_shared (the penalties' context)
@@ -1009,7 +1010,8 @@ class HydragenLlamaForCausalLM(nn.Module):
             raise NotImplementedError(f"quantize_weights(dtype={dtype}): {FP8_DTYPE} and {FP4_DTYPE} are the formats")
         cls = Fp4Linear if dtype == FP4_DTYPE else Fp8Linear
         if self.config.num_experts > 0:
-            raise NotImplementedError("quantize_weights() on a model with experts: the expert kernels take 16-bit weights only")
+            raise NotImplementedError("quantize_weights() on a model with experts: its linear layers stay 16-bit; quantize_experts() stores the "
+                                      "expert weights in fp8")
         if self.weights_quantized:
             raise RuntimeError("quantize_weights() was already called on this model")
         skip = set(skip)
@@ -1036,6 +1038,24 @@ class HydragenLlamaForCausalLM(nn.Module):
         if "lm_head" not in skip:
             self.lm_head = cls.from_linears((self.lm_head,), scratch)
         self.weights_quantized = True
+
+    def quantize_experts(self) -> None:
+        """Store every layer's expert weights in fp8 (moe.quantize_experts: e4m3fn codes with one power-of-two scale per expert and
+        output channel; activations, accumulators and outputs stay 16-bit) and release the 16-bit storage: each layer's
+        `mlp.experts` becomes a moe.Fp8Experts and MoeMLP runs hyd_moe_mlp_w8 on it.  The router, the attention projections and
+        the head stay 16-bit.  A captured graph is invalidated; a dense model and a second call raise.  state_dict() carries
+        `experts.gate_up_proj` / `.down_proj` as codes with `experts.gate_up_proj_scale` / `.down_proj_scale`; loading it into a
+        model quantized the same way restores it bit for bit."""
+        if self.config.num_experts <= 0:
+            raise NotImplementedError("quantize_experts() on a model without experts: quantize_weights() stores a dense model's linear weights in fp8")
+        if self.experts_quantized:
+            raise RuntimeError("quantize_experts() was already called on this model")
+        if any(p.device.type == "meta" for p in self.parameters()):
+            raise RuntimeError("quantize_experts() needs loaded weights (the model is on the meta device)")
+        self.maybe_invalidate()
+        for layer in self.model.layers:
+            layer.mlp.experts = Fp8Experts.from_experts(layer.mlp.experts)
+        self.experts_quantized = True
 
     def maybe_invalidate(self):
         if self.graphed_model is not None:

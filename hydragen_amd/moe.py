@@ -9,6 +9,12 @@ device, capture-safe) and `MoeMLP`, the module a decoder layer of a model with e
     y[t] = sum_j weights[t, j] * (act[t, j] @ Wd[e_j]^T)                      (in j order; rounded once by whoever compares)
 
 The weight layouts are transformers 5's (`experts.gate_up_proj` [E, 2 I, H], `experts.down_proj` [E, H, I], `gate.weight` [E, H]).
+
+fp8 experts (`quantize_experts`, hyd_moe_mlp_w8, csrc/moe_w8.hip, `Fp8Experts`): the two expert tensors as e4m3fn codes with one
+power-of-two fp32 scale per expert and output channel -- weight_quant.quantize_weight's rule on the [E N, K] view.  The fp8 MLP is
+DEFINED as `moe_reference` on the float64 dequantized weights (code * scale, exact), and `moe_error_bound` on the same weights is
+its bound: the codes are exact 16-bit values and the scales powers of two applied to the fp32 sums, so a kernel differs from the
+16-bit kernels on the dequantized weights in accumulation order only.  The router stays a 16-bit F.linear.
 """
 
 from __future__ import annotations
@@ -20,6 +26,8 @@ import torch
 from torch import Tensor, nn
 
 from . import _lib
+from .kv_quant import FP8_DTYPE
+from .weight_quant import quantize_weight
 
 
 # ---- the definition ----------------------------------------------------------------------------------------------------------------
@@ -103,17 +111,50 @@ def moe_error_bound(x: Tensor, router_w: Tensor, gate_up: Tensor, down: Tensor, 
     return bound + u16 * out.abs() + tiny
 
 
+def quantize_experts(gate_up: Tensor, down: Tensor) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """gate_up [E, 2 I, H], down [E, H, I] (any float dtype) -> (gate_up8 e4m3fn [E, 2 I, H], gate_up_scale float32 [E, 2 I], down8
+    [E, H, I], down_scale [E, H]): quantize_weight on the [E N, K] view -- a gate row, an up row and a down row each own a scale."""
+    out = []
+    for w in (gate_up, down):
+        if w.ndim != 3:
+            raise ValueError(f"quantize_experts takes [E, N, K] expert weights, got {tuple(w.shape)}")
+        w8, scale = quantize_weight(w.reshape(-1, w.shape[2]))
+        out += [w8.view(w.shape), scale.view(w.shape[:2])]
+    return tuple(out)
+
+
+def _check_experts8(gate_up8: Tensor, gate_up_scale: Tensor, down8: Tensor, down_scale: Tensor):
+    for name, w8, scale in (("gate_up", gate_up8, gate_up_scale), ("down", down8, down_scale)):
+        if w8.dtype != FP8_DTYPE or w8.ndim != 3:
+            raise TypeError(f"{name} must be a {FP8_DTYPE} [E, N, K] tensor, got {tuple(w8.shape)} {w8.dtype}")
+        if scale is None or scale.dtype != torch.float32 or tuple(scale.shape) != tuple(w8.shape[:2]):
+            raise ValueError(f"{name}_scale must be float32 {tuple(w8.shape[:2])}, got {None if scale is None else (tuple(scale.shape), scale.dtype)}")
+
+
+def dequantize_experts(gate_up8: Tensor, gate_up_scale: Tensor, down8: Tensor, down_scale: Tensor, dtype: torch.dtype = torch.float64) -> tuple[Tensor, Tensor]:
+    """(gate_up, down) = code * scale in `dtype`: exact in float64 and float32, and in a 16-bit dtype as long as the product stays in
+    its normal range."""
+    _check_experts8(gate_up8, gate_up_scale, down8, down_scale)
+    return tuple((w8.double() * scale.double()[:, :, None]).to(dtype) for w8, scale in ((gate_up8, gate_up_scale), (down8, down_scale)))
+
+
 # ---- the device path ---------------------------------------------------------------------------------------------------------------
 MOE_MAX_ROWS = 128  # HYD_MOE_MAX_ROWS: rows per hyd_moe_mlp call; moe_mlp chunks longer inputs (the MLP is row-independent: exact)
 
+_MOE_FIELDS = [
+    ("x", C.c_void_p), ("logits", C.c_void_p), ("gate_up", C.c_void_p), ("down", C.c_void_p), ("y", C.c_void_p), ("workspace", C.c_void_p),
+    ("workspace_bytes", C.c_size_t), ("ids_out", C.c_void_p), ("weights_out", C.c_void_p), ("x_row_stride", C.c_int64), ("y_row_stride", C.c_int64),
+    ("T", C.c_int32), ("E", C.c_int32), ("k", C.c_int32), ("H", C.c_int32), ("I", C.c_int32), ("renormalize", C.c_int32), ("dtype", C.c_int32),
+    ("reserved", C.c_int32),
+]
+
 
 class MoeParams(C.Structure):  # hyd_moe_params
-    _fields_ = [
-        ("x", C.c_void_p), ("logits", C.c_void_p), ("gate_up", C.c_void_p), ("down", C.c_void_p), ("y", C.c_void_p), ("workspace", C.c_void_p),
-        ("workspace_bytes", C.c_size_t), ("ids_out", C.c_void_p), ("weights_out", C.c_void_p), ("x_row_stride", C.c_int64), ("y_row_stride", C.c_int64),
-        ("T", C.c_int32), ("E", C.c_int32), ("k", C.c_int32), ("H", C.c_int32), ("I", C.c_int32), ("renormalize", C.c_int32), ("dtype", C.c_int32),
-        ("reserved", C.c_int32),
-    ]
+    _fields_ = _MOE_FIELDS
+
+
+class MoeW8Params(C.Structure):  # hyd_moe_w8_params
+    _fields_ = _MOE_FIELDS + [("gate_up_scale", C.c_void_p), ("down_scale", C.c_void_p)]
 
 
 _workspaces: dict = {}  # (device, rows, E, k, H, I, dtype) -> uint8 tensor: allocated on first use, so that a graph's replay allocates nothing
@@ -128,17 +169,21 @@ def _workspace(device, T, E, k, H, I, dtype) -> Tensor:
     return ws
 
 
-def moe_rows(x: Tensor, logits: Tensor, gate_up: Tensor, down: Tensor, k: int, renormalize: bool, out: Tensor, ids_out: Optional[Tensor] = None,
-             weights_out: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
-    """One hyd_moe_mlp call on the current stream: x [T, H] (T <= MOE_MAX_ROWS, unit last stride), logits [T, E] contiguous, into
-    out [T, H] (unit last stride); ids_out int32 / weights_out float32 [T, k] receive the routing.  The C layer refuses what is
-    out of range."""
+def _moe_call(x, logits, gate_up, down, scales, k, renormalize, out, ids_out, weights_out, workspace) -> Tensor:
+    """moe_rows (scales None: 16-bit weights of x's dtype) and moe_rows_w8 (scales = (gate_up_scale, down_scale): e4m3fn codes)."""
     from .flash import _require_gpu, _stream
 
-    _require_gpu(x, logits, gate_up, down, out, ids_out, weights_out, workspace)
+    _require_gpu(x, logits, gate_up, down, out, ids_out, weights_out, workspace, *(scales or ()))
     (T, H), E, I = x.shape, gate_up.shape[0], down.shape[2]
-    if not (x.dtype == logits.dtype == gate_up.dtype == down.dtype == out.dtype) or x.dtype not in (torch.float16, torch.bfloat16):
-        raise TypeError("x, logits, gate_up, down and out must share one of float16 / bfloat16")
+    if scales is None:
+        if not (x.dtype == logits.dtype == gate_up.dtype == down.dtype == out.dtype) or x.dtype not in (torch.float16, torch.bfloat16):
+            raise TypeError("x, logits, gate_up, down and out must share one of float16 / bfloat16")
+    else:
+        _check_experts8(gate_up, scales[0], down, scales[1])
+        if not (x.dtype == logits.dtype == out.dtype) or x.dtype not in (torch.float16, torch.bfloat16):
+            raise TypeError("x, logits and out must share one of float16 / bfloat16")
+        if not (scales[0].is_contiguous() and scales[1].is_contiguous()):
+            raise ValueError("gate_up_scale and down_scale must be contiguous")
     if tuple(logits.shape) != (T, E) or tuple(gate_up.shape) != (E, 2 * I, H) or tuple(down.shape) != (E, H, I) or tuple(out.shape) != (T, H):
         raise ValueError(f"shapes: x {tuple(x.shape)}, logits {tuple(logits.shape)}, gate_up {tuple(gate_up.shape)}, down {tuple(down.shape)}, out {tuple(out.shape)}")
     if x.stride(1) != 1 or out.stride(1) != 1 or not (logits.is_contiguous() and gate_up.is_contiguous() and down.is_contiguous()):
@@ -148,7 +193,7 @@ def moe_rows(x: Tensor, logits: Tensor, gate_up: Tensor, down: Tensor, k: int, r
             raise ValueError(f"{name} must be a contiguous [{T}, {k}] {dt} tensor")
     if workspace is None:
         workspace = _workspace(x.device, T, E, k, H, I, x.dtype)
-    p = MoeParams()
+    p = MoeParams() if scales is None else MoeW8Params()
     p.x, p.logits, p.gate_up, p.down, p.y = x.data_ptr(), logits.data_ptr(), gate_up.data_ptr(), down.data_ptr(), out.data_ptr()
     p.workspace, p.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
     p.ids_out = None if ids_out is None else ids_out.data_ptr()
@@ -156,19 +201,45 @@ def moe_rows(x: Tensor, logits: Tensor, gate_up: Tensor, down: Tensor, k: int, r
     p.x_row_stride, p.y_row_stride = (x.stride(0), out.stride(0)) if T > 1 else (H, H)  # (one row: the stride is never used)
     p.T, p.E, p.k, p.H, p.I, p.renormalize = T, E, k, H, I, int(bool(renormalize))
     p.dtype = _lib.HYD_F16 if x.dtype == torch.float16 else _lib.HYD_BF16
-    _lib.check(_lib.load().hyd_moe_mlp(C.byref(p), _stream()))
+    if scales is None:
+        _lib.check(_lib.load().hyd_moe_mlp(C.byref(p), _stream()))
+    else:
+        p.gate_up_scale, p.down_scale = scales[0].data_ptr(), scales[1].data_ptr()
+        _lib.check(_lib.load().hyd_moe_mlp_w8(C.byref(p), _stream()))
     return out
 
 
-def moe_mlp(x: Tensor, router_w: Tensor, gate_up: Tensor, down: Tensor, k: int, renormalize: bool, *, return_routing: bool = False):
+def moe_rows(x: Tensor, logits: Tensor, gate_up: Tensor, down: Tensor, k: int, renormalize: bool, out: Tensor, ids_out: Optional[Tensor] = None,
+             weights_out: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
+    """One hyd_moe_mlp call on the current stream: x [T, H] (T <= MOE_MAX_ROWS, unit last stride), logits [T, E] contiguous, into
+    out [T, H] (unit last stride); ids_out int32 / weights_out float32 [T, k] receive the routing.  The C layer refuses what is
+    out of range."""
+    return _moe_call(x, logits, gate_up, down, None, k, renormalize, out, ids_out, weights_out, workspace)
+
+
+def moe_rows_w8(x: Tensor, logits: Tensor, gate_up8: Tensor, gate_up_scale: Tensor, down8: Tensor, down_scale: Tensor, k: int, renormalize: bool,
+                out: Tensor, ids_out: Optional[Tensor] = None, weights_out: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
+    """One hyd_moe_mlp_w8 call on the current stream: moe_rows on quantize_experts' four tensors (contiguous); x, logits and out
+    stay 16-bit, the workspace is moe_rows'."""
+    return _moe_call(x, logits, gate_up8, down8, (gate_up_scale, down_scale), k, renormalize, out, ids_out, weights_out, workspace)
+
+
+def moe_mlp(x: Tensor, router_w: Tensor, gate_up: Tensor, down: Tensor, k: int, renormalize: bool, *, return_routing: bool = False,
+            gate_up_scale: Optional[Tensor] = None, down_scale: Optional[Tensor] = None):
     """The routed MLP of x [..., H]: logits = F.linear(x, router_w) in the 16-bit dtype, then one hyd_moe_mlp call per chunk of
     MOE_MAX_ROWS rows (rows are independent, so chunking is exact).  The workspace is cached per (device, shapes): a captured graph
     replays without allocating it.  CPU tensors run the definition, rounded once to the dtype.  `return_routing`: (y, ids [T, k]
-    int32, weights [T, k] float32)."""
+    int32, weights [T, k] float32).  With `gate_up_scale` and `down_scale` (both or neither), gate_up and down are quantize_experts'
+    e4m3fn codes: hyd_moe_mlp_w8 per chunk, and on the CPU the definition on the dequantized weights."""
+    if (gate_up_scale is None) != (down_scale is None):
+        raise ValueError("gate_up_scale and down_scale come together")
+    scales = None if gate_up_scale is None else (gate_up_scale, down_scale)
     x2 = x.reshape(-1, x.shape[-1])
-    T, E = x2.shape[0], gate_up.shape[0]
+    T = x2.shape[0]
     logits = nn.functional.linear(x2, router_w)
     if not x.is_cuda:
+        if scales is not None:
+            gate_up, down = dequantize_experts(gate_up, gate_up_scale, down, down_scale)
         y = moe_reference(x2, router_w, gate_up, down, k, renormalize, logits=logits).to(x.dtype).view(x.shape)
         if not return_routing:
             return y
@@ -179,7 +250,7 @@ def moe_mlp(x: Tensor, router_w: Tensor, gate_up: Tensor, down: Tensor, k: int, 
     w = torch.empty((T, k), dtype=torch.float32, device=x.device) if return_routing else None
     for r in range(0, T, MOE_MAX_ROWS):
         rows = slice(r, min(T, r + MOE_MAX_ROWS))
-        moe_rows(x2[rows], logits[rows], gate_up, down, k, renormalize, y[rows], None if ids is None else ids[rows], None if w is None else w[rows])
+        _moe_call(x2[rows], logits[rows], gate_up, down, scales, k, renormalize, y[rows], None if ids is None else ids[rows], None if w is None else w[rows], None)
     y = y.view(x.shape)
     return (y, ids, w) if return_routing else y
 
@@ -191,9 +262,42 @@ class _Experts(nn.Module):
         self.down_proj = nn.Parameter(torch.empty(E, H, I))
 
 
+class Fp8Experts(nn.Module):
+    """A layer's experts in fp8: buffers `gate_up_proj` e4m3fn [E, 2 I, H], `gate_up_proj_scale` float32 [E, 2 I], `down_proj`
+    e4m3fn [E, H, I] and `down_proj_scale` float32 [E, H] (they travel in the state dict and are never trained).  `dtype` is the
+    activation dtype the experts were quantized from."""
+
+    def __init__(self, gate_up_proj: Tensor, gate_up_proj_scale: Tensor, down_proj: Tensor, down_proj_scale: Tensor, dtype: torch.dtype = torch.bfloat16):
+        super().__init__()
+        _check_experts8(gate_up_proj, gate_up_proj_scale, down_proj, down_proj_scale)
+        self.dtype = dtype
+        for name, t in (("gate_up_proj", gate_up_proj), ("gate_up_proj_scale", gate_up_proj_scale), ("down_proj", down_proj), ("down_proj_scale", down_proj_scale)):
+            self.register_buffer(name, t.contiguous())
+
+    @classmethod
+    def from_experts(cls, experts: nn.Module) -> "Fp8Experts":
+        return cls(*quantize_experts(experts.gate_up_proj, experts.down_proj), dtype=experts.gate_up_proj.dtype)
+
+    def _apply(self, fn, recurse=True):
+        """`.to(device)` moves the buffers as they are.  A floating-point cast (`.half()`, `.to(dtype)`) would turn the codes and
+        the scales into 16-bit values: they keep their formats, and the cast sets the activation dtype instead (Fp8Linear's rule)."""
+        kept = {n: b for n, b in self.named_buffers(recurse=False)}
+        super()._apply(fn, recurse)
+        if self.gate_up_proj.dtype != FP8_DTYPE:
+            self.dtype = self.gate_up_proj.dtype
+        for n, b in kept.items():
+            if getattr(self, n).dtype != b.dtype:
+                setattr(self, n, b.to(getattr(self, n).device))
+        return self
+
+    def extra_repr(self) -> str:
+        return f"experts={self.gate_up_proj.shape[0]}, hidden={self.down_proj.shape[1]}, intermediate={self.down_proj.shape[2]}, fp8 weights for {self.dtype}"
+
+
 class MoeMLP(nn.Module):
     """A decoder layer's routed MLP under transformers 5's parameter names and layouts (`gate.weight` [E, H],
-    `experts.gate_up_proj` [E, 2 I, H], `experts.down_proj` [E, H, I]: Mixtral's and Qwen3-MoE's alike under `model.layers.N.mlp.`)."""
+    `experts.gate_up_proj` [E, 2 I, H], `experts.down_proj` [E, H, I]: Mixtral's and Qwen3-MoE's alike under `model.layers.N.mlp.`).
+    `experts` holds the 16-bit parameters, or an Fp8Experts after HydragenLlamaForCausalLM.quantize_experts()."""
 
     def __init__(self, hidden_size: int, intermediate_size: int, num_experts: int, top_k: int, renormalize: bool):
         super().__init__()
@@ -202,4 +306,6 @@ class MoeMLP(nn.Module):
         self.top_k, self.renormalize = top_k, renormalize
 
     def forward(self, x: Tensor) -> Tensor:
-        return moe_mlp(x, self.gate.weight, self.experts.gate_up_proj, self.experts.down_proj, self.top_k, self.renormalize)
+        e = self.experts
+        scales = dict(gate_up_scale=e.gate_up_proj_scale, down_scale=e.down_proj_scale) if isinstance(e, Fp8Experts) else {}
+        return moe_mlp(x, self.gate.weight, e.gate_up_proj, e.down_proj, self.top_k, self.renormalize, **scales)

@@ -1224,6 +1224,37 @@ typedef struct hyd_moe_params {
 HYD_API size_t hyd_moe_workspace_bytes(int32_t T, int32_t E, int32_t k, int32_t H, int32_t I, int32_t dtype);
 HYD_API int hyd_moe_mlp(const hyd_moe_params* p, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The same MLP on fp8 expert weights (csrc/moe_w8.hip; moe.quantize_experts is the quantizer): gate_up and down hold e4m3fn codes
+ * (one byte per weight, the same shapes, contiguous, 16-byte aligned) with one power-of-two fp32 scale per expert and output
+ * channel, gate_up_scale [E, 2 I] and down_scale [E, H] (contiguous, 4-byte aligned, not null).  The scales multiply the fp32 sums:
+ *   act[t, j]    = round16(silu(sg * (x[t] . Wg8[e]^T)) * (su * (x[t] . Wu8[e]^T)))
+ *   y[t]         = round16(sum_j (sd * (act[t, j] . Wd8[e]^T)) * weights[t, j])
+ * which is hyd_moe_mlp on the dequantized weights (code * scale, exact in 16 bits) up to the order of the fp32 additions.
+ * x, logits, act, yslot and y keep their types; the ranges, the workspace (hyd_moe_workspace_bytes), the five launches, the
+ * capture and repeatability properties and the error codes are hyd_moe_mlp's.  A new symbol and a new struct: the version stays 500.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct hyd_moe_w8_params {
+    const void* x;           /* [T, H] dtype, row t at x + t * x_row_stride                                   */
+    const void* logits;      /* [T, E] dtype, contiguous                                                      */
+    const void* gate_up;     /* [E, 2 I, H] e4m3fn codes, contiguous                                          */
+    const void* down;        /* [E, H, I] e4m3fn codes, contiguous                                            */
+    void* y;                 /* [T, H] dtype, row t at y + t * y_row_stride                                   */
+    void* workspace;
+    size_t workspace_bytes;
+    int32_t* ids_out;        /* [T, k] or NULL                                                                */
+    float* weights_out;      /* [T, k] or NULL                                                                */
+    int64_t x_row_stride, y_row_stride;
+    int32_t T, E, k, H, I;
+    int32_t renormalize;     /* 0 | 1                                                                         */
+    int32_t dtype;           /* HYD_F16 | HYD_BF16: x, logits and y                                           */
+    int32_t reserved;
+    const float* gate_up_scale; /* [E, 2 I]                                                                   */
+    const float* down_scale;    /* [E, H]                                                                     */
+    } hyd_moe_w8_params;
+
+HYD_API int hyd_moe_mlp_w8(const hyd_moe_w8_params* p, void* stream);
+
 HYD_API int hyd_version(void);
 HYD_API const char* hyd_last_error_string(void);
 

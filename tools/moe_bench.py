@@ -3,6 +3,7 @@ time to stream the weights it has to read and against transformers' own block.  
 --out or stdout) -- nothing here is promised in advance.
 
     python tools/moe_bench.py [--out profiles/moe.md] [--rows 1,8,32,128] [--rounds 5] [--skip-eager]
+    python tools/moe_bench.py --experts fp8 --out profiles/moe.md     (appends the fp8 section to the file)
 
 Per shape -- a Mixtral-8x7B layer (E 8, k 2, H 4096, I 14336) and a Qwen3-30B-A3B layer (E 128, k 8, H 2048, I 768), bf16, random
 weights -- and per row count T: a ring of distinct layers whose ACTIVATED experts together exceed the 256 MB Infinity Cache, so every
@@ -10,7 +11,9 @@ call streams its weights from HBM as it does inside a model; one pass over the r
 gaps), the figure is the median over the rounds, per layer.  Beside it: the floor -- the bytes of the distinct activated experts of a
 layer (mean over the ring: 3 H I 2 bytes each) at 8 TB/s -- and transformers' sparse block on the same weights, run eagerly (it
 synchronises with the host to loop over the experts that were hit, so it cannot be captured; wall time per layer with a device
-synchronisation at the end of the ring)."""
+synchronisation at the end of the ring).
+--experts fp8: the same rings with their experts quantized (moe.quantize_experts, hyd_moe_mlp_w8) beside the 16-bit originals, both
+captured, replayed alternately round by round in this one process; the fp8 floor is half the bytes."""
 from __future__ import annotations
 
 import argparse
@@ -122,16 +125,57 @@ def shape_table(name, kind, E, k, H, I, rows, rounds, eager, out):
     out("")
 
 
+def fp8_table(name, E, k, H, I, rows, rounds, out):
+    from hydragen_amd import moe
+
+    expert_bytes = 3 * H * I * 2
+    n = max(2, RING_BYTES // (min(E, k * min(rows)) * expert_bytes // 2) + 2)  # the fp8 ring, too, exceeds the Infinity Cache
+    gen = torch.Generator(device=DEV).manual_seed(E + H)
+    mk = lambda *s, sd: torch.randn(s, device=DEV, dtype=torch.bfloat16, generator=gen) * sd  # noqa: E731
+    layers = [(mk(E, H, sd=0.05), mk(E, 2 * I, H, sd=0.02), mk(E, H, I, sd=0.02)) for _ in range(n)]
+    quant = [moe.quantize_experts(gate_up, down) for _, gate_up, down in layers]
+    out(f"### {name}: E = {E}, k = {k}, H = {H}, I = {I} ({n} layers per ring)\n")
+    out("| T | 16-bit us (min .. max) | fp8 us (min .. max) | fp8 / 16-bit | distinct experts hit | fp8 floor us (8 TB/s) | fp8 / floor | fp8 TB/s |")
+    out("|---|---|---|---|---|---|---|---|")
+    for T in rows:
+        x = torch.randn((T, H), device=DEV, dtype=torch.bfloat16, generator=gen)
+        hit = statistics.mean(int(moe.moe_mlp(x, *l, k, True, return_routing=True)[1].unique().numel()) for l in layers)
+
+        def run16():
+            for l in layers:
+                moe.moe_mlp(x, *l, k, True)
+
+        def run8():
+            for (router, _, _), q in zip(layers, quant):
+                moe.moe_mlp(x, router, q[0], q[2], k, True, gate_up_scale=q[1], down_scale=q[3])
+
+        graphs = [graph_of(run16), graph_of(run8)]
+        ts = ([], [])
+        for r in range(rounds + 1):
+            for i, g in enumerate(graphs):
+                t = replay_us(g, n, 1 if r == 0 else 20)
+                if r:
+                    ts[i].append(t)
+        us16, us8 = (statistics.median(t) for t in ts)
+        floor = hit * expert_bytes / 2 / (HBM_TBS * 1e6)
+        out(f"| {T} | {us16:.1f} ({min(ts[0]):.1f} .. {max(ts[0]):.1f}) | {us8:.1f} ({min(ts[1]):.1f} .. {max(ts[1]):.1f}) | {us8 / us16:.2f} | {hit:.1f} | {floor:.1f} | "
+            f"{us8 / floor:.2f} | {hit * expert_bytes / 2 / us8 * 1e-6:.2f} |")
+        del graphs
+    out("")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--rows", default="1,8,32,128")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--skip-eager", action="store_true")
+    ap.add_argument("--experts", choices=["16bit", "fp8"], default="16bit")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("moe_bench.py measures on the GPU: no device found")
-    lines = []
+    fp8 = args.experts == "fp8"
+    lines = Path(args.out).read_text().rstrip("\n").split("\n") + [""] if fp8 and args.out and Path(args.out).exists() else []
 
     def out(s):
         lines.append(s)
@@ -139,6 +183,14 @@ def main():
         if args.out:
             Path(args.out).write_text("\n".join(lines) + "\n")
 
+    if fp8:
+        out("## fp8 experts (`hyd_moe_mlp_w8`) against the 16-bit kernels of the same build\n")
+        out("The same rings with their experts quantized (`moe.quantize_experts`), both forms captured and replayed alternately in one process, bf16 "
+            "activations; median (min .. max) over the rounds, per layer.  The fp8 floor is the activated experts' code bytes at 8 TB/s.\n")
+        for name, _, E, k, H, I in SHAPES:
+            fp8_table(name, E, k, H, I, [int(r) for r in args.rows.split(",")], args.rounds, out)
+            torch.cuda.empty_cache()
+        return
     out("# Mixture-of-experts MLP: measurements\n")
     out("One layer's `moe_mlp` (router GEMM, then route / group / gate|up + SwiGLU / down / combine) under a HIP graph, bf16, per layer of a ring "
         "of distinct layers; the floor is the bytes of the distinct activated experts at 8 TB/s.\n")
