@@ -1,4 +1,5 @@
-// C ABI, the mixture-of-experts MLP (moe.hip, moe_w8.hip): hyd_moe_workspace_bytes, hyd_moe_mlp, hyd_moe_mlp_w8.
+// C ABI, the mixture-of-experts MLP (moe.hip, moe_w8.hip): hyd_moe_workspace_bytes, hyd_moe_mlp, hyd_moe_mlp_w8,
+// hyd_moe_mlp_w4 (moe_w4.hip).
 #include "api_core.h"
 
 using namespace hyd;
@@ -21,7 +22,7 @@ int check_moe_shapes(int T, int E, int k, int H, int I, int dtype, bool say) {
     return HYD_OK;
 }
 
-// the checks and the kernel arguments that hyd_moe_params and hyd_moe_w8_params share (P: either; the fields carry the same names)
+// the checks and the kernel arguments that hyd_moe_params, hyd_moe_w8_params and hyd_moe_w4_params share (P: either; the fields carry the same names)
 template <typename P>
 int moe_args(const P* p, MoeArgs& a) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
@@ -51,6 +52,16 @@ int moe_args(const P* p, MoeArgs& a) {
     return HYD_OK;
 }
 
+// the two scale pointers of the quantized forms (P: hyd_moe_w8_params or hyd_moe_w4_params)
+template <typename P>
+int moe_scales(const P* p, MoeW8Args& a) {
+    if (int rc = check_not_null({{p->gate_up_scale, "gate_up_scale"}, {p->down_scale, "down_scale"}})) return rc;
+    if (int rc = check_elem_align({{p->gate_up_scale, 4, "gate_up_scale"}, {p->down_scale, 4, "down_scale"}})) return rc;
+    a.gate_up_scale = p->gate_up_scale;
+    a.down_scale = p->down_scale;
+    return HYD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -70,12 +81,21 @@ int hyd_moe_mlp(const hyd_moe_params* p, void* stream) {
 int hyd_moe_mlp_w8(const hyd_moe_w8_params* p, void* stream) {
     MoeW8Args a;
     int rc = moe_args(p, a.c);
-    if (rc) return rc;
-    if ((rc = check_not_null({{p->gate_up_scale, "gate_up_scale"}, {p->down_scale, "down_scale"}}))) return rc;
-    if ((rc = check_elem_align({{p->gate_up_scale, 4, "gate_up_scale"}, {p->down_scale, 4, "down_scale"}}))) return rc;
-    a.gate_up_scale = p->gate_up_scale;
-    a.down_scale = p->down_scale;
+    if (rc || (rc = moe_scales(p, a))) return rc;
     return launched(launch_moe_mlp_w8(a, p->dtype, static_cast<hipStream_t>(stream)), "moe_mlp_w8 kernel launches");
+}
+
+int hyd_moe_mlp_w4(const hyd_moe_w4_params* p, void* stream) {
+    MoeW4Args a;
+    int rc = moe_args(p, a.c.c);
+    if (rc || (rc = moe_scales(p, a.c))) return rc;
+    if ((rc = check_not_null({{p->gate_up_shift, "gate_up_shift"}, {p->down_shift, "down_shift"}}))) return rc;
+    // a K that is whole steps (K % 256 == 0) reads a half step's four shift bytes of a row as one aligned load: rows are K / 32 = 8 n bytes
+    if ((p->H % 256 == 0 && misaligned(p->gate_up_shift, 8)) || (p->I % 256 == 0 && misaligned(p->down_shift, 8)))
+        return fail(HYD_ERR_BAD_ARG, "gate_up_shift (H %d) / down_shift (I %d) must be 8-byte aligned where the depth is a multiple of 256", p->H, p->I);
+    a.gate_up_shift = p->gate_up_shift;
+    a.down_shift = p->down_shift;
+    return launched(launch_moe_mlp_w4(a, p->dtype, static_cast<hipStream_t>(stream)), "moe_mlp_w4 kernel launches");
 }
 
 }  // extern "C"

@@ -389,12 +389,19 @@ struct MoeW8Args {  // moe_w8.hip: the same call on e4m3fn codes (c.gate_up / c.
     const float* down_scale;     // [E, H]
 };
 
+struct MoeW4Args {  // moe_w4.hip: the same call on packed e2m1 codes (c.c.gate_up [E, 2 I, H / 2] / c.c.down [E, H, I / 2]) with a shift per group of 32 k
+    MoeW8Args c;
+    const uint8_t* gate_up_shift;  // [E, 2 I, H / 32]
+    const uint8_t* down_shift;     // [E, H, I / 32]
+};
+
 // launchers (defined next to the kernels); return hipError_t as int
 MoeLayout moe_layout(int T, int E, int k, int H, int I);    // moe.hip, shapes only
 int launch_moe_mlp(const MoeArgs& a, int dtype, hipStream_t s);  // moe.hip: the five launches of one routed MLP
 int launch_moe_route_group(const MoeArgs& a, int dtype, hipStream_t s);  // moe.hip: the first two of them (checks the ranges) ...
 int launch_moe_combine(const MoeArgs& a, int dtype, hipStream_t s);      // ... and the last, shared with
 int launch_moe_mlp_w8(const MoeW8Args& a, int dtype, hipStream_t s);     // moe_w8.hip: the same five launches on fp8 expert weights
+int launch_moe_mlp_w4(const MoeW4Args& a, int dtype, hipStream_t s);     // moe_w4.hip: ... and on 4-bit (e2m1) expert weights
 LinearW8Plan plan_linear_w8(int M, int N, int K);                                        // linear_w8.hip, shapes only
 int launch_linear_w8(const LinearW8Args& a, const LinearW8Plan& pl, int dtype, hipStream_t s);  // linear_w8.hip
 int launch_linear_w8_reduce(const LinearW8Args& a, int dtype, hipStream_t s);            // linear_w8.hip: the split slices' second launch alone

@@ -30,7 +30,7 @@ from .flash import flash_attention, flash_attention_seqlen, padded_head_dim
 from . import kv_quant as _kv_quant
 from .kv_quant import FP8_DTYPE, dequantize_kv, quantize_kv, scale_constant
 from .tp import all_reduce_sum
-from .moe import Fp8Experts, MoeMLP
+from .moe import Fp4Experts, Fp8Experts, MoeMLP
 from .weight_quant import FP4_DTYPE, Fp4Linear, Fp8Linear, W8Scratch
 
 
@@ -1039,13 +1039,18 @@ class HydragenLlamaForCausalLM(nn.Module):
             self.lm_head = cls.from_linears((self.lm_head,), scratch)
         self.weights_quantized = True
 
-    def quantize_experts(self) -> None:
+    def quantize_experts(self, dtype: torch.dtype = FP8_DTYPE) -> None:
         """Store every layer's expert weights in fp8 (moe.quantize_experts: e4m3fn codes with one power-of-two scale per expert and
         output channel; activations, accumulators and outputs stay 16-bit) and release the 16-bit storage: each layer's
         `mlp.experts` becomes a moe.Fp8Experts and MoeMLP runs hyd_moe_mlp_w8 on it.  The router, the attention projections and
         the head stay 16-bit.  A captured graph is invalidated; a dense model and a second call raise.  state_dict() carries
         `experts.gate_up_proj` / `.down_proj` as codes with `experts.gate_up_proj_scale` / `.down_proj_scale`; loading it into a
-        model quantized the same way restores it bit for bit."""
+        model quantized the same way restores it bit for bit.
+        dtype=torch.float4_e2m1fn_x2 stores 4-bit e2m1 codes with a shift per group of 32 and the per-channel scale instead
+        (moe.quantize_experts_fp4; `mlp.experts` becomes a moe.Fp4Experts with the further buffers `experts.gate_up_proj_shift` /
+        `.down_proj_shift`, and MoeMLP runs hyd_moe_mlp_w4 on it)."""
+        if dtype not in (FP8_DTYPE, FP4_DTYPE):
+            raise NotImplementedError(f"quantize_experts(dtype={dtype}): {FP8_DTYPE} and {FP4_DTYPE} are the formats")
         if self.config.num_experts <= 0:
             raise NotImplementedError("quantize_experts() on a model without experts: quantize_weights() stores a dense model's linear weights in fp8")
         if self.experts_quantized:
@@ -1054,7 +1059,7 @@ class HydragenLlamaForCausalLM(nn.Module):
             raise RuntimeError("quantize_experts() needs loaded weights (the model is on the meta device)")
         self.maybe_invalidate()
         for layer in self.model.layers:
-            layer.mlp.experts = Fp8Experts.from_experts(layer.mlp.experts)
+            layer.mlp.experts = (Fp4Experts if dtype == FP4_DTYPE else Fp8Experts).from_experts(layer.mlp.experts)
         self.experts_quantized = True
 
     def maybe_invalidate(self):

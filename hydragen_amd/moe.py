@@ -15,6 +15,13 @@ power-of-two fp32 scale per expert and output channel -- weight_quant.quantize_w
 DEFINED as `moe_reference` on the float64 dequantized weights (code * scale, exact), and `moe_error_bound` on the same weights is
 its bound: the codes are exact 16-bit values and the scales powers of two applied to the fp32 sums, so a kernel differs from the
 16-bit kernels on the dequantized weights in accumulation order only.  The router stays a 16-bit F.linear.
+
+4-bit experts (`quantize_experts_fp4`, hyd_moe_mlp_w4, csrc/moe_w4.hip, `Fp4Experts`): weight_quant.quantize_weight_fp4's format on
+the same view -- packed e2m1 codes [E, N, K / 2], a shift 0..12 per group of 32 k [E, N, K / 32], a power-of-two scale per expert
+and output channel [E, N].  The 4-bit MLP is DEFINED the same way, as `moe_reference` on e2m1(code) * 2^-shift * scale in float64
+with `moe_error_bound` on the same weights: e2m1 * 2^-shift lies in [2^-13, 6], an exact normal value in both 16-bit types, and the
+channel scale multiplies the fp32 sum, so here too a kernel differs in accumulation order only (what the quantizer costs is the
+quantizer's, not the kernel's: the bound has no term for it).
 """
 
 from __future__ import annotations
@@ -27,7 +34,7 @@ from torch import Tensor, nn
 
 from . import _lib
 from .kv_quant import FP8_DTYPE
-from .weight_quant import quantize_weight
+from .weight_quant import _group_values, quantize_weight, quantize_weight_fp4
 
 
 # ---- the definition ----------------------------------------------------------------------------------------------------------------
@@ -138,6 +145,42 @@ def dequantize_experts(gate_up8: Tensor, gate_up_scale: Tensor, down8: Tensor, d
     return tuple((w8.double() * scale.double()[:, :, None]).to(dtype) for w8, scale in ((gate_up8, gate_up_scale), (down8, down_scale)))
 
 
+def quantize_experts_fp4(gate_up: Tensor, down: Tensor) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """gate_up [E, 2 I, H], down [E, H, I] (any float dtype) -> (gate_up4 uint8 [E, 2 I, H / 2], gate_up_shift uint8 [E, 2 I, H / 32],
+    gate_up_scale float32 [E, 2 I], down4 [E, H, I / 2], down_shift [E, H, I / 32], down_scale [E, H]): quantize_weight_fp4 on the
+    [E N, K] view.  Byte b of a row holds k = 2 b in its low nibble and k = 2 b + 1 in its high nibble, as in Fp4Linear."""
+    out = []
+    for w in (gate_up, down):
+        if w.ndim != 3:
+            raise ValueError(f"quantize_experts_fp4 takes [E, N, K] expert weights, got {tuple(w.shape)}")
+        w4, shift, scale = quantize_weight_fp4(w.reshape(-1, w.shape[2]))
+        out += [w4.view(*w.shape[:2], -1), shift.view(*w.shape[:2], -1), scale.view(w.shape[:2])]
+    return tuple(out)
+
+
+def _check_experts4(gate_up4: Tensor, gate_up_shift: Tensor, gate_up_scale: Tensor, down4: Tensor, down_shift: Tensor, down_scale: Tensor):
+    for name, w4, shift, scale in (("gate_up", gate_up4, gate_up_shift, gate_up_scale), ("down", down4, down_shift, down_scale)):
+        if w4.dtype != torch.uint8 or w4.ndim != 3 or w4.shape[2] % 16:
+            raise TypeError(f"{name} must be a uint8 [E, N, K / 2] tensor of packed e2m1 codes with K % 32 == 0, got {tuple(w4.shape)} {w4.dtype}")
+        E, N, K2 = w4.shape
+        if shift is None or shift.dtype != torch.uint8 or tuple(shift.shape) != (E, N, K2 // 16):
+            raise ValueError(f"{name}_shift must be uint8 {(E, N, K2 // 16)}, got {None if shift is None else (tuple(shift.shape), shift.dtype)}")
+        if scale is None or scale.dtype != torch.float32 or tuple(scale.shape) != (E, N):
+            raise ValueError(f"{name}_scale must be float32 {(E, N)}, got {None if scale is None else (tuple(scale.shape), scale.dtype)}")
+
+
+def dequantize_experts_fp4(gate_up4: Tensor, gate_up_shift: Tensor, gate_up_scale: Tensor, down4: Tensor, down_shift: Tensor, down_scale: Tensor,
+                           dtype: torch.dtype = torch.float64) -> tuple[Tensor, Tensor]:
+    """(gate_up, down) = e2m1(code) * 2^-shift * scale in `dtype`: exact in float64 and float32, and in a 16-bit dtype as long as the
+    product stays in its normal range."""
+    _check_experts4(gate_up4, gate_up_shift, gate_up_scale, down4, down_shift, down_scale)
+    out = []
+    for w4, shift, scale in ((gate_up4, gate_up_shift, gate_up_scale), (down4, down_shift, down_scale)):
+        E, N, K2 = w4.shape
+        out.append((_group_values(w4.reshape(E * N, K2), shift.reshape(E * N, -1), torch.float64).view(E, N, 2 * K2) * scale.double()[:, :, None]).to(dtype))
+    return tuple(out)
+
+
 # ---- the device path ---------------------------------------------------------------------------------------------------------------
 MOE_MAX_ROWS = 128  # HYD_MOE_MAX_ROWS: rows per hyd_moe_mlp call; moe_mlp chunks longer inputs (the MLP is row-independent: exact)
 
@@ -157,6 +200,10 @@ class MoeW8Params(C.Structure):  # hyd_moe_w8_params
     _fields_ = _MOE_FIELDS + [("gate_up_scale", C.c_void_p), ("down_scale", C.c_void_p)]
 
 
+class MoeW4Params(C.Structure):  # hyd_moe_w4_params
+    _fields_ = MoeW8Params._fields_ + [("gate_up_shift", C.c_void_p), ("down_shift", C.c_void_p)]
+
+
 _workspaces: dict = {}  # (device, rows, E, k, H, I, dtype) -> uint8 tensor: allocated on first use, so that a graph's replay allocates nothing
 
 
@@ -170,21 +217,26 @@ def _workspace(device, T, E, k, H, I, dtype) -> Tensor:
 
 
 def _moe_call(x, logits, gate_up, down, scales, k, renormalize, out, ids_out, weights_out, workspace) -> Tensor:
-    """moe_rows (scales None: 16-bit weights of x's dtype) and moe_rows_w8 (scales = (gate_up_scale, down_scale): e4m3fn codes)."""
+    """moe_rows (scales None: 16-bit weights of x's dtype), moe_rows_w8 (scales = (gate_up_scale, down_scale): e4m3fn codes) and
+    moe_rows_w4 (scales = (gate_up_scale, down_scale, gate_up_shift, down_shift): packed e2m1 codes, two k per byte)."""
     from .flash import _require_gpu, _stream
 
     _require_gpu(x, logits, gate_up, down, out, ids_out, weights_out, workspace, *(scales or ()))
-    (T, H), E, I = x.shape, gate_up.shape[0], down.shape[2]
+    fp4 = scales is not None and len(scales) == 4
+    (T, H), E, I, per = x.shape, gate_up.shape[0], down.shape[2] * (2 if fp4 else 1), 2 if fp4 else 1  # per: k per element of the weights
     if scales is None:
         if not (x.dtype == logits.dtype == gate_up.dtype == down.dtype == out.dtype) or x.dtype not in (torch.float16, torch.bfloat16):
             raise TypeError("x, logits, gate_up, down and out must share one of float16 / bfloat16")
     else:
-        _check_experts8(gate_up, scales[0], down, scales[1])
+        if fp4:
+            _check_experts4(gate_up, scales[2], scales[0], down, scales[3], scales[1])
+        else:
+            _check_experts8(gate_up, scales[0], down, scales[1])
         if not (x.dtype == logits.dtype == out.dtype) or x.dtype not in (torch.float16, torch.bfloat16):
             raise TypeError("x, logits and out must share one of float16 / bfloat16")
-        if not (scales[0].is_contiguous() and scales[1].is_contiguous()):
-            raise ValueError("gate_up_scale and down_scale must be contiguous")
-    if tuple(logits.shape) != (T, E) or tuple(gate_up.shape) != (E, 2 * I, H) or tuple(down.shape) != (E, H, I) or tuple(out.shape) != (T, H):
+        if not all(s.is_contiguous() for s in scales):
+            raise ValueError("gate_up_scale and down_scale" + (", gate_up_shift and down_shift" if fp4 else "") + " must be contiguous")
+    if tuple(logits.shape) != (T, E) or tuple(gate_up.shape) != (E, 2 * I, H // per) or tuple(down.shape) != (E, H, I // per) or tuple(out.shape) != (T, H):
         raise ValueError(f"shapes: x {tuple(x.shape)}, logits {tuple(logits.shape)}, gate_up {tuple(gate_up.shape)}, down {tuple(down.shape)}, out {tuple(out.shape)}")
     if x.stride(1) != 1 or out.stride(1) != 1 or not (logits.is_contiguous() and gate_up.is_contiguous() and down.is_contiguous()):
         raise ValueError("x and out need a unit last stride; logits, gate_up and down must be contiguous")
@@ -193,7 +245,7 @@ def _moe_call(x, logits, gate_up, down, scales, k, renormalize, out, ids_out, we
             raise ValueError(f"{name} must be a contiguous [{T}, {k}] {dt} tensor")
     if workspace is None:
         workspace = _workspace(x.device, T, E, k, H, I, x.dtype)
-    p = MoeParams() if scales is None else MoeW8Params()
+    p = MoeParams() if scales is None else MoeW4Params() if fp4 else MoeW8Params()
     p.x, p.logits, p.gate_up, p.down, p.y = x.data_ptr(), logits.data_ptr(), gate_up.data_ptr(), down.data_ptr(), out.data_ptr()
     p.workspace, p.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
     p.ids_out = None if ids_out is None else ids_out.data_ptr()
@@ -203,8 +255,12 @@ def _moe_call(x, logits, gate_up, down, scales, k, renormalize, out, ids_out, we
     p.dtype = _lib.HYD_F16 if x.dtype == torch.float16 else _lib.HYD_BF16
     if scales is None:
         _lib.check(_lib.load().hyd_moe_mlp(C.byref(p), _stream()))
+        return out
+    p.gate_up_scale, p.down_scale = scales[0].data_ptr(), scales[1].data_ptr()
+    if fp4:
+        p.gate_up_shift, p.down_shift = scales[2].data_ptr(), scales[3].data_ptr()
+        _lib.check(_lib.load().hyd_moe_mlp_w4(C.byref(p), _stream()))
     else:
-        p.gate_up_scale, p.down_scale = scales[0].data_ptr(), scales[1].data_ptr()
         _lib.check(_lib.load().hyd_moe_mlp_w8(C.byref(p), _stream()))
     return out
 
@@ -224,21 +280,35 @@ def moe_rows_w8(x: Tensor, logits: Tensor, gate_up8: Tensor, gate_up_scale: Tens
     return _moe_call(x, logits, gate_up8, down8, (gate_up_scale, down_scale), k, renormalize, out, ids_out, weights_out, workspace)
 
 
+def moe_rows_w4(x: Tensor, logits: Tensor, gate_up4: Tensor, gate_up_shift: Tensor, gate_up_scale: Tensor, down4: Tensor, down_shift: Tensor,
+                down_scale: Tensor, k: int, renormalize: bool, out: Tensor, ids_out: Optional[Tensor] = None, weights_out: Optional[Tensor] = None,
+                workspace: Optional[Tensor] = None) -> Tensor:
+    """One hyd_moe_mlp_w4 call on the current stream: moe_rows on quantize_experts_fp4's six tensors (contiguous); x, logits and out
+    stay 16-bit, the workspace is moe_rows'."""
+    return _moe_call(x, logits, gate_up4, down4, (gate_up_scale, down_scale, gate_up_shift, down_shift), k, renormalize, out, ids_out, weights_out, workspace)
+
+
 def moe_mlp(x: Tensor, router_w: Tensor, gate_up: Tensor, down: Tensor, k: int, renormalize: bool, *, return_routing: bool = False,
-            gate_up_scale: Optional[Tensor] = None, down_scale: Optional[Tensor] = None):
+            gate_up_scale: Optional[Tensor] = None, down_scale: Optional[Tensor] = None, gate_up_shift: Optional[Tensor] = None,
+            down_shift: Optional[Tensor] = None):
     """The routed MLP of x [..., H]: logits = F.linear(x, router_w) in the 16-bit dtype, then one hyd_moe_mlp call per chunk of
     MOE_MAX_ROWS rows (rows are independent, so chunking is exact).  The workspace is cached per (device, shapes): a captured graph
     replays without allocating it.  CPU tensors run the definition, rounded once to the dtype.  `return_routing`: (y, ids [T, k]
     int32, weights [T, k] float32).  With `gate_up_scale` and `down_scale` (both or neither), gate_up and down are quantize_experts'
-    e4m3fn codes: hyd_moe_mlp_w8 per chunk, and on the CPU the definition on the dequantized weights."""
+    e4m3fn codes: hyd_moe_mlp_w8 per chunk, and on the CPU the definition on the dequantized weights.  With `gate_up_shift` and
+    `down_shift` as well (both, and only with the scales), they are quantize_experts_fp4's packed e2m1 codes: hyd_moe_mlp_w4."""
     if (gate_up_scale is None) != (down_scale is None):
         raise ValueError("gate_up_scale and down_scale come together")
-    scales = None if gate_up_scale is None else (gate_up_scale, down_scale)
+    if (gate_up_shift is None) != (down_shift is None) or (gate_up_shift is not None and gate_up_scale is None):
+        raise ValueError("gate_up_shift and down_shift come together, and with gate_up_scale and down_scale")
+    scales = None if gate_up_scale is None else (gate_up_scale, down_scale) if gate_up_shift is None else (gate_up_scale, down_scale, gate_up_shift, down_shift)
     x2 = x.reshape(-1, x.shape[-1])
     T = x2.shape[0]
     logits = nn.functional.linear(x2, router_w)
     if not x.is_cuda:
-        if scales is not None:
+        if gate_up_shift is not None:
+            gate_up, down = dequantize_experts_fp4(gate_up, gate_up_shift, gate_up_scale, down, down_shift, down_scale)
+        elif scales is not None:
             gate_up, down = dequantize_experts(gate_up, gate_up_scale, down, down_scale)
         y = moe_reference(x2, router_w, gate_up, down, k, renormalize, logits=logits).to(x.dtype).view(x.shape)
         if not return_routing:
@@ -294,10 +364,47 @@ class Fp8Experts(nn.Module):
         return f"experts={self.gate_up_proj.shape[0]}, hidden={self.down_proj.shape[1]}, intermediate={self.down_proj.shape[2]}, fp8 weights for {self.dtype}"
 
 
+class Fp4Experts(nn.Module):
+    """A layer's experts in 4 bits: buffers `gate_up_proj` uint8 [E, 2 I, H / 2], `gate_up_proj_shift` uint8 [E, 2 I, H / 32],
+    `gate_up_proj_scale` float32 [E, 2 I], `down_proj` uint8 [E, H, I / 2], `down_proj_shift` uint8 [E, H, I / 32] and
+    `down_proj_scale` float32 [E, H] (they travel in the state dict and are never trained).  `dtype` is the activation dtype the
+    experts were quantized from."""
+
+    NAMES = ("gate_up_proj", "gate_up_proj_shift", "gate_up_proj_scale", "down_proj", "down_proj_shift", "down_proj_scale")
+
+    def __init__(self, gate_up_proj: Tensor, gate_up_proj_shift: Tensor, gate_up_proj_scale: Tensor, down_proj: Tensor, down_proj_shift: Tensor,
+                 down_proj_scale: Tensor, dtype: torch.dtype = torch.bfloat16):
+        super().__init__()
+        bufs = (gate_up_proj, gate_up_proj_shift, gate_up_proj_scale, down_proj, down_proj_shift, down_proj_scale)
+        _check_experts4(*bufs)
+        self.dtype = dtype
+        for name, t in zip(self.NAMES, bufs):
+            self.register_buffer(name, t.contiguous())
+
+    @classmethod
+    def from_experts(cls, experts: nn.Module) -> "Fp4Experts":
+        return cls(*quantize_experts_fp4(experts.gate_up_proj, experts.down_proj), dtype=experts.gate_up_proj.dtype)
+
+    def _apply(self, fn, recurse=True):
+        """Fp8Experts' rule: `.to(device)` moves the buffers as they are; a floating-point cast reaches the scales only (codes and
+        shifts are integers), is taken as the new activation dtype and undone on the buffers."""
+        kept = {n: b for n, b in self.named_buffers(recurse=False)}
+        super()._apply(fn, recurse)
+        if self.gate_up_proj_scale.dtype != torch.float32:
+            self.dtype = self.gate_up_proj_scale.dtype
+        for n, b in kept.items():
+            if getattr(self, n).dtype != b.dtype:
+                setattr(self, n, b.to(getattr(self, n).device))
+        return self
+
+    def extra_repr(self) -> str:
+        return f"experts={self.gate_up_proj.shape[0]}, hidden={self.down_proj.shape[1]}, intermediate={2 * self.down_proj.shape[2]}, e2m1 weights for {self.dtype}"
+
+
 class MoeMLP(nn.Module):
     """A decoder layer's routed MLP under transformers 5's parameter names and layouts (`gate.weight` [E, H],
     `experts.gate_up_proj` [E, 2 I, H], `experts.down_proj` [E, H, I]: Mixtral's and Qwen3-MoE's alike under `model.layers.N.mlp.`).
-    `experts` holds the 16-bit parameters, or an Fp8Experts after HydragenLlamaForCausalLM.quantize_experts()."""
+    `experts` holds the 16-bit parameters, or an Fp8Experts / Fp4Experts after HydragenLlamaForCausalLM.quantize_experts()."""
 
     def __init__(self, hidden_size: int, intermediate_size: int, num_experts: int, top_k: int, renormalize: bool):
         super().__init__()
@@ -307,5 +414,7 @@ class MoeMLP(nn.Module):
 
     def forward(self, x: Tensor) -> Tensor:
         e = self.experts
-        scales = dict(gate_up_scale=e.gate_up_proj_scale, down_scale=e.down_proj_scale) if isinstance(e, Fp8Experts) else {}
+        scales = dict(gate_up_scale=e.gate_up_proj_scale, down_scale=e.down_proj_scale) if isinstance(e, (Fp8Experts, Fp4Experts)) else {}
+        if isinstance(e, Fp4Experts):
+            scales.update(gate_up_shift=e.gate_up_proj_shift, down_shift=e.down_proj_shift)
         return moe_mlp(x, self.gate.weight, e.gate_up_proj, e.down_proj, self.top_k, self.renormalize, **scales)

@@ -1255,6 +1255,43 @@ typedef struct hyd_moe_w8_params {
 
 HYD_API int hyd_moe_mlp_w8(const hyd_moe_w8_params* p, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The same MLP on 4-bit expert weights (csrc/moe_w4.hip; moe.quantize_experts_fp4 is the quantizer): hyd_linear_w4's format per
+ * expert.  gate_up [E, 2 I, H / 2] and down [E, H, I / 2] hold packed OCP e2m1 codes (byte b of a row: k = 2 b in the low nibble,
+ * k = 2 b + 1 in the high one; contiguous, 16-byte aligned), gate_up_shift [E, 2 I, H / 32] and down_shift [E, H, I / 32] one
+ * shift 0..12 per group of 32 k (contiguous, not null; 8-byte aligned where that tensor's depth -- H for gate_up, I for down -- is a
+ * multiple of 256, no alignment otherwise), gate_up_scale [E, 2 I] and down_scale [E, H] one power-of-two fp32 scale per expert
+ * and output channel (contiguous, 4-byte aligned, not null).  A weight is e2m1(code) * 2^-shift * scale; e2m1 * 2^-shift is an
+ * exact 16-bit value and the scales multiply the fp32 sums:
+ *   act[t, j]    = round16(silu(sg * (x[t] . Wg4[e]^T)) * (su * (x[t] . Wu4[e]^T)))
+ *   y[t]         = round16(sum_j (sd * (act[t, j] . Wd4[e]^T)) * weights[t, j])
+ * which is hyd_moe_mlp on the dequantized weights up to the order of the fp32 additions.  x, logits, act, yslot and y keep their
+ * types; the ranges, the workspace (hyd_moe_workspace_bytes), the five launches, the capture and repeatability properties and the
+ * error codes are hyd_moe_mlp's.  A new symbol and a new struct: the version stays 500.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct hyd_moe_w4_params {
+    const void* x;           /* [T, H] dtype, row t at x + t * x_row_stride                                   */
+    const void* logits;      /* [T, E] dtype, contiguous                                                      */
+    const void* gate_up;     /* [E, 2 I, H / 2] packed e2m1 codes, contiguous                                 */
+    const void* down;        /* [E, H, I / 2] packed e2m1 codes, contiguous                                   */
+    void* y;                 /* [T, H] dtype, row t at y + t * y_row_stride                                   */
+    void* workspace;
+    size_t workspace_bytes;
+    int32_t* ids_out;        /* [T, k] or NULL                                                                */
+    float* weights_out;      /* [T, k] or NULL                                                                */
+    int64_t x_row_stride, y_row_stride;
+    int32_t T, E, k, H, I;
+    int32_t renormalize;     /* 0 | 1                                                                         */
+    int32_t dtype;           /* HYD_F16 | HYD_BF16: x, logits and y                                           */
+    int32_t reserved;
+    const float* gate_up_scale;   /* [E, 2 I]                                                                 */
+    const float* down_scale;      /* [E, H]                                                                   */
+    const uint8_t* gate_up_shift; /* [E, 2 I, H / 32]                                                         */
+    const uint8_t* down_shift;    /* [E, H, I / 32]                                                           */
+    } hyd_moe_w4_params;
+
+HYD_API int hyd_moe_mlp_w4(const hyd_moe_w4_params* p, void* stream);
+
 HYD_API int hyd_version(void);
 HYD_API const char* hyd_last_error_string(void);
 

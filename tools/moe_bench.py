@@ -4,6 +4,7 @@ time to stream the weights it has to read and against transformers' own block.  
 
     python tools/moe_bench.py [--out profiles/moe.md] [--rows 1,8,32,128] [--rounds 5] [--skip-eager]
     python tools/moe_bench.py --experts fp8 --out profiles/moe.md     (appends the fp8 section to the file)
+    python tools/moe_bench.py --experts fp4 --rows 1,8,16,32,64,128 --out profiles/moe.md     (appends the 4-bit section)
 
 Per shape -- a Mixtral-8x7B layer (E 8, k 2, H 4096, I 14336) and a Qwen3-30B-A3B layer (E 128, k 8, H 2048, I 768), bf16, random
 weights -- and per row count T: a ring of distinct layers whose ACTIVATED experts together exceed the 256 MB Infinity Cache, so every
@@ -13,7 +14,9 @@ layer (mean over the ring: 3 H I 2 bytes each) at 8 TB/s -- and transformers' sp
 synchronises with the host to loop over the experts that were hit, so it cannot be captured; wall time per layer with a device
 synchronisation at the end of the ring).
 --experts fp8: the same rings with their experts quantized (moe.quantize_experts, hyd_moe_mlp_w8) beside the 16-bit originals, both
-captured, replayed alternately round by round in this one process; the fp8 floor is half the bytes."""
+captured, replayed alternately round by round in this one process; the fp8 floor is half the bytes.
+--experts fp4: three forms of the same rings -- 16-bit, fp8 and 4-bit (moe.quantize_experts_fp4, hyd_moe_mlp_w4) -- alternated the same
+way; the 4-bit floor is the codes, shifts and scales of the activated experts (4.25 bits per weight and 4 bytes per channel)."""
 from __future__ import annotations
 
 import argparse
@@ -164,18 +167,66 @@ def fp8_table(name, E, k, H, I, rows, rounds, out):
     out("")
 
 
+def fp4_table(name, E, k, H, I, rows, rounds, out):
+    from hydragen_amd import moe
+
+    expert_bytes = 3 * H * I * 2
+    expert4_bytes = 3 * H * I * 17 // 32 + 4 * (2 * I + H)  # codes + shifts, and the channels' scales
+    n = max(2, RING_BYTES // (min(E, k * min(rows)) * expert4_bytes) + 2)  # the 4-bit ring, too, exceeds the Infinity Cache
+    gen = torch.Generator(device=DEV).manual_seed(E + H)
+    mk = lambda *s, sd: torch.randn(s, device=DEV, dtype=torch.bfloat16, generator=gen) * sd  # noqa: E731
+    layers = [(mk(E, H, sd=0.05), mk(E, 2 * I, H, sd=0.02), mk(E, H, I, sd=0.02)) for _ in range(n)]
+    quant8 = [moe.quantize_experts(gate_up, down) for _, gate_up, down in layers]
+    # (expert by expert: the quantizer's float64 temporaries of a whole Mixtral layer would not be small)
+    quant4 = [tuple(torch.cat(t) for t in zip(*(moe.quantize_experts_fp4(gate_up[e:e + 1], down[e:e + 1]) for e in range(E)))) for _, gate_up, down in layers]
+    out(f"### {name}: E = {E}, k = {k}, H = {H}, I = {I} ({n} layers per ring; resident experts per layer: {E * expert_bytes / 2**20:.0f} MiB in 16 bits, "
+        f"{E * expert_bytes / 2**21:.0f} MiB in fp8, {E * expert4_bytes / 2**20:.0f} MiB in 4 bits)\n")
+    out("| T | 16-bit us (min .. max) | fp8 us (min .. max) | 4-bit us (min .. max) | 4-bit / fp8 | 4-bit / 16-bit | distinct experts hit | 4-bit floor us (8 TB/s) | 4-bit / floor | 4-bit TB/s |")
+    out("|---|---|---|---|---|---|---|---|---|---|")
+    for T in rows:
+        x = torch.randn((T, H), device=DEV, dtype=torch.bfloat16, generator=gen)
+        hit = statistics.mean(int(moe.moe_mlp(x, *l, k, True, return_routing=True)[1].unique().numel()) for l in layers)
+
+        def run16():
+            for l in layers:
+                moe.moe_mlp(x, *l, k, True)
+
+        def run8():
+            for (router, _, _), q in zip(layers, quant8):
+                moe.moe_mlp(x, router, q[0], q[2], k, True, gate_up_scale=q[1], down_scale=q[3])
+
+        def run4():
+            for (router, _, _), q in zip(layers, quant4):
+                moe.moe_mlp(x, router, q[0], q[3], k, True, gate_up_shift=q[1], gate_up_scale=q[2], down_shift=q[4], down_scale=q[5])
+
+        graphs = [graph_of(run16), graph_of(run8), graph_of(run4)]
+        ts = ([], [], [])
+        for r in range(rounds + 1):
+            for i, g in enumerate(graphs):
+                t = replay_us(g, n, 1 if r == 0 else 20)
+                if r:
+                    ts[i].append(t)
+        us16, us8, us4 = (statistics.median(t) for t in ts)
+        floor = hit * expert4_bytes / (HBM_TBS * 1e6)
+        spread = lambda i: f"({min(ts[i]):.1f} .. {max(ts[i]):.1f})"  # noqa: E731
+        out(f"| {T} | {us16:.1f} {spread(0)} | {us8:.1f} {spread(1)} | {us4:.1f} {spread(2)} | {us4 / us8:.2f} | {us4 / us16:.2f} | {hit:.1f} | {floor:.1f} | "
+            f"{us4 / floor:.2f} | {hit * expert4_bytes / us4 * 1e-6:.2f} |")
+        del graphs
+    out("")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--rows", default="1,8,32,128")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--skip-eager", action="store_true")
-    ap.add_argument("--experts", choices=["16bit", "fp8"], default="16bit")
+    ap.add_argument("--experts", choices=["16bit", "fp8", "fp4"], default="16bit")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("moe_bench.py measures on the GPU: no device found")
-    fp8 = args.experts == "fp8"
-    lines = Path(args.out).read_text().rstrip("\n").split("\n") + [""] if fp8 and args.out and Path(args.out).exists() else []
+    fp8, fp4 = args.experts == "fp8", args.experts == "fp4"
+    lines = Path(args.out).read_text().rstrip("\n").split("\n") + [""] if (fp8 or fp4) and args.out and Path(args.out).exists() else []
 
     def out(s):
         lines.append(s)
@@ -183,6 +234,14 @@ def main():
         if args.out:
             Path(args.out).write_text("\n".join(lines) + "\n")
 
+    if fp4:
+        out("## 4-bit experts (`hyd_moe_mlp_w4`) against the fp8 and the 16-bit kernels of the same build\n")
+        out("The same rings in three forms (`moe.quantize_experts`, `moe.quantize_experts_fp4`), all captured and replayed alternately in one process, bf16 "
+            "activations; median (min .. max) over the rounds, per layer.  The 4-bit floor is the activated experts' codes, shifts and scales at 8 TB/s.\n")
+        for name, _, E, k, H, I in SHAPES:
+            fp4_table(name, E, k, H, I, [int(r) for r in args.rows.split(",")], args.rounds, out)
+            torch.cuda.empty_cache()
+        return
     if fp8:
         out("## fp8 experts (`hyd_moe_mlp_w8`) against the 16-bit kernels of the same build\n")
         out("The same rings with their experts quantized (`moe.quantize_experts`), both forms captured and replayed alternately in one process, bf16 "
