@@ -1,19 +1,19 @@
 // C ABI, the mixture-of-experts MLP (moe.hip, moe_w8.hip): hyd_moe_workspace_bytes, hyd_moe_mlp, hyd_moe_mlp_w8,
-// hyd_moe_mlp_w4 (moe_w4.hip).
+// hyd_moe_mlp_w4 (moe_w4.hip), hyd_moe_grouped_workspace_bytes and hyd_moe_mlp_grouped (moe_grouped.hip).
 #include "api_core.h"
 
 using namespace hyd;
 
 namespace {
 
-// the ranges of moe.hip; `say` false: the size query's silent form
-int check_moe_shapes(int T, int E, int k, int H, int I, int dtype, bool say) {
+// the ranges of moe.hip (max_rows = kMoeMaxRows) and of moe_grouped.hip (kMoeGroupedMaxRows); `say` false: the size query's silent form
+int check_moe_shapes(int T, int E, int k, int H, int I, int dtype, bool say, int max_rows = kMoeMaxRows) {
     const bool ok_dtype = dtype == HYD_F16 || dtype == HYD_BF16;
-    const bool ok = T >= 1 && T <= kMoeMaxRows && E >= 1 && E <= kMoeMaxExperts && k >= 1 && k <= kMoeMaxTopK && k <= E && H >= 64 && H % 64 == 0 &&
+    const bool ok = T >= 1 && T <= max_rows && E >= 1 && E <= kMoeMaxExperts && k >= 1 && k <= kMoeMaxTopK && k <= E && H >= 64 && H % 64 == 0 &&
                     I >= 32 && I % 32 == 0;
     if (!say) return ok && ok_dtype ? HYD_OK : HYD_ERR_BAD_ARG;
     if (!ok_dtype) return fail(HYD_ERR_UNSUPPORTED, "dtype %d: f16 / bf16 activations and expert weights", dtype);
-    if (T < 1 || T > kMoeMaxRows) return fail(HYD_ERR_BAD_ARG, "T %d: 1 to %d rows per call (longer inputs are chunked by the caller)", T, kMoeMaxRows);
+    if (T < 1 || T > max_rows) return fail(HYD_ERR_BAD_ARG, "T %d: 1 to %d rows per call (longer inputs are chunked by the caller)", T, max_rows);
     if (E < 1 || E > kMoeMaxExperts) return fail(HYD_ERR_BAD_ARG, "E %d: 1 to %d experts", E, kMoeMaxExperts);
     if (k < 1 || k > kMoeMaxTopK) return fail(HYD_ERR_BAD_ARG, "k %d: 1 to %d experts per row", k, kMoeMaxTopK);
     if (k > E) return fail(HYD_ERR_BAD_ARG, "k %d exceeds E %d", k, E);
@@ -22,11 +22,12 @@ int check_moe_shapes(int T, int E, int k, int H, int I, int dtype, bool say) {
     return HYD_OK;
 }
 
-// the checks and the kernel arguments that hyd_moe_params, hyd_moe_w8_params and hyd_moe_w4_params share (P: either; the fields carry the same names)
+// the checks and the kernel arguments that hyd_moe_params, hyd_moe_w8_params and hyd_moe_w4_params share (P: either; the fields carry the same names);
+// `grouped`: hyd_moe_mlp_grouped's range of T and its workspace slices (the tile table goes to grouped->tiles)
 template <typename P>
-int moe_args(const P* p, MoeArgs& a) {
+int moe_args(const P* p, MoeArgs& a, MoeGroupedArgs* grouped = nullptr) {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
-    int rc = check_moe_shapes(p->T, p->E, p->k, p->H, p->I, p->dtype, true);
+    int rc = check_moe_shapes(p->T, p->E, p->k, p->H, p->I, p->dtype, true, grouped ? kMoeGroupedMaxRows : kMoeMaxRows);
     if (rc) return rc;
     if (p->renormalize != 0 && p->renormalize != 1) return fail(HYD_ERR_BAD_ARG, "renormalize %d must be 0 or 1", p->renormalize);
     if ((rc = check_ptrs_align({{p->x, "x"}, {p->gate_up, "gate_up"}, {p->down, "down"}, {p->y, "y"}}))) return rc;
@@ -35,10 +36,13 @@ int moe_args(const P* p, MoeArgs& a) {
     if ((rc = check_strides8({{p->x_row_stride, "x_row_stride"}, {p->y_row_stride, "y_row_stride"}}))) return rc;
     if (p->x_row_stride < p->H || p->y_row_stride < p->H)
         return fail(HYD_ERR_BAD_ARG, "x_row_stride %lld or y_row_stride %lld < H %d", (long long)p->x_row_stride, (long long)p->y_row_stride, p->H);
-    const MoeLayout l = moe_layout(p->T, p->E, p->k, p->H, p->I);
+    MoeLayout l = moe_layout(p->T, p->E, p->k, p->H, p->I);
+    const MoeGroupedLayout gl = moe_grouped_layout(p->T, p->E, p->k, p->H, p->I);
+    if (grouped)  // (no offsets slice: the tile table stands in its place, and a.offsets is not handed out)
+        l = MoeLayout{gl.ids, gl.weights, gl.counts, gl.tiles, gl.slots, gl.act, gl.yslot, gl.bytes};
     if (!p->workspace || p->workspace_bytes < l.bytes)
-        return fail(HYD_ERR_WORKSPACE, "moe_mlp needs %zu workspace bytes for T %d E %d k %d H %d I %d, got %zu", l.bytes, p->T, p->E, p->k, p->H, p->I,
-                    p->workspace ? p->workspace_bytes : (size_t)0);
+        return fail(HYD_ERR_WORKSPACE, "%s needs %zu workspace bytes for T %d E %d k %d H %d I %d, got %zu", grouped ? "moe_mlp_grouped" : "moe_mlp", l.bytes,
+                    p->T, p->E, p->k, p->H, p->I, p->workspace ? p->workspace_bytes : (size_t)0);
     if (misaligned(p->workspace, 16)) return fail(HYD_ERR_WORKSPACE, "workspace must be 16-byte aligned");
     char* ws = static_cast<char*>(p->workspace);
     memset(&a, 0, sizeof(a));
@@ -49,6 +53,10 @@ int moe_args(const P* p, MoeArgs& a) {
     a.ids_out = p->ids_out; a.weights_out = p->weights_out;
     a.xs = p->x_row_stride; a.ys = p->y_row_stride;
     a.T = p->T; a.E = p->E; a.k = p->k; a.H = p->H; a.I = p->I; a.renorm = p->renormalize;
+    if (grouped) {
+        a.offsets = nullptr;
+        grouped->tiles = reinterpret_cast<int32_t*>(ws + gl.tiles);
+    }
     return HYD_OK;
 }
 
@@ -76,6 +84,19 @@ int hyd_moe_mlp(const hyd_moe_params* p, void* stream) {
     const int rc = moe_args(p, a);
     if (rc) return rc;
     return launched(launch_moe_mlp(a, p->dtype, static_cast<hipStream_t>(stream)), "moe_mlp kernel launches");
+}
+
+size_t hyd_moe_grouped_workspace_bytes(int32_t T, int32_t E, int32_t k, int32_t H, int32_t I, int32_t dtype) {
+    if (check_moe_shapes(T, E, k, H, I, dtype, false, kMoeGroupedMaxRows)) return 0;
+    return moe_grouped_layout(T, E, k, H, I).bytes;
+}
+
+int hyd_moe_mlp_grouped(const hyd_moe_params* p, void* stream) {
+    MoeGroupedArgs a;
+    memset(&a, 0, sizeof(a));
+    const int rc = moe_args(p, a.c, &a);
+    if (rc) return rc;
+    return launched(launch_moe_mlp_grouped(a, p->dtype, static_cast<hipStream_t>(stream)), "moe_mlp_grouped kernel launches");
 }
 
 int hyd_moe_mlp_w8(const hyd_moe_w8_params* p, void* stream) {

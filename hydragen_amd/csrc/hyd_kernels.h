@@ -395,7 +395,22 @@ struct MoeW4Args {  // moe_w4.hip: the same call on packed e2m1 codes (c.c.gate_
     const uint8_t* down_shift;     // [E, H, I / 32]
 };
 
+constexpr int kMoeGroupedMaxRows = 2048;  // rows per hyd_moe_mlp_grouped call (HYD_MOE_GROUPED_MAX_ROWS)
+
+struct MoeGroupedLayout {  // moe_grouped.hip: the slices of hyd_moe_mlp_grouped's workspace (byte offsets, each a multiple of 16), from the shapes alone
+    size_t ids, weights, counts, slots, tiles, act, yslot, bytes;
+};
+
+struct MoeGroupedArgs {  // moe_grouped.hip: route -> count -> place -> tiled gate|up + SwiGLU -> tiled down * weight -> combine
+    MoeArgs c;           // offsets is unused; act rows are indexed by sorted position, not by slot
+    int32_t* tiles;      // [ntiles][4]: expert, first sorted position, rows (0: unused entry), 0
+    int32_t ntiles, bm;  // set by the launcher: ceil(T k / bm) + min(E, T k) entries of bm sorted slots
+};
+
 // launchers (defined next to the kernels); return hipError_t as int
+MoeGroupedLayout moe_grouped_layout(int T, int E, int k, int H, int I);          // moe_grouped.hip, shapes only
+int launch_moe_mlp_grouped(const MoeGroupedArgs& a, int dtype, hipStream_t s);  // moe_grouped.hip: the seven launches of one routed MLP
+int launch_moe_route(const MoeArgs& a, int dtype, hipStream_t s);               // moe.hip: the route launch alone, any T
 MoeLayout moe_layout(int T, int E, int k, int H, int I);    // moe.hip, shapes only
 int launch_moe_mlp(const MoeArgs& a, int dtype, hipStream_t s);  // moe.hip: the five launches of one routed MLP
 int launch_moe_route_group(const MoeArgs& a, int dtype, hipStream_t s);  // moe.hip: the first two of them (checks the ranges) ...

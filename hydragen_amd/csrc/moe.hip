@@ -321,14 +321,18 @@ static bool moe_shapes_ok(const MoeArgs& a) {
 }
 
 // the launches around the two expert products, for every weight format (moe_w8.hip): route and group ...
-int launch_moe_route_group(const MoeArgs& a, int dtype, hipStream_t s) {
-    if (!moe_shapes_ok(a)) return (int)hipErrorInvalidValue;
+int launch_moe_route(const MoeArgs& a, int dtype, hipStream_t s) {  // (no limit on T of its own: moe_grouped.hip routes up to 2048 rows)
     const dim3 grid((unsigned)((a.T + kWaves - 1) / kWaves)), block(kThreads);
     if (dtype == HYD_F16)
         hipLaunchKernelGGL(moe_route_kernel<F16>, grid, block, 0, s, a);
     else
         hipLaunchKernelGGL(moe_route_kernel<BF16>, grid, block, 0, s, a);
-    const int rc = (int)hipGetLastError();
+    return (int)hipGetLastError();
+}
+
+int launch_moe_route_group(const MoeArgs& a, int dtype, hipStream_t s) {
+    if (!moe_shapes_ok(a)) return (int)hipErrorInvalidValue;
+    const int rc = launch_moe_route(a, dtype, s);
     if (rc) return rc;
     hipLaunchKernelGGL(moe_group_kernel, dim3(1), dim3(kGroupThreads), 0, s, a);
     return (int)hipGetLastError();

@@ -8,6 +8,9 @@ device, capture-safe) and `MoeMLP`, the module a decoder layer of a model with e
     act[t, j] = round16(silu(x[t] @ Wg[e_j]^T) * (x[t] @ Wu[e_j]^T))          (gate_up[e] = Wg[e] rows, then Wu[e] rows)
     y[t] = sum_j weights[t, j] * (act[t, j] @ Wd[e_j]^T)                      (in j order; rounded once by whoever compares)
 
+Large inputs with 16-bit experts (`moe_rows_grouped`, hyd_moe_mlp_grouped, csrc/moe_grouped.hip): up to 2048 rows per call, the slots
+sorted by expert and both products tiled through LDS, so that an expert is read once per call; the same definition and bound.
+
 The weight layouts are transformers 5's (`experts.gate_up_proj` [E, 2 I, H], `experts.down_proj` [E, H, I], `gate.weight` [E, H]).
 
 fp8 experts (`quantize_experts`, hyd_moe_mlp_w8, csrc/moe_w8.hip, `Fp8Experts`): the two expert tensors as e4m3fn codes with one
@@ -183,6 +186,8 @@ def dequantize_experts_fp4(gate_up4: Tensor, gate_up_shift: Tensor, gate_up_scal
 
 # ---- the device path ---------------------------------------------------------------------------------------------------------------
 MOE_MAX_ROWS = 128  # HYD_MOE_MAX_ROWS: rows per hyd_moe_mlp call; moe_mlp chunks longer inputs (the MLP is row-independent: exact)
+MOE_GROUPED_MAX_ROWS = 2048  # HYD_MOE_GROUPED_MAX_ROWS: rows per hyd_moe_mlp_grouped call (csrc/moe_grouped.hip)
+MOE_GROUPED_MIN_ROWS = 512  # moe_mlp: 16-bit experts take the grouped call from this many rows on (profiles/moe.md has the measurement)
 
 _MOE_FIELDS = [
     ("x", C.c_void_p), ("logits", C.c_void_p), ("gate_up", C.c_void_p), ("down", C.c_void_p), ("y", C.c_void_p), ("workspace", C.c_void_p),
@@ -204,20 +209,21 @@ class MoeW4Params(C.Structure):  # hyd_moe_w4_params
     _fields_ = MoeW8Params._fields_ + [("gate_up_shift", C.c_void_p), ("down_shift", C.c_void_p)]
 
 
-_workspaces: dict = {}  # (device, rows, E, k, H, I, dtype) -> uint8 tensor: allocated on first use, so that a graph's replay allocates nothing
+_workspaces: dict = {}  # (device, rows, E, k, H, I, dtype, grouped) -> uint8 tensor: allocated on first use, so that a graph's replay allocates nothing
 
 
-def _workspace(device, T, E, k, H, I, dtype) -> Tensor:
-    key = (device, T, E, k, H, I, dtype)
+def _workspace(device, T, E, k, H, I, dtype, grouped=False) -> Tensor:
+    key = (device, T, E, k, H, I, dtype, grouped)
     ws = _workspaces.get(key)
     if ws is None:
-        need = int(_lib.load().hyd_moe_workspace_bytes(T, E, k, H, I, _lib.HYD_F16 if dtype == torch.float16 else _lib.HYD_BF16))
+        query = _lib.load().hyd_moe_grouped_workspace_bytes if grouped else _lib.load().hyd_moe_workspace_bytes
+        need = int(query(T, E, k, H, I, _lib.HYD_F16 if dtype == torch.float16 else _lib.HYD_BF16))
         ws = _workspaces[key] = torch.empty((max(need, 16),), dtype=torch.uint8, device=device)
     return ws
 
 
-def _moe_call(x, logits, gate_up, down, scales, k, renormalize, out, ids_out, weights_out, workspace) -> Tensor:
-    """moe_rows (scales None: 16-bit weights of x's dtype), moe_rows_w8 (scales = (gate_up_scale, down_scale): e4m3fn codes) and
+def _moe_call(x, logits, gate_up, down, scales, k, renormalize, out, ids_out, weights_out, workspace, grouped=False) -> Tensor:
+    """moe_rows (scales None: 16-bit weights of x's dtype), moe_rows_grouped (the same with `grouped`: hyd_moe_mlp_grouped), moe_rows_w8 (scales = (gate_up_scale, down_scale): e4m3fn codes) and
     moe_rows_w4 (scales = (gate_up_scale, down_scale, gate_up_shift, down_shift): packed e2m1 codes, two k per byte)."""
     from .flash import _require_gpu, _stream
 
@@ -244,7 +250,7 @@ def _moe_call(x, logits, gate_up, down, scales, k, renormalize, out, ids_out, we
         if t is not None and (t.dtype != dt or tuple(t.shape) != (T, k) or not t.is_contiguous()):
             raise ValueError(f"{name} must be a contiguous [{T}, {k}] {dt} tensor")
     if workspace is None:
-        workspace = _workspace(x.device, T, E, k, H, I, x.dtype)
+        workspace = _workspace(x.device, T, E, k, H, I, x.dtype, grouped)
     p = MoeParams() if scales is None else MoeW4Params() if fp4 else MoeW8Params()
     p.x, p.logits, p.gate_up, p.down, p.y = x.data_ptr(), logits.data_ptr(), gate_up.data_ptr(), down.data_ptr(), out.data_ptr()
     p.workspace, p.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
@@ -254,7 +260,7 @@ def _moe_call(x, logits, gate_up, down, scales, k, renormalize, out, ids_out, we
     p.T, p.E, p.k, p.H, p.I, p.renormalize = T, E, k, H, I, int(bool(renormalize))
     p.dtype = _lib.HYD_F16 if x.dtype == torch.float16 else _lib.HYD_BF16
     if scales is None:
-        _lib.check(_lib.load().hyd_moe_mlp(C.byref(p), _stream()))
+        _lib.check((_lib.load().hyd_moe_mlp_grouped if grouped else _lib.load().hyd_moe_mlp)(C.byref(p), _stream()))
         return out
     p.gate_up_scale, p.down_scale = scales[0].data_ptr(), scales[1].data_ptr()
     if fp4:
@@ -271,6 +277,15 @@ def moe_rows(x: Tensor, logits: Tensor, gate_up: Tensor, down: Tensor, k: int, r
     out [T, H] (unit last stride); ids_out int32 / weights_out float32 [T, k] receive the routing.  The C layer refuses what is
     out of range."""
     return _moe_call(x, logits, gate_up, down, None, k, renormalize, out, ids_out, weights_out, workspace)
+
+
+def moe_rows_grouped(x: Tensor, logits: Tensor, gate_up: Tensor, down: Tensor, k: int, renormalize: bool, out: Tensor, ids_out: Optional[Tensor] = None,
+                     weights_out: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
+    """One hyd_moe_mlp_grouped call on the current stream: moe_rows for T <= MOE_GROUPED_MAX_ROWS rows, the slots sorted by expert
+    and both products tiled through LDS, so that every chosen expert is read once.  The same routing and the same roundings as
+    moe_rows; the fp32 sums inside the two products are added in another order.  Its workspace (hyd_moe_grouped_workspace_bytes) is
+    cached per (device, shapes) like moe_rows'."""
+    return _moe_call(x, logits, gate_up, down, None, k, renormalize, out, ids_out, weights_out, workspace, grouped=True)
 
 
 def moe_rows_w8(x: Tensor, logits: Tensor, gate_up8: Tensor, gate_up_scale: Tensor, down8: Tensor, down_scale: Tensor, k: int, renormalize: bool,
@@ -292,7 +307,8 @@ def moe_mlp(x: Tensor, router_w: Tensor, gate_up: Tensor, down: Tensor, k: int, 
             gate_up_scale: Optional[Tensor] = None, down_scale: Optional[Tensor] = None, gate_up_shift: Optional[Tensor] = None,
             down_shift: Optional[Tensor] = None):
     """The routed MLP of x [..., H]: logits = F.linear(x, router_w) in the 16-bit dtype, then one hyd_moe_mlp call per chunk of
-    MOE_MAX_ROWS rows (rows are independent, so chunking is exact).  The workspace is cached per (device, shapes): a captured graph
+    MOE_MAX_ROWS rows (rows are independent, so chunking is exact); 16-bit experts on MOE_GROUPED_MIN_ROWS rows and more take
+    hyd_moe_mlp_grouped per chunk of MOE_GROUPED_MAX_ROWS rows instead (each expert read once per chunk).  The workspace is cached per (device, shapes): a captured graph
     replays without allocating it.  CPU tensors run the definition, rounded once to the dtype.  `return_routing`: (y, ids [T, k]
     int32, weights [T, k] float32).  With `gate_up_scale` and `down_scale` (both or neither), gate_up and down are quantize_experts'
     e4m3fn codes: hyd_moe_mlp_w8 per chunk, and on the CPU the definition on the dequantized weights.  With `gate_up_shift` and
@@ -318,9 +334,12 @@ def moe_mlp(x: Tensor, router_w: Tensor, gate_up: Tensor, down: Tensor, k: int, 
     y = torch.empty_like(x2)
     ids = torch.empty((T, k), dtype=torch.int32, device=x.device) if return_routing else None
     w = torch.empty((T, k), dtype=torch.float32, device=x.device) if return_routing else None
-    for r in range(0, T, MOE_MAX_ROWS):
-        rows = slice(r, min(T, r + MOE_MAX_ROWS))
-        _moe_call(x2[rows], logits[rows], gate_up, down, scales, k, renormalize, y[rows], None if ids is None else ids[rows], None if w is None else w[rows], None)
+    grouped = scales is None and T >= MOE_GROUPED_MIN_ROWS
+    step = MOE_GROUPED_MAX_ROWS if grouped else MOE_MAX_ROWS
+    for r in range(0, T, step):
+        rows = slice(r, min(T, r + step))
+        _moe_call(x2[rows], logits[rows], gate_up, down, scales, k, renormalize, y[rows], None if ids is None else ids[rows], None if w is None else w[rows], None,
+                  grouped)
     y = y.view(x.shape)
     return (y, ids, w) if return_routing else y
 

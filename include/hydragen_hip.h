@@ -1292,6 +1292,26 @@ typedef struct hyd_moe_w4_params {
 
 HYD_API int hyd_moe_mlp_w4(const hyd_moe_w4_params* p, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The same MLP for large calls (csrc/moe_grouped.hip): hyd_moe_params with its meaning in hyd_moe_mlp, but
+ * 1 <= T <= HYD_MOE_GROUPED_MAX_ROWS (T k <= 16384 slots).  The slots are sorted by expert on the device (a counting sort: an
+ * expert's slots stay in ascending order) and both products run as tiled GEMMs per expert and row tile of 64 or 128 sorted slots
+ * (chosen from T k / E), with both operands staged in LDS: every chosen expert is read once per call.  The result is hyd_moe_mlp's
+ * up to the order of the fp32 additions inside the two products; routing, act's rounding, the route weight's product and the
+ * combine are the same.  Seven launches on `stream` whose grids depend on the shapes alone; nothing is read back, nothing
+ * allocated, no float atomics: capture-safe, and two calls give the same bits.  A row of y depends on its own row of x and of
+ * logits only.
+ * The workspace (16-byte aligned) holds, each slice rounded up to 16 bytes: ids int32 [T k], weights float [T k], counts int32
+ * [E], slots int32 [T k] (slot numbers sorted by expert), tiles int32 [ceil(T k / 64) + min(E, T k)][4] (expert, first sorted
+ * position, rows, 0 per row tile), act 16-bit [T k, I] (rows in sorted order), yslot float [T k, H];
+ * hyd_moe_grouped_workspace_bytes answers their sum, or 0 for shapes outside the ranges.  The error codes are hyd_moe_mlp's, all
+ * before any launch.  New symbols and no new struct: the version stays 500.
+ * ------------------------------------------------------------------------------------------ */
+#define HYD_MOE_GROUPED_MAX_ROWS 2048
+
+HYD_API size_t hyd_moe_grouped_workspace_bytes(int32_t T, int32_t E, int32_t k, int32_t H, int32_t I, int32_t dtype);
+HYD_API int hyd_moe_mlp_grouped(const hyd_moe_params* p, void* stream);
+
 HYD_API int hyd_version(void);
 HYD_API const char* hyd_last_error_string(void);
 
