@@ -382,6 +382,7 @@ EXPORTS = {
     "hyd_moe_mlp_w4": (C.c_int, [C.c_void_p, C.c_void_p]),  # hyd_moe_w4_params*: moe.MoeW4Params
     "hyd_moe_grouped_workspace_bytes": (C.c_size_t, [C.c_int32] * 6),
     "hyd_moe_mlp_grouped": (C.c_int, [C.c_void_p, C.c_void_p]),  # hyd_moe_params*: moe.MoeParams
+    "hyd_moe_mlp_grouped_w8": (C.c_int, [C.c_void_p, C.c_void_p]),  # hyd_moe_w8_params*: moe.MoeW8Params
     # hyd_qk_norm* travels as a plain pointer: its mirror is fused_decode.QkNorm (pass C.byref of one, or None)
     "hyd_rope_append_decode_qkn": (C.c_int, [C.POINTER(RopeParams), C.POINTER(KvQuant), C.c_void_p, C.c_void_p]),
     "hyd_rope_append_multi_qkn": (C.c_int, [C.POINTER(RopeMultiParams), C.c_void_p, C.c_void_p]),

@@ -1,5 +1,6 @@
 // C ABI, the mixture-of-experts MLP (moe.hip, moe_w8.hip): hyd_moe_workspace_bytes, hyd_moe_mlp, hyd_moe_mlp_w8,
-// hyd_moe_mlp_w4 (moe_w4.hip), hyd_moe_grouped_workspace_bytes and hyd_moe_mlp_grouped (moe_grouped.hip).
+// hyd_moe_mlp_w4 (moe_w4.hip), hyd_moe_grouped_workspace_bytes and hyd_moe_mlp_grouped (moe_grouped.hip), hyd_moe_mlp_grouped_w8
+// (moe_grouped_w8.hip).
 #include "api_core.h"
 
 using namespace hyd;
@@ -23,9 +24,10 @@ int check_moe_shapes(int T, int E, int k, int H, int I, int dtype, bool say, int
 }
 
 // the checks and the kernel arguments that hyd_moe_params, hyd_moe_w8_params and hyd_moe_w4_params share (P: either; the fields carry the same names);
-// `grouped`: hyd_moe_mlp_grouped's range of T and its workspace slices (the tile table goes to grouped->tiles)
+// `grouped`: hyd_moe_mlp_grouped's range of T and its workspace slices (the tile table goes to grouped->tiles), `grouped_name`: the grouped call's
+// name in the workspace message
 template <typename P>
-int moe_args(const P* p, MoeArgs& a, MoeGroupedArgs* grouped = nullptr) {
+int moe_args(const P* p, MoeArgs& a, MoeGroupedArgs* grouped = nullptr, const char* grouped_name = "moe_mlp_grouped") {
     if (!p) return fail(HYD_ERR_BAD_ARG, "null params");
     int rc = check_moe_shapes(p->T, p->E, p->k, p->H, p->I, p->dtype, true, grouped ? kMoeGroupedMaxRows : kMoeMaxRows);
     if (rc) return rc;
@@ -41,7 +43,7 @@ int moe_args(const P* p, MoeArgs& a, MoeGroupedArgs* grouped = nullptr) {
     if (grouped)  // (no offsets slice: the tile table stands in its place, and a.offsets is not handed out)
         l = MoeLayout{gl.ids, gl.weights, gl.counts, gl.tiles, gl.slots, gl.act, gl.yslot, gl.bytes};
     if (!p->workspace || p->workspace_bytes < l.bytes)
-        return fail(HYD_ERR_WORKSPACE, "%s needs %zu workspace bytes for T %d E %d k %d H %d I %d, got %zu", grouped ? "moe_mlp_grouped" : "moe_mlp", l.bytes,
+        return fail(HYD_ERR_WORKSPACE, "%s needs %zu workspace bytes for T %d E %d k %d H %d I %d, got %zu", grouped ? grouped_name : "moe_mlp", l.bytes,
                     p->T, p->E, p->k, p->H, p->I, p->workspace ? p->workspace_bytes : (size_t)0);
     if (misaligned(p->workspace, 16)) return fail(HYD_ERR_WORKSPACE, "workspace must be 16-byte aligned");
     char* ws = static_cast<char*>(p->workspace);
@@ -97,6 +99,17 @@ int hyd_moe_mlp_grouped(const hyd_moe_params* p, void* stream) {
     const int rc = moe_args(p, a.c, &a);
     if (rc) return rc;
     return launched(launch_moe_mlp_grouped(a, p->dtype, static_cast<hipStream_t>(stream)), "moe_mlp_grouped kernel launches");
+}
+
+int hyd_moe_mlp_grouped_w8(const hyd_moe_w8_params* p, void* stream) {
+    MoeGroupedW8Args a;
+    memset(&a, 0, sizeof(a));
+    MoeW8Args scales;
+    int rc = moe_args(p, a.g.c, &a.g, "moe_mlp_grouped_w8");
+    if (rc || (rc = moe_scales(p, scales))) return rc;
+    a.gate_up_scale = scales.gate_up_scale;
+    a.down_scale = scales.down_scale;
+    return launched(launch_moe_mlp_grouped_w8(a, p->dtype, static_cast<hipStream_t>(stream)), "moe_mlp_grouped_w8 kernel launches");
 }
 
 int hyd_moe_mlp_w8(const hyd_moe_w8_params* p, void* stream) {

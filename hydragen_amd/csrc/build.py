@@ -14,15 +14,15 @@ from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 HERE = Path(__file__).resolve().parent
-SOURCES = ["api_core.hip", "api_attn.hip", "api_layer.hip", "api_logits.hip", "api_generate.hip", "api_kv.hip", "api_comm.hip", "api_moe.hip", "prefix_attn_w64.hip", "prefix_attn_w64_f16.hip", "suffix_attn.hip", "suffix_attn_fp8.hip", "suffix_attn_gqa.hip", "suffix_attn_gqa_fp8.hip", "suffix_attn_gqa_fp8_causal.hip", "suffix_attn_causal.hip", "draft_lookup.hip", "draft_accept.hip", "draft_accept_stop.hip", "draft_constrain.hip", "combine.hip", "rope_append.hip", "layer_ops.hip", "sample_filter.hip", "sample_penalty.hip", "sample_penalty_drafts.hip", "sample_constrain.hip", "sample_rows.hip", "token_logprob.hip", "stop_update.hip", "kv_promote.hip", "kv_gather.hip", "kv_scale.hip", "linear_w8.hip", "linear_w4.hip", "moe.hip", "moe_w8.hip", "moe_w4.hip", "moe_grouped.hip", "allreduce.hip"]
+SOURCES = ["api_core.hip", "api_attn.hip", "api_layer.hip", "api_logits.hip", "api_generate.hip", "api_kv.hip", "api_comm.hip", "api_moe.hip", "prefix_attn_w64.hip", "prefix_attn_w64_f16.hip", "suffix_attn.hip", "suffix_attn_fp8.hip", "suffix_attn_gqa.hip", "suffix_attn_gqa_fp8.hip", "suffix_attn_gqa_fp8_causal.hip", "suffix_attn_causal.hip", "draft_lookup.hip", "draft_accept.hip", "draft_accept_stop.hip", "draft_constrain.hip", "combine.hip", "rope_append.hip", "layer_ops.hip", "sample_filter.hip", "sample_penalty.hip", "sample_penalty_drafts.hip", "sample_constrain.hip", "sample_rows.hip", "token_logprob.hip", "stop_update.hip", "kv_promote.hip", "kv_gather.hip", "kv_scale.hip", "linear_w8.hip", "linear_w4.hip", "moe.hip", "moe_w8.hip", "moe_w4.hip", "moe_grouped.hip", "moe_grouped_w8.hip", "allreduce.hip"]
 HEADERS = sorted(h.name for h in HERE.glob("*.h")) + ["../../include/hydragen_hip.h"]
 LIB = HERE / "libhydragen_hip.so"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Werror", "-Wno-unused-function"]
 # linear_w4.hip is compiled without the packed fp32 instructions (v_pk_{add,mul,fma}_f32): its fp32 arithmetic is the epilogue's scale
-# products only, and new code keeps to the scalar forms (moe.hip, moe_w8.hip, moe_w4.hip, moe_grouped.hip: the epilogues' SwiGLU, scales, route weights and slot sums)
+# products only, and new code keeps to the scalar forms (moe.hip, moe_w8.hip, moe_w4.hip, moe_grouped.hip, moe_grouped_w8.hip: the epilogues' SwiGLU, scales, route weights and slot sums)
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_FLAGS = {"linear_w4.hip": _NO_PACKED_FP32, "moe.hip": _NO_PACKED_FP32, "moe_w8.hip": _NO_PACKED_FP32, "moe_w4.hip": _NO_PACKED_FP32, "moe_grouped.hip": _NO_PACKED_FP32}
+EXTRA_FLAGS = {"linear_w4.hip": _NO_PACKED_FP32, "moe.hip": _NO_PACKED_FP32, "moe_w8.hip": _NO_PACKED_FP32, "moe_w4.hip": _NO_PACKED_FP32, "moe_grouped.hip": _NO_PACKED_FP32, "moe_grouped_w8.hip": _NO_PACKED_FP32}
 if os.environ.get("HYD_ABLATION_BUILD"):  # development only: A/B switches, timing-ablation kernel variants
     FLAGS.append("-DHYD_ABLATION_BUILD")
 

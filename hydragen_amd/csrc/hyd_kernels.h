@@ -407,9 +407,17 @@ struct MoeGroupedArgs {  // moe_grouped.hip: route -> count -> place -> tiled ga
     int32_t ntiles, bm;  // set by the launcher: ceil(T k / bm) + min(E, T k) entries of bm sorted slots
 };
 
+struct MoeGroupedW8Args {  // moe_grouped_w8.hip: the grouped call on e4m3fn codes (g.c.gate_up / g.c.down = the code bytes), MoeW8Args' scales
+    MoeGroupedArgs g;
+    const float* gate_up_scale;  // [E, 2 I]
+    const float* down_scale;     // [E, H]
+};
+
 // launchers (defined next to the kernels); return hipError_t as int
 MoeGroupedLayout moe_grouped_layout(int T, int E, int k, int H, int I);          // moe_grouped.hip, shapes only
 int launch_moe_mlp_grouped(const MoeGroupedArgs& a, int dtype, hipStream_t s);  // moe_grouped.hip: the seven launches of one routed MLP
+int launch_moe_grouped_sort(MoeGroupedArgs& a, int dtype, hipStream_t s);       // moe_grouped.hip: the first three of them (checks the ranges, sets a.bm and a.ntiles)
+int launch_moe_mlp_grouped_w8(const MoeGroupedW8Args& a, int dtype, hipStream_t s);  // moe_grouped_w8.hip: the same seven launches on fp8 expert weights
 int launch_moe_route(const MoeArgs& a, int dtype, hipStream_t s);               // moe.hip: the route launch alone, any T
 MoeLayout moe_layout(int T, int E, int k, int H, int I);    // moe.hip, shapes only
 int launch_moe_mlp(const MoeArgs& a, int dtype, hipStream_t s);  // moe.hip: the five launches of one routed MLP

@@ -23,6 +23,7 @@
 // the wave of that half ends with g and u of the same (slot, channel) in the same lane.
 //   Rows past a tile's count are clamped duplicates of its last row and are never stored; channels past I / H are clamped duplicates
 // whose waves skip their MFMAs and store nothing; a 16-byte chunk at or past K is zeros in both operands and never loaded.
+//   launch_moe_grouped_sort makes the route, count and place launches alone: moe_grouped_w8.hip puts its own products behind them.
 #include "mma_tiles.h"  // kThreads, kWaves, mfma16
 
 namespace hyd {
@@ -250,8 +251,8 @@ static int launch_products(const MoeGroupedArgs& a, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
-int launch_moe_mlp_grouped(const MoeGroupedArgs& args, int dtype, hipStream_t s) {
-    MoeGroupedArgs a = args;
+// route, count and place: the launches in front of the products, shared with moe_grouped_w8.hip; sets the tile height and the table's size
+int launch_moe_grouped_sort(MoeGroupedArgs& a, int dtype, hipStream_t s) {
     if (!grouped_shapes_ok(a.c.T, a.c.E, a.c.k, a.c.H, a.c.I)) return (int)hipErrorInvalidValue;
     const int n = a.c.T * a.c.k;
     a.bm = grouped_bm(a.c.T, a.c.E, a.c.k);
@@ -261,7 +262,13 @@ int launch_moe_mlp_grouped(const MoeGroupedArgs& args, int dtype, hipStream_t s)
     hipLaunchKernelGGL(moe_grouped_count_kernel, dim3((unsigned)a.c.E), dim3(64), 0, s, a);
     if ((rc = (int)hipGetLastError())) return rc;
     hipLaunchKernelGGL(moe_grouped_place_kernel, dim3((unsigned)a.c.E), dim3(64), 0, s, a);
-    if ((rc = (int)hipGetLastError())) return rc;
+    return (int)hipGetLastError();
+}
+
+int launch_moe_mlp_grouped(const MoeGroupedArgs& args, int dtype, hipStream_t s) {
+    MoeGroupedArgs a = args;
+    int rc = launch_moe_grouped_sort(a, dtype, s);
+    if (rc) return rc;
     if (dtype == HYD_F16)
         rc = a.bm == 128 ? launch_products<F16, 128>(a, s) : launch_products<F16, 64>(a, s);
     else

@@ -19,6 +19,11 @@ DEFINED as `moe_reference` on the float64 dequantized weights (code * scale, exa
 its bound: the codes are exact 16-bit values and the scales powers of two applied to the fp32 sums, so a kernel differs from the
 16-bit kernels on the dequantized weights in accumulation order only.  The router stays a 16-bit F.linear.
 
+Large inputs with fp8 experts (`moe_rows_grouped_w8`, hyd_moe_mlp_grouped_w8, csrc/moe_grouped_w8.hip): the grouped call on the same
+four tensors -- its sort, its workspace and its range of rows, the weights carried as codes through LDS and widened in registers; the
+fp8 definition and bound.  `moe_mlp(..., grouped=True)` reaches it, and `MoeMLP` with Fp8Experts from MOE_GROUPED_W8_MIN_ROWS rows
+on (profiles/moe.md has the measurement that sets it).  4-bit experts have no grouped kernel.
+
 4-bit experts (`quantize_experts_fp4`, hyd_moe_mlp_w4, csrc/moe_w4.hip, `Fp4Experts`): weight_quant.quantize_weight_fp4's format on
 the same view -- packed e2m1 codes [E, N, K / 2], a shift 0..12 per group of 32 k [E, N, K / 32], a power-of-two scale per expert
 and output channel [E, N].  The 4-bit MLP is DEFINED the same way, as `moe_reference` on e2m1(code) * 2^-shift * scale in float64
@@ -188,6 +193,9 @@ def dequantize_experts_fp4(gate_up4: Tensor, gate_up_shift: Tensor, gate_up_scal
 MOE_MAX_ROWS = 128  # HYD_MOE_MAX_ROWS: rows per hyd_moe_mlp call; moe_mlp chunks longer inputs (the MLP is row-independent: exact)
 MOE_GROUPED_MAX_ROWS = 2048  # HYD_MOE_GROUPED_MAX_ROWS: rows per hyd_moe_mlp_grouped call (csrc/moe_grouped.hip)
 MOE_GROUPED_MIN_ROWS = 512  # moe_mlp: 16-bit experts take the grouped call from this many rows on (profiles/moe.md has the measurement)
+# MoeMLP: Fp8Experts take hyd_moe_mlp_grouped_w8 from this many rows on (None: never).  256 is the smallest size measured: 2.1 - 2.5 x the
+# chunked fp8 route there on both layers of profiles/moe.md, spreads under 1 %; smaller calls were not measured
+MOE_GROUPED_W8_MIN_ROWS: Optional[int] = 256
 
 _MOE_FIELDS = [
     ("x", C.c_void_p), ("logits", C.c_void_p), ("gate_up", C.c_void_p), ("down", C.c_void_p), ("y", C.c_void_p), ("workspace", C.c_void_p),
@@ -223,12 +231,15 @@ def _workspace(device, T, E, k, H, I, dtype, grouped=False) -> Tensor:
 
 
 def _moe_call(x, logits, gate_up, down, scales, k, renormalize, out, ids_out, weights_out, workspace, grouped=False) -> Tensor:
-    """moe_rows (scales None: 16-bit weights of x's dtype), moe_rows_grouped (the same with `grouped`: hyd_moe_mlp_grouped), moe_rows_w8 (scales = (gate_up_scale, down_scale): e4m3fn codes) and
+    """moe_rows (scales None: 16-bit weights of x's dtype), moe_rows_grouped (the same with `grouped`: hyd_moe_mlp_grouped), moe_rows_w8 (scales = (gate_up_scale, down_scale): e4m3fn codes),
+    moe_rows_grouped_w8 (the same with `grouped`: hyd_moe_mlp_grouped_w8) and
     moe_rows_w4 (scales = (gate_up_scale, down_scale, gate_up_shift, down_shift): packed e2m1 codes, two k per byte)."""
     from .flash import _require_gpu, _stream
 
     _require_gpu(x, logits, gate_up, down, out, ids_out, weights_out, workspace, *(scales or ()))
     fp4 = scales is not None and len(scales) == 4
+    if fp4 and grouped:
+        raise ValueError("4-bit experts have no grouped call")
     (T, H), E, I, per = x.shape, gate_up.shape[0], down.shape[2] * (2 if fp4 else 1), 2 if fp4 else 1  # per: k per element of the weights
     if scales is None:
         if not (x.dtype == logits.dtype == gate_up.dtype == down.dtype == out.dtype) or x.dtype not in (torch.float16, torch.bfloat16):
@@ -267,7 +278,7 @@ def _moe_call(x, logits, gate_up, down, scales, k, renormalize, out, ids_out, we
         p.gate_up_shift, p.down_shift = scales[2].data_ptr(), scales[3].data_ptr()
         _lib.check(_lib.load().hyd_moe_mlp_w4(C.byref(p), _stream()))
     else:
-        _lib.check(_lib.load().hyd_moe_mlp_w8(C.byref(p), _stream()))
+        _lib.check((_lib.load().hyd_moe_mlp_grouped_w8 if grouped else _lib.load().hyd_moe_mlp_w8)(C.byref(p), _stream()))
     return out
 
 
@@ -295,6 +306,14 @@ def moe_rows_w8(x: Tensor, logits: Tensor, gate_up8: Tensor, gate_up_scale: Tens
     return _moe_call(x, logits, gate_up8, down8, (gate_up_scale, down_scale), k, renormalize, out, ids_out, weights_out, workspace)
 
 
+def moe_rows_grouped_w8(x: Tensor, logits: Tensor, gate_up8: Tensor, gate_up_scale: Tensor, down8: Tensor, down_scale: Tensor, k: int, renormalize: bool,
+                        out: Tensor, ids_out: Optional[Tensor] = None, weights_out: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
+    """One hyd_moe_mlp_grouped_w8 call on the current stream: moe_rows_grouped (T <= MOE_GROUPED_MAX_ROWS rows, every chosen expert
+    read once) on quantize_experts' four tensors (contiguous).  The same routing and roundings as moe_rows_w8; the fp32 sums inside
+    the two products are added in another order.  The workspace is moe_rows_grouped's, cached under the same key."""
+    return _moe_call(x, logits, gate_up8, down8, (gate_up_scale, down_scale), k, renormalize, out, ids_out, weights_out, workspace, grouped=True)
+
+
 def moe_rows_w4(x: Tensor, logits: Tensor, gate_up4: Tensor, gate_up_shift: Tensor, gate_up_scale: Tensor, down4: Tensor, down_shift: Tensor,
                 down_scale: Tensor, k: int, renormalize: bool, out: Tensor, ids_out: Optional[Tensor] = None, weights_out: Optional[Tensor] = None,
                 workspace: Optional[Tensor] = None) -> Tensor:
@@ -305,14 +324,17 @@ def moe_rows_w4(x: Tensor, logits: Tensor, gate_up4: Tensor, gate_up_shift: Tens
 
 def moe_mlp(x: Tensor, router_w: Tensor, gate_up: Tensor, down: Tensor, k: int, renormalize: bool, *, return_routing: bool = False,
             gate_up_scale: Optional[Tensor] = None, down_scale: Optional[Tensor] = None, gate_up_shift: Optional[Tensor] = None,
-            down_shift: Optional[Tensor] = None):
+            down_shift: Optional[Tensor] = None, grouped: Optional[bool] = None):
     """The routed MLP of x [..., H]: logits = F.linear(x, router_w) in the 16-bit dtype, then one hyd_moe_mlp call per chunk of
     MOE_MAX_ROWS rows (rows are independent, so chunking is exact); 16-bit experts on MOE_GROUPED_MIN_ROWS rows and more take
     hyd_moe_mlp_grouped per chunk of MOE_GROUPED_MAX_ROWS rows instead (each expert read once per chunk).  The workspace is cached per (device, shapes): a captured graph
     replays without allocating it.  CPU tensors run the definition, rounded once to the dtype.  `return_routing`: (y, ids [T, k]
     int32, weights [T, k] float32).  With `gate_up_scale` and `down_scale` (both or neither), gate_up and down are quantize_experts'
     e4m3fn codes: hyd_moe_mlp_w8 per chunk, and on the CPU the definition on the dequantized weights.  With `gate_up_shift` and
-    `down_shift` as well (both, and only with the scales), they are quantize_experts_fp4's packed e2m1 codes: hyd_moe_mlp_w4."""
+    `down_shift` as well (both, and only with the scales), they are quantize_experts_fp4's packed e2m1 codes: hyd_moe_mlp_w4.
+    `grouped`: None is the rule above (fp8 and 4-bit experts take the 128-row calls at every size); True takes the grouped call per
+    chunk of MOE_GROUPED_MAX_ROWS rows at any T -- hyd_moe_mlp_grouped, or hyd_moe_mlp_grouped_w8 for fp8 experts; 4-bit experts
+    have none: ValueError -- and False the 128-row calls at any T.  On the CPU the keyword changes nothing."""
     if (gate_up_scale is None) != (down_scale is None):
         raise ValueError("gate_up_scale and down_scale come together")
     if (gate_up_shift is None) != (down_shift is None) or (gate_up_shift is not None and gate_up_scale is None):
@@ -334,7 +356,10 @@ def moe_mlp(x: Tensor, router_w: Tensor, gate_up: Tensor, down: Tensor, k: int, 
     y = torch.empty_like(x2)
     ids = torch.empty((T, k), dtype=torch.int32, device=x.device) if return_routing else None
     w = torch.empty((T, k), dtype=torch.float32, device=x.device) if return_routing else None
-    grouped = scales is None and T >= MOE_GROUPED_MIN_ROWS
+    if grouped and gate_up_shift is not None:
+        raise ValueError("grouped=True: 4-bit experts have no grouped call")
+    if grouped is None:
+        grouped = scales is None and T >= MOE_GROUPED_MIN_ROWS
     step = MOE_GROUPED_MAX_ROWS if grouped else MOE_MAX_ROWS
     for r in range(0, T, step):
         rows = slice(r, min(T, r + step))
@@ -436,4 +461,6 @@ class MoeMLP(nn.Module):
         scales = dict(gate_up_scale=e.gate_up_proj_scale, down_scale=e.down_proj_scale) if isinstance(e, (Fp8Experts, Fp4Experts)) else {}
         if isinstance(e, Fp4Experts):
             scales.update(gate_up_shift=e.gate_up_proj_shift, down_shift=e.down_proj_shift)
-        return moe_mlp(x, self.gate.weight, e.gate_up_proj, e.down_proj, self.top_k, self.renormalize, **scales)
+        rows = x.numel() // x.shape[-1]
+        grouped = True if isinstance(e, Fp8Experts) and MOE_GROUPED_W8_MIN_ROWS is not None and rows >= MOE_GROUPED_W8_MIN_ROWS else None
+        return moe_mlp(x, self.gate.weight, e.gate_up_proj, e.down_proj, self.top_k, self.renormalize, grouped=grouped, **scales)

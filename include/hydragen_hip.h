@@ -1312,6 +1312,19 @@ HYD_API int hyd_moe_mlp_w4(const hyd_moe_w4_params* p, void* stream);
 HYD_API size_t hyd_moe_grouped_workspace_bytes(int32_t T, int32_t E, int32_t k, int32_t H, int32_t I, int32_t dtype);
 HYD_API int hyd_moe_mlp_grouped(const hyd_moe_params* p, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The large call on fp8 expert weights (csrc/moe_grouped_w8.hip): hyd_moe_w8_params with its meaning in hyd_moe_mlp_w8 (e4m3fn
+ * codes, one power-of-two fp32 scale per expert and output channel applied to the fp32 sums; codes 0x7f / 0xff are outside the
+ * format's use here), in hyd_moe_mlp_grouped's range 1 <= T <= HYD_MOE_GROUPED_MAX_ROWS and with ITS workspace
+ * (hyd_moe_grouped_workspace_bytes is the query) and its seven launches: the same route, sort and combine kernels, and two tiled
+ * products of this file's own that carry the weights as codes through LDS and widen them in registers.  The result is
+ * hyd_moe_mlp_grouped's on the dequantized weights (code * scale) up to the order of fp32 additions.  Capture-safe; nothing is read
+ * back or allocated, no float atomics, two calls give the same bits.  The error codes and messages are hyd_moe_mlp_grouped's and
+ * hyd_moe_mlp_w8's (the scale pointers), with this call's name in the workspace and launch messages.  A new symbol and no new
+ * struct: the version stays 500.
+ * ------------------------------------------------------------------------------------------ */
+HYD_API int hyd_moe_mlp_grouped_w8(const hyd_moe_w8_params* p, void* stream);
+
 HYD_API int hyd_version(void);
 HYD_API const char* hyd_last_error_string(void);
 

@@ -6,6 +6,7 @@ time to stream the weights it has to read and against transformers' own block.  
     python tools/moe_bench.py --experts fp8 --out profiles/moe.md     (appends the fp8 section to the file)
     python tools/moe_bench.py --experts fp4 --rows 1,8,16,32,64,128 --out profiles/moe.md     (appends the 4-bit section)
     python tools/moe_bench.py --experts grouped --out profiles/moe.md     (appends the large-call section)
+    python tools/moe_bench.py --experts grouped_fp8 --out profiles/moe.md     (appends the large-call section for fp8 experts)
 
 Per shape -- a Mixtral-8x7B layer (E 8, k 2, H 4096, I 14336) and a Qwen3-30B-A3B layer (E 128, k 8, H 2048, I 768), bf16, random
 weights -- and per row count T: a ring of distinct layers whose ACTIVATED experts together exceed the 256 MB Infinity Cache, so every
@@ -20,7 +21,10 @@ captured, replayed alternately round by round in this one process; the fp8 floor
 way; the 4-bit floor is the codes, shifts and scales of the activated experts (4.25 bits per weight and 4 bytes per channel).
 --experts grouped: large calls (default rows 256,512,1024,2048) -- the grouped call (moe.moe_rows_grouped, hyd_moe_mlp_grouped) beside
 the chunked route (moe.moe_rows per 128 rows), both behind the same router GEMM, alternated the same way; two floors: the activated
-experts' bytes at 8 TB/s and the two products' FLOPs at the dense bf16 peak."""
+experts' bytes at 8 TB/s and the two products' FLOPs at the dense bf16 peak.
+--experts grouped_fp8: the same rows and rings with their experts quantized -- the chunked fp8 route (moe.moe_rows_w8 per 128 rows), the
+grouped fp8 call (moe.moe_rows_grouped_w8, hyd_moe_mlp_grouped_w8) and the grouped 16-bit call on the originals, alternated the same
+way; the byte floor is the activated experts' code bytes."""
 from __future__ import annotations
 
 import argparse
@@ -263,19 +267,67 @@ def grouped_table(name, E, k, H, I, rows, rounds, out):
     out("")
 
 
+def grouped_fp8_table(name, E, k, H, I, rows, rounds, out):
+    from hydragen_amd import moe
+
+    expert_bytes = 3 * H * I  # codes
+    n = max(2, RING_BYTES // (min(E, k * min(rows)) * expert_bytes) + 2)  # the fp8 ring, too, exceeds the Infinity Cache
+    gen = torch.Generator(device=DEV).manual_seed(E + H)
+    mk = lambda *s, sd: torch.randn(s, device=DEV, dtype=torch.bfloat16, generator=gen) * sd  # noqa: E731
+    layers = [(mk(E, H, sd=0.05), mk(E, 2 * I, H, sd=0.02), mk(E, H, I, sd=0.02)) for _ in range(n)]
+    quant = [moe.quantize_experts(gate_up, down) for _, gate_up, down in layers]
+    out(f"### {name}: E = {E}, k = {k}, H = {H}, I = {I} ({n} layers per ring, {E * expert_bytes / 2**20:.0f} MiB of fp8 experts per layer)\n")
+    out("| T | chunked fp8 us (min .. max) | grouped fp8 us (min .. max) | grouped 16-bit us (min .. max) | chunked fp8 / grouped fp8 | grouped 16-bit / grouped fp8 | "
+        "distinct experts hit | fp8 byte floor us (8 TB/s) | FLOP floor us (2.5 PFLOP/s) | grouped fp8 / FLOP floor |")
+    out("|---|---|---|---|---|---|---|---|---|---|")
+    for T in rows:
+        x = torch.randn((T, H), device=DEV, dtype=torch.bfloat16, generator=gen)
+        y = torch.empty_like(x)
+        hit = statistics.mean(int(moe.moe_mlp(x, *l, k, True, return_routing=True)[1].unique().numel()) for l in layers)
+
+        def run_chunked8():
+            for (router, _, _), q in zip(layers, quant):
+                logits = torch.nn.functional.linear(x, router)
+                for r in range(0, T, moe.MOE_MAX_ROWS):
+                    moe.moe_rows_w8(x[r:r + moe.MOE_MAX_ROWS], logits[r:r + moe.MOE_MAX_ROWS], *q, k, True, y[r:r + moe.MOE_MAX_ROWS])
+
+        def run_grouped8():
+            for (router, _, _), q in zip(layers, quant):
+                moe.moe_rows_grouped_w8(x, torch.nn.functional.linear(x, router), *q, k, True, y)
+
+        def run_grouped16():
+            for router, gate_up, down in layers:
+                moe.moe_rows_grouped(x, torch.nn.functional.linear(x, router), gate_up, down, k, True, y)
+
+        graphs = [graph_of(run_chunked8), graph_of(run_grouped8), graph_of(run_grouped16)]
+        ts = ([], [], [])
+        for r in range(rounds + 1):
+            for i, g in enumerate(graphs):
+                t = replay_us(g, n, 1 if r == 0 else 10)
+                if r:
+                    ts[i].append(t)
+        usc, us8, us16 = (statistics.median(t) for t in ts)
+        floor_b, floor_f = hit * expert_bytes / (HBM_TBS * 1e6), 2 * T * k * 3 * H * I / (BF16_PFLOPS * 1e9)
+        spread = lambda i: f"({min(ts[i]):.1f} .. {max(ts[i]):.1f})"  # noqa: E731
+        out(f"| {T} | {usc:.1f} {spread(0)} | {us8:.1f} {spread(1)} | {us16:.1f} {spread(2)} | {usc / us8:.2f} | {us16 / us8:.2f} | {hit:.1f} | {floor_b:.1f} | "
+            f"{floor_f:.1f} | {us8 / floor_f:.2f} |")
+        del graphs
+    out("")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
-    ap.add_argument("--rows", default=None, help="default 1,8,32,128; --experts grouped: 256,512,1024,2048")
+    ap.add_argument("--rows", default=None, help="default 1,8,32,128; --experts grouped / grouped_fp8: 256,512,1024,2048")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--skip-eager", action="store_true")
-    ap.add_argument("--experts", choices=["16bit", "fp8", "fp4", "grouped"], default="16bit")
+    ap.add_argument("--experts", choices=["16bit", "fp8", "fp4", "grouped", "grouped_fp8"], default="16bit")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("moe_bench.py measures on the GPU: no device found")
-    fp8, fp4, grouped = args.experts == "fp8", args.experts == "fp4", args.experts == "grouped"
-    args.rows = args.rows or ("256,512,1024,2048" if grouped else "1,8,32,128")
-    lines = Path(args.out).read_text().rstrip("\n").split("\n") + [""] if (fp8 or fp4 or grouped) and args.out and Path(args.out).exists() else []
+    fp8, fp4, grouped, grouped8 = args.experts == "fp8", args.experts == "fp4", args.experts == "grouped", args.experts == "grouped_fp8"
+    args.rows = args.rows or ("256,512,1024,2048" if grouped or grouped8 else "1,8,32,128")
+    lines = Path(args.out).read_text().rstrip("\n").split("\n") + [""] if (fp8 or fp4 or grouped or grouped8) and args.out and Path(args.out).exists() else []
 
     def out(s):
         lines.append(s)
@@ -283,6 +335,15 @@ def main():
         if args.out:
             Path(args.out).write_text("\n".join(lines) + "\n")
 
+    if grouped8:
+        out("## Large calls on fp8 experts: the grouped call (`hyd_moe_mlp_grouped_w8`) against the chunked fp8 route and the 16-bit grouped call\n")
+        out("`moe_rows_w8` per 128 rows, `moe_rows_grouped_w8` once, and `moe_rows_grouped` once on the 16-bit originals, each behind the router GEMM, all "
+            "captured and replayed alternately in one process on a ring of distinct layers, bf16 activations; median (min .. max) over the rounds, per layer.  "
+            "Floors: the activated experts' code bytes at 8 TB/s, and 2 T k 3 H I FLOPs at the dense bf16 peak.\n")
+        for name, _, E, k, H, I in SHAPES:
+            grouped_fp8_table(name, E, k, H, I, [int(r) for r in args.rows.split(",")], args.rounds, out)
+            torch.cuda.empty_cache()
+        return
     if grouped:
         out("## Large calls: the grouped call (`hyd_moe_mlp_grouped`) against the chunked route of the same build\n")
         out("`moe_rows_grouped` once and `moe_rows` per 128 rows, each behind the router GEMM, both captured and replayed alternately in one process on a "
